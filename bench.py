@@ -104,6 +104,7 @@ PMC_FILES_BY_SHAPE = {(10_000_000, 2_500_000, 1e-4): {6: ((("r05_tall_slice_pmc_
 # against 9.57 with 8 on one box (profiles/r05_c4_chunks_16_vs_8.txt).
 CHUNK_ENTRIES = 1.3e9
 UNCHUNKED_ENTRIES = 2.6e9   # a row block up to this size is an ordinary DeviceMatrix (config 3, the 1/8 slice = one of 8 ranks of config 4)
+DUMP_MAX_VALUES = 4_000_000   # --dump-outputs: float64 values written at most (32 MB)
 
 
 def parse():
@@ -137,7 +138,12 @@ def parse():
                         "as keep a chunk below 2.6e9 stored entries (1 = an ordinary DeviceMatrix with its CSR)")
     p.add_argument("--format", type=int, default=0, choices=[0, 1, 2],
                    help="slp_matrix_set_format policy of the timed run: 0 best available, 1 no value dictionary, 2 CSR kernels")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the solution x they left as DIR/x.npy (float64; above "
+                        f"{DUMP_MAX_VALUES} variables a fixed, seeded sample of x, see dump_outputs)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
     args.default_workload = args.config is None and args.n is None and args.m is None and args.density is None
     if args.method is None:
         args.method = "admm_blocks" if args.config == "c5" else "admm"
@@ -400,6 +406,17 @@ def cpu_baseline_blocks(args, rows_per_block, cg_steps_full):
     }
 
 
+def dump_outputs(path, x):
+    """``--dump-outputs``: the solution over the LP's n variables that the timed steps left -- what ``SparseLP.solve`` hands its
+    caller -- as ``path/x.npy`` (float64).  Above DUMP_MAX_VALUES variables the file holds ``x[idx]`` instead, ``idx`` the sorted
+    DUMP_MAX_VALUES indices ``np.random.default_rng(0).choice(n, DUMP_MAX_VALUES, replace=False)`` draws: the same entries for
+    every run with the same n, so two builds can be compared value for value."""
+    os.makedirs(path, exist_ok=True)
+    if x.size > DUMP_MAX_VALUES:
+        x = x[np.sort(np.random.default_rng(0).choice(x.size, DUMP_MAX_VALUES, replace=False))]
+    np.save(os.path.join(path, "x.npy"), np.ascontiguousarray(x, dtype=np.float64))
+
+
 def timed_steps(lib, solver, warmup, steps):
     solver.iterate(warmup)
     _lib.check(lib.slp_comm_barrier())
@@ -564,6 +581,7 @@ def main():
             a3.n, a3.m, a3.density = CONFIGS["c3"]
             a3.chunks = 0
             a3.no_cpu_baseline = True
+            a3.dump_outputs = None   # the dump is the headline run's
             try:
                 sec = run_workload(lib, a3, rank, world, distributed)
                 out["secondary"] = {"c3": {k: sec[k] for k in ("metric", "value", "unit", "ms_per_step", "config", "roofline",
@@ -659,6 +677,8 @@ def run_workload(lib, args, rank, world, distributed):
     _lib.check(lib.slp_comm_allreduce_host(_lib.ptr(nnz), 1, 0))
     nnz_total = int(nnz[0])
     obj = solver.objective()
+    if rank == 0 and args.dump_outputs:   # (x is the same on every rank: the ranks all-reduce what updates it)
+        dump_outputs(args.dump_outputs, solver.x(args.n) if args.method == "admm" else solver.x())
 
     out = None
     if rank == 0:

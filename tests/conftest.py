@@ -9,6 +9,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 GOLDEN = os.path.join(REPO, "tests", "golden")
+# The GPU suite never has more than six processes with the GPU open at once, its own pytest process included, so that it
+# can share a GPU node with other jobs.  The pytest process holds the GPU after its first in-process test and a launcher may
+# stand between it and the ranks: a test that starts ranks of its own on one GPU starts at most four.
+MAX_RANKS_ON_ONE_GPU = 4
 
 
 def pytest_configure(config):

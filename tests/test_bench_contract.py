@@ -7,6 +7,8 @@ import sys
 
 import pytest
 
+from conftest import MAX_RANKS_ON_ONE_GPU
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 TOP = {"metric": str, "value": float, "unit": str, "n_gpus": int, "steps": int, "warmup": int, "ms_per_step": float,
@@ -142,6 +144,58 @@ def test_live_bench_line(method):
     assert d["steps"] == 4 and d["warmup"] == 1 and d["n_gpus"] == 1
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("method", ["admm", "chambolle_pock_ppd"])
+def test_dump_outputs_holds_the_solution_of_the_timed_steps(method, tmp_path):
+    """``--dump-outputs DIR``: DIR/x.npy is the solution over the n variables that the K timed steps left, float64, the same
+    for two runs with the same arguments, and its objective is the line's ``objective_after_run``."""
+    import numpy as np
+
+    n, m, p = 20000, 40000, 0.001
+    xs = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--n", str(n), "--m", str(m), "--density", str(p),
+                            "--steps", "3", "--warmup", "1", "--method", method, "--no-cpu-baseline", "--no-general",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=REPO)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["warmup"] == 1
+        assert sorted(os.listdir(out)) == ["x.npy"]
+        x = np.load(out / "x.npy")
+        assert x.dtype == np.float64 and x.shape == (n,) and np.all(np.isfinite(x))
+        xs.append((x, d["objective_after_run"]))
+    assert np.array_equal(xs[0][0], xs[1][0]) and xs[0][1] == xs[1][1]
+    sys.path.insert(0, REPO)
+    from pysparselp_amd.problems import random_lp_on_device
+
+    a, xf, c, lb, ub, b = random_lp_on_device(n, m, p, seed=0)
+    a.close()
+    assert float(c.dot(xs[0][0])) == xs[0][1]
+
+
+def test_dump_outputs_samples_a_large_solution_the_same_way_every_time(tmp_path):
+    """Above DUMP_MAX_VALUES variables x.npy holds a fixed sample of x: sorted indices drawn with seed 0, float64."""
+    code = ("import runpy, sys\nimport numpy as np\nb = runpy.run_path(sys.argv[1])\ncap = b['DUMP_MAX_VALUES']\n"
+            "x = np.arange(cap + 1_000_000, dtype=np.float32)\n"
+            "b['dump_outputs'](sys.argv[2] + '/a', x)\nb['dump_outputs'](sys.argv[2] + '/b', x)\n"
+            "b['dump_outputs'](sys.argv[2] + '/c', x[:1000])\n")
+    r = subprocess.run([sys.executable, "-c", code, os.path.join(REPO, "bench.py"), str(tmp_path)], capture_output=True, text=True,
+                       timeout=120, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+    import numpy as np
+
+    a, b, c = (np.load(tmp_path / k / "x.npy") for k in "abc")
+    assert a.dtype == np.float64 and a.size == 4_000_000 and a.nbytes <= 64e6
+    assert np.array_equal(a, b) and np.all(np.diff(a) > 0)          # the same sorted entries of x (here x[i] = i) each time
+    assert c.dtype == np.float64 and np.array_equal(c, np.arange(1000))   # a small x is written whole
+
+
+def test_steps_below_one_are_rejected():
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120,
+                       cwd=REPO)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+
 def _launch(nproc, extra_env, port, more=()):
     env = dict(os.environ, **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
@@ -266,13 +320,15 @@ def test_bench_block_groups_under_the_launcher_two_ranks_on_one_gpu():
 
 @pytest.mark.gpu
 @pytest.mark.timeout(1200)
-def test_bench_under_the_launcher_eight_ranks_on_one_gpu():
-    """The driver's 8-GPU launch line (`torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8`) with all eight ranks on
-    ONE device through the host transport: eight row blocks, one line from rank 0, the single-process objective."""
-    eight = _launch(8, {"SLP_DEVICE": "0", "SLP_COMM_TRANSPORT": "host", "SLP_STRIP_MIN_NNZ": "1"}, 29661)
-    check_line(eight, need_cpu_baseline=False)
-    assert eight["n_gpus"] == 8 and eight["scaling"] == "strong" and eight["config"]["collectives_per_iteration"] == 2.0
+def test_bench_under_the_launcher_four_ranks_on_one_gpu():
+    """The driver's 4-GPU launch line (`torch.distributed.run --nproc-per-node 4 ... bench.py --gpus 4`) with all four ranks on
+    ONE device through the host transport: four row blocks, one line from rank 0, the single-process objective.  (Four, not
+    eight: see conftest.MAX_RANKS_ON_ONE_GPU.)"""
+    world = MAX_RANKS_ON_ONE_GPU
+    four = _launch(world, {"SLP_DEVICE": "0", "SLP_COMM_TRANSPORT": "host", "SLP_STRIP_MIN_NNZ": "1"}, 29661)
+    check_line(four, need_cpu_baseline=False)
+    assert four["n_gpus"] == world and four["scaling"] == "strong" and four["config"]["collectives_per_iteration"] == 2.0
     one = _launch(1, {"SLP_STRIP_MIN_NNZ": "1"}, 29671)
-    assert eight["config"]["nnz"] == one["config"]["nnz"]
-    assert abs(eight["objective_after_run"] - one["objective_after_run"]) <= 1e-9 * (1 + abs(one["objective_after_run"]))
+    assert four["config"]["nnz"] == one["config"]["nnz"]
+    assert abs(four["objective_after_run"] - one["objective_after_run"]) <= 1e-9 * (1 + abs(one["objective_after_run"]))
 

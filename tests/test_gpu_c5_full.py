@@ -11,8 +11,9 @@ Full size (needs ~295 GB of free device memory; skips with the reason below that
     conjugate-gradient bar (in this dual form that is the constraint residual ``A z - z_s`` of the projected point);
   * two runs from the same start bit-identical (x and CG step counts).
 Reduced shape (8 blocks of 6000 rows x 2e5 variables, tall cells in both orientations), the partition the driver's runs use:
-  * 8 blocks on 1 rank = 2 ranks x 4 blocks = 8 ranks x 1 block through the host transport (asynchronous form where a rank
-    holds several blocks): replicas bit-identical, x equal to 1e-9, G all-reduces per iteration;
+  * 8 blocks on 1 rank = 2 ranks x 4 blocks = 4 ranks x 2 blocks through the host transport (asynchronous form where a rank
+    holds several blocks; four ranks at most: conftest.MAX_RANKS_ON_ONE_GPU): replicas bit-identical, x equal to 1e-9,
+    G all-reduces per iteration;
   * the one-rank group against the oracle's matrix-free form (``oracle.lp_admm_blocks_cg``, pinned against the reference's LU
     iterates in tests/test_admm_blocks.py) to 1e-9.
 -m gpu."""
@@ -25,6 +26,7 @@ import numpy as np
 import pytest
 import scipy.sparse
 
+from conftest import MAX_RANKS_ON_ONE_GPU
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
@@ -129,7 +131,7 @@ def test_block_solver_properties_on_the_whole_lp_not_an_oracle_comparison(c5):
 RN, RROWS, RP, RSEED, RIT = 200_000, 6000, 1.5e-4, 5, 6
 
 
-def _rank(rank, world, port, q):
+def _rank(rank, world, port, q, blocks=G):
     try:
         sys.path.insert(0, REPO)
         os.environ.update({"RANK": str(rank), "WORLD_SIZE": str(world), "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port),
@@ -141,9 +143,9 @@ def _rank(rank, world, port, q):
         lib = _lib.lib(0)
         if world > 1:
             init_comm_from_env(rank, world)
-        m = G * RROWS
+        m = blocks * RROWS
         r0, rows = row_block(m, world, rank)
-        per = G // world
+        per = blocks // world
         grp, xf, c, lb, ub, b = DeviceBlocksGroup.from_generator(RN, m, RP, RSEED, [RROWS * g for g in range(per + 1)], row_offset=r0)
         assert all(mat.spmv_kernel(False) == 6 and mat.spmv_kernel(True) == 6 for mat in grp._mats)   # tall cells
         c0 = int(lib.slp_comm_collectives())
@@ -164,13 +166,13 @@ def _rank(rank, world, port, q):
         q.put((rank, {"error": traceback.format_exc() + repr(e)}))
 
 
-def _run(world):
+def _run(world, blocks=G):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_rank, args=(r, world, port, q)) for r in range(world)]
+    procs = [ctx.Process(target=_rank, args=(r, world, port, q, blocks)) for r in range(world)]
     for pr in procs:
         pr.start()
     res = {}
@@ -185,14 +187,14 @@ def _run(world):
 
 
 @pytest.mark.timeout(2400)
-def test_eight_blocks_on_one_rank_equal_two_by_four_and_eight_by_one():
+def test_eight_blocks_on_one_rank_equal_two_by_four_and_four_by_two():
     from pysparselp_amd.device import DeviceMatrix
 
     one = _run(1)[0]
     assert one["collectives"] == 0 and np.all(np.isfinite(one["x"]))
     for res, rhs in one["residuals"]:
         assert rhs > 0 and res <= 1e-12 * rhs
-    for world in (2, 8):
+    for world in (2, MAX_RANKS_ON_ONE_GPU):
         got = _run(world)
         per = G // world
         for r in range(world):
@@ -217,6 +219,22 @@ def test_eight_blocks_on_one_rank_equal_two_by_four_and_eight_by_one():
     err = float(np.max(np.abs(one["x"] - want) / (1 + np.abs(want))))
     assert err <= 1e-9, err
 
+
+@pytest.mark.timeout(1200)
+def test_one_block_per_rank_equals_the_blocks_on_one_rank():
+    """A rank holding ONE block of a distributed group (what ``bench.py --config c5 --gpus 8`` runs) takes the group's other
+    branch: no overlapped all-reduces, one all-reduce of the block's summand after its projection (csrc/slp_blocks.hip
+    slp_blocks_group_iterate, ``overlap = distributed && count > 1``).  Four blocks on one rank = four ranks x one block."""
+    blocks = MAX_RANKS_ON_ONE_GPU
+    one = _run(1, blocks)[0]
+    got = _run(blocks, blocks)
+    for r in range(blocks):
+        assert got[r]["collectives"] == RIT                               # one all-reduce of n doubles per iteration
+        assert got[r]["timed"][0] == RIT and got[r]["timed"][1] > 0 and got[r]["timed"][2] == RIT * 8.0 * RN
+        assert got[r]["timed"][4] == 0                                    # nothing on the second stream (no overlap)
+        assert np.array_equal(got[r]["x"], got[0]["x"]), r
+    err = float(np.max(np.abs(got[0]["x"] - one["x"]) / (1 + np.abs(one["x"]))))
+    assert err <= 1e-9, err
 
 def test_blocks_side_by_side_on_streams_change_nothing():
     """Round 6: with SLP_BLOCKS_STREAMS=1 the blocks' projections run side by side from a group's second iteration
