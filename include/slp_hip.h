@@ -77,9 +77,16 @@ int slp_matrix_spmv_t(slp_matrix *a, const double *y, double *out, int order);
 /* y = |A|^p x (transposed = 0) or |A|^p^T x (transposed = 1), entry-wise power: the products whose results with a vector
  * of ones are the sums behind Chambolle-Pock's diagonal preconditioners (ChambollePockPPD.py:122-179: np.abs(A) ** p,
  * column sums in row order, row sums in storage order).  Runs on the strip / tall-cell copy of that orientation with its
- * value table raised to the power (what slp_cp_create_on does at set-up); an error when the copy cannot (no copy, or fp64
- * wide strips).  A checker's entry point: lets the set-up sums of a matrix without CSR be verified slice by slice. */
+ * value table raised to the power, or with |v|^p formed on the fly for fp64 entries (what slp_cp_create_on does at set-up);
+ * an error when there is no such copy.  A checker's entry point: lets the set-up sums of a matrix without CSR be verified
+ * slice by slice. */
 int slp_matrix_spmv_abs_pow(slp_matrix *a, int transposed, double p, const double *x, double *y);
+/* y0 = A x0 and y1 = A x1 (transposed = 0), or A^T x0 and A^T x1 (transposed = 1), in ONE pass over the strip / wide-strip /
+ * tall-cell copy of that orientation when there is one (two products otherwise).  It stands for two csr_matvec calls of
+ * the matrix-free ADMM's conjugate-gradient products that the solver runs as one pass (ADMM.py:262 for two vectors:
+ * cg_rows2; ADMM.py:148 for two vectors: cg_cols2).  Each output is bit for bit the single-vector slp_matrix_spmv /
+ * slp_matrix_spmv_t in SLP_ORDER_AUTO on the same copy.  A checker's entry point for the two-vector kernels. */
+int slp_matrix_spmv2(slp_matrix *a, int transposed, const double *x0, const double *x1, double *y0, double *y1);
 /* Copies of the device arrays: CSR (transposed = 0) or the device-built
  * transposed CSR, i.e. CSC of A (transposed = 1).  Any pointer may be NULL. */
 int slp_matrix_download(slp_matrix *a, int transposed, int64_t *indptr,

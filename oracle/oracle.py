@@ -241,6 +241,26 @@ def rmatvec(a, y):
     return out
 
 
+def row_error_bound(a, x, k_extra=2):
+    """Per-row bound on ``|dev_i - oracle_i|`` for two evaluations of ``(a x)_i`` that sum the same products in ANY order:
+    ``2 gamma(k_i + k_extra) (|a| |x|)_i``, with ``k_i`` the stored entries of row ``i``, ``gamma(k) = k u / (1 - k u)`` and
+    ``u = 2^-53`` (the standard worst-case bound of a length-k dot product, Higham, Accuracy and Stability of Numerical
+    Algorithms, 2nd ed., eq. 3.5), once for each side.  ``k_extra`` leaves room for a rounding per term before the sum (an ulp
+    of ``pow`` in ``|v| ** p``).  Rows without entries get bound 0: both sides must be +0.0."""
+    a = as_csr(a)
+    x = _f64(x)
+    assert x.size == a.shape[1]
+    k = np.diff(a.indptr).astype(np.float64)
+    u = 2.0 ** -53
+    ku = (k + k_extra) * u
+    gamma = ku / (1.0 - ku)
+    mag = np.empty(a.shape[0])
+    _lib().orc_csr_matvec(a.shape[0], _p(a.indptr), _p(a.indices), _p(np.abs(a.data)), _p(np.abs(x)), _p(mag))
+    bound = 2.0 * gamma * mag
+    bound[k == 0] = 0.0
+    return bound
+
+
 def rmatvec_acc(a, y, out):
     """``out += y * a`` continuing the chains of additions in ``out`` (in place; rows of ``a`` sorted by column): the next row
     chunk of a stacked matrix -- the result over all chunks is ``rmatvec`` of the stacked matrix bit for bit."""

@@ -10,6 +10,14 @@
 
 namespace slp {
 
+// np.minimum(np.maximum(x2, lb), ub) (ChambollePockPPD.py:221-222) as numpy computes it: a NaN stays, and of two equal operands
+// the SECOND is returned (x86 maxpd / minpd) -- x2 = -0.0 against a bound +0.0 gives +0.0, and a bound -0.0 against x2 = +0.0
+// gives -0.0 (the generator rounds bounds to 0.01: lb = -0.0, ub = +0.0 occurs).
+__device__ __forceinline__ double cp_clip(double x2, double l, double u) {
+    x2 = (x2 > l || x2 != x2) ? x2 : l;
+    return (x2 < u || x2 != x2) ? x2 : u;
+}
+
 constexpr int kMaxPartials = 4096;
 
 // ---------------------------------------------------------------------------
@@ -97,8 +105,7 @@ __global__ __launch_bounds__(kBlock) void k_cp_primal(i64 n, const i64 *__restri
             const double xo = x[j];
             double x2 = xo - t[j] * d;  // :220
             const double l = lb[j], u = ub[j];
-            x2 = (x2 < l) ? l : x2;  // np.maximum(x2, lb)
-            x2 = (x2 > u) ? u : x2;  // np.minimum(x2, ub)
+            x2 = cp_clip(x2, l, u);  // np.maximum(x2, lb), np.minimum(x2, ub)
             z[j] = one_plus_theta * x2 - theta * xo;  // :226
             x[j] = x2;
             if (d_out) d_out[j] = d;
@@ -224,8 +231,7 @@ __global__ __launch_bounds__(kBlock) void k_cp_primal_ell(i64 n, const unsigned 
         else if (m_eq > 0) d = cj + se;
         else d = cj + si;
         double x2 = xo - tj * d;  // :220
-        x2 = (x2 < l) ? l : x2;
-        x2 = (x2 > u) ? u : x2;
+        x2 = cp_clip(x2, l, u);
         z[j] = one_plus_theta * x2 - theta * xo;  // :226
         x[j] = x2;
         if (d_out) d_out[j] = d;

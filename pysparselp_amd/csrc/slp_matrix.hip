@@ -691,13 +691,32 @@ int slp_matrix_spmv_abs_pow(slp_matrix *m, int transposed, double p, const doubl
         SLP_REQUIRE(m && x && y, "slp_matrix_spmv_abs_pow: NULL argument");
         const StripJds *f = fast_format(m, transposed != 0);
         SLP_REQUIRE(f && strip_abs_pow_supported(*f), "slp_matrix_spmv_abs_pow: needs a strip / tall-cell copy of this orientation that can "
-                                                     "raise its entries to a power (slp_matrix_spmv_kernel 1-4, 6, 7)");
+                                                     "raise its entries to a power (slp_matrix_spmv_kernel 1-7)");
         const size_t nin = (size_t)(transposed ? m->a.nrow : m->a.ncol), nout = (size_t)(transposed ? m->a.ncol : m->a.nrow);
         DevBuf<double> vx(nin), vo(nout);
         vx.upload(x, nin);
         strip_spmv_abs_pow(*f, p, vx.p, vo.p);
         SLP_HIP(hipStreamSynchronize(ctx().stream));
         vo.download(y, nout);
+    })
+}
+
+int slp_matrix_spmv2(slp_matrix *m, int transposed, const double *x0, const double *x1, double *y0, double *y1) {
+    SLP_API_INT({
+        SLP_REQUIRE(m && x0 && x1 && y0 && y1, "slp_matrix_spmv2: NULL argument");
+        const size_t nin = (size_t)(transposed ? m->a.nrow : m->a.ncol), nout = (size_t)(transposed ? m->a.ncol : m->a.nrow);
+        DevBuf<double> vx0(nin), vx1(nin), vo0(nout), vo1(nout);
+        vx0.upload(x0, nin);
+        vx1.upload(x1, nin);
+        if (const StripJds *f = fast_format(m, transposed != 0)) {
+            strip_spmv2(*f, vx0.p, vx1.p, vo0.p, vo1.p);
+        } else {
+            matrix_spmv(m, transposed != 0, vx0.p, vo0.p, SLP_ORDER_AUTO);
+            matrix_spmv(m, transposed != 0, vx1.p, vo1.p, SLP_ORDER_AUTO);
+        }
+        SLP_HIP(hipStreamSynchronize(ctx().stream));
+        vo0.download(y0, nout);
+        vo1.download(y1, nout);
     })
 }
 

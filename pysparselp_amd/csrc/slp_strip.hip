@@ -919,10 +919,11 @@ __global__ __launch_bounds__(kStripT, NV == 1 ? SLP_QUAD_WAVES : 4) void k_qstri
 // gather from stays L2-resident, and inside a (row block, strip) cell the entries are stored as jagged diagonals
 // exactly like in the LDS strips (coalesced entry stream).  Row sums keep the sequential storage order.
 // DICT: 4-byte entries (value id | column << 11) + value table in LDS; else fp64 value + uint32 column.
+// POW (fp64 entries only): every stored value v enters as |v|^pw * 1.0, as in k_strip_spmv (dictionary copies get a |v|^pw table).
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
-template <bool DICT, bool ACC = false>
+template <bool DICT, bool ACC = false, bool POW = false>
 __global__ __launch_bounds__(kStripT, 8) void k_wstrip_spmv(i64 nrow, i64 ncol, i64 T, const i64 *__restrict__ base,
                                                             const unsigned short *__restrict__ perm,
                                                             const unsigned char *__restrict__ slen,
@@ -930,7 +931,8 @@ __global__ __launch_bounds__(kStripT, 8) void k_wstrip_spmv(i64 nrow, i64 ncol, 
                                                             const double *__restrict__ val, const unsigned int *__restrict__ col,
                                                             const double *__restrict__ dict, int D, const double *__restrict__ x0,
                                                             const double *__restrict__ x1, double *__restrict__ out0,
-                                                            double *__restrict__ out1) {
+                                                            double *__restrict__ out1, double pw) {
+    static_assert(!(DICT && POW), "dictionary copies take |v|^pw through their value table");
     // one right-hand side per pass: two strips of x would compete for the L2 (a two-vector version measured 50 ms for the
     // pair against 2 x 12.5 ms on the 2.5e6 x 1e7 slice)
     constexpr int NV = 1;
@@ -991,11 +993,11 @@ __global__ __launch_bounds__(kStripT, 8) void k_wstrip_spmv(i64 nrow, i64 ncol, 
 #pragma unroll
             for (int i = 0; i < kU; ++i) {
                 if (s + i < n0) {
-                    const double wa = DICT ? dv[q[i].x & ((1u << kWideColShift) - 1)] : w[i].x;
+                    const double wa = DICT ? dv[q[i].x & ((1u << kWideColShift) - 1)] : (POW ? abs_pow(w[i].x, pw) * 1.0 : w[i].x);
                     a0 += wa * g0[i];
                     if (NV == 2) b0 += wa * h0[i];
                     if (s + i < n1) {
-                        const double wb = DICT ? dv[q[i].y & ((1u << kWideColShift) - 1)] : w[i].y;
+                        const double wb = DICT ? dv[q[i].y & ((1u << kWideColShift) - 1)] : (POW ? abs_pow(w[i].y, pw) * 1.0 : w[i].y);
                         a1 += wb * g1[i];
                         if (NV == 2) b1 += wb * h1[i];
                     }
@@ -1169,16 +1171,21 @@ static bool nt_loads() {  // SLP_NT_LOADS=0 / 1: plain / non-temporal entry load
         else { constexpr bool ACC = false; CALL; }         \
     } while (0)
 
-static void wide_launch(const StripJds &f, int nv, const double *x0, const double *x1, double *o0, double *o1, int accum, int S = 0) {
+// pow (fp64 entries only): the |v|^pw product (strip_spmv_pow_one)
+static void wide_launch(const StripJds &f, int nv, const double *x0, const double *x1, double *o0, double *o1, int accum, int S = 0,
+                        bool pow = false, double pw = 0.0) {
     const dim3 grid((unsigned)f.B, (unsigned)(S > 0 ? S : f.S)), block(kStripT);
     hipStream_t st = ctx().stream;
     const unsigned int *ent = reinterpret_cast<const unsigned int *>(f.ent.p), *col = reinterpret_cast<const unsigned int *>(f.col.p);
-#define SLP_WIDE(DICT)                                                                                                                \
-    hipLaunchKernelGGL((k_wstrip_spmv<DICT, ACC>), grid, block, 0, st, f.nrow, f.ncol, f.T, f.base.p, f.perm.p, f.slen.p, f.soff.p, ent, \
-                       f.val.p, col, f.dict, f.D, x0, x1, o0, o1)
+#define SLP_WIDE(DICT, POW)                                                                                                                \
+    hipLaunchKernelGGL((k_wstrip_spmv<DICT, ACC, POW>), grid, block, 0, st, f.nrow, f.ncol, f.T, f.base.p, f.perm.p, f.slen.p, f.soff.p, \
+                       ent, f.val.p, col, f.dict, f.D, x0, x1, o0, o1, pw)
     (void)nv;
-    if (f.D > 0) SLP_WITH_ACC(accum, SLP_WIDE(true));
-    else SLP_WITH_ACC(accum, SLP_WIDE(false));
+    if (pow) {
+        SLP_REQUIRE(f.D == 0, "wide_launch: |v|^pw over a dictionary copy goes through its value table");
+        SLP_WITH_ACC(accum, SLP_WIDE(false, true));
+    } else if (f.D > 0) SLP_WITH_ACC(accum, SLP_WIDE(true, false));
+    else SLP_WITH_ACC(accum, SLP_WIDE(false, false));
 #undef SLP_WIDE
 }
 
@@ -1323,7 +1330,13 @@ void strip_spmv(const StripJds &f, const double *x, double *out) {
 
 static void strip_spmv_pow_one(const StripJds &f, double pw, const double *x, double *out, int accum) {
     if (f.ok && f.tall && f.D == 0) { tall_spmv_pow(f, pw, x, out, accum); return; }
-    SLP_REQUIRE(f.ok && !f.wide && !f.tall && f.D == 0, "strip_spmv_pow: not an fp64 strip copy");
+    SLP_REQUIRE(f.ok && !f.tall && f.D == 0, "strip_spmv_pow: not an fp64 strip copy");
+    if (f.wide) {
+        wide_launch(f, 1, x, x, f.S > 1 ? f.part.p : out, nullptr, accum, f.S, true, pw);
+        if (f.S > 1) strip_combine(f, f.part.p, out, accum);
+        SLP_HIP(hipGetLastError());
+        return;
+    }
     SLP_WITH_ACC(accum, hipLaunchKernelGGL((k_strip_spmv<0, true, false, true, ACC>), dim3((unsigned)f.B, (unsigned)f.S), dim3(kStripT), 0,
                                            ctx().stream, f.nrow, f.ncol, f.T, f.base.p, f.perm.p, f.slen.p, f.soff.p, f.val.p, f.col.p, x,
                                            f.S > 1 ? f.part.p : out, pw));
@@ -1331,7 +1344,7 @@ static void strip_spmv_pow_one(const StripJds &f, double pw, const double *x, do
     SLP_HIP(hipGetLastError());
 }
 
-// y = |A|^pw x over the fp64 strip copy: every row the same chain of additions as the CSR walk with |v|^pw * 1.0 terms.
+// y = |A|^pw x over an fp64 strip / wide-strip / tall-cell copy: every row the same chain of additions as the CSR walk with |v|^pw * 1.0 terms.
 void strip_spmv_pow(const StripJds &f, double pw, const double *x, double *out) {
     if (f.parts.empty()) { strip_spmv_pow_one(f, pw, x, out, 0); return; }
     for_parts(f, [&](const StripJds &g, i64 xo, i64 oo, int accum) { strip_spmv_pow_one(g, pw, x + xo, out + oo, accum); });
@@ -1358,15 +1371,15 @@ void strip_spmv_with_dict(const StripJds &f, const double *table, const double *
     strip_spmv_with_dict_one(f, table, x, out, 0);
 }
 
-// Can strip_spmv_abs_pow run on this copy?  Dictionary copies of every kind, fp64 LDS strips and fp64 tall cells (not the
-// fp64 wide strips, the fallback of the fallback).
+// Can strip_spmv_abs_pow run on this copy?  Every kind: dictionary copies through a |v|^pw table, fp64 LDS strips, wide strips
+// and tall cells with |v|^pw on the fly.
 bool strip_abs_pow_supported(const StripJds &f) {
     if (!f.parts.empty()) {
         for (const StripJds *g : f.parts)
             if (!strip_abs_pow_supported(*g)) return false;
         return true;
     }
-    return f.ok && (f.D > 0 || !f.wide);
+    return f.ok;
 }
 
 // out = |A|^pw x: every stored value v enters as |v|^pw * 1.0 (the sums behind the Chambolle-Pock preconditioners,

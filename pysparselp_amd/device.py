@@ -72,6 +72,16 @@ class DeviceMatrix:
         _lib.check(self._l.slp_matrix_spmv_abs_pow(self._h, int(bool(transposed)), float(p), _lib.ptr(x), _lib.ptr(out)))
         return out
 
+    def matvec2(self, x0, x1, transposed=False):
+        """``(A x0, A x1)`` or, ``transposed``, ``(A^T x0, A^T x1)`` through the two-vector pass of that orientation's strip /
+        wide-strip / tall-cell copy (the matrix-free ADMM's paired CG products), two products without one."""
+        x0, x1 = _lib.f64(x0), _lib.f64(x1)
+        nin, nout = (self.shape[0], self.shape[1]) if transposed else (self.shape[1], self.shape[0])
+        assert x0.size == nin and x1.size == nin
+        y0, y1 = np.empty(nout), np.empty(nout)
+        _lib.check(self._l.slp_matrix_spmv2(self._h, int(bool(transposed)), _lib.ptr(x0), _lib.ptr(x1), _lib.ptr(y0), _lib.ptr(y1)))
+        return y0, y1
+
     def download(self, transposed=False):
         """scipy CSR copy of the device arrays (``transposed=True``: the device-built A^T)."""
         nrow, ncol = (self.shape[1], self.shape[0]) if transposed else self.shape
