@@ -16,10 +16,13 @@ block never exists).  N > 1 row-partitions the SAME problem over the N GPUs
 processes + a TCP id exchange, no torch anywhere); the driver's ``python -m
 torch.distributed.run --nproc-per-node N ... bench.py --gpus N`` works too (bench.py
 only reads the RANK / WORLD_SIZE / MASTER_* it sets).  ``--config c3`` runs BASELINE config 3 (1e6 x 2e6 at
-1e-3, the headline of rounds 1-3); at N = 1 the default run appends it as
+1e-3, the headline of rounds 1-3); at N = 1 ``--full`` on the default workload appends it as
 ``secondary.c3`` (same code path, a few seconds).
 
-Rank 0 prints ONE JSON line (contract in the task statement) carrying
+Rank 0 prints ONE JSON line.  A plain run does only what the headline figure needs: it sets the workload up, runs the
+warm-up and the K timed steps, writes ``--dump-outputs`` and prints the line -- ``metric``, ``value``, ``ms_per_step``
+and the other headline keys, ``config``, ``exchange``, ``objective_after_run``, ``setup_seconds``, ``setup_breakdown``
+and ``device_memory``, all read off the run itself.  ``--full`` runs the same timed steps and then measures the rest:
 
 ``roofline``      the dominant kernel (the SpMV ``y = A x`` of the timed step): bytes that kernel HAS TO MOVE per launch
                   (the matrix copy it streams + the vector it reads + the vector it writes) / its HIP-event time, against
@@ -35,8 +38,10 @@ Rank 0 prints ONE JSON line (contract in the task statement) carrying
                   of the full size), ITERATIONS ONLY (setup excluded), scaled by the row ratio; ``extrapolated: true``;
                   ``matrix_products_per_iteration`` = the products of the reference's form of the iteration that it times
                   (ADMM 10, Chambolle-Pock 2; the device spends ``config.matrix_passes_per_iteration`` = 4 / 2 on the same iterates).
-``chambolle_pock`` / ``cpu_baseline.chambolle_pock``  (default line) the Chambolle-Pock rate on the same resident LP and the oracle's on
+``chambolle_pock`` / ``cpu_baseline.chambolle_pock``  (default workload) the Chambolle-Pock rate on the same resident LP and the oracle's on
                   the same sample: the method where both sides do the SAME two products per iteration.
+``secondary.c3``  (default workload, N = 1) BASELINE config 3 through the same code, ``--full`` included.
+
 ``--eq-frac 0.1``  SURVEY 8(d)'s second workload: the first tenth of the rows are equalities a_i x = a_i x_feasible
                   (randomLP.py:62-68); a chunked block is cut at the boundary, Chambolle-Pock keeps the reference's
                   (c + y_eq a_eq) + y_ineq a_ineq bit for bit (csrc/slp_cp.hip cp_split_setup).
@@ -117,7 +122,11 @@ def parse():
     p.add_argument("--n", "--vars", dest="n", type=int, default=None, help="variables (default: config c4)")
     p.add_argument("--m", "--rows", dest="m", type=int, default=None, help="inequality constraints")
     p.add_argument("--density", type=float, default=None)
-    p.add_argument("--no-secondary", action="store_true", help="skip the config-3 block the default N = 1 run appends")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also measure what the headline figure does not need: the roofline's own product "
+                        "timings, Chambolle-Pock on the same LP, the general fp64 path, the CPU baseline and the secondary config-3 "
+                        "block (the timed steps and the headline keys are the same with and without it)")
+    p.add_argument("--no-secondary", action="store_true", help="--full: skip the config-3 block the default N = 1 run appends")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--method", default=None, choices=["admm", "chambolle_pock_ppd", "admm_blocks"],
                    help="default: admm (admm_blocks for --config c5)")
@@ -128,8 +137,8 @@ def parse():
                    help="admm_blocks: row blocks on every rank (DeviceBlocksGroup; default 1, for --config c5: 8 / gpus)")
     p.add_argument("--chunks-per-block", type=int, default=1, help="admm_blocks with block groups: row chunks every block is converted in")
     p.add_argument("--jacobi", action="store_true", help="admm_blocks: Jacobi-preconditioned conjugate gradients (slp_blocks_set_precond)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-general", action="store_true", help="skip the general (fp64 strip entries) block")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (and the Chambolle-Pock figure)")
+    p.add_argument("--no-general", action="store_true", help="--full: skip the general (fp64 strip entries) block")
     p.add_argument("--keep-csr", dest="release_csr", action="store_false",
                    help="keep both CSR orientations resident during the timed region (default: released once the strip copies exist)")
     p.add_argument("--cpu-sample-rows", type=int, default=0, help="rows of the CPU sample (default m / 10)")
@@ -222,6 +231,53 @@ def spmv_block(lib, a, transposed, shape, reps=5):
         out["traffic"] = traffic
         out["traffic_source"] = src
     return out, which
+
+
+def roofline_block(lib, a, shape, args, world, passes, nnz_total, prod, dt):
+    """``--full``: the line's ``roofline`` -- both SpMV orientations of rank 0's resident matrix timed in runs of their own
+    (spmv_block), with the products of the timed steps (``prod``: slp_product_timing_read) beside them; (roofline, the kernel id
+    of y = A x)."""
+    ms_step = 1e3 * dt / args.steps
+    ax, which = spmv_block(lib, a, False, shape)
+    aty, _ = spmv_block(lib, a, True, shape)
+    # one iteration = `passes` single-vector sweeps, alternating orientations: bytes the iteration has to move
+    # (block groups: every block of the rank runs its own `passes`; the products are timed on the first block)
+    iter_bytes = passes / 2.0 * (ax["bytes_per_product"] + aty["bytes_per_product"])
+    roofline = {
+        "bound": "hbm",
+        "kernel": ax["kernel"] + " -- rank 0's row block",
+        "achieved": ax["achieved"],
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": ax["frac"],
+        "traffic": ax["traffic"],
+        "traffic_source": ax["traffic_source"],
+        "traffic_measured_in_this_run": False,  # a committed rocprofv3 PMC summary of this command, not a counter of this run
+        "definition": "achieved = bytes the kernel has to move per product y = A x (the matrix copy it streams + x read once + y "
+                      "written once) / HIP-event time per product on the library's stream; traffic = rocprofv3 PMC "
+                      "(FETCH_SIZE x 2 + WRITE_SIZE, separate passes) of the same kernel on the same workload, per product",
+        "bytes_per_product": ax["bytes_per_product"],
+        "matrix_copy_bytes_per_product": ax["matrix_copy_bytes_per_product"],
+        "ms_per_product": ax["ms_per_product"],
+        "products_timed": ax["products_timed"],               # back-to-back, behind ~0.1 s of untimed ones (spmv_block)
+        # the products of the K timed steps themselves (HIP event pairs around each, both orientations: the solver's own
+        # launches on the stream they ran on): their number, average duration and what that is in bytes moved per second
+        "timed_region": (None if prod[0] == 0 else {
+            "products": int(prod[0]), "products_per_step": prod[0] / args.steps,
+            "ms_per_product": prod[1] / prod[0], "longest_ms": prod[2],
+            "bytes_per_product": 0.5 * (ax["bytes_per_product"] + aty["bytes_per_product"]),
+            "achieved": 0.5 * (ax["bytes_per_product"] + aty["bytes_per_product"]) / (prod[1] / prod[0] * 1e-3) / 1e9,
+            "frac": 0.5 * (ax["bytes_per_product"] + aty["bytes_per_product"]) / (prod[1] / prod[0] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "share_of_step": prod[1] / (1e3 * dt)}),
+        "launches_per_product": ax["launches_per_product"],   # a chunked matrix may take one launch per row chunk
+        "ms_per_launch": ax["ms_per_launch"],                 # = ms_per_product / launches_per_product
+        "csr_equivalent": ax["csr_equivalent"],
+        "spmv_transposed": aty,
+        "iteration": {"bytes": iter_bytes, "achieved": iter_bytes / (ms_step * 1e-3) / 1e9,
+                      "frac_of_all_gpus": iter_bytes / (ms_step * 1e-3) / 1e9 / (HBM_PEAK_GBS * world),
+                      "csr_equivalent_gbps": passes * 12 * nnz_total / (ms_step * 1e-3) / 1e9},
+    }
+    return roofline, which
 
 
 def cpu_baseline(args, method, also_cp=False):
@@ -572,7 +628,7 @@ def main():
         out = run_workload(lib, args, rank, world, distributed)
         out["config"]["chunks_doubled_after"] = oom
     if rank == 0:
-        if world == 1 and args.default_workload and not args.no_secondary and args.method != "admm_blocks":
+        if args.full and world == 1 and args.default_workload and not args.no_secondary and args.method != "admm_blocks":
             # BASELINE config 3 through the same code: the headline workload of rounds 1-3, for continuity.  The headline line
             # does not depend on it: whatever goes wrong here is recorded, the line is printed all the same.
             import copy
@@ -655,7 +711,9 @@ def run_workload(lib, args, rank, world, distributed):
     _lib.check(lib.slp_comm_barrier())
     coll0 = int(lib.slp_comm_collectives())
     _lib.check(lib.slp_comm_timing(1))   # HIP event pairs around every collective: recorded now, read after the timed region
-    _lib.check(lib.slp_product_timing(1))  # ... and around every product of the solver (the stream it runs on): roofline.timed_region
+    # ... and around every product of the solver (the stream it runs on): roofline.timed_region.  On in every run, --full or not,
+    # so that the timed steps are the same steps either way.
+    _lib.check(lib.slp_product_timing(1))
     t0 = time.perf_counter()
     solver.iterate(args.steps)
     _lib.check(lib.slp_comm_timing(0))   # (the closing barrier's all-reduce is not part of an iteration)
@@ -683,50 +741,12 @@ def run_workload(lib, args, rank, world, distributed):
     out = None
     if rank == 0:
         ms_step = 1e3 * dt / args.steps
-        ax, which = spmv_block(lib, a, False, shape)
-        aty, _ = spmv_block(lib, a, True, shape)
         passes = solver.matrix_passes_per_iteration()
         if args.method == "admm_blocks":  # per block: 3 products + 2 per conjugate-gradient step (rank 0's count over its blocks)
             passes = 3 * args.blocks_per_rank + 2 * (solver.cg_steps() - cg0) / args.steps
             if args.block_group:   # the products were timed on ONE block: bytes per iteration = passes x that block's bytes
                 pass
-        # one iteration = `passes` single-vector sweeps, alternating orientations: bytes the iteration has to move
-        # (block groups: every block of the rank runs its own `passes`; the products are timed on the first block)
-        iter_bytes = passes / 2.0 * (ax["bytes_per_product"] + aty["bytes_per_product"])
-        roofline = {
-            "bound": "hbm",
-            "kernel": ax["kernel"] + " -- rank 0's row block",
-            "achieved": ax["achieved"],
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": ax["frac"],
-            "traffic": ax["traffic"],
-            "traffic_source": ax["traffic_source"],
-            "traffic_measured_in_this_run": False,  # a committed rocprofv3 PMC summary of this command, not a counter of this run
-            "definition": "achieved = bytes the kernel has to move per product y = A x (the matrix copy it streams + x read once + y "
-                          "written once) / HIP-event time per product on the library's stream; traffic = rocprofv3 PMC "
-                          "(FETCH_SIZE x 2 + WRITE_SIZE, separate passes) of the same kernel on the same workload, per product",
-            "bytes_per_product": ax["bytes_per_product"],
-            "matrix_copy_bytes_per_product": ax["matrix_copy_bytes_per_product"],
-            "ms_per_product": ax["ms_per_product"],
-            "products_timed": ax["products_timed"],               # back-to-back, behind ~0.1 s of untimed ones (spmv_block)
-            # the products of the K timed steps themselves (HIP event pairs around each, both orientations: the solver's own
-            # launches on the stream they ran on): their number, average duration and what that is in bytes moved per second
-            "timed_region": (None if prod[0] == 0 else {
-                "products": int(prod[0]), "products_per_step": prod[0] / args.steps,
-                "ms_per_product": prod[1] / prod[0], "longest_ms": prod[2],
-                "bytes_per_product": 0.5 * (ax["bytes_per_product"] + aty["bytes_per_product"]),
-                "achieved": 0.5 * (ax["bytes_per_product"] + aty["bytes_per_product"]) / (prod[1] / prod[0] * 1e-3) / 1e9,
-                "frac": 0.5 * (ax["bytes_per_product"] + aty["bytes_per_product"]) / (prod[1] / prod[0] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "share_of_step": prod[1] / (1e3 * dt)}),
-            "launches_per_product": ax["launches_per_product"],   # a chunked matrix may take one launch per row chunk
-            "ms_per_launch": ax["ms_per_launch"],                 # = ms_per_product / launches_per_product
-            "csr_equivalent": ax["csr_equivalent"],
-            "spmv_transposed": aty,
-            "iteration": {"bytes": iter_bytes, "achieved": iter_bytes / (ms_step * 1e-3) / 1e9,
-                          "frac_of_all_gpus": iter_bytes / (ms_step * 1e-3) / 1e9 / (HBM_PEAK_GBS * world),
-                          "csr_equivalent_gbps": passes * 12 * nnz_total / (ms_step * 1e-3) / 1e9},
-        }
+        roofline, which = roofline_block(lib, a, shape, args, world, passes, nnz_total, prod, dt) if args.full else (None, None)
         out = {
             "metric": {"admm": "admm", "admm_blocks": "admm_blocks", "chambolle_pock_ppd": "chambolle_pock"}[args.method] + "_iterations_per_sec",
             "value": args.steps / dt,
@@ -765,7 +785,7 @@ def run_workload(lib, args, rank, world, distributed):
             # what of a step was exchange: HIP event pairs around every collective of the timed region (slp_comm_timing), max over
             # the ranks; under RCCL a pair brackets the collective's kernel, whose duration includes the wait for the slowest peer
             "exchange": exchange_block(args, world, distributed, coll, exch, exch_max, ms_step),
-            "roofline": roofline,
+            **({"roofline": roofline} if args.full else {}),
             "objective_after_run": obj,
             "setup_seconds": t_gen,
             "setup_breakdown": {"generate_lp_seconds": t_generate, "solver_setup_seconds": t_gen - t_generate,
@@ -778,7 +798,7 @@ def run_workload(lib, args, rank, world, distributed):
         }
         solver.close()
         solver = None
-        if world == 1 and args.method == "admm" and args.default_workload and not args.no_cpu_baseline:
+        if args.full and world == 1 and args.method == "admm" and args.default_workload and not args.no_cpu_baseline:
             # Chambolle-Pock on the same resident LP, beside the ADMM figure: the method where the CPU path and the device do the SAME
             # two products per iteration (cpu_baseline.chambolle_pock is its partner)
             try:
@@ -790,12 +810,12 @@ def run_workload(lib, args, rank, world, distributed):
                 cp.close()
             except Exception as e:  # noqa: BLE001 -- never a reason to lose the headline line
                 out["chambolle_pock"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_general and args.format == 0 and which >= 2 and args.method != "admm_blocks" and chunks == 1:
+        if args.full and world == 1 and not args.no_general and args.format == 0 and which >= 2 and args.method != "admm_blocks" and chunks == 1:
             if released:  # the CSR entries are gone: the same rows again from the counter-based generator
                 a.close()
                 a = DeviceMatrix.random(rows, args.n, args.density, args.seed, r0)
             roofline["general_fp64"] = general_block(lib, args, a, b, c, lb, ub, shape)
-        if world == 1 and not args.no_general and args.format == 0 and which == 6 and args.method != "admm_blocks" and chunks > 1:
+        if args.full and world == 1 and not args.no_general and args.format == 0 and which == 6 and args.method != "admm_blocks" and chunks > 1:
             # The metric's LP with ARBITRARY coefficients: fp64 entries are 12.4 B per stored entry as tall cells -- both
             # orientations of the whole LP would be 2.4 x the 5.2 B dictionary copies (509 GB) and do not fit one GPU.  What one
             # GPU holds of it is measured instead: the first EIGHTH of the rows (the row block of one of 8 ranks = --config
@@ -814,7 +834,7 @@ def run_workload(lib, args, rank, world, distributed):
                                   "with fp64 entries needs min_gpus GPUs, where a rank's rates are these per-share rates scaled by its "
                                   "share of the rows (plus the exchange)"})
             roofline["general_fp64"] = share
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             a.close()
             a = None
             _lib.check(lib.slp_trim())

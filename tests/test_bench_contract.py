@@ -134,7 +134,7 @@ def test_committed_round4_bench_lines(name):
 @pytest.mark.parametrize("method", ["admm", "chambolle_pock_ppd"])
 def test_live_bench_line(method):
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--n", "20000", "--m", "40000", "--density", "0.001",
-                        "--steps", "4", "--warmup", "1", "--method", method],
+                        "--steps", "4", "--warmup", "1", "--method", method, "--full"],
                        capture_output=True, text=True, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -191,6 +191,47 @@ def test_dump_outputs_samples_a_large_solution_the_same_way_every_time(tmp_path)
     assert c.dtype == np.float64 and np.array_equal(c, np.arange(1000))   # a small x is written whole
 
 
+FULL_ONLY = ("roofline", "chambolle_pock", "cpu_baseline", "secondary")   # what --full measures after the timed steps
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("method", ["admm", "chambolle_pock_ppd"])
+def test_plain_line_is_the_headline_of_the_full_one(method, tmp_path):
+    """Without ``--full`` bench.py sets up, warms up, times the K steps, dumps x and prints the line: the headline keys, meaning
+    what they mean under ``--full``, and nothing that ``--full`` measures after the timed steps.  Both runs time the same steps:
+    same LP, same x, same objective."""
+    import numpy as np
+
+    runs = {}
+    for mode in ("plain", "full"):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--n", "20000", "--m", "40000", "--density", "0.001",
+                            "--steps", "4", "--warmup", "1", "--method", method, "--dump-outputs", str(tmp_path / mode)]
+                           + (["--full"] if mode == "full" else []), capture_output=True, text=True, timeout=600, cwd=REPO)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        runs[mode] = json.loads(lines[0]), np.load(tmp_path / mode / "x.npy")
+    (plain, x_plain), (full, x_full) = runs["plain"], runs["full"]
+    check_line(full, need_cpu_baseline=True)
+    for key, typ in TOP.items():
+        if key != "roofline":
+            assert isinstance(plain[key], typ) or (typ is float and isinstance(plain[key], int)), (key, type(plain.get(key)))
+    assert not [k for k in FULL_ONLY if k in plain] and set(plain) <= set(full)
+    assert plain["vs_baseline"] is None and plain["higher_is_better"] is True and plain["unit"] == "it/s" and plain["dtype"] == "f64"
+    assert abs(plain["value"] - 1000.0 / plain["ms_per_step"]) < 1e-6 * plain["value"]
+    assert plain["steps"] == 4 and plain["warmup"] == 1 and plain["n_gpus"] == 1
+    assert plain["metric"] == full["metric"] and plain["config"] == full["config"]
+    assert plain["objective_after_run"] == full["objective_after_run"] and np.array_equal(x_plain, x_full)
+
+
+def test_full_is_an_option_off_by_default():
+    code = ("import runpy, sys\nb = runpy.run_path(sys.argv[1])\nsys.argv = ['bench.py']\nassert b['parse']().full is False\n"
+            "sys.argv = ['bench.py', '--full']\nassert b['parse']().full is True\n")
+    r = subprocess.run([sys.executable, "-c", code, os.path.join(REPO, "bench.py")], capture_output=True, text=True, timeout=120,
+                       cwd=REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+
 def test_steps_below_one_are_rejected():
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120,
                        cwd=REPO)
@@ -200,7 +241,7 @@ def _launch(nproc, extra_env, port, more=()):
     env = dict(os.environ, **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", str(nproc), "--steps", "4", "--warmup", "2",
-           "--vars", "30000", "--rows", "40000", "--density", "0.001", "--no-cpu-baseline", "--no-general"] + list(more)
+           "--vars", "30000", "--rows", "40000", "--density", "0.001", "--full", "--no-cpu-baseline", "--no-general"] + list(more)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=REPO, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -213,7 +254,7 @@ def _self_launch(nproc, extra_env, more=()):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(extra_env)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(nproc), "--steps", "4", "--warmup", "2",
-           "--vars", "30000", "--rows", "40000", "--density", "0.001", "--no-cpu-baseline", "--no-general"] + list(more)
+           "--vars", "30000", "--rows", "40000", "--density", "0.001", "--full", "--no-cpu-baseline", "--no-general"] + list(more)
     return subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=REPO, env=env)
 
 

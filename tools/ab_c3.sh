@@ -4,7 +4,7 @@ O=gpurun_out/ab_c3
 mkdir -p $O
 for rep in 1 2; do
 for v in "$@"; do
-    SLP_LIB_VARIANT=$v timeout 600 python bench.py --config c3 --no-cpu-baseline --no-general > $O/c3_${v:-new}_$rep.json 2>> $O/err.log
+    SLP_LIB_VARIANT=$v timeout 600 python bench.py --config c3 --full --no-cpu-baseline --no-general > $O/c3_${v:-new}_$rep.json 2>> $O/err.log
     python - "$O/c3_${v:-new}_$rep.json" "${v:-new}" <<'PY'
 import json, sys
 try:

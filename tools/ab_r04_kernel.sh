@@ -8,7 +8,7 @@ O=gpurun_out/ab_r04
 mkdir -p $O
 run() {  # run <tag> <variant or ""> <bench args...>
     local tag=$1 v=$2; shift 2
-    SLP_LIB_VARIANT=$v timeout 600 python bench.py --no-cpu-baseline --no-general --no-secondary "$@" > $O/$tag.json 2>> $O/err.log
+    SLP_LIB_VARIANT=$v timeout 600 python bench.py --full --no-cpu-baseline --no-general --no-secondary "$@" > $O/$tag.json 2>> $O/err.log
     python - "$O/$tag.json" "$tag" <<'PY'
 import json, sys
 try:

@@ -3,12 +3,12 @@
 # Chambolle-Pock on config 4, both methods on the 1/8 slice and on config 3.
 O=gpurun_out/final
 mkdir -p $O
-SLP_TRACE=1 timeout 900 python bench.py > $O/bench_admm_c4_1gpu.json 2> $O/setup_trace_c4_1gpu.txt; echo rc=$?
-timeout 900 python bench.py --method chambolle_pock_ppd --no-secondary > $O/bench_cp_c4_1gpu.json 2> /dev/null; echo rc=$?
-timeout 600 python bench.py --config c4slice > $O/bench_admm_c4slice.json 2> /dev/null; echo rc=$?
-timeout 600 python bench.py --config c4slice --method chambolle_pock_ppd > $O/bench_cp_c4slice.json 2> /dev/null; echo rc=$?
-SLP_TRACE=1 timeout 600 python bench.py --config c3 > $O/bench_admm_c3.json 2> $O/setup_trace_c3.txt; echo rc=$?
-timeout 600 python bench.py --config c3 --method chambolle_pock_ppd > $O/bench_cp_c3.json 2> /dev/null; echo rc=$?
+SLP_TRACE=1 timeout 900 python bench.py --full > $O/bench_admm_c4_1gpu.json 2> $O/setup_trace_c4_1gpu.txt; echo rc=$?
+timeout 900 python bench.py --full --method chambolle_pock_ppd --no-secondary > $O/bench_cp_c4_1gpu.json 2> /dev/null; echo rc=$?
+timeout 600 python bench.py --full --config c4slice > $O/bench_admm_c4slice.json 2> /dev/null; echo rc=$?
+timeout 600 python bench.py --full --config c4slice --method chambolle_pock_ppd > $O/bench_cp_c4slice.json 2> /dev/null; echo rc=$?
+SLP_TRACE=1 timeout 600 python bench.py --full --config c3 > $O/bench_admm_c3.json 2> $O/setup_trace_c3.txt; echo rc=$?
+timeout 600 python bench.py --full --config c3 --method chambolle_pock_ppd > $O/bench_cp_c3.json 2> /dev/null; echo rc=$?
 python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/final/bench_*.json")):

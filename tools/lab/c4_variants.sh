@@ -4,7 +4,7 @@
 OUT=$1; shift
 for rep in 1 2; do
   for v in "$@"; do
-    echo "variant=[${v:-shipped}] $(SLP_LIB_VARIANT=$v timeout 400 python bench.py --no-cpu-baseline --no-secondary --no-general 2>/dev/null | python3 -c "
+    echo "variant=[${v:-shipped}] $(SLP_LIB_VARIANT=$v timeout 400 python bench.py --full --no-cpu-baseline --no-secondary --no-general 2>/dev/null | python3 -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']

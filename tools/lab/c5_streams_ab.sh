@@ -9,7 +9,7 @@ mkdir -p "$(dirname "$OUT")"
 for rep in $(seq 1 $REPS); do
   for mode in ${MODES:-0 1}; do
     export SLP_BLOCKS_STREAMS=$mode
-    echo "streams=[$mode] $(timeout 900 python bench.py --config c5 --no-cpu-baseline 2>/dev/null | python3 -c "
+    echo "streams=[$mode] $(timeout 900 python bench.py --config c5 --full --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']

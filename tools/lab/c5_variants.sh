@@ -4,7 +4,7 @@
 OUT=$1; shift
 for rep in 1 2; do
   for v in "$@"; do
-    echo "variant=[${v:-shipped}] $(SLP_LIB_VARIANT=$v timeout 600 python bench.py --config c5 --no-cpu-baseline 2>/dev/null | python3 -c "
+    echo "variant=[${v:-shipped}] $(SLP_LIB_VARIANT=$v timeout 600 python bench.py --config c5 --full --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']

@@ -7,7 +7,7 @@ R="${GRAFT_REPO_ROOT:?}"
 cd "$R" || exit 1
 O=gpurun_out/${1:-prof_c4}
 mkdir -p $O
-A="--config c4 --no-cpu-baseline --no-secondary"
+A="--config c4 --full --no-cpu-baseline --no-secondary"
 rocprofv3 --kernel-trace --stats -d $R/$O/stats_admm -o admm -- python3 bench.py $A --steps 5 --warmup 2 > $O/stats_admm_bench.json 2> $O/stats_admm.err
 rocprofv3 --pmc FETCH_SIZE -d $R/$O/pmc_fetch -o f -- python3 bench.py $A --steps 2 --warmup 1 > /dev/null 2> $O/pmc_fetch.err
 rocprofv3 --pmc WRITE_SIZE -d $R/$O/pmc_write -o w -- python3 bench.py $A --steps 2 --warmup 1 > /dev/null 2> $O/pmc_write.err

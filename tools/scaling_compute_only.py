@@ -14,7 +14,7 @@ SHAPES = {"c4": (10_000_000, 20_000_000, 1e-4), "c3": (1_000_000, 2_000_000, 1e-
 
 
 def run(extra):
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--no-cpu-baseline", "--no-general", "--no-secondary",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--no-cpu-baseline", "--no-general", "--no-secondary",
                           "--steps", "10", "--warmup", "2"] + extra, capture_output=True, text=True, check=True).stdout.strip().splitlines()[-1]
     d = json.loads(out)
     return {"it_per_s": d["value"], "ms_per_step": d["ms_per_step"], "Ax_ms": d["roofline"]["ms_per_product"],

@@ -14,7 +14,7 @@ def run(rows, variant):
     env.pop("SLP_DICT_VARIANT", None)
     if variant:
         env["SLP_DICT_VARIANT"] = str(variant)
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--no-cpu-baseline", "--no-general", "--steps", "20", "--warmup", "3",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--no-cpu-baseline", "--no-general", "--steps", "20", "--warmup", "3",
                           "--m", str(rows)], capture_output=True, text=True, check=True, env=env).stdout.strip().splitlines()[-1]
     d = json.loads(out)
     return {"ms_per_step": round(d["ms_per_step"], 4), "Ax_ms": round(d["roofline"]["ms_per_product"], 4),
