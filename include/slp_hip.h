@@ -68,6 +68,13 @@ int slp_timer_stop(double *ms);
 typedef struct slp_matrix slp_matrix;
 slp_matrix *slp_matrix_create(int64_t nrow, int64_t ncol, const int64_t *indptr,
                               const int32_t *indices, const double *data);
+/* [A_top; A_bottom] as ONE device CSR from two host CSR blocks with the same column count: replaces the host stacking
+ * of [A_eq; K_ineq] (ChambollePockPPD.py:145-233 concatenates the two blocks into a new CSR before its loop;
+ * tools.py:96-107 stacks them for ADMM).  Each block is uploaded as it is, the bottom block's row offsets are shifted by
+ * nnz(A_top) on the device; no host copy of the values is made.  nrow_top may be 0 (top arrays then unused). */
+slp_matrix *slp_matrix_create_stacked(int64_t ncol, int64_t nrow_top, const int64_t *top_indptr, const int32_t *top_indices,
+                                      const double *top_data, int64_t nrow_bottom, const int64_t *bottom_indptr,
+                                      const int32_t *bottom_indices, const double *bottom_data);
 void slp_matrix_destroy(slp_matrix *a);
 int64_t slp_matrix_nnz(const slp_matrix *a);
 /* y[nrow] = A x[ncol]   (host vectors in, host vector out) */
@@ -338,6 +345,26 @@ slp_admm_cg *slp_admm_cg_create_on_mixed(slp_matrix *a, int64_t m_eq, const doub
 slp_admm_cg *slp_admm_cg_create_on_two_sided(slp_matrix *a, int64_t m_eq, const double *b_lower, const double *b_upper,
                                              const double *c, const double *lb, const double *ub, double gamma_eq,
                                              double gamma_ineq, int order);
+/* The same with the two settings of lp_admm that the forms above fix (ADMM.py:47-101): x0 (NULL: zeros) is the warm
+ * start x = [x0; A_i' x0], A_i' = the inequality rows after the first row scaling (tools.py:88-127 after :77,82), and
+ * xp = max(x, 0) (ADMM.py:98); use_preconditioning = 0 skips the second row scaling (ADMM.py:90-91: the slack entries
+ * stay -1, b is scaled once).  In the in-place form A_i' x0 is taken over the CSR between the two scalings, one
+ * sequential sum per row in storage order; in the value-dictionary form it is inv1_i * (A0 x0)_i from the unscaled
+ * matrix's product copy -- the same value up to the rounding of the row scale taken after the sum instead of per entry. */
+slp_admm_cg *slp_admm_cg_create_on_lp(slp_matrix *a, int64_t m_eq, const double *b_lower, const double *b_upper,
+                                      const double *c, const double *lb, const double *ub, const double *x0,
+                                      double gamma_eq, double gamma_ineq, int use_preconditioning, int order);
+/* The solver from the LP as lp_admm(xstep="cg") receives it, with the arguments of slp_admm_create_lp: replaces the host
+ * set-up chain of the reference's use_cg branch (ADMM.py:73-101: precondition_constraints three times and
+ * convert_to_standard_form_with_bounds, tools.py:88-127,272-290, then one upload of the explicit standard form).  The two
+ * blocks are stacked on the device (slp_matrix_create_stacked; the solver owns the matrix) and set up as
+ * slp_admm_cg_create_on_lp does, slack column implicit.  eq_indptr may be NULL when m_eq = 0; b_lower / b_upper NULL:
+ * -inf / +inf.  With slp_comm_init active the caller passes this rank's rows of [A_eq; A_ineq] only. */
+slp_admm_cg *slp_admm_cg_create_lp(int64_t n, int64_t m_eq, const int64_t *eq_indptr, const int32_t *eq_indices,
+                                   const double *eq_data, const double *b_eq, int64_t m_ineq, const int64_t *in_indptr,
+                                   const int32_t *in_indices, const double *in_data, const double *b_lower,
+                                   const double *b_upper, const double *c, const double *lb, const double *ub,
+                                   const double *x0, double gamma_eq, double gamma_ineq, int use_preconditioning, int order);
 void slp_admm_cg_destroy(slp_admm_cg *s);
 /* Products of A per iteration (same mathematics, fp64 rounding differences only); default 0:
  * 0  ten, as the reference writes the iteration;

@@ -135,6 +135,7 @@ def lp_admm(
     nb_iter_plot=10,
     order=ORDER_AUTO,
     xstep="gauss_seidel",
+    setup="auto",
 ):
     """minimise c.x  s.t.  a_eq x = beq,  b_lower <= a_ineq x <= b_upper,  lb <= x <= ub.
 
@@ -143,13 +144,15 @@ def lp_admm(
     ADMM.py:66-71), run matrix-free -- see ``admm_cg.py``;
     ``"gauss_seidel_unbounded"`` is its plain Gauss-Seidel + over-relaxation
     branch (ADMM.py:164-181).
+    ``setup`` (extension, ``xstep="cg"`` only): where its set-up chain runs,
+    ``"auto"`` / ``"host"`` / ``"device"`` -- see ``admm_cg.lp_admm_cg``.
     """
     if xstep == "cg":
         from .admm_cg import lp_admm_cg
 
         return lp_admm_cg(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0=x0, gamma_eq=gamma_eq, gamma_ineq=gamma_ineq,
                           nb_iter=nb_iter, callback_func=callback_func, max_time=max_time,
-                          use_preconditioning=use_preconditioning, nb_iter_plot=nb_iter_plot, order=order)
+                          use_preconditioning=use_preconditioning, nb_iter_plot=nb_iter_plot, order=order, setup=setup)
     if xstep not in ("gauss_seidel", "gauss_seidel_unbounded"):
         raise ValueError(f"unknown xstep {xstep!r}")
     c = _lib.f64(c)

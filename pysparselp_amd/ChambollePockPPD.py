@@ -142,6 +142,101 @@ class CPState:
         return ms
 
 
+def device_cp(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0=None, alpha=1, theta=1, order=ORDER_AUTO, remove_fixed=False):
+    """The Chambolle-Pock state of the LP as ``chambolle_pock_ppd`` receives it, set up on the device (``setup="device"``):
+    ``[A_eq; A_ineq]`` is stacked on the device (``DeviceMatrix.from_blocks``, or row chunks when it would not fit,
+    ``host_setup.upload``) and ``DeviceCP`` does the one-sided stacking (``gather_rows``) and, with ``remove_fixed``, the
+    removal of fixed variables of ``SparseLP.solve`` (SparseLP.py:1244-1248).  Under a communicator this rank's rows only.
+    Returns ``(state, free, shift)``: ``state.x_reduced()`` is the iterate over the free variables."""
+    from . import host_setup
+    from .scale import DeviceCP, one_sided_rows
+
+    c, lb, ub = _lib.f64(c), _lib.f64(lb), _lib.f64(ub)
+    n = c.size
+    (e0, e1), (i0, i1) = host_setup.local_blocks(a_eq, a_ineq)
+    eq, ineq = host_setup.rows_of(a_eq, e0, e1), host_setup.rows_of(a_ineq, i0, i1)
+    m_eq, m_in = e1 - e0, i1 - i0
+    # the stacked right-hand sides: [b_eq; b_upper] and [-inf; b_lower] (None bounds: +inf / -inf)
+    part = lambda v, r0, r1, fill, k: np.full(k, fill) if v is None else _lib.f64(v)[r0:r1]  # noqa: E731
+    bu = np.concatenate((part(beq, e0, e1, 0.0, m_eq), part(b_upper, i0, i1, np.inf, m_in)))
+    bl = None if b_lower is None else np.concatenate((np.full(m_eq, -np.inf), _lib.f64(b_lower)[i0:i1]))
+    entries = host_setup.chunk_entries(host_setup.nnz_of(eq, ineq), m_eq + m_in, n)
+    free = (ub > lb) if remove_fixed else np.ones(n, dtype=bool)
+    shift = np.where(free, 0.0, lb)
+    if entries is None:
+        mat, _ = host_setup.upload(eq, ineq, n)
+        try:
+            state = DeviceCP(mat, bu, c, lb, ub, alpha=alpha, theta=theta, order=order, m_eq=m_eq, b_lower=bl, remove_fixed=remove_fixed,
+                             x0=x0)
+        except BaseException:
+            mat.close()
+            raise
+        if state.a is mat:
+            state._owned = mat
+        else:
+            mat.close()   # the solver works on a derived copy (fixed variables removed, one-sided stacking)
+        return state, free, shift
+    # chunked: the one-sided stacking needs row gathers, which a chunked matrix (no CSR) cannot serve
+    if bl is not None and one_sided_rows(m_eq + m_in, m_eq, bl, bu) is not None:
+        raise ValueError("this LP needs a chunked matrix on one GPU, and Chambolle-Pock with lower-bounded inequality rows needs the "
+                         f"one-sided stacking (gather_rows), which a chunked matrix cannot serve; {host_setup.MULTI_GPU}")
+    keep = None if free.all() else free
+    mat, a_shift = host_setup.upload(eq, ineq, n, entries, keep=keep, shift=None if keep is None else shift)
+    try:
+        if keep is not None:  # the fixed variables went chunk by chunk (remove_fixed_variables, SparseLP.py:632-674)
+            bu = bu - a_shift
+            c, lb, ub = c[free], lb[free], ub[free]
+            x0 = None if x0 is None else _lib.f64(x0)[free]
+        state = DeviceCP(mat, bu, c, lb, ub, alpha=alpha, theta=theta, order=order, m_eq=m_eq, x0=x0)
+    except BaseException:
+        mat.close()
+        raise
+    state._owned = mat
+    return state, free, shift
+
+
+def _cp_loop(state, c, n, has_ineq, nb_max_iter, nb_iter_plot, callback_func, max_time, start, x_of):
+    """The reporting loop of chambolle_pock_ppd (:195-343) over a solver state; ``x_of(state)`` is its iterate.
+    Returns ``(x, best_integer_solution)``."""
+    best_integer_solution_energy = np.inf
+    best_integer_solution = None
+    niter = 0
+    while niter < nb_max_iter:
+        if niter % nb_iter_plot == 0:
+            state.primal_step()
+            elapsed = time.perf_counter() - start
+            if (max_time is not None) and collective_elapsed(elapsed) > max_time:  # the same decision on every rank
+                break
+            energy1, energy2, max_violated_equality, max_violated_inequality, max_eq_at_x = state.report()[:5]
+            if not has_ineq:
+                max_violated_inequality = 0  # the reference dereferences a_ineq here (:283) and fails
+            x = None
+            if max_eq_at_x == 0 and max_violated_inequality <= 0:  # :284-291 with force_integer=False
+                x = x_of(state)
+                energy_rounded = c.dot(x)
+                if energy_rounded < best_integer_solution_energy:
+                    best_integer_solution_energy = energy_rounded
+                    best_integer_solution = x
+            if callback_func is not None:
+                if x is None:
+                    x = x_of(state)
+                callback_func(niter, x, energy1, energy2, elapsed, max_violated_equality, max_violated_inequality)
+            state.dual_step()
+            niter += 1
+        else:
+            k = min(nb_iter_plot - niter % nb_iter_plot, nb_max_iter - niter)
+            state.iterate(k)
+            niter += k
+    return x_of(state), best_integer_solution
+
+
+def close_device_cp(state):
+    state.close()
+    if getattr(state, "_owned", None) is not None:
+        state._owned.close()
+        state._owned = None
+
+
 def chambolle_pock_ppd(
     c,
     a_eq,
@@ -161,6 +256,7 @@ def chambolle_pock_ppd(
     force_integer=False,
     nb_iter_plot=10,
     order=ORDER_AUTO,
+    setup="auto",
 ):
     """minimise c.x  s.t.  a_eq x = beq,  b_lower <= a_ineq x <= b_upper,  lb <= x <= ub.
 
@@ -168,6 +264,10 @@ def chambolle_pock_ppd(
     include/slp_hip.h; the default reproduces the reference's iterates bit for
     bit while rows are short (mean <= 16 stored entries) and switches to
     wavefront-parallel sums for long rows.
+    ``setup`` (extension): ``"host"`` stacks ``[A_eq; K_ineq]`` on the host and
+    uploads it (reference :74-88,145-233); ``"device"`` uploads the two blocks
+    as they are and stacks them on the device (``device_cp``); ``"auto"`` takes
+    the device at ``SparseLP.DEVICE_SETUP_ENTRIES`` stored entries or more.
     """
     if save_problem or force_integer:
         # debugging pickle / rounding heuristic of the reference: outside the accelerated path (SURVEY.md section 2, #12)
@@ -189,43 +289,25 @@ def chambolle_pock_ppd(
     for a in (a_eq, a_ineq):
         if a is not None:
             assert a.shape[1] == n
+    from . import host_setup
+
+    if host_setup.choose(setup, host_setup.nnz_of(a_eq, a_ineq)) == "device":
+        state, _, _ = device_cp(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, alpha, theta, order)
+        try:
+            x, best_integer_solution = _cp_loop(state, c, n, a_ineq is not None, nb_max_iter, nb_iter_plot, callback_func, max_time,
+                                                start, lambda st: st.x_reduced())
+        finally:
+            close_device_cp(state)
+        return x, best_integer_solution
     ineq, b_ineq = (None, None)
     if a_ineq is not None:
         ineq, b_ineq = one_sided_system(a_ineq, b_lower, b_upper)
         assert b_ineq.size == ineq[3]
 
     state = CPState(c, a_eq, beq, ineq, b_ineq, lb, ub, x0, alpha, theta, order)
-    best_integer_solution_energy = np.inf
-    best_integer_solution = None
     try:
-        niter = 0
-        while niter < nb_max_iter:
-            if niter % nb_iter_plot == 0:
-                state.primal_step()
-                elapsed = time.perf_counter() - start
-                if (max_time is not None) and collective_elapsed(elapsed) > max_time:  # the same decision on every rank
-                    break
-                energy1, energy2, max_violated_equality, max_violated_inequality, max_eq_at_x = state.report()[:5]
-                if a_ineq is None:
-                    max_violated_inequality = 0  # the reference dereferences a_ineq here (:283) and fails
-                x = None
-                if max_eq_at_x == 0 and max_violated_inequality <= 0:  # :284-291 with force_integer=False
-                    x = state.x()
-                    energy_rounded = c.dot(x)
-                    if energy_rounded < best_integer_solution_energy:
-                        best_integer_solution_energy = energy_rounded
-                        best_integer_solution = x
-                if callback_func is not None:
-                    if x is None:
-                        x = state.x()
-                    callback_func(niter, x, energy1, energy2, elapsed, max_violated_equality, max_violated_inequality)
-                state.dual_step()
-                niter += 1
-            else:
-                k = min(nb_iter_plot - niter % nb_iter_plot, nb_max_iter - niter)
-                state.iterate(k)
-                niter += k
-        x = state.x()
+        x, best_integer_solution = _cp_loop(state, c, n, a_ineq is not None, nb_max_iter, nb_iter_plot, callback_func, max_time, start,
+                                            lambda st: st.x())
     finally:
         state.close()
     if best_integer_solution is not None:

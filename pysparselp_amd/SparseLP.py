@@ -75,6 +75,9 @@ def crd_matrix(cols, vals):
 
 
 ADMM_AUTO_M_ENTRIES = 2.0e8  # solve(method="admm", xstep="auto"): above this estimate of nnz(M) the matrix-free x-step is taken
+# setup="auto" (solve with "chambolle_pock_ppd" or the matrix-free "admm", chambolle_pock_ppd, lp_admm_cg): from this many stored
+# constraint entries on, the LP is set up on the device instead of by the reference's host transforms
+DEVICE_SETUP_ENTRIES = 1.0e7
 
 
 class SparseLP:
@@ -354,6 +357,7 @@ class SparseLP:
         ground_truth_indices=None,
         order=ORDER_AUTO,
         xstep="gauss_seidel",
+        setup="auto",
     ):
         """Run a first-order solver on the GPU; returns ``(x, elapsed)`` or ``x``.
 
@@ -364,6 +368,11 @@ class SparseLP:
         (1000 entries per row: ``M`` is dense) and the one that shards over several GPUs -- and ``"auto"`` picks ``"cg"``
         when the standard-form rows promise more than ``ADMM_AUTO_M_ENTRIES`` (2e8) entries in ``M`` (sum of squared row
         lengths) or a communicator is active (the sequential sweep does not partition), else ``"gauss_seidel"``.
+
+        ``setup`` (extension) for ``"chambolle_pock_ppd"`` and the matrix-free ``"admm"``: ``"host"`` prepares the solver as the
+        reference does (for Chambolle-Pock: ``copy.deepcopy`` and ``remove_fixed_variables`` on the host, then the one-sided
+        stacking, SparseLP.py:1244-1248), ``"device"`` uploads the constraint blocks as they are and does all of it on the device,
+        ``"auto"`` takes the device from ``DEVICE_SETUP_ENTRIES`` (1e7) stored entries on.  Same ``x`` and curves either way.
 
         Under a communicator (``parallel.init_comm_from_env`` in every rank of a ``torch.distributed.run`` / ``mpirun``
         launch) every rank calls ``solve`` on the same LP: ``"chambolle_pock_ppd"`` and ``"admm"`` with ``xstep="cg"`` hand
@@ -417,7 +426,7 @@ class SparseLP:
                 xstep = "cg" if (rows_sq > ADMM_AUTO_M_ENTRIES or comm_world()[0] > 1) else "gauss_seidel"
             x = lp_admm(self.costsvector, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds,
                         self.upper_bounds, nb_iter=nb_iter, x0=x0, callback_func=record, max_time=max_time,
-                        nb_iter_plot=nb_iter_plot, order=order, xstep=xstep)
+                        nb_iter_plot=nb_iter_plot, order=order, xstep=xstep, setup=setup)
         elif method == "admm_blocks":  # reference :1210-1225
             from .ADMMBlocks import lp_admm_block_decomposition
 
@@ -425,8 +434,16 @@ class SparseLP:
                                             self.upper_bounds, nb_iter=nb_iter, nb_iter_plot=nb_iter_plot, x0=x0,
                                             callback_func=record, max_time=max_time)
         else:  # chambolle_pock_ppd: fixed variables are eliminated first (reference :1244-1248)
-            reduced = copy.deepcopy(self)
-            free, shift = reduced.remove_fixed_variables()
+            from . import host_setup
+            from .ChambollePockPPD import _cp_loop, close_device_cp, device_cp
+
+            device = (a_eq is not None or a_ineq is not None) and host_setup.choose(setup, host_setup.nnz_of(a_eq, a_ineq)) == "device"
+            if device:  # no deep copy, no host remove_fixed_variables: the fixed variables are dropped on the device
+                state, free, shift = device_cp(self.costsvector, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds,
+                                               self.upper_bounds, x0=None, alpha=1, theta=1, order=order, remove_fixed=True)
+            else:
+                reduced = copy.deepcopy(self)
+                free, shift = reduced.remove_fixed_variables()
             free_ids = np.nonzero(free)[0]
 
             def expand(sol):
@@ -438,11 +455,19 @@ class SparseLP:
             def record_reduced(niter, solution, *rest):
                 record(niter, expand(solution), *rest)
 
-            x, _ = chambolle_pock_ppd(reduced.costsvector, reduced.a_equalities, reduced.b_equalities,
-                                      reduced.a_inequalities, reduced.b_lower, reduced.b_upper, reduced.lower_bounds,
-                                      reduced.upper_bounds, x0=None, alpha=1, theta=1, nb_max_iter=nb_iter,
-                                      callback_func=record_reduced, max_time=max_time, nb_iter_plot=nb_iter_plot,
-                                      order=order)
+            if device:
+                # (the iterate over the free variables goes through expand: DeviceCP.x() puts the fixed ones at +shift)
+                try:
+                    x, _ = _cp_loop(state, self.costsvector[free], state.n, a_ineq is not None, nb_iter, nb_iter_plot, record_reduced,
+                                    max_time, start, lambda st: st.x_reduced())
+                finally:
+                    close_device_cp(state)
+            else:
+                x, _ = chambolle_pock_ppd(reduced.costsvector, reduced.a_equalities, reduced.b_equalities,
+                                          reduced.a_inequalities, reduced.b_lower, reduced.b_upper, reduced.lower_bounds,
+                                          reduced.upper_bounds, x0=None, alpha=1, theta=1, nb_max_iter=nb_iter,
+                                          callback_func=record_reduced, max_time=max_time, nb_iter_plot=nb_iter_plot,
+                                          order=order, setup="host")
             x = expand(x)
         elapsed = time.perf_counter() - start
         return (x, elapsed) if get_timing else x

@@ -39,6 +39,7 @@ _SIGNATURES = {
     "slp_timer_start": (c_int, []),
     "slp_timer_stop": (c_int, [c_vp]),
     "slp_matrix_create": (c_vp, [c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "slp_matrix_create_stacked": (c_vp, [c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "slp_matrix_destroy": (None, [c_vp]),
     "slp_matrix_nnz": (c_i64, [c_vp]),
     "slp_matrix_spmv": (c_int, [c_vp, c_vp, c_vp, c_int]),
@@ -115,6 +116,9 @@ _SIGNATURES = {
     "slp_blocks_cg_steps": (c_i64, [c_vp]),
     "slp_blocks_get_xp": (c_int, [c_vp, c_vp, c_i64]),
     "slp_admm_cg_create_on_two_sided": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),
+    "slp_admm_cg_create_on_lp": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int, c_int]),
+    "slp_admm_cg_create_lp": (c_vp, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                     c_dbl, c_dbl, c_int, c_int]),
     "slp_admm_cg_destroy": (None, [c_vp]),
     "slp_admm_cg_set_reuse": (c_int, [c_vp, c_int]),
     "slp_admm_cg_iterate": (c_int, [c_vp, c_i64]),

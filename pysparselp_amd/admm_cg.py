@@ -71,6 +71,65 @@ class ADMMCGState(_CGBase):
             _lib.ptr(lb), _lib.ptr(ub), _lib.ptr(x0), float(gamma_eq), float(gamma_ineq), int(order)))
 
 
+class ADMMCGLPState(_CGBase):
+    """The solver from the LP as ``lp_admm_cg`` receives it, set up on the device (``setup="device"``): the two constraint blocks
+    are stacked on the device (``slp_admm_cg_create_lp``) -- or built from row chunks when they would not fit it
+    (``host_setup.chunk_entries``) -- and row-normalised there, slack column implicit.  Under a communicator this rank's rows only."""
+
+    def __init__(self, c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, use_preconditioning=True,
+                 order=ORDER_AUTO):
+        from . import host_setup
+        from .tools import CsrArrays
+
+        self._l = _lib.lib()
+        self._mat = None
+        if a_eq is not None and a_eq.shape[0] == 0:
+            a_eq, beq = None, None
+        if a_ineq is None:  # what the reference does on this input (tools.py:92-127)
+            raise UnboundLocalError("local variable 'a_eq2' referenced before assignment (no inequality constraints)")
+        c, lb, ub = _lib.f64(c), _lib.f64(lb), _lib.f64(ub)
+        n = c.size
+        (e0, e1), (i0, i1) = host_setup.local_blocks(a_eq, a_ineq)
+        eq, ineq = host_setup.rows_of(a_eq, e0, e1), host_setup.rows_of(a_ineq, i0, i1)
+        m_eq, m_in = e1 - e0, i1 - i0
+        self.N, self.m = n + m_eq + m_in, m_eq + m_in
+        opt = lambda v, r0, r1: None if v is None else np.ascontiguousarray(_lib.f64(v)[r0:r1])  # noqa: E731
+        beq, b_lower, b_upper = opt(beq, e0, e1), opt(b_lower, i0, i1), opt(b_upper, i0, i1)
+        x0 = None if x0 is None else _lib.f64(x0)
+        entries = host_setup.chunk_entries(host_setup.nnz_of(eq, ineq), self.m, n)
+        if entries is None:
+            arr = lambda blk: (None, None, None) if blk is None else (_lib.ptr(blk.indptr), _lib.ptr(blk.indices), _lib.ptr(blk.data))  # noqa: E731
+            if ineq is None:
+                ineq = CsrArrays(np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0), (0, n))
+            self._h = _lib.check_handle(self._l.slp_admm_cg_create_lp(
+                n, m_eq, *arr(eq), _lib.ptr(beq), m_in, *arr(ineq), _lib.ptr(b_lower), _lib.ptr(b_upper), _lib.ptr(c), _lib.ptr(lb),
+                _lib.ptr(ub), _lib.ptr(x0), float(gamma_eq), float(gamma_ineq), int(bool(use_preconditioning)), int(order)))
+            return
+        # chunked: the deferred row scaling over value-dictionary copies is the only form (no CSR is held to scale in place)
+        if not host_setup.few_distinct_values((eq, ineq)):
+            raise ValueError("this LP needs a chunked matrix on one GPU, and the matrix-free ADMM runs on a chunked matrix only with "
+                             f"value-dictionary copies (at most {host_setup.DICT_MAX} distinct stored values); {host_setup.MULTI_GPU}")
+        self._mat, _ = host_setup.upload(eq, ineq, n, entries)
+        bu = np.concatenate((np.zeros(0) if beq is None else beq, np.full(m_in, np.inf) if b_upper is None else b_upper))
+        bl = None if b_lower is None else np.concatenate((np.full(m_eq, -np.inf), b_lower))
+        try:
+            self._h = _lib.check_handle(self._l.slp_admm_cg_create_on_lp(
+                self._mat._h, m_eq, _lib.ptr(bl), _lib.ptr(bu), _lib.ptr(c), _lib.ptr(lb), _lib.ptr(ub), _lib.ptr(x0), float(gamma_eq),
+                float(gamma_ineq), int(bool(use_preconditioning)), int(order)))
+        except BaseException:
+            self._mat.close()
+            self._mat = None
+            raise
+
+    def close(self):
+        super().close()
+        if getattr(self, "_mat", None) is not None:
+            self._mat.close()
+            self._mat = None
+
+    __del__ = close
+
+
 class DeviceADMM(_CGBase):
     """LP over a DeviceMatrix: the first ``m_eq`` rows are equalities ``a_i x = b_i``, the others inequalities
     ``a_i x <= b_i``.  Setup transforms run on the device and scale the matrix IN PLACE (the DeviceMatrix then
@@ -115,31 +174,39 @@ class DeviceADMM(_CGBase):
 
 def lp_admm_cg(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0=None, gamma_eq=2, gamma_ineq=3, nb_iter=100,
                callback_func=None, max_time=None, use_preconditioning=True, nb_iter_plot=10, order=ORDER_AUTO,
-               reuse=False):
-    """``lp_admm`` of the reference with its ``use_cg`` flags; same signature, callback and return value."""
-    c = _lib.f64(c)
-    n = c.size
-    if x0 is None:
-        x0 = np.zeros(n)
-    if a_eq is not None:
-        a_eq, beq = precondition_constraints(a_eq, beq, alpha=2)
-    if a_ineq is not None:
-        a_ineq, b_lower, b_upper = precondition_constraints(a_ineq, b_lower, b_upper, alpha=2)
-    c2, a, b, lb2, ub2, x_init = convert_to_standard_form_with_bounds(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0)
-    if use_preconditioning:
-        a, b = precondition_constraints(a, b, alpha=2)
-    # under a communicator (parallel.init_comm_from_env): every rank ran the (cheap, deterministic) transforms above on the
-    # whole LP and hands over only its block of the standard-form rows; the N unknowns are replicated
+               reuse=False, setup="auto"):
+    """``lp_admm`` of the reference with its ``use_cg`` flags; same signature, callback and return value.
+
+    ``setup`` (extension): ``"host"`` runs the reference's set-up chain (ADMM.py:73-101) in numpy and uploads the explicit
+    standard form; ``"device"`` uploads the two blocks and runs it on the device (``ADMMCGLPState``); ``"auto"`` takes the
+    device at ``SparseLP.DEVICE_SETUP_ENTRIES`` stored entries or more.  Both give the same iterates up to fp64 rounding."""
+    from . import host_setup
     from .parallel import collective_elapsed, local_rows
 
-    r0, r1, _ = local_rows(a.indptr)
-    if (r0, r1) != (0, a.shape[0]):
-        from .tools import CsrArrays
+    c = _lib.f64(c)
+    n = c.size
+    if host_setup.choose(setup, host_setup.nnz_of(a_eq, a_ineq)) == "device":
+        state = ADMMCGLPState(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, use_preconditioning, order)
+    else:
+        if x0 is None:
+            x0 = np.zeros(n)
+        if a_eq is not None:
+            a_eq, beq = precondition_constraints(a_eq, beq, alpha=2)
+        if a_ineq is not None:
+            a_ineq, b_lower, b_upper = precondition_constraints(a_ineq, b_lower, b_upper, alpha=2)
+        c2, a, b, lb2, ub2, x_init = convert_to_standard_form_with_bounds(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0)
+        if use_preconditioning:
+            a, b = precondition_constraints(a, b, alpha=2)
+        # under a communicator (parallel.init_comm_from_env): every rank ran the (cheap, deterministic) transforms above on the
+        # whole LP and hands over only its block of the standard-form rows; the N unknowns are replicated
+        r0, r1, _ = local_rows(a.indptr)
+        if (r0, r1) != (0, a.shape[0]):
+            from .tools import CsrArrays
 
-        k0, k1 = int(a.indptr[r0]), int(a.indptr[r1])
-        a = CsrArrays(np.asarray(a.indptr[r0:r1 + 1]) - k0, a.indices[k0:k1], a.data[k0:k1], (r1 - r0, a.shape[1]))
-        b = np.ascontiguousarray(b[r0:r1])
-    state = ADMMCGState(a, b, c2, lb2, ub2, x_init, gamma_eq, gamma_ineq, order)
+            k0, k1 = int(a.indptr[r0]), int(a.indptr[r1])
+            a = CsrArrays(np.asarray(a.indptr[r0:r1 + 1]) - k0, a.indices[k0:k1], a.data[k0:k1], (r1 - r0, a.shape[1]))
+            b = np.ascontiguousarray(b[r0:r1])
+        state = ADMMCGState(a, b, c2, lb2, ub2, x_init, gamma_eq, gamma_ineq, order)
     state.set_reuse(reuse)
     try:
         start = time.perf_counter()

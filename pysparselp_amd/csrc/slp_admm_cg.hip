@@ -425,9 +425,10 @@ __global__ __launch_bounds__(kBlock) void k_cg_report_final(int nr, const double
 // Rows i < m_eq are equalities [A_eq' 0] (tools.py:96-107): no slack entry (sc_i = 0, no "+ 1"), and their
 // right-hand side b_eq is scaled in both passes; inequality rows end with right-hand side 0 and the scaled
 // upper bound bu_i on their slack variable.
+// passes = 1 (use_preconditioning=False, ADMM.py:90-91): pass 1 only; the slack entry stays -1.
 template <int L>
 __global__ __launch_bounds__(kBlock) void k_cg_scale_rows(i64 m, i64 m_eq, const i64 *__restrict__ ptr, double *__restrict__ val, int pass,
-                                                          double *__restrict__ bu, double *__restrict__ sc, double *__restrict__ bl) {
+                                                          int passes, double *__restrict__ bu, double *__restrict__ sc, double *__restrict__ bl) {
     const int sub = threadIdx.x & (L - 1);
     const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / L;
     const i64 ngroups = (i64)gridDim.x * kBlock / L;
@@ -442,8 +443,11 @@ __global__ __launch_bounds__(kBlock) void k_cg_scale_rows(i64 m, i64 m_eq, const
         const double inv = 1.0 / nrm;
         for (i64 k = s + sub; k < e; k += L) val[k] = inv * val[k];
         if (sub == 0) {
-            if (pass == 1) { bu[i] = inv * bu[i]; if (bl && i >= m_eq) bl[i] = inv * bl[i]; }  // b_lower is scaled like b_upper (tools.py:286-288)
-            else if (i >= m_eq) sc[i] = inv * -1.0;
+            if (pass == 1) {
+                bu[i] = inv * bu[i];
+                if (bl && i >= m_eq) bl[i] = inv * bl[i];  // b_lower is scaled like b_upper (tools.py:286-288)
+                if (passes == 1) sc[i] = i >= m_eq ? -1.0 : 0.0;
+            } else if (i >= m_eq) sc[i] = inv * -1.0;
             else { sc[i] = 0.0; bu[i] = inv * bu[i]; }
         }
     }
@@ -481,20 +485,39 @@ __global__ __launch_bounds__(kBlock) void k_cg_row_sq(i64 m, const i64 *__restri
     }
 }
 
-__global__ void k_cg_row_scales_from(i64 m, i64 m_eq, const double *__restrict__ sq, double *__restrict__ bu, double *__restrict__ sc,
-                                     double *__restrict__ rs, double *__restrict__ bl) {
+// passes = 1: inv2_i = 1 (no second scaling: every product by it is exact).  ax0 != NULL: xs_i = inv1_i * (A0 x0)_i, the slack part
+// of the warm start (tools.py:127 over the once-scaled inequality rows; 0 on equality rows).
+__global__ void k_cg_row_scales_from(i64 m, i64 m_eq, int passes, const double *__restrict__ sq, double *__restrict__ bu,
+                                     double *__restrict__ sc, double *__restrict__ rs, double *__restrict__ bl,
+                                     const double *__restrict__ ax0, double *__restrict__ xs) {
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (i64)gridDim.x * blockDim.x) {
         double nrm = sqrt(sq[2 * i]);
         if (nrm == 0.0) nrm = 1.0;
         const double inv1 = 1.0 / nrm;
-        double acc = sq[2 * i + 1];
-        if (i >= m_eq) acc = acc + 1.0;
-        nrm = sqrt(acc);
-        if (nrm == 0.0) nrm = 1.0;
-        const double inv2 = 1.0 / nrm;
+        double inv2 = 1.0;
+        if (passes == 2) {
+            double acc = sq[2 * i + 1];
+            if (i >= m_eq) acc = acc + 1.0;
+            nrm = sqrt(acc);
+            if (nrm == 0.0) nrm = 1.0;
+            inv2 = 1.0 / nrm;
+        }
         rs[i] = inv2 * inv1;
         if (i >= m_eq) { sc[i] = inv2 * -1.0; bu[i] = inv1 * bu[i]; if (bl) bl[i] = inv1 * bl[i]; }
         else { sc[i] = 0.0; bu[i] = inv2 * (inv1 * bu[i]); }
+        if (ax0) xs[i] = i >= m_eq ? inv1 * ax0[i] : 0.0;
+    }
+}
+
+// xs_i = a_i x0 over the stored entries in storage order, one lane per row (csr_matvec's sequential sum; 0 on equality rows):
+// the slack part of the warm start, taken between scaling pass 1 and pass 2 (tools.py:127)
+__global__ void k_cg_rows_x0(i64 m, i64 m_eq, const i64 *__restrict__ ptr, const i32 *__restrict__ idx, const double *__restrict__ val,
+                             const double *__restrict__ x0, double *__restrict__ xs) {
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (i64)gridDim.x * blockDim.x) {
+        double acc = 0.0;
+        if (i >= m_eq)
+            for (i64 k = ptr[i]; k < ptr[i + 1]; ++k) acc += val[k] * x0[idx[k]];
+        xs[i] = acc;
     }
 }
 
@@ -986,102 +1009,179 @@ slp_admm_cg *slp_admm_cg_create_on_mixed(slp_matrix *a_ineq, int64_t m_eq, const
     return slp_admm_cg_create_on_two_sided(a_ineq, m_eq, nullptr, b_upper, c, lb, ub, gamma_eq, gamma_ineq, order);
 }
 
+}  // extern "C"
+
+namespace slp {
+
+// The implicit-slack set-up of the matrix-free ADMM on a resident matrix (ADMM.py:76-101, tools.py:272-290,88-127): row
+// scalings (pass 2 only with passes = 2, use_preconditioning), standard form [A_eq' 0; A_ineq' -I] with the slack column kept
+// as the vector sc, the right-hand sides and bounds, the warm start x = [x0; A_ineq' x0] (x0 != NULL, A_ineq' = the rows after
+// pass 1) with xp = max(x, 0), and the solver's vectors.  s->a = a, borrowed.  Throws; the caller owns s.
+static void cg_setup_on(slp_admm_cg *s, slp_matrix *a_ineq, i64 m_eq, const double *b_lower, const double *b_upper, const double *c,
+                        const double *lb, const double *ub, const double *x0, double gamma_eq, double gamma_ineq, int passes, int order) {
+    const bool chunked = !a_ineq->chunks.empty();
+    if (!chunked) require_csr(a_ineq, "slp_admm_cg_create_on");  // the row norms are taken over the CSR entries
+    Phase ph("slp_admm_cg_create_on");
+    hipStream_t st = ctx().stream;
+    s->a = a_ineq;
+    s->owns_a = false;
+    CsrDev &a = a_ineq->a;
+    const i64 m = a.nrow, n = a.ncol;
+    s->n_o = n; s->m = m; s->ns = m; s->N = n + m;
+    s->gamma_eq = gamma_eq; s->gamma_ineq = gamma_ineq; s->order = order;
+    DevBuf<double> bu((size_t)m);
+    bu.upload(b_upper, (size_t)m);
+    DevBuf<double> bl;  // optional lower bounds of the inequality rows (entries of equality rows are ignored)
+    if (b_lower) bl.upload(b_lower, (size_t)m);
+    DevBuf<double> x0d, xs;  // warm start: x0 and the slack part A_ineq' x0
+    if (x0) { x0d.upload(x0, (size_t)n); xs.alloc((size_t)m); }
+    s->sc.alloc((size_t)m);
+    // Few distinct stored values and long rows: keep the matrix as it is (value-dictionary strips) and carry
+    // the two row scalings as a vector.  Otherwise: rows scaled in place, twice; the transposed copy is
+    // (re)built from the scaled values.
+    // the in-place normalisation below is not idempotent (pass 2 adds the slack entry's 1)
+    SLP_REQUIRE(!a_ineq->scaled, "slp_admm_cg_create_on: this matrix was already row-normalised in place by an earlier ADMM "
+                                 "setup; scaling it again would solve a different problem -- build the solver on a fresh matrix");
+    bool deferred = false;
+    if (chunked) {
+        // a chunked matrix holds no CSR: only the deferred form exists, from the row sums its chunks kept
+        const StripJds *f0 = fast_format(a_ineq, false), *f1 = fast_format(a_ineq, true);
+        deferred = f0->D > 0 && f1->D > 0;
+        for (const slp_matrix *ch : a_ineq->chunks) deferred = deferred && ch->rowsq.n == 2 * (size_t)ch->a.nrow;
+        SLP_REQUIRE(deferred, "slp_admm_cg_create_on: a chunked matrix runs the matrix-free ADMM on value-dictionary copies only "
+                              "(its rows cannot be scaled in place: no CSR is held)");
+    } else if (m && n && (strip_wanted(a, 2) || strip_wanted(a, 1) || strip_wanted(a, 3) || tall_wanted(a.nrow, a.ncol, a.nnz)) &&
+               matrix_dictionary(a_ineq)) {
+        const StripJds *f0 = fast_format(a_ineq, false), *f1 = fast_format(a_ineq, true);
+        deferred = f0 && f1 && f0->D > 0 && f1->D > 0;
+    }
+    if (deferred) {
+        s->rs.alloc((size_t)m);
+        s->wsw.alloc((size_t)m);
+        s->wsv1.alloc((size_t)m);
+        DevBuf<double> sq(2 * (size_t)m);
+        if (chunked) {
+            for (size_t k = 0; k < a_ineq->chunks.size(); ++k) {
+                const slp_matrix *ch = a_ineq->chunks[k];
+                SLP_HIP(hipMemcpyAsync(sq.p + 2 * a_ineq->chunk_row0[k], ch->rowsq.p, 2 * (size_t)ch->a.nrow * sizeof(double),
+                                       hipMemcpyDeviceToDevice, st));
+            }
+        } else {
+            matrix_row_squares(a, sq.p);
+        }
+        DevBuf<double> ax0;  // A0 x0 over the unscaled matrix's product copy: the warm start's slack part is inv1 o (A0 x0)
+        if (x0 && m) {
+            ax0.alloc((size_t)m);
+            strip_spmv(*fast_format(a_ineq, false), x0d.p, ax0.p);
+        }
+        hipLaunchKernelGGL(k_cg_row_scales_from, dim3(grid_for(m, kBlock)), dim3(kBlock), 0, st, m, (i64)m_eq, passes, sq.p, bu.p, s->sc.p,
+                           s->rs.p, bl.p, ax0.p, xs.p);
+        SLP_HIP(hipGetLastError());
+        SLP_HIP(hipStreamSynchronize(st));
+    } else if (m) {
+        // in place: the matrix then holds the row-normalised values and every derived copy is rebuilt -- refuse when
+        // that would pull the data from under another solver
+        SLP_REQUIRE(a_ineq->borrowers == 0, "slp_admm_cg_create_on: another solver created on this matrix is still alive; the "
+                                            "in-place row normalisation would change the values it iterates on");
+        invalidate_derived(a_ineq);
+        a_ineq->scaled = true;
+        const int lanes = lanes_for(a, SLP_ORDER_TREE);
+        for (int pass = 1; pass <= passes; ++pass) {
+            SLP_DISPATCH_LANES(lanes, hipLaunchKernelGGL((k_cg_scale_rows<L>), dim3(grid_for(m * lanes, kBlock)), dim3(kBlock), 0,
+                                                         st, m, (i64)m_eq, a.ptr.p, a.val.p, pass, passes, bu.p, s->sc.p, bl.p));
+            SLP_HIP(hipGetLastError());
+            if (pass == 1 && x0) {
+                hipLaunchKernelGGL(k_cg_rows_x0, dim3(grid_for(m, kBlock)), dim3(kBlock), 0, st, m, (i64)m_eq, a.ptr.p, a.idx.p, a.val.p,
+                                   x0d.p, xs.p);
+                SLP_HIP(hipGetLastError());
+            }
+        }
+    }
+    if (!deferred) ensure_transposed(a_ineq);
+    // c2 = [c; 0]  lb2 = [lb; -inf]  ub2 = [ub; bu']  b = 0  x0 = 0   (equality rows: b = b_eq'', slack pinned to 0)
+    const size_t N = (size_t)s->N;
+    s->c.alloc(N); s->lb.alloc(N); s->ub.alloc(N); s->x.alloc(N); s->b.alloc((size_t)m);
+    s->c.zero(); s->x.zero(); s->b.zero();
+    SLP_HIP(hipMemcpyAsync(s->c.p, c, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    SLP_HIP(hipMemcpyAsync(s->lb.p, lb, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    SLP_HIP(hipMemcpyAsync(s->ub.p, ub, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    if (x0) {  // x = [x0; A_ineq' x0]
+        if (n) SLP_HIP(hipMemcpyAsync(s->x.p, x0d.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        if (m) SLP_HIP(hipMemcpyAsync(s->x.p + n, xs.p, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    if (m) {
+        hipLaunchKernelGGL(k_cg_split_rows, dim3(grid_for(m, kBlock)), dim3(kBlock), 0, st, m, (i64)m_eq, bu.p, bl.p, s->b.p, s->lb.p + n,
+                           s->ub.p + n);
+        SLP_HIP(hipGetLastError());
+    }
+    SLP_HIP(hipStreamSynchronize(st));
+    cg_alloc_state(s);
+    if (x0) {
+        if (N) hipLaunchKernelGGL(k_cg_max0, dim3(grid_for((i64)N, kBlock)), dim3(kBlock), 0, st, (i64)N, s->x.p, s->xp.p);  // ADMM.py:98
+        SLP_HIP(hipGetLastError());
+    } else {
+        s->xp.zero();  // max(0, 0)
+    }
+    SLP_HIP(hipStreamSynchronize(st));
+}
+
+}  // namespace slp
+
+extern "C" {
+
 slp_admm_cg *slp_admm_cg_create_on_two_sided(slp_matrix *a_ineq, int64_t m_eq, const double *b_lower, const double *b_upper,
                                              const double *c, const double *lb, const double *ub, double gamma_eq, double gamma_ineq,
                                              int order) {
+    return slp_admm_cg_create_on_lp(a_ineq, m_eq, b_lower, b_upper, c, lb, ub, nullptr, gamma_eq, gamma_ineq, 1, order);
+}
+
+slp_admm_cg *slp_admm_cg_create_on_lp(slp_matrix *a, int64_t m_eq, const double *b_lower, const double *b_upper, const double *c,
+                                      const double *lb, const double *ub, const double *x0, double gamma_eq, double gamma_ineq,
+                                      int use_preconditioning, int order) {
     SLP_API_PTR({
-        SLP_REQUIRE(a_ineq && b_upper && c && lb && ub, "slp_admm_cg_create_on: NULL argument");
-        SLP_REQUIRE(m_eq >= 0 && m_eq <= a_ineq->a.nrow, "slp_admm_cg_create_on_mixed: m_eq out of range");
-        const bool chunked = !a_ineq->chunks.empty();
-        if (!chunked) require_csr(a_ineq, "slp_admm_cg_create_on");  // the row norms are taken over the CSR entries
-        Phase ph("slp_admm_cg_create_on");
+        SLP_REQUIRE(a && b_upper && c && lb && ub, "slp_admm_cg_create_on: NULL argument");
+        SLP_REQUIRE(m_eq >= 0 && m_eq <= a->a.nrow, "slp_admm_cg_create_on_mixed: m_eq out of range");
         auto *s = new slp_admm_cg();
         try {
-            hipStream_t st = ctx().stream;
-            s->a = a_ineq;
-            s->owns_a = false;
-            CsrDev &a = a_ineq->a;
-            const i64 m = a.nrow, n = a.ncol;
-            s->n_o = n; s->m = m; s->ns = m; s->N = n + m;
-            s->gamma_eq = gamma_eq; s->gamma_ineq = gamma_ineq; s->order = order;
-            DevBuf<double> bu((size_t)m);
-            bu.upload(b_upper, (size_t)m);
-            DevBuf<double> bl;  // optional lower bounds of the inequality rows (entries of equality rows are ignored)
-            if (b_lower) bl.upload(b_lower, (size_t)m);
-            s->sc.alloc((size_t)m);
-            // Few distinct stored values and long rows: keep the matrix as it is (value-dictionary strips) and carry
-            // the two row scalings as a vector.  Otherwise: rows scaled in place, twice; the transposed copy is
-            // (re)built from the scaled values.
-            // the in-place normalisation below is not idempotent (pass 2 adds the slack entry's 1)
-            SLP_REQUIRE(!a_ineq->scaled, "slp_admm_cg_create_on: this matrix was already row-normalised in place by an earlier ADMM "
-                                         "setup; scaling it again would solve a different problem -- build the solver on a fresh matrix");
-            bool deferred = false;
-            if (chunked) {
-                // a chunked matrix holds no CSR: only the deferred form exists, from the row sums its chunks kept
-                const StripJds *f0 = fast_format(a_ineq, false), *f1 = fast_format(a_ineq, true);
-                deferred = f0->D > 0 && f1->D > 0;
-                for (const slp_matrix *ch : a_ineq->chunks) deferred = deferred && ch->rowsq.n == 2 * (size_t)ch->a.nrow;
-                SLP_REQUIRE(deferred, "slp_admm_cg_create_on: a chunked matrix runs the matrix-free ADMM on value-dictionary copies only "
-                                      "(its rows cannot be scaled in place: no CSR is held)");
-            } else if (m && n && (strip_wanted(a, 2) || strip_wanted(a, 1) || strip_wanted(a, 3) || tall_wanted(a.nrow, a.ncol, a.nnz)) &&
-                       matrix_dictionary(a_ineq)) {
-                const StripJds *f0 = fast_format(a_ineq, false), *f1 = fast_format(a_ineq, true);
-                deferred = f0 && f1 && f0->D > 0 && f1->D > 0;
-            }
-            if (deferred) {
-                s->rs.alloc((size_t)m);
-                s->wsw.alloc((size_t)m);
-                s->wsv1.alloc((size_t)m);
-                DevBuf<double> sq(2 * (size_t)m);
-                if (chunked) {
-                    for (size_t k = 0; k < a_ineq->chunks.size(); ++k) {
-                        const slp_matrix *ch = a_ineq->chunks[k];
-                        SLP_HIP(hipMemcpyAsync(sq.p + 2 * a_ineq->chunk_row0[k], ch->rowsq.p, 2 * (size_t)ch->a.nrow * sizeof(double),
-                                               hipMemcpyDeviceToDevice, st));
-                    }
-                } else {
-                    matrix_row_squares(a, sq.p);
-                }
-                hipLaunchKernelGGL(k_cg_row_scales_from, dim3(grid_for(m, kBlock)), dim3(kBlock), 0, st, m, (i64)m_eq, sq.p, bu.p, s->sc.p,
-                                   s->rs.p, bl.p);
-                SLP_HIP(hipGetLastError());
-                SLP_HIP(hipStreamSynchronize(st));
-            } else if (m) {
-                // in place: the matrix then holds the row-normalised values and every derived copy is rebuilt -- refuse when
-                // that would pull the data from under another solver
-                SLP_REQUIRE(a_ineq->borrowers == 0, "slp_admm_cg_create_on: another solver created on this matrix is still alive; the "
-                                                    "in-place row normalisation would change the values it iterates on");
-                invalidate_derived(a_ineq);
-                a_ineq->scaled = true;
-                const int lanes = lanes_for(a, SLP_ORDER_TREE);
-                for (int pass = 1; pass <= 2; ++pass) {
-                    SLP_DISPATCH_LANES(lanes, hipLaunchKernelGGL((k_cg_scale_rows<L>), dim3(grid_for(m * lanes, kBlock)), dim3(kBlock), 0,
-                                                                 st, m, (i64)m_eq, a.ptr.p, a.val.p, pass, bu.p, s->sc.p, bl.p));
-                    SLP_HIP(hipGetLastError());
-                }
-            }
-            if (!deferred) ensure_transposed(a_ineq);
-            // c2 = [c; 0]  lb2 = [lb; -inf]  ub2 = [ub; bu']  b = 0  x0 = 0   (equality rows: b = b_eq'', slack pinned to 0)
-            const size_t N = (size_t)s->N;
-            s->c.alloc(N); s->lb.alloc(N); s->ub.alloc(N); s->x.alloc(N); s->b.alloc((size_t)m);
-            s->c.zero(); s->x.zero(); s->b.zero();
-            SLP_HIP(hipMemcpyAsync(s->c.p, c, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-            SLP_HIP(hipMemcpyAsync(s->lb.p, lb, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-            SLP_HIP(hipMemcpyAsync(s->ub.p, ub, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-            if (m) {
-                hipLaunchKernelGGL(k_cg_split_rows, dim3(grid_for(m, kBlock)), dim3(kBlock), 0, st, m, (i64)m_eq, bu.p, bl.p, s->b.p, s->lb.p + n,
-                                   s->ub.p + n);
-                SLP_HIP(hipGetLastError());
-            }
-            SLP_HIP(hipStreamSynchronize(st));
-            cg_alloc_state(s);
-            s->xp.zero();  // max(0, 0)
-            SLP_HIP(hipStreamSynchronize(st));
+            cg_setup_on(s, a, m_eq, b_lower, b_upper, c, lb, ub, x0, gamma_eq, gamma_ineq, use_preconditioning ? 2 : 1, order);
         } catch (...) {
             delete s;
             throw;
         }
-        ++a_ineq->borrowers;
+        ++a->borrowers;
+        return s;
+    })
+}
+
+slp_admm_cg *slp_admm_cg_create_lp(int64_t n, int64_t m_eq, const int64_t *eq_indptr, const int32_t *eq_indices, const double *eq_data,
+                                   const double *b_eq, int64_t m_ineq, const int64_t *in_indptr, const int32_t *in_indices,
+                                   const double *in_data, const double *b_lower, const double *b_upper, const double *c, const double *lb,
+                                   const double *ub, const double *x0, double gamma_eq, double gamma_ineq, int use_preconditioning,
+                                   int order) {
+    SLP_API_PTR({
+        SLP_REQUIRE(n >= 0 && m_eq >= 0 && m_ineq >= 0 && in_indptr && c && lb && ub, "slp_admm_cg_create_lp: bad arguments");
+        SLP_REQUIRE(m_eq == 0 || (eq_indptr && b_eq), "slp_admm_cg_create_lp: equality rows without their arrays");
+        const i64 m = m_eq + m_ineq;
+        // b = [b_eq; b_upper] and [-inf; b_lower] over the stacked rows (NULL bounds: +inf / -inf, tools.py:114-121)
+        std::vector<double> bu((size_t)m), bl;
+        for (i64 i = 0; i < m_eq; ++i) bu[i] = b_eq[i];
+        for (i64 i = 0; i < m_ineq; ++i) bu[m_eq + i] = b_upper ? b_upper[i] : __builtin_inf();
+        if (b_lower) {
+            bl.assign((size_t)m, -__builtin_inf());
+            for (i64 i = 0; i < m_ineq; ++i) bl[m_eq + i] = b_lower[i];
+        }
+        slp_matrix *a = slp_matrix_create_stacked(n, m_eq, eq_indptr, eq_indices, eq_data, m_ineq, in_indptr, in_indices, in_data);
+        if (!a) throw Error(slp_last_error());
+        auto *s = new slp_admm_cg();
+        try {
+            cg_setup_on(s, a, m_eq, b_lower ? bl.data() : nullptr, bu.data(), c, lb, ub, x0, gamma_eq, gamma_ineq,
+                        use_preconditioning ? 2 : 1, order);
+            s->owns_a = true;
+        } catch (...) {
+            delete s;
+            delete a;
+            throw;
+        }
         return s;
     })
 }

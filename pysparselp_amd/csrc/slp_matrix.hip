@@ -446,25 +446,57 @@ __global__ void k_validate_csr(i64 nrow, i64 ncol, i64 nnz, const i64 *__restric
     if (b) atomicOr(bad, b);
 }
 
-static slp_matrix *matrix_from_host(i64 nrow, i64 ncol, const i64 *indptr, const i32 *indices, const double *data) {
-    SLP_REQUIRE(nrow >= 0 && ncol >= 0 && indptr != nullptr, "slp_matrix_create: bad arguments");
+// rows of the bottom block of a stacked upload: their offsets continue after the top block's entries
+__global__ void k_shift_ptr(i64 count, i64 *__restrict__ ptr, i64 off) {
+    for (i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x; r < count; r += (i64)gridDim.x * blockDim.x) ptr[r] += off;
+}
+
+// [top; bottom] from two host CSR blocks of ncol columns (nrow_b = 0: the top block alone).  Each block is copied as it is
+// into its part of the device arrays; the bottom block's row offsets are shifted by nnz(top) on the device.
+static slp_matrix *matrix_from_host_blocks(i64 nrow, i64 ncol, const i64 *indptr, const i32 *indices, const double *data, i64 nrow_b,
+                                           const i64 *indptr_b, const i32 *indices_b, const double *data_b) {
+    SLP_REQUIRE(nrow >= 0 && nrow_b >= 0 && ncol >= 0 && indptr != nullptr && (nrow_b == 0 || indptr_b != nullptr),
+                "slp_matrix_create: bad arguments");
     SLP_REQUIRE(ncol < (i64)1 << 31, "column count must fit int32");
-    const i64 nnz = indptr[nrow];
-    SLP_REQUIRE(indptr[0] == 0 && nnz >= 0, "slp_matrix_create: indptr must start at 0");
-    SLP_REQUIRE(nnz == 0 || (indices != nullptr && data != nullptr), "slp_matrix_create: NULL indices / data");
+    const i64 nnz_t = indptr[nrow], nnz_b = nrow_b ? indptr_b[nrow_b] : 0;
+    SLP_REQUIRE(indptr[0] == 0 && nnz_t >= 0 && (nrow_b == 0 || (indptr_b[0] == 0 && nnz_b >= 0)), "slp_matrix_create: indptr must start at 0");
+    SLP_REQUIRE(nnz_t == 0 || (indices != nullptr && data != nullptr), "slp_matrix_create: NULL indices / data");
+    SLP_REQUIRE(nnz_b == 0 || (indices_b != nullptr && data_b != nullptr), "slp_matrix_create: NULL indices / data");
+    const i64 nrow_all = nrow + nrow_b, nnz = nnz_t + nnz_b;
     ctx();
     auto *m = new slp_matrix();
     try {
-        m->a.nrow = nrow;
+        m->a.nrow = nrow_all;
         m->a.ncol = ncol;
         m->a.nnz = nnz;
-        m->a.ptr.upload(indptr, (size_t)nrow + 1);
-        m->a.idx.upload(indices, (size_t)nnz);
-        m->a.val.upload(data, (size_t)nnz);
+        if (nrow_b == 0) {
+            m->a.ptr.upload(indptr, (size_t)nrow + 1);
+            m->a.idx.upload(indices, (size_t)nnz);
+            m->a.val.upload(data, (size_t)nnz);
+        } else {
+            hipStream_t st = ctx().stream;
+            m->a.ptr.alloc((size_t)nrow_all + 1);
+            m->a.idx.alloc((size_t)nnz);
+            m->a.val.alloc((size_t)nnz);
+            SLP_HIP(hipMemcpyAsync(m->a.ptr.p, indptr, ((size_t)nrow + 1) * sizeof(i64), hipMemcpyHostToDevice, st));
+            SLP_HIP(hipMemcpyAsync(m->a.ptr.p + nrow + 1, indptr_b + 1, (size_t)nrow_b * sizeof(i64), hipMemcpyHostToDevice, st));
+            if (nnz_t) {
+                SLP_HIP(hipMemcpyAsync(m->a.idx.p, indices, (size_t)nnz_t * sizeof(i32), hipMemcpyHostToDevice, st));
+                SLP_HIP(hipMemcpyAsync(m->a.val.p, data, (size_t)nnz_t * sizeof(double), hipMemcpyHostToDevice, st));
+            }
+            if (nnz_b) {
+                SLP_HIP(hipMemcpyAsync(m->a.idx.p + nnz_t, indices_b, (size_t)nnz_b * sizeof(i32), hipMemcpyHostToDevice, st));
+                SLP_HIP(hipMemcpyAsync(m->a.val.p + nnz_t, data_b, (size_t)nnz_b * sizeof(double), hipMemcpyHostToDevice, st));
+            }
+            if (nnz_t)
+                hipLaunchKernelGGL(k_shift_ptr, dim3(grid_for(nrow_b, kBlock)), dim3(kBlock), 0, st, nrow_b, m->a.ptr.p + nrow + 1, nnz_t);
+            SLP_HIP(hipGetLastError());
+            SLP_HIP(hipStreamSynchronize(st));  // the host blocks may be freed by the caller
+        }
         DevBuf<int> bad(1);
         bad.zero();
-        hipLaunchKernelGGL(k_validate_csr, dim3(grid_for(std::max(nrow, nnz), kBlock)), dim3(kBlock), 0, ctx().stream, nrow, ncol, nnz,
-                           m->a.ptr.p, m->a.idx.p, bad.p);
+        hipLaunchKernelGGL(k_validate_csr, dim3(grid_for(std::max(nrow_all, nnz), kBlock)), dim3(kBlock), 0, ctx().stream, nrow_all, ncol,
+                           nnz, m->a.ptr.p, m->a.idx.p, bad.p);
         SLP_HIP(hipGetLastError());
         int hbad = 0;
         bad.download(&hbad, 1);
@@ -476,6 +508,10 @@ static slp_matrix *matrix_from_host(i64 nrow, i64 ncol, const i64 *indptr, const
         throw;
     }
     return m;
+}
+
+static slp_matrix *matrix_from_host(i64 nrow, i64 ncol, const i64 *indptr, const i32 *indices, const double *data) {
+    return matrix_from_host_blocks(nrow, ncol, indptr, indices, data, 0, nullptr, nullptr, nullptr);
 }
 
 // ---- row gather: out row r = scale[r] * (row src[r] of a); used for the device-side one-sided stacking
@@ -660,6 +696,16 @@ int slp_timer_stop(double *ms) {
 slp_matrix *slp_matrix_create(int64_t nrow, int64_t ncol, const int64_t *indptr, const int32_t *indices,
                               const double *data) {
     SLP_API_PTR({ return matrix_from_host(nrow, ncol, indptr, indices, data); })
+}
+
+slp_matrix *slp_matrix_create_stacked(int64_t ncol, int64_t nrow_top, const int64_t *top_indptr, const int32_t *top_indices,
+                                      const double *top_data, int64_t nrow_bottom, const int64_t *bottom_indptr,
+                                      const int32_t *bottom_indices, const double *bottom_data) {
+    SLP_API_PTR({
+        if (nrow_top == 0) return matrix_from_host(nrow_bottom, ncol, bottom_indptr, bottom_indices, bottom_data);
+        return matrix_from_host_blocks(nrow_top, ncol, top_indptr, top_indices, top_data, nrow_bottom, bottom_indptr, bottom_indices,
+                                       bottom_data);
+    })
 }
 
 void slp_matrix_destroy(slp_matrix *a) { delete a; }

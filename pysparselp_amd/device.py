@@ -24,6 +24,23 @@ class DeviceMatrix:
         return cls(h, a.shape)
 
     @classmethod
+    def from_blocks(cls, top, bottom, ncol):
+        """``[top; bottom]`` from two host CSR blocks of ``ncol`` columns (scipy matrices, ``CsrArrays`` or ``None`` for no rows),
+        stacked on the device (``slp_matrix_create_stacked``): each block is uploaded as it is, no host copy of the values."""
+        l = _lib.lib()
+        arrays, rows = [], 0
+        for blk in (top, bottom):
+            if blk is None or blk.shape[0] == 0:
+                arrays += [0, None, None, None]
+                continue
+            assert blk.shape[1] == ncol
+            indptr, indices, data = _lib.csr_arrays(blk)
+            arrays += [blk.shape[0], _lib.ptr(indptr), _lib.ptr(indices), _lib.ptr(data)]
+            rows += blk.shape[0]
+        h = _lib.check_handle(l.slp_matrix_create_stacked(int(ncol), *arrays))
+        return cls(h, (rows, ncol))
+
+    @classmethod
     def random(cls, nrow, ncol, density, seed, row_offset=0):
         """Rows ``row_offset .. row_offset+nrow`` of the synthetic benchmark matrix
         (distribution of the reference's randomLP.rand_sparse, generated on the GPU)."""

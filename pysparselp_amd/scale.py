@@ -38,10 +38,12 @@ def one_sided_rows(m, m_eq, b_lower, b_upper):
 class DeviceCP:
     """Chambolle-Pock (reference ChambollePockPPD.py:195-343) on a DeviceMatrix."""
 
-    def __init__(self, a, b_upper, c, lb, ub, alpha=1.0, theta=1.0, order=ORDER_AUTO, m_eq=0, b_lower=None, remove_fixed=False):
+    def __init__(self, a, b_upper, c, lb, ub, alpha=1.0, theta=1.0, order=ORDER_AUTO, m_eq=0, b_lower=None, remove_fixed=False,
+                 x0=None):
         """``remove_fixed=False`` is the reference's ``chambolle_pock_ppd`` function on the LP as given;
         ``remove_fixed=True`` adds what ``SparseLP.solve`` does before calling it (SparseLP.py:1244-1248): variables with
-        ``ub == lb`` are dropped -- here on the device (column compaction + ``b - A shift``)."""
+        ``ub == lb`` are dropped -- here on the device (column compaction + ``b - A shift``).  ``x0``: the starting point over
+        all variables (zeros when ``None``; the free ones are taken with ``remove_fixed``)."""
         self._l = _lib.lib()
         self.n_full = a.shape[1]
         c, b_upper, lb, ub = _lib.f64(c), _lib.f64(b_upper), _lib.f64(lb), _lib.f64(ub)
@@ -57,13 +59,15 @@ class DeviceCP:
             if b_lower is not None:
                 b_lower = b_lower - a_shift
             c, lb, ub = c[self.free], lb[self.free], ub[self.free]
+            x0 = None if x0 is None else _lib.f64(x0)[self.free]
+        x0 = None if x0 is None else _lib.f64(x0)
         self.n = a.shape[1]
         self.c = np.ascontiguousarray(c)
         if b_lower is not None:
             a, b_upper = self._one_sided(a, int(m_eq), b_lower, b_upper)
         self.a = a
         self._h = _lib.check_handle(self._l.slp_cp_create_on(a._h, int(m_eq), _lib.ptr(b_upper), _lib.ptr(self.c), _lib.ptr(lb),
-                                                             _lib.ptr(ub), None, float(alpha), float(theta), int(order)))
+                                                             _lib.ptr(ub), _lib.ptr(x0), float(alpha), float(theta), int(order)))
 
     def _one_sided(self, a, m_eq, b_lower, b_upper):
         plan = one_sided_rows(a.shape[0], m_eq, b_lower, b_upper)
