@@ -432,6 +432,33 @@ int slp_blocks_report(slp_blocks *s, double out[2]);
 int64_t slp_blocks_cg_steps(const slp_blocks *s);
 int slp_blocks_get_xp(slp_blocks *s, double *xp, int64_t count);
 
+/* ---- ADMM with the equality constraints exact in every x-step (lp_admm2) -- *
+ * Replaces the loop of lp_admm2 (ADMM.py:407-472) and the sparse LU of its KKT matrix [gamma I, A^T; A, 0] (:330-342):
+ * every x-step projects (-c + gamma xp - lambda) / gamma onto {A x = b} of the standard form A = [A_eq 0; A_ineq -I]
+ * (:411-413) matrix-free, by the row-block conjugate gradients of slp_blocks_create_on (dual form A A^T + [0; I], or the
+ * primal form I + A^T A when every row is an inequality and m >= n), warm-started from the previous solution.  The rows of
+ * `a`: the first m_eq equalities a_i x = b_upper_i, the others b_lower_i <= a_i x <= b_upper_i (b_lower may be NULL = -inf),
+ * slack column implicit; any slp_matrix (CSR, strip, tall-cell, chunked).  x0 (n values, NULL = 0): the slacks start at
+ * A_ineq x0 (tools.py:123-124), xp at x0 clamped to the bounds (ADMM.py:323-325), lambda at 0; alpha = 1.95 (:279).
+ * The whole LP on this rank: no collectives, also under slp_comm_init.  Parity with the LU form is a tolerance
+ * (slp_admm2_set_cg, as slp_blocks_set_cg).  `a` stays owned by the caller. */
+typedef struct slp_admm2 slp_admm2;
+slp_admm2 *slp_admm2_create_on(slp_matrix *a, int64_t m_eq, const double *b_lower, const double *b_upper, const double *c,
+                               const double *lb, const double *ub, const double *x0, double gamma);
+void slp_admm2_destroy(slp_admm2 *s);
+/* Relative residual of the conjugate gradients (default 1e-13) and the most steps per x-step (default 500). */
+int slp_admm2_set_cg(slp_admm2 *s, double tol, int max_steps);
+/* k iterations of ADMM.py:407-472: x-step (:411-428), xp-step (:433-435), multiplier step (:472). */
+int slp_admm2_iterate(slp_admm2 *s, int64_t k);
+/* After an iteration: out[0] = the energy of ADMM.py:396-402 (c.x + gamma/2 |x - xp|^2 + lambda.(x - xp), lambda before
+ * the iteration's multiplier step, over the variables and the slacks), out[1] = CG steps taken so far. */
+int slp_admm2_report(slp_admm2 *s, double out[2]);
+int64_t slp_admm2_cg_steps(const slp_admm2 *s);
+/* The first `count` entries of the over-relaxed x (what lp_admm2 returns, :474), not of xp. */
+int slp_admm2_get_x(slp_admm2 *s, double *x, int64_t count);
+/* As slp_blocks_projection_residual, for the last x-step. */
+int slp_admm2_projection_residual(slp_admm2 *s, double out[2]);
+
 /* ---- synthetic random LP on the device (randomLP.py:14-75) -------------- *
  * Row r of A_ineq (global row index row_offset + r): every entry is non-zero
  * with probability `density`, value round(N(0,1)*100)/100, exact zeros

@@ -196,3 +196,90 @@ def lp_admm(
         return state.x(n)
     finally:
         state.close()
+
+
+def lp_admm2(
+    c,
+    a_eq,
+    beq,
+    a_ineq,
+    b_lower,
+    b_upper,
+    lb,
+    ub,
+    x0=None,
+    gamma_ineq=0.7,
+    nb_iter=100,
+    callback_func=None,
+    max_time=None,
+    use_preconditioning=False,
+    nb_iter_plot=10,
+    cg_tol=1e-13,
+    cg_max_steps=500,
+):
+    """minimise c.x  s.t.  a_eq x = beq,  b_lower <= a_ineq x <= b_upper,  lb <= x <= ub  (reference ADMM.py:272-474).
+
+    ADMM with the equality constraints of the slack standard form kept exact in every x-step.  Where the reference factorises
+    the KKT matrix ``[gamma I, A^T; A, 0]`` once with a sparse LU (:330-342), the x-step here is the matrix-free projection of
+    csrc/slp_blocks.hip (conjugate gradients on the device, relative residual ``cg_tol``, at most ``cg_max_steps`` steps,
+    warm-started): the iterates agree with the LU form to that tolerance, not bit for bit.  Same signature, reporting cadence
+    (``nb_iter + 1`` iterations, a report after those with ``niter % nb_iter_plot == 0``, ``max_time`` checked there before
+    the callback) and return value (the first ``n`` entries of the over-relaxed ``x``, :474).  ``max_time=None`` means no
+    limit.  ``[A_eq; A_ineq]`` is uploaded as the caller holds it (row chunks when it would not fit the device); the slack
+    column stays implicit.  ``use_preconditioning=True`` runs the reference's transforms (:308-330) on the host and hands
+    the explicit standard form over, all rows equalities (not for LPs that need chunks)."""
+    from . import host_setup
+    from .scale import DeviceADMM2
+    from .tools import CsrArrays
+
+    start = time.perf_counter()
+    c = _lib.f64(c)
+    n = c.size
+    a_eq, a_ineq = CsrArrays.from_any(a_eq), CsrArrays.from_any(a_ineq)
+    if a_ineq is None:  # what the reference does on this input (tools.py:92-127)
+        raise UnboundLocalError("local variable 'a_eq2' referenced before assignment (no inequality constraints)")
+    x0 = np.zeros(n) if x0 is None else _lib.f64(x0)
+    if use_preconditioning:  # :308-318, :320-322, :328-329
+        if a_eq is not None:
+            a_eq, beq = precondition_constraints(a_eq, beq, alpha=2)
+        a_ineq, b_lower, b_upper = precondition_constraints(a_ineq, b_lower, b_upper, alpha=2)
+        c, a, b, lb, ub, x0 = convert_to_standard_form_with_bounds(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0)
+        a, b = precondition_constraints(a, b, alpha=2)
+        if host_setup.chunk_entries(a.nnz, a.shape[0], a.shape[1]) is not None:
+            raise ValueError("lp_admm2 with use_preconditioning=True needs the explicit standard form in one piece, and this LP "
+                             "would be built from row chunks; " + host_setup.MULTI_GPU)
+        eq, ineq, m_eq, b_all, bl_all = a, None, a.shape[0], _lib.f64(b), None
+    else:
+        m_eq = 0 if a_eq is None else a_eq.shape[0]
+        m_in = a_ineq.shape[0]
+        b_upper = np.full(m_in, np.inf) if b_upper is None else _lib.f64(b_upper)
+        b_lower = np.full(m_in, -np.inf) if b_lower is None else _lib.f64(b_lower)
+        b_all = np.concatenate((np.zeros(0) if a_eq is None else _lib.f64(beq), b_upper))
+        bl_all = np.concatenate((np.zeros(m_eq), b_lower))
+        eq, ineq = a_eq, a_ineq
+    ncol = ineq.shape[1] if ineq is not None else eq.shape[1]
+    nrow = (0 if eq is None else eq.shape[0]) + (0 if ineq is None else ineq.shape[0])
+    entries = host_setup.chunk_entries(host_setup.nnz_of(eq, ineq), nrow, ncol)
+    mat, _ = host_setup.upload(eq, ineq, ncol, entries)
+    state = None
+    try:
+        state = DeviceADMM2(mat, b_all, c, lb, ub, m_eq=m_eq, b_lower=bl_all, x0=x0, gamma=gamma_ineq, cg_tol=cg_tol,
+                            cg_max_steps=cg_max_steps)
+        i = 0
+        while i <= nb_iter:  # :407: nb_iter + 1 iterations, a report after those with i % nb_iter_plot == 0
+            k = 1 if i % nb_iter_plot == 0 else min(nb_iter_plot - i % nb_iter_plot, nb_iter + 1 - i)
+            reports = (i + k - 1) % nb_iter_plot == 0
+            state.iterate(k)
+            i += k
+            if reports:
+                elapsed = time.perf_counter() - start
+                if max_time is not None and elapsed > max_time:
+                    break
+                energy = state.report()[0]
+                if callback_func is not None:
+                    callback_func(i - 1, state.x(n), energy, energy, elapsed, 0, 0)
+        return state.x(n)
+    finally:
+        if state is not None:
+            state.close()
+        mat.close()

@@ -11,7 +11,8 @@ first-order solvers need (reference SparseLP.py:162-1383): the LP is held as
 with scipy CSR matrices, and ``solve`` (reference :990-1002, :1064-1093,
 :1193-1208, :1243-1288, :1378-1383) runs one of the GPU solvers and fills the
 same convergence-curve attributes.  The hot-path methods ``"admm"`` and
-``"chambolle_pock_ppd"`` and the block-splitting ``"admm_blocks"`` exist here; the other solvers of the reference
+``"chambolle_pock_ppd"``, the block-splitting ``"admm_blocks"`` and ``"admm2"`` (ADMM with exact equality projections)
+exist here; the other solvers of the reference
 (interior point, dual ascent, external solver bridges, rounding heuristics,
 MPS export) are out of scope.
 """
@@ -26,7 +27,7 @@ from .ADMM import lp_admm
 from .ChambollePockPPD import chambolle_pock_ppd
 from ._lib import ORDER_AUTO
 
-solving_methods = ("chambolle_pock_ppd", "admm", "admm_blocks")
+solving_methods = ("chambolle_pock_ppd", "admm", "admm_blocks", "admm2")
 
 _SCALARS = (int, float, np.integer, np.floating)
 
@@ -377,8 +378,11 @@ class SparseLP:
         Under a communicator (``parallel.init_comm_from_env`` in every rank of a ``torch.distributed.run`` / ``mpirun``
         launch) every rank calls ``solve`` on the same LP: ``"chambolle_pock_ppd"`` and ``"admm"`` with ``xstep="cg"`` hand
         over only this rank's block of constraint rows (equal stored entries per rank), exchange one / two all-reduces of
-        the variable vector per iteration and return the same ``x`` on every rank; the exact Gauss-Seidel ADMM and
-        ``admm_blocks`` run as replicas.
+        the variable vector per iteration and return the same ``x`` on every rank; the exact Gauss-Seidel ADMM,
+        ``admm_blocks`` and ``admm2`` run as replicas.
+
+        ``"admm2"`` is the reference's ``lp_admm2`` (ADMM.py:272-474) with its KKT solves matrix-free (conjugate gradients on
+        the device, see ``ADMM.lp_admm2``); ``setup`` and ``order`` do not apply to it.
 
         Fills, at every report (every ``nb_iter_plot`` iterations): ``itrn_curve,
         opttime_curve, dopttime_curve, pobj_curve, dobj_curve,
@@ -433,6 +437,11 @@ class SparseLP:
             x = lp_admm_block_decomposition(self.costsvector, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds,
                                             self.upper_bounds, nb_iter=nb_iter, nb_iter_plot=nb_iter_plot, x0=x0,
                                             callback_func=record, max_time=max_time)
+        elif method == "admm2":  # reference :1226-1241: no deep copy, no fixed-variable removal
+            from .ADMM import lp_admm2
+
+            x = lp_admm2(self.costsvector, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds, self.upper_bounds,
+                         nb_iter=nb_iter, x0=x0, callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
         else:  # chambolle_pock_ppd: fixed variables are eliminated first (reference :1244-1248)
             from . import host_setup
             from .ChambollePockPPD import _cp_loop, close_device_cp, device_cp

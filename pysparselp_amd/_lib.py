@@ -115,6 +115,14 @@ _SIGNATURES = {
     "slp_blocks_report": (c_int, [c_vp, c_vp]),
     "slp_blocks_cg_steps": (c_i64, [c_vp]),
     "slp_blocks_get_xp": (c_int, [c_vp, c_vp, c_i64]),
+    "slp_admm2_create_on": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl]),
+    "slp_admm2_destroy": (None, [c_vp]),
+    "slp_admm2_set_cg": (c_int, [c_vp, c_dbl, c_int]),
+    "slp_admm2_iterate": (c_int, [c_vp, c_i64]),
+    "slp_admm2_report": (c_int, [c_vp, c_vp]),
+    "slp_admm2_cg_steps": (c_i64, [c_vp]),
+    "slp_admm2_get_x": (c_int, [c_vp, c_vp, c_i64]),
+    "slp_admm2_projection_residual": (c_int, [c_vp, c_vp]),
     "slp_admm_cg_create_on_two_sided": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),
     "slp_admm_cg_create_on_lp": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int, c_int]),
     "slp_admm_cg_create_lp": (c_vp, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

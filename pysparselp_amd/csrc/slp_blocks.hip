@@ -317,6 +317,113 @@ __global__ __launch_bounds__(kBlock) void k_rb_energy(i64 n, i64 m, i64 m_eq, co
     if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
+// ---- ADMM with the equality constraints exact in every x-step (reference ADMM.py:272-474, lp_admm2) ------------------
+// Its x-step is the KKT system [gamma I, A^T; A, 0] [x; mu] = [-c + gamma xp - lambda; b] of the standard form
+// A = [A_eq 0; A_ineq -I] (:330-342, :411-413): the projection of v = (-c + gamma xp - lambda) / gamma onto {A x = b},
+// solved by the row-block conjugate gradients above (dual form A A^T + [0; I], or the primal form I + A^T A).  Around it,
+// per variable and per slack, in one pass each: the over-relaxed x (:428), the clamp (:433-435), the terms of the report
+// energy with lambda before its update (:396-402) as per-workgroup partial sums, and the multiplier update (:472).
+constexpr int kA2Terms = 3;   // partial sums per workgroup: c.x, 0.5 gamma |x - xp|^2, lambda.(x - xp)
+
+__global__ void k_a2_v(i64 n, const double *__restrict__ c, const double *__restrict__ xp, const double *__restrict__ lam, double gamma,
+                       double *__restrict__ v) {
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (i64)gridDim.x * blockDim.x)
+        v[j] = ((-c[j] + gamma * xp[j]) - lam[j]) / gamma;
+}
+
+// writes the workgroup's three energy terms to part[k * stride + blockIdx.x]
+__device__ __forceinline__ void a2_energy_out(double ec, double ed, double el, double *lds, double *__restrict__ part, int stride) {
+    const double rc = block_reduce<false>(ec, lds);
+    __syncthreads();
+    const double rd = block_reduce<false>(ed, lds);
+    __syncthreads();
+    const double rl = block_reduce<false>(el, lds);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = rc;
+        part[stride + blockIdx.x] = rd;
+        part[2 * stride + blockIdx.x] = rl;
+    }
+}
+
+// variables: xh = v - u (dual form, u = A^T nu) or xh = sol (primal form); x = alpha xh + (1 - alpha) xp ;
+// xp = clamp(x + lambda / gamma, lb, ub) ; energy terms ; lambda += gamma (x - xp)
+template <bool DUAL>
+__global__ __launch_bounds__(kBlock) void k_a2_x(i64 n, const double *__restrict__ v, const double *__restrict__ u,
+                                                 const double *__restrict__ sol, const double *__restrict__ c,
+                                                 const double *__restrict__ lb, const double *__restrict__ ub, double alpha,
+                                                 double one_minus_alpha, double gamma, double *__restrict__ x, double *__restrict__ xp,
+                                                 double *__restrict__ lam, double *__restrict__ part, int stride) {
+    __shared__ double lds[kBlock / kWave];
+    double ec = 0.0, ed = 0.0, el = 0.0;
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (i64)gridDim.x * blockDim.x) {
+        const double xh = DUAL ? v[j] - u[j] : sol[j];
+        const double xj = alpha * xh + one_minus_alpha * xp[j];
+        const double l = lam[j];
+        double a = xj + l / gamma;
+        const double lo = lb[j], hi = ub[j];
+        a = (a > lo) ? a : lo;  // np.maximum / np.minimum
+        a = (a < hi) ? a : hi;
+        const double d = xj - a;
+        ec += c[j] * xj;
+        ed += d * d;
+        el += l * d;
+        x[j] = xj;
+        xp[j] = a;
+        lam[j] = l + gamma * d;
+    }
+    a2_energy_out(ec, 0.5 * gamma * ed, el, lds, part, stride);
+}
+
+// slacks (rows m_eq .. m, cost 0): xh = vs + nu (dual form) or xh = w = A sol (primal form); the same updates
+template <bool DUAL>
+__global__ __launch_bounds__(kBlock) void k_a2_slack(i64 m, i64 m_eq, const double *__restrict__ vs, const double *__restrict__ nu,
+                                                     const double *__restrict__ w, const double *__restrict__ slo,
+                                                     const double *__restrict__ shi, double alpha, double one_minus_alpha, double gamma,
+                                                     double *__restrict__ xs, double *__restrict__ xps, double *__restrict__ lams,
+                                                     double *__restrict__ part, int stride) {
+    __shared__ double lds[kBlock / kWave];
+    double ed = 0.0, el = 0.0;
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x + m_eq; i < m; i += (i64)gridDim.x * blockDim.x) {
+        const double xh = DUAL ? vs[i] + nu[i] : w[i];
+        const double xi = alpha * xh + one_minus_alpha * xps[i];
+        const double l = lams[i];
+        double a = xi + l / gamma;
+        const double lo = slo[i], hi = shi[i];
+        a = (a > lo) ? a : lo;
+        a = (a < hi) ? a : hi;
+        const double d = xi - a;
+        ed += d * d;
+        el += l * d;
+        xs[i] = xi;
+        xps[i] = a;
+        lams[i] = l + gamma * d;
+    }
+    a2_energy_out(0.0, 0.5 * gamma * ed, el, lds, part, stride);
+}
+
+// set-up: x = x0 ; xp = clamp(x0, lb, ub)  (:323-325)
+__global__ void k_a2_init_x(i64 n, const double *__restrict__ lb, const double *__restrict__ ub, double *__restrict__ x,
+                            double *__restrict__ xp) {
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (i64)gridDim.x * blockDim.x) {
+        double a = x[j];
+        a = (a > lb[j]) ? a : lb[j];
+        a = (a < ub[j]) ? a : ub[j];
+        xp[j] = a;
+    }
+}
+
+// set-up of the slacks: xs = (A x0)_i (tools.py:123-124) ; xps = clamp(xs, b_lower, b_upper)
+__global__ void k_a2_init_slack(i64 m, i64 m_eq, const double *__restrict__ ax, const double *__restrict__ slo,
+                                const double *__restrict__ shi, double *__restrict__ xs, double *__restrict__ xps) {
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x + m_eq; i < m; i += (i64)gridDim.x * blockDim.x) {
+        double a = ax[i];
+        xs[i] = a;
+        a = (a > slo[i]) ? a : slo[i];
+        a = (a < shi[i]) ? a : shi[i];
+        xps[i] = a;
+    }
+}
+
 }  // namespace slp
 
 using namespace slp;
@@ -345,6 +452,14 @@ struct slp_blocks {
     // each on a stream of its own (slp_blocks_group_iterate)
     struct { i64 m = 0; double *sol = nullptr; bool pc = false; int it = 0; } cg;
     bool warmed = false;      // has run a projection on the library's stream (slp_blocks_group_iterate)
+};
+
+// lp_admm2 (slp_admm2_create_on): the row-block state above is its projection and its vectors -- x / xp / lam over the
+// variables, xs / xps / lams over the implicit slacks -- with no copies, no consensus and no exchange
+struct slp_admm2 : slp_blocks {
+    int gx = 0, gs = 0;        // workgroups of the fused variable / slack passes = their energy partial sums per term
+    DevBuf<double> epart;      // [kA2Terms][gx + gs], written by every iteration
+    DevBuf<double> escal;      // the three reduced terms (slp_admm2_report)
 };
 
 namespace slp {
@@ -440,11 +555,11 @@ static void rb_apply_primal(slp_blocks *s, const double *dir, double *q) {  // q
     hipLaunchKernelGGL(k_rb_add_vec, dim3(grid_for(s->N, kBlock)), dim3(kBlock), 0, ctx().stream, s->N, dir, q);
 }
 
-static void rb_project_begin(slp_blocks *s) {
+// the projection system of the point (v, vs) up to the first inner products of its conjugate gradients; v is already set
+static void rb_system_begin(slp_blocks *s) {
     hipStream_t st = ctx().stream;
     const i64 n = s->N, m = s->m, me = s->m_eq;
     const int gn = grid_for(n, kBlock), gm = grid_for(m, kBlock);
-    hipLaunchKernelGGL(k_rb_v, dim3(gn), dim3(kBlock), 0, st, n, s->xp.p, s->lam.p, s->gamma, s->v.p);
     if (s->primal) {
         hipLaunchKernelGGL(k_rb_vs, dim3(gm), dim3(kBlock), 0, st, m, s->xps.p, s->lams.p, s->gamma, s->vs.p);
         matrix_spmv(s->a, true, s->vs.p, s->u.p, SLP_ORDER_AUTO);
@@ -460,6 +575,11 @@ static void rb_project_begin(slp_blocks *s) {
         blk_cg_begin(s);
     }
     SLP_HIP(hipGetLastError());
+}
+
+static void rb_project_begin(slp_blocks *s) {
+    hipLaunchKernelGGL(k_rb_v, dim3(grid_for(s->N, kBlock)), dim3(kBlock), 0, ctx().stream, s->N, s->xp.p, s->lam.p, s->gamma, s->v.p);
+    rb_system_begin(s);
 }
 
 // the next `check_every` conjugate-gradient steps of the block's projection; true when it has none left
@@ -539,6 +659,56 @@ static void blk_iteration(slp_blocks *s) {
     SLP_HIP(hipGetLastError());
 }
 
+// A matrix without CSR entries (a chunked matrix, or one whose CSR was released) serves as long as both products run on its
+// strip / tall-cell copies: the row-block solvers only ever multiply (BASELINE config 5: eight 5e5 x 5e7 blocks on one GPU
+// exist as 26 GB of tall cells each, never as 60 GB of CSR).  True when the matrix has no CSR entries.
+static bool rb_matrix_check(slp_matrix *a, const char *who) {
+    const bool csrless = !a->chunks.empty() || a->csr_released;
+    if (csrless)
+        SLP_REQUIRE(fast_format(a, false) && fast_format(a, true),
+                    std::string(who) + ": the CSR entries of this matrix are gone and it has no strip copies in both orientations");
+    return csrless;
+}
+
+static void rb_matrix_formats(slp_matrix *a) {
+    ensure_transposed(a);  // a copy of A^T (tall cells come straight from the CSR of A), else the transposed CSR
+    fast_format(a, false);
+    fast_format(a, true);
+}
+
+// all rows inequalities and m >= n: the better-conditioned primal form of the projection (SLP_BLOCKS_PRIMAL=0/1 forces)
+static bool rb_primal_form(i64 m, i64 n, i64 m_eq) {
+    const char *ep = getenv("SLP_BLOCKS_PRIMAL");
+    return m_eq == 0 && m > 0 && (ep ? ep[0] == '1' : m >= n);
+}
+
+// one iteration of ADMM.py:407-472 (the report in between is slp_admm2_report over this iteration's partial sums)
+static void a2_iteration(slp_admm2 *s) {
+    hipStream_t st = ctx().stream;
+    const i64 n = s->N, m = s->m, me = s->m_eq;
+    const int stride = s->gx + s->gs;
+    hipLaunchKernelGGL(k_a2_v, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, n, s->c.p, s->xp.p, s->lam.p, s->gamma, s->v.p);
+    rb_system_begin(s);
+    while (!rb_project_round(s)) {}
+    const double al = s->alpha, oma = 1.0 - s->alpha, g = s->gamma;
+    if (s->primal) {
+        matrix_spmv(s->a, false, s->xsol.p, s->w.p, SLP_ORDER_AUTO);  // the projected slacks s = A x
+        hipLaunchKernelGGL(k_a2_x<false>, dim3(s->gx), dim3(kBlock), 0, st, n, s->v.p, s->u.p, s->xsol.p, s->c.p, s->lb.p, s->ub.p, al, oma,
+                           g, s->x.p, s->xp.p, s->lam.p, s->epart.p, stride);
+        hipLaunchKernelGGL(k_a2_slack<false>, dim3(s->gs), dim3(kBlock), 0, st, m, (i64)0, s->vs.p, s->nu.p, s->w.p, s->slo.p, s->shi.p, al,
+                           oma, g, s->xs.p, s->xps.p, s->lams.p, s->epart.p + s->gx, stride);
+    } else {
+        if (m > 0) matrix_spmv(s->a, true, s->nu.p, s->u.p, SLP_ORDER_AUTO);
+        else s->u.zero();
+        hipLaunchKernelGGL(k_a2_x<true>, dim3(s->gx), dim3(kBlock), 0, st, n, s->v.p, s->u.p, s->xsol.p, s->c.p, s->lb.p, s->ub.p, al, oma,
+                           g, s->x.p, s->xp.p, s->lam.p, s->epart.p, stride);
+        if (m > me)
+            hipLaunchKernelGGL(k_a2_slack<true>, dim3(s->gs), dim3(kBlock), 0, st, m, me, s->vs.p, s->nu.p, s->w.p, s->slo.p, s->shi.p, al,
+                               oma, g, s->xs.p, s->xps.p, s->lams.p, s->epart.p + s->gx, stride);
+    }
+    SLP_HIP(hipGetLastError());
+}
+
 }  // namespace slp
 
 extern "C" {
@@ -583,24 +753,14 @@ slp_blocks *slp_blocks_create_on(slp_matrix *a, int64_t m_eq, const double *b_lo
         SLP_REQUIRE(a && b_upper && c && lb && ub, "slp_blocks_create_on: NULL argument");
         SLP_REQUIRE(m_eq >= 0 && m_eq <= a->a.nrow, "slp_blocks_create_on: m_eq out of range");
         SLP_REQUIRE(gamma > 0.0, "slp_blocks_create_on: gamma must be positive");
-        // A matrix without CSR entries (a chunked matrix, or one whose CSR was released) serves as long as both products run on
-        // its strip / tall-cell copies: the block ADMM only ever multiplies (BASELINE config 5: eight 5e5 x 5e7 blocks on one
-        // GPU exist as 26 GB of tall cells each, never as 60 GB of CSR).
-        const bool csrless = !a->chunks.empty() || a->csr_released;
-        if (csrless)
-            SLP_REQUIRE(fast_format(a, false) && fast_format(a, true),
-                        "slp_blocks_create_on: the CSR entries of this matrix are gone and it has no strip copies in both orientations");
+        const bool csrless = rb_matrix_check(a, "slp_blocks_create_on");
         auto *s = new slp_blocks();
         try {
             hipStream_t st = ctx().stream;
             const i64 m = a->a.nrow, n = a->a.ncol;
             s->a = a; s->row_block = true; s->m = m; s->N = n; s->P = n; s->m_eq = m_eq; s->gamma = gamma;
             s->distributed = comm_active();
-            if (!csrless) {
-                ensure_transposed(a);  // a copy of A^T (tall cells come straight from the CSR of A), else the transposed CSR
-                fast_format(a, false);
-                fast_format(a, true);
-            }
+            if (!csrless) rb_matrix_formats(a);
             const size_t sn = (size_t)n, sm = (size_t)m;
             // standard form (tools.py:88-127): b = [b_eq; 0], slack bounds [b_lower, b_upper]; x0 = 0 so xp0 = clamp(0) (:84-86)
             std::vector<double> hb(sm, 0.0), hlo(sm, 0.0), hhi(sm, 0.0), hx(sn), hs(sm, 0.0);
@@ -615,9 +775,7 @@ slp_blocks *slp_blocks_create_on(slp_matrix *a, int64_t m_eq, const double *b_lo
             s->c.upload(c, sn); s->lb.upload(lb, sn); s->ub.upload(ub, sn); s->xp.upload(hx.data(), sn);
             s->x.alloc(sn); s->lam.alloc(sn); s->lam.zero(); s->v.alloc(sn); s->u.alloc(sn); s->acc.alloc(sn);
             s->used.alloc(sn); s->copies.alloc(sn);
-            // all rows inequalities and m >= n: the better-conditioned primal form of the projection (SLP_BLOCKS_PRIMAL=0/1 forces)
-            const char *ep = getenv("SLP_BLOCKS_PRIMAL");
-            s->primal = m_eq == 0 && m > 0 && (ep ? ep[0] == '1' : m >= n);
+            s->primal = rb_primal_form(m, n, m_eq);
             const size_t sv = s->primal ? sn : sm;  // the CG runs over the rows (dual form) or over the original variables (primal form)
             s->nu.alloc(sm); s->nu.zero(); s->w.alloc(sm); s->q.alloc(sv); s->r.alloc(sv); s->dir.alloc(sv); s->rhs.alloc(sv);
             if (s->primal) { s->xsol.alloc(sn); s->xsol.zero(); s->zero_m.alloc(sm); s->zero_m.zero(); }
@@ -905,5 +1063,102 @@ int slp_blocks_get_xp(slp_blocks *s, double *xp, int64_t count) {
         s->xp.download(xp, (size_t)count);
     })
 }
+
+slp_admm2 *slp_admm2_create_on(slp_matrix *a, int64_t m_eq, const double *b_lower, const double *b_upper, const double *c,
+                               const double *lb, const double *ub, const double *x0, double gamma) {
+    SLP_API_PTR({
+        SLP_REQUIRE(a && b_upper && c && lb && ub, "slp_admm2_create_on: NULL argument");
+        SLP_REQUIRE(m_eq >= 0 && m_eq <= a->a.nrow, "slp_admm2_create_on: m_eq out of range");
+        SLP_REQUIRE(a->a.ncol > 0, "slp_admm2_create_on: no variables");
+        SLP_REQUIRE(gamma > 0.0, "slp_admm2_create_on: gamma must be positive");
+        const bool csrless = rb_matrix_check(a, "slp_admm2_create_on");
+        auto *s = new slp_admm2();
+        try {
+            hipStream_t st = ctx().stream;
+            const i64 m = a->a.nrow, n = a->a.ncol;
+            // the whole LP on every rank: no collectives, also under an active communicator
+            s->a = a; s->row_block = true; s->distributed = false; s->m = m; s->N = n; s->P = n; s->m_eq = m_eq; s->gamma = gamma;
+            if (!csrless) rb_matrix_formats(a);
+            const size_t sn = (size_t)n, sm = (size_t)m;
+            // standard form (tools.py:88-127): b = [b_eq; 0], slack bounds [b_lower, b_upper]
+            std::vector<double> hb(sm, 0.0), hlo(sm, 0.0), hhi(sm, 0.0);
+            for (i64 i = 0; i < m; ++i) {
+                if (i < m_eq) { hb[(size_t)i] = b_upper[i]; continue; }
+                hlo[(size_t)i] = b_lower ? b_lower[i] : -INFINITY;
+                hhi[(size_t)i] = b_upper[i];
+            }
+            s->b.upload(hb.data(), sm); s->slo.upload(hlo.data(), sm); s->shi.upload(hhi.data(), sm);
+            s->c.upload(c, sn); s->lb.upload(lb, sn); s->ub.upload(ub, sn);
+            if (x0) s->x.upload(x0, sn);
+            else { s->x.alloc(sn); s->x.zero(); }
+            s->xp.alloc(sn);
+            hipLaunchKernelGGL(k_a2_init_x, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, n, s->lb.p, s->ub.p, s->x.p, s->xp.p);
+            s->primal = rb_primal_form(m, n, m_eq);
+            const size_t sv = s->primal ? sn : sm;
+            s->lam.alloc(sn); s->lam.zero(); s->v.alloc(sn); s->u.alloc(sn);
+            s->nu.alloc(sm); s->nu.zero(); s->w.alloc(sm); s->q.alloc(sv); s->r.alloc(sv); s->dir.alloc(sv); s->rhs.alloc(sv);
+            if (s->primal) { s->xsol.alloc(sn); s->xsol.zero(); }
+            s->vs.alloc(sm); s->xs.alloc(sm); s->xs.zero(); s->xps.alloc(sm); s->xps.zero(); s->lams.alloc(sm); s->lams.zero();
+            if (m > m_eq) {  // slacks of x0 (tools.py:123-124) by one product on the device, then clamped (ADMM.py:323-325)
+                matrix_spmv(a, false, s->x.p, s->w.p, SLP_ORDER_AUTO);
+                hipLaunchKernelGGL(k_a2_init_slack, dim3(grid_for(m - m_eq, kBlock)), dim3(kBlock), 0, st, m, m_eq, s->w.p, s->slo.p, s->shi.p,
+                                   s->xs.p, s->xps.p);
+            }
+            s->part.alloc(kBlkPartials); s->scal.alloc(B_COUNT); s->scal.zero();
+            s->gx = std::min(grid_for(n, kBlock), kBlkPartials);
+            s->gs = m > m_eq ? std::min(grid_for(m - m_eq, kBlock), kBlkPartials) : 0;
+            s->epart.alloc((size_t)kA2Terms * (size_t)(s->gx + s->gs)); s->epart.zero();
+            s->escal.alloc(kA2Terms); s->escal.zero();
+            SLP_HIP(hipGetLastError());
+            SLP_HIP(hipStreamSynchronize(st));
+        } catch (...) {
+            delete s;
+            throw;
+        }
+        ++a->borrowers;
+        return s;
+    })
+}
+
+void slp_admm2_destroy(slp_admm2 *s) {
+    if (!s) return;
+    --s->a->borrowers;
+    delete s;
+}
+
+int slp_admm2_set_cg(slp_admm2 *s, double tol, int max_steps) { return slp_blocks_set_cg(s, tol, max_steps); }
+
+int slp_admm2_iterate(slp_admm2 *s, int64_t k) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && k >= 0, "slp_admm2_iterate: bad arguments");
+        for (i64 it = 0; it < k; ++it) a2_iteration(s);
+    })
+}
+
+int slp_admm2_report(slp_admm2 *s, double out[2]) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && out, "slp_admm2_report: NULL argument");
+        hipStream_t st = ctx().stream;
+        const int stride = s->gx + s->gs;
+        for (int k = 0; k < kA2Terms; ++k)
+            hipLaunchKernelGGL(k_blk_finish, dim3(1), dim3(kBlock), 0, st, stride, s->epart.p + (size_t)k * stride, s->escal.p, k, 0);
+        SLP_HIP(hipGetLastError());
+        double h[kA2Terms];
+        s->escal.download(h, kA2Terms);
+        out[0] = (h[0] + h[1]) + h[2];   // ADMM.py:396-402
+        out[1] = (double)s->cg_steps;
+    })
+}
+
+int64_t slp_admm2_cg_steps(const slp_admm2 *s) { return s ? (int64_t)s->cg_steps : -1; }
+
+int slp_admm2_get_x(slp_admm2 *s, double *x, int64_t count) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && x && count >= 0 && count <= s->N, "slp_admm2_get_x: bad arguments");
+        s->x.download(x, (size_t)count);
+    })
+}
+
+int slp_admm2_projection_residual(slp_admm2 *s, double out[2]) { return slp_blocks_projection_residual(s, out); }
 
 }  // extern "C"

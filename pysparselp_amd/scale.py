@@ -220,6 +220,70 @@ class DeviceBlocks:
         return "block-splitting ADMM (ADMMBlocks.py), one block per rank, matrix-free per-block projections (CG), gamma=0.7, alpha=1.95"
 
 
+class DeviceADMM2:
+    """ADMM with the equality constraints exact in every x-step (reference ADMM.py:272-474, ``lp_admm2``) on a resident
+    DeviceMatrix / ChunkedDeviceMatrix ``a``: the first ``m_eq`` rows are equalities, the others
+    ``b_lower <= a_i x <= b_upper`` (slack column implicit).  The KKT solve of every x-step is the matrix-free row-block
+    projection of ``DeviceBlocks`` (conjugate gradients, warm-started).  The whole LP on this rank: no collectives, also
+    under a communicator."""
+
+    def __init__(self, a, b_upper, c, lb, ub, m_eq=0, b_lower=None, x0=None, gamma=0.7, cg_tol=1e-13, cg_max_steps=500):
+        self._l = _lib.lib()
+        self.a = a
+        self.n = a.shape[1]
+        self.c = _lib.f64(c)
+        b_upper, lb, ub = _lib.f64(b_upper), _lib.f64(lb), _lib.f64(ub)
+        b_lower = None if b_lower is None else _lib.f64(b_lower)
+        x0 = None if x0 is None else _lib.f64(x0)
+        assert self.c.size == self.n and lb.size == self.n and ub.size == self.n and (x0 is None or x0.size == self.n)
+        assert b_upper.size == a.shape[0] and (b_lower is None or b_lower.size == a.shape[0])
+        self._h = _lib.check_handle(self._l.slp_admm2_create_on(
+            a._h, int(m_eq), _lib.ptr(b_lower), _lib.ptr(b_upper), _lib.ptr(self.c), _lib.ptr(lb), _lib.ptr(ub), _lib.ptr(x0),
+            float(gamma)))
+        _lib.check(self._l.slp_admm2_set_cg(self._h, float(cg_tol), int(cg_max_steps)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._l.slp_admm2_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def iterate(self, k):
+        _lib.check(self._l.slp_admm2_iterate(self._h, int(k)))
+
+    def report(self):
+        """``(energy, CG steps so far)`` after the last iteration: the energy of ADMM.py:396-402, lambda before its update."""
+        out = np.zeros(2)
+        _lib.check(self._l.slp_admm2_report(self._h, _lib.ptr(out)))
+        return out
+
+    def x(self, count=None):
+        """The over-relaxed ``x`` (what ``lp_admm2`` returns, ADMM.py:474), its first ``count`` entries (default: ``n``)."""
+        count = self.n if count is None else int(count)
+        out = np.empty(count)
+        _lib.check(self._l.slp_admm2_get_x(self._h, _lib.ptr(out), count))
+        return out
+
+    def objective(self):
+        return float(self.c.dot(self.x()))
+
+    def cg_steps(self):
+        return int(self._l.slp_admm2_cg_steps(self._h))
+
+    def projection_residual(self):
+        """``(|| rhs - S sol ||_2, || rhs ||_2)`` of the last x-step's projection system, operator applied afresh."""
+        out = np.zeros(2)
+        _lib.check(self._l.slp_admm2_projection_residual(self._h, _lib.ptr(out)))
+        return float(out[0]), float(out[1])
+
+    def matrix_passes_per_iteration(self):
+        return None  # 2 + 2 per conjugate-gradient step; see cg_steps()
+
+    def describe(self):
+        return "ADMM with exact equality projections (ADMM.py lp_admm2), matrix-free KKT solves (CG), gamma=0.7, alpha=1.95"
+
+
 class DeviceBlocksGroup:
     """Block-splitting ADMM with SEVERAL row blocks on this rank (the ``blocks`` metadata of the reference,
     ADMMBlocks.py:93-95,178-243, at scale): block g = rows ``cuts[g] .. cuts[g + 1]`` of the DeviceMatrix ``a`` (cut on the
