@@ -459,6 +459,49 @@ int slp_admm2_get_x(slp_admm2 *s, double *x, int64_t count);
 /* As slp_blocks_projection_residual, for the last x-step. */
 int slp_admm2_projection_residual(slp_admm2 *s, double out[2]);
 
+/* ---- dual gradient ascent with the exact dual line search (DualGradientAscent.py:36-245) ---- *
+ * The rows of `a`: the first m_eq equalities a_i x = b_i, the others inequalities a_i x <= b_i; y0: the m start multipliers
+ * (the reference draws them, :93-101); any slp_matrix (CSR, strip, tall-cell, chunked).  One iteration: c_bar = (c + A_e^T y_e)
+ * + A_i^T y_i and the dual argmin x (:103-115), K x once, then the inequality block and the equality block, both on that c_bar
+ * and x (:145-209): masked gradient g, d = K^T g, the search over the breakpoints -c_bar_j / d_j (:36-65) and the y update.
+ * All products in SLP_ORDER_SEQUENTIAL.  The search runs fused in one workgroup (breakpoints sorted and summed in LDS; possible
+ * up to 8192 variables) for n <= 2048, else as key build / radix sort / tiled scans / bisection; SLP_DGA_PATH=fused|general or
+ * slp_dga_set_path (0 auto, 1 fused, 2 general) force one; both give the same bits.  Nothing is read back inside slp_dga_iterate: block
+ * predicates, step, tie-draw count and status live in device memory.  The whole LP on this rank: no collectives.
+ * `a` stays owned by the caller. */
+typedef struct slp_dga slp_dga;
+slp_dga *slp_dga_create_on(slp_matrix *a, int64_t m_eq, const double *b, const double *c, const double *lb, const double *ub,
+                           const double *y0);
+void slp_dga_destroy(slp_dga *s);
+int slp_dga_set_path(slp_dga *s, int path);
+int slp_dga_path(const slp_dga *s);   /* 1 fused, 2 general */
+/* Up to k iterations.  A tie of the search (:56-60) takes one uniform draw from the buffer slp_dga_push_random fills, at most
+ * two per iteration: the call stops early (status bit 4, slp_dga_iterations tells how far it got) once fewer than two draws
+ * per iteration to come are certain to be left; push more and call again. */
+int slp_dga_iterate(slp_dga *s, int64_t k);
+int64_t slp_dga_iterations(const slp_dga *s);
+/* Appends `count` draws (numpy.random.RandomState(0).random_sample, continuing the stream of y0) behind the unused ones. */
+int slp_dga_push_random(slp_dga *s, const double *draws, int64_t count);
+/* out[0] = sticky status bits: 1 a negative (or NaN) step (the reference's assert, :167,:204), 2 an empty breakpoint set (its
+ * IndexError), 4 the draw buffer ran dry, 8 a NaN breakpoint, 16 no sign change of the derivative on the whole line;
+ * out[1] = tie draws taken so far, out[2] = draws left in the buffer, out[3] = iterations done. */
+int slp_dga_status(slp_dga *s, int64_t out[4]);
+/* x of the top of the last iteration (of y0 before the first): what the reference returns; y = [y_eq; y_ineq] now. */
+int slp_dga_get_x(slp_dga *s, double *x);
+int slp_dga_get_y(slp_dga *s, double *y);
+/* For the multipliers as they are now: out[0] = the dual energy (:117-128; -inf: dual infeasible), with x their argmin
+ * out[1] = the largest violation (a_i x - b_i, |.| on equality rows) and out[2] = the sum of the positive ones. */
+int slp_dga_report(slp_dga *s, double out[3]);
+/* Measurement only: HIP events at the stage boundaries of every iteration while on; _read (after the timed region) gives the
+ * milliseconds spent in out[0] the products, [1] the sort, [2] the scans, [3] everything else, [4] the fused search. */
+int slp_dga_timing(slp_dga *s, int on);
+int slp_dga_timing_read(slp_dga *s, double out[5]);
+/* exact_dual_line_search (:36-65) alone: direction (m values, zeros are no entries) over the rows of `a`, b (m), c_bar / ub /
+ * lb (n), path as slp_dga_set_path, `draws` for a tie.  out[0] = the step, out[1] = status bits, out[2] = draws taken,
+ * out[3] = breakpoints. */
+int slp_dga_line_search(slp_matrix *a, const double *direction, const double *b, const double *c_bar, const double *ub,
+                        const double *lb, int path, const double *draws, int64_t ndraws, double out[4]);
+
 /* ---- synthetic random LP on the device (randomLP.py:14-75) -------------- *
  * Row r of A_ineq (global row index row_offset + r): every entry is non-zero
  * with probability `density`, value round(N(0,1)*100)/100, exact zeros

@@ -11,9 +11,9 @@ first-order solvers need (reference SparseLP.py:162-1383): the LP is held as
 with scipy CSR matrices, and ``solve`` (reference :990-1002, :1064-1093,
 :1193-1208, :1243-1288, :1378-1383) runs one of the GPU solvers and fills the
 same convergence-curve attributes.  The hot-path methods ``"admm"`` and
-``"chambolle_pock_ppd"``, the block-splitting ``"admm_blocks"`` and ``"admm2"`` (ADMM with exact equality projections)
-exist here; the other solvers of the reference
-(interior point, dual ascent, external solver bridges, rounding heuristics,
+``"chambolle_pock_ppd"``, the block-splitting ``"admm_blocks"``, ``"admm2"`` (ADMM with exact equality projections) and
+``"dual_gradient_ascent"`` (exact line search in the dual) exist here; the other solvers of the reference
+(interior point, dual coordinate ascent, external solver bridges, rounding heuristics,
 MPS export) are out of scope.
 """
 import copy
@@ -28,6 +28,8 @@ from .ChambollePockPPD import chambolle_pock_ppd
 from ._lib import ORDER_AUTO
 
 solving_methods = ("chambolle_pock_ppd", "admm", "admm_blocks", "admm2")
+# methods that ascend in the dual and return feasible multipliers; ``solve`` accepts ``solving_methods + dual_methods``
+dual_methods = ("dual_gradient_ascent",)
 
 _SCALARS = (int, float, np.integer, np.floating)
 
@@ -384,6 +386,10 @@ class SparseLP:
         ``"admm2"`` is the reference's ``lp_admm2`` (ADMM.py:272-474) with its KKT solves matrix-free (conjugate gradients on
         the device, see ``ADMM.lp_admm2``); ``setup`` and ``order`` do not apply to it.
 
+        ``"dual_gradient_ascent"`` (one of ``dual_methods``) is the reference's method of that name (SparseLP.py:1290-1300,
+        ``DualGradientAscent.dual_gradient_ascent``): it reports every 100 iterations whatever ``nb_iter_plot``, refuses a finite
+        ``b_lower`` with ``ValueError``, and runs as a replica under a communicator; ``setup`` and ``order`` do not apply.
+
         Fills, at every report (every ``nb_iter_plot`` iterations): ``itrn_curve,
         opttime_curve, dopttime_curve, pobj_curve, dobj_curve,
         max_violated_constraint, max_violated_equality, max_violated_inequality,
@@ -391,8 +397,10 @@ class SparseLP:
         As in the reference, ``callback_func`` is accepted and unused (it is
         shadowed by the internal bookkeeping callback, reference :997,:1064).
         """
-        if method not in solving_methods:
-            raise ValueError(f"method {method!r} not valid; available methods: {solving_methods}")
+        if method not in solving_methods + dual_methods:
+            raise ValueError(f"method {method!r} not valid; available methods: {solving_methods + dual_methods}")
+        if method == "dual_gradient_ascent" and self.b_lower is not None and np.size(self.b_lower) and np.max(self.b_lower) != -np.inf:
+            raise ValueError("dual_gradient_ascent needs one-sided inequalities: b_lower must be None or all -inf")
         a_ineq = self.a_inequalities if (self.a_inequalities is not None and self.a_inequalities.shape[0] > 0) else None
         a_eq, b_eq = (self.a_equalities, self.b_equalities) if self.a_equalities.shape[0] > 0 else (None, None)
         if a_ineq is not None:
@@ -442,6 +450,11 @@ class SparseLP:
 
             x = lp_admm2(self.costsvector, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds, self.upper_bounds,
                          nb_iter=nb_iter, x0=x0, callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
+        elif method == "dual_gradient_ascent":  # reference :1290-1300
+            from .DualGradientAscent import dual_gradient_ascent
+
+            x, _, _ = dual_gradient_ascent(x=x0, lp=self, nb_max_iter=nb_iter, callback_func=record, y_eq=None, y_ineq=None,
+                                           max_time=max_time, nb_iter_plot=nb_iter_plot)
         else:  # chambolle_pock_ppd: fixed variables are eliminated first (reference :1244-1248)
             from . import host_setup
             from .ChambollePockPPD import _cp_loop, close_device_cp, device_cp

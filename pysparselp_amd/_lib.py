@@ -123,6 +123,20 @@ _SIGNATURES = {
     "slp_admm2_cg_steps": (c_i64, [c_vp]),
     "slp_admm2_get_x": (c_int, [c_vp, c_vp, c_i64]),
     "slp_admm2_projection_residual": (c_int, [c_vp, c_vp]),
+    "slp_dga_create_on": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "slp_dga_destroy": (None, [c_vp]),
+    "slp_dga_set_path": (c_int, [c_vp, c_int]),
+    "slp_dga_path": (c_int, [c_vp]),
+    "slp_dga_iterate": (c_int, [c_vp, c_i64]),
+    "slp_dga_iterations": (c_i64, [c_vp]),
+    "slp_dga_push_random": (c_int, [c_vp, c_vp, c_i64]),
+    "slp_dga_status": (c_int, [c_vp, c_vp]),
+    "slp_dga_get_x": (c_int, [c_vp, c_vp]),
+    "slp_dga_get_y": (c_int, [c_vp, c_vp]),
+    "slp_dga_report": (c_int, [c_vp, c_vp]),
+    "slp_dga_timing": (c_int, [c_vp, c_int]),
+    "slp_dga_timing_read": (c_int, [c_vp, c_vp]),
+    "slp_dga_line_search": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp]),
     "slp_admm_cg_create_on_two_sided": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),
     "slp_admm_cg_create_on_lp": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int, c_int]),
     "slp_admm_cg_create_lp": (c_vp, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
