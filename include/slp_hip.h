@@ -228,6 +228,40 @@ int slp_cp_get_preconditioners(slp_cp *s, double *t, double *sigma); /* n, m */
  * (SpMV^T + update), ms[2] dual kernel (SpMV + update). */
 int slp_cp_bench(slp_cp *s, int64_t k, double ms[3]);
 
+/* ---- batched Chambolle-Pock: `batch` LPs over one constraint matrix ------ *
+ * No counterpart in the reference: `batch` calls of chambolle_pock_ppd (ChambollePockPPD.py:36-346) on LPs that share
+ * K = [A_eq; A_ineq] and differ in c and, optionally, in b, lb, ub, x0, advanced together -- two launches per iteration
+ * for all of them.  The matrix is read once per row and launch, T and Sigma (:122-179: functions of K and alpha only) exist
+ * once, the iterates lie instance-fastest (csrc/slp_cp_batch.hip).  Every instance walks its rows in storage order with one
+ * accumulator: bit for bit the iterate of slp_cp in SLP_ORDER_SEQUENTIAL on that instance, at any row length.
+ * c is [batch x n], row-major; b [m_eq + m_ineq], lb, ub, x0 [n] are one shared vector (*_batched = 0), which the library
+ * replicates, or [batch x len] (*_batched = 1); x0 may be NULL (zeros, :91-94).  The inequalities are already one-sided
+ * (:74-88).  NULL + slp_last_error(), and nothing left allocated: batch < 1; the device memory for the batched vectors
+ * ((5 n + 2 m) * 8 * batch bytes for x, z, c, lb, ub, y, b, plus x4 of the report, the staging of one host vector and
+ * the matrix) is not free -- checked with slp_device_memory before anything is allocated or any batched argument is read;
+ * a column index out of range. */
+typedef struct slp_cp_batch slp_cp_batch;
+slp_cp_batch *slp_cp_batch_create(int64_t n, int64_t m_eq, int64_t m_ineq, const int64_t *indptr, const int32_t *indices,
+                                  const double *data, int64_t batch, const double *b, int b_batched, const double *c,
+                                  const double *lb, int lb_batched, const double *ub, int ub_batched, const double *x0,
+                                  int x0_batched, double alpha, double theta);
+void slp_cp_batch_destroy(slp_cp_batch *s);
+/* k whole iterations (:198-240,:333-342) of every instance, enqueued as plain launches without host synchronisation. */
+int slp_cp_batch_iterate(slp_cp_batch *s, int64_t k);
+/* The two halves of a reporting iteration, as slp_cp_primal_step / slp_cp_dual_step (:242-329 sits between them). */
+int slp_cp_batch_primal_step(slp_cp_batch *s);
+int slp_cp_batch_dual_step(slp_cp_batch *s);
+/* out[5 k + 0..4]: the five numbers of slp_cp_report (:248-283) for instance k, same conventions for absent row kinds.
+ * The maxima are exact; the two energies are sums in a fixed order of their own (slices of rows, then the slices). */
+int slp_cp_batch_report(slp_cp_batch *s, double *out);  /* batch x 5 */
+int slp_cp_batch_get_x(slp_cp_batch *s, double *x);     /* batch x n, row-major (:345) */
+int slp_cp_batch_get_y(slp_cp_batch *s, double *y);     /* batch x (m_eq + m_ineq) */
+/* The shared T[n], Sigma[m] (:122-179): those of slp_cp_get_preconditioners on the same K and alpha.  Either may be NULL. */
+int slp_cp_batch_get_preconditioners(slp_cp_batch *s, double *t, double *sigma);
+/* As slp_cp_bench, per batched iteration (:198-240,:333-342 for all instances): ms[0] iteration, ms[1] primal kernel,
+ * ms[2] dual kernel. */
+int slp_cp_batch_bench(slp_cp_batch *s, int64_t k, double ms[3]);
+
 /* ---- projected Gauss-Seidel: replaces gaussSiedel.pyx ------------------- *
  * boundedGaussSeidelClass.__init__ (gaussSiedel.pyx:87-92) and .solve
  * (:95-153).  The sweep keeps the reference's lexicographic data dependence

@@ -9,6 +9,11 @@ iteration 0), same return value ``(x[:n], best_integer_solution)``.
 The host keeps only the control flow; the preconditioners, every SpMV / SpMV^T,
 the projections and the report reductions run on the GPU
 (pysparselp_amd/csrc/slp_cp.hip) through the C ABI of include/slp_hip.h.
+
+``chambolle_pock_ppd_batch`` (extension) solves B LPs that share the constraint
+matrices and differ in ``c`` (optionally in the right-hand sides, the bounds and
+``x0``) together: two launches per iteration for all of them
+(pysparselp_amd/csrc/slp_cp_batch.hip).
 """
 import time
 
@@ -313,3 +318,251 @@ def chambolle_pock_ppd(
     if best_integer_solution is not None:
         best_integer_solution = best_integer_solution[:n]
     return x[:n], best_integer_solution
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# batched form: B LPs over one constraint structure
+def _batched(name, v, batch, size):
+    """``v`` as float64, shape ``(size,)`` (shared by the instances) or ``(batch, size)``; returns ``(array, is_batched)``."""
+    v = np.asarray(v, dtype=np.float64)
+    if v.shape == (size,):
+        return np.ascontiguousarray(v), False
+    if v.shape == (batch, size):
+        return np.ascontiguousarray(v), True
+    raise ValueError(f"{name} has shape {v.shape}: expected ({size},) shared by the instances, or ({batch}, {size})")
+
+
+def one_sided_system_batch(a_ineq, b_lower, b_upper):
+    """``one_sided_system`` for right-hand sides that may carry a leading instance axis: the row selection (which bounds are
+    finite, reference :74-88) must be the same for every instance -- ``ValueError`` otherwise --, the structure is that of
+    ``one_sided_system`` and the selection is applied to every instance's bounds.  Returns ``(mat, b)``, ``b`` of shape
+    ``(rows,)`` when both bounds are shared, else ``(B, rows)``."""
+    b_upper = np.asarray(b_upper, dtype=np.float64)
+    lower = None if b_lower is None else np.asarray(b_lower, dtype=np.float64)
+    if b_upper.ndim == 1 and (lower is None or lower.ndim == 1):
+        return one_sided_system(a_ineq, lower, b_upper)
+    batch = b_upper.shape[0] if b_upper.ndim == 2 else lower.shape[0]
+    bu = np.broadcast_to(b_upper, (batch, b_upper.shape[-1]))
+    if lower is None:
+        # (as the reference: without b_lower no row is selected, infinite upper bounds stay)
+        mat, _ = one_sided_system(a_ineq, None, bu[0])
+        return mat, np.ascontiguousarray(bu)
+    bl = np.broadcast_to(lower, (batch, lower.shape[-1]))
+    up_mask, lo_mask = bu != np.inf, bl != -np.inf
+    if np.any(up_mask != up_mask[0]) or np.any(lo_mask != lo_mask[0]):
+        k = int(np.nonzero(np.any(up_mask != up_mask[0], axis=1) | np.any(lo_mask != lo_mask[0], axis=1))[0][0])
+        raise ValueError(f"instance {k} has another pattern of finite b_lower / b_upper than instance 0: the one-sided stacking "
+                         "(which rows exist) must be the same for all instances of a batch")
+    mat, _ = one_sided_system(a_ineq, bl[0], bu[0])
+    up, lo = np.nonzero(up_mask[0])[0], np.nonzero(lo_mask[0])[0]
+    return mat, np.ascontiguousarray(np.hstack((bu[:, up], -bl[:, lo])))
+
+
+class CPBatchState:
+    """Device-resident batched Chambolle-Pock state (thin RAII wrapper of ``slp_cp_batch``): ``c`` is ``(B, n)``; ``beq``,
+    ``b_ineq``, ``lb``, ``ub``, ``x0`` are shared vectors or carry a leading axis ``B``; ``ineq`` as ``CPState``'s."""
+
+    def __init__(self, c, a_eq, beq, ineq, b_ineq, lb, ub, x0, alpha, theta):
+        c = _lib.f64(c)
+        if c.ndim != 2 or c.shape[0] < 1:
+            raise ValueError(f"c has shape {c.shape}: expected (B, n) with B >= 1")
+        self.batch, self.n = c.shape
+        lb, lb_b = _batched("lb", lb, self.batch, self.n)
+        ub, ub_b = _batched("ub", ub, self.batch, self.n)
+        x0, x0_b = (None, False) if x0 is None else _batched("x0", x0, self.batch, self.n)
+        parts_ptr, parts_idx, parts_val, parts_b = [np.zeros(1, dtype=np.int64)], [], [], []
+        self.m_eq = 0
+        if a_eq is not None:
+            p, j, v = _lib.csr_arrays(a_eq)
+            self.m_eq = a_eq.shape[0]
+            parts_ptr.append(p[1:])
+            parts_idx.append(j)
+            parts_val.append(v)
+            parts_b.append(_batched("beq", beq, self.batch, self.m_eq))
+        self.m_ineq = 0
+        if ineq is not None:
+            p, j, v, rows = ineq
+            self.m_ineq = rows
+            off = parts_ptr[-1][-1] if len(parts_ptr) > 1 else 0
+            parts_ptr.append(off + p[1:])
+            parts_idx.append(j)
+            parts_val.append(v)
+            parts_b.append(_batched("b_ineq", b_ineq, self.batch, rows))
+        indptr = np.ascontiguousarray(np.concatenate(parts_ptr), dtype=np.int64)
+        indices = np.ascontiguousarray(np.concatenate(parts_idx) if parts_idx else np.zeros(0), dtype=np.int32)
+        data = _lib.f64(np.concatenate(parts_val) if parts_val else np.zeros(0))
+        if indices.size and (indices.min() < 0 or indices.max() >= self.n):
+            raise ValueError("constraint matrix has a column index outside [0, n)")
+        if self.m_eq + self.m_ineq == 0:
+            raise ValueError("no constraint rows: chambolle_pock_ppd_batch returns the box vertex without a solver state")
+        b_b = any(flag for _, flag in parts_b)
+        if b_b:  # one kind of rows shared, the other per instance: the shared part is replicated here
+            b = np.ascontiguousarray(np.hstack([v if flag else np.broadcast_to(v, (self.batch, v.size)) for v, flag in parts_b]))
+        else:
+            b = np.ascontiguousarray(np.concatenate([v for v, _ in parts_b]))
+        # all of the above needs no GPU; the library is loaded (and bound to a device) only now
+        self._l = _lib.lib()
+        self._h = _lib.check_handle(self._l.slp_cp_batch_create(
+            self.n, self.m_eq, self.m_ineq, _lib.ptr(indptr), _lib.ptr(indices), _lib.ptr(data), self.batch, _lib.ptr(b), int(b_b),
+            _lib.ptr(c), _lib.ptr(lb), int(lb_b), _lib.ptr(ub), int(ub_b), _lib.ptr(x0), int(x0_b), float(alpha), float(theta)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._l.slp_cp_batch_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def iterate(self, k):
+        _lib.check(self._l.slp_cp_batch_iterate(self._h, int(k)))
+
+    def primal_step(self):
+        _lib.check(self._l.slp_cp_batch_primal_step(self._h))
+
+    def dual_step(self):
+        _lib.check(self._l.slp_cp_batch_dual_step(self._h))
+
+    def report(self):
+        """``(B, 5)``: energy1, energy2, max |A_e z - b_e|, max (A_i x - b_i), max |A_e x - b_e| per instance."""
+        out = np.zeros((self.batch, 5))
+        _lib.check(self._l.slp_cp_batch_report(self._h, _lib.ptr(out)))
+        return out
+
+    def x(self):
+        out = np.empty((self.batch, self.n))
+        _lib.check(self._l.slp_cp_batch_get_x(self._h, _lib.ptr(out)))
+        return out
+
+    def y(self):
+        out = np.empty((self.batch, self.m_eq + self.m_ineq))
+        _lib.check(self._l.slp_cp_batch_get_y(self._h, _lib.ptr(out)))
+        return out
+
+    def preconditioners(self):
+        t, s = np.empty(self.n), np.empty(self.m_eq + self.m_ineq)
+        _lib.check(self._l.slp_cp_batch_get_preconditioners(self._h, _lib.ptr(t), _lib.ptr(s)))
+        return t, s
+
+    def bench(self, k):
+        ms = np.zeros(3)
+        _lib.check(self._l.slp_cp_batch_bench(self._h, int(k), _lib.ptr(ms)))
+        return ms
+
+
+def _cp_batch_loop(state, c, has_ineq, nb_max_iter, nb_iter_plot, callback_func, max_time, start):
+    """``_cp_loop`` for a batched state: same cadence; the report's numbers are arrays of length B, ``max_time`` stops the whole
+    batch, the best feasible iterate (:284-291 with force_integer=False) is kept per instance."""
+    batch = c.shape[0]
+    best_energy = np.full(batch, np.inf)
+    best = [None] * batch
+    niter = 0
+    while niter < nb_max_iter:
+        if niter % nb_iter_plot == 0:
+            state.primal_step()
+            elapsed = time.perf_counter() - start
+            if (max_time is not None) and collective_elapsed(elapsed) > max_time:
+                break
+            energy1, energy2, max_violated_equality, max_violated_inequality, max_eq_at_x = state.report().T.copy()
+            if not has_ineq:
+                max_violated_inequality = np.zeros(batch)
+            x = None
+            feasible = np.nonzero((max_eq_at_x == 0) & (max_violated_inequality <= 0))[0]
+            if feasible.size:
+                x = state.x()
+                for k in feasible:
+                    energy_rounded = c[k].dot(x[k])
+                    if energy_rounded < best_energy[k]:
+                        best_energy[k] = energy_rounded
+                        best[k] = x[k].copy()
+            if callback_func is not None:
+                if x is None:
+                    x = state.x()
+                callback_func(niter, x, energy1, energy2, elapsed, max_violated_equality, max_violated_inequality)
+            state.dual_step()
+            niter += 1
+        else:
+            k = min(nb_iter_plot - niter % nb_iter_plot, nb_max_iter - niter)
+            state.iterate(k)
+            niter += k
+    return state.x(), best
+
+
+def chambolle_pock_ppd_batch(
+    c,
+    a_eq,
+    beq,
+    a_ineq,
+    b_lower,
+    b_upper,
+    lb,
+    ub,
+    x0=None,
+    alpha=1,
+    theta=1,
+    nb_max_iter=100,
+    callback_func=None,
+    max_time=None,
+    nb_iter_plot=10,
+):
+    """``chambolle_pock_ppd`` for B LPs at once (extension; the reference solves one LP per call):
+    minimise ``c[k].x``  s.t.  ``a_eq x = beq[k]``, ``b_lower[k] <= a_ineq x <= b_upper[k]``, ``lb[k] <= x <= ub[k]`` for every k.
+
+    ``c`` has shape ``(B, n)``; ``beq``, ``b_lower``, ``b_upper``, ``lb``, ``ub``, ``x0`` each have their single-instance shape
+    (shared by all instances) or a leading axis ``B``.  The instances share the constraint matrices, hence the one-sided
+    stacking (:74-88): which of ``b_lower`` / ``b_upper`` are finite must be the same for every instance (``ValueError``
+    otherwise, like every shape error raised before anything is uploaded).  All B iterates advance in the same two launches
+    per iteration; every instance is bit for bit what ``chambolle_pock_ppd(..., order=ORDER_SEQUENTIAL)`` computes for it.
+
+    The reporting loop is that of ``chambolle_pock_ppd``: ``callback_func(niter, X, energy1, energy2, elapsed,
+    max_violated_equality, max_violated_inequality)`` every ``nb_iter_plot`` iterations with ``X`` of shape ``(B, n)`` and arrays
+    of length B; ``max_time`` stops the whole batch at a report.  Returns ``(X, best_integer_solutions)``, the latter a list
+    of B entries (``None`` or the best feasible iterate of that instance, :284-291).  Without any constraint it returns the
+    box vertex of every instance, ``X`` alone, as the reference does (:147-151).
+
+    Under a communicator every rank solves the whole batch (a replica): the rows are not partitioned.
+    """
+    start = time.perf_counter()
+    c = np.asarray(c, dtype=np.float64)
+    if c.ndim != 2:
+        raise ValueError(f"c has shape {c.shape}: expected (B, n), one row of costs per instance")
+    batch, n = c.shape
+    if batch < 1:
+        raise ValueError("an empty batch: c needs at least one row (B >= 1)")
+    c = np.ascontiguousarray(c)
+    lb, _ = _batched("lb", lb, batch, n)
+    ub, _ = _batched("ub", ub, batch, n)
+    if x0 is not None:
+        x0, _ = _batched("x0", x0, batch, n)
+    if a_eq is not None and a_eq.shape[0] == 0:  # reference :70-72
+        a_eq, beq = None, None
+    if a_ineq is not None and a_ineq.shape[0] == 0:
+        a_ineq = None
+    for name, a in (("a_eq", a_eq), ("a_ineq", a_ineq)):
+        if a is not None:
+            if a.shape[1] != n:
+                raise ValueError(f"{name} has {a.shape[1]} columns, c has {n}")
+            if a.indices.size and (a.indices.min() < 0 or a.indices.max() >= n):
+                raise ValueError(f"{name} has a column index outside [0, {n})")
+    if a_eq is not None:
+        beq, _ = _batched("beq", beq, batch, a_eq.shape[0])
+    if a_eq is None and a_ineq is None:  # reference :147-151: no constraints, a vertex of the box per instance
+        lbb, ubb = np.broadcast_to(lb, c.shape), np.broadcast_to(ub, c.shape)
+        x = np.zeros(c.shape)
+        x[c > 0] = lbb[c > 0]
+        x[c < 0] = ubb[c < 0]
+        return x
+    ineq, b_ineq = (None, None)
+    if a_ineq is not None:
+        rows = a_ineq.shape[0]
+        b_upper, _ = _batched("b_upper", b_upper, batch, rows)
+        if b_lower is not None:
+            b_lower, _ = _batched("b_lower", b_lower, batch, rows)
+        ineq, b_ineq = one_sided_system_batch(a_ineq, b_lower, b_upper)
+        assert b_ineq.shape[-1] == ineq[3]
+
+    state = CPBatchState(c, a_eq, beq, ineq, b_ineq, lb, ub, x0, alpha, theta)
+    try:
+        x, best = _cp_batch_loop(state, c, a_ineq is not None, nb_max_iter, nb_iter_plot, callback_func, max_time, start)
+    finally:
+        state.close()
+    return x, best

@@ -24,12 +24,14 @@ import numpy as np
 import scipy.sparse
 
 from .ADMM import lp_admm
-from .ChambollePockPPD import chambolle_pock_ppd
+from .ChambollePockPPD import chambolle_pock_ppd, chambolle_pock_ppd_batch
 from ._lib import ORDER_AUTO
 
 solving_methods = ("chambolle_pock_ppd", "admm", "admm_blocks", "admm2")
 # methods that ascend in the dual and return feasible multipliers; ``solve`` accepts ``solving_methods + dual_methods``
 dual_methods = ("dual_gradient_ascent",)
+# methods of ``solve_batch``: many cost vectors over this LP's constraints, advanced together
+batch_methods = ("chambolle_pock_ppd",)
 
 _SCALARS = (int, float, np.integer, np.floating)
 
@@ -491,5 +493,77 @@ class SparseLP:
                                           callback_func=record_reduced, max_time=max_time, nb_iter_plot=nb_iter_plot,
                                           order=order, setup="host")
             x = expand(x)
+        elapsed = time.perf_counter() - start
+        return (x, elapsed) if get_timing else x
+
+    def solve_batch(
+        self,
+        costs,
+        method="chambolle_pock_ppd",
+        get_timing=True,
+        nb_iter=10000,
+        max_time=None,
+        nb_iter_plot=10,
+        ground_truth=None,
+        ground_truth_indices=None,
+    ):
+        """Solve this LP once for every row of ``costs`` (shape ``(B, nb_variables)``) in place of ``costsvector``, all B solves
+        advancing together on the GPU (extension: the reference solves one LP per call); returns ``(X, elapsed)`` or ``X``,
+        ``X`` of shape ``(B, nb_variables)``.
+
+        Only ``method="chambolle_pock_ppd"`` exists in batched form (``ChambollePockPPD.chambolle_pock_ppd_batch``); any other
+        raises ``ValueError``.  Bounds and right-hand sides are the LP's own, so ``remove_fixed_variables`` is one reduction for
+        all instances, done once on the host as ``solve(setup="host")`` does (reference :1244-1248); ``X[k]`` and the k-th
+        component of every curve are what ``solve(method="chambolle_pock_ppd", order=ORDER_SEQUENTIAL)`` gives on a copy of the LP
+        whose ``costsvector`` is ``costs[k]`` (``x`` bit for bit).
+
+        Fills the curve attributes of ``solve`` at every report: ``itrn_curve``, ``opttime_curve``, ``dopttime_curve`` are lists of
+        scalars; ``pobj_curve``, ``dobj_curve``, ``max_violated_equality``, ``max_violated_inequality``, ``max_violated_constraint``
+        (and, with ``ground_truth``, the two distance curves) are lists of arrays of length B.  ``max_time`` stops the whole
+        batch.  Under a communicator every rank solves the whole batch (a replica).
+        """
+        if method not in batch_methods:
+            raise ValueError(f"method {method!r} has no batched form; solve_batch supports: {batch_methods}")
+        costs = np.asarray(costs, dtype=np.float64)
+        if costs.ndim != 2 or costs.shape[1] != self.nb_variables:
+            raise ValueError(f"costs has shape {costs.shape}: expected (B, {self.nb_variables}), one row per instance")
+        batch = costs.shape[0]
+        if batch < 1:
+            raise ValueError("an empty batch: costs needs at least one row (B >= 1)")
+        start = time.perf_counter()
+        for name in ("distance_to_ground_truth", "distanceToGroundTruthAfterRounding", "opttime_curve", "dopttime_curve",
+                     "pobj_curve", "dobj_curve", "pobjbound", "max_violated_inequality", "max_violated_equality",
+                     "max_violated_constraint", "itrn_curve"):
+            setattr(self, name, [])
+        reduced = copy.deepcopy(self)
+        free, shift = reduced.remove_fixed_variables()
+        free_ids = np.nonzero(free)[0]
+
+        def expand(sol):
+            # reference :1259,:1288 per instance: x = m_change * sol - shift (note the sign it applies to the fixed values)
+            full = np.zeros((sol.shape[0], free.size))
+            full[:, free_ids] = sol
+            return full - shift
+
+        def record(niter, solution, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
+            solution = expand(solution)
+            if ground_truth is not None:
+                picked = solution[:, ground_truth_indices]
+                axes = tuple(range(1, picked.ndim))
+                self.distance_to_ground_truth.append(np.mean(np.abs(ground_truth - picked), axis=axes))
+                self.distanceToGroundTruthAfterRounding.append(np.mean(np.abs(ground_truth - np.round(picked)), axis=axes))
+            self.itrn_curve.append(niter)
+            self.opttime_curve.append(duration)
+            self.dopttime_curve.append(duration)
+            self.dobj_curve.append(np.array(energy2, dtype=np.float64))
+            self.pobj_curve.append(np.array(energy1, dtype=np.float64))
+            self.max_violated_constraint.append(np.array([self.max_constraint_violation(solution[k]) for k in range(batch)]))
+            self.max_violated_equality.append(np.array(max_violated_equality, dtype=np.float64))
+            self.max_violated_inequality.append(np.array(max_violated_inequality, dtype=np.float64))
+
+        res = chambolle_pock_ppd_batch(costs[:, free], reduced.a_equalities, reduced.b_equalities, reduced.a_inequalities,
+                                       reduced.b_lower, reduced.b_upper, reduced.lower_bounds, reduced.upper_bounds, x0=None, alpha=1,
+                                       theta=1, nb_max_iter=nb_iter, callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
+        x = expand(res[0] if isinstance(res, tuple) else res)
         elapsed = time.perf_counter() - start
         return (x, elapsed) if get_timing else x

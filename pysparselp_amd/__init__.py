@@ -4,9 +4,11 @@
 signature (modules mirror the reference's: ``SparseLP``, ``ADMM``, ``ChambollePockPPD``, ``ADMMBlocks``,
 ``gaussSiedel``, ``MPSparser``, ``netlib``, ``tools``; ``device`` / ``scale`` / ``problems`` / ``parallel`` hold the
 device-resident, at-scale and multi-GPU entry points); the inner loops run in hand-written HIP kernels (libslp_hip.so,
-C ABI in include/slp_hip.h).  There is no CPU fallback: without the built
+C ABI in include/slp_hip.h).  ``SparseLP.solve_batch`` / ``chambolle_pock_ppd_batch`` solve many cost vectors over one
+constraint matrix together (Chambolle-Pock, all instances per launch).  There is no CPU fallback: without the built
 library and a HIP device every solver call raises ``SlpError``.
 """
 from ._lib import ORDER_AUTO, ORDER_SEQUENTIAL, ORDER_TREE, SlpError  # noqa: F401
+from .ChambollePockPPD import CPBatchState, chambolle_pock_ppd_batch  # noqa: F401
 
-__all__ = ["ORDER_AUTO", "ORDER_SEQUENTIAL", "ORDER_TREE", "SlpError"]
+__all__ = ["ORDER_AUTO", "ORDER_SEQUENTIAL", "ORDER_TREE", "SlpError", "CPBatchState", "chambolle_pock_ppd_batch"]

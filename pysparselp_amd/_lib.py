@@ -78,6 +78,17 @@ _SIGNATURES = {
     "slp_cp_get_y": (c_int, [c_vp, c_vp]),
     "slp_cp_get_preconditioners": (c_int, [c_vp, c_vp, c_vp]),
     "slp_cp_bench": (c_int, [c_vp, c_i64, c_vp]),
+    "slp_cp_batch_create": (c_vp, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int,
+                                   c_dbl, c_dbl]),
+    "slp_cp_batch_destroy": (None, [c_vp]),
+    "slp_cp_batch_iterate": (c_int, [c_vp, c_i64]),
+    "slp_cp_batch_primal_step": (c_int, [c_vp]),
+    "slp_cp_batch_dual_step": (c_int, [c_vp]),
+    "slp_cp_batch_report": (c_int, [c_vp, c_vp]),
+    "slp_cp_batch_get_x": (c_int, [c_vp, c_vp]),
+    "slp_cp_batch_get_y": (c_int, [c_vp, c_vp]),
+    "slp_cp_batch_get_preconditioners": (c_int, [c_vp, c_vp, c_vp]),
+    "slp_cp_batch_bench": (c_int, [c_vp, c_i64, c_vp]),
     "slp_gs_create": (c_vp, [c_i64, c_vp, c_vp, c_vp]),
     "slp_gs_destroy": (None, [c_vp]),
     "slp_gs_num_levels": (c_i64, [c_vp]),

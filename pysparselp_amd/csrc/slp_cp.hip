@@ -10,14 +10,6 @@
 
 namespace slp {
 
-// np.minimum(np.maximum(x2, lb), ub) (ChambollePockPPD.py:221-222) as numpy computes it: a NaN stays, and of two equal operands
-// the SECOND is returned (x86 maxpd / minpd) -- x2 = -0.0 against a bound +0.0 gives +0.0, and a bound -0.0 against x2 = +0.0
-// gives -0.0 (the generator rounds bounds to 0.01: lb = -0.0, ub = +0.0 occurs).
-__device__ __forceinline__ double cp_clip(double x2, double l, double u) {
-    x2 = (x2 > l || x2 != x2) ? x2 : l;
-    return (x2 < u || x2 != x2) ? x2 : u;
-}
-
 constexpr int kMaxPartials = 4096;
 
 // ---------------------------------------------------------------------------
@@ -665,6 +657,21 @@ static void cp_setup(slp_cp *s) {
     }
     // ELL copies are the solver's own; everything else that is not a strip copy walks the matrix's CSR arrays
     s->csr_bound = (s->n > 0 && !cp_primal_strips(s) && !s->split && !s->ell_w_cols) || (s->m > 0 && !fast_format(s->k, false) && !s->ell_w_rows);
+}
+
+// T and Sigma alone, by the CSR walks above, for a solver that is no slp_cp: the batched Chambolle-Pock (slp_cp_batch.hip), whose
+// instances share them.  One GPU, the whole K: no exchange, also under a communicator.
+void cp_preconditioners_csr(slp_matrix *k, i64 m_eq, double alpha, double *t, double *sigma) {
+    hipStream_t st = ctx().stream;
+    require_csr(k, "Chambolle-Pock preconditioners (CSR walk)");
+    build_transpose(k);
+    const CsrDev &a = k->a, &at = k->at;
+    if (a.ncol)
+        hipLaunchKernelGGL(k_cp_colsum, dim3(grid_for(a.ncol, kBlock)), dim3(kBlock), 0, st, a.ncol, at.ptr.p, at.idx.p, at.val.p, (i32)m_eq,
+                           a.nrow - m_eq, 2.0 - alpha, t, 1);
+    if (a.nrow)
+        hipLaunchKernelGGL(k_cp_rowsum, dim3(grid_for(a.nrow, kBlock)), dim3(kBlock), 0, st, a.nrow, a.ptr.p, a.val.p, alpha, sigma);
+    SLP_HIP(hipGetLastError());
 }
 
 static void cp_primal(slp_cp *s, bool store_d) {

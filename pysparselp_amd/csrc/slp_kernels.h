@@ -73,6 +73,14 @@ __device__ __forceinline__ double abs_pow(double a, double p) {
     return pow(a, p);
 }
 
+// np.minimum(np.maximum(x2, lb), ub) (ChambollePockPPD.py:221-222) as numpy computes it: a NaN stays, and of two equal operands
+// the SECOND is returned (x86 maxpd / minpd) -- x2 = -0.0 against a bound +0.0 gives +0.0, and a bound -0.0 against x2 = +0.0
+// gives -0.0 (the generator rounds bounds to 0.01: lb = -0.0, ub = +0.0 occurs).
+__device__ __forceinline__ double cp_clip(double x2, double l, double u) {
+    x2 = (x2 > l || x2 != x2) ? x2 : l;
+    return (x2 < u || x2 != x2) ? x2 : u;
+}
+
 // ---- one row . dense vector -------------------------------------------------
 // L == 1: storage order, single accumulator (bit-exact csr_matvec semantics).
 // L  > 1: lane `sub` of the row's L-lane group takes entries sub, sub+L, ...;
