@@ -335,6 +335,46 @@ int64_t slp_admm_num_levels(const slp_admm *s);
 int slp_admm_num_bands(const slp_admm *s);
 int slp_admm_bench(slp_admm *s, int64_t k, double *ms);
 
+/* ---- batched ADMM (projected Gauss-Seidel x-step): `batch` LPs over one constraint structure ---- *
+ * No counterpart in the reference: `batch` calls of lp_admm (ADMM.py:47-269, as shipped: one projected Gauss-Seidel sweep per
+ * iteration, :135,:162) on LPs that share both constraint blocks and their right-hand sides and differ in c and, optionally, in
+ * lb, ub, x0.  The set-up chain of slp_admm_create_lp (ADMM.py:73-101) runs once; A, M, its level plan, A^T b and the slack bounds
+ * exist once, x, y, q and lambda per instance, instance-fastest in tiles (csrc/slp_admm_batch.hip).  Every dot product is formed by
+ * one lane in storage order with one accumulator: each instance is bit for bit the iterate of slp_admm in SLP_ORDER_SEQUENTIAL
+ * and of the reference.  The arguments are those of slp_admm_create_lp, plus: c is [batch x n] row-major (c_batched = 1; 0 only
+ * with batch == 1); lb, ub, x0 [n] are one shared vector (*_batched = 0) or [batch x n] (*_batched = 1); x0 may be NULL (zeros).
+ * Two forms of the iteration with the same arithmetic, chosen from the shapes and batch (SLP_ADMM_BATCH_FORM=tile|levels
+ * forces one): "tile" -- one workgroup per tile of instances runs whole iterations in one launch, no synchronisation wider than
+ * a workgroup barrier; "levels" -- one launch per dependency level over (row, instance) lanes.
+ * NULL + slp_last_error(), and nothing left allocated: batch < 1; no inequality block (tools.py:92); a column index out of
+ * range; the device memory for the batch -- (3 N + m + n) * 8 * batch bytes for x, y, q, lambda, c, N more per batched lb / ub /
+ * x0, N = n + m_ineq, plus the shared matrices -- is not free, checked with slp_device_memory before anything is allocated or
+ * any batched argument is read. */
+typedef struct slp_admm_batch slp_admm_batch;
+slp_admm_batch *slp_admm_batch_create_lp(int64_t n, int64_t m_eq, const int64_t *eq_indptr, const int32_t *eq_indices,
+                                         const double *eq_data, const double *b_eq, int64_t m_ineq, const int64_t *in_indptr,
+                                         const int32_t *in_indices, const double *in_data, const double *b_lower,
+                                         const double *b_upper, int64_t batch, const double *c, int c_batched, const double *lb,
+                                         int lb_batched, const double *ub, int ub_batched, const double *x0, int x0_batched,
+                                         double gamma_eq, double gamma_ineq, int use_preconditioning);
+void slp_admm_batch_destroy(slp_admm_batch *s);
+/* k whole iterations (:148,:162,:259-263) of every instance, enqueued without host synchronisation; the tile form puts up to a
+ * bounded number of them into one launch and splits longer runs. */
+int slp_admm_batch_iterate(slp_admm_batch *s, int64_t k);
+/* Halves of one iteration around the reference's report (:213-248), as slp_admm_sweep_step / slp_admm_multiplier_step. */
+int slp_admm_batch_sweep_step(slp_admm_batch *s);
+int slp_admm_batch_multiplier_step(slp_admm_batch *s);
+/* out[3 k + 0..2]: the three numbers of slp_admm_report (:124-132,:221,:222) for instance k.  The maxima are exact; the energy
+ * is a sum in a fixed order of its own (slices of rows, then the slices). */
+int slp_admm_batch_report(slp_admm_batch *s, double *out);                  /* batch x 3 */
+int slp_admm_batch_get_x(slp_admm_batch *s, double *x, int64_t count);      /* batch x count, row-major: first `count` entries (:268) */
+int slp_admm_batch_get_lambda(slp_admm_batch *s, double *lam);              /* batch x (m_eq + m_ineq) (:261-263) */
+int64_t slp_admm_batch_num_levels(const slp_admm_batch *s);                 /* dependency levels of M's sweep (gaussSiedel.pyx:131-152) */
+/* The form of the iteration: 0 tile, 1 levels. */
+int slp_admm_batch_form(const slp_admm_batch *s);
+/* As slp_admm_bench: average GPU milliseconds per batched iteration (:143-268 for all instances) over k, by HIP events. */
+int slp_admm_batch_bench(slp_admm_batch *s, int64_t k, double *ms);
+
 /* ---- ADMM, matrix-free conjugate-gradient x-step ------------------------- *
  * The reference's own alternative x-step (ADMM.py:182-201 with
  * conjugateGradientLinearSolver.py:30-52, selected by its hard-coded flags

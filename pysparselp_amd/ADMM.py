@@ -198,6 +198,198 @@ def lp_admm(
         state.close()
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# batched form: B LPs over one constraint structure
+def _shared_or_batched(name, v, batch, size):
+    """``v`` as float64, shape ``(size,)`` (shared by the instances) or ``(batch, size)``; returns ``(array, is_batched)``."""
+    v = np.asarray(v, dtype=np.float64)
+    if v.shape == (size,):
+        return np.ascontiguousarray(v), False
+    if v.shape == (batch, size):
+        return np.ascontiguousarray(v), True
+    raise ValueError(f"{name} has shape {v.shape}: expected ({size},) shared by the instances, or ({batch}, {size})")
+
+
+def _validate_batch(cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0):
+    """Everything ``lp_admm_batch`` can refuse without a GPU; returns the arguments as contiguous float64 arrays / CSR triples."""
+    from .tools import CsrArrays
+
+    cs = np.asarray(cs, dtype=np.float64)
+    if cs.ndim != 2:
+        raise ValueError(f"cs has shape {cs.shape}: expected (B, n), one row of costs per instance")
+    batch, n = cs.shape
+    if batch < 1:
+        raise ValueError("an empty batch: cs needs at least one row (B >= 1)")
+    if n < 1:
+        raise ValueError(f"cs has shape {cs.shape}: the LP needs at least one variable")
+    if not np.all(np.isfinite(cs)):
+        k = int(np.nonzero(~np.all(np.isfinite(cs), axis=1))[0][0])
+        raise ValueError(f"instance {k} has a cost that is not finite")
+    for name, v in (("beq", beq), ("b_lower", b_lower), ("b_upper", b_upper)):
+        if v is not None and np.ndim(v) != 1:
+            raise ValueError(f"{name} has shape {np.shape(v)}: the right-hand sides are shared by the instances of a batch "
+                             "(per-instance right-hand sides are not built)")
+    a_eq, a_ineq = CsrArrays.from_any(a_eq), CsrArrays.from_any(a_ineq)
+    if a_ineq is None:
+        raise ValueError("no inequality block: the reference cannot form the standard form without one (tools.py:92)")
+    for name, a in (("a_eq", a_eq), ("a_ineq", a_ineq)):
+        if a is not None:
+            if a.shape[1] != n:
+                raise ValueError(f"{name} has {a.shape[1]} columns, cs has {n}")
+            if a.indices.size and (a.indices.min() < 0 or a.indices.max() >= n):
+                raise ValueError(f"{name} has a column index outside [0, {n})")
+    m_eq, m_ineq = (0 if a_eq is None else a_eq.shape[0]), a_ineq.shape[0]
+
+    def rhs(name, v, rows):
+        if v is None:
+            return None
+        v = _lib.f64(v)
+        if v.shape != (rows,):
+            raise ValueError(f"{name} has shape {v.shape}: expected ({rows},)")
+        if np.any(np.isnan(v)):
+            raise ValueError(f"{name} has a NaN")
+        return v
+
+    beq = rhs("beq", beq, m_eq) if a_eq is not None else None
+    if a_eq is not None and beq is None:
+        raise ValueError("a_eq without beq")
+    b_lower, b_upper = rhs("b_lower", b_lower, m_ineq), rhs("b_upper", b_upper, m_ineq)
+    lb, lb_b = _shared_or_batched("lb", lb, batch, n)
+    ub, ub_b = _shared_or_batched("ub", ub, batch, n)
+    if np.any(np.isnan(lb)) or np.any(np.isnan(ub)):
+        raise ValueError("lb / ub has a NaN")
+    x0_b = False
+    if x0 is not None:
+        x0, x0_b = _shared_or_batched("x0", x0, batch, n)
+        if not np.all(np.isfinite(x0)):
+            raise ValueError("x0 has an entry that is not finite")
+    return np.ascontiguousarray(cs), a_eq, beq, a_ineq, b_lower, b_upper, lb, lb_b, ub, ub_b, x0, x0_b
+
+
+class ADMMBatchState:
+    """Device-resident batched ADMM state (thin RAII wrapper of ``slp_admm_batch``): ``cs`` is ``(B, n)``; ``lb``, ``ub``, ``x0``
+    are shared vectors or carry a leading axis ``B``; the constraint blocks and their right-hand sides are shared."""
+
+    def __init__(self, cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0=None, gamma_eq=2, gamma_ineq=3, use_preconditioning=True):
+        cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, lb_b, ub, ub_b, x0, x0_b = _validate_batch(cs, a_eq, beq, a_ineq, b_lower, b_upper,
+                                                                                                lb, ub, x0)
+        self.batch, self.n = cs.shape
+        m_eq = a_eq.shape[0] if a_eq is not None else 0
+        m_ineq = a_ineq.shape[0]
+        self.N, self.m = self.n + m_ineq, m_eq + m_ineq
+        eq = (None, None, None) if a_eq is None else (_lib.ptr(a_eq.indptr), _lib.ptr(a_eq.indices), _lib.ptr(a_eq.data))
+        # all of the above needs no GPU; the library is loaded (and bound to a device) only now
+        self._l = _lib.lib()
+        self._h = _lib.check_handle(self._l.slp_admm_batch_create_lp(
+            self.n, m_eq, *eq, _lib.ptr(beq), m_ineq, _lib.ptr(a_ineq.indptr), _lib.ptr(a_ineq.indices), _lib.ptr(a_ineq.data),
+            _lib.ptr(b_lower), _lib.ptr(b_upper), self.batch, _lib.ptr(cs), 1, _lib.ptr(lb), int(lb_b), _lib.ptr(ub), int(ub_b),
+            _lib.ptr(x0), int(x0_b), float(gamma_eq), float(gamma_ineq), int(bool(use_preconditioning))))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._l.slp_admm_batch_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def iterate(self, k):
+        _lib.check(self._l.slp_admm_batch_iterate(self._h, int(k)))
+
+    def sweep_step(self):
+        _lib.check(self._l.slp_admm_batch_sweep_step(self._h))
+
+    def multiplier_step(self):
+        _lib.check(self._l.slp_admm_batch_multiplier_step(self._h))
+
+    def report(self):
+        """``(B, 3)``: augmented-Lagrangian energy, max |A x - b|, max(0, -min x) per instance."""
+        out = np.zeros((self.batch, 3))
+        _lib.check(self._l.slp_admm_batch_report(self._h, _lib.ptr(out)))
+        return out
+
+    def x(self, count=None):
+        count = self.N if count is None else int(count)
+        out = np.empty((self.batch, count))
+        _lib.check(self._l.slp_admm_batch_get_x(self._h, _lib.ptr(out), count))
+        return out
+
+    def lam(self):
+        out = np.empty((self.batch, self.m))
+        _lib.check(self._l.slp_admm_batch_get_lambda(self._h, _lib.ptr(out)))
+        return out
+
+    def num_levels(self):
+        return int(self._l.slp_admm_batch_num_levels(self._h))
+
+    def form(self):
+        """``"tile"`` (one workgroup per tile of instances runs whole iterations) or ``"levels"`` (one launch per level)."""
+        return ("tile", "levels")[int(self._l.slp_admm_batch_form(self._h))]
+
+    def bench(self, k):
+        """GPU milliseconds per batched iteration over ``k`` iterations (HIP events)."""
+        ms = np.zeros(1)
+        _lib.check(self._l.slp_admm_batch_bench(self._h, int(k), _lib.ptr(ms)))
+        return float(ms[0])
+
+
+def lp_admm_batch(
+    cs,
+    a_eq,
+    beq,
+    a_ineq,
+    b_lower,
+    b_upper,
+    lb,
+    ub,
+    x0=None,
+    gamma_eq=2,
+    gamma_ineq=3,
+    nb_iter=100,
+    callback_func=None,
+    max_time=None,
+    use_preconditioning=True,
+    nb_iter_plot=10,
+):
+    """``lp_admm`` for B LPs at once (extension; the reference solves one LP per call): minimise ``cs[k].x``  s.t.
+    ``a_eq x = beq``, ``b_lower <= a_ineq x <= b_upper``, ``lb[k] <= x <= ub[k]`` for every k.
+
+    ``cs`` has shape ``(B, n)``; ``lb``, ``ub`` and ``x0`` each have shape ``(n,)`` (shared by all instances) or ``(B, n)``.
+    The right-hand sides are shared: a 2-D ``beq``, ``b_lower`` or ``b_upper`` raises ``ValueError`` (per-instance right-hand
+    sides are not built), like every shape, finiteness and column-index error, before anything is uploaded.  The instances
+    share the whole set-up chain (ADMM.py:73-101), ``M`` and its Gauss-Seidel plan; every instance is bit for bit what
+    ``lp_admm(..., order=ORDER_SEQUENTIAL)`` computes for it.
+
+    The loop is that of ``lp_admm``: ``nb_iter + 1`` sweeps, a report after those with ``i % nb_iter_plot == 0`` --
+    ``callback_func(i, X, energy, energy, elapsed, max_violated_equality, max_violated_inequality)`` with ``X`` of shape
+    ``(B, n)`` and arrays of length B; ``max_time`` stops the whole batch at a report.  Returns ``X``.
+
+    Under a communicator every rank solves the whole batch (a replica).
+    """
+    state = ADMMBatchState(cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, use_preconditioning)
+    n = state.n
+    try:
+        start = time.perf_counter()
+        i = 0
+        while i <= nb_iter:  # ADMM.py:143: nb_iter + 1 sweeps
+            if i % nb_iter_plot == 0:
+                state.sweep_step()
+                elapsed = time.perf_counter() - start
+                if max_time is not None and elapsed > max_time:
+                    break
+                energy, max_violated_equality, max_violated_inequality = state.report().T.copy()
+                if callback_func is not None:
+                    callback_func(i, state.x(n), energy, energy.copy(), elapsed, max_violated_equality, max_violated_inequality)
+                state.multiplier_step()
+                i += 1
+            else:
+                k = min(nb_iter_plot - i % nb_iter_plot, nb_iter + 1 - i)
+                state.iterate(k)
+                i += k
+        return state.x(n)
+    finally:
+        state.close()
+
+
 def lp_admm2(
     c,
     a_eq,

@@ -23,7 +23,7 @@ import numpy as np
 
 import scipy.sparse
 
-from .ADMM import lp_admm
+from .ADMM import lp_admm, lp_admm_batch
 from .ChambollePockPPD import chambolle_pock_ppd, chambolle_pock_ppd_batch
 from ._lib import ORDER_AUTO
 
@@ -565,5 +565,64 @@ class SparseLP:
                                        reduced.b_lower, reduced.b_upper, reduced.lower_bounds, reduced.upper_bounds, x0=None, alpha=1,
                                        theta=1, nb_max_iter=nb_iter, callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
         x = expand(res[0] if isinstance(res, tuple) else res)
+        elapsed = time.perf_counter() - start
+        return (x, elapsed) if get_timing else x
+
+    def solve_admm_batch(
+        self,
+        costs,
+        get_timing=True,
+        nb_iter=10000,
+        max_time=None,
+        nb_iter_plot=10,
+        ground_truth=None,
+        ground_truth_indices=None,
+    ):
+        """Solve this LP with ``method="admm"`` once for every row of ``costs`` (shape ``(B, nb_variables)``) in place of
+        ``costsvector``, all B solves advancing together on the GPU (``ADMM.lp_admm_batch``; extension: the reference solves one LP
+        per call); returns ``(X, elapsed)`` or ``X``, ``X`` of shape ``(B, nb_variables)``.
+
+        Bounds, constraints and right-hand sides are the LP's own.  ``X[k]`` and the k-th component of every curve are what
+        ``solve(method="admm", order=ORDER_SEQUENTIAL, setup="host")`` gives on a copy of the LP whose ``costsvector`` is
+        ``costs[k]`` (``x`` and the violation curves bit for bit, the energies to the rounding of another summation order).
+        ``solve_batch(method="admm")`` keeps refusing: the batched Chambolle-Pock and this method fill their curves alike but
+        report at different places of their iterations.
+
+        Fills the curve attributes of ``solve`` at every report: ``itrn_curve``, ``opttime_curve``, ``dopttime_curve`` are lists of
+        scalars; ``pobj_curve``, ``dobj_curve``, ``max_violated_equality``, ``max_violated_inequality``, ``max_violated_constraint``
+        (and, with ``ground_truth``, the two distance curves) are lists of arrays of length B.  ``max_time`` stops the whole
+        batch.  Under a communicator every rank solves the whole batch (a replica).
+        """
+        costs = np.asarray(costs, dtype=np.float64)
+        if costs.ndim != 2 or costs.shape[1] != self.nb_variables:
+            raise ValueError(f"costs has shape {costs.shape}: expected (B, {self.nb_variables}), one row per instance")
+        batch = costs.shape[0]
+        if batch < 1:
+            raise ValueError("an empty batch: costs needs at least one row (B >= 1)")
+        a_ineq = self.a_inequalities if (self.a_inequalities is not None and self.a_inequalities.shape[0] > 0) else None
+        a_eq, b_eq = (self.a_equalities, self.b_equalities) if self.a_equalities.shape[0] > 0 else (None, None)
+        start = time.perf_counter()
+        for name in ("distance_to_ground_truth", "distanceToGroundTruthAfterRounding", "opttime_curve", "dopttime_curve",
+                     "pobj_curve", "dobj_curve", "pobjbound", "max_violated_inequality", "max_violated_equality",
+                     "max_violated_constraint", "itrn_curve"):
+            setattr(self, name, [])
+
+        def record(niter, solution, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
+            if ground_truth is not None:
+                picked = solution[:, ground_truth_indices]
+                axes = tuple(range(1, picked.ndim))
+                self.distance_to_ground_truth.append(np.mean(np.abs(ground_truth - picked), axis=axes))
+                self.distanceToGroundTruthAfterRounding.append(np.mean(np.abs(ground_truth - np.round(picked)), axis=axes))
+            self.itrn_curve.append(niter)
+            self.opttime_curve.append(duration)
+            self.dopttime_curve.append(duration)
+            self.dobj_curve.append(np.array(energy2, dtype=np.float64))
+            self.pobj_curve.append(np.array(energy1, dtype=np.float64))
+            self.max_violated_constraint.append(np.array([self.max_constraint_violation(solution[k]) for k in range(batch)]))
+            self.max_violated_equality.append(np.array(max_violated_equality, dtype=np.float64))
+            self.max_violated_inequality.append(np.array(max_violated_inequality, dtype=np.float64))
+
+        x = lp_admm_batch(costs, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds, self.upper_bounds, nb_iter=nb_iter,
+                          callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
         elapsed = time.perf_counter() - start
         return (x, elapsed) if get_timing else x

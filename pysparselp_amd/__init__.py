@@ -5,10 +5,13 @@ signature (modules mirror the reference's: ``SparseLP``, ``ADMM``, ``ChambollePo
 ``gaussSiedel``, ``MPSparser``, ``netlib``, ``tools``; ``device`` / ``scale`` / ``problems`` / ``parallel`` hold the
 device-resident, at-scale and multi-GPU entry points); the inner loops run in hand-written HIP kernels (libslp_hip.so,
 C ABI in include/slp_hip.h).  ``SparseLP.solve_batch`` / ``chambolle_pock_ppd_batch`` solve many cost vectors over one
-constraint matrix together (Chambolle-Pock, all instances per launch).  There is no CPU fallback: without the built
+constraint matrix together (Chambolle-Pock, all instances per launch); ``SparseLP.solve_admm_batch`` / ``lp_admm_batch``
+do the same for ADMM with the projected Gauss-Seidel x-step.  There is no CPU fallback: without the built
 library and a HIP device every solver call raises ``SlpError``.
 """
 from ._lib import ORDER_AUTO, ORDER_SEQUENTIAL, ORDER_TREE, SlpError  # noqa: F401
+from .ADMM import ADMMBatchState, lp_admm_batch  # noqa: F401
 from .ChambollePockPPD import CPBatchState, chambolle_pock_ppd_batch  # noqa: F401
 
-__all__ = ["ORDER_AUTO", "ORDER_SEQUENTIAL", "ORDER_TREE", "SlpError", "CPBatchState", "chambolle_pock_ppd_batch"]
+__all__ = ["ORDER_AUTO", "ORDER_SEQUENTIAL", "ORDER_TREE", "SlpError", "CPBatchState", "chambolle_pock_ppd_batch",
+           "ADMMBatchState", "lp_admm_batch"]

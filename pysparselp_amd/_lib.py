@@ -111,6 +111,18 @@ _SIGNATURES = {
     "slp_admm_num_levels": (c_i64, [c_vp]),
     "slp_admm_num_bands": (c_int, [c_vp]),
     "slp_admm_bench": (c_int, [c_vp, c_i64, c_vp]),
+    "slp_admm_batch_create_lp": (c_vp, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_int,
+                                        c_vp, c_int, c_vp, c_int, c_dbl, c_dbl, c_int]),
+    "slp_admm_batch_destroy": (None, [c_vp]),
+    "slp_admm_batch_iterate": (c_int, [c_vp, c_i64]),
+    "slp_admm_batch_sweep_step": (c_int, [c_vp]),
+    "slp_admm_batch_multiplier_step": (c_int, [c_vp]),
+    "slp_admm_batch_report": (c_int, [c_vp, c_vp]),
+    "slp_admm_batch_get_x": (c_int, [c_vp, c_vp, c_i64]),
+    "slp_admm_batch_get_lambda": (c_int, [c_vp, c_vp]),
+    "slp_admm_batch_num_levels": (c_i64, [c_vp]),
+    "slp_admm_batch_form": (c_int, [c_vp]),
+    "slp_admm_batch_bench": (c_int, [c_vp, c_i64, c_vp]),
     "slp_admm_cg_create": (c_vp, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),
     "slp_admm_cg_create_on": (c_vp, [c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),
     "slp_admm_cg_create_on_mixed": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),

@@ -19,6 +19,7 @@
 
 #include "slp_common.h"
 #include "slp_kernels.h"
+#include "slp_admm_shared.h"
 
 namespace slp {
 
@@ -591,6 +592,8 @@ struct GsPlan {
     DevBuf<i32> rows;        // rows sorted by level (stable: increasing row inside a level)
     DevBuf<i64> lptr_dev;    // level pointer on the device (single-workgroup path)
     std::vector<i64> lptr;   // level pointer on the host (launch sizes)
+    bool levels_only = false; // set before planning: only the level-ordered copy of the matrix (rows of a level contiguous: no bands,
+                              // which reorder the rows inside their runs) and no lane records -- what the batched ADMM reads
     bool one_block = false;
     bool pipelined = false;  // runs of narrow levels go through the single-workgroup kernel with the register ring
     bool has_far = false;    // (windowed) some entry reads a row updated by the same kernel more than kGsWinLevels - 1 levels before
@@ -769,7 +772,7 @@ static void gs_plan(GsPlan &g, i64 n, const i64 *indptr, const i32 *indices, con
         is_launch[(size_t)l] = launch ? 1 : 0;
         narrow_levels += launch ? 0 : 1;
     }
-    const bool pipeline = n > 0 && g.nnz < ((i64)1 << 31) && !(ep && ep[0] == '0') && (forced || !g.one_block) &&
+    const bool pipeline = !g.levels_only && n > 0 && g.nnz < ((i64)1 << 31) && !(ep && ep[0] == '0') && (forced || !g.one_block) &&
                           (forced || narrow_levels >= 16) && narrow_levels > 0;
 
     ms_levels = plan_ms();
@@ -1341,9 +1344,16 @@ static void gs_plan_any(GsPlan &g, i64 n, i64 nnz, const i64 *dptr, const i32 *d
         Phase ph("gs_plan_device");
         ok = gs_plan_device(g, n, nnz, dptr, didx, dval);
     }
-    if (!ok) { g = GsPlan(); host_plan(g); return; }
+    if (!ok) {
+        const bool levels_only = g.levels_only;
+        g = GsPlan();
+        g.levels_only = levels_only;
+        host_plan(g);
+        return;
+    }
     if (mode == 2) {
         GsPlan h;
+        h.levels_only = g.levels_only;
         host_plan(h);
         gs_plan_compare(g, h);
     }
@@ -1769,11 +1779,16 @@ __global__ void k_fill_const(i64 n, double v, double *__restrict__ p) {
 // holds them, then -- row normalisation of each block (tools.py:272-290), slack standard form (tools.py:88-127), row
 // normalisation of the stacked system, M (slp_matrix_normal), A^T b -- run in HBM with the reference's entry orders and
 // accumulation orders, so the state equals the host-prepared one bit for bit.
-slp_admm *slp_admm_create_lp(int64_t n, int64_t m_eq, const int64_t *eq_indptr, const int32_t *eq_indices, const double *eq_data,
-                             const double *b_eq, int64_t m_ineq, const int64_t *in_indptr, const int32_t *in_indices,
-                             const double *in_data, const double *b_lower, const double *b_upper, const double *c, const double *lb,
-                             const double *ub, const double *x0, double gamma_eq, double gamma_ineq, int use_preconditioning, int order) {
-    SLP_API_PTR({
+// (scaled_ineq != NULL: the row-normalised inequality block of :76-83 is handed to the caller instead of being dropped -- the
+// batched solver forms the slack part of every instance's start with it, slp_admm_batch.hip; levels_only: GsPlan::levels_only)
+}  // extern "C"
+namespace slp {
+slp_admm *admm_create_lp(int64_t n, int64_t m_eq, const int64_t *eq_indptr, const int32_t *eq_indices, const double *eq_data,
+                         const double *b_eq, int64_t m_ineq, const int64_t *in_indptr, const int32_t *in_indices,
+                         const double *in_data, const double *b_lower, const double *b_upper, const double *c, const double *lb,
+                         const double *ub, const double *x0, double gamma_eq, double gamma_ineq, int use_preconditioning, int order,
+                         slp_matrix **scaled_ineq, bool levels_only) {
+    {
         SLP_REQUIRE(n >= 0 && m_eq >= 0 && m_ineq >= 0 && c && lb && ub, "slp_admm_create_lp: bad arguments");
         SLP_REQUIRE(in_indptr, "slp_admm_create_lp: the inequality block is required (the reference's standard form is undefined "
                                "without it, tools.py:92)");
@@ -1786,6 +1801,7 @@ slp_admm *slp_admm_create_lp(int64_t n, int64_t m_eq, const int64_t *eq_indptr, 
         try {
             const i64 m = m_eq + m_ineq, N = n + m_ineq;
             s->N = N; s->m = m; s->gamma_eq = gamma_eq; s->gamma_ineq = gamma_ineq; s->order = order;
+            s->plan.levels_only = levels_only;
             if (eq_indptr) {  // a 0-row equality block stays a block, like `a_eq is not None` in the reference
                 ae = slp_matrix_create(m_eq, n, eq_indptr, eq_indices, eq_data);
                 if (!ae) throw Error(slp_last_error());
@@ -1824,10 +1840,42 @@ slp_admm *slp_admm_create_lp(int64_t n, int64_t m_eq, const int64_t *eq_indptr, 
                 a2 = nullptr;
             }
             SLP_HIP(hipStreamSynchronize(st));
+            if (scaled_ineq) { *scaled_ineq = ai2; ai2 = nullptr; }
             drop();
             admm_finish_create(s, nullptr, nullptr, nullptr);
-        } catch (...) { drop(); slp_admm_destroy(s); throw; }
+        } catch (...) {
+            drop();
+            if (scaled_ineq) { delete *scaled_ineq; *scaled_ineq = nullptr; }
+            slp_admm_destroy(s);
+            throw;
+        }
         return s;
+    }
+}
+
+// what the batched solver reads of a state created above in SLP_ORDER_SEQUENTIAL and never iterated (slp_admm_shared.h)
+void admm_shared(slp_admm *s, AdmmShared *v) {
+    GsPlan &g = s->plan;
+    v->a = s->a;
+    v->N = s->N; v->m = s->m;
+    v->b = s->b.p; v->lb = s->lb.p; v->ub = s->ub.p; v->x0 = s->x.p;
+    v->atb = s->y.p;  // admm_finish_create leaves A^T b there; the first right-hand side overwrites it
+    v->nlevels = g.nlevels; v->max_width = g.max_width; v->nnz_m = g.nnz;
+    v->lptr = g.lptr;
+    v->gs_ptr = g.ptr.p; v->gs_idx = g.idx.p; v->gs_val = g.val.p; v->gs_invd = g.invd.p; v->gs_rows = g.rows.p;
+    SLP_REQUIRE(g.levels_only && !g.pipelined && g.nbands == 0, "admm_shared: the state must be created with levels_only");
+    g.one_block = false;  // (were the state ever swept: one launch per level)
+}
+}  // namespace slp
+extern "C" {
+
+slp_admm *slp_admm_create_lp(int64_t n, int64_t m_eq, const int64_t *eq_indptr, const int32_t *eq_indices, const double *eq_data,
+                             const double *b_eq, int64_t m_ineq, const int64_t *in_indptr, const int32_t *in_indices,
+                             const double *in_data, const double *b_lower, const double *b_upper, const double *c, const double *lb,
+                             const double *ub, const double *x0, double gamma_eq, double gamma_ineq, int use_preconditioning, int order) {
+    SLP_API_PTR({
+        return admm_create_lp(n, m_eq, eq_indptr, eq_indices, eq_data, b_eq, m_ineq, in_indptr, in_indices, in_data, b_lower, b_upper, c,
+                              lb, ub, x0, gamma_eq, gamma_ineq, use_preconditioning, order, nullptr, false);
     })
 }
 

@@ -1,0 +1,603 @@
+// slp_admm_batch.hip -- batched ADMM with the projected Gauss-Seidel x-step: B instances of ONE constraint structure.
+// No counterpart in the reference (single-threaded numpy: B solves are B calls of lp_admm, ADMM.py:47-269).  The instances share
+// the standard-form A, M = gamma_eq A^T A + gamma_ineq I, A^T b, the Gauss-Seidel plan (level order, 1 / diag) and the slack
+// bounds: all of it depends on the constraints only and is built once by the set-up chain of slp_admm_create_lp
+// (slp_admm_shared.h).  Per instance there is c, hence q = -c + gamma_eq A^T b, and optionally lb, ub, x0 of the original
+// variables.  One iteration of an instance, with the expressions and the summation order of slp_admm in SLP_ORDER_SEQUENTIAL
+// (every dot product by one lane, in storage order, one accumulator):
+//   y_j = ((q_j + gamma_ineq xp_j) - (A^T lambda)_j) - 0                         k_admm_rhs<1>          [ADMM.py:148]
+//   level by level: v = w (y_i - sum_k x[idx_k] val_k) invd + x_i, clamped       k_gs_level<true>       [gaussSiedel.pyx:131-152]
+//   lambda_i += gamma_eq ((A x)_i - b_i)                                         k_admm_multiplier<1>   [ADMM.py:261-263]
+// xp is max(x0, 0) before the first multiplier step and x afterwards (:98, :259).  w = 1 (:162): the factor is left out, 1.0 * t
+// is t bit for bit; so is the subtraction of lambda_ineq = +0.
+//
+// Layout (as slp_cp_batch.hip).  Bt is the instance-tile width, the batch is padded to Bp = Bt * ntiles instances.  A batched
+// vector over len elements lies tile by tile, the instance fastest inside a tile:  v(j, k) at ((k / Bt) * len + j) * Bt + k % Bt
+// (x, y, q, xp0 over N = n + m_ineq; lambda over m; c over n; lb, ub over N when they differ per instance, one shared vector
+// otherwise).  Lanes of padding instances are idle in every kernel: their state stays as allocated (zero).
+//
+// Two forms of the iteration, the same arithmetic (admmb_rhs_one / admmb_sweep_one / admmb_mult_one):
+//   tile    k_admmb_tile: ONE workgroup of 1024 lanes owns a tile and runs k whole iterations of its instances in one launch;
+//           stages and levels are separated by __syncthreads(), x / y / lambda stay in global memory and are re-read across the
+//           barriers with workgroup-scope relaxed loads (as k_gs_sweep_one_block).  No atomics between workgroups, no spin
+//           waits, no grid barrier: a workgroup never waits for another.  A lane is one (row of the level, instance of the tile).
+//   levels  k_admmb_rhs, one k_admmb_level per dependency level, k_admmb_mult: plain launches over (row, instance) lanes of all
+//           tiles -- for few wide levels, where one compute unit per tile would leave the chip idle.
+// admmb_choose() picks form and tile width from the shapes and B; SLP_ADMM_BATCH_FORM=tile|levels forces the form
+// (SLP_ADMM_BATCH_TILE=1|2|..|64 the width: timing runs).
+//
+// Report (:213-248), per instance: row pass r = A x - b -> sum r^2, sum lambda r, max |r|; column pass -> c.x, sum (x - xp)^2,
+// max -x.  Row i (column j) belongs to slice i mod S; a slice adds its terms in increasing i, one lane per instance adds the S
+// slice sums in increasing slice order (k_cpb_report_*); maxima are exact in any order.
+#include <algorithm>
+#include <cstring>
+
+#include "slp_common.h"
+#include "slp_kernels.h"
+#include "slp_admm_shared.h"
+
+namespace slp {
+
+constexpr int kAdmmbBlock = 1024;     // lanes of the tile form's workgroup
+constexpr int kAdmmbMaxSlices = 1024;
+constexpr i64 kAdmmbUnitsPerLaunch = 8192;  // workgroup passes (a few microseconds each) one launch of the tile form may hold
+
+struct AdmmbArgs {
+    i64 N, m, n, B, nlevels;
+    const i64 *tptr; const i32 *tidx; const double *tval;   // rows of A^T
+    const i64 *aptr; const i32 *aidx; const double *aval;   // rows of A
+    const i64 *gptr; const i32 *gidx; const double *gval; const double *ginvd; const i32 *grows; const i64 *lptr;  // M, level order
+    const double *b;                                        // [m]
+    const double *q, *c, *lb, *ub, *xp0;
+    double *x, *y, *lam;
+    int lb_b, ub_b, xp0_b;                                  // 1: tiled per instance, 0: one shared vector
+    double gamma_eq, gamma_ineq;
+};
+
+// a value another lane of the workgroup may have stored before the last barrier: never kept in a register across it
+#ifndef SLP_ADMMB_SCOPE
+#define SLP_ADMMB_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
+#endif
+__device__ __forceinline__ double admmb_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, SLP_ADMMB_SCOPE); }
+
+// sum_q val[q] * v[idx[q] * BT] over s <= q < e: storage order, one accumulator; loads four entries ahead (row_dot<1>)
+template <int BT>
+__device__ __forceinline__ double admmb_dot(i64 s, i64 e, const i32 *__restrict__ idx, const double *__restrict__ val, const double *v) {
+    double acc = 0.0;
+    for (i64 q0 = s; q0 < e; q0 += 4) {
+        i32 j[4];
+        double a[4], g[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const i64 qq = (q0 + q < e) ? q0 + q : e - 1;
+            j[q] = idx[qq];
+            a[q] = val[qq];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) g[q] = admmb_ld(v + (i64)j[q] * BT);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (q0 + q < e) acc += a[q] * g[q];
+    }
+    return acc;
+}
+
+template <int BT>
+__device__ __forceinline__ void admmb_rhs_one(const AdmmbArgs &a, i64 tile, int k, i64 j, bool first) {
+    const double s = admmb_dot<BT>(a.tptr[j], a.tptr[j + 1], a.tidx, a.tval, a.lam + tile * a.m * BT + k);
+    const i64 o = (tile * a.N + j) * BT + k;
+    const double xp = first ? a.xp0[a.xp0_b ? o : j] : admmb_ld(a.x + o);
+    a.y[o] = (a.q[o] + a.gamma_ineq * xp) - s;  // :148
+}
+
+template <int BT>
+__device__ __forceinline__ void admmb_sweep_one(const AdmmbArgs &a, i64 tile, int k, i64 t) {
+    const i64 i = a.grows[t];
+    const i64 o = (tile * a.N + i) * BT + k;
+    const double bi = admmb_ld(a.y + o), xi = admmb_ld(a.x + o), inv = a.ginvd[t];
+    const double l = a.lb[a.lb_b ? o : i], u = a.ub[a.ub_b ? o : i];
+    double v = admmb_dot<BT>(a.gptr[t], a.gptr[t + 1], a.gidx, a.gval, a.x + tile * a.N * BT + k);
+    v = (bi - v) * inv + xi;  // gaussSiedel.pyx:145 with w = 1
+    if (v < l) v = l;         // :148-151
+    else if (v > u) v = u;
+    a.x[o] = v;
+}
+
+template <int BT>
+__device__ __forceinline__ void admmb_mult_one(const AdmmbArgs &a, i64 tile, int k, i64 i) {
+    const double ax = admmb_dot<BT>(a.aptr[i], a.aptr[i + 1], a.aidx, a.aval, a.x + tile * a.N * BT + k);
+    const i64 o = (tile * a.m + i) * BT + k;
+    a.lam[o] = admmb_ld(a.lam + o) + a.gamma_eq * (ax - a.b[i]);  // :261-263
+}
+
+// ---- tile form: `iters` iterations of one tile in one workgroup.  stages: bit 0 right-hand side + sweep, bit 1 multiplier.
+template <int BT>
+__global__ __launch_bounds__(kAdmmbBlock) void k_admmb_tile(AdmmbArgs a, int iters, int first, int stages) {
+    const int k = threadIdx.x & (BT - 1);
+    const i64 tile = blockIdx.x;
+    const i64 g = threadIdx.x / BT;
+    constexpr i64 ng = kAdmmbBlock / BT;
+    const bool active = tile * BT + k < a.B;
+    for (int it = 0; it < iters; ++it) {
+        if (stages & 1) {
+            if (active)
+                for (i64 j = g; j < a.N; j += ng) admmb_rhs_one<BT>(a, tile, k, j, first && it == 0);
+            __syncthreads();
+            for (i64 l = 0; l < a.nlevels; ++l) {
+                const i64 beg = a.lptr[l], end = a.lptr[l + 1];
+                if (active)
+                    for (i64 t = beg + g; t < end; t += ng) admmb_sweep_one<BT>(a, tile, k, t);
+                __syncthreads();  // same compute unit: the stores of this level are visible to the next one
+            }
+        }
+        if (stages & 2) {
+            if (active)
+                for (i64 i = g; i < a.m; i += ng) admmb_mult_one<BT>(a, tile, k, i);
+            __syncthreads();
+        }
+    }
+}
+
+// ---- levels form: lanes over (row, instance) of all tiles; blockIdx.y is the tile
+template <int BT>
+__global__ __launch_bounds__(kBlock) void k_admmb_rhs(AdmmbArgs a, int first) {
+    const int k = threadIdx.x & (BT - 1);
+    const i64 tile = blockIdx.y;
+    if (tile * BT + k >= a.B) return;
+    const i64 ng = (i64)gridDim.x * kBlock / BT;
+    for (i64 j = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; j < a.N; j += ng) admmb_rhs_one<BT>(a, tile, k, j, first != 0);
+}
+
+template <int BT>
+__global__ __launch_bounds__(kBlock) void k_admmb_level(AdmmbArgs a, i64 beg, i64 end) {
+    const int k = threadIdx.x & (BT - 1);
+    const i64 tile = blockIdx.y;
+    if (tile * BT + k >= a.B) return;
+    const i64 ng = (i64)gridDim.x * kBlock / BT;
+    for (i64 t = beg + ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; t < end; t += ng) admmb_sweep_one<BT>(a, tile, k, t);
+}
+
+template <int BT>
+__global__ __launch_bounds__(kBlock) void k_admmb_mult(AdmmbArgs a) {
+    const int k = threadIdx.x & (BT - 1);
+    const i64 tile = blockIdx.y;
+    if (tile * BT + k >= a.B) return;
+    const i64 ng = (i64)gridDim.x * kBlock / BT;
+    for (i64 i = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; i < a.m; i += ng) admmb_mult_one<BT>(a, tile, k, i);
+}
+
+// ---- report.  part[(q * S + slice) * Bp + instance], S = gridDim.x * 256 / BT slices
+//   rows: q = 0 sum r^2, 1 sum lambda r, 2 max |r|       columns: q = 0 sum c x, 1 sum (x - xp)^2, 2 max -x
+template <int BT>
+__global__ __launch_bounds__(kBlock) void k_admmb_report_rows(AdmmbArgs a, i64 Bp, double *__restrict__ part) {
+    const int k = threadIdx.x & (BT - 1);
+    const i64 tile = blockIdx.y;
+    const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT, ng = (i64)gridDim.x * kBlock / BT;
+    const i64 inst = tile * BT + k;
+    double s0 = 0.0, s1 = 0.0, mx = -__builtin_inf();
+    if (inst < a.B)
+        for (i64 i = group; i < a.m; i += ng) {
+            const double ax = admmb_dot<BT>(a.aptr[i], a.aptr[i + 1], a.aidx, a.aval, a.x + tile * a.N * BT + k);
+            const double r = ax - a.b[i];
+            s0 += r * r;
+            s1 += a.lam[(tile * a.m + i) * BT + k] * r;
+            const double ar = fabs(r);
+            mx = ar > mx ? ar : mx;
+        }
+    part[(0 * ng + group) * Bp + inst] = s0;
+    part[(1 * ng + group) * Bp + inst] = s1;
+    part[(2 * ng + group) * Bp + inst] = mx;
+}
+
+template <int BT>
+__global__ __launch_bounds__(kBlock) void k_admmb_report_cols(AdmmbArgs a, int first, i64 Bp, double *__restrict__ part) {
+    const int k = threadIdx.x & (BT - 1);
+    const i64 tile = blockIdx.y;
+    const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT, ng = (i64)gridDim.x * kBlock / BT;
+    const i64 inst = tile * BT + k;
+    double s0 = 0.0, s1 = 0.0, mx = -__builtin_inf();
+    if (inst < a.B)
+        for (i64 j = group; j < a.N; j += ng) {
+            const i64 o = (tile * a.N + j) * BT + k;
+            const double xj = a.x[o];
+            const double dx = first ? xj - a.xp0[a.xp0_b ? o : j] : 0.0;  // xp is x itself after the first multiplier step
+            if (j < a.n) s0 += a.c[(tile * a.n + j) * BT + k] * xj;      // the slack columns cost nothing
+            s1 += dx * dx;
+            mx = (-xj) > mx ? (-xj) : mx;
+        }
+    part[(0 * ng + group) * Bp + inst] = s0;
+    part[(1 * ng + group) * Bp + inst] = s1;
+    part[(2 * ng + group) * Bp + inst] = mx;
+}
+
+// one lane per instance: the slice sums in increasing slice order; out[3 inst + 0..2] as slp_admm_report
+__global__ void k_admmb_report_final(i64 B, i64 Bp, i64 srows, const double *__restrict__ rp, i64 scols, const double *__restrict__ cp,
+                                     double gamma_eq, double gamma_ineq, double *__restrict__ out) {
+    const i64 inst = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (inst >= B) return;
+    double r0 = 0.0, r1 = 0.0, r2 = -__builtin_inf(), c0 = 0.0, c1 = 0.0, c2 = -__builtin_inf();
+    for (i64 g = 0; g < srows; ++g) {
+        r0 += rp[(0 * srows + g) * Bp + inst];
+        r1 += rp[(1 * srows + g) * Bp + inst];
+        const double v = rp[(2 * srows + g) * Bp + inst];
+        r2 = v > r2 ? v : r2;
+    }
+    for (i64 g = 0; g < scols; ++g) {
+        c0 += cp[(0 * scols + g) * Bp + inst];
+        c1 += cp[(1 * scols + g) * Bp + inst];
+        const double v = cp[(2 * scols + g) * Bp + inst];
+        c2 = v > c2 ? v : c2;
+    }
+    out[inst * 3 + 0] = c0 + 0.5 * gamma_eq * r0 + 0.5 * gamma_ineq * c1 + r1;  // :124-132
+    out[inst * 3 + 1] = r2;                                                      // :221
+    out[inst * 3 + 2] = (c2 > 0.0) ? c2 : 0.0;                                   // :222
+}
+
+// ---- set-up.  src [B x slen] row-major (or one shared [slen] vector) -> the tiled layout over len >= slen elements; elements
+// slen .. len come from the shared `tail` (the slack part of a bound).  Padding instances: zero.
+__global__ void k_admmb_scatter(i64 len, i64 slen, i64 B, int BT, i64 Bp, const double *__restrict__ src, int batched,
+                                const double *__restrict__ tail, double *__restrict__ dst) {
+    const i64 total = len * Bp;
+    for (i64 o = (i64)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (i64)gridDim.x * blockDim.x) {
+        const i64 k = o % BT, rest = o / BT, j = rest % len, tile = rest / len;
+        const i64 inst = tile * BT + k;
+        double v = 0.0;
+        if (inst < B) v = j < slen ? src[batched ? inst * slen + j : j] : tail[j - slen];
+        dst[o] = v;
+    }
+}
+
+// the first `count` of len elements of every instance -> [B x count], row-major
+__global__ void k_admmb_gather(i64 len, i64 count, i64 B, int BT, const double *__restrict__ src, double *__restrict__ dst) {
+    const i64 total = count * B;
+    for (i64 o = (i64)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (i64)gridDim.x * blockDim.x) {
+        const i64 inst = o / count, j = o - inst * count;
+        dst[o] = src[((inst / BT) * len + j) * BT + inst % BT];
+    }
+}
+
+// q = (-c) + gamma_eq A^T b (k_admm_q; c = +0 on the slack columns), tiled
+__global__ void k_admmb_q(i64 N, i64 n, i64 B, int BT, i64 Bp, const double *__restrict__ c, const double *__restrict__ atb,
+                          double gamma_eq, double *__restrict__ q) {
+    const i64 total = N * Bp;
+    for (i64 o = (i64)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (i64)gridDim.x * blockDim.x) {
+        const i64 k = o % BT, rest = o / BT, j = rest % N, tile = rest / N;
+        const double cj = j < n ? c[(tile * n + j) * BT + k] : 0.0;
+        q[o] = tile * BT + k < B ? (-cj) + gamma_eq * atb[j] : 0.0;
+    }
+}
+
+// np.maximum(x, 0) (ADMM.py:98), element by element in whatever layout
+__global__ void k_admmb_max0(i64 count, const double *__restrict__ x, double *__restrict__ xp) {
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < count; j += (i64)gridDim.x * blockDim.x) xp[j] = (x[j] < 0.0) ? 0.0 : x[j];
+}
+
+}  // namespace slp
+
+using namespace slp;
+
+struct slp_admm_batch {
+    slp_admm *base = nullptr;  // owned: the shared state (A, M's plan, A^T b, slack bounds)
+    AdmmShared sh;
+    i64 n = 0, N = 0, m = 0, B = 0, Bp = 0, ntiles = 0;
+    int Bt = 1, form = 0;      // form: 0 tile, 1 levels
+    i64 kmax = 1;              // iterations per launch of the tile form
+    bool xp_is_x = false;      // false only before the first multiplier step (:98 vs :259)
+    double gamma_eq = 2, gamma_ineq = 3;
+    DevBuf<i64> lptr;
+    DevBuf<double> c, q, lb, ub, x, xp0, y, lam, rowparts, colparts, out;
+    bool lb_b = false, ub_b = false, x0_b = false;
+    ~slp_admm_batch() { if (base) slp_admm_destroy(base); }
+};
+
+namespace slp {
+
+#define SLP_ADMMB_TILE(bt, CALL)                           \
+    switch (bt) {                                          \
+        case 1:  { constexpr int BT = 1;  CALL; } break;   \
+        case 2:  { constexpr int BT = 2;  CALL; } break;   \
+        case 4:  { constexpr int BT = 4;  CALL; } break;   \
+        case 8:  { constexpr int BT = 8;  CALL; } break;   \
+        case 16: { constexpr int BT = 16; CALL; } break;   \
+        case 32: { constexpr int BT = 32; CALL; } break;   \
+        default: { constexpr int BT = 64; CALL; } break;   \
+    }
+
+// Form and tile width: a function of the shapes and B only ("Batched ADMM").
+//   tile form    when the levels are narrow (fewer than 4096 rows on average: even 16 instances per row do not fill the chip
+//                from one level) or there are at least as many instances as compute units; width 1 while every instance can
+//                have a compute unit of its own (B <= 256), then 4 (B <= 1024), then 16.
+//   levels form  otherwise; width 1 for a single instance, 4 up to four, 16 beyond.
+static void admmb_choose(i64 N, i64 nlevels, i64 B, int *form, int *bt) {
+    const i64 mean_width = N / std::max<i64>(nlevels, 1);
+    int f = (mean_width < 4096 || B >= 256) ? 0 : 1;
+    if (const char *e = getenv("SLP_ADMM_BATCH_FORM")) {
+        if (!strcmp(e, "tile")) f = 0;
+        else if (!strcmp(e, "levels")) f = 1;
+        else if (e[0]) throw Error(std::string("SLP_ADMM_BATCH_FORM must be tile or levels, not ") + e);
+    }
+    int w = f == 0 ? (B <= 256 ? 1 : (B <= 1024 ? 4 : 16)) : (B == 1 ? 1 : (B <= 4 ? 4 : 16));
+    if (const char *e = getenv("SLP_ADMM_BATCH_TILE")) {
+        const int v = atoi(e);
+        if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64) w = v;
+        else if (e[0]) throw Error(std::string("SLP_ADMM_BATCH_TILE must be a power of two up to 64, not ") + e);
+    }
+    *form = f;
+    *bt = w;
+}
+
+static AdmmbArgs admmb_args(const slp_admm_batch *s) {
+    AdmmbArgs a;
+    const CsrDev &A = s->sh.a->a, &At = s->sh.a->at;
+    a.N = s->N; a.m = s->m; a.n = s->n; a.B = s->B; a.nlevels = s->sh.nlevels;
+    a.tptr = At.ptr.p; a.tidx = At.idx.p; a.tval = At.val.p;
+    a.aptr = A.ptr.p; a.aidx = A.idx.p; a.aval = A.val.p;
+    a.gptr = s->sh.gs_ptr; a.gidx = s->sh.gs_idx; a.gval = s->sh.gs_val; a.ginvd = s->sh.gs_invd; a.grows = s->sh.gs_rows;
+    a.lptr = s->lptr.p;
+    a.b = s->sh.b;
+    a.q = s->q.p; a.c = s->c.p;
+    a.lb = s->lb_b ? s->lb.p : s->sh.lb;
+    a.ub = s->ub_b ? s->ub.p : s->sh.ub;
+    a.xp0 = s->xp0.p;
+    a.x = s->x.p; a.y = s->y.p; a.lam = s->lam.p;
+    a.lb_b = s->lb_b; a.ub_b = s->ub_b; a.xp0_b = s->x0_b;
+    a.gamma_eq = s->gamma_eq; a.gamma_ineq = s->gamma_ineq;
+    return a;
+}
+
+static dim3 admmb_grid(const slp_admm_batch *s, i64 rows) { return dim3((unsigned)grid_for(rows * s->Bt, kBlock), (unsigned)s->ntiles); }
+
+// stages: bit 0 right-hand side + sweep, bit 1 multiplier; `iters` whole iterations when both are set
+static void admmb_run(slp_admm_batch *s, i64 iters, int stages) {
+    if (s->N == 0 || iters <= 0) return;
+    hipStream_t st = ctx().stream;
+    const AdmmbArgs a = admmb_args(s);
+    if (s->form == 0) {
+        while (iters > 0) {
+            const i64 k = std::min(iters, s->kmax);
+            const int first = ((stages & 1) && !s->xp_is_x) ? 1 : 0;
+            SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_tile<BT>), dim3((unsigned)s->ntiles), dim3(kAdmmbBlock), 0, st, a, (int)k, first,
+                                                     stages));
+            SLP_HIP(hipGetLastError());
+            if (stages & 2) s->xp_is_x = true;  // :259
+            iters -= k;
+        }
+        return;
+    }
+    for (i64 it = 0; it < iters; ++it) {
+        if (stages & 1) {
+            SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_rhs<BT>), admmb_grid(s, s->N), dim3(kBlock), 0, st, a, s->xp_is_x ? 0 : 1));
+            for (i64 l = 0; l < s->sh.nlevels; ++l) {
+                const i64 beg = s->sh.lptr[(size_t)l], end = s->sh.lptr[(size_t)l + 1];
+                if (end <= beg) continue;
+                SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_level<BT>), admmb_grid(s, end - beg), dim3(kBlock), 0, st, a, beg, end));
+            }
+        }
+        if (stages & 2) {
+            s->xp_is_x = true;
+            if (s->m > 0) SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_mult<BT>), admmb_grid(s, s->m), dim3(kBlock), 0, st, a));
+        }
+        SLP_HIP(hipGetLastError());
+    }
+}
+
+static dim3 admmb_report_grid(const slp_admm_batch *s, i64 rows) {
+    const i64 per_block = kBlock / s->Bt;
+    i64 g = (rows + per_block - 1) / per_block;
+    const i64 cap = std::max<i64>(1, kAdmmbMaxSlices / per_block);
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return dim3((unsigned)g, (unsigned)s->ntiles);
+}
+
+static void admmb_scatter(slp_admm_batch *s, i64 len, i64 slen, const double *src, int batched, const double *tail, double *dst) {
+    hipLaunchKernelGGL(k_admmb_scatter, dim3(grid_for(len * s->Bp, kBlock)), dim3(kBlock), 0, ctx().stream, len, slen, s->B, s->Bt, s->Bp, src,
+                       batched, tail, dst);
+    SLP_HIP(hipGetLastError());
+}
+
+static void admmb_download(slp_admm_batch *s, const DevBuf<double> &src, i64 len, i64 count, double *host) {
+    if (count == 0) return;
+    DevBuf<double> stage((size_t)count * (size_t)s->B);
+    hipLaunchKernelGGL(k_admmb_gather, dim3(grid_for(count * s->B, kBlock)), dim3(kBlock), 0, ctx().stream, len, count, s->B, s->Bt, src.p,
+                       stage.p);
+    SLP_HIP(hipGetLastError());
+    stage.download(host, (size_t)count * (size_t)s->B);
+}
+
+static void admmb_check_indices(const char *what, i64 rows, i64 n, const int64_t *indptr, const int32_t *indices) {
+    SLP_REQUIRE(indptr[0] == 0 && indptr[rows] >= 0, std::string("slp_admm_batch_create_lp: bad row pointer of the ") + what + " block");
+    for (i64 q = 0; q < indptr[rows]; ++q)
+        SLP_REQUIRE(indices[q] >= 0 && indices[q] < n, std::string("slp_admm_batch_create_lp: column index out of range in the ") + what + " block");
+}
+
+}  // namespace slp
+
+extern "C" {
+
+slp_admm_batch *slp_admm_batch_create_lp(int64_t n, int64_t m_eq, const int64_t *eq_indptr, const int32_t *eq_indices,
+                                         const double *eq_data, const double *b_eq, int64_t m_ineq, const int64_t *in_indptr,
+                                         const int32_t *in_indices, const double *in_data, const double *b_lower,
+                                         const double *b_upper, int64_t batch, const double *c, int c_batched, const double *lb,
+                                         int lb_batched, const double *ub, int ub_batched, const double *x0, int x0_batched,
+                                         double gamma_eq, double gamma_ineq, int use_preconditioning) {
+    SLP_API_PTR({
+        SLP_REQUIRE(batch >= 1, "slp_admm_batch_create_lp: batch must be at least 1");
+        SLP_REQUIRE(in_indptr, "slp_admm_batch_create_lp: the inequality block is required (the reference's standard form is "
+                               "undefined without it, tools.py:92)");
+        SLP_REQUIRE(n >= 1 && m_eq >= 0 && m_ineq >= 0 && c && lb && ub, "slp_admm_batch_create_lp: bad arguments");
+        SLP_REQUIRE(m_eq == 0 || (eq_indptr && b_eq), "slp_admm_batch_create_lp: NULL equality block");
+        SLP_REQUIRE(c_batched || batch == 1, "slp_admm_batch_create_lp: c must be [batch x n] (c_batched = 1) for more than one instance");
+        if (eq_indptr) admmb_check_indices("equality", m_eq, n, eq_indptr, eq_indices);
+        admmb_check_indices("inequality", m_ineq, n, in_indptr, in_indices);
+        const i64 N = n + m_ineq, m = m_eq + m_ineq;
+        // M's level count is not known yet: the form's rule needs it, so the width used for the estimate is the widest padding
+        // either form can choose for this B (at most 15 padding instances)
+        const double bp_max = (double)((batch + 15) / 16 * 16);
+        {
+            // nothing is allocated, and no batched argument is read, before this check.  Batched: x, y, q over N, lambda over m, c
+            // over n, xp0 / lb / ub over N where they differ per instance; the staging of one host argument and of the starts; the
+            // report's slice sums.  Shared: both copies of A, M with its level-ordered copy and the lane records of the set-up
+            // (at most sum of squared row lengths entries).
+            i64 free_b = 0, total_b = 0;
+            SLP_REQUIRE(slp_device_memory(&free_b, &total_b) == 0, slp_last_error());
+            const double vectors = ((3.0 + (x0_batched ? 1 : 0) + (lb_batched ? 1 : 0) + (ub_batched ? 1 : 0)) * (double)N + (double)m + (double)n) *
+                                   8.0 * bp_max;
+            double nnz_a = (double)in_indptr[m_ineq] + (double)m_ineq + (eq_indptr ? (double)eq_indptr[m_eq] : 0.0), sq = 0.0;
+            for (i64 i = 0; i < m_ineq; ++i) { const double l = (double)(in_indptr[i + 1] - in_indptr[i]) + 1.0; sq += l * l; }
+            for (i64 i = 0; eq_indptr && i < m_eq; ++i) { const double l = (double)(eq_indptr[i + 1] - eq_indptr[i]); sq += l * l; }
+            const double need = vectors + 8.0 * (double)(x0_batched ? N + n : n) * (double)batch + 8.0 * 6.0 * kAdmmbMaxSlices * bp_max +
+                                64.0 * nnz_a + 40.0 * (sq + (double)N) + 16.0 * 8.0 * (double)(N + m);
+            const double have = (double)free_b + (double)slp_cached_bytes();
+            if (need > have)
+                throw Error("slp_admm_batch_create_lp: " + std::to_string(batch) + " instances need " + std::to_string(need / 1e9) +
+                            " GB of device memory (batched vectors: " + std::to_string(vectors / 1e9) + " GB), " +
+                            std::to_string(have / 1e9) + " GB are free");
+        }
+        auto *s = new slp_admm_batch();
+        slp_matrix *ai2 = nullptr;
+        try {
+            hipStream_t st = ctx().stream;
+            // instance 0's vectors stand for the shared chain: nothing of it but q, the start and the bounds of the original
+            // variables depends on them, and those are rebuilt per instance below
+            s->base = admm_create_lp(n, m_eq, eq_indptr, eq_indices, eq_data, b_eq, m_ineq, in_indptr, in_indices, in_data, b_lower, b_upper, c,
+                                     lb, ub, x0, gamma_eq, gamma_ineq, use_preconditioning, SLP_ORDER_SEQUENTIAL, x0_batched ? &ai2 : nullptr, true);
+            admm_shared(s->base, &s->sh);
+            require_csr(s->sh.a, "slp_admm_batch_create_lp");
+            s->n = n; s->N = N; s->m = m; s->B = batch;
+            s->gamma_eq = gamma_eq; s->gamma_ineq = gamma_ineq;
+            admmb_choose(N, s->sh.nlevels, batch, &s->form, &s->Bt);
+            s->ntiles = (batch - 1) / s->Bt + 1;
+            s->Bp = s->ntiles * s->Bt;
+            SLP_REQUIRE(s->form == 0 || s->ntiles <= 65535, "slp_admm_batch_create_lp: at most 65535 tiles in the levels form");
+            {
+                i64 units = (N * s->Bt + kAdmmbBlock - 1) / kAdmmbBlock + (m * s->Bt + kAdmmbBlock - 1) / kAdmmbBlock;
+                for (i64 l = 0; l < s->sh.nlevels; ++l)
+                    units += std::max<i64>(1, ((s->sh.lptr[(size_t)l + 1] - s->sh.lptr[(size_t)l]) * s->Bt + kAdmmbBlock - 1) / kAdmmbBlock);
+                s->kmax = std::min<i64>(64, std::max<i64>(1, kAdmmbUnitsPerLaunch / std::max<i64>(units, 1)));
+            }
+            s->lb_b = lb_batched != 0; s->ub_b = ub_batched != 0; s->x0_b = x0 && x0_batched;
+            s->lptr.upload(s->sh.lptr.data(), s->sh.lptr.size());
+            const size_t nb = (size_t)N * (size_t)s->Bp;
+            s->c.alloc((size_t)n * (size_t)s->Bp);
+            s->q.alloc(nb); s->x.alloc(nb); s->y.alloc(nb);
+            s->y.zero();
+            s->lam.alloc((size_t)m * (size_t)s->Bp);
+            s->lam.zero();
+            s->rowparts.alloc((size_t)3 * kAdmmbMaxSlices * (size_t)s->Bp);
+            s->colparts.alloc((size_t)3 * kAdmmbMaxSlices * (size_t)s->Bp);
+            s->out.alloc((size_t)3 * (size_t)s->Bp);
+            s->out.zero();
+            {
+                DevBuf<double> stage((size_t)n * (size_t)batch);
+                auto stage_in = [&](const double *host, int batched) {
+                    SLP_HIP(hipMemcpyAsync(stage.p, host, (size_t)n * (size_t)(batched ? batch : 1) * sizeof(double), hipMemcpyHostToDevice, st));
+                };
+                stage_in(c, c_batched);
+                admmb_scatter(s, n, n, stage.p, c_batched, nullptr, s->c.p);
+                // A^T b of the set-up has not been overwritten: the base state never iterates
+                hipLaunchKernelGGL(k_admmb_q, dim3(grid_for(N * s->Bp, kBlock)), dim3(kBlock), 0, st, N, n, s->B, s->Bt, s->Bp, s->c.p, s->sh.atb,
+                                   gamma_eq, s->q.p);
+                SLP_HIP(hipGetLastError());
+                SLP_HIP(hipStreamSynchronize(st));  // the stage is reused
+                if (s->lb_b) {   // [lb_k; scaled b_lower]
+                    s->lb.alloc(nb);
+                    stage_in(lb, 1);
+                    admmb_scatter(s, N, n, stage.p, 1, s->sh.lb + n, s->lb.p);
+                    SLP_HIP(hipStreamSynchronize(st));
+                }
+                if (s->ub_b) {
+                    s->ub.alloc(nb);
+                    stage_in(ub, 1);
+                    admmb_scatter(s, N, n, stage.p, 1, s->sh.ub + n, s->ub.p);
+                    SLP_HIP(hipStreamSynchronize(st));
+                }
+                if (s->x0_b) {   // x_k = [x0_k; A_ineq x0_k] with the scaled block, in its stored order (:84-86)
+                    DevBuf<double> starts((size_t)N * (size_t)batch);
+                    stage_in(x0, 1);
+                    for (i64 k = 0; k < batch; ++k) {
+                        SLP_HIP(hipMemcpyAsync(starts.p + k * N, stage.p + k * n, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+                        if (m_ineq) launch_spmv(ai2->a, starts.p + k * N, starts.p + k * N + n, SLP_ORDER_SEQUENTIAL);
+                    }
+                    admmb_scatter(s, N, N, starts.p, 1, nullptr, s->x.p);
+                    s->xp0.alloc(nb);
+                    hipLaunchKernelGGL(k_admmb_max0, dim3(grid_for((i64)nb, kBlock)), dim3(kBlock), 0, st, (i64)nb, s->x.p, s->xp0.p);
+                    SLP_HIP(hipGetLastError());
+                    SLP_HIP(hipStreamSynchronize(st));
+                } else {         // one start for all: held once
+                    admmb_scatter(s, N, N, s->sh.x0, 0, nullptr, s->x.p);
+                    s->xp0.alloc((size_t)N);
+                    hipLaunchKernelGGL(k_admmb_max0, dim3(grid_for(N, kBlock)), dim3(kBlock), 0, st, N, s->sh.x0, s->xp0.p);
+                    SLP_HIP(hipGetLastError());
+                }
+            }
+            SLP_HIP(hipStreamSynchronize(st));
+            delete ai2;
+            ai2 = nullptr;
+        } catch (...) {
+            delete ai2;
+            delete s;
+            throw;
+        }
+        return s;
+    })
+}
+
+void slp_admm_batch_destroy(slp_admm_batch *s) { delete s; }
+
+int slp_admm_batch_iterate(slp_admm_batch *s, int64_t k) {
+    SLP_API_INT({ SLP_REQUIRE(s && k >= 0, "slp_admm_batch_iterate: bad arguments"); admmb_run(s, k, 3); })
+}
+
+int slp_admm_batch_sweep_step(slp_admm_batch *s) { SLP_API_INT({ SLP_REQUIRE(s, "NULL handle"); admmb_run(s, 1, 1); }) }
+
+int slp_admm_batch_multiplier_step(slp_admm_batch *s) { SLP_API_INT({ SLP_REQUIRE(s, "NULL handle"); admmb_run(s, 1, 2); }) }
+
+int slp_admm_batch_report(slp_admm_batch *s, double *out) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && out, "slp_admm_batch_report: NULL argument");
+        hipStream_t st = ctx().stream;
+        const AdmmbArgs a = admmb_args(s);
+        const dim3 gr = admmb_report_grid(s, s->m), gc = admmb_report_grid(s, s->N);
+        const i64 srows = (i64)gr.x * kBlock / s->Bt, scols = (i64)gc.x * kBlock / s->Bt;
+        SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_report_cols<BT>), gc, dim3(kBlock), 0, st, a, s->xp_is_x ? 0 : 1, s->Bp, s->colparts.p));
+        SLP_HIP(hipGetLastError());
+        SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_report_rows<BT>), gr, dim3(kBlock), 0, st, a, s->Bp, s->rowparts.p));
+        SLP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_admmb_report_final, dim3((unsigned)((s->B + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, s->B, s->Bp, srows,
+                           s->rowparts.p, scols, s->colparts.p, s->gamma_eq, s->gamma_ineq, s->out.p);
+        SLP_HIP(hipGetLastError());
+        s->out.download(out, (size_t)3 * (size_t)s->B);
+    })
+}
+
+int slp_admm_batch_get_x(slp_admm_batch *s, double *x, int64_t count) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && x && count >= 0 && count <= s->N, "slp_admm_batch_get_x: bad arguments");
+        admmb_download(s, s->x, s->N, count, x);
+    })
+}
+
+int slp_admm_batch_get_lambda(slp_admm_batch *s, double *lam) {
+    SLP_API_INT({ SLP_REQUIRE(s && lam, "NULL argument"); admmb_download(s, s->lam, s->m, s->m, lam); })
+}
+
+int64_t slp_admm_batch_num_levels(const slp_admm_batch *s) { return s ? s->sh.nlevels : -1; }
+
+int slp_admm_batch_form(const slp_admm_batch *s) { return s ? s->form : -1; }
+
+int slp_admm_batch_bench(slp_admm_batch *s, int64_t k, double *ms) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && k > 0 && ms, "slp_admm_batch_bench: bad arguments");
+        Context &c = ctx();
+        SLP_HIP(hipEventRecord(c.ev0, c.stream));
+        admmb_run(s, k, 3);
+        SLP_HIP(hipEventRecord(c.ev1, c.stream));
+        SLP_HIP(hipEventSynchronize(c.ev1));
+        float f = 0.f;
+        SLP_HIP(hipEventElapsedTime(&f, c.ev0, c.ev1));
+        *ms = (double)f / (double)k;
+    })
+}
+
+}  // extern "C"

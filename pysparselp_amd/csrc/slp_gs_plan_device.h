@@ -915,7 +915,7 @@ static bool gs_plan_device(GsPlan &g, i64 n, i64 nnz, const i64 *dptr, const i32
         is_launch[(size_t)l] = launch ? 1 : 0;
         narrow_levels += launch ? 0 : 1;
     }
-    const bool pipeline = !(ep && ep[0] == '0') && (forced || !g.one_block) && (forced || narrow_levels >= 16) && narrow_levels > 0;
+    const bool pipeline = !g.levels_only && !(ep && ep[0] == '0') && (forced || !g.one_block) && (forced || narrow_levels >= 16) && narrow_levels > 0;
 
     g.pipelined = false;
     g.windowed = false;
