@@ -576,6 +576,46 @@ int slp_dga_timing_read(slp_dga *s, double out[5]);
 int slp_dga_line_search(slp_matrix *a, const double *direction, const double *b, const double *c_bar, const double *ub,
                         const double *lb, int path, const double *draws, int64_t ndraws, double out[4]);
 
+/* ---- batched dual gradient ascent: B LPs over one constraint matrix and one right-hand side (csrc/slp_dga_batch.hip) ---- *
+ * An extension (the reference solves one LP per call).  The instances share `a`, m_eq and b; c is batch x n; lb, ub (n values, or
+ * batch x n with their `batched` flag) and y0 (m values, or batch x m) may be per instance.  All vectors lie instance-major, a
+ * launch is a grid of (the single solver's blocks, batch).  Instance k is bit for bit what slp_dga computes on its data (the
+ * arithmetic of both is csrc/slp_dga_shared.h): x, y, tie draws taken, status bits; on either search path (fused: one workgroup per
+ * instance, n <= 8192; general: one segmented radix sort over batch segments, scans over (tiles, batch)), for any batch and any
+ * split of the iterations over calls.  SLP_DGA_BATCH_PATH=fused|general or _set_path force a path; automatic: fused for n <= 2048,
+ * and for n <= 8192 from 32 instances on (profiles/dga_batch.json).
+ * All instances read ONE stream of tie draws, each at its own position.  An instance whose start has dual energy -inf is frozen:
+ * x stays the dual argmin of y0 and y stays y0 (what the single solve returns at once, :133-139); the others go on.
+ * Refused before anything is allocated: batch < 1, no constraint rows, a chunked matrix or one whose CSR was released (the batch
+ * walks the CSR pair), a batch whose buffers do not fit the free device memory.  The names do not start with slp_dga_: that
+ * prefix is the single solver's entry points.  `a` stays owned by the caller. */
+typedef struct slp_batch_dga slp_batch_dga;
+slp_batch_dga *slp_batch_dga_create_on(slp_matrix *a, int64_t m_eq, const double *b, int64_t batch, const double *c, const double *lb,
+                                       int lb_batched, const double *ub, int ub_batched, const double *y0, int y0_batched);
+void slp_batch_dga_destroy(slp_batch_dga *s);
+int slp_batch_dga_set_path(slp_batch_dga *s, int path);   /* 0 auto, 1 fused, 2 general */
+int slp_batch_dga_path(const slp_batch_dga *s);           /* 1 fused, 2 general */
+/* The sort of the general search: 1 segmented (one workgroup sorts an instance's segment), 2 global (one device-wide stable sort
+ * of all keys, then a stable sort by instance: the same order); 0 on the fused path.  Chosen when the path is set: global for
+ * more than 2048 variables, or as SLP_DGA_BATCH_SORT=segmented|global says. */
+int slp_batch_dga_sort(const slp_batch_dga *s);
+/* Up to k iterations of every instance.  Stops early for all instances (status bit 4) once two draws per iteration to come are
+ * not certain to be left behind the position of the instance that has taken most. */
+int slp_batch_dga_iterate(slp_batch_dga *s, int64_t k);
+int64_t slp_batch_dga_iterations(const slp_batch_dga *s);
+/* Appends `count` draws to the shared stream; the draws every moving instance has passed are dropped from its front. */
+int slp_batch_dga_push_random(slp_batch_dga *s, const double *draws, int64_t count);
+/* out[2 k] = status bits of instance k (as slp_dga_status), out[2 k + 1] = its tie draws taken; out[2 batch] = draws left behind
+ * the furthest instance, out[2 batch + 1] = iterations done. */
+int slp_batch_dga_status(slp_batch_dga *s, int64_t *out);
+int slp_batch_dga_frozen(slp_batch_dga *s, int32_t *out);   /* batch values: 1 = frozen */
+int slp_batch_dga_get_x(slp_batch_dga *s, double *x);   /* batch x n, row-major */
+int slp_batch_dga_get_y(slp_batch_dga *s, double *y);   /* batch x m */
+/* batch x 3 as slp_dga_report: the dual energy (a certified lower bound of instance k's LP), largest violation, their sum. */
+int slp_batch_dga_report(slp_batch_dga *s, double *out);
+int slp_batch_dga_timing(slp_batch_dga *s, int on);
+int slp_batch_dga_timing_read(slp_batch_dga *s, double out[5]);
+
 /* ---- synthetic random LP on the device (randomLP.py:14-75) -------------- *
  * Row r of A_ineq (global row index row_offset + r): every entry is non-zero
  * with probability `density`, value round(N(0,1)*100)/100, exact zeros

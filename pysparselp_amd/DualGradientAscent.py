@@ -4,7 +4,8 @@ The dual function of ``min c.x, A_e x = b_e, A_i x <= b_u, lb <= x <= ub`` is co
 every iteration moves the inequality multipliers, then the equality multipliers, along their (masked) gradient to the exact
 maximiser on that line -- a sort of the breakpoints ``-c_bar_j / d_j``, two running sums and a bisection
 (csrc/slp_dga.hip).  The multipliers it returns are dual feasible, so their dual energy (``DeviceDGA.report``) is a certified
-lower bound on the LP's value.
+lower bound on the LP's value.  ``DeviceDGABatch`` / ``dual_gradient_ascent_batch`` advance B LPs that share the constraint
+matrix and the right-hand sides together (csrc/slp_dga_batch.hip); instance k is bit for bit the single solve of its data.
 """
 import os
 import time
@@ -16,6 +17,7 @@ from . import _lib
 PATHS = {"auto": 0, "fused": 1, "general": 2}
 FUSED_MAX = 8192    # most variables of the fused search (one workgroup, breakpoints in LDS)
 FUSED_AUTO = 2048   # ... and up to where it is the default (beyond, the general search is faster)
+FUSED_BATCH = 32    # batched: from this many instances on the fused search is the default up to FUSED_MAX variables
 STATUS_NEGATIVE_STEP, STATUS_EMPTY, STATUS_DRAWS_DRY, STATUS_NAN, STATUS_NO_CROSSING = 1, 2, 4, 8, 16
 
 
@@ -211,6 +213,221 @@ def dual_gradient_ascent(x, lp, nb_max_iter=1000, callback_func=None, y_eq=None,
                 if max_time is not None and elapsed > max_time:
                     break
         return result(state.x())
+    finally:
+        if state is not None:
+            state.close()
+        mat.close()
+
+
+# ---- batched: B LPs over one constraint matrix ---------------------------------------------------------------------------------
+
+def _check_status_batch(flags):
+    """The single solver's exception for the first kind of error present, naming the instances that carry it."""
+    flags = np.asarray(flags, dtype=np.int64)
+    for bit in (STATUS_NAN, STATUS_EMPTY, STATUS_NO_CROSSING, STATUS_NEGATIVE_STEP):
+        bad = np.flatnonzero(flags & bit)
+        if bad.size:
+            try:
+                _check_status(bit)
+            except (ValueError, AssertionError) as e:
+                raise type(e)(f"{e} (instances {bad.tolist()} of the batch)") from None
+
+
+def _per_instance(name, v, batch, size):
+    """``v`` of shape ``(size,)`` (shared) or ``(batch, size)`` as a contiguous float64 array and whether it is per instance."""
+    v = np.asarray(v, dtype=np.float64)
+    if v.shape == (size,):
+        return _lib.f64(v), 0
+    if v.shape == (batch, size):
+        return _lib.f64(v), 1
+    raise ValueError(f"{name} has shape {v.shape}: expected ({size},) or (B, {size}) with B = {batch}")
+
+
+class DeviceDGABatch:
+    """``DeviceDGA`` for B LPs over one ``DeviceMatrix`` ``a`` (with its CSR: not chunked) and one ``b`` (``slp_batch_dga_*``):
+    ``c`` of shape ``(B, n)``; ``lb``, ``ub`` of shape ``(n,)`` or ``(B, n)``; ``y0`` of shape ``(m,)`` or ``(B, m)``.  Results
+    carry a leading axis B.  All instances read one stream of tie draws (``draws(count)``, default a private ``RandomState(0)``),
+    each at its own position.  An instance whose start has dual energy ``-inf`` is frozen (``frozen()``): its x and y stay the
+    start's.  ``path``: ``"auto"`` (the fused search, one workgroup per instance, up to ``FUSED_AUTO`` variables and, from
+    ``FUSED_BATCH`` instances on, up to ``FUSED_MAX``; else the general one), ``"fused"``, ``"general"``; the environment's
+    ``SLP_DGA_BATCH_PATH`` picks it when ``path`` is None."""
+
+    def __init__(self, a, b, c, lb, ub, y0, m_eq=0, draws=None, path=None):
+        self.n, self.m, self.m_eq = a.shape[1], a.shape[0], int(m_eq)
+        c = np.asarray(c, dtype=np.float64)
+        if c.ndim != 2 or c.shape[1] != self.n:
+            raise ValueError(f"costs has shape {c.shape}: expected (B, {self.n}), one row per instance")
+        self.batch = c.shape[0]
+        if self.batch < 1:
+            raise ValueError("an empty batch: costs needs at least one row (B >= 1)")
+        if self.m < 1:
+            raise ValueError("dual_gradient_ascent_batch: the LP has no constraint rows")
+        if not 0 <= self.m_eq <= self.m:
+            raise ValueError("m_eq out of range")
+        c, b = _lib.f64(c), _lib.f64(b)
+        if b.shape != (self.m,):
+            raise ValueError(f"b has shape {b.shape}: expected ({self.m},); per-instance right-hand sides are not built")
+        lb, lb_b = _per_instance("lower_bounds", lb, self.batch, self.n)
+        ub, ub_b = _per_instance("upper_bounds", ub, self.batch, self.n)
+        y0, y_b = _per_instance("y0", y0, self.batch, self.m)
+        self._l = _lib.lib()
+        self._draws = draws if draws is not None else np.random.RandomState(0).random_sample
+        self._h = _lib.check_handle(self._l.slp_batch_dga_create_on(a._h, self.m_eq, _lib.ptr(b), self.batch, _lib.ptr(c), _lib.ptr(lb), lb_b,
+                                                                    _lib.ptr(ub), ub_b, _lib.ptr(y0), y_b))
+        self._a = a
+        if path is not None:
+            _lib.check(self._l.slp_batch_dga_set_path(self._h, PATHS[path]))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._l.slp_batch_dga_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def path(self):
+        return {1: "fused", 2: "general"}[int(self._l.slp_batch_dga_path(self._h))]
+
+    def sort(self):
+        """The sort of the general search: ``"segmented"`` or ``"global"`` (two device-wide stable sorts; the default for more than
+        ``FUSED_AUTO`` variables, ``SLP_DGA_BATCH_SORT`` forces one); None on the fused path.  Same order, same bits."""
+        return {0: None, 1: "segmented", 2: "global"}[int(self._l.slp_batch_dga_sort(self._h))]
+
+    def status(self):
+        """``(flags[B], tie draws taken[B], draws left in the buffer behind the furthest instance, iterations done)``; reading it
+        synchronises."""
+        out = np.zeros(2 * self.batch + 2, dtype=np.int64)
+        _lib.check(self._l.slp_batch_dga_status(self._h, _lib.ptr(out)))
+        per = out[:2 * self.batch].reshape(self.batch, 2)
+        return per[:, 0].copy(), per[:, 1].copy(), int(out[-2]), int(out[-1])
+
+    def frozen(self):
+        out = np.zeros(self.batch, dtype=np.int32)
+        _lib.check(self._l.slp_batch_dga_frozen(self._h, _lib.ptr(out)))
+        return out.astype(bool)
+
+    def push_random(self, values):
+        values = _lib.f64(values)
+        _lib.check(self._l.slp_batch_dga_push_random(self._h, _lib.ptr(values), values.size))
+
+    def iterate(self, k, refill=True):
+        """``k`` iterations of every instance, nothing read back in between.  ``refill``: the shared draw buffer is topped up to
+        two draws per iteration behind the furthest instance first; without it the call stops early, for all instances, when the
+        buffer could run dry (``status()[3]`` tells how far it got)."""
+        k = int(k)
+        if refill:
+            left = self.status()[2]
+            if left < 2 * k:
+                self.push_random(self._draws(2 * k - left))
+        _lib.check(self._l.slp_batch_dga_iterate(self._h, k))
+
+    def check(self):
+        flags = self.status()[0]
+        _check_status_batch(flags & ~STATUS_DRAWS_DRY)
+        return flags
+
+    def x(self):
+        x = np.empty((self.batch, self.n))
+        _lib.check(self._l.slp_batch_dga_get_x(self._h, _lib.ptr(x)))
+        return x
+
+    def y(self):
+        y = np.empty((self.batch, self.m))
+        _lib.check(self._l.slp_batch_dga_get_y(self._h, _lib.ptr(y)))
+        return y[:, :self.m_eq].copy(), y[:, self.m_eq:].copy()
+
+    def report(self):
+        """Array of shape ``(B, 3)``: per instance ``(dual energy, largest violation, sum of violations)`` of its multipliers as
+        they are, x their dual argmin.  Column 0 is a certified lower bound on the instance's LP value."""
+        out = np.zeros((self.batch, 3))
+        _lib.check(self._l.slp_batch_dga_report(self._h, _lib.ptr(out)))
+        return out
+
+    def timing(self, on):
+        _lib.check(self._l.slp_batch_dga_timing(self._h, int(bool(on))))
+
+    def timing_read(self):
+        """Milliseconds per stage since ``timing(True)``: products, sort, scans, rest, fused search."""
+        out = np.zeros(5)
+        _lib.check(self._l.slp_batch_dga_timing_read(self._h, _lib.ptr(out)))
+        return dict(zip(("products", "sort", "scans", "rest", "fused_search"), (float(v) for v in out)))
+
+
+def dual_gradient_ascent_batch(lp, costs, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None, lower_bounds=None,
+                               upper_bounds=None, path=None):
+    """``dual_gradient_ascent`` for every row of ``costs`` (shape ``(B, n)``) in place of ``lp.costsvector``, all B solves advancing
+    together on the device (an extension: the reference solves one LP per call); returns ``(X, Y_eq, Y_ineq)`` with a leading
+    axis B (``Y_ineq`` is None without inequality rows).
+
+    ``lower_bounds`` / ``upper_bounds`` default to the LP's; each of shape ``(n,)`` or ``(B, n)``.  ``y_eq`` / ``y_ineq``: shape
+    ``(m,)`` or ``(B, m)``; the default is the reference's seed-0 start, the same for every instance, and every instance's tie
+    draws continue that stream from its own position -- so instance k is bit for bit ``dual_gradient_ascent`` on a copy of the LP
+    with ``costs[k]`` (and its bounds and start).  An instance whose start is dual infeasible (energy ``-inf``) stands still at
+    its start, which is what its single solve returns; the others go on.  ``callback_func(niter, X, 0, 0, elapsed, 0, 0)`` is
+    called for ``niter % 100 == 0``; ``max_time`` is tested there and stops the whole batch.  A finite ``b_lower``, a 2-D
+    right-hand side, a wrong shape, B < 1 or an LP without rows raises ``ValueError`` before the library is loaded; a status error
+    raises the single solver's exception, naming the instances."""
+    return _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path)[:3]
+
+
+def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path):
+    """``dual_gradient_ascent_batch`` plus, as a fourth value, the final ``DeviceDGABatch.report()``."""
+    b_lower = getattr(lp, "b_lower", None)
+    if b_lower is not None and np.size(b_lower) > 0 and np.max(b_lower) != -np.inf:
+        raise ValueError("dual_gradient_ascent needs one-sided inequalities: b_lower must be None or all -inf")
+    from .device import DeviceMatrix
+    from .tools import CsrArrays
+
+    start = time.perf_counter()
+    costs = np.asarray(costs, dtype=np.float64)
+    n = np.size(lp.costsvector)
+    if costs.ndim != 2 or costs.shape[1] != n:
+        raise ValueError(f"costs has shape {costs.shape}: expected (B, {n}), one row per instance")
+    batch = costs.shape[0]
+    if batch < 1:
+        raise ValueError("an empty batch: costs needs at least one row (B >= 1)")
+    a_eq, a_ineq = CsrArrays.from_any(lp.a_equalities), CsrArrays.from_any(lp.a_inequalities)
+    m_eq = 0 if a_eq is None else a_eq.shape[0]
+    m_in = 0 if a_ineq is None else a_ineq.shape[0]
+    if m_eq + m_in == 0:
+        raise ValueError("dual_gradient_ascent_batch: the LP has no constraint rows")
+    for name, rhs, rows in (("b_equalities", lp.b_equalities, m_eq), ("b_upper", lp.b_upper, m_in)):
+        if rows and np.shape(rhs) != (rows,):
+            raise ValueError(f"{name} has shape {np.shape(rhs)}: expected ({rows},); per-instance right-hand sides are not built")
+    lb, _ = _per_instance("lower_bounds", lp.lower_bounds if lower_bounds is None else lower_bounds, batch, n)
+    ub, _ = _per_instance("upper_bounds", lp.upper_bounds if upper_bounds is None else upper_bounds, batch, n)
+    rs = np.random.RandomState(0)   # the reference draws the starts it is not given; the tie draws continue that stream
+    ye, ye_b = _per_instance("y_eq", -rs.rand(m_eq) if y_eq is None else y_eq, batch, m_eq)
+    if y_ineq is None:
+        y_ineq = np.abs(rs.rand(m_in)) if a_ineq is not None else np.zeros(0)
+    yi, yi_b = _per_instance("y_ineq", y_ineq, batch, m_in)
+    if ye_b or yi_b:
+        y0 = np.concatenate((np.broadcast_to(ye, (batch, m_eq)), np.broadcast_to(yi, (batch, m_in))), axis=1)
+    else:
+        y0 = np.concatenate((ye, yi))
+    b = np.concatenate((_lib.f64(lp.b_equalities) if m_eq else np.zeros(0), _lib.f64(lp.b_upper) if m_in else np.zeros(0)))
+    mat = DeviceMatrix.from_blocks(a_eq if m_eq else None, a_ineq if m_in else None, n)
+    state = None
+
+    def result():
+        ye, yi = state.y()
+        return state.x(), ye, (yi if a_ineq is not None else None), state.report()
+
+    try:
+        state = DeviceDGABatch(mat, b, costs, lb, ub, y0, m_eq=m_eq, draws=rs.random_sample, path=path)
+        i = 0
+        while i < nb_max_iter and not state.frozen().all():
+            k = 1 if i % 100 == 0 else min(100 - i % 100, nb_max_iter - i)
+            state.iterate(k)
+            i += k
+            state.check()
+            if (i - 1) % 100 == 0:
+                elapsed = time.perf_counter() - start
+                if callback_func is not None:
+                    callback_func(i - 1, state.x(), 0, 0, elapsed, 0, 0)
+                if max_time is not None and elapsed > max_time:
+                    break
+        return result()
     finally:
         if state is not None:
             state.close()

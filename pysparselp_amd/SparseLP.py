@@ -626,3 +626,67 @@ class SparseLP:
                           callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
         elapsed = time.perf_counter() - start
         return (x, elapsed) if get_timing else x
+
+    def solve_dga_batch(
+        self,
+        costs,
+        get_timing=True,
+        nb_iter=10000,
+        max_time=None,
+        nb_iter_plot=10,
+        ground_truth=None,
+        ground_truth_indices=None,
+        lower_bounds=None,
+        upper_bounds=None,
+    ):
+        """Run ``method="dual_gradient_ascent"`` once for every row of ``costs`` (shape ``(B, nb_variables)``) in place of
+        ``costsvector``, all B solves advancing together on the GPU (``DualGradientAscent.dual_gradient_ascent_batch``; extension:
+        the reference solves one LP per call); returns ``(X, elapsed)`` or ``X``, ``X`` of shape ``(B, nb_variables)``.
+
+        Constraints and right-hand sides are the LP's own; ``lower_bounds`` / ``upper_bounds`` (shape ``(nb_variables,)`` or
+        ``(B, nb_variables)``) default to the LP's.  ``X[k]`` and the k-th component of every curve are what
+        ``solve(method="dual_gradient_ascent")`` gives on a copy of the LP whose ``costsvector`` is ``costs[k]`` (bit for bit).
+        Also sets ``self.dual_multipliers = (Y_eq, Y_ineq)`` and ``self.dual_lower_bounds`` of shape ``(B,)``: the dual energies of
+        the returned multipliers, each a certified lower bound on its instance's LP value.  ``solve_batch(method=
+        "dual_gradient_ascent")`` keeps refusing: it is the batched Chambolle-Pock only.
+
+        Reports every 100 iterations whatever ``nb_iter_plot``, as the single method does.  ``itrn_curve``, ``opttime_curve``,
+        ``dopttime_curve`` are lists of scalars; ``pobj_curve``, ``dobj_curve``, ``max_violated_equality``,
+        ``max_violated_inequality``, ``max_violated_constraint`` (and, with ``ground_truth``, the two distance curves) are lists of
+        arrays of length B (``max_violated_constraint`` is taken against the LP's own bounds).  ``max_time`` stops the whole batch.  Under a communicator every rank solves the whole batch (a replica).
+        """
+        from .DualGradientAscent import _dga_batch_run
+
+        costs = np.asarray(costs, dtype=np.float64)
+        if costs.ndim != 2 or costs.shape[1] != self.nb_variables:
+            raise ValueError(f"costs has shape {costs.shape}: expected (B, {self.nb_variables}), one row per instance")
+        batch = costs.shape[0]
+        if batch < 1:
+            raise ValueError("an empty batch: costs needs at least one row (B >= 1)")
+        if self.b_lower is not None and np.size(self.b_lower) and np.max(self.b_lower) != -np.inf:
+            raise ValueError("dual_gradient_ascent needs one-sided inequalities: b_lower must be None or all -inf")
+        start = time.perf_counter()
+        for name in ("distance_to_ground_truth", "distanceToGroundTruthAfterRounding", "opttime_curve", "dopttime_curve",
+                     "pobj_curve", "dobj_curve", "pobjbound", "max_violated_inequality", "max_violated_equality",
+                     "max_violated_constraint", "itrn_curve"):
+            setattr(self, name, [])
+
+        def record(niter, solution, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
+            if ground_truth is not None:   # instance by instance: the expressions (and so the sums) of ``solve``
+                picked = [solution[k][ground_truth_indices] for k in range(batch)]
+                self.distance_to_ground_truth.append(np.array([np.mean(np.abs(ground_truth - p)) for p in picked]))
+                self.distanceToGroundTruthAfterRounding.append(np.array([np.mean(np.abs(ground_truth - np.round(p))) for p in picked]))
+            self.itrn_curve.append(niter)
+            self.opttime_curve.append(duration)
+            self.dopttime_curve.append(duration)
+            self.dobj_curve.append(np.full(batch, energy2, dtype=np.float64))
+            self.pobj_curve.append(np.full(batch, energy1, dtype=np.float64))
+            self.max_violated_constraint.append(np.array([self.max_constraint_violation(solution[k]) for k in range(batch)]))
+            self.max_violated_equality.append(np.full(batch, max_violated_equality, dtype=np.float64))
+            self.max_violated_inequality.append(np.full(batch, max_violated_inequality, dtype=np.float64))
+
+        x, y_eq, y_ineq, report = _dga_batch_run(self, costs, nb_iter, record, None, None, max_time, lower_bounds, upper_bounds, None)
+        self.dual_multipliers = (y_eq, y_ineq)
+        self.dual_lower_bounds = report[:, 0].copy()
+        elapsed = time.perf_counter() - start
+        return (x, elapsed) if get_timing else x
