@@ -74,28 +74,63 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
     const __amdgpu_buffer_rsrc_t rs_x =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(x + wg.x0), 0, (int)(wg.ncol * 8), 0x00020000);
 
-    // A slot as a buffer of its own: `width` words from word `so` of the payload -- the lanes past the slot's width lie behind the
-    // descriptor's end (the load returns 0, no memory request) with no per-lane predicate: the slot's base and size are wave-uniform,
-    // so the descriptor is a few SCALAR instructions where a compare and a select per load and lane used to be (round 6: 224 of the
-    // ~1200 vector instructions of eight packets)
-    auto slot_pay = [&](unsigned int so, unsigned int width) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned int *>(wg.pay) + so, 0, (int)(width * 4u), 0x00020000);
+    // A slot is `width` words from word `so` of the payload.  ONE descriptor per segment (the payload's; the fp64 values'): a
+    // slot's load differs from its neighbour's in the scalar offset (the slot's first byte) and in num_records (the slot's LAST
+    // byte + 1) only, so the four descriptor words stay in one register quad whose third word is rewritten in front of each
+    // load -- with the sum the next slot's offset needs anyway.  The range check of a raw buffer on this hardware covers the
+    // scalar offset: a lane is out of range when scalar offset + vector offset >= num_records (measured -- with num_records =
+    // the slot's width alone every lane of a slot behind the first reads 0; tests/test_gpu_tall_frame.py pins it: under the other
+    // rule the lanes past a slot would read the next slot's items).  So the lanes past the slot's width lie behind the
+    // descriptor's end (the load returns 0, no memory request) with no per-lane predicate.  Round 6 gave every load a descriptor
+    // of its own, base included: a 64-bit shift and add, the mask of the high word, the size, on the CU's one scalar unit in all
+    // 16 waves (7 scalar instructions per load, 46 of a packet's 63).  The descriptor is kept as four plain words because
+    // __builtin_amdgcn_make_buffer_rsrc per load makes the compiler copy base and flags into a fresh quad each time (3 s_mov per
+    // load).
+    // (A row block's payload is addressed in 32-bit bytes here: below 4 GB, i.e. 2^29 fp64 entries per row block.)
+    typedef unsigned int rsrc_words_t __attribute__((ext_vector_type(4)));
+    auto words_of = [](const void *base) {
+        const unsigned long long a = (unsigned long long)base;
+        rsrc_words_t d;
+        d[0] = (unsigned int)a; d[1] = (unsigned int)(a >> 32) & 0xffffu; d[2] = 0u; d[3] = 0x00020000u;
+        return d;
     };
-    auto slot_val = [&](unsigned int so, unsigned int width) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(DICT ? x : wg.val) + so, 0, (int)(width * 8u), 0x00020000);
+    auto as_rsrc = [](const rsrc_words_t &d) {
+        __amdgpu_buffer_rsrc_t r;
+        __builtin_memcpy(&r, &d, sizeof(r));
+        return r;
     };
+    rsrc_words_t dpay = words_of(wg.pay), dval = words_of(DICT ? (const void *)x : (const void *)wg.val);
+    auto slot_pay = [&](unsigned int end) { dpay[2] = end; return as_rsrc(dpay); };            // (end: byte behind the slot's words)
+    auto slot_val = [&](unsigned int end) { dval[2] = 2u * end; return as_rsrc(dval); };
 
     TallRegs<DICT> regs[kDepth];
-    unsigned int hw[2 * kDepth];
+    unsigned int hw[kDepth];        // this lane's dword of the headers of the packets depth .. 2 depth - 1 ahead
 
-    auto widths = [&](unsigned int h, unsigned int *c) {
+    // A packet's header is read ONCE, when its payload is about to be issued (`depth` packets before its items are taken):
+    // six v_readlane and the unpacking to scalars that both halves of the issue share; the two fields consume() needs `depth`
+    // steps later (tile word, lanes with a fifth item) wait in scalar registers (2 x depth of them).  Offsets and widths are
+    // unpacked as BYTES of payload words, the unit of the scalar offset and of num_records.  (Round 6 read lanes 0 and 2-5 in
+    // either half of the issue and lanes 1 and 4 again in consume(): 13 v_readlane per packet for 6 dwords.)
+    struct TallHdr {
+        unsigned int off;              // payload offset of the packet inside its row block
+        unsigned int xw;               // TallPkt::xsrc
+        unsigned int w[kTallSlots];    // lanes whose list is longer than slot k
+    };
+    static_assert(kTallT <= (1 << 14), "a width's two bits below its upper half-word are zero: (c >> 14) is 4 x the upper width");
+    auto unpack = [&](unsigned int h) {
+        TallHdr t;
+        t.off = (unsigned int)__builtin_amdgcn_readlane((int)h, 0) * 4u;
+        t.xw = (unsigned int)__builtin_amdgcn_readlane((int)h, 1);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const unsigned int v = (unsigned int)__builtin_amdgcn_readlane((int)h, 2 + i);
-            c[2 * i] = v & 0xffffu;
-            c[2 * i + 1] = v >> 16;
+            t.w[2 * i] = (v & 0xffffu) * 4u;
+            t.w[2 * i + 1] = v >> 14;
         }
+        return t;
     };
+    const unsigned int wbytes = wbase * 4u;   // (a wave takes slot k's items iff wbytes < w[k])
+    unsigned int xwq[kDepth], c4q[kDepth];
 
     // this lane's two 16-byte pieces of an x-tile (doubles 2p, 2p + 1 of each tile half).  A piece that straddles the end of x
     // (odd width) may fetch the 8 bytes behind it: every device block carries 16 bytes of slack, and no item names that column
@@ -108,76 +143,49 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
         }
     };
 
-    auto issue = [&](TallRegs<DICT> &g, unsigned int h) {
-        const unsigned int off = (unsigned int)__builtin_amdgcn_readlane((int)h, 0);
-        const unsigned int xs = (unsigned int)__builtin_amdgcn_readlane((int)h, 1) & 0x7fffffffu;
-        unsigned int c[kTallSlots];
-        widths(h, c);
-        unsigned int so = off;   // (words)
+    // The payload of a packet goes out in two halves: the registers of slots 0-3 are free once the first four items are done, so
+    // their loads for the packet `depth` ahead go out BETWEEN the two groups of items (in the shadow of the LDS latency) instead
+    // of behind all of them
+    auto issue_part = [&](TallRegs<DICT> &g, const TallHdr &t, const int part) {
         const unsigned int mine = (unsigned int)p * 4u;
-#pragma unroll
-        for (int k = 0; k < kTallSlots; ++k) {
-            g.lo[k] = __builtin_amdgcn_raw_buffer_load_b32(slot_pay(so, c[k]), mine, 0, 2);  // streamed once
-            if (!DICT) {
-                const auto v = __builtin_amdgcn_raw_buffer_load_b64(slot_val(so, c[k]), 2u * mine, 0, 2);
-                g.val[k] = __hiloint2double((int)v[1], (int)v[0]);
-            }
-            so += c[k];
-        }
-        if (DICT) {
-            g.hi[0] = __builtin_amdgcn_raw_buffer_load_b32(slot_pay(so, c[0]), mine, 0, 2);
-            so += c[0];
-            g.hi[DICT ? 1 : 0] = __builtin_amdgcn_raw_buffer_load_b32(slot_pay(so, c[4]), mine, 0, 2);
-        }
-        // columns past ncol read 0: the displacement of each double is part of the voffset, which the descriptor's range check
-        // covers (an soffset is not checked on gfx9 raw buffers)
-        // lane p carries doubles 2p, 2p + 1 of the tile's first half and of its second half: consecutive lanes then write
-        // consecutive 16-byte pieces of the LDS tile (no bank conflicts; with 4p .. 4p + 3 per lane the two 16-byte writes of a
-        // lane pair collided -- the tile write was the largest single item of the kernel's ablation, 0.9 of 4.1 ms)
-        const unsigned int xo = (xs == kNoTile || !tile_lane) ? kOob : (xs + 2u * (unsigned int)p) * 8u;
-        load_tile(g, xo);
-    };
-
-    // issue() in two halves: the registers of slots 0-3 are free once the first four items are done, so their loads for the packet
-    // `depth` ahead go out BETWEEN the two groups of items (in the shadow of the LDS latency) instead of behind all of them
-    auto issue_part = [&](TallRegs<DICT> &g, unsigned int h, const int part) {
-        const unsigned int off = (unsigned int)__builtin_amdgcn_readlane((int)h, 0);
-        unsigned int c[kTallSlots];
-        widths(h, c);
-        const unsigned int mine = (unsigned int)p * 4u;
-        unsigned int so = off;   // (words)
-        if (part == 1) so += c[0] + c[1] + c[2] + c[3];
         // A packet without a fifth item (lists of <= 4 items: the metric's density, where a cell is one such packet) issues no
         // loads for slots 4-7 and their fifth bytes -- a uniform branch; consume() takes the second group under the same test.  The
         // compiler then counts the loads in flight by the path without them (vmcnt(24-26) instead of 36-41): exact for those
         // packets, a shorter prefetch distance behind a packet that has the second group.  3.30 / 3.30 -> 3.25 / 3.22 ms on the
         // slice, unchanged where lists are five long (profiles/r05_tall_half_packets.log).
-        if (part == 0 || wbase < c[4]) {   // (per wave: the waves past the fifth items' lanes skip them too)
+        if (part == 0 || wbytes < t.w[4]) {   // (per wave: the waves past the fifth items' lanes skip them too)
+            unsigned int so = t.off;   // (bytes)
+            if (part == 1) so += t.w[0] + t.w[1] + t.w[2] + t.w[3];
 #pragma unroll
             for (int k = 4 * part; k < 4 * part + 4; ++k) {
-                g.lo[k] = __builtin_amdgcn_raw_buffer_load_b32(slot_pay(so, c[k]), mine, 0, 2);
+                const unsigned int end = so + t.w[k];   // (= the next slot's first byte)
+                g.lo[k] = __builtin_amdgcn_raw_buffer_load_b32(slot_pay(end), mine, (int)so, 2);   // streamed once
                 if (!DICT) {
-                    const auto v = __builtin_amdgcn_raw_buffer_load_b64(slot_val(so, c[k]), 2u * mine, 0, 2);
+                    const auto v = __builtin_amdgcn_raw_buffer_load_b64(slot_val(end), 2u * mine, (int)(2u * so), 2);
                     g.val[DICT ? 0 : k] = __hiloint2double((int)v[1], (int)v[0]);
                 }
-                so += c[k];
+                so = end;
             }
             if (DICT) {
-                if (part == 0) so += c[4] + c[5] + c[6] + c[7];   // the fifth bytes follow the eight slots: slots 0-3, then slots 4-7
-                else so += c[0];
-                g.hi[DICT ? part : 0] = __builtin_amdgcn_raw_buffer_load_b32(slot_pay(so, c[4 * part]), mine, 0, 2);
+                if (part == 0) so += t.w[4] + t.w[5] + t.w[6] + t.w[7];   // the fifth bytes follow the eight slots: slots 0-3, then slots 4-7
+                else so += t.w[0];
+                g.hi[DICT ? part : 0] = __builtin_amdgcn_raw_buffer_load_b32(slot_pay(so + t.w[4 * part]), mine, (int)so, 2);
             }
         }
         if (part == 1) {   // the tile of the packet `depth` ahead: behind all of this packet's items
-            const unsigned int xs = (unsigned int)__builtin_amdgcn_readlane((int)h, 1) & 0x7fffffffu;
+            // columns past ncol read 0: the displacement of each double is part of the voffset, which the descriptor's range check
+            // covers
+            // lane p carries doubles 2p, 2p + 1 of the tile's first half and of its second half: consecutive lanes then write
+            // consecutive 16-byte pieces of the LDS tile (no bank conflicts; with 4p .. 4p + 3 per lane the two 16-byte writes of a
+            // lane pair collided -- the tile write was the largest single item of the kernel's ablation, 0.9 of 4.1 ms)
+            const unsigned int xs = t.xw & 0x7fffffffu;
             const unsigned int xo = (xs == kNoTile || !tile_lane) ? kOob : (xs + 2u * (unsigned int)p) * 8u;
             load_tile(g, xo);
         }
     };
 
-    auto consume = [&](TallRegs<DICT> &g, unsigned int h, unsigned int hnext, auto &&between) {
-        const unsigned int xw = (unsigned int)__builtin_amdgcn_readlane((int)h, 1);
-        const unsigned int c4 = (unsigned int)__builtin_amdgcn_readlane((int)h, 4) & 0xffffu;   // lanes with a fifth item
+    // (xw, c4: the packet's tile word and the bytes of its lanes with a fifth item, as its header's unpack() left them)
+    auto consume = [&](TallRegs<DICT> &g, const unsigned int xw, const unsigned int c4, auto &&between) {
         if (xw & kPktNewCell) {
             // sums of the previous cell (other lanes owned these rows there) and the x-tile: LDS only, loads stay in flight
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -239,21 +247,37 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
         };
         group(0);   // (a wave without items -- nearly never -- reads cell 0 of the arrays and stores into the scratch cell)
         between();
-        if (wbase < c4) group(4);
+        if (wbytes < c4) group(4);
     };
 
     // prologue: headers of the first 2 x depth packets, payload of the first depth
 #pragma unroll
-    for (int u = 0; u < 2 * kDepth; ++u) hw[u] = hd[(i64)u * 8];
-#pragma unroll
-    for (int u = 0; u < kDepth; ++u) issue(regs[u], hw[u]);
+    for (int u = 0; u < kDepth; ++u) {
+        const TallHdr t = unpack(hd[(i64)u * 8]);
+        xwq[u] = t.xw;
+        c4q[u] = t.w[4];
+        issue_part(regs[u], t, 0);
+        issue_part(regs[u], t, 1);
+        hw[u] = hd[(i64)(u + kDepth) * 8];
+    }
     __syncthreads();
     for (int jj = 0; jj < npk; jj += 2 * kDepth) {
 #pragma unroll
         for (int u = 0; u < 2 * kDepth; ++u) {
-            consume(regs[u % kDepth], hw[u], hw[(u + kDepth) % (2 * kDepth)], [&]() { issue_part(regs[u % kDepth], hw[(u + kDepth) % (2 * kDepth)], 0); });   // packet jj + u
-            issue_part(regs[u % kDepth], hw[(u + kDepth) % (2 * kDepth)], 1);                                               // (payload of packet jj + u + depth)
-            hw[u] = hd[(i64)(jj + u + 2 * kDepth) * 8];                     // header of packet jj + u + 2 depth
+            const int i = u % kDepth;
+            const unsigned int xw = xwq[i], c4 = c4q[i];                     // packet jj + u
+            // header of packet jj + u + depth: unpacked BEHIND this packet's first items, in the shadow of their LDS reads.  In
+            // front of the cell's barrier the same instructions made A x 0.2 and 0.35 ms slower (mean of three alternating runs) on the
+            // two boxes where both places were timed side by side
+            TallHdr t;
+            consume(regs[i], xw, c4, [&]() {
+                t = unpack(hw[i]);
+                xwq[i] = t.xw;
+                c4q[i] = t.w[4];
+                issue_part(regs[i], t, 0);
+            });
+            issue_part(regs[i], t, 1);
+            hw[i] = hd[(i64)(jj + u + 2 * kDepth) * 8];                      // header of packet jj + u + 2 depth
         }
     }
     __syncthreads();   // (every wave is done with this segment's tiles and value table)
