@@ -262,6 +262,44 @@ int slp_cp_batch_get_preconditioners(slp_cp_batch *s, double *t, double *sigma);
  * ms[2] dual kernel. */
 int slp_cp_batch_bench(slp_cp_batch *s, int64_t k, double ms[3]);
 
+/* ---- Chambolle-Pock on a set of LPs with different matrices --------------- *
+ * No counterpart in the reference: `count` calls of chambolle_pock_ppd (ChambollePockPPD.py:36-346) on LPs of any shapes,
+ * one workgroup per LP, whole iterations inside one launch (csrc/slp_cp_many.hip).  Every LP is bit for bit the iterate of
+ * slp_cp in SLP_ORDER_SEQUENTIAL on that LP alone.  alpha and theta are shared.
+ * n, m_eq, m_ineq [count]: the shapes.  The K_k = [A_eq,k; A_ineq,k] come as ONE block-diagonal CSR: the columns of LP k are
+ * offset by sum_{l<k} n_l; the rows are the equality rows of all LPs (LP 0, LP 1, ...) followed by the inequality rows of all
+ * LPs (already one-sided, :74-88); b follows that row order.  c, lb, ub, x0 are concatenated LP by LP; x0 may be NULL (zeros).
+ * Two forms of the same arithmetic, chosen per LP from its shape: x, z, y in LDS for the whole launch when 2 n + m is at
+ * most slp_cp_many_lds_limit() doubles, else in global memory (SLP_CP_MANY_FORM=lds|global forces one for all LPs; lds on an
+ * LP that does not fit is an error).  A launch holds a bounded number of iterations, fixed from the shapes; SLP_CP_MANY_KMAX=<k>
+ * lowers it (1: one iteration per launch); the iterates do not depend on it.
+ * NULL + slp_last_error(), and nothing left allocated: count < 1; an LP without a variable or without a row; indptr not
+ * starting at 0 or decreasing; a column index outside its LP's columns; the set does not fit the device -- checked with
+ * slp_device_memory before anything is allocated. */
+typedef struct slp_cp_many slp_cp_many;
+slp_cp_many *slp_cp_many_create(int64_t count, const int64_t *n, const int64_t *m_eq, const int64_t *m_ineq, const int64_t *indptr,
+                                const int32_t *indices, const double *data, const double *b, const double *c, const double *lb,
+                                const double *ub, const double *x0, double alpha, double theta);
+void slp_cp_many_destroy(slp_cp_many *s);
+/* k whole iterations (:198-240,:333-342) of every LP, enqueued without host synchronisation. */
+int slp_cp_many_iterate(slp_cp_many *s, int64_t k);
+/* The two halves of a reporting iteration, as slp_cp_primal_step / slp_cp_dual_step (:242-329 sits between them). */
+int slp_cp_many_primal_step(slp_cp_many *s);
+int slp_cp_many_dual_step(slp_cp_many *s);
+/* out[5 k + 0..4]: the five numbers of slp_cp_report (:248-283) for LP k, same conventions for absent row kinds.  The maxima
+ * are exact; the two energies are sums in a fixed order of their own, a function of the shapes only. */
+int slp_cp_many_report(slp_cp_many *s, double *out);    /* count x 5 */
+int slp_cp_many_get_x(slp_cp_many *s, double *x);       /* sum n_k, LP by LP */
+int slp_cp_many_get_y(slp_cp_many *s, double *y);       /* sum m_k, LP by LP, each [y_eq,k; y_ineq,k] */
+/* T and Sigma (:122-179) LP by LP, laid out as x and y: those of slp_cp_get_preconditioners on each LP.  Either may be NULL. */
+int slp_cp_many_get_preconditioners(slp_cp_many *s, double *t, double *sigma);
+/* The form LP k runs in: 0 LDS, 1 global memory; -1 for a bad argument. */
+int slp_cp_many_form(const slp_cp_many *s, int64_t k);
+/* Doubles of x, z, y (2 n + m) an LP may hold in LDS. */
+int64_t slp_cp_many_lds_limit(void);
+/* As slp_cp_bench, per iteration of the whole set: ms[0] iteration, ms[1] primal half alone, ms[2] dual half alone. */
+int slp_cp_many_bench(slp_cp_many *s, int64_t k, double ms[3]);
+
 /* ---- projected Gauss-Seidel: replaces gaussSiedel.pyx ------------------- *
  * boundedGaussSeidelClass.__init__ (gaussSiedel.pyx:87-92) and .solve
  * (:95-153).  The sweep keeps the reference's lexicographic data dependence

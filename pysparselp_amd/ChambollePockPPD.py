@@ -566,3 +566,280 @@ def chambolle_pock_ppd_batch(
     finally:
         state.close()
     return x, best
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# a set of LPs with different matrices: one workgroup per LP
+def _many_problem(k, problem):
+    """LP ``k`` of a set, validated (``ValueError``) and brought to the solver's form without touching the library:
+    ``(c, lb, ub, eq, beq, ineq, b_ineq)`` with ``eq`` raw CSR arrays ``(indptr, indices, data, rows)`` or ``None``, ``ineq`` the
+    one-sided system of ``one_sided_system`` or ``None``."""
+    try:
+        count = len(problem)
+    except TypeError:
+        count = -1
+    if count != 8:
+        raise ValueError(f"LP {k} is not a tuple of 8 entries (c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub)")
+    c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub = problem
+    c = _lib.f64(c)
+    if c.ndim != 1 or c.size < 1:
+        raise ValueError(f"LP {k}: c has shape {c.shape}, expected (n,) with n >= 1")
+    n = c.size
+    lb, ub = _lib.f64(lb), _lib.f64(ub)
+    for name, v in (("lb", lb), ("ub", ub)):
+        if v.shape != (n,):
+            raise ValueError(f"LP {k}: {name} has shape {v.shape}, c has {n} entries")
+    if a_eq is not None and a_eq.shape[0] == 0:  # reference :70-72
+        a_eq, beq = None, None
+    if a_ineq is not None and a_ineq.shape[0] == 0:
+        a_ineq = None
+    for name, a in (("a_eq", a_eq), ("a_ineq", a_ineq)):
+        if a is not None:
+            if a.shape[1] != n:
+                raise ValueError(f"LP {k}: {name} has {a.shape[1]} columns, c has {n} entries")
+            if a.indices.size and (a.indices.min() < 0 or a.indices.max() >= n):
+                raise ValueError(f"LP {k}: {name} has a column index outside [0, {n})")
+    eq = None
+    if a_eq is not None:
+        beq = _lib.f64(beq)
+        if beq.shape != (a_eq.shape[0],):
+            raise ValueError(f"LP {k}: beq has shape {beq.shape}, a_eq has {a_eq.shape[0]} rows")
+        eq = _lib.csr_arrays(a_eq) + (a_eq.shape[0],)
+    ineq, b_ineq = None, None
+    if a_ineq is not None:
+        rows = a_ineq.shape[0]
+        b_upper = _lib.f64(b_upper)
+        if b_upper.shape != (rows,):
+            raise ValueError(f"LP {k}: b_upper has shape {b_upper.shape}, a_ineq has {rows} rows")
+        if b_lower is not None:
+            b_lower = _lib.f64(b_lower)
+            if b_lower.shape != (rows,):
+                raise ValueError(f"LP {k}: b_lower has shape {b_lower.shape}, a_ineq has {rows} rows")
+        ineq, b_ineq = one_sided_system(a_ineq, b_lower, b_upper)
+    return c, lb, ub, eq, beq, ineq, b_ineq
+
+
+def many_system(lps):
+    """The LPs ``(c, lb, ub, eq, beq, ineq, b_ineq)`` of ``_many_problem`` (each with at least one row) as the one system
+    ``slp_cp_many_create`` takes -- a dict of:
+
+    ``n``, ``m_eq``, ``m_ineq``: the shapes, int64 arrays of length ``count``;
+    ``col0``, ``eq0``, ``in0``: the per-LP table -- first column, first equality row and first inequality row of every LP;
+    ``indptr``, ``indices``, ``data``: the block-diagonal CSR of the ``K_k = [A_eq,k; A_ineq,k]``: the columns of LP k offset by
+    ``col0[k]``; the rows are the equality rows of all LPs (LP 0, LP 1, ...) followed by the inequality rows of all LPs;
+    ``b`` in that row order; ``c``, ``lb``, ``ub`` concatenated LP by LP."""
+    count = len(lps)
+    n = np.array([lp[0].size for lp in lps], dtype=np.int64)
+    m_eq = np.array([0 if lp[3] is None else lp[3][3] for lp in lps], dtype=np.int64)
+    m_ineq = np.array([0 if lp[5] is None else lp[5][3] for lp in lps], dtype=np.int64)
+    first = lambda sizes: np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64)  # noqa: E731
+    col0, eq0 = first(n), first(m_eq)
+    in0 = int(m_eq.sum()) + first(m_ineq)
+    ptr, idx, val, b = [np.zeros(1, dtype=np.int64)], [], [], []
+    entries = 0
+    for part, rhs in ((3, 4), (5, 6)):
+        for k in range(count):
+            if lps[k][part] is None:
+                continue
+            p, j, v, _ = lps[k][part]
+            ptr.append(entries + p[1:])
+            idx.append(j.astype(np.int64) + col0[k])
+            val.append(v)
+            b.append(_lib.f64(lps[k][rhs]))
+            entries += int(p[-1])
+    cat = lambda parts, dtype: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0), dtype=dtype)  # noqa: E731
+    if int(n.sum()) >= 2 ** 31 or int(m_eq.sum() + m_ineq.sum()) >= 2 ** 31:
+        raise ValueError("the set has 2^31 or more variables or rows")
+    return dict(n=n, m_eq=m_eq, m_ineq=m_ineq, col0=col0, eq0=eq0, in0=in0, indptr=cat(ptr, np.int64), indices=cat(idx, np.int32),
+                data=cat(val, np.float64), b=cat(b, np.float64), c=cat([lp[0] for lp in lps], np.float64),
+                lb=cat([lp[1] for lp in lps], np.float64), ub=cat([lp[2] for lp in lps], np.float64))
+
+
+class CPManyState:
+    """Device-resident Chambolle-Pock state of a set of LPs (thin RAII wrapper of ``slp_cp_many``).  ``lps``: the LPs as
+    ``_many_problem`` returns them, each with at least one row; ``x0``: ``None`` or one start (or ``None``: zeros) per LP."""
+
+    FORMS = ("lds", "global")
+
+    def __init__(self, lps, x0=None, alpha=1, theta=1):
+        if len(lps) < 1:
+            raise ValueError("an empty set of LPs")
+        s = many_system(lps)
+        self.count = len(lps)
+        self.n, self.m = s["n"], s["m_eq"] + s["m_ineq"]
+        self.system = s
+        start = None
+        if x0 is not None and any(v is not None for v in x0):
+            start = _lib.f64(np.concatenate([np.zeros(int(nk)) if v is None else _lib.f64(v) for v, nk in zip(x0, self.n)]))
+            assert start.size == int(self.n.sum())
+        # all of the above needs no GPU; the library is loaded (and bound to a device) only now
+        self._l = _lib.lib()
+        self._h = _lib.check_handle(self._l.slp_cp_many_create(
+            self.count, _lib.ptr(s["n"]), _lib.ptr(s["m_eq"]), _lib.ptr(s["m_ineq"]), _lib.ptr(s["indptr"]), _lib.ptr(s["indices"]),
+            _lib.ptr(s["data"]), _lib.ptr(s["b"]), _lib.ptr(s["c"]), _lib.ptr(s["lb"]), _lib.ptr(s["ub"]), _lib.ptr(start),
+            float(alpha), float(theta)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._l.slp_cp_many_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def iterate(self, k):
+        _lib.check(self._l.slp_cp_many_iterate(self._h, int(k)))
+
+    def primal_step(self):
+        _lib.check(self._l.slp_cp_many_primal_step(self._h))
+
+    def dual_step(self):
+        _lib.check(self._l.slp_cp_many_dual_step(self._h))
+
+    def report(self):
+        """``(count, 5)``: energy1, energy2, max |A_e z - b_e|, max (A_i x - b_i), max |A_e x - b_e| per LP."""
+        out = np.zeros((self.count, 5))
+        _lib.check(self._l.slp_cp_many_report(self._h, _lib.ptr(out)))
+        return out
+
+    def _split(self, flat, sizes):
+        return [v.copy() for v in np.split(flat, np.cumsum(sizes)[:-1])]
+
+    def x(self):
+        out = np.empty(int(self.n.sum()))
+        _lib.check(self._l.slp_cp_many_get_x(self._h, _lib.ptr(out)))
+        return self._split(out, self.n)
+
+    def y(self):
+        """Per LP ``[y_eq; y_ineq]``."""
+        out = np.empty(int(self.m.sum()))
+        _lib.check(self._l.slp_cp_many_get_y(self._h, _lib.ptr(out)))
+        return self._split(out, self.m)
+
+    def preconditioners(self):
+        t, s = np.empty(int(self.n.sum())), np.empty(int(self.m.sum()))
+        _lib.check(self._l.slp_cp_many_get_preconditioners(self._h, _lib.ptr(t), _lib.ptr(s)))
+        return self._split(t, self.n), self._split(s, self.m)
+
+    def form(self, k):
+        """``"lds"`` or ``"global"``: where LP ``k`` keeps x, z, y during a launch."""
+        f = int(self._l.slp_cp_many_form(self._h, int(k)))
+        if f < 0:
+            raise IndexError(f"LP {k} of {self.count}")
+        return self.FORMS[f]
+
+    def bench(self, k):
+        ms = np.zeros(3)
+        _lib.check(self._l.slp_cp_many_bench(self._h, int(k), _lib.ptr(ms)))
+        return ms
+
+
+def many_lds_limit():
+    """Doubles of x, z, y (``2 n + m``) an LP may hold in LDS (``slp_cp_many_lds_limit``)."""
+    return int(_lib.load().slp_cp_many_lds_limit())
+
+
+def _box_vertex(c, lb, ub):
+    x = np.zeros_like(lb)  # reference :147-151
+    x[c > 0] = lb[c > 0]
+    x[c < 0] = ub[c < 0]
+    return x
+
+
+def chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=100, callback_func=None, max_time=None, nb_iter_plot=10):
+    """``chambolle_pock_ppd`` for a list of LPs whose matrices differ (extension; the reference solves one LP per call).
+
+    ``problems`` is a sequence of 8-tuples ``(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub)``, each as ``chambolle_pock_ppd``
+    takes them (one-sided stacking for a finite ``b_lower``, :74-88; an absent kind of rows is ``None`` or a matrix without
+    rows); ``x0`` is ``None`` or a sequence with one start (or ``None``) per LP; ``alpha`` and ``theta`` are shared.  Every shape
+    error is a ``ValueError`` raised before the library is loaded.  The LPs become one block-diagonal system on the device and
+    every LP is one workgroup that runs whole iterations inside one launch, its iterates in LDS where they fit
+    (pysparselp_amd/csrc/slp_cp_many.hip); every LP is bit for bit what ``chambolle_pock_ppd(..., order=ORDER_SEQUENTIAL)``
+    computes for it alone.
+
+    The reporting loop is that of ``chambolle_pock_ppd``: ``callback_func(niter, xs, energy1, energy2, elapsed,
+    max_violated_equality, max_violated_inequality)`` every ``nb_iter_plot`` iterations with ``xs`` a list of arrays and the rest
+    arrays of length ``count``; ``max_time`` stops all LPs at a report.  Returns ``(xs, best_integer_solutions)``, two lists (the
+    latter: ``None`` or the best feasible iterate of that LP, :284-291).  An LP without any constraint gets its box vertex
+    (:147-151) and takes no part in the iterations.
+
+    Under a communicator every rank solves the whole list (a replica).  For LPs that share one matrix
+    ``chambolle_pock_ppd_batch`` reads the matrix once for all of them.  The block-diagonal concatenation of the list handed to
+    ``chambolle_pock_ppd`` as ONE LP computes the same bits per block in two launches per iteration; which of the two is faster at
+    a given count is what ``tools/bench_cp_many.py`` measures -- not measured yet.
+    """
+    start = time.perf_counter()
+    try:
+        count = len(problems)
+    except TypeError:
+        raise ValueError("problems must be a sequence of 8-tuples (c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub)") from None
+    if count < 1:
+        raise ValueError("an empty list of LPs: problems needs at least one entry")
+    lps = [_many_problem(k, p) for k, p in enumerate(problems)]
+    if x0 is not None:
+        try:
+            given = len(x0)
+        except TypeError:
+            given = -1
+        if given != count:
+            raise ValueError(f"x0 must be None or a sequence of {count} starts, one per LP")
+        x0 = [None if v is None else _lib.f64(v) for v in x0]
+        for k, v in enumerate(x0):
+            if v is not None and v.shape != lps[k][0].shape:
+                raise ValueError(f"LP {k}: x0 has shape {v.shape}, c has {lps[k][0].size} entries")
+    solved = [k for k in range(count) if lps[k][3] is not None or lps[k][5] is not None]
+    xs = [None if (lps[k][3] is not None or lps[k][5] is not None) else _box_vertex(*lps[k][:3]) for k in range(count)]
+    best = [None] * count
+    if not solved:
+        return xs, best
+    costs = [lps[k][0] for k in solved]
+    has_ineq = np.array([lps[k][5] is not None for k in solved])
+    state = CPManyState([lps[k] for k in solved], None if x0 is None else [x0[k] for k in solved], alpha, theta)
+
+    def spread(values, fill):
+        """Per-LP numbers of the solved LPs over the whole list."""
+        out = np.array(fill, dtype=np.float64)
+        out[solved] = values
+        return out
+
+    def all_x(part):
+        out = list(xs)
+        for k, v in zip(solved, part):
+            out[k] = v
+        return out
+
+    free_energy = np.array([0.0 if xs[k] is None else lps[k][0].dot(xs[k]) for k in range(count)])
+    try:
+        best_energy = np.full(len(solved), np.inf)
+        niter = 0
+        while niter < nb_max_iter:
+            if niter % nb_iter_plot == 0:
+                state.primal_step()
+                elapsed = time.perf_counter() - start
+                if (max_time is not None) and collective_elapsed(elapsed) > max_time:  # the same decision on every rank
+                    break
+                energy1, energy2, max_violated_equality, max_violated_inequality, max_eq_at_x = state.report().T.copy()
+                max_violated_inequality[~has_ineq] = 0  # the reference dereferences a_ineq here (:283) and fails
+                x = None
+                feasible = np.nonzero((max_eq_at_x == 0) & (max_violated_inequality <= 0))[0]
+                if feasible.size:
+                    x = state.x()
+                    for i in feasible:
+                        energy_rounded = costs[i].dot(x[i])
+                        if energy_rounded < best_energy[i]:
+                            best_energy[i] = energy_rounded
+                            best[solved[i]] = x[i].copy()
+                if callback_func is not None:
+                    if x is None:
+                        x = state.x()
+                    callback_func(niter, all_x(x), spread(energy1, free_energy), spread(energy2, free_energy), elapsed,
+                                  spread(max_violated_equality, np.zeros(count)), spread(max_violated_inequality, np.zeros(count)))
+                state.dual_step()
+                niter += 1
+            else:
+                k = min(nb_iter_plot - niter % nb_iter_plot, nb_max_iter - niter)
+                state.iterate(k)
+                niter += k
+        xs = all_x(state.x())
+    finally:
+        state.close()
+    return xs, best

@@ -24,7 +24,7 @@ import numpy as np
 import scipy.sparse
 
 from .ADMM import lp_admm, lp_admm_batch
-from .ChambollePockPPD import chambolle_pock_ppd, chambolle_pock_ppd_batch
+from .ChambollePockPPD import chambolle_pock_ppd, chambolle_pock_ppd_batch, chambolle_pock_ppd_many
 from ._lib import ORDER_AUTO
 
 solving_methods = ("chambolle_pock_ppd", "admm", "admm_blocks", "admm2")
@@ -32,6 +32,8 @@ solving_methods = ("chambolle_pock_ppd", "admm", "admm_blocks", "admm2")
 dual_methods = ("dual_gradient_ascent",)
 # methods of ``solve_batch``: many cost vectors over this LP's constraints, advanced together
 batch_methods = ("chambolle_pock_ppd",)
+# methods of ``solve_many``: a list of LPs with matrices of their own, one workgroup per LP
+many_methods = ("chambolle_pock_ppd",)
 
 _SCALARS = (int, float, np.integer, np.floating)
 
@@ -690,3 +692,64 @@ class SparseLP:
         self.dual_lower_bounds = report[:, 0].copy()
         elapsed = time.perf_counter() - start
         return (x, elapsed) if get_timing else x
+
+
+_CURVES = ("distance_to_ground_truth", "distanceToGroundTruthAfterRounding", "opttime_curve", "dopttime_curve", "pobj_curve",
+           "dobj_curve", "pobjbound", "max_violated_inequality", "max_violated_equality", "max_violated_constraint", "itrn_curve")
+
+
+def solve_many(lps, method="chambolle_pock_ppd", get_timing=True, nb_iter=10000, max_time=None, nb_iter_plot=10):
+    """Solve a list of ``SparseLP`` objects whose matrices differ in ONE call, every LP one workgroup on the GPU (extension: the
+    reference solves one LP per call); returns the list of ``x``, or ``(xs, elapsed)`` with ``get_timing``.
+
+    Only ``method="chambolle_pock_ppd"`` exists in this form (``many_methods``; ``ChambollePockPPD.chambolle_pock_ppd_many``); any
+    other raises ``ValueError``.  Per LP the preparation is that of ``solve(setup="host")``: ``copy.deepcopy`` and
+    ``remove_fixed_variables`` on the host (reference :1244-1248), ``x = m_change * sol - shift`` afterwards (:1259,:1288).
+    ``xs[k]`` is bit for bit what ``lps[k].solve(method="chambolle_pock_ppd", order=ORDER_SEQUENTIAL, setup="host")`` returns.
+
+    Fills every LP's curve attributes as ``solve`` does, at every report: ``itrn_curve``, ``opttime_curve``, ``dopttime_curve``,
+    ``pobj_curve``, ``dobj_curve``, ``max_violated_constraint``, ``max_violated_equality``, ``max_violated_inequality``.
+    ``max_time`` stops all LPs at a report.  Under a communicator every rank solves the whole list (a replica).
+    """
+    if method not in many_methods:
+        raise ValueError(f"method {method!r} has no one-workgroup-per-LP form; solve_many supports: {many_methods}")
+    lps = list(lps)
+    if len(lps) < 1:
+        raise ValueError("an empty list of LPs")
+    start = time.perf_counter()
+    problems, maps = [], []
+    for lp in lps:
+        for name in _CURVES:
+            setattr(lp, name, [])
+        reduced = copy.deepcopy(lp)
+        free, shift = reduced.remove_fixed_variables()
+        if reduced.nb_variables < 1:
+            raise ValueError("an LP of the list has no free variable (lower_bounds == upper_bounds everywhere)")
+        maps.append((np.nonzero(free)[0], free.size, shift))
+        problems.append((reduced.costsvector, reduced.a_equalities, reduced.b_equalities, reduced.a_inequalities, reduced.b_lower,
+                         reduced.b_upper, reduced.lower_bounds, reduced.upper_bounds))
+
+    def expand(k, sol):
+        # reference :1259,:1288: x = m_change * sol - shift (note the sign it applies to the fixed values)
+        free_ids, size, shift = maps[k]
+        full = np.zeros(size)
+        full[free_ids] = sol
+        return full - shift
+
+    def record(niter, solutions, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
+        for k, lp in enumerate(lps):
+            solution = expand(k, solutions[k])
+            lp.itrn_curve.append(niter)
+            lp.opttime_curve.append(duration)
+            lp.dopttime_curve.append(duration)
+            lp.dobj_curve.append(energy2[k])
+            lp.pobj_curve.append(energy1[k])
+            lp.max_violated_constraint.append(lp.max_constraint_violation(solution))
+            lp.max_violated_equality.append(max_violated_equality[k])
+            lp.max_violated_inequality.append(max_violated_inequality[k])
+
+    sols, _ = chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=nb_iter, callback_func=record, max_time=max_time,
+                                      nb_iter_plot=nb_iter_plot)
+    xs = [expand(k, sol) for k, sol in enumerate(sols)]
+    elapsed = time.perf_counter() - start
+    return (xs, elapsed) if get_timing else xs

@@ -89,6 +89,18 @@ _SIGNATURES = {
     "slp_cp_batch_get_y": (c_int, [c_vp, c_vp]),
     "slp_cp_batch_get_preconditioners": (c_int, [c_vp, c_vp, c_vp]),
     "slp_cp_batch_bench": (c_int, [c_vp, c_i64, c_vp]),
+    "slp_cp_many_create": (c_vp, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl]),
+    "slp_cp_many_destroy": (None, [c_vp]),
+    "slp_cp_many_iterate": (c_int, [c_vp, c_i64]),
+    "slp_cp_many_primal_step": (c_int, [c_vp]),
+    "slp_cp_many_dual_step": (c_int, [c_vp]),
+    "slp_cp_many_report": (c_int, [c_vp, c_vp]),
+    "slp_cp_many_get_x": (c_int, [c_vp, c_vp]),
+    "slp_cp_many_get_y": (c_int, [c_vp, c_vp]),
+    "slp_cp_many_get_preconditioners": (c_int, [c_vp, c_vp, c_vp]),
+    "slp_cp_many_form": (c_int, [c_vp, c_i64]),
+    "slp_cp_many_lds_limit": (c_i64, []),
+    "slp_cp_many_bench": (c_int, [c_vp, c_i64, c_vp]),
     "slp_gs_create": (c_vp, [c_i64, c_vp, c_vp, c_vp]),
     "slp_gs_destroy": (None, [c_vp]),
     "slp_gs_num_levels": (c_i64, [c_vp]),

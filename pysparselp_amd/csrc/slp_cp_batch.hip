@@ -24,6 +24,7 @@
 // function of the shapes only); a slice adds its terms in increasing r, and one lane per instance adds the S slice sums
 // in increasing slice order (maxima are exact in any order).  x4 is written by the primal half of a reporting iteration.
 #include "slp_common.h"
+#include "slp_cp_shared.h"
 #include "slp_kernels.h"
 
 namespace slp {
@@ -79,37 +80,15 @@ __global__ __launch_bounds__(kBlock) void k_cpb_primal(i64 n, i64 m, const i64 *
     for (i64 jj = group; jj < n; jj += ngroups) {
         const i64 j = cpb_uniform<BT>(jj);
         const i64 s = tptr[j], e = tptr[j + 1];
-        // storage order, equality and inequality partial sums apart (row_dot_split<1>); loads four entries ahead, adds in order
-        double se = 0.0, si = 0.0;
-        for (i64 q0 = s; q0 < e; q0 += 4) {
-            i32 r[4];
-            double a[4], g[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const i64 qq = (q0 + q < e) ? q0 + q : e - 1;
-                r[q] = tidx[qq];
-                a[q] = tval[qq];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) g[q] = yt[(i64)r[q] * BT];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (q0 + q < e) {
-                    const double p = a[q] * g[q];
-                    if (r[q] < m_eq) se += p;
-                    else si += p;
-                }
-        }
+        // storage order, equality and inequality partial sums apart (slp_cp_shared.h: the set solver runs the same functions)
+        double se, si;
+        cp_column_sums(s, e, tidx, tval, yt, BT, m_eq, CpLoadPlain(), &se, &si);
         const i64 o = (tile * n + j) * BT + k;
-        const double cj = c[o];
-        double d;
-        if (m_eq > 0 && m_ineq > 0) d = (cj + se) + si;  // :206,216
-        else if (m_eq > 0) d = cj + se;
-        else d = cj + si;
+        const double d = cp_direction(c[o], se, si, m_eq > 0, m_ineq > 0);  // :206,216
         const double xo = x[o], l = lb[o], u = ub[o];
-        double x2 = xo - t[j] * d;  // :220
-        x2 = cp_clip(x2, l, u);
-        z[o] = one_plus_theta * x2 - theta * xo;  // :226
+        double x2, zn;
+        cp_primal_point(d, xo, t[j], l, u, one_plus_theta, theta, &x2, &zn);  // :220,226
+        z[o] = zn;
         x[o] = x2;
         if (STORE) x4[o] = (d < 0.0) ? u : l;
     }
@@ -129,27 +108,9 @@ __global__ __launch_bounds__(kBlock) void k_cpb_dual(i64 n, i64 m, const i64 *__
     for (i64 ii = group; ii < m; ii += ngroups) {
         const i64 i = cpb_uniform<BT>(ii);
         const i64 s = ptr[i], e = ptr[i + 1];
-        double kz = 0.0;  // row_dot<1>
-        for (i64 q0 = s; q0 < e; q0 += 4) {
-            i32 j[4];
-            double a[4], g[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const i64 qq = (q0 + q < e) ? q0 + q : e - 1;
-                j[q] = idx[qq];
-                a[q] = val[qq];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) g[q] = zt[(i64)j[q] * BT];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (q0 + q < e) kz += a[q] * g[q];
-        }
+        const double kz = cp_row_sum(s, e, idx, val, zt, BT, CpLoadPlain());
         const i64 o = (tile * m + i) * BT + k;
-        const double r = kz - b[o];           // :235,240
-        double yn = y[o] + sigma[i] * r;      // :334,339
-        if (i >= m_eq) yn = (yn < 0.0) ? 0.0 : yn;  // :341
-        y[o] = yn;
+        y[o] = cp_dual_point(kz, b[o], y[o], sigma[i], i >= m_eq);  // :235,240,:334,339,:341
     }
 }
 

@@ -1,0 +1,453 @@
+// slp_cp_many.hip -- Chambolle-Pock on a SET of LPs whose constraint matrices differ: one workgroup per LP, whole iterations
+// inside one launch.  No counterpart in the reference (single-threaded numpy: N solves are N calls of chambolle_pock_ppd,
+// ChambollePockPPD.py:36-346, each of them two launches per iteration here and bound by launch latency when the LP is small).
+// An iteration of the method has no global scalar -- no dot product, no step size beyond the per-row Sigma and the per-column T --
+// so it is two sparse walks separated by a barrier, and N independent LPs are N independent workgroups:
+//   primal half : a lane walks its column of K^T, d = (c + se) + si, x+ = clip(x - T d), z = (1+theta) x+ - theta x   [:198-228]
+//   barrier
+//   dual half   : a lane walks its row of K, y += Sigma (K z - b), inequality rows clamped at 0                        [:231-240,:333-342]
+//   barrier
+// with the device functions of slp_cp_shared.h: every LP is bit for bit the iterate of slp_cp in SLP_ORDER_SEQUENTIAL on that LP.
+//
+// Layout.  The K_k = [A_eq,k; A_ineq,k] form ONE block-diagonal CSR: the columns of LP k are offset by sum_{l<k} n_l; the rows are
+// all equality rows (LP 0, LP 1, ...) followed by all inequality rows, so that "row < m_eq" with the global m_eq = sum m_eq,k
+// tells the two kinds apart and the set-up of the single solver (build_transpose: rows increasing inside a column;
+// cp_preconditioners_csr: per-column and per-row sums) gives every LP the entry order and the T, Sigma of its own set-up.  After
+// that set-up the index arrays of both orientations are rewritten IN PLACE to indices local to their LP (column - col0; row
+// - eq0, or m_eq,k + row - in0): both forms of the kernel then address an LP's vectors from their base, in LDS or in global memory.
+// x, z, x4, c, lb, ub, T are concatenated LP by LP; y is kept LP by LP as [y_eq,k; y_ineq,k]; b and Sigma in the row order of K.
+// CpmLp, one per LP, holds its column range and its two row ranges.
+//
+// Two forms, the same arithmetic, chosen per LP from its shape only (SLP_CP_MANY_FORM=lds|global forces one):
+//   lds     2 n + m <= kCpmLdsLimit doubles: x, z, y live in LDS for the whole launch, loaded at its start and written back at its end;
+//   global  x, z, y stay in global memory and are re-read across the barriers with workgroup-scope relaxed loads, nothing kept in
+//           a register across a barrier (as k_admmb_tile, k_gs_sweep_one_block).
+// c, T, lb, ub, b, Sigma are read from global memory in both.  The LPs of each form are one launch; its workgroup has
+// W = the power of two >= max_k max(n_k, m_k) over the LPs of that form, clamped to 64 .. 1024 lanes (lanes loop beyond).
+// No atomics between workgroups, no spin waits, no grid barrier: a workgroup never waits for another.
+//
+// Launch cap.  A launch holds at most kCpmUnitsPerLaunch workgroup passes (a pass: the workgroup once over its columns or rows) per
+// compute unit: iterations per launch = kCpmUnitsPerLaunch / (passes per iteration of the largest LP * ceil(LPs / compute units)),
+// between 1 and 1024; longer runs are split.  SLP_CP_MANY_KMAX=<k> lowers the cap (1: one iteration per launch); the iterates do not
+// depend on it.
+//
+// Report, per LP, one workgroup of 256 lanes on the written-back state: lane t takes rows (columns) t, t + 256, ... in increasing
+// order -- per row the three chains K x, K x4, K z of one walk -- then block_reduce: a fixed order, a function of the shapes only.
+// The maxima are exact.  x4 is written by the primal half of a reporting iteration.
+#include <algorithm>
+#include <memory>
+#include <type_traits>
+
+#include "slp_common.h"
+#include "slp_cp_shared.h"
+#include "slp_kernels.h"
+
+namespace slp {
+
+// slp_cp.hip: T and Sigma by the CSR walks of the single-instance set-up
+void cp_preconditioners_csr(slp_matrix *k, i64 m_eq, double alpha, double *t, double *sigma);
+
+constexpr int kCpmMaxBlock = 1024;
+// doubles of x, z, y an LP may hold in LDS: 160 000 of the compute unit's 163 840 bytes; the rest stays free for a kernel's static
+// scratch (block_reduce: 32 bytes)
+constexpr i64 kCpmLdsLimit = 20000;
+constexpr i64 kCpmUnitsPerLaunch = 8192;
+constexpr i64 kCpmMaxItersPerLaunch = 1024;
+
+struct CpmLp {
+    i64 col0;      // first column: x, z, x4, c, lb, ub, T; rows of K^T
+    i64 eq0, in0;  // first equality row, first inequality row in K: b, Sigma, row pointers
+    i64 y0;        // where [y_eq; y_ineq] lie in y
+    i32 n, m_eq, m_in;
+    i32 form;      // 0 lds, 1 global
+};
+
+// row `r` of the LP (equality rows first) in the row order of K
+__device__ __forceinline__ i64 cpm_row(const CpmLp &lp, i32 r) { return r < lp.m_eq ? lp.eq0 + r : lp.in0 + (r - lp.m_eq); }
+
+// the index arrays of both orientations, global -> local to the LP; one workgroup per LP
+__global__ __launch_bounds__(kBlock) void k_cpm_localise(const CpmLp *__restrict__ lps, const i64 *__restrict__ ptr, i32 *__restrict__ idx,
+                                                         const i64 *__restrict__ tptr, i32 *__restrict__ tidx, i64 m_eq_all) {
+    const CpmLp lp = lps[blockIdx.x];
+    const i32 m = lp.m_eq + lp.m_in;
+    for (i32 r = threadIdx.x; r < m; r += kBlock) {
+        const i64 g = cpm_row(lp, r);
+        for (i64 q = ptr[g]; q < ptr[g + 1]; ++q) idx[q] = (i32)(idx[q] - lp.col0);
+    }
+    for (i32 j = threadIdx.x; j < lp.n; j += kBlock)
+        for (i64 q = tptr[lp.col0 + j]; q < tptr[lp.col0 + j + 1]; ++q) {
+            const i64 g = tidx[q];
+            tidx[q] = (i32)(g < m_eq_all ? g - lp.eq0 : lp.m_eq + (g - lp.in0));
+        }
+}
+
+struct CpmArgs {
+    const CpmLp *lps;
+    const i32 *list;  // the LPs of this launch
+    const i64 *ptr, *tptr;
+    const i32 *idx, *tidx;  // local indices
+    const double *val, *tval, *c, *t, *lb, *ub, *b, *sigma;
+    double *x, *z, *y, *x4;
+    double one_plus_theta, theta;
+};
+
+// `iters` times the stages of one LP (bit 0 primal half, bit 1 dual half); store: the primal half also writes x4 (:260-261)
+template <bool LDS>
+__global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int iters, int stages, int store) {
+    extern __shared__ __attribute__((aligned(16))) double cpm_lds[];
+    using LD = typename std::conditional<LDS, CpLoadPlain, CpLoadWorkgroup>::type;
+    const LD ld;
+    const CpmLp lp = a.lps[a.list[blockIdx.x]];
+    const i32 n = lp.n, m = lp.m_eq + lp.m_in, W = (i32)blockDim.x, tid = (i32)threadIdx.x;
+    const bool has_eq = lp.m_eq > 0, has_in = lp.m_in > 0;
+    double *xg = a.x + lp.col0, *zg = a.z + lp.col0, *yg = a.y + lp.y0;
+    double *xs = xg, *zs = zg, *ys = yg;
+    if (LDS) {
+        xs = cpm_lds;
+        zs = xs + n;
+        ys = zs + n;
+        for (i32 j = tid; j < n; j += W) { xs[j] = xg[j]; zs[j] = zg[j]; }
+        for (i32 r = tid; r < m; r += W) ys[r] = yg[r];
+        __syncthreads();
+    }
+    const double *c = a.c + lp.col0, *t = a.t + lp.col0, *lb = a.lb + lp.col0, *ub = a.ub + lp.col0;
+    const i64 *tptr = a.tptr + lp.col0;
+    for (int it = 0; it < iters; ++it) {
+        if (stages & 1) {
+            for (i32 j = tid; j < n; j += W) {
+                double se, si;
+                cp_column_sums(tptr[j], tptr[j + 1], a.tidx, a.tval, ys, 1, lp.m_eq, ld, &se, &si);
+                const double d = cp_direction(c[j], se, si, has_eq, has_in);
+                const double xo = ld(xs + j), l = lb[j], u = ub[j];
+                double x2, zn;
+                cp_primal_point(d, xo, t[j], l, u, a.one_plus_theta, a.theta, &x2, &zn);
+                zs[j] = zn;
+                xs[j] = x2;
+                if (store) a.x4[lp.col0 + j] = (d < 0.0) ? u : l;
+            }
+            __syncthreads();  // same compute unit: the stores of this half are visible to the next one
+        }
+        if (stages & 2) {
+            for (i32 r = tid; r < m; r += W) {
+                const i64 g = cpm_row(lp, r);
+                const double kz = cp_row_sum(a.ptr[g], a.ptr[g + 1], a.idx, a.val, zs, 1, ld);
+                ys[r] = cp_dual_point(kz, a.b[g], ld(ys + r), a.sigma[g], r >= lp.m_eq);
+            }
+            __syncthreads();
+        }
+    }
+    if (LDS) {
+        for (i32 j = tid; j < n; j += W) { xg[j] = xs[j]; zg[j] = zs[j]; }
+        for (i32 r = tid; r < m; r += W) yg[r] = ys[r];
+    }
+}
+
+// out[5 k + 0..4] as slp_cp_report; one workgroup per LP
+__global__ __launch_bounds__(kBlock) void k_cpm_report(CpmArgs a, double *__restrict__ out) {
+    __shared__ double lds[kBlock / kWave];
+    const CpmLp lp = a.lps[blockIdx.x];
+    const i32 m = lp.m_eq + lp.m_in;
+    const double *x = a.x + lp.col0, *x4 = a.x4 + lp.col0, *z = a.z + lp.col0, *y = a.y + lp.y0, *c = a.c + lp.col0;
+    double s1 = 0.0, s2 = 0.0, veq = -__builtin_inf(), vin = -__builtin_inf(), veqx = -__builtin_inf(), c0 = 0.0, c1 = 0.0;
+    for (i32 r = threadIdx.x; r < m; r += kBlock) {
+        const i64 g = cpm_row(lp, r);
+        double kx = 0.0, kx4 = 0.0, kz = 0.0;  // three chains in storage order
+        for (i64 q = a.ptr[g]; q < a.ptr[g + 1]; ++q) {
+            const i32 j = a.idx[q];
+            const double v = a.val[q];
+            kx += v * x[j];
+            kx4 += v * x4[j];
+            kz += v * z[j];
+        }
+        const double bi = a.b[g], yi = y[r];
+        s1 += yi * (kx - bi);
+        s2 += yi * (kx4 - bi);
+        if (r < lp.m_eq) {
+            const double e = fabs(kz - bi), ex = fabs(kx - bi);
+            veq = e > veq ? e : veq;
+            veqx = ex > veqx ? ex : veqx;
+        } else {
+            const double v = kx - bi;
+            vin = v > vin ? v : vin;
+        }
+    }
+    for (i32 j = threadIdx.x; j < lp.n; j += kBlock) {
+        const double cj = c[j];
+        c0 += cj * x[j];
+        c1 += cj * x4[j];
+    }
+    const double r0 = block_reduce<false>(s1, lds), r1 = block_reduce<false>(s2, lds);
+    const double r2 = block_reduce<true>(veq, lds), r3 = block_reduce<true>(vin, lds), r4 = block_reduce<true>(veqx, lds);
+    const double r5 = block_reduce<false>(c0, lds), r6 = block_reduce<false>(c1, lds);
+    if (threadIdx.x == 0) {
+        double *o = out + (i64)blockIdx.x * 5;
+        o[0] = r5 + r0;
+        o[1] = r6 + r1;
+        o[2] = (lp.m_eq > 0) ? (r2 == -__builtin_inf() ? 0.0 : r2) : 0.0;
+        o[3] = r3;
+        o[4] = (r4 == -__builtin_inf()) ? 0.0 : r4;
+    }
+}
+
+}  // namespace slp
+
+using namespace slp;
+
+struct slp_cp_many {
+    slp_matrix *k = nullptr;  // owned; its index arrays are local to the LPs once the set-up is done
+    i64 count = 0, n = 0, m = 0, m_eq = 0;
+    double alpha = 1, theta = 1;
+    std::vector<CpmLp> lps;
+    // the LPs of each form: their list on the device, the workgroup, the dynamic LDS and the iterations one launch may hold
+    struct Group {
+        std::vector<i32> ids;
+        DevBuf<i32> list;
+        int block = kWave;
+        size_t lds_bytes = 0;
+        i64 kmax = 1;
+    } group[2];
+    DevBuf<CpmLp> table;
+    DevBuf<double> b, c, lb, ub, t, sigma, x, z, y, x4, out;
+    ~slp_cp_many() { delete k; }
+};
+
+namespace slp {
+
+static CpmArgs cpm_args(const slp_cp_many *s, int g) {
+    const CsrDev &a = s->k->a, &at = s->k->at;
+    CpmArgs r;
+    r.lps = s->table.p;
+    r.list = s->group[g].list.p;
+    r.ptr = a.ptr.p; r.tptr = at.ptr.p;
+    r.idx = a.idx.p; r.tidx = at.idx.p;
+    r.val = a.val.p; r.tval = at.val.p;
+    r.c = s->c.p; r.t = s->t.p; r.lb = s->lb.p; r.ub = s->ub.p; r.b = s->b.p; r.sigma = s->sigma.p;
+    r.x = s->x.p; r.z = s->z.p; r.y = s->y.p; r.x4 = s->x4.p;
+    r.one_plus_theta = 1.0 + s->theta;
+    r.theta = s->theta;
+    return r;
+}
+
+// `k` times the stages, in launches of at most kmax iterations per form
+static void cpm_run(slp_cp_many *s, i64 k, int stages, bool store) {
+    hipStream_t st = ctx().stream;
+    for (int g = 0; g < 2; ++g) {
+        const slp_cp_many::Group &gr = s->group[g];
+        if (gr.ids.empty()) continue;
+        const CpmArgs a = cpm_args(s, g);
+        for (i64 done = 0; done < k;) {
+            const int it = (int)std::min<i64>(gr.kmax, k - done);
+            if (g == 0)
+                hipLaunchKernelGGL((k_cpm_iterate<true>), dim3((unsigned)gr.ids.size()), dim3(gr.block), gr.lds_bytes, st, a, it, stages,
+                                   (int)store);
+            else
+                hipLaunchKernelGGL((k_cpm_iterate<false>), dim3((unsigned)gr.ids.size()), dim3(gr.block), 0, st, a, it, stages, (int)store);
+            SLP_HIP(hipGetLastError());
+            done += it;
+        }
+    }
+}
+
+// form per LP, workgroup, LDS and launch cap per form -- from the shapes (and the two environment switches) only
+static void cpm_plan(slp_cp_many *s) {
+    int force = -1;
+    if (const char *e = getenv("SLP_CP_MANY_FORM")) {
+        if (!strcmp(e, "lds")) force = 0;
+        else if (!strcmp(e, "global")) force = 1;
+        else if (e[0]) throw Error(std::string("SLP_CP_MANY_FORM must be lds or global, not ") + e);
+    }
+    i64 cap = kCpmMaxItersPerLaunch;
+    if (const char *e = getenv("SLP_CP_MANY_KMAX")) {
+        if (e[0]) {
+            const i64 v = atoll(e);
+            if (v < 1) throw Error(std::string("SLP_CP_MANY_KMAX must be a positive number of iterations, not ") + e);
+            cap = std::min(cap, v);
+        }
+    }
+    for (i64 k = 0; k < s->count; ++k) {
+        CpmLp &lp = s->lps[(size_t)k];
+        const i64 doubles = 2 * (i64)lp.n + lp.m_eq + lp.m_in;
+        const bool fits = doubles <= kCpmLdsLimit;
+        if (force == 0 && !fits)
+            throw Error("slp_cp_many_create: SLP_CP_MANY_FORM=lds, but LP " + std::to_string(k) + " needs " + std::to_string(doubles) +
+                        " doubles of LDS (2 n + m) and the form holds " + std::to_string(kCpmLdsLimit));
+        lp.form = force >= 0 ? force : (fits ? 0 : 1);
+        s->group[lp.form].ids.push_back((i32)k);
+    }
+    const i64 cus = std::max(1, ctx().num_cu);
+    for (int g = 0; g < 2; ++g) {
+        slp_cp_many::Group &gr = s->group[g];
+        if (gr.ids.empty()) continue;
+        i64 widest = 1, doubles = 0;
+        for (i32 k : gr.ids) {
+            const CpmLp &lp = s->lps[(size_t)k];
+            widest = std::max<i64>(widest, std::max<i64>(lp.n, (i64)lp.m_eq + lp.m_in));
+            doubles = std::max<i64>(doubles, 2 * (i64)lp.n + lp.m_eq + lp.m_in);
+        }
+        int w = kWave;
+        while (w < widest && w < kCpmMaxBlock) w *= 2;
+        gr.block = w;
+        gr.lds_bytes = g == 0 ? (size_t)doubles * sizeof(double) : 0;
+        i64 passes = 1;
+        for (i32 k : gr.ids) {
+            const CpmLp &lp = s->lps[(size_t)k];
+            passes = std::max<i64>(passes, (lp.n + w - 1) / w + ((i64)lp.m_eq + lp.m_in + w - 1) / w);
+        }
+        const i64 rounds = ((i64)gr.ids.size() + cus - 1) / cus;
+        gr.kmax = std::min(cap, std::max<i64>(1, kCpmUnitsPerLaunch / (passes * rounds)));
+    }
+}
+
+}  // namespace slp
+
+extern "C" {
+
+int64_t slp_cp_many_lds_limit(void) { return kCpmLdsLimit; }
+
+slp_cp_many *slp_cp_many_create(int64_t count, const int64_t *n, const int64_t *m_eq, const int64_t *m_ineq, const int64_t *indptr,
+                                const int32_t *indices, const double *data, const double *b, const double *c, const double *lb,
+                                const double *ub, const double *x0, double alpha, double theta) {
+    SLP_API_PTR({
+        SLP_REQUIRE(count >= 1, "slp_cp_many_create: count must be at least 1");
+        SLP_REQUIRE(n && m_eq && m_ineq && indptr && b && c && lb && ub, "slp_cp_many_create: NULL argument");
+        // everything below up to the memory check reads the host arrays only: nothing is allocated before the set is known to be
+        // well formed and to fit
+        auto s = std::unique_ptr<slp_cp_many>(new slp_cp_many());
+        s->count = count; s->alpha = alpha; s->theta = theta;
+        s->lps.resize((size_t)count);
+        i64 N = 0, Me = 0, Mi = 0;
+        for (i64 k = 0; k < count; ++k) {
+            SLP_REQUIRE(n[k] >= 1 && m_eq[k] >= 0 && m_ineq[k] >= 0 && m_eq[k] + m_ineq[k] >= 1,
+                        "slp_cp_many_create: every LP needs at least one variable and one row");
+            CpmLp &lp = s->lps[(size_t)k];
+            lp.col0 = N; lp.eq0 = Me; lp.in0 = Mi;  // in0: completed below, once the equality rows are counted
+            lp.y0 = Me + Mi;
+            N += n[k]; Me += m_eq[k]; Mi += m_ineq[k];
+            SLP_REQUIRE(N < ((i64)1 << 31) && Me + Mi < ((i64)1 << 31), "slp_cp_many_create: the set has 2^31 or more variables or rows");
+            lp.n = (i32)n[k]; lp.m_eq = (i32)m_eq[k]; lp.m_in = (i32)m_ineq[k];
+        }
+        for (CpmLp &lp : s->lps) lp.in0 += Me;
+        const i64 M = Me + Mi;
+        s->n = N; s->m = M; s->m_eq = Me;
+        SLP_REQUIRE(indptr[0] == 0, "slp_cp_many_create: indptr must start at 0");
+        for (i64 r = 0; r < M; ++r) SLP_REQUIRE(indptr[r + 1] >= indptr[r], "slp_cp_many_create: indptr must be non-decreasing");
+        const i64 nnz = indptr[M];
+        SLP_REQUIRE(nnz == 0 || (indices && data), "slp_cp_many_create: NULL argument");
+        for (i64 k = 0; k < count; ++k) {
+            const CpmLp &lp = s->lps[(size_t)k];
+            const i64 lo = lp.col0, hi = lp.col0 + lp.n;
+            const i64 q0[2] = {indptr[lp.eq0], indptr[lp.in0]}, q1[2] = {indptr[lp.eq0 + lp.m_eq], indptr[lp.in0 + lp.m_in]};
+            for (int part = 0; part < 2; ++part)
+                for (i64 q = q0[part]; q < q1[part]; ++q)
+                    if (indices[q] < lo || indices[q] >= hi)
+                        throw Error("slp_cp_many_create: a row of LP " + std::to_string(k) + " has the column index " + std::to_string(indices[q]) +
+                                    " outside the LP's columns [" + std::to_string(lo) + ", " + std::to_string(hi) + ")");
+        }
+        cpm_plan(s.get());
+        {
+            // the CSR pair and the scratch of the device transposition, seven vectors over the columns (x, z, x4, c, lb, ub, T),
+            // three over the rows (y, b, Sigma), the table, the lists and the report
+            i64 free_b = 0, total_b = 0;
+            SLP_REQUIRE(slp_device_memory(&free_b, &total_b) == 0, slp_last_error());
+            const double need = 40.0 * (double)nnz + 16.0 * (double)(N + M + 2) + 8.0 * (7.0 * (double)N + 3.0 * (double)M) +
+                                (double)count * (double)(sizeof(CpmLp) + sizeof(i32) + 5 * sizeof(double));
+            const double have = (double)free_b + (double)slp_cached_bytes();
+            if (need > have)
+                throw Error("slp_cp_many_create: " + std::to_string(count) + " LPs need " + std::to_string(need / 1e9) +
+                            " GB of device memory, " + std::to_string(have / 1e9) + " GB are free");
+        }
+        s->k = slp_matrix_create(M, N, indptr, indices, data);
+        if (!s->k) throw Error(slp_last_error());
+        require_csr(s->k, "slp_cp_many_create");
+        build_transpose(s->k);
+        s->t.alloc((size_t)N);
+        s->sigma.alloc((size_t)M);
+        cp_preconditioners_csr(s->k, Me, alpha, s->t.p, s->sigma.p);
+        s->table.upload(s->lps.data(), (size_t)count);
+        hipLaunchKernelGGL(k_cpm_localise, dim3((unsigned)count), dim3(kBlock), 0, ctx().stream, s->table.p, s->k->a.ptr.p, s->k->a.idx.p,
+                           s->k->at.ptr.p, s->k->at.idx.p, Me);
+        SLP_HIP(hipGetLastError());
+        for (int g = 0; g < 2; ++g)
+            if (!s->group[g].ids.empty()) s->group[g].list.upload(s->group[g].ids.data(), s->group[g].ids.size());
+        if (s->group[0].lds_bytes > 48 * 1024)
+            SLP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cpm_iterate<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)(kCpmLdsLimit * sizeof(double))));
+        s->c.upload(c, (size_t)N);
+        s->lb.upload(lb, (size_t)N);
+        s->ub.upload(ub, (size_t)N);
+        s->b.upload(b, (size_t)M);
+        s->x.alloc((size_t)N);
+        if (x0) s->x.upload(x0, (size_t)N);
+        else s->x.zero();
+        s->z.copy_from(s->x);  // x3 = x (:190)
+        s->y.alloc((size_t)M);
+        s->y.zero();           // :166,177
+        s->x4.alloc((size_t)N);
+        s->x4.zero();
+        s->out.alloc((size_t)5 * (size_t)count);
+        SLP_HIP(hipStreamSynchronize(ctx().stream));
+        return s.release();
+    })
+}
+
+void slp_cp_many_destroy(slp_cp_many *s) { delete s; }
+
+int slp_cp_many_iterate(slp_cp_many *s, int64_t k) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && k >= 0, "slp_cp_many_iterate: bad arguments");
+        cpm_run(s, k, 3, false);
+    })
+}
+
+int slp_cp_many_primal_step(slp_cp_many *s) { SLP_API_INT({ SLP_REQUIRE(s, "NULL handle"); cpm_run(s, 1, 1, true); }) }
+
+int slp_cp_many_dual_step(slp_cp_many *s) { SLP_API_INT({ SLP_REQUIRE(s, "NULL handle"); cpm_run(s, 1, 2, false); }) }
+
+int slp_cp_many_report(slp_cp_many *s, double *out) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && out, "slp_cp_many_report: NULL argument");
+        hipLaunchKernelGGL(k_cpm_report, dim3((unsigned)s->count), dim3(kBlock), 0, ctx().stream, cpm_args(s, 0), s->out.p);
+        SLP_HIP(hipGetLastError());
+        s->out.download(out, (size_t)5 * (size_t)s->count);
+    })
+}
+
+int slp_cp_many_get_x(slp_cp_many *s, double *x) { SLP_API_INT({ SLP_REQUIRE(s && x, "NULL argument"); s->x.download(x, (size_t)s->n); }) }
+
+int slp_cp_many_get_y(slp_cp_many *s, double *y) { SLP_API_INT({ SLP_REQUIRE(s && y, "NULL argument"); s->y.download(y, (size_t)s->m); }) }
+
+int slp_cp_many_get_preconditioners(slp_cp_many *s, double *t, double *sigma) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "NULL handle");
+        if (t) s->t.download(t, (size_t)s->n);
+        if (sigma) {  // Sigma lies in the row order of K: LP by LP for the caller, as y
+            std::vector<double> h((size_t)s->m);
+            s->sigma.download(h.data(), (size_t)s->m);
+            for (const CpmLp &lp : s->lps) {
+                for (i32 r = 0; r < lp.m_eq; ++r) sigma[lp.y0 + r] = h[(size_t)(lp.eq0 + r)];
+                for (i32 r = 0; r < lp.m_in; ++r) sigma[lp.y0 + lp.m_eq + r] = h[(size_t)(lp.in0 + r)];
+            }
+        }
+    })
+}
+
+int slp_cp_many_form(const slp_cp_many *s, int64_t k) { return (s && k >= 0 && k < s->count) ? s->lps[(size_t)k].form : -1; }
+
+int slp_cp_many_bench(slp_cp_many *s, int64_t k, double ms[3]) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && k > 0 && ms, "slp_cp_many_bench: bad arguments");
+        Context &c = ctx();
+        const int stages[3] = {3, 1, 2};
+        for (int q = 0; q < 3; ++q) {
+            float f = 0.f;
+            SLP_HIP(hipEventRecord(c.ev0, c.stream));
+            cpm_run(s, k, stages[q], false);
+            SLP_HIP(hipEventRecord(c.ev1, c.stream));
+            SLP_HIP(hipEventSynchronize(c.ev1));
+            SLP_HIP(hipEventElapsedTime(&f, c.ev0, c.ev1));
+            ms[q] = (double)f / (double)k;
+        }
+    })
+}
+
+}  // extern "C"
