@@ -654,6 +654,49 @@ int slp_batch_dga_report(slp_batch_dga *s, double *out);
 int slp_batch_dga_timing(slp_batch_dga *s, int on);
 int slp_batch_dga_timing_read(slp_batch_dga *s, double out[5]);
 
+/* ---- dual gradient ascent on a LIST of LPs with matrices of their own (slp_dga_many.hip) --------------------------------------
+ * Replaces: `count` calls of dual_gradient_ascent (reference DualGradientAscent.py:68-245), one LP each -- here `count` handles
+ * of slp_dga_create_on iterated one after another, each about 30 launches per iteration.  One workgroup of 1024 lanes per LP
+ * runs whole iterations inside one launch; LP k is bit for bit what slp_dga_* computes on LP k alone (x, y, tie draws taken,
+ * status bits, report).  Every LP has at most 8192 variables (the fused search); an LP with more belongs to slp_dga_create_on.
+ * LP k: n[k] variables, m_eq[k] equality rows followed by m_ineq[k] inequality rows.  indptr / indices / data: the CSR rows of all
+ * K_k = [A_eq,k; A_ineq,k] one LP after another, indptr running over the whole list, indices LOCAL to the LP (0 .. n[k]).  b and
+ * y0 follow the rows; c, lb, ub the columns, LP by LP.  draw_offset[k]: the position in the one stream of uniform draws at which
+ * LP k's tie draws begin (the draws its default start took; 0 for a given start).
+ * Refused before anything is allocated or launched: count < 1, an LP with more than 8192 variables, without variables or without
+ * rows, 2^31 or more variables, rows or entries in all, a column index outside its LP, a list that does not fit the free device
+ * memory, SLP_DGA_MANY_KMAX that is no positive number.  An LP whose start has dual energy -inf is frozen, as in the batch. */
+typedef struct slp_many_dga slp_many_dga;
+slp_many_dga *slp_many_dga_create(int64_t count, const int64_t *n, const int64_t *m_eq, const int64_t *m_ineq, const int64_t *indptr,
+                                  const int32_t *indices, const double *data, const double *b, const double *c, const double *lb,
+                                  const double *ub, const double *y0, const int64_t *draw_offset);
+void slp_many_dga_destroy(slp_many_dga *s);
+/* Replaces: k iterations of the reference's loop (:141-240) on every LP of the list.  Split into launches of at most
+ * slp_many_dga_kmax iterations; stops early for all LPs (status bit 4) once two draws per iteration to come are not certain to be
+ * left behind the furthest position.  The iterates do not depend on the split. */
+int slp_many_dga_iterate(slp_many_dga *s, int64_t k);
+/* Replaces: numpy.random.rand() of the tie rule (:55-63).  Appends `count` draws to the one stream (it starts at position 0: the
+ * draws of the default starts included); the draws no moving LP can still read are dropped from its front. */
+int slp_many_dga_push_random(slp_many_dga *s, const double *draws, int64_t count);
+/* Replaces: the reference's assert and IndexError of the line search, per LP.  out[2 k] = status bits of LP k (as
+ * slp_dga_status), out[2 k + 1] = its tie draws taken; out[2 count] = draws left behind the furthest position,
+ * out[2 count + 1] = iterations done. */
+int slp_many_dga_status(slp_many_dga *s, int64_t *out);
+/* Replaces: the early return of a dual-infeasible start (:133-139), per LP.  count values: 1 = frozen */
+int slp_many_dga_frozen(slp_many_dga *s, int32_t *out);
+/* Replaces: the returned x (:245), all LPs concatenated */
+int slp_many_dga_get_x(slp_many_dga *s, double *x);
+/* Replaces: the returned y_eq, y_ineq (:245), [y_eq,k; y_ineq,k] LP by LP */
+int slp_many_dga_get_y(slp_many_dga *s, double *y);
+/* Replaces: eval(y_eq, y_ineq) (:117-131) per LP.  count x 3 as slp_dga_report: the dual energy (a certified lower bound of LP
+ * k's value), largest violation, their sum. */
+int slp_many_dga_report(slp_many_dga *s, double *out);
+/* Replaces: nothing in the reference (timing of the launches).  An iteration is one launch here: all its time is out[4]. */
+int slp_many_dga_timing(slp_many_dga *s, int on);
+int slp_many_dga_timing_read(slp_many_dga *s, double out[5]);
+/* Replaces: nothing in the reference.  Iterations one launch holds at most: from the shapes, lowered by SLP_DGA_MANY_KMAX. */
+int64_t slp_many_dga_kmax(const slp_many_dga *s);
+
 /* ---- synthetic random LP on the device (randomLP.py:14-75) -------------- *
  * Row r of A_ineq (global row index row_offset + r): every entry is non-zero
  * with probability `density`, value round(N(0,1)*100)/100, exact zeros

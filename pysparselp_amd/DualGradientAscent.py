@@ -6,6 +6,8 @@ maximiser on that line -- a sort of the breakpoints ``-c_bar_j / d_j``, two runn
 (csrc/slp_dga.hip).  The multipliers it returns are dual feasible, so their dual energy (``DeviceDGA.report``) is a certified
 lower bound on the LP's value.  ``DeviceDGABatch`` / ``dual_gradient_ascent_batch`` advance B LPs that share the constraint
 matrix and the right-hand sides together (csrc/slp_dga_batch.hip); instance k is bit for bit the single solve of its data.
+``DeviceDGAMany`` / ``dual_gradient_ascent_many`` advance a list of LPs with matrices of their own, one workgroup per LP and whole
+iterations inside a launch (csrc/slp_dga_many.hip); LP k is bit for bit the single solve of ``lps[k]``.
 """
 import os
 import time
@@ -432,3 +434,285 @@ def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time
         if state is not None:
             state.close()
         mat.close()
+
+
+# ---- a list of LPs with matrices of their own: one workgroup per LP ------------------------------------------------------------
+
+def _dga_many_lp(k, lp):
+    """LP ``k`` of a list, validated (``ValueError``) and brought to the solver's form without touching the library:
+    ``(c, lb, ub, eq, b_eq, ineq, b_upper)`` with ``eq`` / ``ineq`` ``CsrArrays`` or None (a block without rows is None)."""
+    from .tools import CsrArrays
+
+    try:
+        b_lower = getattr(lp, "b_lower", None)
+        c = _lib.f64(lp.costsvector)
+        a_eq, a_ineq = CsrArrays.from_any(lp.a_equalities), CsrArrays.from_any(lp.a_inequalities)
+        lb, ub = _lib.f64(lp.lower_bounds), _lib.f64(lp.upper_bounds)
+    except AttributeError as e:
+        raise ValueError(f"LP {k} is not an LP object (costsvector, a_equalities, b_equalities, a_inequalities, b_upper, b_lower, "
+                         f"lower_bounds, upper_bounds): {e}") from None
+    if b_lower is not None and np.size(b_lower) > 0 and np.max(b_lower) != -np.inf:
+        raise ValueError(f"LP {k}: dual_gradient_ascent needs one-sided inequalities: b_lower must be None or all -inf")
+    if c.ndim != 1 or c.size < 1:
+        raise ValueError(f"LP {k}: costsvector has shape {c.shape}, expected (n,) with n >= 1")
+    n = c.size
+    if n > FUSED_MAX:
+        raise ValueError(f"LP {k} has {n} variables: the list form holds at most {FUSED_MAX} per LP (one workgroup, breakpoints in "
+                         "LDS); an LP with more belongs to the single solver, dual_gradient_ascent")
+    for name, v in (("lower_bounds", lb), ("upper_bounds", ub)):
+        if v.shape != (n,):
+            raise ValueError(f"LP {k}: {name} has shape {v.shape}, costsvector has {n} entries")
+    out = []
+    for name, a, rhs_name in (("a_equalities", a_eq, "b_equalities"), ("a_inequalities", a_ineq, "b_upper")):
+        if a is None or a.shape[0] == 0:
+            out += [None, np.zeros(0)]
+            continue
+        if a.shape[1] != n:
+            raise ValueError(f"LP {k}: {name} has {a.shape[1]} columns, costsvector has {n} entries")
+        if a.indptr.shape != (a.shape[0] + 1,) or a.indptr[0] != 0 or np.any(np.diff(a.indptr) < 0) or a.indptr[-1] != a.indices.size \
+                or a.indices.size != a.data.size:
+            raise ValueError(f"LP {k}: {name} is not a well-formed CSR matrix")
+        if a.indices.size and (a.indices.min() < 0 or a.indices.max() >= n):
+            raise ValueError(f"LP {k}: {name} has a column index outside [0, {n})")
+        rhs = _lib.f64(getattr(lp, rhs_name))
+        if rhs.shape != (a.shape[0],):
+            raise ValueError(f"LP {k}: {rhs_name} has shape {rhs.shape}, {name} has {a.shape[0]} rows")
+        out += [a, rhs]
+    if out[0] is None and out[2] is None:
+        raise ValueError(f"LP {k} has no constraint rows")
+    return (c, lb, ub) + tuple(out)
+
+
+def dga_many_start(lps, y_eq=None, y_ineq=None):
+    """``(y0s, draw_offsets)`` of the validated LPs: per LP ``[y_eq; y_ineq]`` -- the caller's, or the reference's seed-0 start for
+    the LP's own shape (``-rand(m_eq)``, then ``|rand(m_ineq)|``) -- and the position in the seed-0 stream at which the LP's tie
+    draws begin: the number of draws its default start took (0 when both parts are given)."""
+    count = len(lps)
+    given = []
+    for name, v in (("y_eq", y_eq), ("y_ineq", y_ineq)):
+        if v is None:
+            v = [None] * count
+        try:
+            v = list(v)
+        except TypeError:
+            v = None
+        if v is None or len(v) != count:
+            raise ValueError(f"{name} must be None or a sequence of {count} entries, one array (or None) per LP")
+        given.append(v)
+    y0s, offsets = [], []
+    for k, lp in enumerate(lps):
+        m_eq = 0 if lp[3] is None else lp[3].shape[0]
+        m_in = 0 if lp[5] is None else lp[5].shape[0]
+        rs = np.random.RandomState(0)
+        parts, taken = [], 0
+        for name, v, rows, sign in (("y_eq", given[0][k], m_eq, -1.0), ("y_ineq", given[1][k], m_in, 1.0)):
+            if v is None:
+                v = -rs.rand(rows) if sign < 0 else np.abs(rs.rand(rows))
+                taken += rows
+            else:
+                v = _lib.f64(v).copy()
+                if v.shape != (rows,):
+                    raise ValueError(f"LP {k}: {name} has shape {v.shape}, the LP has {rows} such rows")
+            parts.append(v)
+        y0s.append(np.concatenate(parts))
+        offsets.append(taken)
+    return y0s, offsets
+
+
+def dga_many_system(lps, y0s, draw_offsets):
+    """The validated LPs as the arrays ``slp_many_dga_create`` takes -- a dict of:
+
+    ``n``, ``m_eq``, ``m_ineq``, ``draw_offset``: int64 arrays of length ``count``; ``col0``, ``row0``: first column and first row of
+    every LP; ``indptr``, ``indices``, ``data``: the CSR rows of all ``K_k = [A_eq,k; A_ineq,k]``, one LP after another, ``indptr``
+    running over the whole list, ``indices`` local to the LP and every row in its own storage order; ``b``, ``y0`` in that row order;
+    ``c``, ``lb``, ``ub`` concatenated LP by LP.  Needs no GPU."""
+    count = len(lps)
+    if count < 1:
+        raise ValueError("an empty list of LPs")
+    n = np.array([lp[0].size for lp in lps], dtype=np.int64)
+    m_eq = np.array([0 if lp[3] is None else lp[3].shape[0] for lp in lps], dtype=np.int64)
+    m_ineq = np.array([0 if lp[5] is None else lp[5].shape[0] for lp in lps], dtype=np.int64)
+    first = lambda sizes: np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64)  # noqa: E731
+    ptr, idx, val, b = [np.zeros(1, dtype=np.int64)], [], [], []
+    entries = 0
+    for lp in lps:
+        for a, rhs in ((lp[3], lp[4]), (lp[5], lp[6])):
+            if a is None:
+                continue
+            ptr.append(entries + a.indptr[1:])
+            idx.append(a.indices)
+            val.append(a.data)
+            b.append(rhs)
+            entries += a.nnz
+    if int(n.sum()) >= 2 ** 31 or int(m_eq.sum() + m_ineq.sum()) >= 2 ** 31 or entries >= 2 ** 31:
+        raise ValueError("the list has 2^31 or more variables, rows or entries")
+    cat = lambda parts, dtype: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0), dtype=dtype)  # noqa: E731
+    y0 = cat(list(y0s), np.float64)
+    assert y0.size == int(m_eq.sum() + m_ineq.sum()) and len(draw_offsets) == count
+    return dict(n=n, m_eq=m_eq, m_ineq=m_ineq, col0=first(n), row0=first(m_eq + m_ineq), indptr=cat(ptr, np.int64),
+                indices=cat(idx, np.int32), data=cat(val, np.float64), b=cat(b, np.float64), c=cat([lp[0] for lp in lps], np.float64),
+                lb=cat([lp[1] for lp in lps], np.float64), ub=cat([lp[2] for lp in lps], np.float64), y0=y0,
+                draw_offset=np.ascontiguousarray(draw_offsets, dtype=np.int64))
+
+
+def _check_status_many(flags):
+    """The single solver's exception for the first kind of error present, naming the LPs that carry it."""
+    flags = np.asarray(flags, dtype=np.int64)
+    for bit in (STATUS_NAN, STATUS_EMPTY, STATUS_NO_CROSSING, STATUS_NEGATIVE_STEP):
+        bad = np.flatnonzero(flags & bit)
+        if bad.size:
+            try:
+                _check_status(bit)
+            except (ValueError, AssertionError) as e:
+                raise type(e)(f"{e} (LPs {bad.tolist()} of the list)") from None
+
+
+class DeviceDGAMany:
+    """``DeviceDGA`` for a list of LPs with matrices of their own (``slp_many_dga_*``): one workgroup per LP runs whole iterations
+    inside a launch.  ``lps``: the LPs as ``_dga_many_lp`` returns them (each at most ``FUSED_MAX`` variables and at least one
+    row); ``y0s``: per LP ``[y_eq; y_ineq]``; ``draw_offsets``: per LP the position in the stream of draws at which its tie draws
+    begin (``dga_many_start`` gives both).  ``draws(count)`` gives the next ``count`` draws of that one stream FROM ITS START
+    (default: a private ``RandomState(0)``); every LP reads it at its own position.  Results are lists of per-LP arrays.  An LP
+    whose start has dual energy ``-inf`` is frozen (``frozen()``): its x and y stay the start's."""
+
+    def __init__(self, lps, y0s, draw_offsets, draws=None):
+        s = dga_many_system(lps, y0s, draw_offsets)
+        self.count = len(lps)
+        self.n, self.m_eq, self.m = s["n"], s["m_eq"], s["m_eq"] + s["m_ineq"]
+        self.system = s
+        self._draws = draws if draws is not None else np.random.RandomState(0).random_sample
+        # all of the above needs no GPU; the library is loaded (and bound to a device) only now
+        self._l = _lib.lib()
+        self._h = _lib.check_handle(self._l.slp_many_dga_create(
+            self.count, _lib.ptr(s["n"]), _lib.ptr(s["m_eq"]), _lib.ptr(s["m_ineq"]), _lib.ptr(s["indptr"]), _lib.ptr(s["indices"]),
+            _lib.ptr(s["data"]), _lib.ptr(s["b"]), _lib.ptr(s["c"]), _lib.ptr(s["lb"]), _lib.ptr(s["ub"]), _lib.ptr(s["y0"]),
+            _lib.ptr(s["draw_offset"])))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._l.slp_many_dga_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def kmax(self):
+        """Iterations one launch holds at most (from the shapes; ``SLP_DGA_MANY_KMAX`` lowers it)."""
+        return int(self._l.slp_many_dga_kmax(self._h))
+
+    def status(self):
+        """``(flags[count], tie draws taken[count], draws left in the buffer behind the furthest position, iterations done)``;
+        reading it synchronises."""
+        out = np.zeros(2 * self.count + 2, dtype=np.int64)
+        _lib.check(self._l.slp_many_dga_status(self._h, _lib.ptr(out)))
+        per = out[:2 * self.count].reshape(self.count, 2)
+        return per[:, 0].copy(), per[:, 1].copy(), int(out[-2]), int(out[-1])
+
+    def frozen(self):
+        out = np.zeros(self.count, dtype=np.int32)
+        _lib.check(self._l.slp_many_dga_frozen(self._h, _lib.ptr(out)))
+        return out.astype(bool)
+
+    def push_random(self, values):
+        values = _lib.f64(values)
+        _lib.check(self._l.slp_many_dga_push_random(self._h, _lib.ptr(values), values.size))
+
+    def iterate(self, k, refill=True):
+        """``k`` iterations of every LP, nothing read back in between.  ``refill``: the shared draw buffer is topped up to two
+        draws per iteration behind the furthest position first; without it the call stops early, for all LPs, when the buffer
+        could run dry (``status()[3]`` tells how far it got)."""
+        k = int(k)
+        if refill:
+            left = self.status()[2]
+            if left < 2 * k:
+                self.push_random(self._draws(2 * k - left))
+        _lib.check(self._l.slp_many_dga_iterate(self._h, k))
+
+    def check(self):
+        flags = self.status()[0]
+        _check_status_many(flags & ~STATUS_DRAWS_DRY)
+        return flags
+
+    def _split(self, flat, sizes):
+        return [v.copy() for v in np.split(flat, np.cumsum(sizes)[:-1])]
+
+    def x(self):
+        out = np.empty(int(self.n.sum()))
+        _lib.check(self._l.slp_many_dga_get_x(self._h, _lib.ptr(out)))
+        return self._split(out, self.n)
+
+    def y(self):
+        """``(y_eqs, y_ineqs)``: two lists of per-LP arrays."""
+        out = np.empty(int(self.m.sum()))
+        _lib.check(self._l.slp_many_dga_get_y(self._h, _lib.ptr(out)))
+        both = self._split(out, self.m)
+        return [v[:me].copy() for v, me in zip(both, self.m_eq)], [v[me:].copy() for v, me in zip(both, self.m_eq)]
+
+    def report(self):
+        """Array of shape ``(count, 3)``: per LP ``(dual energy, largest violation, sum of violations)`` of its multipliers as they
+        are, x their dual argmin.  Column 0 is a certified lower bound on the LP's value."""
+        out = np.zeros((self.count, 3))
+        _lib.check(self._l.slp_many_dga_report(self._h, _lib.ptr(out)))
+        return out
+
+    def timing(self, on):
+        _lib.check(self._l.slp_many_dga_timing(self._h, int(bool(on))))
+
+    def timing_read(self):
+        """Milliseconds since ``timing(True)`` in the layout of ``DeviceDGA.timing_read``; an iteration is one launch here, so all
+        of it stands under ``fused_search``."""
+        out = np.zeros(5)
+        _lib.check(self._l.slp_many_dga_timing_read(self._h, _lib.ptr(out)))
+        return dict(zip(("products", "sort", "scans", "rest", "fused_search"), (float(v) for v in out)))
+
+
+def dual_gradient_ascent_many(lps, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None):
+    """``dual_gradient_ascent`` on every LP of ``lps`` -- LPs whose constraint matrices differ -- all advancing together on the
+    device, one workgroup per LP (an extension: the reference solves one LP per call); returns ``(xs, y_eqs, y_ineqs)``, lists of
+    per-LP arrays (``y_ineqs[k]`` is None where ``lps[k].a_inequalities`` is None).
+
+    ``lps``: a sequence of objects with the reference's attributes, as ``dual_gradient_ascent`` takes; every LP has at most
+    ``FUSED_MAX`` = 8192 variables (an LP with more belongs to ``dual_gradient_ascent``).  ``y_eq`` / ``y_ineq``: None, or one
+    entry (or None) per LP.  The default start of LP k is the reference's seed-0 start for its own shape and its tie draws
+    continue that stream, so LP k is bit for bit ``dual_gradient_ascent`` on ``lps[k]``.  An LP whose start is dual infeasible
+    (energy ``-inf``) stands still at its start, which is what its single solve returns; the others go on.
+    ``callback_func(niter, xs, 0, 0, elapsed, 0, 0)`` is called for ``niter % 100 == 0``; ``max_time`` is tested there and stops
+    the whole list.  A finite ``b_lower``, a shape error, an LP without rows or with more than 8192 variables, or an empty list
+    raises ``ValueError`` naming the LP, before the library is loaded; a status error raises the single solver's exception,
+    naming the LPs."""
+    return _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time)[:3]
+
+
+def _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, frozen_out=None):
+    """``dual_gradient_ascent_many`` plus, as a fourth value, the final ``DeviceDGAMany.report()``; ``frozen_out``: a list that
+    receives the frozen flags before the first iteration."""
+    start = time.perf_counter()
+    try:
+        lps = list(lps)
+    except TypeError:
+        raise ValueError("lps must be a sequence of LP objects") from None
+    if len(lps) < 1:
+        raise ValueError("an empty list of LPs")
+    forms = [_dga_many_lp(k, lp) for k, lp in enumerate(lps)]
+    y0s, offsets = dga_many_start(forms, y_eq, y_ineq)
+    has_ineq = [getattr(lp, "a_inequalities", None) is not None for lp in lps]
+    state = DeviceDGAMany(forms, y0s, offsets, draws=np.random.RandomState(0).random_sample)
+    try:
+        frozen = state.frozen()
+        if frozen_out is not None:
+            frozen_out[:] = frozen.tolist()
+        i = 0
+        while i < nb_max_iter and not frozen.all():
+            k = 1 if i % 100 == 0 else min(100 - i % 100, nb_max_iter - i)
+            state.iterate(k)
+            i += k
+            state.check()
+            if (i - 1) % 100 == 0:
+                elapsed = time.perf_counter() - start
+                if callback_func is not None:
+                    callback_func(i - 1, state.x(), 0, 0, elapsed, 0, 0)
+                if max_time is not None and elapsed > max_time:
+                    break
+        yes, yis = state.y()
+        return state.x(), yes, [yi if h else None for yi, h in zip(yis, has_ineq)], state.report()
+    finally:
+        state.close()

@@ -753,3 +753,46 @@ def solve_many(lps, method="chambolle_pock_ppd", get_timing=True, nb_iter=10000,
     xs = [expand(k, sol) for k, sol in enumerate(sols)]
     elapsed = time.perf_counter() - start
     return (xs, elapsed) if get_timing else xs
+
+
+def solve_dga_many(lps, get_timing=True, nb_iter=10000, max_time=None):
+    """Run ``method="dual_gradient_ascent"`` on a list of ``SparseLP`` objects whose matrices differ in ONE call, every LP one
+    workgroup on the GPU (``DualGradientAscent.dual_gradient_ascent_many``; extension: the reference solves one LP per call);
+    returns the list of ``x``, or ``(xs, elapsed)`` with ``get_timing``.  Every LP has at most 8192 variables.
+
+    ``xs[k]`` and every curve of ``lps[k]`` apart from the times are bit for bit what ``lps[k].solve(method=
+    "dual_gradient_ascent")`` gives: a report every 100 iterations, none for an LP whose start is dual infeasible.  Also sets
+    ``lp.dual_multipliers = (y_eq, y_ineq)`` and ``lp.dual_lower_bound`` on each LP: the dual energy of the returned multipliers,
+    a certified lower bound on that LP's value.  ``solve_many(method="dual_gradient_ascent")`` keeps refusing: it is the
+    Chambolle-Pock list form only.  ``max_time`` stops all LPs at a report.  Under a communicator every rank solves the whole
+    list (a replica)."""
+    from .DualGradientAscent import _dga_many_run
+
+    lps = list(lps)
+    if len(lps) < 1:
+        raise ValueError("an empty list of LPs")
+    start = time.perf_counter()
+    for lp in lps:
+        for name in _CURVES:
+            setattr(lp, name, [])
+    frozen = []
+
+    def record(niter, solutions, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
+        for k, lp in enumerate(lps):
+            if frozen[k]:   # its single solve returns before the first report
+                continue
+            lp.itrn_curve.append(niter)
+            lp.opttime_curve.append(duration)
+            lp.dopttime_curve.append(duration)
+            lp.dobj_curve.append(energy2)
+            lp.pobj_curve.append(energy1)
+            lp.max_violated_constraint.append(lp.max_constraint_violation(solutions[k]))
+            lp.max_violated_equality.append(max_violated_equality)
+            lp.max_violated_inequality.append(max_violated_inequality)
+
+    xs, y_eqs, y_ineqs, report = _dga_many_run(lps, nb_iter, record, None, None, max_time, frozen_out=frozen)
+    for k, lp in enumerate(lps):
+        lp.dual_multipliers = (y_eqs[k], y_ineqs[k])
+        lp.dual_lower_bound = float(report[k, 0])
+    elapsed = time.perf_counter() - start
+    return (xs, elapsed) if get_timing else xs

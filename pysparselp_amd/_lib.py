@@ -187,6 +187,18 @@ _SIGNATURES = {
     "slp_batch_dga_report": (c_int, [c_vp, c_vp]),
     "slp_batch_dga_timing": (c_int, [c_vp, c_int]),
     "slp_batch_dga_timing_read": (c_int, [c_vp, c_vp]),
+    "slp_many_dga_create": (c_vp, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "slp_many_dga_destroy": (None, [c_vp]),
+    "slp_many_dga_iterate": (c_int, [c_vp, c_i64]),
+    "slp_many_dga_push_random": (c_int, [c_vp, c_vp, c_i64]),
+    "slp_many_dga_status": (c_int, [c_vp, c_vp]),
+    "slp_many_dga_frozen": (c_int, [c_vp, c_vp]),
+    "slp_many_dga_get_x": (c_int, [c_vp, c_vp]),
+    "slp_many_dga_get_y": (c_int, [c_vp, c_vp]),
+    "slp_many_dga_report": (c_int, [c_vp, c_vp]),
+    "slp_many_dga_timing": (c_int, [c_vp, c_int]),
+    "slp_many_dga_timing_read": (c_int, [c_vp, c_vp]),
+    "slp_many_dga_kmax": (c_i64, [c_vp]),
     "slp_admm_cg_create_on_two_sided": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),
     "slp_admm_cg_create_on_lp": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int, c_int]),
     "slp_admm_cg_create_lp": (c_vp, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

@@ -60,14 +60,15 @@ __global__ void k_dga_grad(i64 m, i64 r0, i64 r1, int ineq, const double *__rest
                            const double *__restrict__ y, double *__restrict__ g, double *__restrict__ part_gb,
                            double *__restrict__ part_min, int *__restrict__ part_any) {
     __shared__ double red[kBlock / kWave];
-    dga_grad_body(m, r0, r1, ineq, ax, b, y, g, part_gb, part_min, part_any, red);
+    dga_grad_body(m, r0, r1, ineq, ax, b, y, g, part_gb, part_min, part_any, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x,
+                  dga_part_tiles(m, (int)blockIdx.x, (int)gridDim.x), red);
 }
 
 // one workgroup: the block's scalars from the partial results
 __global__ void k_dga_begin(int parts, const double *__restrict__ part_gb, const double *__restrict__ part_min,
                             const int *__restrict__ part_any, DgaCtl *__restrict__ ctl) {
     __shared__ double red[kBlock / kWave];
-    dga_begin_body(parts, part_gb, part_min, part_any, ctl, red);
+    dga_begin_body(parts, part_gb, part_min, part_any, ctl, (int)threadIdx.x, red);
 }
 
 __global__ void k_dga_update(i64 r0, i64 r1, int ineq, const DgaCtl *__restrict__ ctl, const double *__restrict__ g,

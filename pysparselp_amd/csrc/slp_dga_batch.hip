@@ -91,7 +91,8 @@ __global__ void k_dgab_grad(i64 m, i64 r0, i64 r1, int ineq, const double *__res
     const i64 inst = blockIdx.y;
     if (ctl[inst].frozen) return;
     dga_grad_body(m, r0, r1, ineq, ax + inst * m, b, y + inst * m, g + inst * m, part_gb + inst * kDgaParts, part_min + inst * kDgaParts,
-                  part_any + inst * kDgaParts, red);
+                  part_any + inst * kDgaParts, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x,
+                  dga_part_tiles(m, (int)blockIdx.x, (int)gridDim.x), red);
 }
 
 // one workgroup per instance: the block's scalars; a frozen instance's predicate is off
@@ -103,7 +104,7 @@ __global__ void k_dgab_begin(const double *__restrict__ part_gb, const double *_
         if (threadIdx.x == 0) { ctl[inst].active = 0; ctl[inst].t = 0.0; }
         return;
     }
-    dga_begin_body(kDgaParts, part_gb + inst * kDgaParts, part_min + inst * kDgaParts, part_any + inst * kDgaParts, ctl + inst, red);
+    dga_begin_body(kDgaParts, part_gb + inst * kDgaParts, part_min + inst * kDgaParts, part_any + inst * kDgaParts, ctl + inst, (int)threadIdx.x, red);
 }
 
 __global__ void k_dgab_update(i64 m, i64 r0, i64 r1, int ineq, const DgaCtl *__restrict__ ctl, const double *__restrict__ g,

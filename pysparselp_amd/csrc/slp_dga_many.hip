@@ -1,0 +1,518 @@
+// slp_dga_many.hip -- dual gradient ascent on a LIST of LPs whose constraint matrices differ: one workgroup of 1024 lanes per LP,
+// whole iterations inside one launch.  No counterpart in the reference (N solves are N calls of dual_gradient_ascent,
+// DualGradientAscent.py:68-245; here each of them is about 30 launches per iteration and bound by launch latency when the LP is
+// small).  Every chain of additions is the single solver's (slp_dga_shared.h, included by slp_dga.hip and slp_dga_batch.hip too),
+// so LP k is bit for bit what slp_dga computes on LP k alone: x, y, the tie draws taken, the sticky flags and the report.
+//
+// One iteration of an LP is what dgab_iteration does for one instance, with barriers in place of launch boundaries:
+//   column pass : a lane per column: the two masked sums of K^T y in storage order, c_bar, x = the dual argmin      (k_dgab_cols)
+//   row pass    : a lane per row: K x, one sequential chain                                                         (row_dot<1>)
+//   per kind of rows (inequalities, then equalities; each only if the LP has that kind):
+//     gradient pass -- the kDgaParts partial results, computed by the four virtual blocks (4 waves each) of the workgroup, four
+//                      parts per round; the parts past the last tile are (0.0, +inf, 0) and are stored as such
+//     the block's scalars -- the kDgaParts partial results reduced as one more 256-lane tile
+//     d = K^T g, a lane per column; the fused search (dga_fused_body, breakpoints in LDS); the update of y
+// Iterates stay in global memory and are re-read across the barriers with workgroup-scope relaxed loads (DgaLoadWorkgroup);
+// nothing but the shapes is kept in a register across a barrier.  No atomics between workgroups, no spin waits, no grid barrier:
+// a workgroup never waits for another.  Every loop is bounded by the shapes or by `iters`; every barrier is in control flow that
+// is uniform over the workgroup (`active` and `frozen` are read by all lanes after a barrier; a frozen LP's workgroup returns
+// before its first barrier).
+//
+// Layout.  All vectors are concatenated LP by LP: c, lb, ub, x, c_bar, d over the columns, b, y, K x, g over the rows with
+// [eq; ineq] contiguous per LP.  K_k is CSR over the LP's rows, K_k^T CSR over its columns with rows increasing inside a column
+// (the order build_transpose gives the single solver); the index arrays are local to the LP, the pointer arrays hold positions in
+// the entry arrays of the whole list.  DgmLp, one per LP, holds its column base, row base, shape, padding and draw offset.
+//
+// Dynamic LDS: 16 reduction slots, then the search's fused_lds_bytes(npad) for the largest npad of the list.
+//
+// Launch cap.  A launch holds at most kDgmUnitsPerLaunch workgroup passes per compute unit (a pass: the workgroup once over its
+// columns, its rows, a round of the gradient pass or a stage of the sort): iterations per launch = kDgmUnitsPerLaunch / (passes per
+// iteration of the largest LP * ceil(LPs / compute units)), between 1 and 1024, and no more than the draws on the device allow
+// (two per iteration behind the furthest LP).  Longer runs are split; SLP_DGA_MANY_KMAX=<k> lowers the cap.  The iterates do not
+// depend on the split.
+//
+// Tie draws: all LPs read the one stream of uniform draws, LP k at its own position draw_offset_k + consumed_k (draw_offset_k: the
+// draws its default start took).  The device holds a window of the stream from the smallest position on.
+// Report, frozen test and start are ordinary launches over (kDgaParts, count) with the shared energy bodies.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <memory>
+
+#include "slp_common.h"
+#include "slp_kernels.h"
+#include "slp_dga_shared.h"
+
+using namespace slp;
+
+namespace {
+
+constexpr i64 kDgmUnitsPerLaunch = 8192;
+constexpr i64 kDgmMaxItersPerLaunch = 1024;
+constexpr size_t kDgmSlotBytes = 16 * sizeof(double);   // 4 reduction slots for each of the 4 virtual blocks
+
+struct DgmLp {
+    i64 col0, row0;                   // first column (c, lb, ub, x, c_bar, d; rows of K^T), first row (b, y, K x, g; rows of K)
+    unsigned long long draw_offset;   // position in the stream of draws of the LP's first tie draw
+    i32 n, m_eq, m_in, npad;
+};
+
+struct DgmArgs {
+    const DgmLp *lps;
+    const i64 *ptr, *tptr;    // positions in the entry arrays of the list
+    const i32 *idx, *tidx;    // local to the LP
+    const double *val, *tval, *b, *c, *lb, *ub;
+    double *y, *x, *cbar, *ax, *g, *d, *part_gb, *part_min;
+    int *part_any;
+    DgaCtl *ctl;
+    const double *rnd;
+    unsigned long long rnd_base, rnd_count;
+};
+
+// column j of the LP: the two masked sums of K^T y in storage order (k_dgab_cols), c_bar and the dual argmin
+template <class LD>
+__device__ __forceinline__ void dgm_column(const DgmLp &lp, i32 j, const i64 *tptr, const i32 *tidx, const double *tval, const double *y,
+                                           const double *c, const double *lb, const double *ub, double *cbar, double *x, LD ld) {
+    double se = 0.0, si = 0.0;
+    for (i64 q = tptr[j]; q < tptr[j + 1]; ++q) {
+        const i32 r = tidx[q];
+        const double a = tval[q], yv = ld(y + r);
+        se += a * (r < lp.m_eq ? yv : 0.0);
+        si += a * (r < lp.m_eq ? 0.0 : yv);
+    }
+    double cb = c[j];
+    if (lp.m_eq > 0) cb = cb + se;
+    if (lp.m_in > 0) cb = cb + si;
+    cbar[j] = cb;
+    x[j] = dga_argmin_x(cb, lb[j], ub[j]);
+}
+
+// entries s <= q < e of a row times v: storage order, one accumulator (row_dot<1>: loads four entries ahead, adds in order)
+template <class LD>
+__device__ __forceinline__ double dgm_dot(i64 s, i64 e, const i32 *idx, const double *val, const double *v, LD ld) {
+    double acc = 0.0;
+    for (i64 k = s; k < e; k += 4) {
+        i32 j[4];
+        double a[4], xv[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const i64 kk = (k + q < e) ? k + q : e - 1;
+            j[q] = idx[kk];
+            a[q] = val[kk];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) xv[q] = ld(v + j[q]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (k + q < e) acc += a[q] * xv[q];
+    }
+    return acc;
+}
+
+// `iters` iterations of the LP blockIdx.x
+__global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int iters) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dgm_lds[];
+    const DgaLoadWorkgroup ld;
+    const DgmLp lp = a.lps[blockIdx.x];
+    DgaCtl *ctl = a.ctl + blockIdx.x;
+    if (ctl->frozen) return;   // set before the launch: the same for every lane
+    const i32 n = lp.n, m = lp.m_eq + lp.m_in, tid = (i32)threadIdx.x, group = tid >> 8, tl = tid & (kBlock - 1);
+    double *slots = reinterpret_cast<double *>(dgm_lds) + 4 * group;
+    unsigned char *search_lds = dgm_lds + kDgmSlotBytes;
+    const double *c = a.c + lp.col0, *lb = a.lb + lp.col0, *ub = a.ub + lp.col0, *b = a.b + lp.row0;
+    double *x = a.x + lp.col0, *cbar = a.cbar + lp.col0, *d = a.d + lp.col0;
+    double *y = a.y + lp.row0, *ax = a.ax + lp.row0, *g = a.g + lp.row0;
+    const i64 *ptr = a.ptr + lp.row0, *tptr = a.tptr + lp.col0;
+    double *part_gb = a.part_gb + (i64)blockIdx.x * kDgaParts, *part_min = a.part_min + (i64)blockIdx.x * kDgaParts;
+    int *part_any = a.part_any + (i64)blockIdx.x * kDgaParts;
+    // the window of draws as this LP's positions see it: its draw `consumed` is rnd[draw_offset + consumed - rnd_base]
+    const double *rnd = a.rnd;
+    unsigned long long rnd_base = 0, rnd_count = a.rnd_count;
+    if (lp.draw_offset >= a.rnd_base) {
+        const unsigned long long skip = lp.draw_offset - a.rnd_base;
+        rnd += (skip < rnd_count) ? skip : rnd_count;
+        rnd_count = (skip < rnd_count) ? rnd_count - skip : 0;
+    } else {
+        rnd_base = a.rnd_base - lp.draw_offset;
+    }
+    // the gradient pass: parts with tiles, four of them per round
+    const i32 tiles = (m + kBlock - 1) / kBlock, per = (tiles + kDgaParts - 1) / kDgaParts;
+    const i32 rounds = ((tiles + per - 1) / per + 3) / 4;
+    for (int it = 0; it < iters; ++it) {
+        for (i32 j = tid; j < n; j += kDgaFusedThreads) dgm_column(lp, j, tptr, a.tidx, a.tval, y, c, lb, ub, cbar, x, ld);
+        __syncthreads();   // same compute unit: the stores of a stage are visible to the next one
+        for (i32 i = tid; i < m; i += kDgaFusedThreads) ax[i] = dgm_dot(ptr[i], ptr[i + 1], a.idx, a.val, x, ld);
+        __syncthreads();
+        for (int kind = 1; kind >= 0; --kind) {   // inequalities first, then equalities
+            const int ineq = kind;
+            const i32 r0 = ineq ? lp.m_eq : 0, r1 = ineq ? m : lp.m_eq;
+            if (r1 == r0) continue;
+            for (i32 rd = 0; rd < rounds; ++rd)
+                dga_grad_body(m, r0, r1, ineq, ax, b, y, g, part_gb, part_min, part_any, 4 * rd + group, kDgaParts, tl, per, slots, ld);
+            for (i32 p = 4 * rounds + tid; p < kDgaParts; p += kDgaFusedThreads) {
+                part_gb[p] = 0.0;
+                part_min[p] = __builtin_inf();
+                part_any[p] = 0;
+            }
+            __syncthreads();
+            dga_begin_body(kDgaParts, part_gb, part_min, part_any, ctl, tl, slots, group == 0, ld);
+            __syncthreads();
+            if (!ld(&ctl->active)) continue;   // read by all lanes after the barrier
+            for (i32 j = tid; j < n; j += kDgaFusedThreads) d[j] = dgm_dot(tptr[j], tptr[j + 1], a.tidx, a.tval, g, ld);
+            __syncthreads();
+            dga_fused_body(n, lp.npad, d, cbar, lb, ub, ctl, rnd, rnd_base, rnd_count, ineq, search_lds, ld);
+            __syncthreads();
+            const double t = ld(&ctl->t);
+            for (i32 i = r0 + tid; i < r1; i += kDgaFusedThreads) y[i] = dga_update_y(ld(y + i), t, ld(g + i), ineq);
+            __syncthreads();
+        }
+    }
+}
+
+// ---- start, frozen test and report: ordinary launches over (.., count) --------------------------------------------------------
+
+__global__ __launch_bounds__(kBlock) void k_dgm_cols(DgmArgs a, double *__restrict__ cbar, double *__restrict__ x) {
+    const DgmLp lp = a.lps[blockIdx.y];
+    for (i32 j = blockIdx.x * blockDim.x + threadIdx.x; j < lp.n; j += gridDim.x * blockDim.x)
+        dgm_column(lp, j, a.tptr + lp.col0, a.tidx, a.tval, a.y + lp.row0, a.c + lp.col0, a.lb + lp.col0, a.ub + lp.col0, cbar + lp.col0,
+                   x + lp.col0, DgaLoadPlain());
+}
+
+__global__ __launch_bounds__(kBlock) void k_dgm_rows(DgmArgs a, const double *__restrict__ x, double *__restrict__ out) {
+    const DgmLp lp = a.lps[blockIdx.y];
+    const i64 *ptr = a.ptr + lp.row0;
+    for (i32 i = blockIdx.x * blockDim.x + threadIdx.x; i < lp.m_eq + lp.m_in; i += gridDim.x * blockDim.x)
+        out[lp.row0 + i] = dgm_dot(ptr[i], ptr[i + 1], a.idx, a.val, x + lp.col0, DgaLoadPlain());
+}
+
+__global__ void k_dgm_energy_x(DgmArgs a, const double *__restrict__ cbar, double *__restrict__ part) {
+    __shared__ double red[kBlock / kWave];
+    const DgmLp lp = a.lps[blockIdx.y];
+    dga_energy_x_body(lp.n, cbar + lp.col0, a.lb + lp.col0, a.ub + lp.col0, part + (i64)blockIdx.y * 4 * kDgaParts, red);
+}
+
+__global__ void k_dgm_energy_y(DgmArgs a, const double *__restrict__ ax, double *__restrict__ part) {
+    __shared__ double red[kBlock / kWave];
+    const DgmLp lp = a.lps[blockIdx.y];
+    dga_energy_y_body(lp.m_eq + lp.m_in, lp.m_eq, a.y + lp.row0, a.b + lp.row0, ax + lp.row0, part + (i64)blockIdx.y * 4 * kDgaParts + kDgaParts,
+                      red);
+}
+
+}  // namespace
+
+struct slp_many_dga {
+    i64 count = 0, n = 0, m = 0;   // LPs, all columns, all rows
+    i32 max_n = 1, max_m = 1, max_npad = 64;
+    i64 kmax = 1;                  // iterations one launch may hold
+    std::vector<DgmLp> lps;
+    DevBuf<DgmLp> table;
+    DevBuf<i64> ptr, tptr;
+    DevBuf<i32> idx, tidx;
+    DevBuf<double> val, tval, b, c, lb, ub, y, x, cbar, ax, g, d, rcbar, rx, rax, rpart, part_gb, part_min;
+    DevBuf<int> part_any;
+    DevBuf<DgaCtl> ctl;
+    // the shared stream of tie draws
+    DevBuf<double> rnd;
+    std::vector<double> rnd_host;       // the draws from rnd_base on
+    unsigned long long rnd_base = 0;    // position (in the stream of draws) of rnd[0]
+    unsigned long long draws_bound = 0; // no LP stands behind this position (2 per iteration since the last read)
+    unsigned int host_flags = 0;
+    i64 iters = 0;
+    StageTimer timer;
+};
+
+namespace {
+
+DgmArgs dgm_args(const slp_many_dga *s) {
+    DgmArgs r;
+    r.lps = s->table.p;
+    r.ptr = s->ptr.p; r.tptr = s->tptr.p;
+    r.idx = s->idx.p; r.tidx = s->tidx.p;
+    r.val = s->val.p; r.tval = s->tval.p;
+    r.b = s->b.p; r.c = s->c.p; r.lb = s->lb.p; r.ub = s->ub.p;
+    r.y = s->y.p; r.x = s->x.p; r.cbar = s->cbar.p; r.ax = s->ax.p; r.g = s->g.p; r.d = s->d.p;
+    r.part_gb = s->part_gb.p; r.part_min = s->part_min.p; r.part_any = s->part_any.p;
+    r.ctl = s->ctl.p;
+    r.rnd = s->rnd.p;
+    r.rnd_base = s->rnd_base;
+    r.rnd_count = (unsigned long long)s->rnd_host.size();
+    return r;
+}
+
+// workgroup passes of one iteration of an LP: from its shape only
+i64 dgm_passes(const DgmLp &lp) {
+    const i64 w = kDgaFusedThreads, n = lp.n, m = (i64)lp.m_eq + lp.m_in;
+    const i64 cols = (n + w - 1) / w, rows = (m + w - 1) / w;
+    const i64 tiles = (m + kBlock - 1) / kBlock, per = (tiles + kDgaParts - 1) / kDgaParts;
+    const i64 grad = (((tiles + per - 1) / per + 3) / 4) * per;
+    i64 stages = 0;
+    for (i64 size = 2; size <= lp.npad; size <<= 1)
+        for (i64 stride = size >> 1; stride > 0; stride >>= 1) ++stages;
+    const i64 sort = stages * std::max<i64>(1, lp.npad / (2 * w));
+    const i64 scans = 8 * ((n + 4 * kDgaTile - 1) / (4 * kDgaTile));
+    const i64 kinds = (lp.m_eq > 0) + (lp.m_in > 0);
+    return cols + rows + kinds * (grad + 1 + cols + sort + scans + rows);
+}
+
+void dgm_plan(slp_many_dga *s) {
+    i64 cap = kDgmMaxItersPerLaunch;
+    if (const char *e = getenv("SLP_DGA_MANY_KMAX")) {
+        if (e[0]) {
+            char *end = nullptr;
+            const long long v = strtoll(e, &end, 10);
+            if (v < 1 || (end && *end)) throw Error(std::string("SLP_DGA_MANY_KMAX must be a positive number of iterations, not ") + e);
+            cap = std::min<i64>(cap, v);
+        }
+    }
+    i64 passes = 1;
+    for (const DgmLp &lp : s->lps) passes = std::max(passes, dgm_passes(lp));
+    const i64 cus = std::max(1, ctx().num_cu);
+    const i64 waves = (s->count + cus - 1) / cus;
+    s->kmax = std::min(cap, std::max<i64>(1, kDgmUnitsPerLaunch / (passes * waves)));
+}
+
+size_t dgm_lds_bytes(const slp_many_dga *s) { return kDgmSlotBytes + fused_lds_bytes(s->max_npad); }
+
+dim3 dgm_grid(i64 work, i64 count) { return dim3((unsigned)std::max<i64>(1, (work + kBlock - 1) / kBlock), (unsigned)count); }
+
+// c_bar and x of the multipliers into (cbar, x), for every LP
+void dgm_argmin(slp_many_dga *s, double *cbar, double *x) {
+    hipLaunchKernelGGL(k_dgm_cols, dgm_grid(s->max_n, s->count), dim3(kBlock), 0, ctx().stream, dgm_args(s), cbar, x);
+    SLP_HIP(hipGetLastError());
+}
+
+void dgm_report(slp_many_dga *s, double *out) {
+    hipStream_t st = ctx().stream;
+    const size_t sc = (size_t)s->count;
+    if (!s->rcbar.p) { s->rcbar.alloc((size_t)s->n); s->rx.alloc((size_t)s->n); s->rax.alloc((size_t)s->m); s->rpart.alloc((size_t)4 * kDgaParts * sc); }
+    const DgmArgs a = dgm_args(s);
+    dgm_argmin(s, s->rcbar.p, s->rx.p);
+    hipLaunchKernelGGL(k_dgm_rows, dgm_grid(s->max_m, s->count), dim3(kBlock), 0, st, a, s->rx.p, s->rax.p);
+    hipLaunchKernelGGL(k_dgm_energy_x, dim3(kDgaParts, (unsigned)sc), dim3(kBlock), 0, st, a, s->rcbar.p, s->rpart.p);
+    hipLaunchKernelGGL(k_dgm_energy_y, dim3(kDgaParts, (unsigned)sc), dim3(kBlock), 0, st, a, s->rax.p, s->rpart.p);
+    SLP_HIP(hipGetLastError());
+    std::vector<double> h((size_t)4 * kDgaParts * sc);
+    s->rpart.download(h.data(), h.size());
+    for (size_t k = 0; k < sc; ++k) dga_report_finish(h.data() + k * 4 * kDgaParts, true, out + 3 * k);
+}
+
+// the controls of all LPs; refreshes the bound on the positions in the stream of draws
+void dgm_read_ctl(slp_many_dga *s, std::vector<DgaCtl> &h) {
+    h.resize((size_t)s->count);
+    s->ctl.download(h.data(), (size_t)s->count);
+    unsigned long long mx = 0;
+    for (size_t k = 0; k < h.size(); ++k)
+        if (!h[k].frozen) mx = std::max(mx, s->lps[k].draw_offset + h[k].consumed);
+    s->draws_bound = mx;
+}
+
+}  // namespace
+
+extern "C" {
+
+slp_many_dga *slp_many_dga_create(int64_t count, const int64_t *n, const int64_t *m_eq, const int64_t *m_ineq, const int64_t *indptr,
+                                  const int32_t *indices, const double *data, const double *b, const double *c, const double *lb,
+                                  const double *ub, const double *y0, const int64_t *draw_offset) {
+    SLP_API_PTR({
+        SLP_REQUIRE(count >= 1, "slp_many_dga_create: count must be at least 1");
+        SLP_REQUIRE(count <= 65535, "slp_many_dga_create: at most 65535 LPs");
+        SLP_REQUIRE(n && m_eq && m_ineq && indptr && b && c && lb && ub && y0 && draw_offset, "slp_many_dga_create: NULL argument");
+        // everything below up to the memory check reads the host arrays only: nothing is allocated or launched before the list is
+        // known to be well formed and to fit
+        auto s = std::unique_ptr<slp_many_dga>(new slp_many_dga());
+        s->count = count;
+        s->lps.resize((size_t)count);
+        i64 N = 0, M = 0;
+        for (i64 k = 0; k < count; ++k) {
+            if (n[k] > kDgaFusedMax)
+                throw Error("slp_many_dga_create: LP " + std::to_string(k) + " has " + std::to_string(n[k]) + " variables; the list form holds at most " +
+                            std::to_string(kDgaFusedMax) + " per LP (an LP with more belongs to the single solver, slp_dga_create_on)");
+            if (n[k] < 1 || m_eq[k] < 0 || m_ineq[k] < 0 || m_eq[k] + m_ineq[k] < 1)
+                throw Error("slp_many_dga_create: LP " + std::to_string(k) + " needs at least one variable and one constraint row");
+            SLP_REQUIRE(draw_offset[k] >= 0, "slp_many_dga_create: a negative draw offset");
+            DgmLp &lp = s->lps[(size_t)k];
+            lp.col0 = N; lp.row0 = M;
+            N += n[k]; M += m_eq[k] + m_ineq[k];
+            SLP_REQUIRE(N < ((i64)1 << 31) && M < ((i64)1 << 31), "slp_many_dga_create: the list has 2^31 or more variables or rows");
+            SLP_REQUIRE(m_eq[k] + m_ineq[k] < ((i64)1 << 31) - kBlock, "slp_many_dga_create: an LP has too many rows");
+            lp.n = (i32)n[k]; lp.m_eq = (i32)m_eq[k]; lp.m_in = (i32)m_ineq[k];
+            lp.draw_offset = (unsigned long long)draw_offset[k];
+            int npad = 64;
+            while (npad < lp.n) npad <<= 1;
+            lp.npad = npad;
+            s->max_n = std::max(s->max_n, lp.n);
+            s->max_m = std::max(s->max_m, lp.m_eq + lp.m_in);
+            s->max_npad = std::max(s->max_npad, npad);
+        }
+        s->n = N; s->m = M;
+        SLP_REQUIRE(indptr[0] == 0, "slp_many_dga_create: indptr must start at 0");
+        for (i64 r = 0; r < M; ++r) SLP_REQUIRE(indptr[r + 1] >= indptr[r], "slp_many_dga_create: indptr must be non-decreasing");
+        const i64 nnz = indptr[M];
+        SLP_REQUIRE(nnz < ((i64)1 << 31), "slp_many_dga_create: the list has 2^31 or more entries");
+        SLP_REQUIRE(nnz == 0 || (indices && data), "slp_many_dga_create: NULL argument");
+        for (i64 k = 0; k < count; ++k) {
+            const DgmLp &lp = s->lps[(size_t)k];
+            for (i64 q = indptr[lp.row0]; q < indptr[lp.row0 + lp.m_eq + lp.m_in]; ++q)
+                if (indices[q] < 0 || indices[q] >= lp.n)
+                    throw Error("slp_many_dga_create: a row of LP " + std::to_string(k) + " has the column index " + std::to_string(indices[q]) +
+                                ", not local to the LP's " + std::to_string(lp.n) + " columns");
+        }
+        dgm_plan(s.get());
+        {
+            // both orientations (20 B an entry), the pointers, ten vectors over the columns (c, lb, ub, x, c_bar, d and the report's
+            // two), seven over the rows, per LP the table, the controls and the partial results of the pass and of the report
+            i64 free_b = 0, total_b = 0;
+            SLP_REQUIRE(slp_device_memory(&free_b, &total_b) == 0, slp_last_error());
+            const double need = 24.0 * (double)nnz + 8.0 * (double)(N + M + 2) + 8.0 * (8.0 * (double)N + 7.0 * (double)M) +
+                                (double)count * (double)(sizeof(DgmLp) + sizeof(DgaCtl) + 8.0 * 7.0 * kDgaParts);
+            const double have = (double)free_b + (double)slp_cached_bytes();
+            if (need > have)
+                throw Error("slp_many_dga_create: " + std::to_string(count) + " LPs need " + std::to_string(need / 1e9) +
+                            " GB of device memory, " + std::to_string(have / 1e9) + " GB are free");
+        }
+        // K_k^T on the host: a counting transposition per LP walks its rows in order, so rows increase inside a column
+        std::vector<i64> tptr((size_t)N + 1, 0);
+        std::vector<i32> tidx((size_t)nnz);
+        std::vector<double> tval((size_t)nnz);
+        {
+            std::vector<i64> fill;
+            for (const DgmLp &lp : s->lps) {
+                const i64 m = (i64)lp.m_eq + lp.m_in, q0 = indptr[lp.row0], q1 = indptr[lp.row0 + m];
+                fill.assign((size_t)lp.n + 1, 0);
+                for (i64 q = q0; q < q1; ++q) ++fill[(size_t)indices[q] + 1];
+                fill[0] = q0;
+                for (i32 j = 0; j < lp.n; ++j) fill[(size_t)j + 1] += fill[(size_t)j];
+                for (i32 j = 0; j <= lp.n; ++j) tptr[(size_t)(lp.col0 + j)] = fill[(size_t)j];
+                for (i64 r = 0; r < m; ++r)
+                    for (i64 q = indptr[lp.row0 + r]; q < indptr[lp.row0 + r + 1]; ++q) {
+                        const i64 at = fill[(size_t)indices[q]]++;
+                        tidx[(size_t)at] = (i32)r;
+                        tval[(size_t)at] = data[q];
+                    }
+            }
+        }
+        const size_t sn = (size_t)N, sm = (size_t)M, sc = (size_t)count, sz = (size_t)nnz;
+        s->table.upload(s->lps.data(), sc);
+        s->ptr.upload(indptr, sm + 1);
+        s->tptr.upload(tptr.data(), sn + 1);
+        s->idx.alloc(sz); s->val.alloc(sz); s->tidx.alloc(sz); s->tval.alloc(sz);
+        if (sz) { s->idx.upload(indices, sz); s->val.upload(data, sz); s->tidx.upload(tidx.data(), sz); s->tval.upload(tval.data(), sz); }
+        s->b.upload(b, sm); s->c.upload(c, sn); s->lb.upload(lb, sn); s->ub.upload(ub, sn); s->y.upload(y0, sm);
+        s->x.alloc(sn); s->cbar.alloc(sn); s->d.alloc(sn); s->ax.alloc(sm); s->g.alloc(sm);
+        s->part_gb.alloc((size_t)kDgaParts * sc); s->part_min.alloc((size_t)kDgaParts * sc); s->part_any.alloc((size_t)kDgaParts * sc);
+        s->rnd.alloc(1);
+        s->ctl.alloc(sc);
+        s->ctl.zero();
+        SLP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dgm_iterate), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(kDgmSlotBytes + fused_lds_bytes(kDgaFusedMax))));
+        dgm_argmin(s.get(), s->cbar.p, s->x.p);   // the x of y0: what a frozen LP keeps
+        // a start whose dual energy is -inf freezes its LP (the single solve returns at once, :133-139)
+        std::vector<double> rep(3 * sc);
+        dgm_report(s.get(), rep.data());
+        std::vector<DgaCtl> h(sc);
+        memset(h.data(), 0, sc * sizeof(DgaCtl));
+        for (size_t k = 0; k < sc; ++k) h[k].frozen = rep[3 * k] == -INFINITY;
+        s->ctl.upload(h.data(), sc);
+        dgm_read_ctl(s.get(), h);
+        return s.release();
+    })
+}
+
+void slp_many_dga_destroy(slp_many_dga *s) { delete s; }
+
+int64_t slp_many_dga_kmax(const slp_many_dga *s) { return s ? s->kmax : -1; }
+
+int slp_many_dga_iterate(slp_many_dga *s, int64_t k) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && k >= 0, "slp_many_dga_iterate: bad arguments");
+        hipStream_t st = ctx().stream;
+        for (i64 done = 0; done < k;) {
+            const unsigned long long have = s->rnd_base + (unsigned long long)s->rnd_host.size();
+            // at most two tie draws per LP and iteration: iterations the buffer cannot run dry in
+            const i64 safe = have > s->draws_bound ? (i64)std::min<unsigned long long>((have - s->draws_bound) / 2, 1u << 30) : 0;
+            const int it = (int)std::min<i64>(std::min<i64>(s->kmax, k - done), safe);
+            if (it < 1) {
+                s->host_flags |= DGA_RAND_DRY;
+                break;
+            }
+            s->draws_bound += 2 * (unsigned long long)it;
+            s->timer.mark(-1);
+            hipLaunchKernelGGL(k_dgm_iterate, dim3((unsigned)s->count), dim3(kDgaFusedThreads), dgm_lds_bytes(s), st, dgm_args(s), it);
+            SLP_HIP(hipGetLastError());
+            s->timer.mark(ST_FUSED);
+            done += it;
+            s->iters += it;
+        }
+    })
+}
+
+int slp_many_dga_push_random(slp_many_dga *s, const double *draws, int64_t count) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && count >= 0 && (draws || count == 0), "slp_many_dga_push_random: bad arguments");
+        std::vector<DgaCtl> h;
+        dgm_read_ctl(s, h);
+        s->rnd_host.insert(s->rnd_host.end(), draws, draws + count);
+        // the draws every moving LP has passed (or never reaches: the start of the stream went into the default starts) are dropped
+        unsigned long long taken = ~0ull;
+        for (size_t k = 0; k < h.size(); ++k)
+            if (!h[k].frozen) taken = std::min(taken, s->lps[k].draw_offset + h[k].consumed);
+        if (taken != ~0ull && taken > s->rnd_base) {
+            const size_t drop = std::min<size_t>((size_t)(taken - s->rnd_base), s->rnd_host.size());
+            s->rnd_host.erase(s->rnd_host.begin(), s->rnd_host.begin() + (ptrdiff_t)drop);
+            s->rnd_base += drop;
+        }
+        if (!s->rnd_host.empty()) s->rnd.upload(s->rnd_host.data(), s->rnd_host.size());
+        s->host_flags &= ~(unsigned int)DGA_RAND_DRY;
+    })
+}
+
+int slp_many_dga_status(slp_many_dga *s, int64_t *out) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && out, "slp_many_dga_status: NULL argument");
+        std::vector<DgaCtl> h;
+        dgm_read_ctl(s, h);
+        for (i64 k = 0; k < s->count; ++k) {
+            out[2 * k] = (int64_t)(h[(size_t)k].flags | s->host_flags);
+            out[2 * k + 1] = (int64_t)h[(size_t)k].consumed;
+        }
+        out[2 * s->count] = (int64_t)(s->rnd_base + s->rnd_host.size()) - (int64_t)s->draws_bound;
+        out[2 * s->count + 1] = s->iters;
+    })
+}
+
+int slp_many_dga_frozen(slp_many_dga *s, int32_t *out) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && out, "slp_many_dga_frozen: NULL argument");
+        std::vector<DgaCtl> h;
+        dgm_read_ctl(s, h);
+        for (i64 k = 0; k < s->count; ++k) out[k] = h[(size_t)k].frozen;
+    })
+}
+
+int slp_many_dga_get_x(slp_many_dga *s, double *x) { SLP_API_INT({ SLP_REQUIRE(s && x, "NULL argument"); s->x.download(x, (size_t)s->n); }) }
+
+int slp_many_dga_get_y(slp_many_dga *s, double *y) { SLP_API_INT({ SLP_REQUIRE(s && y, "NULL argument"); s->y.download(y, (size_t)s->m); }) }
+
+int slp_many_dga_report(slp_many_dga *s, double *out) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && out, "slp_many_dga_report: NULL argument");
+        dgm_report(s, out);
+    })
+}
+
+int slp_many_dga_timing(slp_many_dga *s, int on) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_dga_timing: NULL handle");
+        s->timer.on = on != 0;
+        if (on) s->timer.used = 0;
+    })
+}
+
+int slp_many_dga_timing_read(slp_many_dga *s, double out[5]) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && out, "slp_many_dga_timing_read: NULL argument");
+        s->timer.read(out);
+    })
+}
+
+}  // extern "C"

@@ -2,6 +2,10 @@
 // constraint matrix) both run: every chain of additions exists once, here, so instance k of a batch is bit for bit the single
 // solve of its data.  The bodies below are whole kernels minus their addressing: the single solver's kernels call them on its
 // vectors, the batched kernels on the segment of the instance blockIdx.y.  blockIdx.x / gridDim.x mean the same in both.
+// slp_dga_many.hip (a list of LPs with matrices of their own, one workgroup of 1024 lanes per LP, whole iterations inside a launch)
+// runs the same bodies: the gradient pass and the block's scalars take (part index, lane in block, wave-sum slots) in place of
+// blockIdx.x / threadIdx.x / one LDS array, so that a 1024-lane workgroup computes them as four "virtual blocks" of four waves,
+// and the vectors an earlier stage of the same launch wrote are read through LD (DgaLoadWorkgroup).
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -31,6 +35,46 @@ struct DgaCtl {
     unsigned int flags;            // sticky, DGA_*
     int frozen;                    // batch only: the instance's start is dual infeasible (energy -inf), it stands still
 };
+
+struct DgaLoadPlain {   // written by an earlier launch
+    __device__ __forceinline__ double operator()(const double *p) const { return *p; }
+    __device__ __forceinline__ int operator()(const int *p) const { return *p; }
+};
+struct DgaLoadWorkgroup {   // global memory written by other lanes of this workgroup before the last barrier (as CpLoadWorkgroup)
+    __device__ __forceinline__ double operator()(const double *p) const { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    __device__ __forceinline__ int operator()(const int *p) const { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+};
+
+// block_reduce over one "virtual block": the 256 lanes (4 waves) whose lane in block is tl = 0 .. 255 -- a wave_sum / wave_max per
+// wave, then the four wave results in order; valid where tl == 0.  slots: 4 doubles of LDS of this virtual block.  Two barriers:
+// every thread of the workgroup calls it.  With 256-lane workgroups and tl = threadIdx.x it is block_reduce.
+template <bool IS_MAX>
+__device__ __forceinline__ double dga_block_reduce(double v, int tl, double *slots) {
+    v = IS_MAX ? wave_max(v) : wave_sum(v);
+    if ((tl & (kWave - 1)) == 0) slots[tl / kWave] = v;
+    __syncthreads();
+    double r = IS_MAX ? -__builtin_inf() : 0.0;
+    if (tl == 0) {
+        r = slots[0];
+#pragma unroll
+        for (int i = 1; i < kBlock / kWave; ++i) {
+            if (IS_MAX) r = (slots[i] > r) ? slots[i] : r;
+            else r += slots[i];
+        }
+    }
+    __syncthreads();
+    return r;
+}
+
+// "any lane of the virtual block": valid in all its lanes.  Two barriers.
+__device__ __forceinline__ int dga_block_or(int v, int tl, double *slots) {
+    const int w = __any(v);
+    if ((tl & (kWave - 1)) == 0) slots[tl / kWave] = w ? 1.0 : 0.0;
+    __syncthreads();
+    const int r = (slots[0] != 0.0) | (slots[1] != 0.0) | (slots[2] != 0.0) | (slots[3] != 0.0);
+    __syncthreads();
+    return r;
+}
 
 // order-preserving 64-bit image of a double; -0.0 and +0.0 share one key (numpy's sort takes them as equal)
 __device__ __forceinline__ unsigned long long key_of(double a) {
@@ -71,32 +115,33 @@ __device__ __forceinline__ void group_excl_scan(double tot, double *lds, double 
 
 // the four elements of thread `tl` (0..255) of scan tile `tile`: forward min(d ub, d lb) at positions r, backward max(..) at
 // positions nb - 1 - r, r = 1024 tile + 4 tl + e; 0.0 beyond the nb breakpoints
-template <bool BACKWARD>
+template <bool BACKWARD, class LD = DgaLoadPlain>
 __device__ __forceinline__ void tile_values(int tile, int tl, int nb, const int *__restrict__ cols, const double *__restrict__ d,
-                                            const double *__restrict__ lb, const double *__restrict__ ub, double v[4]) {
+                                            const double *__restrict__ lb, const double *__restrict__ ub, double v[4], LD ld = LD()) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int r = tile * kDgaTile + 4 * tl + e;
         double val = 0.0;
         if (r < nb) {
             const int j = cols[BACKWARD ? nb - 1 - r : r];
-            const double dj = d[j], u = dj * ub[j], l = dj * lb[j];
+            const double dj = ld(d + j), u = dj * ub[j], l = dj * lb[j];
             val = BACKWARD ? ((u > l) ? u : l) : ((u < l) ? u : l);
         }
         v[e] = val;
     }
 }
 
-__device__ __forceinline__ double alpha_at(int p, const int *cols, const double *cbar, const double *d) {
+template <class LD = DgaLoadPlain>
+__device__ __forceinline__ double alpha_at(int p, const int *cols, const double *cbar, const double *d, LD ld = LD()) {
     const int j = cols[p];
-    return -cbar[j] / d[j];
+    return -ld(cbar + j) / ld(d + j);
 }
 
 // numpy.searchsorted(-deriv, 0) (side="left": the bisection of npy_binsearch), the tie rule and the step (:55-65, :168-173)
-template <class Deriv>
+template <class Deriv, class LD = DgaLoadPlain>
 __device__ __forceinline__ void finish_search(DgaCtl *ctl, int nb, Deriv deriv, const int *cols, const double *cbar,
                                               const double *d, const double *rnd, unsigned long long rnd_base,
-                                              unsigned long long rnd_count, int ineq) {
+                                              unsigned long long rnd_count, int ineq, LD ld = LD()) {
     if (nb == 0) {
         ctl->flags |= DGA_EMPTY;
         ctl->t = 0.0;
@@ -123,9 +168,9 @@ __device__ __forceinline__ void finish_search(DgaCtl *ctl, int nb, Deriv deriv, 
         if (at >= rnd_base && at - rnd_base < rnd_count) r = rnd[at - rnd_base];
         else ctl->flags |= DGA_RAND_DRY;
         ctl->consumed = at + 1;
-        t = r * alpha_at(k, cols, cbar, d) + (1.0 - r) * alpha_at(km1, cols, cbar, d);
+        t = r * alpha_at(k, cols, cbar, d, ld) + (1.0 - r) * alpha_at(km1, cols, cbar, d, ld);
     } else {
-        t = alpha_at(km1, cols, cbar, d);
+        t = alpha_at(km1, cols, cbar, d, ld);
     }
     if (!(t >= 0.0)) ctl->flags |= DGA_NEG_STEP;
     if (t != t) ctl->flags |= DGA_NAN;
@@ -154,23 +199,29 @@ __device__ __forceinline__ double dga_update_y(double yi, double t, double gi, i
 // ---- the gradient pass ---------------------------------------------------------------------------------------------------------
 
 // The gradient of rows r0 .. r1 (0.0 elsewhere: the vector K^T multiplies), masked where y <= 0 on inequality rows (:159-161),
-// and per workgroup: g . b over its tiles of 256 rows (each a shuffle tree, the tiles in order), any g < 0 (inequalities) / any
-// g != 0 (equalities), min y / -g over g < 0.  ax == NULL: g is given (slp_dga_line_search).  red: kBlock / kWave doubles of LDS.
+// and per part: g . b over its tiles of 256 rows (each a shuffle tree, the tiles in order), any g < 0 (inequalities) / any
+// g != 0 (equalities), min y / -g over g < 0.  ax == NULL: g is given (slp_dga_line_search).
+// Part `part` of `parts` covers tiles part * per .. (part + 1) * per, per = ceil(tiles / parts); a part without tiles gives
+// (0.0, +inf, 0).  It is computed by one virtual block (tl: the lane in it, slots: its 4 doubles of LDS) in `steps` rounds of
+// barriers, which every thread of the workgroup runs: the part's own tile count where a workgroup is one virtual block (the single
+// and the batched solver: part = blockIdx.x, parts = gridDim.x, tl = threadIdx.x), `per` where four of them share a workgroup.
+template <class LD = DgaLoadPlain>
 __device__ __forceinline__ void dga_grad_body(i64 m, i64 r0, i64 r1, int ineq, const double *__restrict__ ax, const double *__restrict__ b,
                                               const double *__restrict__ y, double *__restrict__ g, double *__restrict__ part_gb,
-                                              double *__restrict__ part_min, int *__restrict__ part_any, double *red) {
-    const i64 tiles = (m + kBlock - 1) / kBlock, per = (tiles + gridDim.x - 1) / gridDim.x;
-    const i64 t0 = (i64)blockIdx.x * per, t1 = (t0 + per < tiles) ? t0 + per : tiles;
+                                              double *__restrict__ part_min, int *__restrict__ part_any, int part, int parts, int tl,
+                                              i64 steps, double *slots, LD ld = LD()) {
+    const i64 tiles = (m + kBlock - 1) / kBlock, per = (tiles + parts - 1) / parts;
+    const i64 t0 = (i64)part * per, t1 = (t0 + per < tiles) ? t0 + per : tiles;
     double acc = 0.0, mn = __builtin_inf();
     int any = 0;
-    for (i64 t = t0; t < t1; ++t) {
-        const i64 i = t * kBlock + threadIdx.x;
+    for (i64 step = 0; step < steps; ++step) {
+        const i64 t = t0 + step, i = t * kBlock + tl;
         double gi = 0.0, term = 0.0;
-        if (i < m) {
+        if (t < t1 && i < m) {
             if (ax) {
                 if (i >= r0 && i < r1) {
-                    gi = ax[i] - b[i];
-                    if (ineq && y[i] <= 0.0 && !(gi > 0.0)) gi = (gi != gi) ? gi : 0.0;
+                    gi = ld(ax + i) - b[i];
+                    if (ineq && ld(y + i) <= 0.0 && !(gi > 0.0)) gi = (gi != gi) ? gi : 0.0;
                 }
                 g[i] = gi;
             } else {
@@ -181,33 +232,43 @@ __device__ __forceinline__ void dga_grad_body(i64 m, i64 r0, i64 r1, int ineq, c
             if (ineq) {
                 if (gi < 0.0) {
                     any = 1;
-                    const double r = y ? y[i] / -gi : __builtin_inf();
+                    const double r = y ? ld(y + i) / -gi : __builtin_inf();
                     mn = (r < mn) ? r : mn;
                 }
             } else if (gi != 0.0) {
                 any = 1;
             }
         }
-        const double s = block_reduce<false>(term, red);
-        if (threadIdx.x == 0) acc += s;
+        const double s = dga_block_reduce<false>(term, tl, slots);
+        if (tl == 0 && t < t1) acc += s;
     }
-    mn = -block_reduce<true>(-mn, red);
-    any = __syncthreads_or(any);
-    if (threadIdx.x == 0) {
-        part_gb[blockIdx.x] = acc;
-        part_min[blockIdx.x] = mn;
-        part_any[blockIdx.x] = any;
+    mn = -dga_block_reduce<true>(-mn, tl, slots);
+    any = dga_block_or(any, tl, slots);
+    if (tl == 0) {
+        part_gb[part] = acc;
+        part_min[part] = mn;
+        part_any[part] = any;
     }
 }
 
-// one workgroup: the block's scalars from the partial results
+// the tiles part `part` of `parts` holds of m rows: the `steps` of a workgroup that is one virtual block
+__device__ __forceinline__ i64 dga_part_tiles(i64 m, int part, int parts) {
+    const i64 tiles = (m + kBlock - 1) / kBlock, per = (tiles + parts - 1) / parts;
+    const i64 t0 = (i64)part * per, t1 = (t0 + per < tiles) ? t0 + per : tiles;
+    return t1 > t0 ? t1 - t0 : 0;
+}
+
+// the block's scalars from the partial results, reduced as one more 256-lane tile by a virtual block (tl, slots); `writer`: the
+// virtual block whose lane 0 stores them (every virtual block of the workgroup runs the barriers)
+template <class LD = DgaLoadPlain>
 __device__ __forceinline__ void dga_begin_body(int parts, const double *__restrict__ part_gb, const double *__restrict__ part_min,
-                                               const int *__restrict__ part_any, DgaCtl *__restrict__ ctl, double *red) {
-    const int i = threadIdx.x;
-    const double gb = block_reduce<false>(i < parts ? part_gb[i] : 0.0, red);
-    const double mn = -block_reduce<true>(i < parts ? -part_min[i] : -__builtin_inf(), red);
-    const int any = __syncthreads_or(i < parts ? part_any[i] : 0);
-    if (i == 0) {
+                                               const int *__restrict__ part_any, DgaCtl *__restrict__ ctl, int tl, double *slots,
+                                               bool writer = true, LD ld = LD()) {
+    const int i = tl;
+    const double gb = dga_block_reduce<false>(i < parts ? ld(part_gb + i) : 0.0, tl, slots);
+    const double mn = -dga_block_reduce<true>(i < parts ? -ld(part_min + i) : -__builtin_inf(), tl, slots);
+    const int any = dga_block_or(i < parts ? ld(part_any + i) : 0, tl, slots);
+    if (i == 0 && writer) {
         ctl->gb = gb;
         ctl->minratio = mn;
         ctl->active = any;
@@ -323,10 +384,11 @@ inline size_t fused_lds_bytes(int npad) { return (size_t)npad * 12 + 40 * sizeof
 
 // dga_lds: fused_lds_bytes(npad) bytes, 16-byte aligned:
 // [npad] 8-byte slots (keys, then the derivative) | [npad] columns | 16 wave sums | 8 tile sums forward | 8 backward | scalars
+template <class LD = DgaLoadPlain>
 __device__ __forceinline__ void dga_fused_body(int n, int npad, const double *__restrict__ d, const double *__restrict__ cbar,
                                                const double *__restrict__ lb, const double *__restrict__ ub, DgaCtl *__restrict__ ctl,
                                                const double *__restrict__ rnd, unsigned long long rnd_base, unsigned long long rnd_count,
-                                               int ineq, unsigned char *dga_lds) {
+                                               int ineq, unsigned char *dga_lds, LD ld = LD()) {
     unsigned long long *slot = reinterpret_cast<unsigned long long *>(dga_lds);
     double *slotd = reinterpret_cast<double *>(dga_lds);
     int *cols = reinterpret_cast<int *>(dga_lds + (size_t)npad * 8);
@@ -342,9 +404,9 @@ __device__ __forceinline__ void dga_fused_body(int n, int npad, const double *__
         int col = 0x7fffffff;
         if (j < n) {
             col = j;
-            const double dj = d[j];
+            const double dj = ld(d + j);
             if (dj != 0.0) {
-                const double a = -cbar[j] / dj;
+                const double a = -ld(cbar + j) / dj;
                 if (a != a) bad = 1;
                 else { key = key_of(a); ++mine; }
             }
@@ -379,10 +441,10 @@ __device__ __forceinline__ void dga_fused_body(int n, int npad, const double *__
     // tile sums (4 tiles per pass: one per group of 4 waves), their scan, then the final passes
     for (int t0 = 0; t0 < tiles; t0 += 4) {
         const int tile = t0 + group;
-        tile_values<false>(tile, tl, nb, cols, d, lb, ub, v);
+        tile_values<false>(tile, tl, nb, cols, d, lb, ub, v, ld);
         group_excl_scan(((v[0] + v[1]) + v[2]) + v[3], lds, ex, total);
         if (tl == 0 && tile < tiles) tot_f[tile] = total;
-        tile_values<true>(tile, tl, nb, cols, d, lb, ub, v);
+        tile_values<true>(tile, tl, nb, cols, d, lb, ub, v, ld);
         group_excl_scan(((v[0] + v[1]) + v[2]) + v[3], lds, ex, total);
         if (tl == 0 && tile < tiles) tot_b[tile] = total;
     }
@@ -393,7 +455,7 @@ __device__ __forceinline__ void dga_fused_body(int n, int npad, const double *__
     // backward: slot[p] = -(g.b) + B[p]
     for (int t0 = 0; t0 < tiles; t0 += 4) {
         const int tile = t0 + group;
-        tile_values<true>(tile, tl, nb, cols, d, lb, ub, v);
+        tile_values<true>(tile, tl, nb, cols, d, lb, ub, v, ld);
         group_excl_scan(((v[0] + v[1]) + v[2]) + v[3], lds, ex, total);
         double run = (tile < tiles ? tot_b[tile] : 0.0) + ex;
 #pragma unroll
@@ -407,7 +469,7 @@ __device__ __forceinline__ void dga_fused_body(int n, int npad, const double *__
     // forward: derivative[p + 1] += F[p]; the last one has no backward part
     for (int t0 = 0; t0 < tiles; t0 += 4) {
         const int tile = t0 + group;
-        tile_values<false>(tile, tl, nb, cols, d, lb, ub, v);
+        tile_values<false>(tile, tl, nb, cols, d, lb, ub, v, ld);
         group_excl_scan(((v[0] + v[1]) + v[2]) + v[3], lds, ex, total);
         double run = (tile < tiles ? tot_f[tile] : 0.0) + ex;
 #pragma unroll
@@ -423,7 +485,7 @@ __device__ __forceinline__ void dga_fused_body(int n, int npad, const double *__
         ctl->nb = nb;
         if (cnt[1]) ctl->flags |= DGA_NAN;
         auto deriv = [&](int k) { return k < nb ? slotd[k] : last[0]; };
-        finish_search(ctl, nb, deriv, cols, cbar, d, rnd, rnd_base, rnd_count, ineq);
+        finish_search(ctl, nb, deriv, cols, cbar, d, rnd, rnd_base, rnd_count, ineq, ld);
     }
 }
 
