@@ -1,0 +1,145 @@
+"""What keeps tests/test_gpu_fuzz_batched.py from passing vacuously, checked without a GPU on the generators and CPU references of
+tools/fuzz_batched.py with the GPU test's own seed and case count: the dual-ascent LPs mostly run clean, some raise each of the
+two line-search errors in a way the device can be compared with, the horizons are worth comparing,
+HiGHS solves every clean one, and the Chambolle-Pock / ADMM LPs are accepted by the entry points and reach the wave, tile and
+padding sizes they are drawn for."""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import fuzz_batched  # noqa: E402
+
+SEED, CASES = fuzz_batched.TEST_SEED, fuzz_batched.TEST_CASES
+
+
+def _pool():
+    return [lp for batch in fuzz_batched.dga_pool(CASES, SEED) for lp in batch]
+
+
+def test_dga_lps_mostly_run_clean_and_some_raise_each_error():
+    stats = fuzz_batched.dga_statistics(CASES, SEED)
+    for kind, s in stats.items():
+        print(f"{kind}: {s['clean']} clean / {s['no_crossing']} no-crossing / {s['empty']} empty / {s['negative']} negative step of "
+              f"{s['drawn']}; {s['comparable_raises']} raises comparable on the device; shortest horizon of a clean LP {s['min_horizon']}")
+        assert s["drawn"] >= CASES // 2 and 2 * s["clean"] >= s["drawn"], kind
+    assert sum(s["no_crossing"] for s in stats.values()) >= 1 and sum(s["empty"] for s in stats.values()) >= 1
+    comparable = {lp.fail[1] for lp in _pool() if lp.status_ok}
+    assert {"never changes sign", "empty breakpoint set"} <= comparable
+    # a raise in a later iteration with clean LPs around it: the status checks compare iterates before and after it
+    assert any(lp.status_ok and lp.fail[0] > 0 for lp in _pool())
+    # dga_cpu in the device's own order runs clean wherever the reference's order does: the device must then end without a flag,
+    # and the GPU test asserts that no dual bound went unchecked
+    assert all(lp.device_fail is None for lp in _pool() if lp.clean)
+    for kind in ("integer", "decimal"):   # every kind meets every edge size; some LPs take tie draws, at different counts
+        assert set(fuzz_batched.EDGE_N) <= {lp.args[0].size for lp in _pool()}
+        draws = {lp.states[fuzz_batched.DGA_ITERS - 1][3] for lp in _pool() if lp.kind == kind and lp.clean}
+        print(f"{kind}: tie draws taken after {fuzz_batched.DGA_ITERS} iterations: {sorted(draws)}")
+    assert len({lp.states[fuzz_batched.DGA_ITERS - 1][3] for lp in _pool() if lp.clean}) >= 3
+    assert fuzz_batched.DGA_TILE_EDGE in [len(batch) for batch in fuzz_batched.dga_pool(CASES, SEED)]
+    assert max(len(lps) for lps in fuzz_batched.dga_lists(CASES, SEED)) > 256
+
+
+def test_dga_lps_have_a_horizon_worth_comparing():
+    """The horizon -- how far dga_cpu agrees with itself in its three orders -- is the full run on the decimal-valued clean LPs
+    and falls below 10 iterations on at most one clean LP in ten of either kind (integer-valued: equal breakpoints, which the
+    reference's unstable sort and the device's stable one order differently)."""
+    for kind in ("integer", "decimal"):
+        clean = [lp for lp in _pool() if lp.kind == kind and lp.clean]
+        short = [lp.name for lp in clean if lp.horizon < 10]
+        full = sum(lp.horizon == fuzz_batched.DGA_ITERS - 1 for lp in clean)
+        print(f"{kind}: {len(clean)} clean, {full} with the full horizon, horizons {sorted({lp.horizon for lp in clean})}, below 10: {len(short)}")
+        late = sum(len(lp.late_stops()) for lp in clean)
+        print(f"{kind}: {late} comparisons behind the horizon, with dga_cpu in the device's order")
+        assert 10 * len(short) <= len(clean) and 2 * full >= len(clean), kind
+    for lp in _pool():   # only the compared prefix is shortened: no LP with a complete iteration is left out
+        assert lp.stops() == sorted({s for s in fuzz_batched.DGA_STOPS if s <= lp.horizon} | ({lp.horizon} if lp.horizon >= 0 else set()))
+        assert all(s in lp.states for s in lp.stops())
+
+
+def test_dga_lps_meet_the_solvers_preconditions_and_highs_solves_the_clean_ones():
+    from pysparselp_amd.DualGradientAscent import FUSED_MAX
+
+    for lp in _pool():
+        c, a_eq, b_eq, a_ineq, b_upper, lb, ub = lp.args
+        assert 1 <= c.size <= FUSED_MAX and sum(lp.rows) >= 1, lp.name
+        assert np.all(np.isfinite(lb)) and np.all(np.isfinite(ub)) and np.all(lb <= ub), lp.name
+        if lp.kind == "integer":
+            for v in (c, lb, ub, b_eq, a_eq.data) + (() if a_ineq is None else (b_upper, a_ineq.data)):
+                assert np.array_equal(v, np.round(v)), lp.name
+            assert np.all(a_eq.data != 0) and (a_ineq is None or np.all(a_ineq.data != 0))
+        if lp.clean:
+            assert lp.linprog().status == 0, (lp.name, lp.linprog().message)
+    assert any(np.any(lp.args[5] == lp.args[6]) for lp in _pool())
+    assert any(np.any(lp.args[0] == 0) for lp in _pool())
+
+
+def _finite_side_per_row(problem):
+    _, _, _, a_ineq, bl, bu, _, _ = problem
+    if a_ineq is None:
+        return True
+    bu, bl = np.atleast_2d(bu), (None if bl is None else np.atleast_2d(bl))
+    return bool(np.all(np.isfinite(bu) | (False if bl is None else np.isfinite(bl))))
+
+
+def _shape_facts(lps):
+    """(the n that occur, the longest row, an empty row?, an empty column over both blocks?)"""
+    ns, longest, empty_row, empty_col = set(), 0, False, False
+    for lp in lps:
+        n = lp["c"].shape[-1]
+        ns.add(n)
+        blocks = [a for a in (lp["a_eq"], lp["a_ineq"]) if a is not None]
+        longest = max([longest] + [int(np.diff(a.indptr).max()) for a in blocks if a.shape[0]])
+        empty_row = empty_row or any(np.any(np.diff(a.indptr) == 0) for a in blocks)
+        used = np.zeros(n, dtype=bool)
+        for a in blocks:
+            used[a.indices] = True
+            assert np.all(a.data != 0)
+        empty_col = empty_col or not used.all()
+    return ns, longest, empty_row, empty_col
+
+
+def test_cp_and_admm_lps_pass_validation_and_reach_the_edge_sizes():
+    from pysparselp_amd.ADMM import _validate_batch
+    from pysparselp_amd.ChambollePockPPD import _many_problem, one_sided_system_batch
+
+    cp_batches = fuzz_batched.cp_batch_cases(CASES, SEED)
+    admm_batches = fuzz_batched.admm_batch_cases(CASES, SEED)
+    lists = fuzz_batched.cp_many_cases(CASES, SEED)
+    for args, its, plot in cp_batches:
+        assert 1 <= its <= 60 and plot in fuzz_batched.CADENCES
+        if args["a_ineq"] is not None:   # the pattern of finite sides is that of instance 0 in every instance
+            mat, b = one_sided_system_batch(args["a_ineq"], args["b_lower"], args["b_upper"])
+            assert b.shape[-1] == mat[3]
+        for k in range(args["c"].shape[0]):
+            problem, x0 = fuzz_batched.of_instance(args, k)
+            _many_problem(k, problem)
+            assert _finite_side_per_row(problem) and np.all(problem[6] <= problem[7])
+    for args, its, plot in admm_batches:
+        assert args["a_ineq"] is not None and np.all(np.isfinite(args["c"]))
+        _validate_batch(args["c"], args["a_eq"], args["beq"], args["a_ineq"], args["b_lower"], args["b_upper"], args["lb"], args["ub"], args["x0"])
+        assert _finite_side_per_row(fuzz_batched.of_instance(args, 0)[0])
+    for lps, its, plot in lists:
+        for k, lp in enumerate({id(lp): lp for lp in lps}.values()):
+            _many_problem(k, fuzz_batched.of_instance(lp, 0)[0])
+            assert _finite_side_per_row(fuzz_batched.of_instance(lp, 0)[0])
+    assert fuzz_batched.CP_TILE_EDGE in [a["c"].shape[0] for a, _, _ in cp_batches]
+    assert fuzz_batched.ADMM_TILE_EDGE in [a["c"].shape[0] for a, _, _ in admm_batches]
+    assert max(len(lps) for lps, _, _ in lists) > 256 and {len(lps) for lps, _, _ in lists} >= {1, 2, 3}
+    everything = [a for a, _, _ in cp_batches] + [a for a, _, _ in admm_batches] + [lp for lps, _, _ in lists for lp in lps]
+    ns, longest, empty_row, empty_col = _shape_facts(everything)
+    print("n drawn:", sorted(ns), "longest row:", longest)
+    assert set(fuzz_batched.EDGE_N) <= ns and longest > 64 and empty_row and empty_col
+    for name, family in (("cp_batch", [a for a, _, _ in cp_batches]), ("admm_batch", [a for a, _, _ in admm_batches]),
+                         ("cp_many", [lp for lps, _, _ in lists for lp in lps])):
+        ns, longest, empty_row, empty_col = _shape_facts(family)
+        print(name, "edge n drawn:", sorted(ns & set(fuzz_batched.EDGE_N)), "longest row:", longest)
+        assert longest > 64 and empty_row and empty_col and set(fuzz_batched.EDGE_N) <= ns, name
+        assert any(np.any(lp["lb"] == lp["ub"]) for lp in family) and any(np.any(np.isinf(lp["lb"])) for lp in family), name
+        assert any(lp["x0"] is not None for lp in family) and any(lp["x0"] is None for lp in family), name
+        assert any(lp["b_lower"] is not None for lp in family) and any(lp["b_lower"] is None for lp in family), name
+    assert any(a["a_ineq"] is None for a, _, _ in cp_batches) and any(lp["a_ineq"] is None for lps, _, _ in lists for lp in lps)
+    assert any(a["a_eq"] is None for a, _, _ in cp_batches) and any(a["a_eq"] is not None for a, _, _ in cp_batches)
+    assert any(a["b_upper"] is not None and a["b_upper"].ndim == 2 for a, _, _ in cp_batches)   # per-instance right-hand sides
+    assert any(a["lb"].ndim == 2 for a, _, _ in cp_batches) and any(a["lb"].ndim == 2 for a, _, _ in admm_batches)

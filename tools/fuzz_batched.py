@@ -1,0 +1,991 @@
+"""Randomised cross-check of the batched, list and dual-ascent solver families against their CPU references, bit for bit:
+``chambolle_pock_ppd_batch`` / ``chambolle_pock_ppd_many`` against ``oracle.chambolle_pock_ppd``, ``lp_admm_batch`` against
+``oracle.lp_admm``, ``DeviceDGA`` / ``DeviceDGABatch`` / ``DeviceDGAMany`` against tests/dga_cpu.py in the reference's order of sums
+(up to the iteration to which dga_cpu agrees with itself in its three orders, behind it in the device's own order), each batch instance and list LP
+also against the single solver alone, the status bits of the LPs on which dga_cpu raises, and the dual bound against HiGHS.
+
+The LPs have wave / tile / padding sizes (n in 1, 2, 3, 63, 64, 65, 127, 129, 255, 257), an empty row, an empty column, a row of
+more than 64 entries, one- / two-sided / mixed rows, infinite and equal bounds, warm starts and odd reporting cadences.
+
+    python tools/fuzz_batched.py [--cases 24] [--seed 0] [--family cp_batch,cp_many,admm_batch,dga,dga_batch,dga_many]
+
+The generators and the CPU references need no GPU (tests/test_fuzz_batched_host.py checks on them that the GPU runs compare what
+they claim to); the ``run_*`` functions need one."""
+import argparse
+import contextlib
+import os
+import sys
+
+import numpy as np
+import scipy.optimize
+import scipy.sparse
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (REPO, os.path.join(REPO, "tests")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+from dga_cpu import dga_cpu, dual_argmin  # noqa: E402
+
+EDGE_N = (1, 2, 3, 63, 64, 65, 127, 129, 255, 257)
+BATCH_SIZES = (1, 2, 3, 7)
+CADENCES = (1, 7, 10, 10 ** 9)
+ENERGY_TOL = dict(rtol=1e-9, atol=1e-9)   # the project's bar for the reports' fixed-order sums (tests/test_gpu_cp_batch.py)
+CP_TILE_EDGE, ADMM_TILE_EDGE, DGA_TILE_EDGE = 65, 17, 65   # the remainder sizes of the families' own tile-edge tests
+LONG_LIST = 260    # more LPs than compute units (256), by cycling
+DGA_ITERS = 40
+DGA_STOPS = (0, 9, DGA_ITERS - 1)
+STATUS_BITS = {"negative step": 1, "empty breakpoint set": 2, "never changes sign": 16}
+TEST_SEED, TEST_CASES = 20, 24   # what tests/test_gpu_fuzz_batched.py runs and tests/test_fuzz_batched_host.py checks
+
+
+# ---- generators ----------------------------------------------------------------------------------------------------------------
+
+def _decimal(rng, size):
+    return np.round(rng.randn(size) * 100) / 100
+
+
+def random_lp(rng, family, n=None):
+    """A small LP as a dict ``c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0`` (``a_eq`` None without equality rows), feasible
+    at a point ``xf``.  ``family``: ``"cp"`` (any rows; now and then equality rows only), ``"admm"`` (always an inequality block),
+    ``"dga"`` (one-sided rows, finite bounds, no start).  ``n``: the number of variables, drawn when None.  Stored values are
+    multiples of 0.01 plus 0.005: no stored zero."""
+    drawn = int(rng.choice(EDGE_N)) if rng.rand() < 0.5 else int(rng.randint(2, 71))
+    n = drawn if n is None else n
+    me = int(rng.choice([0, 0, 1, 5, 12]))
+    mi = int(rng.randint(1, 91))
+    dens = float(rng.choice([0.05, 0.2, 0.5]))
+    ae = scipy.sparse.random(me, n, density=dens, random_state=rng, format="lil")
+    ai = scipy.sparse.random(mi, n, density=dens, random_state=rng, format="lil")
+    empty_row = int(rng.randint(0, mi)) if mi > 1 else None
+    # a row of more than 64 entries takes every column at n = 65: no empty column there
+    empty_col = int(rng.randint(0, n)) if n > 1 and n != 65 else None
+    if n > 64:
+        long_row = 0 if mi == 1 else int(rng.choice([r for r in range(mi) if r != empty_row]))
+        cols = np.array([j for j in range(n) if j != empty_col])
+        ai[long_row, rng.choice(cols, size=int(rng.randint(65, cols.size + 1)), replace=False)] = 1.0
+    if empty_row is not None:
+        ai[empty_row, :] = 0
+    if empty_col is not None:
+        ai[:, empty_col] = 0
+        ae[:, empty_col] = 0
+    ae, ai = ae.tocsr(), ai.tocsr()
+    ae.eliminate_zeros()
+    ai.eliminate_zeros()
+    ae.data = _decimal(rng, ae.nnz) + 0.005
+    ai.data = _decimal(rng, ai.nnz) + 0.005
+    xf = _decimal(rng, n)
+    be = ae @ xf
+    bu = ai @ xf + rng.rand(mi)
+    bl = ai @ xf - rng.rand(mi)
+    mode = "upper" if family == "dga" else str(rng.choice(["upper", "two", "mixed"]))
+    if mode == "upper":
+        bl = None
+    elif mode == "mixed":   # every row keeps a finite side
+        bl[rng.rand(mi) < 0.4] = -np.inf
+        drop = rng.rand(mi) < 0.3
+        bu[drop & np.isfinite(bl)] = np.inf
+    c = _decimal(rng, n)
+    t = np.abs(rng.randn(n)) + 0.1
+    t[rng.rand(n) < 0.15] = 0.0    # fixed variables: lb == ub
+    lb, ub = xf - t, xf + t
+    x0 = None
+    if family != "dga":
+        lb[rng.rand(n) < 0.2] = -np.inf
+        ub[rng.rand(n) < 0.2] = np.inf
+        x0 = None if rng.rand() < 0.5 else np.round(rng.randn(n), 2)
+    eq_only = me > 0 and rng.rand() < (0.25 if family == "cp" else 0.1 if family == "dga" else 0.0)
+    lp = dict(c=c, a_eq=ae if me else None, beq=be if me else None, a_ineq=ai, b_lower=bl, b_upper=bu, lb=lb, ub=ub, x0=x0)
+    if eq_only:
+        lp.update(a_ineq=None, b_lower=None, b_upper=None)
+    return lp
+
+
+def batch_of(rng, lp, batch, family):
+    """``lp`` as ``batch`` instances: ``c`` becomes ``(batch, n)``; instance 0 is the LP as drawn, instance 1 has exact zeros among
+    its costs, the others perturb ``c`` and, by coin flip, ``lb`` / ``ub`` (widened, infinite stays infinite), ``x0`` and -- for
+    ``family == "cp"`` -- the right-hand sides (the pattern of finite sides stays that of instance 0)."""
+    c = lp["c"]
+    n = c.size
+    cs = np.tile(c, (batch, 1))
+    cs[1:] = c * (1 + 0.2 * rng.randn(batch - 1, n)) + 0.05 * rng.randn(batch - 1, n)
+    if batch > 1:
+        cs[1, ::3] = 0.0
+    out = dict(lp, c=cs)
+    if batch == 1:
+        return out
+    if rng.rand() < 0.5:
+        lbs, ubs = np.tile(lp["lb"], (batch, 1)), np.tile(lp["ub"], (batch, 1))
+        lbs[1:] -= 0.1 * rng.rand(batch - 1, n)
+        ubs[1:] += 0.1 * rng.rand(batch - 1, n)
+        out.update(lb=lbs, ub=ubs)
+    if rng.rand() < 0.5:
+        x0 = np.tile(np.zeros(n) if lp["x0"] is None else lp["x0"], (batch, 1))
+        x0[1:] += np.round(0.1 * rng.randn(batch - 1, n), 3)
+        out["x0"] = x0
+    if family == "cp" and rng.rand() < 0.5:
+        if lp["a_eq"] is not None:
+            bes = np.tile(lp["beq"], (batch, 1))
+            bes[1:] += 0.01 * rng.randn(batch - 1, bes.shape[1])
+            out["beq"] = bes
+        if lp["a_ineq"] is not None:
+            bus = np.tile(lp["b_upper"], (batch, 1))
+            bus[1:] += 0.01 * rng.rand(batch - 1, bus.shape[1])
+            out["b_upper"] = bus
+            if lp["b_lower"] is not None:
+                bls = np.tile(lp["b_lower"], (batch, 1))
+                bls[1:] -= 0.01 * rng.rand(batch - 1, bls.shape[1])
+                out["b_lower"] = bls
+    return out
+
+
+def of_instance(args, k):
+    """``((c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub), x0)`` of instance ``k`` of a batch (or of a single LP: ``c`` 1-D)."""
+    pick = lambda v: v if (v is None or np.ndim(v) == 1) else v[k]  # noqa: E731
+    return ((pick(args["c"]), args["a_eq"], pick(args["beq"]), args["a_ineq"], pick(args["b_lower"]), pick(args["b_upper"]),
+             pick(args["lb"]), pick(args["ub"])), pick(args["x0"]))
+
+
+def edge_n(case):
+    """Cases 0 .. 9 of every family have the sizes of ``EDGE_N`` in turn, so that every family meets every edge; None: drawn."""
+    return EDGE_N[case] if case < len(EDGE_N) else None
+
+
+def large_case(cases):
+    """The case that carries a family's large instance -- the tile-edge batch, the list longer than 256: the first behind the
+    forced edge sizes, or the last."""
+    return min(len(EDGE_N), cases - 1)
+
+
+def batch_sizes(rng, cases, edge):
+    """One size per case from ``BATCH_SIZES``; ``large_case`` has the family's tile-edge size."""
+    sizes = [int(rng.choice(BATCH_SIZES)) for _ in range(cases)]
+    sizes[large_case(cases)] = edge
+    return sizes
+
+
+def cp_batch_cases(cases, seed):
+    """``[(args, iterations, cadence)]`` of ``run_cp_batch``."""
+    rng = np.random.RandomState(seed)
+    sizes = batch_sizes(rng, cases, CP_TILE_EDGE)
+    return [(batch_of(rng, random_lp(rng, "cp", edge_n(case)), b, "cp"), int(rng.randint(1, 61)), int(rng.choice(CADENCES)))
+            for case, b in enumerate(sizes)]
+
+
+def admm_batch_cases(cases, seed):
+    """``[(args, iterations, cadence)]`` of ``run_admm_batch``: always an inequality block, finite costs, shared right-hand sides."""
+    rng = np.random.RandomState(seed + 1000)
+    sizes = batch_sizes(rng, cases, ADMM_TILE_EDGE)
+    return [(batch_of(rng, random_lp(rng, "admm", edge_n(case)), b, "admm"), int(rng.randint(1, 61)), int(rng.choice(CADENCES)))
+            for case, b in enumerate(sizes)]
+
+
+def cp_many_cases(cases, seed):
+    """``[(lps, iterations, cadence)]`` of ``run_cp_many``: lists of 1 to 9 LPs of different shapes (the first LP of cases 0 .. 9 has the
+    edge sizes in turn); ``large_case`` cycles its LPs to ``LONG_LIST`` entries."""
+    rng = np.random.RandomState(seed + 2000)
+    out = []
+    for case in range(cases):
+        lps = [random_lp(rng, "cp", edge_n(case) if k == 0 else None) for k in range(int(rng.randint(1, 10)))]
+        if case == large_case(cases):
+            lps = [lps[k % len(lps)] for k in range(LONG_LIST)]
+        out.append((lps, int(rng.randint(1, 61)), int(rng.choice(CADENCES))))
+    return out
+
+
+# ---- dual gradient ascent: LPs, batches, lists and their CPU references -----------------------------------------------------------
+
+def _integer_dga_args(rng, n=None):
+    """The construction of ``integer_lp`` (tests/test_gpu_dga.py) at small size: integer entries ``round(10 N(0, 1))`` (0 -> 1),
+    one entry per column stratum, integer bounds (some equal), costs and slacks: every term of the line search's sums is an
+    integer, so the search does not depend on their order.  Every other LP is the same construction with entries +-1, bound
+    ranges 0 .. 2 and slacks 0 .. 2: the derivative's values are small integers, so it often vanishes at a breakpoint and the
+    search takes a tie draw."""
+    drawn = int(rng.choice(EDGE_N)) if rng.rand() < 0.5 else int(rng.randint(2, 71))
+    n = drawn if n is None else n
+    m_eq = int(rng.choice([0, 0, 1, 5, 12]))
+    m = m_eq + int(rng.randint(1, 91))
+    k = int(min(n, rng.randint(1, 7)))
+    unit = rng.rand() < 0.5
+    cols = (np.arange(k) * (n // k) + rng.randint(0, n // k, size=(m, k))).astype(np.int32)
+    vals = np.round(10 * rng.randn(m, k))
+    vals[vals == 0] = 1.0
+    if unit:
+        vals = np.sign(vals)
+    a = scipy.sparse.csr_matrix((vals.ravel(), cols.ravel(), np.arange(0, m * k + 1, k)), shape=(m, n))
+    lb = rng.randint(-5, 1, size=n).astype(np.float64)
+    ub = lb + rng.randint(0, 3 if unit else 10, size=n)
+    xf = lb + np.floor(rng.rand(n) * (ub - lb + 1))
+    ax = a @ xf
+    b = ax + rng.randint(0, 3 if unit else 50, size=m)
+    b[:m_eq] = ax[:m_eq]
+    c = np.round((2 if unit else 10) * rng.randn(n))
+    if m_eq > 0 and rng.rand() < 0.1:
+        return c, a[:m_eq].tocsr(), b[:m_eq], None, None, lb, ub
+    return c, a[:m_eq].tocsr(), b[:m_eq], a[m_eq:].tocsr(), b[m_eq:], lb, ub
+
+
+def _decimal_dga_args(rng, n=None):
+    lp = random_lp(rng, "dga", n)
+    n = lp["c"].size
+    a_eq = lp["a_eq"] if lp["a_eq"] is not None else scipy.sparse.csr_matrix((0, n))
+    b_eq = lp["beq"] if lp["beq"] is not None else np.zeros(0)
+    return lp["c"], a_eq, b_eq, lp["a_ineq"], lp["b_upper"], lp["lb"], lp["ub"]
+
+
+def _status_of(error):
+    if isinstance(error, AssertionError):
+        return "negative step"
+    return next(name for name in STATUS_BITS if name in str(error))
+
+
+def cpu_states(args, order, iters=DGA_ITERS):
+    """``({it: (x, y_eq, y_ineq, draws)}, fail)`` of ``dga_cpu`` in the given order of sums: every iteration it completes (key -1:
+    the start) and ``fail`` = None or ``(t, name)`` when it raises in iteration ``t`` (0-based: ``t`` iterations are complete)."""
+    def run(k):
+        return dga_cpu(*args, nb_max_iter=k, order=order, keep=range(k))
+
+    try:
+        return run(iters), None
+    except (ValueError, AssertionError) as e:
+        name = _status_of(e)
+    lo, hi = 0, iters   # run(lo) completes, run(hi) raises
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        try:
+            run(mid)
+            lo = mid
+        except (ValueError, AssertionError):
+            hi = mid
+    return run(lo), (lo, name)
+
+
+def _same_state(p, q):
+    return (np.array_equal(p[0], q[0]) and np.array_equal(p[1], q[1]) and p[3] == q[3]
+            and ((p[2] is None and q[2] is None) or np.array_equal(p[2], q[2])))
+
+
+class DgaLP:
+    """One LP of the dual-ascent families: ``args`` as ``dga_cpu`` takes them, ``kind`` (``"integer"`` / ``"decimal"``), a name for
+    messages, and its CPU reference (never modified):
+
+    ``states``        ``{it: (x, y_eq, y_ineq, draws)}`` in the reference's order of sums, every iteration it completes;
+    ``fail``          None (the LP is ``clean``), or ``(t, name)``: dga_cpu raises ``name`` in iteration ``t``;
+    ``horizon``       the last iteration the device is compared with ``states`` at: the last complete one at which the orders
+                      ``"reference"``, ``"blocked"`` and ``"device"`` agree bit for bit (the rule of tests/golden/make_dga_golden.py).
+                      A decimal-valued LP leaves it through a rounding difference of the sums.  An integer-valued one, whose sums
+                      are exact, leaves it through equal breakpoints: the derivative inside a group of equal breakpoints depends
+                      on the order the sort gives them (``np.argsort`` there, by (alpha, column) on the device), so the search may
+                      count a tie draw in one order and not in the other;
+    ``device_states`` the same run with ``order="device"``, the CPU model of the device's own sort and sums: what the device is
+                      compared with at the stops behind the horizon (``device_fail``: as ``fail``);
+    ``status_ok``     the raise itself is comparable: all orders agree up to iteration ``t - 1`` and raise the same error in ``t``."""
+
+    def __init__(self, args, kind, name):
+        self.args, self.kind, self.name = args, kind, name
+        self._opt = None
+        self.single = {}   # path -> result of the single solver (filled by the GPU runs)
+        self.rows = args[1].shape[0], (0 if args[3] is None else args[3].shape[0])
+        self.states, self.fail = cpu_states(args, "reference")
+        self.clean = self.fail is None
+        last = DGA_ITERS - 1 if self.clean else self.fail[0] - 1
+        self.horizon, same_raise = last, True
+        for order in ("blocked", "device"):
+            other, other_fail = cpu_states(args, order)
+            agree = -1
+            while agree < last and agree + 1 in other and _same_state(self.states[agree + 1], other[agree + 1]):
+                agree += 1
+            self.horizon = min(self.horizon, agree)
+            same_raise = same_raise and other_fail == self.fail
+        self.device_states, self.device_fail = other, other_fail
+        self.status_ok = not self.clean and same_raise and self.horizon == last
+
+    def stops(self):
+        """The iterations the device is compared at: 0, 9 and the last of 40 inside the horizon, and the horizon itself."""
+        return sorted({s for s in DGA_STOPS if s <= self.horizon} | ({self.horizon} if self.horizon >= 0 else set()))
+
+    def late_stops(self):
+        """The stops behind the horizon that the ``"device"`` order completes: compared with ``device_states``."""
+        return [s for s in DGA_STOPS if s > self.horizon and s in self.device_states]
+
+    def linprog(self):
+        if self._opt is None:
+            c, a_eq, b_eq, a_ineq, b_upper, lb, ub = self.args
+            self._opt = scipy.optimize.linprog(c, A_ub=a_ineq, b_ub=b_upper, A_eq=a_eq if a_eq.shape[0] else None,
+                                               b_eq=b_eq if a_eq.shape[0] else None, bounds=np.column_stack((lb, ub)), method="highs")
+        return self._opt
+
+    def bound_slack(self, y_eq, y_ineq):
+        """The rounding of the device's dual energy: gamma_(n + m + 2) (sum |c_bar_j| max(|lb_j|, |ub_j|) + sum |y_i b_i|)."""
+        c, a_eq, b_eq, a_ineq, b_upper, lb, ub = self.args
+        c_bar, _ = dual_argmin(c, a_eq, a_ineq, lb, ub, y_eq, y_ineq)
+        k = c.size + sum(self.rows) + 2
+        gamma = k * 2.0 ** -53 / (1 - k * 2.0 ** -53)
+        terms = np.sum(np.abs(c_bar) * np.maximum(np.abs(lb), np.abs(ub))) + np.sum(np.abs(y_eq * b_eq))
+        if a_ineq is not None:
+            terms += np.sum(np.abs(y_ineq * b_upper))
+        return gamma * terms
+
+
+_POOLS = {}
+
+
+def dga_pool(cases, seed):
+    """``cases`` batches of the dual-ascent families, alternately integer- and decimal-valued: ``[[DgaLP, ...], ...]``, the LPs of
+    one batch over one matrix and one right-hand side.  Instance 0 is the LP as drawn, instance 1 has exact zeros among its
+    costs, the others perturb the costs and, by coin flip, widen the bounds (integers stay integers).  Cases 0 .. 9 have the
+    edge sizes in turn, ``large_case`` has ``DGA_TILE_EDGE`` instances.  ``run_dga``, ``run_dga_batch`` and ``run_dga_many`` share the pool and its references."""
+    key = (cases, seed)
+    if key not in _POOLS:
+        rng = np.random.RandomState(seed + 3000)
+        sizes = batch_sizes(rng, cases, DGA_TILE_EDGE)
+        pool = []
+        for case, batch in enumerate(sizes):
+            kind = ("integer", "decimal")[case % 2]
+            args = _integer_dga_args(rng, edge_n(case)) if kind == "integer" else _decimal_dga_args(rng, edge_n(case))
+            pool.append([DgaLP(a, kind, f"seed {seed} case {case} ({kind}) instance {k}")
+                         for k, a in enumerate(perturbed(rng, args, kind, batch))])
+        _POOLS[key] = pool
+    return _POOLS[key]
+
+
+def perturbed(rng, args, kind, batch):
+    """``batch`` LPs over the matrix and right-hand sides of ``args``: see ``dga_pool``."""
+    c, lb, ub = args[0], args[5], args[6]
+    n = c.size
+    out = [args]
+    for k in range(1, batch):
+        if kind == "integer":
+            ck = c + np.round((1 if np.max(np.abs(args[1].data), initial=0) <= 1 and np.max(np.abs(c)) < 10 else 3) * rng.randn(n))
+            widen = (lambda: rng.randint(0, 3, size=n).astype(np.float64))
+        else:
+            ck = c * (1 + 0.2 * rng.randn(n)) + 0.05 * rng.randn(n)
+            widen = (lambda: 0.1 * rng.rand(n))
+        if k == 1:
+            ck[::3] = 0.0
+        lbk, ubk = lb, ub
+        if rng.rand() < 0.5:
+            lbk, ubk = lb - widen(), ub + widen()
+        out.append((ck,) + tuple(args[1:5]) + (lbk, ubk))
+    return out
+
+
+def dga_lists(cases, seed):
+    """``[[DgaLP, ...], ...]``: ``cases`` lists of 1 to 9 LPs of different shapes drawn from the pool; ``large_case`` is cycled to
+    ``LONG_LIST`` entries."""
+    pool = dga_pool(cases, seed)
+    rng = np.random.RandomState(seed + 4000)
+    lists = []
+    for case in range(cases):
+        picks = rng.choice(len(pool), size=min(len(pool), int(rng.randint(1, 10))), replace=False)
+        lps = [pool[p][int(rng.randint(0, len(pool[p])))] for p in picks]
+        if case == large_case(cases):
+            lps = [lps[k % len(lps)] for k in range(LONG_LIST)]
+        lists.append(lps)
+    return lists
+
+
+def dga_statistics(cases, seed):
+    """Per value kind ``dict(drawn, clean, no_crossing, empty, negative, comparable_raises, short_horizon, min_horizon, late)`` over all
+    the LPs of the pool -- what tests/test_fuzz_batched_host.py asserts on."""
+    out = {}
+    for kind in ("integer", "decimal"):
+        lps = [lp for batch in dga_pool(cases, seed) for lp in batch if lp.kind == kind]
+        names = [lp.fail[1] for lp in lps if lp.fail is not None]
+        clean = [lp for lp in lps if lp.clean]
+        out[kind] = dict(drawn=len(lps), clean=len(clean), no_crossing=names.count("never changes sign"),
+                         empty=names.count("empty breakpoint set"), negative=names.count("negative step"),
+                         comparable_raises=sum(lp.status_ok for lp in lps),
+                         short_horizon=sum(lp.horizon < 10 for lp in clean), min_horizon=min([lp.horizon for lp in clean], default=-1),
+                         late=sum(len(lp.late_stops()) for lp in lps))
+    return out
+
+
+# ---- the GPU runs: helpers -----------------------------------------------------------------------------------------------------------
+
+@contextlib.contextmanager
+def environment(**values):
+    """The switches the library reads when a state is created; None unsets."""
+    saved = {name: os.environ.get(name) for name in values}
+    try:
+        for name, v in values.items():
+            if v is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = str(v)
+        yield
+    finally:
+        for name, v in saved.items():
+            if v is None:
+                os.environ.pop(name, None)
+            else:
+                os.environ[name] = v
+
+
+def _require(ok, where, layer=None):
+    """``layer()`` -- does the single solver agree with the CPU reference on that LP? -- runs only on a mismatch."""
+    if not ok:
+        raise AssertionError(where + ("" if layer is None else "; " + layer()))
+
+
+def _pieces(k):
+    """``k`` iterations as calls of uneven size."""
+    out = []
+    for p in (1, 3, 7):
+        if k > p:
+            out.append(p)
+            k -= p
+    return out + ([k] if k > 0 else [])
+
+
+class _Reports:
+    """The callback calls of a solver (copies)."""
+
+    def __init__(self):
+        self.it, self.x, self.e1, self.e2, self.veq, self.vineq = [], [], [], [], [], []
+
+    def __call__(self, niter, sol, e1, e2, dur, veq, vineq):
+        self.it.append(niter)
+        self.x.append([np.array(v, copy=True) for v in sol] if isinstance(sol, list) else np.array(sol, copy=True))
+        for store, v in ((self.e1, e1), (self.e2, e2), (self.veq, veq), (self.vineq, vineq)):
+            store.append(np.array(v, dtype=np.float64, copy=True))
+
+
+def _compare_reports(got, k, ref, where, layer, vineq=True):
+    """Instance / LP ``k`` of the batched reports ``got`` against the reference's ``ref``: x and the maxima bit for bit, the
+    energies within ``ENERGY_TOL``."""
+    _require(got.it == ref.it, f"{where}: reports at {got.it}, the reference's at {ref.it}")
+    for i, it in enumerate(ref.it):
+        at = f"{where}, report at iteration {it}"
+        _require(np.array_equal(got.x[i][k], ref.x[i]), at + ": x differs", layer)
+        _require(got.veq[i][k] == ref.veq[i], at + f": max violated equality {got.veq[i][k]!r} != {ref.veq[i]!r}", layer)
+        if vineq:
+            _require(got.vineq[i][k] == ref.vineq[i], at + f": max violated inequality {got.vineq[i][k]!r} != {ref.vineq[i]!r}", layer)
+        for name, g, r in (("energy1", got.e1[i][k], ref.e1[i]), ("energy2", got.e2[i][k], ref.e2[i])):
+            _require(np.allclose(g, r, equal_nan=True, **ENERGY_TOL), at + f": {name} {g!r} != {r!r}", layer)
+
+
+# ---- Chambolle-Pock ------------------------------------------------------------------------------------------------------------------
+
+def cp_reference(problem, x0, its, plot):
+    """``oracle.chambolle_pock_ppd`` on one LP: ``(reports, x, y at the last report point, equalities only?)`` -- y is ``[y_eq;
+    y_ineq]`` as the last iteration's report would see it.  An LP without inequality rows gets the inert all-zero row with a
+    positive bound of tests/test_gpu_edge_cases.py::test_cp_equalities_only_runs_and_reports (the oracle needs the block)."""
+    from oracle import oracle
+
+    c, a_eq, beq, a_ineq, bl, bu, lb, ub = problem
+    n = c.size
+    eq_only = a_ineq is None
+    if eq_only:
+        a_ineq, bl, bu = scipy.sparse.csr_matrix((1, n)), None, np.ones(1)
+    if a_eq is None:
+        a_eq, beq = scipy.sparse.csr_matrix((0, n)), np.zeros(0)
+    rec, last = _Reports(), {}
+
+    def hook(niter, x, y_eq, y_ineq):
+        if niter == its - 1:
+            last["y"] = np.concatenate((np.zeros(0) if y_eq is None else y_eq, np.zeros(0) if (eq_only or y_ineq is None) else y_ineq))
+            last["x"] = x.copy()
+
+    x, _ = oracle.chambolle_pock_ppd(c, a_eq, beq, a_ineq, bl, bu, lb, ub, x0=x0, nb_max_iter=its, nb_iter_plot=plot, callback_func=rec,
+                                     iterate_hook=hook)
+    assert np.array_equal(x, last["x"])
+    return rec, x, last["y"], eq_only
+
+
+def _cp_single_agrees(problem, x0, its, x_ref):
+    def layer():
+        from pysparselp_amd import ORDER_SEQUENTIAL
+        from pysparselp_amd.ChambollePockPPD import chambolle_pock_ppd
+
+        c, a_eq, beq, a_ineq, bl, bu, lb, ub = problem
+        if a_ineq is None:
+            a_ineq, bu = scipy.sparse.csr_matrix((0, c.size)), np.zeros(0)
+        if a_eq is None:
+            a_eq, beq = scipy.sparse.csr_matrix((0, c.size)), np.zeros(0)
+        x, _ = chambolle_pock_ppd(c, a_eq, beq, a_ineq, bl, bu, lb, ub, x0=x0, nb_max_iter=its, nb_iter_plot=10 ** 9, order=ORDER_SEQUENTIAL)
+        return "chambolle_pock_ppd in ORDER_SEQUENTIAL on this LP alone " + ("AGREES" if np.array_equal(x, x_ref) else "DISAGREES") \
+            + " with the oracle"
+    return layer
+
+
+def _state_at_last_report(state, its):
+    """x and y of a Chambolle-Pock state as the report of iteration ``its - 1`` sees them, reached in uneven calls."""
+    for p in _pieces(its - 1):
+        state.iterate(p)
+    state.primal_step()
+    return state.x(), state.y()
+
+
+def run_cp_batch(cases, seed):
+    """``chambolle_pock_ppd_batch`` and ``CPBatchState``: every instance against the oracle.  Returns counts."""
+    from pysparselp_amd import CPBatchState, chambolle_pock_ppd_batch
+    from pysparselp_amd.ChambollePockPPD import one_sided_system_batch
+
+    counts = dict(batches=0, instances=0, reports=0, equalities_only=0)
+    for case, (args, its, plot) in enumerate(cp_batch_cases(cases, seed)):
+        batch = args["c"].shape[0]
+        rec = _Reports()
+        x, _ = chambolle_pock_ppd_batch(args["c"], args["a_eq"], args["beq"], args["a_ineq"], args["b_lower"], args["b_upper"], args["lb"],
+                                        args["ub"], x0=args["x0"], nb_max_iter=its, nb_iter_plot=plot, callback_func=rec)
+        ineq, b_ineq = (None, None) if args["a_ineq"] is None else one_sided_system_batch(args["a_ineq"], args["b_lower"], args["b_upper"])
+        state = CPBatchState(args["c"], args["a_eq"], args["beq"], ineq, b_ineq, args["lb"], args["ub"], args["x0"], 1, 1)
+        try:
+            xs, ys = _state_at_last_report(state, its)
+        finally:
+            state.close()
+        for k in range(batch):
+            problem, x0 = of_instance(args, k)
+            ref, x_ref, y_ref, eq_only = cp_reference(problem, x0, its, plot)
+            where = f"cp_batch seed {seed} case {case} instance {k} of {batch} (n {x_ref.size}, {its} iterations, cadence {plot})"
+            layer = _cp_single_agrees(problem, x0, its, x_ref)
+            _require(np.array_equal(x[k], x_ref), where + ": the returned x differs", layer)
+            _compare_reports(rec, k, ref, where, layer, vineq=not eq_only)
+            if eq_only:
+                _require(all(v[k] == 0 for v in rec.vineq), where + ": a violated inequality without inequality rows")
+            _require(np.array_equal(xs[k], x_ref), where + ": x of the state differs", layer)
+            _require(np.array_equal(ys[k], y_ref), where + ": y differs", layer)
+            counts["instances"] += 1
+            counts["reports"] += len(ref.it)
+            counts["equalities_only"] += eq_only
+        counts["batches"] += 1
+    return counts
+
+
+CP_MANY_SETTINGS = (("default", None, None), ("lds", "lds", None), ("global", "global", None), ("kmax1", None, 1))
+
+
+def run_cp_many(cases, seed):
+    """``chambolle_pock_ppd_many`` and ``CPManyState``: every LP of every list against the oracle, with the form chosen by the
+    library, forced to ``lds`` and to ``global``, and with one iteration per launch.  Returns counts."""
+    from pysparselp_amd import CPManyState, chambolle_pock_ppd_many
+    from pysparselp_amd.ChambollePockPPD import _many_problem
+
+    counts = dict(lists=0, lps=0, runs=0, equalities_only=0, longest=0)
+    for case, (lps, its, plot) in enumerate(cp_many_cases(cases, seed)):
+        problems = [of_instance(lp, 0)[0] for lp in lps]
+        x0 = [lp["x0"] for lp in lps]
+        refs = {}
+        for k, lp in enumerate(lps):   # a cycled list repeats its LPs: one reference each
+            if id(lp) not in refs:
+                refs[id(lp)] = cp_reference(problems[k], x0[k], its, plot)
+        for name, form, kmax in CP_MANY_SETTINGS:
+            with environment(SLP_CP_MANY_FORM=form, SLP_CP_MANY_KMAX=kmax):
+                rec = _Reports()
+                xs, _ = chambolle_pock_ppd_many(problems, x0=x0, nb_max_iter=its, nb_iter_plot=plot, callback_func=rec)
+                state = CPManyState([_many_problem(k, p) for k, p in enumerate(problems)], x0)
+                try:
+                    forms = [state.form(k) for k in range(state.count)]
+                    sx, sy = _state_at_last_report(state, its)
+                finally:
+                    state.close()
+            _require(form is None or set(forms) == {form}, f"cp_many seed {seed} case {case}: forms {set(forms)} under SLP_CP_MANY_FORM={form}")
+            for k, lp in enumerate(lps):
+                ref, x_ref, y_ref, eq_only = refs[id(lp)]
+                where = (f"cp_many seed {seed} case {case} LP {k} of {len(lps)} (n {x_ref.size}, {its} iterations, cadence {plot}), "
+                         f"setting {name}, form {forms[k]}")
+                layer = _cp_single_agrees(problems[k], x0[k], its, x_ref)
+                _require(np.array_equal(xs[k], x_ref), where + ": the returned x differs", layer)
+                _compare_reports(rec, k, ref, where, layer, vineq=not eq_only)
+                if eq_only:
+                    _require(all(v[k] == 0 for v in rec.vineq), where + ": a violated inequality without inequality rows")
+                _require(np.array_equal(sx[k], x_ref), where + ": x of the state differs", layer)
+                _require(np.array_equal(sy[k], y_ref), where + ": y differs", layer)
+            counts["runs"] += 1
+        counts["lists"] += 1
+        counts["lps"] += len(refs)
+        counts["equalities_only"] += sum(r[3] for r in refs.values())
+        counts["longest"] = max(counts["longest"], len(lps))
+    return counts
+
+
+# ---- ADMM ------------------------------------------------------------------------------------------------------------------------------
+
+def admm_reference(problem, x0, its, plot):
+    """``oracle.lp_admm`` on one LP: ``(reports, x, lambda as the report of iteration its sees it)``."""
+    from oracle import oracle
+
+    rec, last = _Reports(), {}
+
+    def hook(i, x, x_all, lambda_eq):
+        if i == its:
+            last["lam"], last["x"] = lambda_eq.copy(), x.copy()
+
+    x = oracle.lp_admm(*problem, x0=x0, nb_iter=its, nb_iter_plot=plot, callback_func=rec, iterate_hook=hook)
+    assert np.array_equal(x, last["x"])
+    return rec, x, last["lam"]
+
+
+def _admm_single_agrees(problem, x0, its, x_ref):
+    def layer():
+        from pysparselp_amd import ORDER_SEQUENTIAL
+        from pysparselp_amd.ADMM import lp_admm
+
+        x = lp_admm(*problem, x0=x0, nb_iter=its, nb_iter_plot=10 ** 9, order=ORDER_SEQUENTIAL)
+        return "lp_admm in ORDER_SEQUENTIAL on this LP alone " + ("AGREES" if np.array_equal(x, x_ref) else "DISAGREES") + " with the oracle"
+    return layer
+
+
+def run_admm_batch(cases, seed):
+    """``lp_admm_batch`` and ``ADMMBatchState`` in both forms of the iteration: every instance against the oracle.  Returns counts."""
+    from pysparselp_amd import ADMMBatchState, lp_admm_batch
+
+    counts = dict(batches=0, instances=0, reports=0)
+    for case, (args, its, plot) in enumerate(admm_batch_cases(cases, seed)):
+        batch, n = args["c"].shape
+        refs = [admm_reference(*of_instance(args, k), its, plot) for k in range(batch)]
+        for form in ("tile", "levels"):
+            with environment(SLP_ADMM_BATCH_FORM=form):
+                rec = _Reports()
+                x = lp_admm_batch(args["c"], args["a_eq"], args["beq"], args["a_ineq"], args["b_lower"], args["b_upper"], args["lb"],
+                                  args["ub"], x0=args["x0"], nb_iter=its, nb_iter_plot=plot, callback_func=rec)
+                state = ADMMBatchState(args["c"], args["a_eq"], args["beq"], args["a_ineq"], args["b_lower"], args["b_upper"], args["lb"],
+                                       args["ub"], args["x0"])
+                try:
+                    _require(state.form() == form, f"admm_batch seed {seed} case {case}: form {state.form()} under {form}")
+                    for p in _pieces(its):
+                        state.iterate(p)
+                    state.sweep_step()
+                    xs, lam = state.x(n), state.lam()
+                finally:
+                    state.close()
+            for k in range(batch):
+                ref, x_ref, lam_ref = refs[k]
+                problem, x0 = of_instance(args, k)
+                where = f"admm_batch seed {seed} case {case} instance {k} of {batch} (n {n}, {its} iterations, cadence {plot}), form {form}"
+                layer = _admm_single_agrees(problem, x0, its, x_ref)
+                _require(np.array_equal(x[k], x_ref), where + ": the returned x differs", layer)
+                _compare_reports(rec, k, ref, where, layer)
+                _require(np.array_equal(xs[k], x_ref), where + ": x of the state differs", layer)
+                _require(np.array_equal(lam[k], lam_ref), where + ": lambda differs", layer)
+        counts["batches"] += 1
+        counts["instances"] += batch
+        counts["reports"] += sum(len(r[0].it) for r in refs)
+    return counts
+
+
+# ---- dual gradient ascent on the device -------------------------------------------------------------------------------------------------
+
+class _LP:
+    """The attributes ``dual_gradient_ascent_many`` reads."""
+
+    def __init__(self, c, a_eq, b_eq, a_ineq, b_upper, lb, ub):
+        self.costsvector, self.a_equalities, self.b_equalities = c, a_eq, b_eq
+        self.a_inequalities, self.b_upper, self.b_lower = a_ineq, b_upper, None
+        self.lower_bounds, self.upper_bounds = lb, ub
+
+
+def _start(lp):
+    """The reference's start (seed 0) for the LP's shape and the generator its tie draws continue."""
+    m_eq, m_in = lp.rows
+    rs = np.random.RandomState(0)
+    y_eq = -rs.rand(m_eq)
+    y_ineq = np.abs(rs.rand(m_in)) if lp.args[3] is not None else np.zeros(0)
+    return np.concatenate((y_eq, y_ineq)), rs
+
+
+def _rhs(lp):
+    return np.concatenate((lp.args[2], lp.args[4] if lp.args[3] is not None else np.zeros(0)))
+
+
+@contextlib.contextmanager
+def single_state(lp, path):
+    from pysparselp_amd.DualGradientAscent import DeviceDGA
+    from pysparselp_amd.device import DeviceMatrix
+
+    c, a_eq, _, a_ineq, _, lb, ub = lp.args
+    y0, rs = _start(lp)
+    mat = DeviceMatrix.from_blocks(a_eq, a_ineq, c.size)
+    state = None
+    try:
+        state = DeviceDGA(mat, _rhs(lp), c, lb, ub, y0, m_eq=a_eq.shape[0], draws=rs.random_sample, path=path)
+        _require(state.path() == path, f"{lp.name}: path {state.path()} under {path}")
+        yield state
+    finally:
+        if state is not None:
+            state.close()
+        mat.close()
+
+
+@contextlib.contextmanager
+def batch_state(lps, path):
+    """``DeviceDGABatch`` over LPs that share the matrix and the right-hand sides; ``path``: ``fused``, ``general-segmented`` or
+    ``general-global``."""
+    from pysparselp_amd.DualGradientAscent import DeviceDGABatch
+    from pysparselp_amd.device import DeviceMatrix
+
+    c, a_eq, _, a_ineq, _, _, _ = lps[0].args
+    y0, rs = _start(lps[0])
+    path, _, sort = path.partition("-")
+    mat = DeviceMatrix.from_blocks(a_eq, a_ineq, c.size)
+    state = None
+    try:
+        with environment(SLP_DGA_BATCH_SORT=sort or None):
+            state = DeviceDGABatch(mat, _rhs(lps[0]), np.array([lp.args[0] for lp in lps]), np.array([lp.args[5] for lp in lps]),
+                                   np.array([lp.args[6] for lp in lps]), y0, m_eq=a_eq.shape[0], draws=rs.random_sample, path=path)
+        _require((state.path(), state.sort()) == (path, sort or None), f"{lps[0].name}: path {state.path()}, sort {state.sort()}")
+        yield state
+    finally:
+        if state is not None:
+            state.close()
+        mat.close()
+
+
+@contextlib.contextmanager
+def many_state(lps, kmax=None):
+    from pysparselp_amd.DualGradientAscent import DeviceDGAMany, _dga_many_lp, dga_many_start
+
+    forms = [_dga_many_lp(k, _LP(*lp.args)) for k, lp in enumerate(lps)]
+    y0s, offsets = dga_many_start(forms)
+    with environment(SLP_DGA_MANY_KMAX=kmax):
+        state = DeviceDGAMany(forms, y0s, offsets)
+    try:
+        yield state
+    finally:
+        state.close()
+
+
+def _snapshot(state, single=False):
+    """``(x, y_eq, y_ineq, draws, flags)``, each indexed by instance / LP (a single state: as a list of one)."""
+    flags, draws, _, _ = state.status()
+    y_eq, y_ineq = state.y()
+    if single:
+        return [state.x()], [y_eq], [y_ineq], [draws], [flags]
+    return state.x(), y_eq, y_ineq, draws, flags
+
+
+def _walk(state, stops, single=False):
+    """``{stop: snapshot}`` after ``stop + 1`` iterations, the iterations split over calls of uneven size."""
+    out, done = {}, 0
+    for s in stops:
+        for p in _pieces(s + 1 - done):
+            state.iterate(p)
+        done = s + 1
+        out[s] = _snapshot(state, single)
+    return out
+
+
+def _instance_equals(snap, k, ref):
+    """Which of x, y_eq, y_ineq, draws of instance ``k`` differ from ``ref = (x, y_eq, y_ineq, draws)``: a list of names."""
+    x, y_eq, y_ineq, draws, _ = snap
+    want_ineq = ref[2] if ref[2] is not None else np.zeros(0)
+    pairs = (("x", x[k], ref[0]), ("y_eq", y_eq[k], ref[1]), ("y_ineq", y_ineq[k], want_ineq))
+    return [name for name, g, r in pairs if not np.array_equal(g, r)] + ([] if int(draws[k]) == ref[3] else ["draws"])
+
+
+def single_result(lp, path):
+    """The single solver on the LP alone, cached per path: ``dict(snaps={stop: snapshot}, report)`` at the LP's stops and after
+    all ``DGA_ITERS`` iterations."""
+    if path not in lp.single:
+        stops = sorted(set(lp.stops()) | set(DGA_STOPS))
+        with single_state(lp, path) as state:
+            snaps = _walk(state, stops, single=True)
+            lp.single[path] = dict(snaps=snaps, report=state.report())
+    return lp.single[path]
+
+
+def _dga_single_agrees(lp, path):
+    def layer():
+        got = single_result(lp, path)
+        bad = [s for s, ref in _references(lp) if got["snaps"][s][4][0] != 0 or _instance_equals(got["snaps"][s], 0, ref)]
+        return f"DeviceDGA ({path}) on this LP alone " + ("AGREES with dga_cpu" if not bad else f"DISAGREES with dga_cpu at {bad}")
+    return layer
+
+
+def _references(lp):
+    """``[(stop, (x, y_eq, y_ineq, draws))]``: the reference's order up to the horizon, the ``"device"`` order behind it."""
+    return [(s, lp.states[s]) for s in lp.stops()] + [(s, lp.device_states[s]) for s in lp.late_stops()]
+
+
+def _compare_with_cpu(snaps, k, lp, where, layer):
+    """Instance ``k`` of the walk against dga_cpu at the LP's stops: flags 0, x, y and draws bit for bit.  Returns comparisons made."""
+    for s, ref in _references(lp):
+        snap = snaps[s]
+        order = "the reference's order" if s <= lp.horizon else "the device's order (behind the horizon)"
+        at = f"{where}, after {s + 1} iterations (horizon {lp.horizon})"
+        _require(int(snap[4][k]) == 0, at + f": status flags {int(snap[4][k])}", layer)
+        bad = _instance_equals(snap, k, ref)
+        _require(not bad, at + f": {', '.join(bad)} differ from dga_cpu in {order}", layer)
+    return len(_references(lp))
+
+
+def _compare_with_single(snap, report, k, lp, path, where):
+    """Instance ``k`` after all iterations against the single solver on it alone, the report's row included."""
+    one = single_result(lp, path)
+    last = one["snaps"][DGA_ITERS - 1]
+    at = f"{where}, after {DGA_ITERS} iterations against DeviceDGA ({path}) alone"
+    _require(int(snap[4][k]) == int(last[4][0]), at + f": status flags {int(snap[4][k])} != {int(last[4][0])}")
+    if int(last[4][0]) == 0:
+        bad = _instance_equals(snap, k, (last[0][0], last[1][0], last[2][0], int(last[3][0])))
+        _require(not bad, at + f": {', '.join(bad)} differ")
+        _require(tuple(float(v) for v in report[k]) == one["report"], at + f": report {tuple(report[k])} != {one['report']}")
+
+
+def _check_bound(counts, lp, flags, energy, y_eq, y_ineq, where):
+    """The certified lower bound against HiGHS: a clean LP's dual energy does not exceed its optimum by more than its rounding.
+    An LP that the device flags has no bound to check; where dga_cpu in the device's order runs clean that is a mismatch, else
+    it is counted as skipped."""
+    if not lp.clean:
+        return
+    if int(flags) != 0:
+        _require(lp.device_fail is not None, f"{where}: status flags {int(flags)} after {DGA_ITERS} iterations, dga_cpu runs clean in the device's order")
+        counts["bounds_skipped"] += 1
+        return
+    res = lp.linprog()
+    _require(res.status == 0, f"{where}: linprog status {res.status} ({res.message})")
+    slack = lp.bound_slack(y_eq, y_ineq)
+    _require(energy <= res.fun + slack, f"{where}: the dual bound {energy!r} exceeds the optimum {res.fun!r} by more than {slack!r}")
+    counts["bounds"] += 1
+
+
+def _status_step(state, lp, k, check_text, where, neighbours=(), single=False):
+    """The raise of dga_cpu in iteration ``t`` on instance ``k``: after ``t`` iterations no flag anywhere and the references'
+    iterates, after one more exactly the bit on ``k``, ``check()`` names it, the neighbours unharmed at ``t + 1``."""
+    t, name = lp.fail
+    bit = STATUS_BITS[name]
+    everyone = [(k, lp)] + list(neighbours)
+    if t > 0:
+        for p in _pieces(t):
+            state.iterate(p)
+        snap = _snapshot(state, single)
+        for i, other in everyone:
+            _require(int(snap[4][i]) == 0, f"{where}: flags {int(snap[4][i])} on {i} after {t} iterations, before the raise")
+            bad = _instance_equals(snap, i, other.states[t - 1])
+            _require(not bad, f"{where}: {', '.join(bad)} of {i} differ from dga_cpu after {t} iterations, before the raise")
+    state.iterate(1)
+    snap = _snapshot(state, single)
+    _require(int(snap[4][k]) == bit, f"{where}: flags {int(snap[4][k])} after iteration {t}, dga_cpu raises '{name}' (bit {bit}) there")
+    try:
+        state.check()
+        raised = None
+    except (ValueError, AssertionError) as e:
+        raised = str(e)
+    _require(raised is not None and name in raised and check_text in raised, f"{where}: check() gave {raised!r}, expected '{name}' {check_text}")
+    for i, other in neighbours:
+        _require(int(snap[4][i]) == 0, f"{where}: flags {int(snap[4][i])} on the clean neighbour {i} after iteration {t}")
+        bad = _instance_equals(snap, i, other.states[t])
+        _require(not bad, f"{where}: {', '.join(bad)} of the clean neighbour {i} differ from dga_cpu after {t + 1} iterations")
+
+
+SINGLE_PATHS = ("fused", "general")
+BATCH_PATHS = ("fused", "general-segmented", "general-global")
+
+
+def run_dga(cases, seed):
+    """``DeviceDGA`` on both search paths: instance 0 of every batch of the pool and every LP on which dga_cpu raises, against
+    dga_cpu; status bits; the dual bound against HiGHS.  Returns counts."""
+    counts = dict(lps=0, comparisons=0, raises=0, bounds=0, bounds_skipped=0)
+    for batch in dga_pool(cases, seed):
+        chosen = [batch[0]] + [lp for lp in batch[1:] if lp.status_ok][:2]
+        for lp in chosen:
+            for path in SINGLE_PATHS:
+                where = f"dga {lp.name}, path {path}"
+                got = single_result(lp, path)
+                counts["comparisons"] += _compare_with_cpu(got["snaps"], 0, lp, where, None)
+                last = got["snaps"][DGA_ITERS - 1]
+                _check_bound(counts, lp, last[4][0], got["report"][0], last[1][0], last[2][0], where)
+                if lp.status_ok:
+                    with single_state(lp, path) as state:
+                        _status_step(state, lp, 0, "", where, single=True)
+                    counts["raises"] += 1
+            counts["lps"] += 1
+    return counts
+
+
+def run_dga_batch(cases, seed):
+    """``DeviceDGABatch`` on its three paths: every instance against dga_cpu and against ``DeviceDGA`` alone (report rows
+    included); a raising cost between two clean instances of its batch; the dual bound.  Returns counts."""
+    counts = dict(batches=0, instances=0, comparisons=0, raises=0, raises_without_neighbours=0, bounds=0, bounds_skipped=0)
+    for case, batch in enumerate(dga_pool(cases, seed)):
+        stops = sorted({s for lp in batch for s in lp.stops()} | set(DGA_STOPS))
+        for path in BATCH_PATHS:
+            one = path.partition("-")[0]
+            with batch_state(batch, path) as state:
+                snaps = _walk(state, stops)
+                report = state.report()
+            for k, lp in enumerate(batch):
+                where = f"dga_batch {lp.name} of {len(batch)}, path {path}"
+                counts["comparisons"] += _compare_with_cpu(snaps, k, lp, where, _dga_single_agrees(lp, one))
+                last = snaps[DGA_ITERS - 1]
+                _compare_with_single(last, report, k, lp, one, where)
+                _check_bound(counts, lp, last[4][k], report[k, 0], last[1][k], last[2][k], where)
+        # a raising instance between two instances of its batch that are clean through the iteration of the raise
+        for k, lp in enumerate(batch):
+            if not lp.status_ok:
+                continue
+            t = lp.fail[0]
+            clean = [other for other in batch if other is not lp and other.clean and other.horizon >= t][:2]
+            trio, at, neighbours = [lp], 0, []
+            if len(clean) == 2:
+                trio, at, neighbours = [clean[0], lp, clean[1]], 1, [(0, clean[0]), (2, clean[1])]
+            else:
+                counts["raises_without_neighbours"] += 1
+            for path in BATCH_PATHS:
+                with batch_state(trio, path) as state:
+                    _status_step(state, lp, at, f"instances [{at}] of the batch", f"dga_batch status {lp.name}, path {path}", neighbours)
+            counts["raises"] += 1
+            break   # one per batch
+        counts["batches"] += 1
+        counts["instances"] += len(batch)
+    return counts
+
+
+def run_dga_many(cases, seed):
+    """``DeviceDGAMany`` with the launch length chosen by the library and with one iteration per launch: every LP of every list
+    against dga_cpu and against ``DeviceDGA`` alone (report rows included); a raising LP between two clean ones; the dual bound.
+    Returns counts."""
+    counts = dict(lists=0, lps=0, comparisons=0, raises=0, bounds=0, bounds_skipped=0, longest=0)
+    pool = dga_pool(cases, seed)
+    for case, lps in enumerate(dga_lists(cases, seed)):
+        stops = sorted({s for lp in lps for s in lp.stops()} | set(DGA_STOPS))
+        for setting, kmax in (("default", None), ("kmax1", 1)):
+            with many_state(lps, kmax) as state:
+                _require(kmax is None or state.kmax() == kmax, f"dga_many seed {seed} list {case}: kmax {state.kmax()} under {kmax}")
+                snaps = _walk(state, stops)
+                report = state.report()
+            for k, lp in enumerate(lps):
+                where = f"dga_many seed {seed} list {case} LP {k} of {len(lps)} ({lp.name}), setting {setting}"
+                counts["comparisons"] += _compare_with_cpu(snaps, k, lp, where, _dga_single_agrees(lp, "fused"))
+                last = snaps[DGA_ITERS - 1]
+                _compare_with_single(last, report, k, lp, "fused", where)
+                _check_bound(counts, lp, last[4][k], report[k, 0], last[1][k], last[2][k], where)
+        counts["lists"] += 1
+        counts["lps"] += len(lps)
+        counts["longest"] = max(counts["longest"], len(lps))
+    # every comparable raise of the pool's first instances between two clean LPs of other shapes
+    everyone = [lp for batch in pool for lp in batch[:3]]
+    for lp in everyone:
+        if not lp.status_ok:
+            continue
+        t = lp.fail[0]
+        clean = [other for other in everyone if other.clean and other.horizon >= t and other.args[1] is not lp.args[1]][:2]
+        _require(len(clean) == 2, f"dga_many status {lp.name}: the pool has no two clean LPs")
+        for setting, kmax in (("default", None), ("kmax1", 1)):
+            with many_state([clean[0], lp, clean[1]], kmax) as state:
+                _status_step(state, lp, 1, "LPs [1] of the list", f"dga_many status {lp.name}, setting {setting}", [(0, clean[0]), (2, clean[1])])
+        counts["raises"] += 1
+    return counts
+
+
+FAMILIES = {"cp_batch": run_cp_batch, "cp_many": run_cp_many, "admm_batch": run_admm_batch, "dga": run_dga, "dga_batch": run_dga_batch,
+            "dga_many": run_dga_many}
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--cases", type=int, default=TEST_CASES)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--family", default=",".join(FAMILIES))
+    args = p.parse_args()
+    failed = 0
+    for name in args.family.split(","):
+        try:
+            print("ok:", name, FAMILIES[name](args.cases, args.seed), flush=True)
+        except AssertionError as e:
+            failed += 1
+            print("MISMATCH:", name, e, flush=True)
+    sys.exit(3 if failed else 0)   # (1 is Python's own: an exception that is no mismatch)
+
+
+if __name__ == "__main__":
+    main()
