@@ -24,6 +24,7 @@ import time
 import numpy as np
 
 from . import _lib
+from ._batch import shared_or_batched
 from ._lib import ORDER_AUTO
 from .tools import convert_to_standard_form_with_bounds, normal_matrix, precondition_constraints
 
@@ -200,16 +201,6 @@ def lp_admm(
 
 # ---------------------------------------------------------------------------------------------------------------------
 # batched form: B LPs over one constraint structure
-def _shared_or_batched(name, v, batch, size):
-    """``v`` as float64, shape ``(size,)`` (shared by the instances) or ``(batch, size)``; returns ``(array, is_batched)``."""
-    v = np.asarray(v, dtype=np.float64)
-    if v.shape == (size,):
-        return np.ascontiguousarray(v), False
-    if v.shape == (batch, size):
-        return np.ascontiguousarray(v), True
-    raise ValueError(f"{name} has shape {v.shape}: expected ({size},) shared by the instances, or ({batch}, {size})")
-
-
 def _validate_batch(cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0):
     """Everything ``lp_admm_batch`` can refuse without a GPU; returns the arguments as contiguous float64 arrays / CSR triples."""
     from .tools import CsrArrays
@@ -254,13 +245,13 @@ def _validate_batch(cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0):
     if a_eq is not None and beq is None:
         raise ValueError("a_eq without beq")
     b_lower, b_upper = rhs("b_lower", b_lower, m_ineq), rhs("b_upper", b_upper, m_ineq)
-    lb, lb_b = _shared_or_batched("lb", lb, batch, n)
-    ub, ub_b = _shared_or_batched("ub", ub, batch, n)
+    lb, lb_b = shared_or_batched("lb", lb, batch, n)
+    ub, ub_b = shared_or_batched("ub", ub, batch, n)
     if np.any(np.isnan(lb)) or np.any(np.isnan(ub)):
         raise ValueError("lb / ub has a NaN")
     x0_b = False
     if x0 is not None:
-        x0, x0_b = _shared_or_batched("x0", x0, batch, n)
+        x0, x0_b = shared_or_batched("x0", x0, batch, n)
         if not np.all(np.isfinite(x0)):
             raise ValueError("x0 has an entry that is not finite")
     return np.ascontiguousarray(cs), a_eq, beq, a_ineq, b_lower, b_upper, lb, lb_b, ub, ub_b, x0, x0_b

@@ -20,6 +20,7 @@ import time
 import numpy as np
 
 from . import _lib
+from ._batch import box_vertex, concat, first_offsets, shared_or_batched, split_by
 from ._lib import ORDER_AUTO
 from .parallel import collective_elapsed
 
@@ -287,10 +288,7 @@ def chambolle_pock_ppd(
     if a_ineq is not None and a_ineq.shape[0] == 0:
         a_ineq = None
     if a_eq is None and a_ineq is None:  # reference :147-151: no constraints, a vertex of the box
-        x = np.zeros_like(lb)
-        x[c > 0] = lb[c > 0]
-        x[c < 0] = ub[c < 0]
-        return x
+        return box_vertex(c, lb, ub)
     for a in (a_eq, a_ineq):
         if a is not None:
             assert a.shape[1] == n
@@ -322,16 +320,6 @@ def chambolle_pock_ppd(
 
 # ---------------------------------------------------------------------------------------------------------------------
 # batched form: B LPs over one constraint structure
-def _batched(name, v, batch, size):
-    """``v`` as float64, shape ``(size,)`` (shared by the instances) or ``(batch, size)``; returns ``(array, is_batched)``."""
-    v = np.asarray(v, dtype=np.float64)
-    if v.shape == (size,):
-        return np.ascontiguousarray(v), False
-    if v.shape == (batch, size):
-        return np.ascontiguousarray(v), True
-    raise ValueError(f"{name} has shape {v.shape}: expected ({size},) shared by the instances, or ({batch}, {size})")
-
-
 def one_sided_system_batch(a_ineq, b_lower, b_upper):
     """``one_sided_system`` for right-hand sides that may carry a leading instance axis: the row selection (which bounds are
     finite, reference :74-88) must be the same for every instance -- ``ValueError`` otherwise --, the structure is that of
@@ -367,9 +355,9 @@ class CPBatchState:
         if c.ndim != 2 or c.shape[0] < 1:
             raise ValueError(f"c has shape {c.shape}: expected (B, n) with B >= 1")
         self.batch, self.n = c.shape
-        lb, lb_b = _batched("lb", lb, self.batch, self.n)
-        ub, ub_b = _batched("ub", ub, self.batch, self.n)
-        x0, x0_b = (None, False) if x0 is None else _batched("x0", x0, self.batch, self.n)
+        lb, lb_b = shared_or_batched("lb", lb, self.batch, self.n)
+        ub, ub_b = shared_or_batched("ub", ub, self.batch, self.n)
+        x0, x0_b = (None, False) if x0 is None else shared_or_batched("x0", x0, self.batch, self.n)
         parts_ptr, parts_idx, parts_val, parts_b = [np.zeros(1, dtype=np.int64)], [], [], []
         self.m_eq = 0
         if a_eq is not None:
@@ -378,7 +366,7 @@ class CPBatchState:
             parts_ptr.append(p[1:])
             parts_idx.append(j)
             parts_val.append(v)
-            parts_b.append(_batched("beq", beq, self.batch, self.m_eq))
+            parts_b.append(shared_or_batched("beq", beq, self.batch, self.m_eq))
         self.m_ineq = 0
         if ineq is not None:
             p, j, v, rows = ineq
@@ -387,7 +375,7 @@ class CPBatchState:
             parts_ptr.append(off + p[1:])
             parts_idx.append(j)
             parts_val.append(v)
-            parts_b.append(_batched("b_ineq", b_ineq, self.batch, rows))
+            parts_b.append(shared_or_batched("b_ineq", b_ineq, self.batch, rows))
         indptr = np.ascontiguousarray(np.concatenate(parts_ptr), dtype=np.int64)
         indices = np.ascontiguousarray(np.concatenate(parts_idx) if parts_idx else np.zeros(0), dtype=np.int32)
         data = _lib.f64(np.concatenate(parts_val) if parts_val else np.zeros(0))
@@ -449,42 +437,43 @@ class CPBatchState:
         return ms
 
 
-def _cp_batch_loop(state, c, has_ineq, nb_max_iter, nb_iter_plot, callback_func, max_time, start):
-    """``_cp_loop`` for a batched state: same cadence; the report's numbers are arrays of length B, ``max_time`` stops the whole
-    batch, the best feasible iterate (:284-291 with force_integer=False) is kept per instance."""
-    batch = c.shape[0]
-    best_energy = np.full(batch, np.inf)
-    best = [None] * batch
+def _cp_report_loop(state, costs, has_ineq, slots, best, all_x, spread, nb_max_iter, nb_iter_plot, callback_func, max_time, start):
+    """``_cp_loop`` for a batched or a list state: same cadence; the report's numbers are arrays with one entry per LP of the
+    state, ``max_time`` stops them all.  ``costs[i]`` and ``has_ineq[i]`` belong to the state's LP ``i``; its best feasible iterate
+    (:284-291 with force_integer=False) goes to ``best[slots[i]]``.  ``all_x`` and ``spread(values, energy=False)`` map the
+    state's iterates and numbers to what the callback sees: the identity for a batch, the whole list (LPs without rows
+    included) for a list.  Returns ``all_x`` of the final iterates."""
+    best_energy = np.full(len(slots), np.inf)
     niter = 0
     while niter < nb_max_iter:
         if niter % nb_iter_plot == 0:
             state.primal_step()
             elapsed = time.perf_counter() - start
-            if (max_time is not None) and collective_elapsed(elapsed) > max_time:
+            if (max_time is not None) and collective_elapsed(elapsed) > max_time:  # the same decision on every rank
                 break
             energy1, energy2, max_violated_equality, max_violated_inequality, max_eq_at_x = state.report().T.copy()
-            if not has_ineq:
-                max_violated_inequality = np.zeros(batch)
+            max_violated_inequality[~has_ineq] = 0  # the reference dereferences a_ineq here (:283) and fails
             x = None
             feasible = np.nonzero((max_eq_at_x == 0) & (max_violated_inequality <= 0))[0]
             if feasible.size:
                 x = state.x()
-                for k in feasible:
-                    energy_rounded = c[k].dot(x[k])
-                    if energy_rounded < best_energy[k]:
-                        best_energy[k] = energy_rounded
-                        best[k] = x[k].copy()
+                for i in feasible:
+                    energy_rounded = costs[i].dot(x[i])
+                    if energy_rounded < best_energy[i]:
+                        best_energy[i] = energy_rounded
+                        best[slots[i]] = x[i].copy()
             if callback_func is not None:
                 if x is None:
                     x = state.x()
-                callback_func(niter, x, energy1, energy2, elapsed, max_violated_equality, max_violated_inequality)
+                callback_func(niter, all_x(x), spread(energy1, True), spread(energy2, True), elapsed, spread(max_violated_equality),
+                              spread(max_violated_inequality))
             state.dual_step()
             niter += 1
         else:
             k = min(nb_iter_plot - niter % nb_iter_plot, nb_max_iter - niter)
             state.iterate(k)
             niter += k
-    return state.x(), best
+    return all_x(state.x())
 
 
 def chambolle_pock_ppd_batch(
@@ -529,10 +518,10 @@ def chambolle_pock_ppd_batch(
     if batch < 1:
         raise ValueError("an empty batch: c needs at least one row (B >= 1)")
     c = np.ascontiguousarray(c)
-    lb, _ = _batched("lb", lb, batch, n)
-    ub, _ = _batched("ub", ub, batch, n)
+    lb, _ = shared_or_batched("lb", lb, batch, n)
+    ub, _ = shared_or_batched("ub", ub, batch, n)
     if x0 is not None:
-        x0, _ = _batched("x0", x0, batch, n)
+        x0, _ = shared_or_batched("x0", x0, batch, n)
     if a_eq is not None and a_eq.shape[0] == 0:  # reference :70-72
         a_eq, beq = None, None
     if a_ineq is not None and a_ineq.shape[0] == 0:
@@ -544,25 +533,23 @@ def chambolle_pock_ppd_batch(
             if a.indices.size and (a.indices.min() < 0 or a.indices.max() >= n):
                 raise ValueError(f"{name} has a column index outside [0, {n})")
     if a_eq is not None:
-        beq, _ = _batched("beq", beq, batch, a_eq.shape[0])
+        beq, _ = shared_or_batched("beq", beq, batch, a_eq.shape[0])
     if a_eq is None and a_ineq is None:  # reference :147-151: no constraints, a vertex of the box per instance
-        lbb, ubb = np.broadcast_to(lb, c.shape), np.broadcast_to(ub, c.shape)
-        x = np.zeros(c.shape)
-        x[c > 0] = lbb[c > 0]
-        x[c < 0] = ubb[c < 0]
-        return x
+        return box_vertex(c, lb, ub)
     ineq, b_ineq = (None, None)
     if a_ineq is not None:
         rows = a_ineq.shape[0]
-        b_upper, _ = _batched("b_upper", b_upper, batch, rows)
+        b_upper, _ = shared_or_batched("b_upper", b_upper, batch, rows)
         if b_lower is not None:
-            b_lower, _ = _batched("b_lower", b_lower, batch, rows)
+            b_lower, _ = shared_or_batched("b_lower", b_lower, batch, rows)
         ineq, b_ineq = one_sided_system_batch(a_ineq, b_lower, b_upper)
         assert b_ineq.shape[-1] == ineq[3]
 
     state = CPBatchState(c, a_eq, beq, ineq, b_ineq, lb, ub, x0, alpha, theta)
+    best = [None] * batch
     try:
-        x, best = _cp_batch_loop(state, c, a_ineq is not None, nb_max_iter, nb_iter_plot, callback_func, max_time, start)
+        x = _cp_report_loop(state, c, np.full(batch, a_ineq is not None), range(batch), best, lambda x: x,
+                            lambda values, energy=False: values, nb_max_iter, nb_iter_plot, callback_func, max_time, start)
     finally:
         state.close()
     return x, best
@@ -632,9 +619,8 @@ def many_system(lps):
     n = np.array([lp[0].size for lp in lps], dtype=np.int64)
     m_eq = np.array([0 if lp[3] is None else lp[3][3] for lp in lps], dtype=np.int64)
     m_ineq = np.array([0 if lp[5] is None else lp[5][3] for lp in lps], dtype=np.int64)
-    first = lambda sizes: np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64)  # noqa: E731
-    col0, eq0 = first(n), first(m_eq)
-    in0 = int(m_eq.sum()) + first(m_ineq)
+    col0, eq0 = first_offsets(n), first_offsets(m_eq)
+    in0 = int(m_eq.sum()) + first_offsets(m_ineq)
     ptr, idx, val, b = [np.zeros(1, dtype=np.int64)], [], [], []
     entries = 0
     for part, rhs in ((3, 4), (5, 6)):
@@ -647,12 +633,11 @@ def many_system(lps):
             val.append(v)
             b.append(_lib.f64(lps[k][rhs]))
             entries += int(p[-1])
-    cat = lambda parts, dtype: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0), dtype=dtype)  # noqa: E731
     if int(n.sum()) >= 2 ** 31 or int(m_eq.sum() + m_ineq.sum()) >= 2 ** 31:
         raise ValueError("the set has 2^31 or more variables or rows")
-    return dict(n=n, m_eq=m_eq, m_ineq=m_ineq, col0=col0, eq0=eq0, in0=in0, indptr=cat(ptr, np.int64), indices=cat(idx, np.int32),
-                data=cat(val, np.float64), b=cat(b, np.float64), c=cat([lp[0] for lp in lps], np.float64),
-                lb=cat([lp[1] for lp in lps], np.float64), ub=cat([lp[2] for lp in lps], np.float64))
+    return dict(n=n, m_eq=m_eq, m_ineq=m_ineq, col0=col0, eq0=eq0, in0=in0, indptr=concat(ptr, np.int64), indices=concat(idx, np.int32),
+                data=concat(val, np.float64), b=concat(b, np.float64), c=concat([lp[0] for lp in lps], np.float64),
+                lb=concat([lp[1] for lp in lps], np.float64), ub=concat([lp[2] for lp in lps], np.float64))
 
 
 class CPManyState:
@@ -701,24 +686,21 @@ class CPManyState:
         _lib.check(self._l.slp_cp_many_report(self._h, _lib.ptr(out)))
         return out
 
-    def _split(self, flat, sizes):
-        return [v.copy() for v in np.split(flat, np.cumsum(sizes)[:-1])]
-
     def x(self):
         out = np.empty(int(self.n.sum()))
         _lib.check(self._l.slp_cp_many_get_x(self._h, _lib.ptr(out)))
-        return self._split(out, self.n)
+        return split_by(out, self.n)
 
     def y(self):
         """Per LP ``[y_eq; y_ineq]``."""
         out = np.empty(int(self.m.sum()))
         _lib.check(self._l.slp_cp_many_get_y(self._h, _lib.ptr(out)))
-        return self._split(out, self.m)
+        return split_by(out, self.m)
 
     def preconditioners(self):
         t, s = np.empty(int(self.n.sum())), np.empty(int(self.m.sum()))
         _lib.check(self._l.slp_cp_many_get_preconditioners(self._h, _lib.ptr(t), _lib.ptr(s)))
-        return self._split(t, self.n), self._split(s, self.m)
+        return split_by(t, self.n), split_by(s, self.m)
 
     def form(self, k):
         """``"lds"`` or ``"global"``: where LP ``k`` keeps x, z, y during a launch."""
@@ -736,13 +718,6 @@ class CPManyState:
 def many_lds_limit():
     """Doubles of x, z, y (``2 n + m``) an LP may hold in LDS (``slp_cp_many_lds_limit``)."""
     return int(_lib.load().slp_cp_many_lds_limit())
-
-
-def _box_vertex(c, lb, ub):
-    x = np.zeros_like(lb)  # reference :147-151
-    x[c > 0] = lb[c > 0]
-    x[c < 0] = ub[c < 0]
-    return x
 
 
 def chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=100, callback_func=None, max_time=None, nb_iter_plot=10):
@@ -787,17 +762,18 @@ def chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=100
             if v is not None and v.shape != lps[k][0].shape:
                 raise ValueError(f"LP {k}: x0 has shape {v.shape}, c has {lps[k][0].size} entries")
     solved = [k for k in range(count) if lps[k][3] is not None or lps[k][5] is not None]
-    xs = [None if (lps[k][3] is not None or lps[k][5] is not None) else _box_vertex(*lps[k][:3]) for k in range(count)]
+    xs = [None if (lps[k][3] is not None or lps[k][5] is not None) else box_vertex(*lps[k][:3]) for k in range(count)]
     best = [None] * count
     if not solved:
         return xs, best
     costs = [lps[k][0] for k in solved]
     has_ineq = np.array([lps[k][5] is not None for k in solved])
     state = CPManyState([lps[k] for k in solved], None if x0 is None else [x0[k] for k in solved], alpha, theta)
+    free_energy = np.array([0.0 if xs[k] is None else lps[k][0].dot(xs[k]) for k in range(count)])
 
-    def spread(values, fill):
+    def spread(values, energy=False):
         """Per-LP numbers of the solved LPs over the whole list."""
-        out = np.array(fill, dtype=np.float64)
+        out = free_energy.copy() if energy else np.zeros(count)
         out[solved] = values
         return out
 
@@ -807,39 +783,8 @@ def chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=100
             out[k] = v
         return out
 
-    free_energy = np.array([0.0 if xs[k] is None else lps[k][0].dot(xs[k]) for k in range(count)])
     try:
-        best_energy = np.full(len(solved), np.inf)
-        niter = 0
-        while niter < nb_max_iter:
-            if niter % nb_iter_plot == 0:
-                state.primal_step()
-                elapsed = time.perf_counter() - start
-                if (max_time is not None) and collective_elapsed(elapsed) > max_time:  # the same decision on every rank
-                    break
-                energy1, energy2, max_violated_equality, max_violated_inequality, max_eq_at_x = state.report().T.copy()
-                max_violated_inequality[~has_ineq] = 0  # the reference dereferences a_ineq here (:283) and fails
-                x = None
-                feasible = np.nonzero((max_eq_at_x == 0) & (max_violated_inequality <= 0))[0]
-                if feasible.size:
-                    x = state.x()
-                    for i in feasible:
-                        energy_rounded = costs[i].dot(x[i])
-                        if energy_rounded < best_energy[i]:
-                            best_energy[i] = energy_rounded
-                            best[solved[i]] = x[i].copy()
-                if callback_func is not None:
-                    if x is None:
-                        x = state.x()
-                    callback_func(niter, all_x(x), spread(energy1, free_energy), spread(energy2, free_energy), elapsed,
-                                  spread(max_violated_equality, np.zeros(count)), spread(max_violated_inequality, np.zeros(count)))
-                state.dual_step()
-                niter += 1
-            else:
-                k = min(nb_iter_plot - niter % nb_iter_plot, nb_max_iter - niter)
-                state.iterate(k)
-                niter += k
-        xs = all_x(state.x())
+        xs = _cp_report_loop(state, costs, has_ineq, solved, best, all_x, spread, nb_max_iter, nb_iter_plot, callback_func, max_time, start)
     finally:
         state.close()
     return xs, best

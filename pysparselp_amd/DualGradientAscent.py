@@ -15,6 +15,7 @@ import time
 import numpy as np
 
 from . import _lib
+from ._batch import check_costs, concat, first_offsets, require_one_sided, shared_or_batched, split_by
 
 PATHS = {"auto": 0, "fused": 1, "general": 2}
 FUSED_MAX = 8192    # most variables of the fused search (one workgroup, breakpoints in LDS)
@@ -35,12 +36,82 @@ def _check_status(flags):
         raise AssertionError("exact_dual_line_search returned a negative step")
 
 
-class DeviceDGA:
+def _check_status_each(flags, where):
+    """The single solver's exception for the first kind of error present, naming the readers that carry it: ``where`` is
+    ``"instances {} of the batch"`` or ``"LPs {} of the list"``."""
+    flags = np.asarray(flags, dtype=np.int64)
+    for bit in (STATUS_NAN, STATUS_EMPTY, STATUS_NO_CROSSING, STATUS_NEGATIVE_STEP):
+        bad = np.flatnonzero(flags & bit)
+        if bad.size:
+            try:
+                _check_status(bit)
+            except (ValueError, AssertionError) as e:
+                raise type(e)(f"{e} ({where.format(bad.tolist())})") from None
+
+
+def _check_status_batch(flags):
+    _check_status_each(flags, DeviceDGABatch._WHERE)
+
+
+class _DeviceDGA:
+    """What the three device wrappers share: the handle ``_h`` of the entry points ``slp_<_PREFIX>_*`` and ``_draws``, the
+    callable that continues the stream of tie draws.  ``_WHERE`` names the readers of a status error (None: one solve)."""
+
+    _PREFIX = None
+    _WHERE = None
+
+    def _call(self, name, *args):
+        return getattr(self._l, f"slp_{self._PREFIX}_{name}")(self._h, *args)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._call("destroy")
+            self._h = None
+
+    __del__ = close
+
+    def push_random(self, values):
+        values = _lib.f64(values)
+        _lib.check(self._call("push_random", _lib.ptr(values), values.size))
+
+    def iterate(self, k, refill=True):
+        """``k`` iterations (of every instance / LP), nothing read back in between.  ``refill``: the draw buffer is topped up to
+        two draws per iteration behind the furthest reader first; without it the call stops early, for all readers, when the
+        buffer could run dry (``status()[3]`` tells how far it got)."""
+        k = int(k)
+        if refill:
+            left = self.status()[2]
+            if left < 2 * k:
+                self.push_random(self._draws(2 * k - left))
+        _lib.check(self._call("iterate", k))
+
+    def check(self):
+        flags = self.status()[0]
+        if self._WHERE is None:
+            _check_status(flags & ~STATUS_DRAWS_DRY)
+        else:
+            _check_status_each(flags & ~STATUS_DRAWS_DRY, self._WHERE)
+        return flags
+
+    def timing(self, on):
+        _lib.check(self._call("timing", int(bool(on))))
+
+    def timing_read(self):
+        """Milliseconds per stage since ``timing(True)``: products, sort, scans, rest, fused search (the list form runs an
+        iteration as one launch, so all of it stands under ``fused_search``)."""
+        out = np.zeros(5)
+        _lib.check(self._call("timing_read", _lib.ptr(out)))
+        return dict(zip(("products", "sort", "scans", "rest", "fused_search"), (float(v) for v in out)))
+
+
+class DeviceDGA(_DeviceDGA):
     """The iteration state on the device (``slp_dga_*``): ``a`` a ``DeviceMatrix`` (any product format, chunked included) whose
     first ``m_eq`` rows are the equalities, ``b`` = ``[b_eq; b_upper]``, ``y0`` the start multipliers, ``draws`` a callable
     ``draws(count)`` giving the next ``count`` uniform draws of the tie rule (default: a private ``RandomState(0)``).
     ``path``: ``"auto"`` (the fused one-workgroup search up to ``FUSED_AUTO`` variables, else the general one), ``"fused"``
     (at most ``FUSED_MAX`` variables), ``"general"``; the environment's ``SLP_DGA_PATH`` picks it when ``path`` is None."""
+
+    _PREFIX = "dga"
 
     def __init__(self, a, b, c, lb, ub, y0, m_eq=0, draws=None, path=None):
         self._l = _lib.lib()
@@ -55,13 +126,6 @@ class DeviceDGA:
         if path is not None:
             _lib.check(self._l.slp_dga_set_path(self._h, PATHS[path]))
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._l.slp_dga_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
     def path(self):
         return {1: "fused", 2: "general"}[int(self._l.slp_dga_path(self._h))]
 
@@ -70,25 +134,6 @@ class DeviceDGA:
         out = np.zeros(4, dtype=np.int64)
         _lib.check(self._l.slp_dga_status(self._h, _lib.ptr(out)))
         return tuple(int(v) for v in out)
-
-    def push_random(self, values):
-        values = _lib.f64(values)
-        _lib.check(self._l.slp_dga_push_random(self._h, _lib.ptr(values), values.size))
-
-    def iterate(self, k, refill=True):
-        """``k`` iterations, nothing read back in between.  ``refill``: the draw buffer is topped up to two draws per iteration
-        first; without it the call stops early when the buffer could run dry (``status()[3]`` tells how far it got)."""
-        k = int(k)
-        if refill:
-            left = self.status()[2]
-            if left < 2 * k:
-                self.push_random(self._draws(2 * k - left))
-        _lib.check(self._l.slp_dga_iterate(self._h, k))
-
-    def check(self):
-        flags = self.status()[0]
-        _check_status(flags & ~STATUS_DRAWS_DRY)
-        return flags
 
     def x(self):
         x = np.empty(self.n)
@@ -105,15 +150,6 @@ class DeviceDGA:
         out = np.zeros(3)
         _lib.check(self._l.slp_dga_report(self._h, _lib.ptr(out)))
         return tuple(float(v) for v in out)
-
-    def timing(self, on):
-        _lib.check(self._l.slp_dga_timing(self._h, int(bool(on))))
-
-    def timing_read(self):
-        """Milliseconds per stage since ``timing(True)``: products, sort, scans, rest, fused search."""
-        out = np.zeros(5)
-        _lib.check(self._l.slp_dga_timing_read(self._h, _lib.ptr(out)))
-        return dict(zip(("products", "sort", "scans", "rest", "fused_search"), (float(v) for v in out)))
 
 
 def exact_dual_line_search(direction, a, b, c_bar, upper_bounds, lower_bounds, draws=None, path=None):
@@ -153,6 +189,24 @@ def exact_dual_line_search(direction, a, b, c_bar, upper_bounds, lower_bounds, d
     return float(out[0])
 
 
+def _dga_drive(state, nb_max_iter, callback_func, max_time, start, all_frozen=False):
+    """The loop of the three forms: iteration ``niter`` with ``niter % 100 == 0`` is a launch of its own, followed by the status
+    check, the callback with the x of the top of that iteration and the test of ``max_time``; the iterations between two such
+    are one call.  Nothing runs when every reader is frozen."""
+    i = 0
+    while i < nb_max_iter and not all_frozen:
+        k = 1 if i % 100 == 0 else min(100 - i % 100, nb_max_iter - i)
+        state.iterate(k)
+        i += k
+        state.check()
+        if (i - 1) % 100 == 0:
+            elapsed = time.perf_counter() - start
+            if callback_func is not None:
+                callback_func(i - 1, state.x(), 0, 0, elapsed, 0, 0)
+            if max_time is not None and elapsed > max_time:
+                break
+
+
 def dual_gradient_ascent(x, lp, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None, nb_iter_plot=1):
     """Gradient ascent in the dual (reference :68-245), same signature and return value ``(x, y_eq, y_ineq)``.
 
@@ -165,9 +219,7 @@ def dual_gradient_ascent(x, lp, nb_max_iter=1000, callback_func=None, y_eq=None,
     ``nb_iter_plot`` only gates the reference's prints and is unused.  ``max_time``, which the reference tests after every
     iteration, is tested where the device loop synchronises anyway: after those callbacks, so at most every 100 iterations;
     the points of a curve do not depend on it.  Under a communicator every rank runs the whole LP as a replica."""
-    b_lower = getattr(lp, "b_lower", None)
-    if b_lower is not None and np.size(b_lower) > 0 and np.max(b_lower) != -np.inf:
-        raise ValueError("dual_gradient_ascent needs one-sided inequalities: b_lower must be None or all -inf")
+    require_one_sided(getattr(lp, "b_lower", None))
     from . import host_setup
     from .tools import CsrArrays
 
@@ -202,18 +254,7 @@ def dual_gradient_ascent(x, lp, nb_max_iter=1000, callback_func=None, y_eq=None,
             return result(state.x())
         if nb_max_iter <= 0:
             return result(x)
-        i = 0
-        while i < nb_max_iter:
-            k = 1 if i % 100 == 0 else min(100 - i % 100, nb_max_iter - i)
-            state.iterate(k)
-            i += k
-            state.check()
-            if (i - 1) % 100 == 0:
-                elapsed = time.perf_counter() - start
-                if callback_func is not None:
-                    callback_func(i - 1, state.x(), 0, 0, elapsed, 0, 0)
-                if max_time is not None and elapsed > max_time:
-                    break
+        _dga_drive(state, nb_max_iter, callback_func, max_time, start)
         return result(state.x())
     finally:
         if state is not None:
@@ -223,29 +264,7 @@ def dual_gradient_ascent(x, lp, nb_max_iter=1000, callback_func=None, y_eq=None,
 
 # ---- batched: B LPs over one constraint matrix ---------------------------------------------------------------------------------
 
-def _check_status_batch(flags):
-    """The single solver's exception for the first kind of error present, naming the instances that carry it."""
-    flags = np.asarray(flags, dtype=np.int64)
-    for bit in (STATUS_NAN, STATUS_EMPTY, STATUS_NO_CROSSING, STATUS_NEGATIVE_STEP):
-        bad = np.flatnonzero(flags & bit)
-        if bad.size:
-            try:
-                _check_status(bit)
-            except (ValueError, AssertionError) as e:
-                raise type(e)(f"{e} (instances {bad.tolist()} of the batch)") from None
-
-
-def _per_instance(name, v, batch, size):
-    """``v`` of shape ``(size,)`` (shared) or ``(batch, size)`` as a contiguous float64 array and whether it is per instance."""
-    v = np.asarray(v, dtype=np.float64)
-    if v.shape == (size,):
-        return _lib.f64(v), 0
-    if v.shape == (batch, size):
-        return _lib.f64(v), 1
-    raise ValueError(f"{name} has shape {v.shape}: expected ({size},) or (B, {size}) with B = {batch}")
-
-
-class DeviceDGABatch:
+class DeviceDGABatch(_DeviceDGA):
     """``DeviceDGA`` for B LPs over one ``DeviceMatrix`` ``a`` (with its CSR: not chunked) and one ``b`` (``slp_batch_dga_*``):
     ``c`` of shape ``(B, n)``; ``lb``, ``ub`` of shape ``(n,)`` or ``(B, n)``; ``y0`` of shape ``(m,)`` or ``(B, m)``.  Results
     carry a leading axis B.  All instances read one stream of tie draws (``draws(count)``, default a private ``RandomState(0)``),
@@ -254,14 +273,12 @@ class DeviceDGABatch:
     ``FUSED_BATCH`` instances on, up to ``FUSED_MAX``; else the general one), ``"fused"``, ``"general"``; the environment's
     ``SLP_DGA_BATCH_PATH`` picks it when ``path`` is None."""
 
+    _PREFIX = "batch_dga"
+    _WHERE = "instances {} of the batch"
+
     def __init__(self, a, b, c, lb, ub, y0, m_eq=0, draws=None, path=None):
         self.n, self.m, self.m_eq = a.shape[1], a.shape[0], int(m_eq)
-        c = np.asarray(c, dtype=np.float64)
-        if c.ndim != 2 or c.shape[1] != self.n:
-            raise ValueError(f"costs has shape {c.shape}: expected (B, {self.n}), one row per instance")
-        self.batch = c.shape[0]
-        if self.batch < 1:
-            raise ValueError("an empty batch: costs needs at least one row (B >= 1)")
+        c, self.batch = check_costs(c, self.n)
         if self.m < 1:
             raise ValueError("dual_gradient_ascent_batch: the LP has no constraint rows")
         if not 0 <= self.m_eq <= self.m:
@@ -269,23 +286,16 @@ class DeviceDGABatch:
         c, b = _lib.f64(c), _lib.f64(b)
         if b.shape != (self.m,):
             raise ValueError(f"b has shape {b.shape}: expected ({self.m},); per-instance right-hand sides are not built")
-        lb, lb_b = _per_instance("lower_bounds", lb, self.batch, self.n)
-        ub, ub_b = _per_instance("upper_bounds", ub, self.batch, self.n)
-        y0, y_b = _per_instance("y0", y0, self.batch, self.m)
+        lb, lb_b = shared_or_batched("lower_bounds", lb, self.batch, self.n)
+        ub, ub_b = shared_or_batched("upper_bounds", ub, self.batch, self.n)
+        y0, y_b = shared_or_batched("y0", y0, self.batch, self.m)
         self._l = _lib.lib()
         self._draws = draws if draws is not None else np.random.RandomState(0).random_sample
-        self._h = _lib.check_handle(self._l.slp_batch_dga_create_on(a._h, self.m_eq, _lib.ptr(b), self.batch, _lib.ptr(c), _lib.ptr(lb), lb_b,
-                                                                    _lib.ptr(ub), ub_b, _lib.ptr(y0), y_b))
+        self._h = _lib.check_handle(self._l.slp_batch_dga_create_on(a._h, self.m_eq, _lib.ptr(b), self.batch, _lib.ptr(c), _lib.ptr(lb),
+                                                                    int(lb_b), _lib.ptr(ub), int(ub_b), _lib.ptr(y0), int(y_b)))
         self._a = a
         if path is not None:
             _lib.check(self._l.slp_batch_dga_set_path(self._h, PATHS[path]))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._l.slp_batch_dga_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def path(self):
         return {1: "fused", 2: "general"}[int(self._l.slp_batch_dga_path(self._h))]
@@ -308,26 +318,6 @@ class DeviceDGABatch:
         _lib.check(self._l.slp_batch_dga_frozen(self._h, _lib.ptr(out)))
         return out.astype(bool)
 
-    def push_random(self, values):
-        values = _lib.f64(values)
-        _lib.check(self._l.slp_batch_dga_push_random(self._h, _lib.ptr(values), values.size))
-
-    def iterate(self, k, refill=True):
-        """``k`` iterations of every instance, nothing read back in between.  ``refill``: the shared draw buffer is topped up to
-        two draws per iteration behind the furthest instance first; without it the call stops early, for all instances, when the
-        buffer could run dry (``status()[3]`` tells how far it got)."""
-        k = int(k)
-        if refill:
-            left = self.status()[2]
-            if left < 2 * k:
-                self.push_random(self._draws(2 * k - left))
-        _lib.check(self._l.slp_batch_dga_iterate(self._h, k))
-
-    def check(self):
-        flags = self.status()[0]
-        _check_status_batch(flags & ~STATUS_DRAWS_DRY)
-        return flags
-
     def x(self):
         x = np.empty((self.batch, self.n))
         _lib.check(self._l.slp_batch_dga_get_x(self._h, _lib.ptr(x)))
@@ -344,15 +334,6 @@ class DeviceDGABatch:
         out = np.zeros((self.batch, 3))
         _lib.check(self._l.slp_batch_dga_report(self._h, _lib.ptr(out)))
         return out
-
-    def timing(self, on):
-        _lib.check(self._l.slp_batch_dga_timing(self._h, int(bool(on))))
-
-    def timing_read(self):
-        """Milliseconds per stage since ``timing(True)``: products, sort, scans, rest, fused search."""
-        out = np.zeros(5)
-        _lib.check(self._l.slp_batch_dga_timing_read(self._h, _lib.ptr(out)))
-        return dict(zip(("products", "sort", "scans", "rest", "fused_search"), (float(v) for v in out)))
 
 
 def dual_gradient_ascent_batch(lp, costs, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None, lower_bounds=None,
@@ -374,20 +355,13 @@ def dual_gradient_ascent_batch(lp, costs, nb_max_iter=1000, callback_func=None, 
 
 def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path):
     """``dual_gradient_ascent_batch`` plus, as a fourth value, the final ``DeviceDGABatch.report()``."""
-    b_lower = getattr(lp, "b_lower", None)
-    if b_lower is not None and np.size(b_lower) > 0 and np.max(b_lower) != -np.inf:
-        raise ValueError("dual_gradient_ascent needs one-sided inequalities: b_lower must be None or all -inf")
+    require_one_sided(getattr(lp, "b_lower", None))
     from .device import DeviceMatrix
     from .tools import CsrArrays
 
     start = time.perf_counter()
-    costs = np.asarray(costs, dtype=np.float64)
     n = np.size(lp.costsvector)
-    if costs.ndim != 2 or costs.shape[1] != n:
-        raise ValueError(f"costs has shape {costs.shape}: expected (B, {n}), one row per instance")
-    batch = costs.shape[0]
-    if batch < 1:
-        raise ValueError("an empty batch: costs needs at least one row (B >= 1)")
+    costs, batch = check_costs(costs, n)
     a_eq, a_ineq = CsrArrays.from_any(lp.a_equalities), CsrArrays.from_any(lp.a_inequalities)
     m_eq = 0 if a_eq is None else a_eq.shape[0]
     m_in = 0 if a_ineq is None else a_ineq.shape[0]
@@ -396,13 +370,13 @@ def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time
     for name, rhs, rows in (("b_equalities", lp.b_equalities, m_eq), ("b_upper", lp.b_upper, m_in)):
         if rows and np.shape(rhs) != (rows,):
             raise ValueError(f"{name} has shape {np.shape(rhs)}: expected ({rows},); per-instance right-hand sides are not built")
-    lb, _ = _per_instance("lower_bounds", lp.lower_bounds if lower_bounds is None else lower_bounds, batch, n)
-    ub, _ = _per_instance("upper_bounds", lp.upper_bounds if upper_bounds is None else upper_bounds, batch, n)
+    lb, _ = shared_or_batched("lower_bounds", lp.lower_bounds if lower_bounds is None else lower_bounds, batch, n)
+    ub, _ = shared_or_batched("upper_bounds", lp.upper_bounds if upper_bounds is None else upper_bounds, batch, n)
     rs = np.random.RandomState(0)   # the reference draws the starts it is not given; the tie draws continue that stream
-    ye, ye_b = _per_instance("y_eq", -rs.rand(m_eq) if y_eq is None else y_eq, batch, m_eq)
+    ye, ye_b = shared_or_batched("y_eq", -rs.rand(m_eq) if y_eq is None else y_eq, batch, m_eq)
     if y_ineq is None:
         y_ineq = np.abs(rs.rand(m_in)) if a_ineq is not None else np.zeros(0)
-    yi, yi_b = _per_instance("y_ineq", y_ineq, batch, m_in)
+    yi, yi_b = shared_or_batched("y_ineq", y_ineq, batch, m_in)
     if ye_b or yi_b:
         y0 = np.concatenate((np.broadcast_to(ye, (batch, m_eq)), np.broadcast_to(yi, (batch, m_in))), axis=1)
     else:
@@ -417,18 +391,7 @@ def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time
 
     try:
         state = DeviceDGABatch(mat, b, costs, lb, ub, y0, m_eq=m_eq, draws=rs.random_sample, path=path)
-        i = 0
-        while i < nb_max_iter and not state.frozen().all():
-            k = 1 if i % 100 == 0 else min(100 - i % 100, nb_max_iter - i)
-            state.iterate(k)
-            i += k
-            state.check()
-            if (i - 1) % 100 == 0:
-                elapsed = time.perf_counter() - start
-                if callback_func is not None:
-                    callback_func(i - 1, state.x(), 0, 0, elapsed, 0, 0)
-                if max_time is not None and elapsed > max_time:
-                    break
+        _dga_drive(state, nb_max_iter, callback_func, max_time, start, all_frozen=state.frozen().all())
         return result()
     finally:
         if state is not None:
@@ -451,8 +414,7 @@ def _dga_many_lp(k, lp):
     except AttributeError as e:
         raise ValueError(f"LP {k} is not an LP object (costsvector, a_equalities, b_equalities, a_inequalities, b_upper, b_lower, "
                          f"lower_bounds, upper_bounds): {e}") from None
-    if b_lower is not None and np.size(b_lower) > 0 and np.max(b_lower) != -np.inf:
-        raise ValueError(f"LP {k}: dual_gradient_ascent needs one-sided inequalities: b_lower must be None or all -inf")
+    require_one_sided(b_lower, prefix=f"LP {k}: ")
     if c.ndim != 1 or c.size < 1:
         raise ValueError(f"LP {k}: costsvector has shape {c.shape}, expected (n,) with n >= 1")
     n = c.size
@@ -532,7 +494,6 @@ def dga_many_system(lps, y0s, draw_offsets):
     n = np.array([lp[0].size for lp in lps], dtype=np.int64)
     m_eq = np.array([0 if lp[3] is None else lp[3].shape[0] for lp in lps], dtype=np.int64)
     m_ineq = np.array([0 if lp[5] is None else lp[5].shape[0] for lp in lps], dtype=np.int64)
-    first = lambda sizes: np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64)  # noqa: E731
     ptr, idx, val, b = [np.zeros(1, dtype=np.int64)], [], [], []
     entries = 0
     for lp in lps:
@@ -546,34 +507,24 @@ def dga_many_system(lps, y0s, draw_offsets):
             entries += a.nnz
     if int(n.sum()) >= 2 ** 31 or int(m_eq.sum() + m_ineq.sum()) >= 2 ** 31 or entries >= 2 ** 31:
         raise ValueError("the list has 2^31 or more variables, rows or entries")
-    cat = lambda parts, dtype: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0), dtype=dtype)  # noqa: E731
-    y0 = cat(list(y0s), np.float64)
+    y0 = concat(list(y0s), np.float64)
     assert y0.size == int(m_eq.sum() + m_ineq.sum()) and len(draw_offsets) == count
-    return dict(n=n, m_eq=m_eq, m_ineq=m_ineq, col0=first(n), row0=first(m_eq + m_ineq), indptr=cat(ptr, np.int64),
-                indices=cat(idx, np.int32), data=cat(val, np.float64), b=cat(b, np.float64), c=cat([lp[0] for lp in lps], np.float64),
-                lb=cat([lp[1] for lp in lps], np.float64), ub=cat([lp[2] for lp in lps], np.float64), y0=y0,
-                draw_offset=np.ascontiguousarray(draw_offsets, dtype=np.int64))
+    return dict(n=n, m_eq=m_eq, m_ineq=m_ineq, col0=first_offsets(n), row0=first_offsets(m_eq + m_ineq), indptr=concat(ptr, np.int64),
+                indices=concat(idx, np.int32), data=concat(val, np.float64), b=concat(b, np.float64),
+                c=concat([lp[0] for lp in lps], np.float64), lb=concat([lp[1] for lp in lps], np.float64),
+                ub=concat([lp[2] for lp in lps], np.float64), y0=y0, draw_offset=np.ascontiguousarray(draw_offsets, dtype=np.int64))
 
 
-def _check_status_many(flags):
-    """The single solver's exception for the first kind of error present, naming the LPs that carry it."""
-    flags = np.asarray(flags, dtype=np.int64)
-    for bit in (STATUS_NAN, STATUS_EMPTY, STATUS_NO_CROSSING, STATUS_NEGATIVE_STEP):
-        bad = np.flatnonzero(flags & bit)
-        if bad.size:
-            try:
-                _check_status(bit)
-            except (ValueError, AssertionError) as e:
-                raise type(e)(f"{e} (LPs {bad.tolist()} of the list)") from None
-
-
-class DeviceDGAMany:
+class DeviceDGAMany(_DeviceDGA):
     """``DeviceDGA`` for a list of LPs with matrices of their own (``slp_many_dga_*``): one workgroup per LP runs whole iterations
     inside a launch.  ``lps``: the LPs as ``_dga_many_lp`` returns them (each at most ``FUSED_MAX`` variables and at least one
     row); ``y0s``: per LP ``[y_eq; y_ineq]``; ``draw_offsets``: per LP the position in the stream of draws at which its tie draws
     begin (``dga_many_start`` gives both).  ``draws(count)`` gives the next ``count`` draws of that one stream FROM ITS START
     (default: a private ``RandomState(0)``); every LP reads it at its own position.  Results are lists of per-LP arrays.  An LP
     whose start has dual energy ``-inf`` is frozen (``frozen()``): its x and y stay the start's."""
+
+    _PREFIX = "many_dga"
+    _WHERE = "LPs {} of the list"
 
     def __init__(self, lps, y0s, draw_offsets, draws=None):
         s = dga_many_system(lps, y0s, draw_offsets)
@@ -587,13 +538,6 @@ class DeviceDGAMany:
             self.count, _lib.ptr(s["n"]), _lib.ptr(s["m_eq"]), _lib.ptr(s["m_ineq"]), _lib.ptr(s["indptr"]), _lib.ptr(s["indices"]),
             _lib.ptr(s["data"]), _lib.ptr(s["b"]), _lib.ptr(s["c"]), _lib.ptr(s["lb"]), _lib.ptr(s["ub"]), _lib.ptr(s["y0"]),
             _lib.ptr(s["draw_offset"])))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._l.slp_many_dga_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def kmax(self):
         """Iterations one launch holds at most (from the shapes; ``SLP_DGA_MANY_KMAX`` lowers it)."""
@@ -612,39 +556,16 @@ class DeviceDGAMany:
         _lib.check(self._l.slp_many_dga_frozen(self._h, _lib.ptr(out)))
         return out.astype(bool)
 
-    def push_random(self, values):
-        values = _lib.f64(values)
-        _lib.check(self._l.slp_many_dga_push_random(self._h, _lib.ptr(values), values.size))
-
-    def iterate(self, k, refill=True):
-        """``k`` iterations of every LP, nothing read back in between.  ``refill``: the shared draw buffer is topped up to two
-        draws per iteration behind the furthest position first; without it the call stops early, for all LPs, when the buffer
-        could run dry (``status()[3]`` tells how far it got)."""
-        k = int(k)
-        if refill:
-            left = self.status()[2]
-            if left < 2 * k:
-                self.push_random(self._draws(2 * k - left))
-        _lib.check(self._l.slp_many_dga_iterate(self._h, k))
-
-    def check(self):
-        flags = self.status()[0]
-        _check_status_many(flags & ~STATUS_DRAWS_DRY)
-        return flags
-
-    def _split(self, flat, sizes):
-        return [v.copy() for v in np.split(flat, np.cumsum(sizes)[:-1])]
-
     def x(self):
         out = np.empty(int(self.n.sum()))
         _lib.check(self._l.slp_many_dga_get_x(self._h, _lib.ptr(out)))
-        return self._split(out, self.n)
+        return split_by(out, self.n)
 
     def y(self):
         """``(y_eqs, y_ineqs)``: two lists of per-LP arrays."""
         out = np.empty(int(self.m.sum()))
         _lib.check(self._l.slp_many_dga_get_y(self._h, _lib.ptr(out)))
-        both = self._split(out, self.m)
+        both = split_by(out, self.m)
         return [v[:me].copy() for v, me in zip(both, self.m_eq)], [v[me:].copy() for v, me in zip(both, self.m_eq)]
 
     def report(self):
@@ -653,16 +574,6 @@ class DeviceDGAMany:
         out = np.zeros((self.count, 3))
         _lib.check(self._l.slp_many_dga_report(self._h, _lib.ptr(out)))
         return out
-
-    def timing(self, on):
-        _lib.check(self._l.slp_many_dga_timing(self._h, int(bool(on))))
-
-    def timing_read(self):
-        """Milliseconds since ``timing(True)`` in the layout of ``DeviceDGA.timing_read``; an iteration is one launch here, so all
-        of it stands under ``fused_search``."""
-        out = np.zeros(5)
-        _lib.check(self._l.slp_many_dga_timing_read(self._h, _lib.ptr(out)))
-        return dict(zip(("products", "sort", "scans", "rest", "fused_search"), (float(v) for v in out)))
 
 
 def dual_gradient_ascent_many(lps, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None):
@@ -700,18 +611,7 @@ def _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, froze
         frozen = state.frozen()
         if frozen_out is not None:
             frozen_out[:] = frozen.tolist()
-        i = 0
-        while i < nb_max_iter and not frozen.all():
-            k = 1 if i % 100 == 0 else min(100 - i % 100, nb_max_iter - i)
-            state.iterate(k)
-            i += k
-            state.check()
-            if (i - 1) % 100 == 0:
-                elapsed = time.perf_counter() - start
-                if callback_func is not None:
-                    callback_func(i - 1, state.x(), 0, 0, elapsed, 0, 0)
-                if max_time is not None and elapsed > max_time:
-                    break
+        _dga_drive(state, nb_max_iter, callback_func, max_time, start, all_frozen=frozen.all())
         yes, yis = state.y()
         return state.x(), yes, [yi if h else None for yi, h in zip(yis, has_ineq)], state.report()
     finally:

@@ -25,6 +25,7 @@ import scipy.sparse
 
 from .ADMM import lp_admm, lp_admm_batch
 from .ChambollePockPPD import chambolle_pock_ppd, chambolle_pock_ppd_batch, chambolle_pock_ppd_many
+from ._batch import check_costs, require_one_sided
 from ._lib import ORDER_AUTO
 
 solving_methods = ("chambolle_pock_ppd", "admm", "admm_blocks", "admm2")
@@ -36,6 +37,69 @@ batch_methods = ("chambolle_pock_ppd",)
 many_methods = ("chambolle_pock_ppd",)
 
 _SCALARS = (int, float, np.integer, np.floating)
+_CURVES = ("distance_to_ground_truth", "distanceToGroundTruthAfterRounding", "opttime_curve", "dopttime_curve", "pobj_curve",
+           "dobj_curve", "pobjbound", "max_violated_inequality", "max_violated_equality", "max_violated_constraint", "itrn_curve")
+
+
+def _reset_curves(lp):
+    for name in _CURVES:
+        setattr(lp, name, [])
+
+
+def _mean_together(distances):
+    """Per instance the mean of its distances to the ground truth, one reduction over the whole batch."""
+    return np.mean(distances, axis=tuple(range(1, distances.ndim)))
+
+
+def _mean_each(distances):
+    """The same instance by instance: the expressions (and so the sums) of ``solve``."""
+    return np.array([np.mean(d) for d in distances])
+
+
+def _batch_recorder(lp, batch, ground_truth, ground_truth_indices, mean=_mean_together, expand=None):
+    """The callback of the three ``(B, ...)`` forms: fills ``lp``'s curves as ``solve`` does, the per-instance ones with arrays of
+    length ``batch`` (a number the solver reports once for all instances is repeated).  ``expand`` maps the solver's iterates to
+    the LP's variables."""
+    def record(niter, solution, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
+        if expand is not None:
+            solution = expand(solution)
+        if ground_truth is not None:
+            picked = solution[:, ground_truth_indices]
+            lp.distance_to_ground_truth.append(mean(np.abs(ground_truth - picked)))
+            lp.distanceToGroundTruthAfterRounding.append(mean(np.abs(ground_truth - np.round(picked))))
+        lp.itrn_curve.append(niter)
+        lp.opttime_curve.append(duration)
+        lp.dopttime_curve.append(duration)
+        lp.dobj_curve.append(np.full(batch, energy2, dtype=np.float64))
+        lp.pobj_curve.append(np.full(batch, energy1, dtype=np.float64))
+        lp.max_violated_constraint.append(np.array([lp.max_constraint_violation(solution[k]) for k in range(batch)]))
+        lp.max_violated_equality.append(np.full(batch, max_violated_equality, dtype=np.float64))
+        lp.max_violated_inequality.append(np.full(batch, max_violated_inequality, dtype=np.float64))
+
+    return record
+
+
+def _list_recorder(lps, expand=None, skip=()):
+    """The callback of the two list forms: fills every LP's curves as its own ``solve`` does; a number reported once for the whole
+    list goes to every LP as it is.  ``expand(k, x)`` maps the solver's iterate of LP ``k`` to its variables; the LPs with a true
+    entry in ``skip`` (filled by the time of the first report) record nothing."""
+    def of(number, k):
+        return number[k] if np.ndim(number) else number
+
+    def record(niter, solutions, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
+        for k, lp in enumerate(lps):
+            if k < len(skip) and skip[k]:
+                continue
+            lp.itrn_curve.append(niter)
+            lp.opttime_curve.append(duration)
+            lp.dopttime_curve.append(duration)
+            lp.dobj_curve.append(of(energy2, k))
+            lp.pobj_curve.append(of(energy1, k))
+            lp.max_violated_constraint.append(lp.max_constraint_violation(solutions[k] if expand is None else expand(k, solutions[k])))
+            lp.max_violated_equality.append(of(max_violated_equality, k))
+            lp.max_violated_inequality.append(of(max_violated_inequality, k))
+
+    return record
 
 
 def empty_csr_matrix(ncols=0):
@@ -410,10 +474,7 @@ class SparseLP:
         if a_ineq is not None:
             assert a_ineq.indices.size == 0 or a_ineq.indices.max() < a_ineq.shape[1]
         start = time.perf_counter()
-        for name in ("distance_to_ground_truth", "distanceToGroundTruthAfterRounding", "opttime_curve", "dopttime_curve",
-                     "pobj_curve", "dobj_curve", "pobjbound", "max_violated_inequality", "max_violated_equality",
-                     "max_violated_constraint", "itrn_curve"):
-            setattr(self, name, [])
+        _reset_curves(self)
 
         def record(niter, solution, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
             if ground_truth is not None:
@@ -526,17 +587,9 @@ class SparseLP:
         """
         if method not in batch_methods:
             raise ValueError(f"method {method!r} has no batched form; solve_batch supports: {batch_methods}")
-        costs = np.asarray(costs, dtype=np.float64)
-        if costs.ndim != 2 or costs.shape[1] != self.nb_variables:
-            raise ValueError(f"costs has shape {costs.shape}: expected (B, {self.nb_variables}), one row per instance")
-        batch = costs.shape[0]
-        if batch < 1:
-            raise ValueError("an empty batch: costs needs at least one row (B >= 1)")
+        costs, batch = check_costs(costs, self.nb_variables)
         start = time.perf_counter()
-        for name in ("distance_to_ground_truth", "distanceToGroundTruthAfterRounding", "opttime_curve", "dopttime_curve",
-                     "pobj_curve", "dobj_curve", "pobjbound", "max_violated_inequality", "max_violated_equality",
-                     "max_violated_constraint", "itrn_curve"):
-            setattr(self, name, [])
+        _reset_curves(self)
         reduced = copy.deepcopy(self)
         free, shift = reduced.remove_fixed_variables()
         free_ids = np.nonzero(free)[0]
@@ -547,22 +600,7 @@ class SparseLP:
             full[:, free_ids] = sol
             return full - shift
 
-        def record(niter, solution, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
-            solution = expand(solution)
-            if ground_truth is not None:
-                picked = solution[:, ground_truth_indices]
-                axes = tuple(range(1, picked.ndim))
-                self.distance_to_ground_truth.append(np.mean(np.abs(ground_truth - picked), axis=axes))
-                self.distanceToGroundTruthAfterRounding.append(np.mean(np.abs(ground_truth - np.round(picked)), axis=axes))
-            self.itrn_curve.append(niter)
-            self.opttime_curve.append(duration)
-            self.dopttime_curve.append(duration)
-            self.dobj_curve.append(np.array(energy2, dtype=np.float64))
-            self.pobj_curve.append(np.array(energy1, dtype=np.float64))
-            self.max_violated_constraint.append(np.array([self.max_constraint_violation(solution[k]) for k in range(batch)]))
-            self.max_violated_equality.append(np.array(max_violated_equality, dtype=np.float64))
-            self.max_violated_inequality.append(np.array(max_violated_inequality, dtype=np.float64))
-
+        record = _batch_recorder(self, batch, ground_truth, ground_truth_indices, expand=expand)
         res = chambolle_pock_ppd_batch(costs[:, free], reduced.a_equalities, reduced.b_equalities, reduced.a_inequalities,
                                        reduced.b_lower, reduced.b_upper, reduced.lower_bounds, reduced.upper_bounds, x0=None, alpha=1,
                                        theta=1, nb_max_iter=nb_iter, callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
@@ -595,35 +633,13 @@ class SparseLP:
         (and, with ``ground_truth``, the two distance curves) are lists of arrays of length B.  ``max_time`` stops the whole
         batch.  Under a communicator every rank solves the whole batch (a replica).
         """
-        costs = np.asarray(costs, dtype=np.float64)
-        if costs.ndim != 2 or costs.shape[1] != self.nb_variables:
-            raise ValueError(f"costs has shape {costs.shape}: expected (B, {self.nb_variables}), one row per instance")
-        batch = costs.shape[0]
-        if batch < 1:
-            raise ValueError("an empty batch: costs needs at least one row (B >= 1)")
+        costs, batch = check_costs(costs, self.nb_variables)
         a_ineq = self.a_inequalities if (self.a_inequalities is not None and self.a_inequalities.shape[0] > 0) else None
         a_eq, b_eq = (self.a_equalities, self.b_equalities) if self.a_equalities.shape[0] > 0 else (None, None)
         start = time.perf_counter()
-        for name in ("distance_to_ground_truth", "distanceToGroundTruthAfterRounding", "opttime_curve", "dopttime_curve",
-                     "pobj_curve", "dobj_curve", "pobjbound", "max_violated_inequality", "max_violated_equality",
-                     "max_violated_constraint", "itrn_curve"):
-            setattr(self, name, [])
+        _reset_curves(self)
 
-        def record(niter, solution, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
-            if ground_truth is not None:
-                picked = solution[:, ground_truth_indices]
-                axes = tuple(range(1, picked.ndim))
-                self.distance_to_ground_truth.append(np.mean(np.abs(ground_truth - picked), axis=axes))
-                self.distanceToGroundTruthAfterRounding.append(np.mean(np.abs(ground_truth - np.round(picked)), axis=axes))
-            self.itrn_curve.append(niter)
-            self.opttime_curve.append(duration)
-            self.dopttime_curve.append(duration)
-            self.dobj_curve.append(np.array(energy2, dtype=np.float64))
-            self.pobj_curve.append(np.array(energy1, dtype=np.float64))
-            self.max_violated_constraint.append(np.array([self.max_constraint_violation(solution[k]) for k in range(batch)]))
-            self.max_violated_equality.append(np.array(max_violated_equality, dtype=np.float64))
-            self.max_violated_inequality.append(np.array(max_violated_inequality, dtype=np.float64))
-
+        record = _batch_recorder(self, batch, ground_truth, ground_truth_indices)
         x = lp_admm_batch(costs, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds, self.upper_bounds, nb_iter=nb_iter,
                           callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
         elapsed = time.perf_counter() - start
@@ -659,43 +675,17 @@ class SparseLP:
         """
         from .DualGradientAscent import _dga_batch_run
 
-        costs = np.asarray(costs, dtype=np.float64)
-        if costs.ndim != 2 or costs.shape[1] != self.nb_variables:
-            raise ValueError(f"costs has shape {costs.shape}: expected (B, {self.nb_variables}), one row per instance")
-        batch = costs.shape[0]
-        if batch < 1:
-            raise ValueError("an empty batch: costs needs at least one row (B >= 1)")
-        if self.b_lower is not None and np.size(self.b_lower) and np.max(self.b_lower) != -np.inf:
-            raise ValueError("dual_gradient_ascent needs one-sided inequalities: b_lower must be None or all -inf")
+        costs, batch = check_costs(costs, self.nb_variables)
+        require_one_sided(self.b_lower)
         start = time.perf_counter()
-        for name in ("distance_to_ground_truth", "distanceToGroundTruthAfterRounding", "opttime_curve", "dopttime_curve",
-                     "pobj_curve", "dobj_curve", "pobjbound", "max_violated_inequality", "max_violated_equality",
-                     "max_violated_constraint", "itrn_curve"):
-            setattr(self, name, [])
+        _reset_curves(self)
 
-        def record(niter, solution, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
-            if ground_truth is not None:   # instance by instance: the expressions (and so the sums) of ``solve``
-                picked = [solution[k][ground_truth_indices] for k in range(batch)]
-                self.distance_to_ground_truth.append(np.array([np.mean(np.abs(ground_truth - p)) for p in picked]))
-                self.distanceToGroundTruthAfterRounding.append(np.array([np.mean(np.abs(ground_truth - np.round(p))) for p in picked]))
-            self.itrn_curve.append(niter)
-            self.opttime_curve.append(duration)
-            self.dopttime_curve.append(duration)
-            self.dobj_curve.append(np.full(batch, energy2, dtype=np.float64))
-            self.pobj_curve.append(np.full(batch, energy1, dtype=np.float64))
-            self.max_violated_constraint.append(np.array([self.max_constraint_violation(solution[k]) for k in range(batch)]))
-            self.max_violated_equality.append(np.full(batch, max_violated_equality, dtype=np.float64))
-            self.max_violated_inequality.append(np.full(batch, max_violated_inequality, dtype=np.float64))
-
+        record = _batch_recorder(self, batch, ground_truth, ground_truth_indices, mean=_mean_each)
         x, y_eq, y_ineq, report = _dga_batch_run(self, costs, nb_iter, record, None, None, max_time, lower_bounds, upper_bounds, None)
         self.dual_multipliers = (y_eq, y_ineq)
         self.dual_lower_bounds = report[:, 0].copy()
         elapsed = time.perf_counter() - start
         return (x, elapsed) if get_timing else x
-
-
-_CURVES = ("distance_to_ground_truth", "distanceToGroundTruthAfterRounding", "opttime_curve", "dopttime_curve", "pobj_curve",
-           "dobj_curve", "pobjbound", "max_violated_inequality", "max_violated_equality", "max_violated_constraint", "itrn_curve")
 
 
 def solve_many(lps, method="chambolle_pock_ppd", get_timing=True, nb_iter=10000, max_time=None, nb_iter_plot=10):
@@ -719,8 +709,7 @@ def solve_many(lps, method="chambolle_pock_ppd", get_timing=True, nb_iter=10000,
     start = time.perf_counter()
     problems, maps = [], []
     for lp in lps:
-        for name in _CURVES:
-            setattr(lp, name, [])
+        _reset_curves(lp)
         reduced = copy.deepcopy(lp)
         free, shift = reduced.remove_fixed_variables()
         if reduced.nb_variables < 1:
@@ -736,20 +725,8 @@ def solve_many(lps, method="chambolle_pock_ppd", get_timing=True, nb_iter=10000,
         full[free_ids] = sol
         return full - shift
 
-    def record(niter, solutions, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
-        for k, lp in enumerate(lps):
-            solution = expand(k, solutions[k])
-            lp.itrn_curve.append(niter)
-            lp.opttime_curve.append(duration)
-            lp.dopttime_curve.append(duration)
-            lp.dobj_curve.append(energy2[k])
-            lp.pobj_curve.append(energy1[k])
-            lp.max_violated_constraint.append(lp.max_constraint_violation(solution))
-            lp.max_violated_equality.append(max_violated_equality[k])
-            lp.max_violated_inequality.append(max_violated_inequality[k])
-
-    sols, _ = chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=nb_iter, callback_func=record, max_time=max_time,
-                                      nb_iter_plot=nb_iter_plot)
+    sols, _ = chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=nb_iter, callback_func=_list_recorder(lps, expand),
+                                      max_time=max_time, nb_iter_plot=nb_iter_plot)
     xs = [expand(k, sol) for k, sol in enumerate(sols)]
     elapsed = time.perf_counter() - start
     return (xs, elapsed) if get_timing else xs
@@ -773,24 +750,9 @@ def solve_dga_many(lps, get_timing=True, nb_iter=10000, max_time=None):
         raise ValueError("an empty list of LPs")
     start = time.perf_counter()
     for lp in lps:
-        for name in _CURVES:
-            setattr(lp, name, [])
-    frozen = []
-
-    def record(niter, solutions, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
-        for k, lp in enumerate(lps):
-            if frozen[k]:   # its single solve returns before the first report
-                continue
-            lp.itrn_curve.append(niter)
-            lp.opttime_curve.append(duration)
-            lp.dopttime_curve.append(duration)
-            lp.dobj_curve.append(energy2)
-            lp.pobj_curve.append(energy1)
-            lp.max_violated_constraint.append(lp.max_constraint_violation(solutions[k]))
-            lp.max_violated_equality.append(max_violated_equality)
-            lp.max_violated_inequality.append(max_violated_inequality)
-
-    xs, y_eqs, y_ineqs, report = _dga_many_run(lps, nb_iter, record, None, None, max_time, frozen_out=frozen)
+        _reset_curves(lp)
+    frozen = []   # a frozen LP records nothing: its single solve returns before the first report
+    xs, y_eqs, y_ineqs, report = _dga_many_run(lps, nb_iter, _list_recorder(lps, skip=frozen), None, None, max_time, frozen_out=frozen)
     for k, lp in enumerate(lps):
         lp.dual_multipliers = (y_eqs[k], y_ineqs[k])
         lp.dual_lower_bound = float(report[k, 0])

@@ -158,8 +158,7 @@ struct DgaSearch {
     DevBuf<unsigned char> sort_tmp;
     size_t sort_bytes = 0;
     DevBuf<double> rnd;
-    std::vector<double> rnd_host;          // the draws from rnd_base on
-    unsigned long long rnd_base = 0;       // index (in the stream of draws) of rnd[0]
+    DgaDrawWindow draws;                   // the host's view of rnd (slp_dga_draws.h)
     StageTimer timer;
 };
 
@@ -195,14 +194,8 @@ void search_setup(DgaSearch &w, i64 n, int path) {
 void search_push_random(DgaSearch &w, const double *r, i64 count) {
     DgaCtl h;
     w.ctl.download(&h, 1);
-    const unsigned long long taken = h.consumed;
-    if (taken > w.rnd_base) {
-        const size_t drop = std::min<size_t>((size_t)(taken - w.rnd_base), w.rnd_host.size());
-        w.rnd_host.erase(w.rnd_host.begin(), w.rnd_host.begin() + (ptrdiff_t)drop);
-        w.rnd_base = taken;   // (a search that ran dry moved `consumed` past the buffer: the stream continues from there)
-    }
-    w.rnd_host.insert(w.rnd_host.end(), r, r + count);
-    if (!w.rnd_host.empty()) w.rnd.upload(w.rnd_host.data(), w.rnd_host.size());
+    w.draws.push(r, count, h.consumed, kJump);
+    if (w.draws.size()) w.rnd.upload(w.draws.data(), (size_t)w.draws.size());
 }
 
 // g (m values, already on the device), its partial results -> the block's scalars -> d = K^T g -> the step in ctl->t
@@ -213,11 +206,11 @@ void search_run(DgaSearch &w, slp_matrix *k, i64 m, const double *g, const doubl
     if (m > 0) matrix_spmv(k, true, g, w.d.p, SLP_ORDER_SEQUENTIAL);
     else w.d.zero();
     w.timer.mark(ST_PRODUCTS);
-    const unsigned long long rc = (unsigned long long)w.rnd_host.size();
+    const unsigned long long rb = w.draws.base, rc = w.draws.size();
     if (w.fused) {
         int npad = w.npad;
         hipLaunchKernelGGL(k_dga_fused, dim3(1), dim3(kDgaFusedThreads), fused_lds_bytes(npad), st, w.n, npad, w.d.p, cbar, lb, ub, w.ctl.p,
-                           w.rnd.p, w.rnd_base, rc, ineq);
+                           w.rnd.p, rb, rc, ineq);
         SLP_HIP(hipGetLastError());
         w.timer.mark(ST_FUSED);
         return;
@@ -234,7 +227,7 @@ void search_run(DgaSearch &w, slp_matrix *k, i64 m, const double *g, const doubl
                        w.B.p);
     SLP_HIP(hipGetLastError());
     w.timer.mark(ST_SCANS);
-    hipLaunchKernelGGL(k_dga_search, dim3(1), dim3(kWave), 0, st, w.ctl.p, w.cols_sorted.p, cbar, w.d.p, w.F.p, w.B.p, w.rnd.p, w.rnd_base, rc,
+    hipLaunchKernelGGL(k_dga_search, dim3(1), dim3(kWave), 0, st, w.ctl.p, w.cols_sorted.p, cbar, w.d.p, w.F.p, w.B.p, w.rnd.p, rb, rc,
                        ineq);
     SLP_HIP(hipGetLastError());
     w.timer.mark(ST_REST);
@@ -248,8 +241,6 @@ struct slp_dga {
     DevBuf<double> b, c, lb, ub, y, x, cbar, se, si, ymask, ax, g, rcbar, rx, rax, rpart;
     DgaSearch w;
     i64 iters = 0;
-    unsigned long long draws_bound = 0;   // no more draws than this were taken so far (2 per iteration since the last read)
-    unsigned int host_flags = 0;
 };
 
 namespace {
@@ -298,9 +289,9 @@ void dga_iteration(slp_dga *s) {
 unsigned int dga_read_ctl(slp_dga *s, DgaCtl *out) {
     DgaCtl h;
     s->w.ctl.download(&h, 1);
-    s->draws_bound = h.consumed;
+    s->w.draws.observe(h.consumed);
     if (out) *out = h;
-    return h.flags | s->host_flags;
+    return h.flags | (s->w.draws.dry ? (unsigned int)DGA_RAND_DRY : 0u);
 }
 
 }  // namespace
@@ -368,13 +359,7 @@ int slp_dga_path(const slp_dga *s) { return s ? (s->w.fused ? 1 : 2) : -1; }
 int slp_dga_iterate(slp_dga *s, int64_t k) {
     SLP_API_INT({
         SLP_REQUIRE(s && k >= 0, "slp_dga_iterate: bad arguments");
-        for (i64 it = 0; it < k; ++it) {
-            const unsigned long long have = s->w.rnd_base + (unsigned long long)s->w.rnd_host.size();
-            if (s->draws_bound + 2 > have) {   // at most two tie draws per iteration: the buffer could run dry
-                s->host_flags |= DGA_RAND_DRY;
-                break;
-            }
-            s->draws_bound += 2;
+        for (i64 it = 0; it < k && s->w.draws.reserve(1); ++it) {   // at most two tie draws per iteration
             dga_iteration(s);
             ++s->iters;
         }
@@ -388,7 +373,6 @@ int slp_dga_push_random(slp_dga *s, const double *draws, int64_t count) {
         SLP_REQUIRE(s && count >= 0 && (draws || count == 0), "slp_dga_push_random: bad arguments");
         search_push_random(s->w, draws, count);
         dga_read_ctl(s, nullptr);
-        s->host_flags &= ~(unsigned int)DGA_RAND_DRY;
     })
 }
 
@@ -398,7 +382,7 @@ int slp_dga_status(slp_dga *s, int64_t out[4]) {
         DgaCtl h;
         out[0] = (int64_t)dga_read_ctl(s, &h);
         out[1] = (int64_t)h.consumed;
-        out[2] = (int64_t)(s->w.rnd_base + s->w.rnd_host.size() - h.consumed);
+        out[2] = s->w.draws.left();
         out[3] = s->iters;
     })
 }
@@ -431,8 +415,7 @@ int slp_dga_report(slp_dga *s, double out[3]) {
 int slp_dga_timing(slp_dga *s, int on) {
     SLP_API_INT({
         SLP_REQUIRE(s, "slp_dga_timing: NULL handle");
-        s->w.timer.on = on != 0;
-        if (on) s->w.timer.used = 0;
+        s->w.timer.set(on);
     })
 }
 

@@ -237,10 +237,7 @@ struct slp_batch_dga {
     size_t sort_bytes1 = 0, sort_bytes2 = 0;
     // the shared stream of tie draws
     DevBuf<double> rnd;
-    std::vector<double> rnd_host;       // the draws from rnd_base on
-    unsigned long long rnd_base = 0;    // index (in the stream of draws) of rnd[0]
-    unsigned long long draws_bound = 0; // no instance has taken more draws than this (2 per iteration since the last read)
-    unsigned int host_flags = 0;
+    DgaDrawWindow draws;   // the host's view of rnd (slp_dga_draws.h)
     i64 iters = 0;
     StageTimer timer;
 };
@@ -331,10 +328,10 @@ void dgab_block(slp_batch_dga *s, i64 r0, i64 r1, int ineq) {
     hipLaunchKernelGGL(k_dgab_product, grid2(n, B), dim3(kBlock), 0, st, n, m, at.ptr.p, at.idx.p, at.val.p, s->g.p, s->ctl.p, 1, s->d.p);
     SLP_HIP(hipGetLastError());
     s->timer.mark(ST_PRODUCTS);
-    const unsigned long long rc = (unsigned long long)s->rnd_host.size();
+    const unsigned long long rb = s->draws.base, rc = s->draws.size();
     if (s->fused) {
         hipLaunchKernelGGL(k_dgab_fused, dim3(ub), dim3(kDgaFusedThreads), fused_lds_bytes(s->npad), st, (int)n, s->npad, s->d.p, s->cbar.p,
-                           s->lb.p, s->lb_stride, s->ub.p, s->ub_stride, s->ctl.p, s->rnd.p, s->rnd_base, rc, ineq);
+                           s->lb.p, s->lb_stride, s->ub.p, s->ub_stride, s->ctl.p, s->rnd.p, rb, rc, ineq);
         SLP_HIP(hipGetLastError());
         s->timer.mark(ST_FUSED);
     } else {
@@ -369,7 +366,7 @@ void dgab_block(slp_batch_dga *s, i64 r0, i64 r1, int ineq) {
         SLP_HIP(hipGetLastError());
         s->timer.mark(ST_SCANS);
         hipLaunchKernelGGL(k_dgab_search, dim3(ub), dim3(kWave), 0, st, (int)n, s->ctl.p, s->cols_sorted.p, s->cbar.p, s->d.p, s->F.p, s->Bw.p,
-                           s->rnd.p, s->rnd_base, rc, ineq);
+                           s->rnd.p, rb, rc, ineq);
         SLP_HIP(hipGetLastError());
         s->timer.mark(ST_REST);
     }
@@ -396,7 +393,7 @@ void dgab_read_ctl(slp_batch_dga *s, std::vector<DgaCtl> &h) {
     s->ctl.download(h.data(), (size_t)s->B);
     unsigned long long mx = 0;
     for (const DgaCtl &c : h) mx = std::max(mx, c.consumed);
-    s->draws_bound = mx;
+    s->draws.observe(mx);
 }
 
 void dgab_report(slp_batch_dga *s, double *out) {
@@ -517,13 +514,7 @@ int slp_batch_dga_sort(const slp_batch_dga *s) { return s ? (s->fused ? 0 : (s->
 int slp_batch_dga_iterate(slp_batch_dga *s, int64_t k) {
     SLP_API_INT({
         SLP_REQUIRE(s && k >= 0, "slp_batch_dga_iterate: bad arguments");
-        for (i64 it = 0; it < k; ++it) {
-            const unsigned long long have = s->rnd_base + (unsigned long long)s->rnd_host.size();
-            if (s->draws_bound + 2 > have) {   // at most two tie draws per instance and iteration: the buffer could run dry
-                s->host_flags |= DGA_RAND_DRY;
-                break;
-            }
-            s->draws_bound += 2;
+        for (i64 it = 0; it < k && s->draws.reserve(1); ++it) {   // at most two tie draws per instance and iteration
             dgab_iteration(s);
             ++s->iters;
         }
@@ -537,18 +528,7 @@ int slp_batch_dga_push_random(slp_batch_dga *s, const double *draws, int64_t cou
         SLP_REQUIRE(s && count >= 0 && (draws || count == 0), "slp_batch_dga_push_random: bad arguments");
         std::vector<DgaCtl> h;
         dgab_read_ctl(s, h);
-        // the draws every moving instance has passed are dropped from the front
-        unsigned long long taken = ~0ull;
-        for (const DgaCtl &c : h)
-            if (!c.frozen) taken = std::min(taken, c.consumed);
-        if (taken != ~0ull && taken > s->rnd_base) {
-            const size_t drop = std::min<size_t>((size_t)(taken - s->rnd_base), s->rnd_host.size());
-            s->rnd_host.erase(s->rnd_host.begin(), s->rnd_host.begin() + (ptrdiff_t)drop);
-            s->rnd_base += drop;
-        }
-        s->rnd_host.insert(s->rnd_host.end(), draws, draws + count);
-        if (!s->rnd_host.empty()) s->rnd.upload(s->rnd_host.data(), s->rnd_host.size());
-        s->host_flags &= ~(unsigned int)DGA_RAND_DRY;
+        dga_push_draws(h, [](size_t) { return 0ull; }, s->draws, s->rnd, draws, count, kDropFirst);
     })
 }
 
@@ -557,12 +537,7 @@ int slp_batch_dga_status(slp_batch_dga *s, int64_t *out) {
         SLP_REQUIRE(s && out, "slp_batch_dga_status: NULL argument");
         std::vector<DgaCtl> h;
         dgab_read_ctl(s, h);
-        for (i64 k = 0; k < s->B; ++k) {
-            out[2 * k] = (int64_t)(h[(size_t)k].flags | s->host_flags);
-            out[2 * k + 1] = (int64_t)h[(size_t)k].consumed;
-        }
-        out[2 * s->B] = (int64_t)(s->rnd_base + s->rnd_host.size()) - (int64_t)s->draws_bound;
-        out[2 * s->B + 1] = s->iters;
+        dga_status_out(h, s->draws, s->iters, out);
     })
 }
 
@@ -571,7 +546,7 @@ int slp_batch_dga_frozen(slp_batch_dga *s, int32_t *out) {
         SLP_REQUIRE(s && out, "slp_batch_dga_frozen: NULL argument");
         std::vector<DgaCtl> h;
         dgab_read_ctl(s, h);
-        for (i64 k = 0; k < s->B; ++k) out[k] = h[(size_t)k].frozen;
+        dga_frozen_out(h, out);
     })
 }
 
@@ -593,8 +568,7 @@ int slp_batch_dga_report(slp_batch_dga *s, double *out) {
 int slp_batch_dga_timing(slp_batch_dga *s, int on) {
     SLP_API_INT({
         SLP_REQUIRE(s, "slp_batch_dga_timing: NULL handle");
-        s->timer.on = on != 0;
-        if (on) s->timer.used = 0;
+        s->timer.set(on);
     })
 }
 

@@ -213,10 +213,7 @@ struct slp_many_dga {
     DevBuf<DgaCtl> ctl;
     // the shared stream of tie draws
     DevBuf<double> rnd;
-    std::vector<double> rnd_host;       // the draws from rnd_base on
-    unsigned long long rnd_base = 0;    // position (in the stream of draws) of rnd[0]
-    unsigned long long draws_bound = 0; // no LP stands behind this position (2 per iteration since the last read)
-    unsigned int host_flags = 0;
+    DgaDrawWindow draws;   // the host's view of rnd (slp_dga_draws.h)
     i64 iters = 0;
     StageTimer timer;
 };
@@ -234,8 +231,8 @@ DgmArgs dgm_args(const slp_many_dga *s) {
     r.part_gb = s->part_gb.p; r.part_min = s->part_min.p; r.part_any = s->part_any.p;
     r.ctl = s->ctl.p;
     r.rnd = s->rnd.p;
-    r.rnd_base = s->rnd_base;
-    r.rnd_count = (unsigned long long)s->rnd_host.size();
+    r.rnd_base = s->draws.base;
+    r.rnd_count = s->draws.size();
     return r;
 }
 
@@ -303,7 +300,7 @@ void dgm_read_ctl(slp_many_dga *s, std::vector<DgaCtl> &h) {
     unsigned long long mx = 0;
     for (size_t k = 0; k < h.size(); ++k)
         if (!h[k].frozen) mx = std::max(mx, s->lps[k].draw_offset + h[k].consumed);
-    s->draws_bound = mx;
+    s->draws.observe(mx);
 }
 
 }  // namespace
@@ -427,15 +424,9 @@ int slp_many_dga_iterate(slp_many_dga *s, int64_t k) {
         SLP_REQUIRE(s && k >= 0, "slp_many_dga_iterate: bad arguments");
         hipStream_t st = ctx().stream;
         for (i64 done = 0; done < k;) {
-            const unsigned long long have = s->rnd_base + (unsigned long long)s->rnd_host.size();
             // at most two tie draws per LP and iteration: iterations the buffer cannot run dry in
-            const i64 safe = have > s->draws_bound ? (i64)std::min<unsigned long long>((have - s->draws_bound) / 2, 1u << 30) : 0;
-            const int it = (int)std::min<i64>(std::min<i64>(s->kmax, k - done), safe);
-            if (it < 1) {
-                s->host_flags |= DGA_RAND_DRY;
-                break;
-            }
-            s->draws_bound += 2 * (unsigned long long)it;
+            const int it = (int)s->draws.reserve(std::min<i64>(s->kmax, k - done));
+            if (it < 1) break;
             s->timer.mark(-1);
             hipLaunchKernelGGL(k_dgm_iterate, dim3((unsigned)s->count), dim3(kDgaFusedThreads), dgm_lds_bytes(s), st, dgm_args(s), it);
             SLP_HIP(hipGetLastError());
@@ -451,18 +442,8 @@ int slp_many_dga_push_random(slp_many_dga *s, const double *draws, int64_t count
         SLP_REQUIRE(s && count >= 0 && (draws || count == 0), "slp_many_dga_push_random: bad arguments");
         std::vector<DgaCtl> h;
         dgm_read_ctl(s, h);
-        s->rnd_host.insert(s->rnd_host.end(), draws, draws + count);
-        // the draws every moving LP has passed (or never reaches: the start of the stream went into the default starts) are dropped
-        unsigned long long taken = ~0ull;
-        for (size_t k = 0; k < h.size(); ++k)
-            if (!h[k].frozen) taken = std::min(taken, s->lps[k].draw_offset + h[k].consumed);
-        if (taken != ~0ull && taken > s->rnd_base) {
-            const size_t drop = std::min<size_t>((size_t)(taken - s->rnd_base), s->rnd_host.size());
-            s->rnd_host.erase(s->rnd_host.begin(), s->rnd_host.begin() + (ptrdiff_t)drop);
-            s->rnd_base += drop;
-        }
-        if (!s->rnd_host.empty()) s->rnd.upload(s->rnd_host.data(), s->rnd_host.size());
-        s->host_flags &= ~(unsigned int)DGA_RAND_DRY;
+        // (an LP never reaches what lies before its offset: the start of the stream went into the default starts)
+        dga_push_draws(h, [s](size_t k) { return s->lps[k].draw_offset; }, s->draws, s->rnd, draws, count, kAppendFirst);
     })
 }
 
@@ -471,12 +452,7 @@ int slp_many_dga_status(slp_many_dga *s, int64_t *out) {
         SLP_REQUIRE(s && out, "slp_many_dga_status: NULL argument");
         std::vector<DgaCtl> h;
         dgm_read_ctl(s, h);
-        for (i64 k = 0; k < s->count; ++k) {
-            out[2 * k] = (int64_t)(h[(size_t)k].flags | s->host_flags);
-            out[2 * k + 1] = (int64_t)h[(size_t)k].consumed;
-        }
-        out[2 * s->count] = (int64_t)(s->rnd_base + s->rnd_host.size()) - (int64_t)s->draws_bound;
-        out[2 * s->count + 1] = s->iters;
+        dga_status_out(h, s->draws, s->iters, out);
     })
 }
 
@@ -485,7 +461,7 @@ int slp_many_dga_frozen(slp_many_dga *s, int32_t *out) {
         SLP_REQUIRE(s && out, "slp_many_dga_frozen: NULL argument");
         std::vector<DgaCtl> h;
         dgm_read_ctl(s, h);
-        for (i64 k = 0; k < s->count; ++k) out[k] = h[(size_t)k].frozen;
+        dga_frozen_out(h, out);
     })
 }
 
@@ -503,8 +479,7 @@ int slp_many_dga_report(slp_many_dga *s, double *out) {
 int slp_many_dga_timing(slp_many_dga *s, int on) {
     SLP_API_INT({
         SLP_REQUIRE(s, "slp_many_dga_timing: NULL handle");
-        s->timer.on = on != 0;
-        if (on) s->timer.used = 0;
+        s->timer.set(on);
     })
 }
 

@@ -12,6 +12,7 @@
 
 #include "slp_common.h"
 #include "slp_kernels.h"
+#include "slp_dga_draws.h"
 
 namespace slp {
 
@@ -554,6 +555,10 @@ struct StageTimer {
     ~StageTimer() {
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     }
+    void set(int enable) {
+        on = enable != 0;
+        if (on) used = 0;
+    }
     void mark(int stage) {
         if (!on || used >= (1u << 20)) return;
         if (ev.size() <= used) {
@@ -578,5 +583,34 @@ struct StageTimer {
         }
     }
 };
+
+// ---- what the batch and the list handles answer alike, from the controls `h` just read back and the window of draws --------------
+
+// (flags, tie draws taken) per reader, then the draws left behind the furthest reader and the iterations done
+inline void dga_status_out(const std::vector<DgaCtl> &h, const DgaDrawWindow &w, i64 iters, int64_t *out) {
+    const size_t count = h.size();
+    const unsigned int dry = w.dry ? (unsigned int)DGA_RAND_DRY : 0u;
+    for (size_t k = 0; k < count; ++k) {
+        out[2 * k] = (int64_t)(h[k].flags | dry);
+        out[2 * k + 1] = (int64_t)h[k].consumed;
+    }
+    out[2 * count] = w.left();
+    out[2 * count + 1] = iters;
+}
+
+inline void dga_frozen_out(const std::vector<DgaCtl> &h, int32_t *out) {
+    for (size_t k = 0; k < h.size(); ++k) out[k] = h[k].frozen;
+}
+
+// what push_random does once the controls are read: `offset(k)` is where reader k's positions begin in the stream
+template <class Offset>
+inline void dga_push_draws(const std::vector<DgaCtl> &h, Offset offset, DgaDrawWindow &w, DevBuf<double> &rnd, const double *draws,
+                           int64_t count, DgaOverrun mode) {
+    unsigned long long passed = ~0ull;   // the draws every moving reader has passed are dropped from the front
+    for (size_t k = 0; k < h.size(); ++k)
+        if (!h[k].frozen) passed = std::min(passed, offset(k) + h[k].consumed);
+    w.push(draws, count, passed, mode);
+    if (w.size()) rnd.upload(w.data(), (size_t)w.size());
+}
 
 }  // namespace slp

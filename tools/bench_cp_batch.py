@@ -29,10 +29,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-
-def spread(v):
-    v = np.asarray(v, dtype=np.float64)
-    return float((v.max() - v.min()) / np.median(v)) if v.size > 1 else 0.0
+from _bench_util import spread  # noqa: E402
 
 
 def single_state(c, ineq, b, lb, ub, csr):

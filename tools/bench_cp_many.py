@@ -33,12 +33,9 @@ import scipy.sparse
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+
+from _bench_util import spread  # noqa: E402
 sys.path.insert(0, os.path.join(REPO, "tests"))
-
-
-def spread(v):
-    v = np.asarray(v, dtype=np.float64)
-    return float((v.max() - v.min()) / np.median(v)) if v.size > 1 else 0.0
 
 
 def perturbed(problem, count, seed):

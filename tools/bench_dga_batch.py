@@ -23,24 +23,14 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
+from _bench_util import spread, timed_between_events  # noqa: E402
+
 FUSED_MAX = 8192
-
-
-def spread(v):
-    v = np.asarray(v, dtype=np.float64)
-    return float((v.max() - v.min()) / np.median(v)) if v.size > 1 else 0.0
 
 
 def timed(lib, state, k):
     """Milliseconds per iteration of `k` iterations between two HIP events; the draws are pushed first."""
-    from pysparselp_amd import _lib
-
-    state.push_random(np.random.RandomState(17).random_sample(2 * k + 2))
-    ms = np.zeros(1)
-    _lib.check(lib.slp_timer_start())
-    state.iterate(k, refill=False)
-    _lib.check(lib.slp_timer_stop(_lib.ptr(ms)))
-    return float(ms[0]) / k
+    return timed_between_events(lib, [state], k, lambda st, k: st.push_random(np.random.RandomState(17).random_sample(2 * k + 2))) / k
 
 
 def stages(state, k):

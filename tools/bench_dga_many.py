@@ -23,6 +23,8 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
+from _bench_util import timed_between_events  # noqa: E402
+
 
 class LP:
     def __init__(self, c, a_eq, b_eq, a_ineq, b_upper, lb, ub):
@@ -58,16 +60,7 @@ def fill(state, k):
 
 def timed(lib, states, k):
     """Milliseconds for `k` iterations of every state, one state after another, between two HIP events."""
-    from pysparselp_amd import _lib
-
-    for st in states:
-        fill(st, k)
-    ms = np.zeros(1)
-    _lib.check(lib.slp_timer_start())
-    for st in states:
-        st.iterate(k, refill=False)
-    _lib.check(lib.slp_timer_stop(_lib.ptr(ms)))
-    return float(ms[0])
+    return timed_between_events(lib, states, k, fill)
 
 
 def iterations_for(lib, states, target_ms, cap):
