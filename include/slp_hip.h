@@ -413,6 +413,52 @@ int slp_admm_batch_form(const slp_admm_batch *s);
 /* As slp_admm_bench: average GPU milliseconds per batched iteration (:143-268 for all instances) over k, by HIP events. */
 int slp_admm_batch_bench(slp_admm_batch *s, int64_t k, double *ms);
 
+/* ---- ADMM on a list of LPs with different matrices ------------------------ *
+ * No counterpart in the reference: `count` calls of lp_admm (ADMM.py:47-269, as shipped: one projected Gauss-Seidel sweep per
+ * iteration, :135,:162) on LPs of any shapes, one workgroup per LP, whole iterations inside one launch
+ * (csrc/slp_admm_many.hip).  Every LP is bit for bit the iterate of slp_admm in SLP_ORDER_SEQUENTIAL on that LP alone.
+ * The LPs arrive as ONE block-diagonal LP: n, m_eq, m_ineq [count] give the shapes; the columns of LP k are offset by
+ * sum_{l<k} n_l; the equality CSR holds the equality rows of all LPs (LP 0, LP 1, ...) with b_eq, the inequality CSR the
+ * inequality rows of all LPs with b_lower / b_upper (NULL: -inf / +inf); c, lb, ub, x0 are concatenated LP by LP; x0 may be
+ * NULL (zeros); the equality arguments may be NULL when no LP has an equality row.  The set-up chain of slp_admm_create_lp
+ * (ADMM.py:73-101) runs once on that composite; gamma_eq, gamma_ineq and use_preconditioning are one value for the list.
+ * Two forms of the same arithmetic, chosen per LP from its shape: x, y, lambda in LDS for the whole launch when 2 N + m
+ * (N = n + m_ineq, m = m_eq + m_ineq) is at most slp_admm_many_lds_limit() doubles, else in global memory
+ * (SLP_ADMM_MANY_FORM=lds|global forces one for all LPs; lds on an LP that does not fit is an error).  SLP_ADMM_MANY_KMAX=<k>
+ * lowers the number of iterations one launch may hold; the iterates do not depend on it.
+ * NULL + slp_last_error(), and nothing left allocated: count < 1; an LP without a variable; no inequality block
+ * (tools.py:92); a row pointer not starting at 0 or decreasing; a column index outside its LP's columns; 2^31 or more
+ * variables + slacks or rows; the list does not fit the device -- checked with slp_device_memory before anything is allocated. */
+typedef struct slp_admm_many slp_admm_many;
+slp_admm_many *slp_admm_many_create(int64_t count, const int64_t *n, const int64_t *m_eq, const int64_t *m_ineq,
+                                    const int64_t *eq_indptr, const int32_t *eq_indices, const double *eq_data, const double *b_eq,
+                                    const int64_t *in_indptr, const int32_t *in_indices, const double *in_data, const double *b_lower,
+                                    const double *b_upper, const double *c, const double *lb, const double *ub, const double *x0,
+                                    double gamma_eq, double gamma_ineq, int use_preconditioning);
+void slp_admm_many_destroy(slp_admm_many *s);
+/* k whole iterations (:148,:162,:259-263) of every LP, enqueued without host synchronisation; runs longer than the launch cap
+ * are split. */
+int slp_admm_many_iterate(slp_admm_many *s, int64_t k);
+/* Halves of one iteration around the reference's report (:213-248), as slp_admm_sweep_step / slp_admm_multiplier_step. */
+int slp_admm_many_sweep_step(slp_admm_many *s);
+int slp_admm_many_multiplier_step(slp_admm_many *s);
+/* out[3 k + 0..2]: the three numbers of slp_admm_report (:124-132,:221,:222) for LP k.  The maxima are exact; the energy is a
+ * sum in a fixed order of its own, a function of the shapes only. */
+int slp_admm_many_report(slp_admm_many *s, double *out);             /* count x 3 */
+/* LP by LP: the first n_k entries of every iterate (:268), or with full != 0 all N_k = n_k + m_ineq,k of its standard form. */
+int slp_admm_many_get_x(slp_admm_many *s, double *x, int full);      /* sum n_k, or sum N_k */
+int slp_admm_many_get_lambda(slp_admm_many *s, double *lam);         /* sum m_k, LP by LP, each [lambda_eq,k; lambda_ineq,k] (:261-263) */
+/* Dependency levels of LP k's sweep (gaussSiedel.pyx:131-152): those of the plan of that LP alone; -1 for a bad argument. */
+int64_t slp_admm_many_num_levels(const slp_admm_many *s, int64_t k);
+/* The form LP k runs in: 0 LDS, 1 global memory; -1 for a bad argument. */
+int slp_admm_many_form(const slp_admm_many *s, int64_t k);
+/* Doubles of x, y, lambda (2 N + m) an LP may hold in LDS. */
+int64_t slp_admm_many_lds_limit(void);
+/* Iterations (:143-268) one launch of the given form (0 LDS, 1 global memory) holds; 0 when no LP runs in it, -1 for a bad argument. */
+int64_t slp_admm_many_kmax(const slp_admm_many *s, int form);
+/* As slp_admm_bench: average GPU milliseconds per iteration of the whole list (:143-268 for all LPs) over k, by HIP events. */
+int slp_admm_many_bench(slp_admm_many *s, int64_t k, double *ms);
+
 /* ---- ADMM, matrix-free conjugate-gradient x-step ------------------------- *
  * The reference's own alternative x-step (ADMM.py:182-201 with
  * conjugateGradientLinearSolver.py:30-52, selected by its hard-coded flags

@@ -24,7 +24,7 @@ import time
 import numpy as np
 
 from . import _lib
-from ._batch import shared_or_batched
+from ._batch import concat, first_offsets, shared_or_batched, split_by
 from ._lib import ORDER_AUTO
 from .tools import convert_to_standard_form_with_bounds, normal_matrix, precondition_constraints
 
@@ -377,6 +377,278 @@ def lp_admm_batch(
                 state.iterate(k)
                 i += k
         return state.x(n)
+    finally:
+        state.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# a list of LPs with different matrices: one workgroup per LP
+def _admm_many_problem(k, problem):
+    """LP ``k`` of a list, validated (``ValueError``) without touching the library:
+    ``(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub)`` with the matrices as ``CsrArrays`` (``a_eq``: ``None`` for an LP without
+    equality rows) and the vectors as contiguous float64 arrays (``b_lower`` / ``b_upper``: -inf / +inf where absent)."""
+    from .tools import CsrArrays
+
+    try:
+        count = len(problem)
+    except TypeError:
+        count = -1
+    if count != 8:
+        raise ValueError(f"LP {k} is not a tuple of 8 entries (c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub)")
+    c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub = problem
+    c = _lib.f64(c)
+    if c.ndim != 1 or c.size < 1:
+        raise ValueError(f"LP {k}: c has shape {c.shape}, expected (n,) with n >= 1")
+    n = c.size
+    if not np.all(np.isfinite(c)):
+        raise ValueError(f"LP {k}: c has an entry that is not finite")
+    lb, ub = _lib.f64(lb), _lib.f64(ub)
+    for name, v in (("lb", lb), ("ub", ub)):
+        if v.shape != (n,):
+            raise ValueError(f"LP {k}: {name} has shape {v.shape}, c has {n} entries")
+        if np.any(np.isnan(v)):
+            raise ValueError(f"LP {k}: {name} has a NaN")
+    a_eq, a_ineq = CsrArrays.from_any(a_eq), CsrArrays.from_any(a_ineq)
+    if a_ineq is None:
+        raise ValueError(f"LP {k} has no inequality block: the reference cannot form the standard form without one (tools.py:92)")
+    if a_eq is not None and a_eq.shape[0] == 0:
+        a_eq, beq = None, None
+    for name, a in (("a_eq", a_eq), ("a_ineq", a_ineq)):
+        if a is not None:
+            if a.shape[1] != n:
+                raise ValueError(f"LP {k}: {name} has {a.shape[1]} columns, c has {n} entries")
+            if a.indptr.shape != (a.shape[0] + 1,) or a.indptr[0] != 0 or np.any(np.diff(a.indptr) < 0) or a.indptr[-1] != a.indices.size \
+                    or a.indices.size != a.data.size:
+                raise ValueError(f"LP {k}: {name} is not a well-formed CSR matrix")
+            if a.indices.size and (a.indices.min() < 0 or a.indices.max() >= n):
+                raise ValueError(f"LP {k}: {name} has a column index outside [0, {n})")
+
+    def rhs(name, v, rows, fill):
+        if v is None:
+            return np.full(rows, fill)
+        v = _lib.f64(v)
+        if v.shape != (rows,):
+            raise ValueError(f"LP {k}: {name} has shape {v.shape}, expected ({rows},)")
+        if np.any(np.isnan(v)):
+            raise ValueError(f"LP {k}: {name} has a NaN")
+        return v
+
+    if a_eq is not None:
+        if beq is None:
+            raise ValueError(f"LP {k}: a_eq without beq")
+        beq = rhs("beq", beq, a_eq.shape[0], 0.0)
+    b_lower = rhs("b_lower", b_lower, a_ineq.shape[0], -np.inf)
+    b_upper = rhs("b_upper", b_upper, a_ineq.shape[0], np.inf)
+    return c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub
+
+
+def admm_many_system(lps):
+    """The LPs ``(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub)`` of ``_admm_many_problem`` as the one block-diagonal LP
+    ``slp_admm_many_create`` takes -- pure numpy, no library.  A dict of:
+
+    ``n``, ``m_eq``, ``m_ineq``: the shapes, int64 arrays of length ``count``;
+    ``col0``, ``eq0``, ``in0``: first column, first row of the equality block and first row of the inequality block of every LP;
+    ``x0`` (``lam0``): where the LP's ``N_k = n_k + m_ineq,k`` standard-form unknowns (its ``m_k = m_eq,k + m_ineq,k`` multipliers)
+    begin in the LP-by-LP vectors the solver returns;
+    ``eq_indptr``, ``eq_indices``, ``eq_data``, ``b_eq``: the equality rows of all LPs (LP 0, LP 1, ...), the columns of LP k offset by
+    ``col0[k]``; ``in_indptr``, ``in_indices``, ``in_data``, ``b_lower``, ``b_upper``: the same for the inequality rows;
+    ``c``, ``lb``, ``ub`` concatenated LP by LP.
+
+    The standard form of this composite has all original variables first and all slacks after them, which keeps the relative
+    order of every LP's columns and rows: the set-up chain of ``lp_admm`` on the composite gives every LP the bits of its own."""
+    n = np.array([lp[0].size for lp in lps], dtype=np.int64)
+    m_eq = np.array([0 if lp[1] is None else lp[1].shape[0] for lp in lps], dtype=np.int64)
+    m_ineq = np.array([lp[3].shape[0] for lp in lps], dtype=np.int64)
+    if int(n.sum() + m_ineq.sum()) >= 2 ** 31 or int(m_eq.sum() + m_ineq.sum()) >= 2 ** 31:
+        raise ValueError("the list has 2^31 or more variables + slacks or rows in total")
+    col0 = first_offsets(n)
+    out = dict(n=n, m_eq=m_eq, m_ineq=m_ineq, col0=col0, eq0=first_offsets(m_eq), in0=first_offsets(m_ineq),
+               x0=first_offsets(n + m_ineq), lam0=first_offsets(m_eq + m_ineq))
+    for tag, part, rhs_names in (("eq", 1, (("b_eq", 2),)), ("in", 3, (("b_lower", 4), ("b_upper", 5)))):
+        ptr, idx, val, entries = [np.zeros(1, dtype=np.int64)], [], [], 0
+        for k, lp in enumerate(lps):
+            a = lp[part]
+            if a is None:
+                continue
+            ptr.append(entries + a.indptr[1:])
+            idx.append(a.indices.astype(np.int64) + col0[k])
+            val.append(a.data)
+            entries += int(a.indptr[-1])
+        out[tag + "_indptr"], out[tag + "_indices"], out[tag + "_data"] = concat(ptr, np.int64), concat(idx, np.int32), concat(val, np.float64)
+        for name, pos in rhs_names:
+            out[name] = concat([lp[pos] for lp in lps if lp[part] is not None], np.float64)
+    for name, pos in (("c", 0), ("lb", 6), ("ub", 7)):
+        out[name] = concat([lp[pos] for lp in lps], np.float64)
+    return out
+
+
+def _admm_many_starts(x0, lps):
+    """``x0`` of ``lp_admm_many`` checked against the LPs: ``None``, or a list with one start (or ``None``) per LP."""
+    if x0 is None:
+        return None
+    try:
+        given = len(x0)
+    except TypeError:
+        given = -1
+    if given != len(lps):
+        raise ValueError(f"x0 must be None or a sequence of {len(lps)} starts, one per LP")
+    x0 = [None if v is None else _lib.f64(v) for v in x0]
+    for k, v in enumerate(x0):
+        if v is not None:
+            if v.shape != lps[k][0].shape:
+                raise ValueError(f"LP {k}: x0 has shape {v.shape}, c has {lps[k][0].size} entries")
+            if not np.all(np.isfinite(v)):
+                raise ValueError(f"LP {k}: x0 has an entry that is not finite")
+    return x0
+
+
+def admm_many_lds_limit():
+    """Doubles of x, y, lambda (``2 N + m``) an LP may hold in LDS (``slp_admm_many_lds_limit``)."""
+    return int(_lib.load().slp_admm_many_lds_limit())
+
+
+class ADMMManyState:
+    """Device-resident ADMM state of a list of LPs (thin RAII wrapper of ``slp_admm_many``).  ``lps``: the LPs as
+    ``_admm_many_problem`` returns them; ``x0``: ``None`` or one start (or ``None``: zeros) per LP, as ``_admm_many_starts``
+    returns it."""
+
+    FORMS = ("lds", "global")
+
+    def __init__(self, lps, x0=None, gamma_eq=2, gamma_ineq=3, use_preconditioning=True):
+        if len(lps) < 1:
+            raise ValueError("an empty list of LPs")
+        s = admm_many_system(lps)
+        self.count = len(lps)
+        self.n, self.N, self.m = s["n"], s["n"] + s["m_ineq"], s["m_eq"] + s["m_ineq"]
+        self.system = s
+        start = None
+        if x0 is not None and any(v is not None for v in x0):
+            start = _lib.f64(np.concatenate([np.zeros(int(nk)) if v is None else _lib.f64(v) for v, nk in zip(x0, self.n)]))
+            assert start.size == int(self.n.sum())
+        has_eq = int(s["m_eq"].sum()) > 0
+        eq = tuple(_lib.ptr(s[name]) if has_eq else None for name in ("eq_indptr", "eq_indices", "eq_data", "b_eq"))
+        # all of the above needs no GPU; the library is loaded (and bound to a device) only now
+        self._l = _lib.lib()
+        self._h = _lib.check_handle(self._l.slp_admm_many_create(
+            self.count, _lib.ptr(s["n"]), _lib.ptr(s["m_eq"]), _lib.ptr(s["m_ineq"]), *eq, _lib.ptr(s["in_indptr"]),
+            _lib.ptr(s["in_indices"]), _lib.ptr(s["in_data"]), _lib.ptr(s["b_lower"]), _lib.ptr(s["b_upper"]), _lib.ptr(s["c"]),
+            _lib.ptr(s["lb"]), _lib.ptr(s["ub"]), _lib.ptr(start), float(gamma_eq), float(gamma_ineq), int(bool(use_preconditioning))))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._l.slp_admm_many_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def iterate(self, k):
+        _lib.check(self._l.slp_admm_many_iterate(self._h, int(k)))
+
+    def sweep_step(self):
+        _lib.check(self._l.slp_admm_many_sweep_step(self._h))
+
+    def multiplier_step(self):
+        _lib.check(self._l.slp_admm_many_multiplier_step(self._h))
+
+    def report(self):
+        """``(count, 3)``: augmented-Lagrangian energy, max |A x - b|, max(0, -min x) per LP."""
+        out = np.zeros((self.count, 3))
+        _lib.check(self._l.slp_admm_many_report(self._h, _lib.ptr(out)))
+        return out
+
+    def x(self, full=False):
+        """Per LP the first ``n_k`` entries of its iterate, or with ``full`` all ``N_k`` of its standard form."""
+        sizes = self.N if full else self.n
+        out = np.empty(int(sizes.sum()))
+        _lib.check(self._l.slp_admm_many_get_x(self._h, _lib.ptr(out), int(bool(full))))
+        return split_by(out, sizes)
+
+    def lam(self):
+        """Per LP ``[lambda_eq; lambda_ineq]``."""
+        out = np.empty(int(self.m.sum()))
+        _lib.check(self._l.slp_admm_many_get_lambda(self._h, _lib.ptr(out)))
+        return split_by(out, self.m)
+
+    def _of_lp(self, k):
+        if not 0 <= int(k) < self.count:
+            raise IndexError(f"LP {k} of {self.count}")
+        return int(k)
+
+    def num_levels(self, k):
+        """Dependency levels of LP ``k``'s sweep: those of the plan of that LP alone."""
+        return int(self._l.slp_admm_many_num_levels(self._h, self._of_lp(k)))
+
+    def form(self, k):
+        """``"lds"`` or ``"global"``: where LP ``k`` keeps x, y, lambda during a launch."""
+        return self.FORMS[int(self._l.slp_admm_many_form(self._h, self._of_lp(k)))]
+
+    def kmax(self, form):
+        """Iterations one launch of the form (``"lds"`` / ``"global"``) holds; 0 when no LP runs in it."""
+        return int(self._l.slp_admm_many_kmax(self._h, self.FORMS.index(form)))
+
+    def bench(self, k):
+        """GPU milliseconds per iteration of the whole list over ``k`` iterations (HIP events)."""
+        ms = np.zeros(1)
+        _lib.check(self._l.slp_admm_many_bench(self._h, int(k), _lib.ptr(ms)))
+        return float(ms[0])
+
+
+def lp_admm_many(
+    problems,
+    x0=None,
+    gamma_eq=2,
+    gamma_ineq=3,
+    nb_iter=100,
+    callback_func=None,
+    max_time=None,
+    use_preconditioning=True,
+    nb_iter_plot=10,
+):
+    """``lp_admm`` for a list of LPs whose matrices differ (extension; the reference solves one LP per call).
+
+    ``problems`` is a sequence of 8-tuples ``(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub)``, each as ``lp_admm`` takes them
+    (``a_eq`` may be ``None`` or a matrix without rows; the inequality block is required, tools.py:92); ``x0`` is ``None`` or a
+    sequence with one start (or ``None``) per LP; ``gamma_eq``, ``gamma_ineq`` and ``use_preconditioning`` are shared.  Every shape,
+    finiteness and column-index error is a ``ValueError`` that names the LP, raised before the library is loaded.  The LPs become
+    one block-diagonal LP whose set-up chain (ADMM.py:73-101) runs once on the device; every LP is then one workgroup that runs
+    whole iterations inside one launch, its iterates in LDS where they fit (pysparselp_amd/csrc/slp_admm_many.hip); every LP is
+    bit for bit what ``lp_admm(..., order=ORDER_SEQUENTIAL)`` computes for it alone.
+
+    The loop is that of ``lp_admm``: ``nb_iter + 1`` sweeps, a report after those with ``i % nb_iter_plot == 0`` --
+    ``callback_func(i, xs, energy, energy, elapsed, max_violated_equality, max_violated_inequality)`` with ``xs`` a list of
+    arrays and the rest arrays of length ``count``; ``max_time`` stops the whole list at a report.  Returns the list of ``x``.
+
+    Under a communicator every rank solves the whole list (a replica).  For LPs that share one matrix ``lp_admm_batch`` builds
+    ``M`` and its plan once for all of them.
+    """
+    try:
+        count = len(problems)
+    except TypeError:
+        raise ValueError("problems must be a sequence of 8-tuples (c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub)") from None
+    if count < 1:
+        raise ValueError("an empty list of LPs: problems needs at least one entry")
+    lps = [_admm_many_problem(k, p) for k, p in enumerate(problems)]
+    x0 = _admm_many_starts(x0, lps)
+    state = ADMMManyState(lps, x0, gamma_eq, gamma_ineq, use_preconditioning)
+    try:
+        start = time.perf_counter()
+        i = 0
+        while i <= nb_iter:  # ADMM.py:143: nb_iter + 1 sweeps
+            if i % nb_iter_plot == 0:
+                state.sweep_step()
+                elapsed = time.perf_counter() - start
+                if max_time is not None and elapsed > max_time:
+                    break
+                energy, max_violated_equality, max_violated_inequality = state.report().T.copy()
+                if callback_func is not None:
+                    callback_func(i, state.x(), energy, energy.copy(), elapsed, max_violated_equality, max_violated_inequality)
+                state.multiplier_step()
+                i += 1
+            else:
+                k = min(nb_iter_plot - i % nb_iter_plot, nb_iter + 1 - i)
+                state.iterate(k)
+                i += k
+        return state.x()
     finally:
         state.close()
 

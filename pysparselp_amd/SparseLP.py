@@ -693,7 +693,8 @@ def solve_many(lps, method="chambolle_pock_ppd", get_timing=True, nb_iter=10000,
     reference solves one LP per call); returns the list of ``x``, or ``(xs, elapsed)`` with ``get_timing``.
 
     Only ``method="chambolle_pock_ppd"`` exists in this form (``many_methods``; ``ChambollePockPPD.chambolle_pock_ppd_many``); any
-    other raises ``ValueError``.  Per LP the preparation is that of ``solve(setup="host")``: ``copy.deepcopy`` and
+    other raises ``ValueError`` -- for ``method="admm"`` on a list see ``solve_admm_many``, for dual gradient ascent
+    ``solve_dga_many``.  Per LP the preparation is that of ``solve(setup="host")``: ``copy.deepcopy`` and
     ``remove_fixed_variables`` on the host (reference :1244-1248), ``x = m_change * sol - shift`` afterwards (:1259,:1288).
     ``xs[k]`` is bit for bit what ``lps[k].solve(method="chambolle_pock_ppd", order=ORDER_SEQUENTIAL, setup="host")`` returns.
 
@@ -756,5 +757,33 @@ def solve_dga_many(lps, get_timing=True, nb_iter=10000, max_time=None):
     for k, lp in enumerate(lps):
         lp.dual_multipliers = (y_eqs[k], y_ineqs[k])
         lp.dual_lower_bound = float(report[k, 0])
+    elapsed = time.perf_counter() - start
+    return (xs, elapsed) if get_timing else xs
+
+
+def solve_admm_many(lps, get_timing=True, nb_iter=10000, max_time=None, nb_iter_plot=10):
+    """Run ``method="admm"`` on a list of ``SparseLP`` objects whose matrices differ in ONE call, every LP one workgroup on the GPU
+    (``ADMM.lp_admm_many``; extension: the reference solves one LP per call); returns the list of ``x``, or ``(xs, elapsed)`` with
+    ``get_timing``.
+
+    ``xs[k]`` and every curve of ``lps[k]`` apart from the times are what ``lps[k].solve(method="admm", order=ORDER_SEQUENTIAL,
+    setup="host")`` gives: ``x`` and the violation curves bit for bit, the energies (``pobj_curve``, ``dobj_curve``) to the rounding
+    of another fixed summation order.  No fixed variables are removed, as ``solve(method="admm")`` removes none.  An LP without
+    inequality rows raises ``ValueError`` (the reference's standard form is undefined without them, tools.py:92).
+    ``solve_many(method="admm")`` keeps refusing: it is the Chambolle-Pock list form only.  ``max_time`` stops all LPs at a
+    report.  Under a communicator every rank solves the whole list (a replica)."""
+    from .ADMM import lp_admm_many
+
+    lps = list(lps)
+    if len(lps) < 1:
+        raise ValueError("an empty list of LPs")
+    start = time.perf_counter()
+    problems = []
+    for lp in lps:
+        _reset_curves(lp)
+        a_ineq = lp.a_inequalities if (lp.a_inequalities is not None and lp.a_inequalities.shape[0] > 0) else None
+        a_eq, b_eq = (lp.a_equalities, lp.b_equalities) if lp.a_equalities.shape[0] > 0 else (None, None)
+        problems.append((lp.costsvector, a_eq, b_eq, a_ineq, lp.b_lower, lp.b_upper, lp.lower_bounds, lp.upper_bounds))
+    xs = lp_admm_many(problems, nb_iter=nb_iter, callback_func=_list_recorder(lps), max_time=max_time, nb_iter_plot=nb_iter_plot)
     elapsed = time.perf_counter() - start
     return (xs, elapsed) if get_timing else xs

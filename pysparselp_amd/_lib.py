@@ -135,6 +135,20 @@ _SIGNATURES = {
     "slp_admm_batch_num_levels": (c_i64, [c_vp]),
     "slp_admm_batch_form": (c_int, [c_vp]),
     "slp_admm_batch_bench": (c_int, [c_vp, c_i64, c_vp]),
+    "slp_admm_many_create": (c_vp, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                    c_dbl, c_dbl, c_int]),
+    "slp_admm_many_destroy": (None, [c_vp]),
+    "slp_admm_many_iterate": (c_int, [c_vp, c_i64]),
+    "slp_admm_many_sweep_step": (c_int, [c_vp]),
+    "slp_admm_many_multiplier_step": (c_int, [c_vp]),
+    "slp_admm_many_report": (c_int, [c_vp, c_vp]),
+    "slp_admm_many_get_x": (c_int, [c_vp, c_vp, c_int]),
+    "slp_admm_many_get_lambda": (c_int, [c_vp, c_vp]),
+    "slp_admm_many_num_levels": (c_i64, [c_vp, c_i64]),
+    "slp_admm_many_form": (c_int, [c_vp, c_i64]),
+    "slp_admm_many_lds_limit": (c_i64, []),
+    "slp_admm_many_kmax": (c_i64, [c_vp, c_int]),
+    "slp_admm_many_bench": (c_int, [c_vp, c_i64, c_vp]),
     "slp_admm_cg_create": (c_vp, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),
     "slp_admm_cg_create_on": (c_vp, [c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),
     "slp_admm_cg_create_on_mixed": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),

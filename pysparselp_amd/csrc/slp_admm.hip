@@ -592,6 +592,8 @@ struct GsPlan {
     DevBuf<i32> rows;        // rows sorted by level (stable: increasing row inside a level)
     DevBuf<i64> lptr_dev;    // level pointer on the device (single-workgroup path)
     std::vector<i64> lptr;   // level pointer on the host (launch sizes)
+    bool earliest_levels = false; // set before planning: every row at the earliest level its inputs allow, whatever the number of
+                              // sinks (see gs_plan) -- a block-diagonal composite then gives every block the levels of its own plan
     bool levels_only = false; // set before planning: only the level-ordered copy of the matrix (rows of a level contiguous: no bands,
                               // which reorder the rows inside their runs) and no lane records -- what the batched ADMM reads
     bool one_block = false;
@@ -725,7 +727,7 @@ static void gs_plan(GsPlan &g, i64 n, const i64 *indptr, const i32 *indices, con
             }
         i64 sinks = 0;
         for (i64 i = 0; i < n; ++i) sinks += (!coupled_up[(size_t)i] && level[(size_t)i] > 0) ? 1 : 0;
-        if (sinks > 4096 && !(es && es[0] == '0')) {
+        if (sinks > 4096 && !(es && es[0] == '0') && !g.earliest_levels) {
             for (i64 i = 0; i < n; ++i)
                 if (!coupled_up[(size_t)i] && level[(size_t)i] > 0) level[(size_t)i] = maxlev + 1;
             // renumber: levels that held nothing else are gone
@@ -1345,15 +1347,17 @@ static void gs_plan_any(GsPlan &g, i64 n, i64 nnz, const i64 *dptr, const i32 *d
         ok = gs_plan_device(g, n, nnz, dptr, didx, dval);
     }
     if (!ok) {
-        const bool levels_only = g.levels_only;
+        const bool levels_only = g.levels_only, earliest_levels = g.earliest_levels;
         g = GsPlan();
         g.levels_only = levels_only;
+        g.earliest_levels = earliest_levels;
         host_plan(g);
         return;
     }
     if (mode == 2) {
         GsPlan h;
         h.levels_only = g.levels_only;
+        h.earliest_levels = g.earliest_levels;
         host_plan(h);
         gs_plan_compare(g, h);
     }
@@ -1780,14 +1784,14 @@ __global__ void k_fill_const(i64 n, double v, double *__restrict__ p) {
 // normalisation of the stacked system, M (slp_matrix_normal), A^T b -- run in HBM with the reference's entry orders and
 // accumulation orders, so the state equals the host-prepared one bit for bit.
 // (scaled_ineq != NULL: the row-normalised inequality block of :76-83 is handed to the caller instead of being dropped -- the
-// batched solver forms the slack part of every instance's start with it, slp_admm_batch.hip; levels_only: GsPlan::levels_only)
+// batched solver forms the slack part of every instance's start with it, slp_admm_batch.hip; levels_only, earliest_levels: GsPlan's)
 }  // extern "C"
 namespace slp {
 slp_admm *admm_create_lp(int64_t n, int64_t m_eq, const int64_t *eq_indptr, const int32_t *eq_indices, const double *eq_data,
                          const double *b_eq, int64_t m_ineq, const int64_t *in_indptr, const int32_t *in_indices,
                          const double *in_data, const double *b_lower, const double *b_upper, const double *c, const double *lb,
                          const double *ub, const double *x0, double gamma_eq, double gamma_ineq, int use_preconditioning, int order,
-                         slp_matrix **scaled_ineq, bool levels_only) {
+                         slp_matrix **scaled_ineq, bool levels_only, bool earliest_levels) {
     {
         SLP_REQUIRE(n >= 0 && m_eq >= 0 && m_ineq >= 0 && c && lb && ub, "slp_admm_create_lp: bad arguments");
         SLP_REQUIRE(in_indptr, "slp_admm_create_lp: the inequality block is required (the reference's standard form is undefined "
@@ -1802,6 +1806,7 @@ slp_admm *admm_create_lp(int64_t n, int64_t m_eq, const int64_t *eq_indptr, cons
             const i64 m = m_eq + m_ineq, N = n + m_ineq;
             s->N = N; s->m = m; s->gamma_eq = gamma_eq; s->gamma_ineq = gamma_ineq; s->order = order;
             s->plan.levels_only = levels_only;
+            s->plan.earliest_levels = earliest_levels;
             if (eq_indptr) {  // a 0-row equality block stays a block, like `a_eq is not None` in the reference
                 ae = slp_matrix_create(m_eq, n, eq_indptr, eq_indices, eq_data);
                 if (!ae) throw Error(slp_last_error());
@@ -1860,6 +1865,7 @@ void admm_shared(slp_admm *s, AdmmShared *v) {
     v->N = s->N; v->m = s->m;
     v->b = s->b.p; v->lb = s->lb.p; v->ub = s->ub.p; v->x0 = s->x.p;
     v->atb = s->y.p;  // admm_finish_create leaves A^T b there; the first right-hand side overwrites it
+    v->c = s->c.p; v->q = s->q.p; v->xp0 = s->xp0.p;
     v->nlevels = g.nlevels; v->max_width = g.max_width; v->nnz_m = g.nnz;
     v->lptr = g.lptr;
     v->gs_ptr = g.ptr.p; v->gs_idx = g.idx.p; v->gs_val = g.val.p; v->gs_invd = g.invd.p; v->gs_rows = g.rows.p;

@@ -16,7 +16,7 @@
 // (x, y, q, xp0 over N = n + m_ineq; lambda over m; c over n; lb, ub over N when they differ per instance, one shared vector
 // otherwise).  Lanes of padding instances are idle in every kernel: their state stays as allocated (zero).
 //
-// Two forms of the iteration, the same arithmetic (admmb_rhs_one / admmb_sweep_one / admmb_mult_one):
+// Two forms of the iteration, the same arithmetic (admm_rhs_one / admm_sweep_one / admm_mult_one of slp_admm_iter.h):
 //   tile    k_admmb_tile: ONE workgroup of 1024 lanes owns a tile and runs k whole iterations of its instances in one launch;
 //           stages and levels are separated by __syncthreads(), x / y / lambda stay in global memory and are re-read across the
 //           barriers with workgroup-scope relaxed loads (as k_gs_sweep_one_block).  No atomics between workgroups, no spin
@@ -34,6 +34,7 @@
 
 #include "slp_common.h"
 #include "slp_kernels.h"
+#include "slp_admm_iter.h"
 #include "slp_admm_shared.h"
 
 namespace slp {
@@ -54,40 +55,16 @@ struct AdmmbArgs {
     double gamma_eq, gamma_ineq;
 };
 
-// a value another lane of the workgroup may have stored before the last barrier: never kept in a register across it
-#ifndef SLP_ADMMB_SCOPE
-#define SLP_ADMMB_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
-#endif
-__device__ __forceinline__ double admmb_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, SLP_ADMMB_SCOPE); }
+// the workgroup-scope relaxed load of slp_admm_iter.h: a value another lane of the workgroup may have stored before the last barrier
+__device__ __forceinline__ double admmb_ld(const double *p) { return AdmmLoadWorkgroup()(p); }
 
-// sum_q val[q] * v[idx[q] * BT] over s <= q < e: storage order, one accumulator; loads four entries ahead (row_dot<1>)
-template <int BT>
-__device__ __forceinline__ double admmb_dot(i64 s, i64 e, const i32 *__restrict__ idx, const double *__restrict__ val, const double *v) {
-    double acc = 0.0;
-    for (i64 q0 = s; q0 < e; q0 += 4) {
-        i32 j[4];
-        double a[4], g[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const i64 qq = (q0 + q < e) ? q0 + q : e - 1;
-            j[q] = idx[qq];
-            a[q] = val[qq];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[q] = admmb_ld(v + (i64)j[q] * BT);
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (q0 + q < e) acc += a[q] * g[q];
-    }
-    return acc;
-}
-
+// the three steps for (row, instance k of the tile): the addresses of the tiled layout around the arithmetic of slp_admm_iter.h
 template <int BT>
 __device__ __forceinline__ void admmb_rhs_one(const AdmmbArgs &a, i64 tile, int k, i64 j, bool first) {
-    const double s = admmb_dot<BT>(a.tptr[j], a.tptr[j + 1], a.tidx, a.tval, a.lam + tile * a.m * BT + k);
     const i64 o = (tile * a.N + j) * BT + k;
-    const double xp = first ? a.xp0[a.xp0_b ? o : j] : admmb_ld(a.x + o);
-    a.y[o] = (a.q[o] + a.gamma_ineq * xp) - s;  // :148
+    const double *xp = first ? a.xp0 + (a.xp0_b ? o : j) : a.x + o;
+    a.y[o] = admm_rhs_one<BT>(a.tptr[j], a.tptr[j + 1], a.tidx, a.tval, a.lam + tile * a.m * BT + k, a.q + o, xp, !first, a.gamma_ineq,
+                              AdmmLoadWorkgroup());  // :148
 }
 
 template <int BT>
@@ -96,18 +73,14 @@ __device__ __forceinline__ void admmb_sweep_one(const AdmmbArgs &a, i64 tile, in
     const i64 o = (tile * a.N + i) * BT + k;
     const double bi = admmb_ld(a.y + o), xi = admmb_ld(a.x + o), inv = a.ginvd[t];
     const double l = a.lb[a.lb_b ? o : i], u = a.ub[a.ub_b ? o : i];
-    double v = admmb_dot<BT>(a.gptr[t], a.gptr[t + 1], a.gidx, a.gval, a.x + tile * a.N * BT + k);
-    v = (bi - v) * inv + xi;  // gaussSiedel.pyx:145 with w = 1
-    if (v < l) v = l;         // :148-151
-    else if (v > u) v = u;
-    a.x[o] = v;
+    a.x[o] = admm_sweep_one<BT>(a.gptr[t], a.gptr[t + 1], a.gidx, a.gval, a.x + tile * a.N * BT + k, bi, xi, inv, l, u, AdmmLoadWorkgroup());
 }
 
 template <int BT>
 __device__ __forceinline__ void admmb_mult_one(const AdmmbArgs &a, i64 tile, int k, i64 i) {
-    const double ax = admmb_dot<BT>(a.aptr[i], a.aptr[i + 1], a.aidx, a.aval, a.x + tile * a.N * BT + k);
     const i64 o = (tile * a.m + i) * BT + k;
-    a.lam[o] = admmb_ld(a.lam + o) + a.gamma_eq * (ax - a.b[i]);  // :261-263
+    a.lam[o] = admm_mult_one<BT>(a.aptr[i], a.aptr[i + 1], a.aidx, a.aval, a.x + tile * a.N * BT + k, a.lam + o, a.b + i, a.gamma_eq,
+                                 AdmmLoadWorkgroup());  // :261-263
 }
 
 // ---- tile form: `iters` iterations of one tile in one workgroup.  stages: bit 0 right-hand side + sweep, bit 1 multiplier.
@@ -177,7 +150,7 @@ __global__ __launch_bounds__(kBlock) void k_admmb_report_rows(AdmmbArgs a, i64 B
     double s0 = 0.0, s1 = 0.0, mx = -__builtin_inf();
     if (inst < a.B)
         for (i64 i = group; i < a.m; i += ng) {
-            const double ax = admmb_dot<BT>(a.aptr[i], a.aptr[i + 1], a.aidx, a.aval, a.x + tile * a.N * BT + k);
+            const double ax = admm_dot<BT>(a.aptr[i], a.aptr[i + 1], a.aidx, a.aval, a.x + tile * a.N * BT + k, AdmmLoadWorkgroup());
             const double r = ax - a.b[i];
             s0 += r * r;
             s1 += a.lam[(tile * a.m + i) * BT + k] * r;

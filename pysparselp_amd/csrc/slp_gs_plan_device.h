@@ -850,7 +850,7 @@ static bool gs_plan_device(GsPlan &g, i64 n, i64 nnz, const i64 *dptr, const i32
         unsigned long long hsinks = 0;
         sinks.download(&hsinks, 1);
         const char *es = getenv("SLP_GS_SINKS");
-        if (hsinks > 4096 && !(es && es[0] == '0')) {
+        if (hsinks > 4096 && !(es && es[0] == '0') && !g.earliest_levels) {
             // rows that nothing waits for: one level of their own behind all others (see gs_plan); levels that held nothing else go
             DevBuf<i32> present((size_t)maxlev + 2), remap((size_t)maxlev + 2);
             present.zero();

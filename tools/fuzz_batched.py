@@ -1,13 +1,13 @@
 """Randomised cross-check of the batched, list and dual-ascent solver families against their CPU references, bit for bit:
-``chambolle_pock_ppd_batch`` / ``chambolle_pock_ppd_many`` against ``oracle.chambolle_pock_ppd``, ``lp_admm_batch`` against
-``oracle.lp_admm``, ``DeviceDGA`` / ``DeviceDGABatch`` / ``DeviceDGAMany`` against tests/dga_cpu.py in the reference's order of sums
+``chambolle_pock_ppd_batch`` / ``chambolle_pock_ppd_many`` against ``oracle.chambolle_pock_ppd``, ``lp_admm_batch`` /
+``lp_admm_many`` against ``oracle.lp_admm``, ``DeviceDGA`` / ``DeviceDGABatch`` / ``DeviceDGAMany`` against tests/dga_cpu.py in the reference's order of sums
 (up to the iteration to which dga_cpu agrees with itself in its three orders, behind it in the device's own order), each batch instance and list LP
 also against the single solver alone, the status bits of the LPs on which dga_cpu raises, and the dual bound against HiGHS.
 
 The LPs have wave / tile / padding sizes (n in 1, 2, 3, 63, 64, 65, 127, 129, 255, 257), an empty row, an empty column, a row of
 more than 64 entries, one- / two-sided / mixed rows, infinite and equal bounds, warm starts and odd reporting cadences.
 
-    python tools/fuzz_batched.py [--cases 24] [--seed 0] [--family cp_batch,cp_many,admm_batch,dga,dga_batch,dga_many]
+    python tools/fuzz_batched.py [--cases 24] [--seed 0] [--family cp_batch,cp_many,admm_batch,admm_many,dga,dga_batch,dga_many]
 
 The generators and the CPU references need no GPU (tests/test_fuzz_batched_host.py checks on them that the GPU runs compare what
 they claim to); the ``run_*`` functions need one."""
@@ -187,6 +187,20 @@ def cp_many_cases(cases, seed):
     out = []
     for case in range(cases):
         lps = [random_lp(rng, "cp", edge_n(case) if k == 0 else None) for k in range(int(rng.randint(1, 10)))]
+        if case == large_case(cases):
+            lps = [lps[k % len(lps)] for k in range(LONG_LIST)]
+        out.append((lps, int(rng.randint(1, 61)), int(rng.choice(CADENCES))))
+    return out
+
+
+def admm_many_cases(cases, seed):
+    """``[(lps, iterations, cadence)]`` of ``run_admm_many``: lists of 1 to 9 LPs of different shapes, each with an inequality block
+    (the first LP of cases 0 .. 9 has the edge sizes in turn); ``large_case`` cycles its LPs to ``LONG_LIST`` entries.  A generator of
+    its own: no other family's draws depend on it."""
+    rng = np.random.RandomState(seed + 5000)
+    out = []
+    for case in range(cases):
+        lps = [random_lp(rng, "admm", edge_n(case) if k == 0 else None) for k in range(int(rng.randint(1, 10)))]
         if case == large_case(cases):
             lps = [lps[k % len(lps)] for k in range(LONG_LIST)]
         out.append((lps, int(rng.randint(1, 61)), int(rng.choice(CADENCES))))
@@ -664,6 +678,54 @@ def run_admm_batch(cases, seed):
     return counts
 
 
+ADMM_MANY_SETTINGS = (("default", None, None), ("lds", "lds", None), ("global", "global", None), ("kmax1", None, 1))
+
+
+def run_admm_many(cases, seed):
+    """``lp_admm_many`` and ``ADMMManyState``: every LP of every list against the oracle at every report and at the end, with the
+    form chosen by the library, forced to ``lds`` and to ``global``, and with one iteration per launch.  Returns counts."""
+    from pysparselp_amd import ADMMManyState, lp_admm_many
+    from pysparselp_amd.ADMM import _admm_many_problem, _admm_many_starts
+
+    counts = dict(lists=0, lps=0, runs=0, longest=0)
+    for case, (lps, its, plot) in enumerate(admm_many_cases(cases, seed)):
+        problems = [of_instance(lp, 0)[0] for lp in lps]
+        x0 = [lp["x0"] for lp in lps]
+        refs = {}
+        for k, lp in enumerate(lps):   # a cycled list repeats its LPs: one reference each
+            if id(lp) not in refs:
+                refs[id(lp)] = admm_reference(problems[k], x0[k], its, plot)
+        for name, form, kmax in ADMM_MANY_SETTINGS:
+            with environment(SLP_ADMM_MANY_FORM=form, SLP_ADMM_MANY_KMAX=kmax):
+                rec = _Reports()
+                xs = lp_admm_many(problems, x0=x0, nb_iter=its, nb_iter_plot=plot, callback_func=rec)
+                checked = [_admm_many_problem(k, p) for k, p in enumerate(problems)]
+                state = ADMMManyState(checked, _admm_many_starts(x0, checked))
+                try:
+                    forms = [state.form(k) for k in range(state.count)]
+                    for p in _pieces(its):
+                        state.iterate(p)
+                    state.sweep_step()
+                    sx, lam = state.x(), state.lam()
+                finally:
+                    state.close()
+            _require(form is None or set(forms) == {form}, f"admm_many seed {seed} case {case}: forms {set(forms)} under SLP_ADMM_MANY_FORM={form}")
+            for k, lp in enumerate(lps):
+                ref, x_ref, lam_ref = refs[id(lp)]
+                where = (f"admm_many seed {seed} case {case} LP {k} of {len(lps)} (n {x_ref.size}, {its} iterations, cadence {plot}), "
+                         f"setting {name}, form {forms[k]}")
+                layer = _admm_single_agrees(problems[k], x0[k], its, x_ref)
+                _require(np.array_equal(xs[k], x_ref), where + ": the returned x differs", layer)
+                _compare_reports(rec, k, ref, where, layer)
+                _require(np.array_equal(sx[k], x_ref), where + ": x of the state differs", layer)
+                _require(np.array_equal(lam[k], lam_ref), where + ": lambda differs", layer)
+            counts["runs"] += 1
+        counts["lists"] += 1
+        counts["lps"] += len(refs)
+        counts["longest"] = max(counts["longest"], len(lps))
+    return counts
+
+
 # ---- dual gradient ascent on the device -------------------------------------------------------------------------------------------------
 
 class _LP:
@@ -967,8 +1029,8 @@ def run_dga_many(cases, seed):
     return counts
 
 
-FAMILIES = {"cp_batch": run_cp_batch, "cp_many": run_cp_many, "admm_batch": run_admm_batch, "dga": run_dga, "dga_batch": run_dga_batch,
-            "dga_many": run_dga_many}
+FAMILIES = {"cp_batch": run_cp_batch, "cp_many": run_cp_many, "admm_batch": run_admm_batch, "admm_many": run_admm_many, "dga": run_dga,
+            "dga_batch": run_dga_batch, "dga_many": run_dga_many}
 
 
 def main():
