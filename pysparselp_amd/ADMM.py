@@ -24,7 +24,8 @@ import time
 import numpy as np
 
 from . import _lib
-from ._batch import concat, first_offsets, shared_or_batched, split_by
+from . import _many
+from ._batch import concat, first_offsets, shared_or_batched
 from ._lib import ORDER_AUTO
 from .tools import convert_to_standard_form_with_bounds, normal_matrix, precondition_constraints
 
@@ -389,25 +390,10 @@ def _admm_many_problem(k, problem):
     equality rows) and the vectors as contiguous float64 arrays (``b_lower`` / ``b_upper``: -inf / +inf where absent)."""
     from .tools import CsrArrays
 
-    try:
-        count = len(problem)
-    except TypeError:
-        count = -1
-    if count != 8:
-        raise ValueError(f"LP {k} is not a tuple of 8 entries (c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub)")
-    c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub = problem
-    c = _lib.f64(c)
-    if c.ndim != 1 or c.size < 1:
-        raise ValueError(f"LP {k}: c has shape {c.shape}, expected (n,) with n >= 1")
+    c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub = _many.unpack_problem(k, problem)
+    c = _many.check_cost(k, "c", c, finite=True)
     n = c.size
-    if not np.all(np.isfinite(c)):
-        raise ValueError(f"LP {k}: c has an entry that is not finite")
-    lb, ub = _lib.f64(lb), _lib.f64(ub)
-    for name, v in (("lb", lb), ("ub", ub)):
-        if v.shape != (n,):
-            raise ValueError(f"LP {k}: {name} has shape {v.shape}, c has {n} entries")
-        if np.any(np.isnan(v)):
-            raise ValueError(f"LP {k}: {name} has a NaN")
+    lb, ub = (_many.check_vector(k, name, v, (n,), f"c has {n} entries", no_nan=True) for name, v in (("lb", lb), ("ub", ub)))
     a_eq, a_ineq = CsrArrays.from_any(a_eq), CsrArrays.from_any(a_ineq)
     if a_ineq is None:
         raise ValueError(f"LP {k} has no inequality block: the reference cannot form the standard form without one (tools.py:92)")
@@ -415,23 +401,10 @@ def _admm_many_problem(k, problem):
         a_eq, beq = None, None
     for name, a in (("a_eq", a_eq), ("a_ineq", a_ineq)):
         if a is not None:
-            if a.shape[1] != n:
-                raise ValueError(f"LP {k}: {name} has {a.shape[1]} columns, c has {n} entries")
-            if a.indptr.shape != (a.shape[0] + 1,) or a.indptr[0] != 0 or np.any(np.diff(a.indptr) < 0) or a.indptr[-1] != a.indices.size \
-                    or a.indices.size != a.data.size:
-                raise ValueError(f"LP {k}: {name} is not a well-formed CSR matrix")
-            if a.indices.size and (a.indices.min() < 0 or a.indices.max() >= n):
-                raise ValueError(f"LP {k}: {name} has a column index outside [0, {n})")
+            _many.check_csr(k, name, a, n, f"c has {n} entries")
 
     def rhs(name, v, rows, fill):
-        if v is None:
-            return np.full(rows, fill)
-        v = _lib.f64(v)
-        if v.shape != (rows,):
-            raise ValueError(f"LP {k}: {name} has shape {v.shape}, expected ({rows},)")
-        if np.any(np.isnan(v)):
-            raise ValueError(f"LP {k}: {name} has a NaN")
-        return v
+        return np.full(rows, fill) if v is None else _many.check_vector(k, name, v, (rows,), f"expected ({rows},)", no_nan=True)
 
     if a_eq is not None:
         if beq is None:
@@ -465,16 +438,9 @@ def admm_many_system(lps):
     out = dict(n=n, m_eq=m_eq, m_ineq=m_ineq, col0=col0, eq0=first_offsets(m_eq), in0=first_offsets(m_ineq),
                x0=first_offsets(n + m_ineq), lam0=first_offsets(m_eq + m_ineq))
     for tag, part, rhs_names in (("eq", 1, (("b_eq", 2),)), ("in", 3, (("b_lower", 4), ("b_upper", 5)))):
-        ptr, idx, val, entries = [np.zeros(1, dtype=np.int64)], [], [], 0
-        for k, lp in enumerate(lps):
-            a = lp[part]
-            if a is None:
-                continue
-            ptr.append(entries + a.indptr[1:])
-            idx.append(a.indices.astype(np.int64) + col0[k])
-            val.append(a.data)
-            entries += int(a.indptr[-1])
-        out[tag + "_indptr"], out[tag + "_indices"], out[tag + "_data"] = concat(ptr, np.int64), concat(idx, np.int32), concat(val, np.float64)
+        have = [k for k, lp in enumerate(lps) if lp[part] is not None]
+        out[tag + "_indptr"], out[tag + "_indices"], out[tag + "_data"] = _many.stack_blocks(
+            [(lps[k][part].indptr, lps[k][part].indices, lps[k][part].data) for k in have], col0[have])
         for name, pos in rhs_names:
             out[name] = concat([lp[pos] for lp in lps if lp[part] is not None], np.float64)
     for name, pos in (("c", 0), ("lb", 6), ("ub", 7)):
@@ -484,22 +450,7 @@ def admm_many_system(lps):
 
 def _admm_many_starts(x0, lps):
     """``x0`` of ``lp_admm_many`` checked against the LPs: ``None``, or a list with one start (or ``None``) per LP."""
-    if x0 is None:
-        return None
-    try:
-        given = len(x0)
-    except TypeError:
-        given = -1
-    if given != len(lps):
-        raise ValueError(f"x0 must be None or a sequence of {len(lps)} starts, one per LP")
-    x0 = [None if v is None else _lib.f64(v) for v in x0]
-    for k, v in enumerate(x0):
-        if v is not None:
-            if v.shape != lps[k][0].shape:
-                raise ValueError(f"LP {k}: x0 has shape {v.shape}, c has {lps[k][0].size} entries")
-            if not np.all(np.isfinite(v)):
-                raise ValueError(f"LP {k}: x0 has an entry that is not finite")
-    return x0
+    return _many.check_starts(x0, lps, finite=True)
 
 
 def admm_many_lds_limit():
@@ -507,12 +458,12 @@ def admm_many_lds_limit():
     return int(_lib.load().slp_admm_many_lds_limit())
 
 
-class ADMMManyState:
+class ADMMManyState(_many.ManyState):
     """Device-resident ADMM state of a list of LPs (thin RAII wrapper of ``slp_admm_many``).  ``lps``: the LPs as
     ``_admm_many_problem`` returns them; ``x0``: ``None`` or one start (or ``None``: zeros) per LP, as ``_admm_many_starts``
     returns it."""
 
-    FORMS = ("lds", "global")
+    _PREFIX = "slp_admm_many"
 
     def __init__(self, lps, x0=None, gamma_eq=2, gamma_ineq=3, use_preconditioning=True):
         if len(lps) < 1:
@@ -521,10 +472,7 @@ class ADMMManyState:
         self.count = len(lps)
         self.n, self.N, self.m = s["n"], s["n"] + s["m_ineq"], s["m_eq"] + s["m_ineq"]
         self.system = s
-        start = None
-        if x0 is not None and any(v is not None for v in x0):
-            start = _lib.f64(np.concatenate([np.zeros(int(nk)) if v is None else _lib.f64(v) for v, nk in zip(x0, self.n)]))
-            assert start.size == int(self.n.sum())
+        start = _many.concat_starts(x0, self.n)
         has_eq = int(s["m_eq"].sum()) > 0
         eq = tuple(_lib.ptr(s[name]) if has_eq else None for name in ("eq_indptr", "eq_indices", "eq_data", "b_eq"))
         # all of the above needs no GPU; the library is loaded (and bound to a device) only now
@@ -533,13 +481,6 @@ class ADMMManyState:
             self.count, _lib.ptr(s["n"]), _lib.ptr(s["m_eq"]), _lib.ptr(s["m_ineq"]), *eq, _lib.ptr(s["in_indptr"]),
             _lib.ptr(s["in_indices"]), _lib.ptr(s["in_data"]), _lib.ptr(s["b_lower"]), _lib.ptr(s["b_upper"]), _lib.ptr(s["c"]),
             _lib.ptr(s["lb"]), _lib.ptr(s["ub"]), _lib.ptr(start), float(gamma_eq), float(gamma_ineq), int(bool(use_preconditioning))))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._l.slp_admm_many_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def iterate(self, k):
         _lib.check(self._l.slp_admm_many_iterate(self._h, int(k)))
@@ -558,29 +499,15 @@ class ADMMManyState:
 
     def x(self, full=False):
         """Per LP the first ``n_k`` entries of its iterate, or with ``full`` all ``N_k`` of its standard form."""
-        sizes = self.N if full else self.n
-        out = np.empty(int(sizes.sum()))
-        _lib.check(self._l.slp_admm_many_get_x(self._h, _lib.ptr(out), int(bool(full))))
-        return split_by(out, sizes)
+        return self._per_lp("x", self.N if full else self.n, int(bool(full)))
 
     def lam(self):
         """Per LP ``[lambda_eq; lambda_ineq]``."""
-        out = np.empty(int(self.m.sum()))
-        _lib.check(self._l.slp_admm_many_get_lambda(self._h, _lib.ptr(out)))
-        return split_by(out, self.m)
-
-    def _of_lp(self, k):
-        if not 0 <= int(k) < self.count:
-            raise IndexError(f"LP {k} of {self.count}")
-        return int(k)
+        return self._per_lp("lambda", self.m)
 
     def num_levels(self, k):
         """Dependency levels of LP ``k``'s sweep: those of the plan of that LP alone."""
         return int(self._l.slp_admm_many_num_levels(self._h, self._of_lp(k)))
-
-    def form(self, k):
-        """``"lds"`` or ``"global"``: where LP ``k`` keeps x, y, lambda during a launch."""
-        return self.FORMS[int(self._l.slp_admm_many_form(self._h, self._of_lp(k)))]
 
     def kmax(self, form):
         """Iterations one launch of the form (``"lds"`` / ``"global"``) holds; 0 when no LP runs in it."""
@@ -621,12 +548,7 @@ def lp_admm_many(
     Under a communicator every rank solves the whole list (a replica).  For LPs that share one matrix ``lp_admm_batch`` builds
     ``M`` and its plan once for all of them.
     """
-    try:
-        count = len(problems)
-    except TypeError:
-        raise ValueError("problems must be a sequence of 8-tuples (c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub)") from None
-    if count < 1:
-        raise ValueError("an empty list of LPs: problems needs at least one entry")
+    _many.count_problems(problems)
     lps = [_admm_many_problem(k, p) for k, p in enumerate(problems)]
     x0 = _admm_many_starts(x0, lps)
     state = ADMMManyState(lps, x0, gamma_eq, gamma_ineq, use_preconditioning)

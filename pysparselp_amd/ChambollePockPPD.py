@@ -20,6 +20,7 @@ import time
 import numpy as np
 
 from . import _lib
+from . import _many
 from ._batch import box_vertex, concat, first_offsets, shared_or_batched, split_by
 from ._lib import ORDER_AUTO
 from .parallel import collective_elapsed
@@ -561,47 +562,27 @@ def _many_problem(k, problem):
     """LP ``k`` of a set, validated (``ValueError``) and brought to the solver's form without touching the library:
     ``(c, lb, ub, eq, beq, ineq, b_ineq)`` with ``eq`` raw CSR arrays ``(indptr, indices, data, rows)`` or ``None``, ``ineq`` the
     one-sided system of ``one_sided_system`` or ``None``."""
-    try:
-        count = len(problem)
-    except TypeError:
-        count = -1
-    if count != 8:
-        raise ValueError(f"LP {k} is not a tuple of 8 entries (c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub)")
-    c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub = problem
-    c = _lib.f64(c)
-    if c.ndim != 1 or c.size < 1:
-        raise ValueError(f"LP {k}: c has shape {c.shape}, expected (n,) with n >= 1")
+    c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub = _many.unpack_problem(k, problem)
+    c = _many.check_cost(k, "c", c)
     n = c.size
-    lb, ub = _lib.f64(lb), _lib.f64(ub)
-    for name, v in (("lb", lb), ("ub", ub)):
-        if v.shape != (n,):
-            raise ValueError(f"LP {k}: {name} has shape {v.shape}, c has {n} entries")
+    lb, ub = (_many.check_vector(k, name, v, (n,), f"c has {n} entries") for name, v in (("lb", lb), ("ub", ub)))
     if a_eq is not None and a_eq.shape[0] == 0:  # reference :70-72
         a_eq, beq = None, None
     if a_ineq is not None and a_ineq.shape[0] == 0:
         a_ineq = None
     for name, a in (("a_eq", a_eq), ("a_ineq", a_ineq)):
         if a is not None:
-            if a.shape[1] != n:
-                raise ValueError(f"LP {k}: {name} has {a.shape[1]} columns, c has {n} entries")
-            if a.indices.size and (a.indices.min() < 0 or a.indices.max() >= n):
-                raise ValueError(f"LP {k}: {name} has a column index outside [0, {n})")
+            _many.check_csr(k, name, a, n, f"c has {n} entries")
     eq = None
     if a_eq is not None:
-        beq = _lib.f64(beq)
-        if beq.shape != (a_eq.shape[0],):
-            raise ValueError(f"LP {k}: beq has shape {beq.shape}, a_eq has {a_eq.shape[0]} rows")
+        beq = _many.check_vector(k, "beq", beq, (a_eq.shape[0],), f"a_eq has {a_eq.shape[0]} rows")
         eq = _lib.csr_arrays(a_eq) + (a_eq.shape[0],)
     ineq, b_ineq = None, None
     if a_ineq is not None:
         rows = a_ineq.shape[0]
-        b_upper = _lib.f64(b_upper)
-        if b_upper.shape != (rows,):
-            raise ValueError(f"LP {k}: b_upper has shape {b_upper.shape}, a_ineq has {rows} rows")
+        b_upper = _many.check_vector(k, "b_upper", b_upper, (rows,), f"a_ineq has {rows} rows")
         if b_lower is not None:
-            b_lower = _lib.f64(b_lower)
-            if b_lower.shape != (rows,):
-                raise ValueError(f"LP {k}: b_lower has shape {b_lower.shape}, a_ineq has {rows} rows")
+            b_lower = _many.check_vector(k, "b_lower", b_lower, (rows,), f"a_ineq has {rows} rows")
         ineq, b_ineq = one_sided_system(a_ineq, b_lower, b_upper)
     return c, lb, ub, eq, beq, ineq, b_ineq
 
@@ -621,30 +602,21 @@ def many_system(lps):
     m_ineq = np.array([0 if lp[5] is None else lp[5][3] for lp in lps], dtype=np.int64)
     col0, eq0 = first_offsets(n), first_offsets(m_eq)
     in0 = int(m_eq.sum()) + first_offsets(m_ineq)
-    ptr, idx, val, b = [np.zeros(1, dtype=np.int64)], [], [], []
-    entries = 0
-    for part, rhs in ((3, 4), (5, 6)):
-        for k in range(count):
-            if lps[k][part] is None:
-                continue
-            p, j, v, _ = lps[k][part]
-            ptr.append(entries + p[1:])
-            idx.append(j.astype(np.int64) + col0[k])
-            val.append(v)
-            b.append(_lib.f64(lps[k][rhs]))
-            entries += int(p[-1])
     if int(n.sum()) >= 2 ** 31 or int(m_eq.sum() + m_ineq.sum()) >= 2 ** 31:
         raise ValueError("the set has 2^31 or more variables or rows")
-    return dict(n=n, m_eq=m_eq, m_ineq=m_ineq, col0=col0, eq0=eq0, in0=in0, indptr=concat(ptr, np.int64), indices=concat(idx, np.int32),
-                data=concat(val, np.float64), b=concat(b, np.float64), c=concat([lp[0] for lp in lps], np.float64),
+    # (LP, its block, its right-hand side): the equality rows of all LPs, then the inequality rows of all LPs
+    rows = [(k, lps[k][part], lps[k][rhs]) for part, rhs in ((3, 4), (5, 6)) for k in range(count) if lps[k][part] is not None]
+    indptr, indices, data = _many.stack_blocks([a[:3] for _, a, _ in rows], [col0[k] for k, _, _ in rows])
+    return dict(n=n, m_eq=m_eq, m_ineq=m_ineq, col0=col0, eq0=eq0, in0=in0, indptr=indptr, indices=indices, data=data,
+                b=concat([b for _, _, b in rows], np.float64), c=concat([lp[0] for lp in lps], np.float64),
                 lb=concat([lp[1] for lp in lps], np.float64), ub=concat([lp[2] for lp in lps], np.float64))
 
 
-class CPManyState:
+class CPManyState(_many.ManyState):
     """Device-resident Chambolle-Pock state of a set of LPs (thin RAII wrapper of ``slp_cp_many``).  ``lps``: the LPs as
     ``_many_problem`` returns them, each with at least one row; ``x0``: ``None`` or one start (or ``None``: zeros) per LP."""
 
-    FORMS = ("lds", "global")
+    _PREFIX = "slp_cp_many"
 
     def __init__(self, lps, x0=None, alpha=1, theta=1):
         if len(lps) < 1:
@@ -653,23 +625,13 @@ class CPManyState:
         self.count = len(lps)
         self.n, self.m = s["n"], s["m_eq"] + s["m_ineq"]
         self.system = s
-        start = None
-        if x0 is not None and any(v is not None for v in x0):
-            start = _lib.f64(np.concatenate([np.zeros(int(nk)) if v is None else _lib.f64(v) for v, nk in zip(x0, self.n)]))
-            assert start.size == int(self.n.sum())
+        start = _many.concat_starts(x0, self.n)
         # all of the above needs no GPU; the library is loaded (and bound to a device) only now
         self._l = _lib.lib()
         self._h = _lib.check_handle(self._l.slp_cp_many_create(
             self.count, _lib.ptr(s["n"]), _lib.ptr(s["m_eq"]), _lib.ptr(s["m_ineq"]), _lib.ptr(s["indptr"]), _lib.ptr(s["indices"]),
             _lib.ptr(s["data"]), _lib.ptr(s["b"]), _lib.ptr(s["c"]), _lib.ptr(s["lb"]), _lib.ptr(s["ub"]), _lib.ptr(start),
             float(alpha), float(theta)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._l.slp_cp_many_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
     def iterate(self, k):
         _lib.check(self._l.slp_cp_many_iterate(self._h, int(k)))
@@ -687,27 +649,16 @@ class CPManyState:
         return out
 
     def x(self):
-        out = np.empty(int(self.n.sum()))
-        _lib.check(self._l.slp_cp_many_get_x(self._h, _lib.ptr(out)))
-        return split_by(out, self.n)
+        return self._per_lp("x", self.n)
 
     def y(self):
         """Per LP ``[y_eq; y_ineq]``."""
-        out = np.empty(int(self.m.sum()))
-        _lib.check(self._l.slp_cp_many_get_y(self._h, _lib.ptr(out)))
-        return split_by(out, self.m)
+        return self._per_lp("y", self.m)
 
     def preconditioners(self):
         t, s = np.empty(int(self.n.sum())), np.empty(int(self.m.sum()))
         _lib.check(self._l.slp_cp_many_get_preconditioners(self._h, _lib.ptr(t), _lib.ptr(s)))
         return split_by(t, self.n), split_by(s, self.m)
-
-    def form(self, k):
-        """``"lds"`` or ``"global"``: where LP ``k`` keeps x, z, y during a launch."""
-        f = int(self._l.slp_cp_many_form(self._h, int(k)))
-        if f < 0:
-            raise IndexError(f"LP {k} of {self.count}")
-        return self.FORMS[f]
 
     def bench(self, k):
         ms = np.zeros(3)
@@ -743,24 +694,9 @@ def chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=100
     a given count is what ``tools/bench_cp_many.py`` measures -- not measured yet.
     """
     start = time.perf_counter()
-    try:
-        count = len(problems)
-    except TypeError:
-        raise ValueError("problems must be a sequence of 8-tuples (c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub)") from None
-    if count < 1:
-        raise ValueError("an empty list of LPs: problems needs at least one entry")
+    count = _many.count_problems(problems)
     lps = [_many_problem(k, p) for k, p in enumerate(problems)]
-    if x0 is not None:
-        try:
-            given = len(x0)
-        except TypeError:
-            given = -1
-        if given != count:
-            raise ValueError(f"x0 must be None or a sequence of {count} starts, one per LP")
-        x0 = [None if v is None else _lib.f64(v) for v in x0]
-        for k, v in enumerate(x0):
-            if v is not None and v.shape != lps[k][0].shape:
-                raise ValueError(f"LP {k}: x0 has shape {v.shape}, c has {lps[k][0].size} entries")
+    x0 = _many.check_starts(x0, lps)
     solved = [k for k in range(count) if lps[k][3] is not None or lps[k][5] is not None]
     xs = [None if (lps[k][3] is not None or lps[k][5] is not None) else box_vertex(*lps[k][:3]) for k in range(count)]
     best = [None] * count

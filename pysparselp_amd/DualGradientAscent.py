@@ -15,6 +15,7 @@ import time
 import numpy as np
 
 from . import _lib
+from . import _many
 from ._batch import check_costs, concat, first_offsets, require_one_sided, shared_or_batched, split_by
 
 PATHS = {"auto": 0, "fused": 1, "general": 2}
@@ -415,31 +416,19 @@ def _dga_many_lp(k, lp):
         raise ValueError(f"LP {k} is not an LP object (costsvector, a_equalities, b_equalities, a_inequalities, b_upper, b_lower, "
                          f"lower_bounds, upper_bounds): {e}") from None
     require_one_sided(b_lower, prefix=f"LP {k}: ")
-    if c.ndim != 1 or c.size < 1:
-        raise ValueError(f"LP {k}: costsvector has shape {c.shape}, expected (n,) with n >= 1")
-    n = c.size
+    n = _many.check_cost(k, "costsvector", c).size
     if n > FUSED_MAX:
         raise ValueError(f"LP {k} has {n} variables: the list form holds at most {FUSED_MAX} per LP (one workgroup, breakpoints in "
                          "LDS); an LP with more belongs to the single solver, dual_gradient_ascent")
     for name, v in (("lower_bounds", lb), ("upper_bounds", ub)):
-        if v.shape != (n,):
-            raise ValueError(f"LP {k}: {name} has shape {v.shape}, costsvector has {n} entries")
+        _many.check_vector(k, name, v, (n,), f"costsvector has {n} entries")
     out = []
     for name, a, rhs_name in (("a_equalities", a_eq, "b_equalities"), ("a_inequalities", a_ineq, "b_upper")):
         if a is None or a.shape[0] == 0:
             out += [None, np.zeros(0)]
             continue
-        if a.shape[1] != n:
-            raise ValueError(f"LP {k}: {name} has {a.shape[1]} columns, costsvector has {n} entries")
-        if a.indptr.shape != (a.shape[0] + 1,) or a.indptr[0] != 0 or np.any(np.diff(a.indptr) < 0) or a.indptr[-1] != a.indices.size \
-                or a.indices.size != a.data.size:
-            raise ValueError(f"LP {k}: {name} is not a well-formed CSR matrix")
-        if a.indices.size and (a.indices.min() < 0 or a.indices.max() >= n):
-            raise ValueError(f"LP {k}: {name} has a column index outside [0, {n})")
-        rhs = _lib.f64(getattr(lp, rhs_name))
-        if rhs.shape != (a.shape[0],):
-            raise ValueError(f"LP {k}: {rhs_name} has shape {rhs.shape}, {name} has {a.shape[0]} rows")
-        out += [a, rhs]
+        _many.check_csr(k, name, a, n, f"costsvector has {n} entries")
+        out += [a, _many.check_vector(k, rhs_name, getattr(lp, rhs_name), (a.shape[0],), f"{name} has {a.shape[0]} rows")]
     if out[0] is None and out[2] is None:
         raise ValueError(f"LP {k} has no constraint rows")
     return (c, lb, ub) + tuple(out)
@@ -472,9 +461,7 @@ def dga_many_start(lps, y_eq=None, y_ineq=None):
                 v = -rs.rand(rows) if sign < 0 else np.abs(rs.rand(rows))
                 taken += rows
             else:
-                v = _lib.f64(v).copy()
-                if v.shape != (rows,):
-                    raise ValueError(f"LP {k}: {name} has shape {v.shape}, the LP has {rows} such rows")
+                v = _many.check_vector(k, name, v, (rows,), f"the LP has {rows} such rows").copy()
             parts.append(v)
         y0s.append(np.concatenate(parts))
         offsets.append(taken)
@@ -494,23 +481,14 @@ def dga_many_system(lps, y0s, draw_offsets):
     n = np.array([lp[0].size for lp in lps], dtype=np.int64)
     m_eq = np.array([0 if lp[3] is None else lp[3].shape[0] for lp in lps], dtype=np.int64)
     m_ineq = np.array([0 if lp[5] is None else lp[5].shape[0] for lp in lps], dtype=np.int64)
-    ptr, idx, val, b = [np.zeros(1, dtype=np.int64)], [], [], []
-    entries = 0
-    for lp in lps:
-        for a, rhs in ((lp[3], lp[4]), (lp[5], lp[6])):
-            if a is None:
-                continue
-            ptr.append(entries + a.indptr[1:])
-            idx.append(a.indices)
-            val.append(a.data)
-            b.append(rhs)
-            entries += a.nnz
-    if int(n.sum()) >= 2 ** 31 or int(m_eq.sum() + m_ineq.sum()) >= 2 ** 31 or entries >= 2 ** 31:
+    blocks = [(a, rhs) for lp in lps for a, rhs in ((lp[3], lp[4]), (lp[5], lp[6])) if a is not None]
+    if int(n.sum()) >= 2 ** 31 or int(m_eq.sum() + m_ineq.sum()) >= 2 ** 31 or sum(a.nnz for a, _ in blocks) >= 2 ** 31:
         raise ValueError("the list has 2^31 or more variables, rows or entries")
+    indptr, indices, data = _many.stack_blocks([(a.indptr, a.indices, a.data) for a, _ in blocks])
     y0 = concat(list(y0s), np.float64)
     assert y0.size == int(m_eq.sum() + m_ineq.sum()) and len(draw_offsets) == count
-    return dict(n=n, m_eq=m_eq, m_ineq=m_ineq, col0=first_offsets(n), row0=first_offsets(m_eq + m_ineq), indptr=concat(ptr, np.int64),
-                indices=concat(idx, np.int32), data=concat(val, np.float64), b=concat(b, np.float64),
+    return dict(n=n, m_eq=m_eq, m_ineq=m_ineq, col0=first_offsets(n), row0=first_offsets(m_eq + m_ineq), indptr=indptr,
+                indices=indices, data=data, b=concat([rhs for _, rhs in blocks], np.float64),
                 c=concat([lp[0] for lp in lps], np.float64), lb=concat([lp[1] for lp in lps], np.float64),
                 ub=concat([lp[2] for lp in lps], np.float64), y0=y0, draw_offset=np.ascontiguousarray(draw_offsets, dtype=np.int64))
 

@@ -25,24 +25,17 @@
 // then that LP's inequality rows: the order of the LP's own standard form; q, xp0, x, lb, ub, c and b are gathered LP by LP.
 // AdmmmLp, one per LP, holds its column and row ranges, where its vectors lie, and its level pointer.
 //
-// Two forms, the same arithmetic, chosen per LP from its shape only (SLP_ADMM_MANY_FORM=lds|global forces one):
-//   lds     2 N + m <= kAdmmmLdsLimit doubles: x, y, lambda live in LDS for the whole launch, x and lambda loaded at its start and
-//           written back at its end, y rebuilt by every right-hand side (160 000 of the compute unit's 163 840 bytes, as kCpmLdsLimit);
-//   global  x, y, lambda stay in global memory and are re-read across the barriers with workgroup-scope relaxed loads, nothing
-//           kept in a register across a barrier (as k_admmb_tile).
-// q, xp0, lb, ub, b and the matrices are read from global memory in both.  The LPs of each form are one launch.
+// Forms, workgroup width and launch cap: slp_many_plan.h (switches SLP_ADMM_MANY_FORM, SLP_ADMM_MANY_KMAX).  Here the lds form
+// holds x, y, lambda (2 N + m <= kAdmmmLdsLimit doubles; y is rebuilt by every right-hand side, so only x and lambda are loaded and
+// written back; the global form as k_admmb_tile); q, xp0, lb, ub, b and the matrices are read from global memory in both.  A pass
+// is the workgroup once over a stage or a level: nlevels + 2 passes per iteration.
 //
-// Workgroup width W, per launch: the power of two >= max over its LPs of max(widest level, ceil(max(N, m) / 4)), clamped to
-// 64 .. 1024 lanes (lanes loop beyond).  An iteration is nlevels + 2 barriers, and a barrier costs with the number of waves that
+// Workgroup width W: a launch wants max over its LPs of max(widest level, ceil(max(N, m) / 4)) lanes.  An iteration is
+// nlevels + 2 barriers, and a barrier costs with the number of waves that
 // meet at it; the levels of small LPs are a few rows wide while N and m reach hundreds, so W follows the widest level, and the
 // two full passes (right-hand side, multipliers) are bounded at four trips per lane instead of sizing W by them.  A function of
 // the shapes (and M's pattern) only.
 // No atomics between workgroups, no spin waits, no grid barrier: a workgroup never waits for another.
-//
-// Launch cap.  A pass is the workgroup once over a stage or a level: nlevels + 2 passes per iteration.  A launch holds at most
-// kAdmmmUnitsPerLaunch passes per compute unit: iterations per launch = kAdmmmUnitsPerLaunch / (passes per iteration of the
-// LP with most levels * ceil(LPs / compute units)), between 1 and 1024; longer runs are split.  SLP_ADMM_MANY_KMAX=<k> lowers the
-// cap (1: one iteration per launch); the iterates do not depend on it.
 //
 // Report (:213-248), per LP, one workgroup of 256 lanes on the written-back state: lane t takes rows (columns) t, t + 256, ...
 // in increasing order, then block_reduce: a fixed order, a function of the shapes only.  The maxima are exact.
@@ -51,18 +44,16 @@
 #include <type_traits>
 #include <utility>
 
-#include "slp_common.h"
 #include "slp_kernels.h"
 #include "slp_admm_iter.h"
 #include "slp_admm_shared.h"
+#include "slp_many.h"
 
 namespace slp {
 
 constexpr int kAdmmmMaxBlock = 1024;
 // doubles of x, y, lambda an LP may hold in LDS: 160 000 of the compute unit's 163 840 bytes (kCpmLdsLimit's reasoning)
 constexpr i64 kAdmmmLdsLimit = 20000;
-constexpr i64 kAdmmmUnitsPerLaunch = 8192;
-constexpr i64 kAdmmmMaxItersPerLaunch = 1024;
 constexpr i64 kAdmmmSinks = 4096;  // gs_plan: more sink rows than this in ONE LP go to a level of their own
 
 struct AdmmmLp {
@@ -76,9 +67,8 @@ struct AdmmmLp {
     i32 form;          // 0 lds, 1 global
 };
 
-// column j of the LP (variables first, then its slacks) / row r of the LP (equality rows first) in the composite's order
+// column j of the LP (variables first, then its slacks) in the composite's order; its rows: many_row
 __device__ __forceinline__ i64 admmm_col(const AdmmmLp &lp, i32 j) { return j < lp.n ? lp.col0 + j : lp.slack0 + (j - lp.n); }
-__device__ __forceinline__ i64 admmm_row(const AdmmmLp &lp, i32 r) { return r < lp.m_eq ? lp.eq0 + r : lp.in0 + (r - lp.m_eq); }
 
 // the index arrays of both orientations of A, composite -> local to the LP; one workgroup per LP (as k_cpm_localise)
 __global__ __launch_bounds__(kBlock) void k_admmm_localise(const AdmmmLp *__restrict__ lps, const i64 *__restrict__ ptr, i32 *__restrict__ idx,
@@ -86,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void k_admmm_localise(const AdmmmLp *__rest
     const AdmmmLp lp = lps[blockIdx.x];
     const i32 m = lp.m_eq + lp.m_in, N = lp.n + lp.m_in;
     for (i32 r = threadIdx.x; r < m; r += kBlock) {
-        const i64 g = admmm_row(lp, r);
+        const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
         for (i64 q = ptr[g]; q < ptr[g + 1]; ++q) {
             const i64 c = idx[q];
             idx[q] = (i32)(c < n_all ? c - lp.col0 : lp.n + (c - lp.slack0));
@@ -145,7 +135,7 @@ __global__ __launch_bounds__(kBlock) void k_admmm_gather_rows(const AdmmmLp *__r
                                                               double *__restrict__ dst) {
     const AdmmmLp lp = lps[blockIdx.x];
     const i32 m = lp.m_eq + lp.m_in;
-    for (i32 r = threadIdx.x; r < m; r += kBlock) dst[lp.lam0 + r] = src[admmm_row(lp, r)];
+    for (i32 r = threadIdx.x; r < m; r += kBlock) dst[lp.lam0 + r] = src[many_row(lp.eq0, lp.in0, lp.m_eq, r)];
 }
 
 struct AdmmmArgs {
@@ -200,7 +190,7 @@ __global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, i
         }
         if (stages & 2) {
             for (i32 r = tid; r < m; r += W) {
-                const i64 g = admmm_row(lp, r);
+                const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
                 ls[r] = admm_mult_one<1>(a.aptr[g], a.aptr[g + 1], a.aidx, a.aval, xs, ls + r, b + r, a.gamma_eq, ld);
             }
             __syncthreads();
@@ -220,7 +210,7 @@ __global__ __launch_bounds__(kBlock) void k_admmm_report(AdmmmArgs a, int first,
     const double *x = a.x + lp.x0, *lam = a.lam + lp.lam0, *b = a.b + lp.lam0, *c = a.c + lp.x0, *xp0 = a.xp0 + lp.x0;
     double s0 = 0.0, s1 = 0.0, mr = -__builtin_inf(), c0 = 0.0, c1 = 0.0, mx = -__builtin_inf();
     for (i32 r = threadIdx.x; r < m; r += kBlock) {
-        const i64 g = admmm_row(lp, r);
+        const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
         const double ax = admm_dot<1>(a.aptr[g], a.aptr[g + 1], a.aidx, a.aval, x, AdmmLoadPlain());
         const double res = ax - b[r];
         s0 += res * res;
@@ -256,16 +246,9 @@ struct slp_admm_many {
     double gamma_eq = 2, gamma_ineq = 3;
     bool xp_is_x = false;      // false only before the first multiplier step (:98 vs :259)
     std::vector<AdmmmLp> lps;
-    // the LPs of each form: their list on the device, the workgroup, the dynamic LDS and the iterations one launch may hold
-    struct Group {
-        std::vector<i32> ids;
-        DevBuf<i32> list;
-        int block = kWave;
-        size_t lds_bytes = 0;
-        i64 kmax = 1;
-    } group[2];
-    int force = -1;
-    i64 cap = kAdmmmMaxItersPerLaunch;
+    ManyGroup group[2];  // the LPs of each form
+    DevBuf<i32> list[2];
+    i64 cap = kManyMaxItersPerLaunch;  // SLP_ADMM_MANY_KMAX
     DevBuf<AdmmmLp> table;
     DevBuf<i64> gptr, lptr;
     DevBuf<i32> gidx, grows;
@@ -280,7 +263,7 @@ static AdmmmArgs admmm_args(const slp_admm_many *s, int g) {
     const CsrDev &A = s->sh.a->a, &At = s->sh.a->at;
     AdmmmArgs r;
     r.lps = s->table.p;
-    r.list = s->group[g].list.p;
+    r.list = s->list[g].p;
     r.tptr = At.ptr.p; r.tidx = At.idx.p; r.tval = At.val.p;
     r.aptr = A.ptr.p; r.aidx = A.idx.p; r.aval = A.val.p;
     r.gptr = s->gptr.p; r.gidx = s->gidx.p; r.gval = s->gval.p; r.ginvd = s->ginvd.p; r.grows = s->grows.p; r.lptr = s->lptr.p;
@@ -295,60 +278,38 @@ static void admmm_run(slp_admm_many *s, i64 k, int stages) {
     if (k <= 0) return;
     hipStream_t st = ctx().stream;
     for (int g = 0; g < 2; ++g) {
-        const slp_admm_many::Group &gr = s->group[g];
+        const ManyGroup &gr = s->group[g];
         if (gr.ids.empty()) continue;
         const AdmmmArgs a = admmm_args(s, g);
         bool xp_is_x = s->xp_is_x;
-        for (i64 done = 0; done < k;) {
-            const int it = (int)std::min<i64>(gr.kmax, k - done);
+        many_split(k, gr.kmax, [&](int it) {
             const int first = ((stages & 1) && !xp_is_x) ? 1 : 0;
             if (g == 0)
                 hipLaunchKernelGGL((k_admmm_iterate<true>), dim3((unsigned)gr.ids.size()), dim3(gr.block), gr.lds_bytes, st, a, it, first, stages);
             else
                 hipLaunchKernelGGL((k_admmm_iterate<false>), dim3((unsigned)gr.ids.size()), dim3(gr.block), 0, st, a, it, first, stages);
-            SLP_HIP(hipGetLastError());
             if (stages & 2) xp_is_x = true;  // :259
-            done += it;
-        }
+            return it;
+        });
     }
     if (stages & 2) s->xp_is_x = true;
 }
 
-// the two environment switches, read before anything is allocated
-static void admmm_switches(slp_admm_many *s) {
-    if (const char *e = getenv("SLP_ADMM_MANY_FORM")) {
-        if (!strcmp(e, "lds")) s->force = 0;
-        else if (!strcmp(e, "global")) s->force = 1;
-        else if (e[0]) throw Error(std::string("SLP_ADMM_MANY_FORM must be lds or global, not ") + e);
-    }
-    if (const char *e = getenv("SLP_ADMM_MANY_KMAX")) {
-        if (e[0]) {
-            const i64 v = atoll(e);
-            if (v < 1) throw Error(std::string("SLP_ADMM_MANY_KMAX must be a positive number of iterations, not ") + e);
-            s->cap = std::min(s->cap, v);
-        }
-    }
-}
-
-// form per LP -- from the shapes (and the switch) only; needs no device
+// the two environment switches and the form per LP -- from the shapes only; needs no device, nothing is allocated yet
 static void admmm_forms(slp_admm_many *s) {
-    for (i64 k = 0; k < s->count; ++k) {
-        AdmmmLp &lp = s->lps[(size_t)k];
-        const i64 doubles = 2 * ((i64)lp.n + lp.m_in) + lp.m_eq + lp.m_in;
-        const bool fits = doubles <= kAdmmmLdsLimit;
-        if (s->force == 0 && !fits)
-            throw Error("slp_admm_many_create: SLP_ADMM_MANY_FORM=lds, but LP " + std::to_string(k) + " needs " + std::to_string(doubles) +
-                        " doubles of LDS (2 N + m) and the form holds " + std::to_string(kAdmmmLdsLimit));
-        lp.form = s->force >= 0 ? s->force : (fits ? 0 : 1);
-        s->group[lp.form].ids.push_back((i32)k);
-    }
+    const int force = many_form_switch("SLP_ADMM_MANY_FORM");
+    s->cap = many_kmax_switch("SLP_ADMM_MANY_KMAX", s->cap);
+    std::vector<i64> lds_doubles;
+    for (const AdmmmLp &lp : s->lps) lds_doubles.push_back(2 * ((i64)lp.n + lp.m_in) + lp.m_eq + lp.m_in);
+    const std::vector<i32> form =
+        many_assign_forms(lds_doubles, kAdmmmLdsLimit, force, "slp_admm_many_create", "SLP_ADMM_MANY_FORM", "2 N + m", s->group);
+    for (size_t k = 0; k < form.size(); ++k) s->lps[k].form = form[k];
 }
 
 // workgroup, LDS and launch cap per form, once the levels of every LP are known
 static void admmm_plan(slp_admm_many *s) {
-    const i64 cus = std::max(1, ctx().num_cu);
     for (int g = 0; g < 2; ++g) {
-        slp_admm_many::Group &gr = s->group[g];
+        ManyGroup &gr = s->group[g];
         if (gr.ids.empty()) continue;
         i64 want = 1, doubles = 0, passes = 1;
         for (i32 k : gr.ids) {
@@ -358,12 +319,9 @@ static void admmm_plan(slp_admm_many *s) {
             doubles = std::max<i64>(doubles, 2 * N + m);
             passes = std::max<i64>(passes, (i64)lp.nlevels + 2);
         }
-        int w = kWave;
-        while (w < want && w < kAdmmmMaxBlock) w *= 2;
-        gr.block = w;
+        gr.block = many_width(want, kAdmmmMaxBlock);
         gr.lds_bytes = g == 0 ? (size_t)doubles * sizeof(double) : 0;
-        const i64 rounds = ((i64)gr.ids.size() + cus - 1) / cus;
-        gr.kmax = std::min(s->cap, std::max<i64>(1, kAdmmmUnitsPerLaunch / (passes * rounds)));
+        gr.kmax = many_launch_cap(kManyUnitsPerLaunch, passes, (i64)gr.ids.size(), ctx().num_cu, s->cap);
     }
 }
 
@@ -475,7 +433,6 @@ slp_admm_many *slp_admm_many_create(int64_t count, const int64_t *n, const int64
         // well formed and to fit
         auto s = std::unique_ptr<slp_admm_many>(new slp_admm_many());
         s->count = count; s->gamma_eq = gamma_eq; s->gamma_ineq = gamma_ineq;
-        admmm_switches(s.get());
         s->lps.resize((size_t)count);
         i64 nn = 0, Me = 0, Mi = 0;
         for (i64 k = 0; k < count; ++k) {
@@ -494,20 +451,15 @@ slp_admm_many *slp_admm_many_create(int64_t count, const int64_t *n, const int64
         s->n = nn; s->N = N; s->m = M; s->m_eq = Me;
         SLP_REQUIRE(Me == 0 || (eq_indptr && b_eq), "slp_admm_many_create: NULL equality block");
         auto check_block = [&](const char *what, const int64_t *indptr, const int32_t *indices, const double *data, i64 rows, bool ineq) {
-            SLP_REQUIRE(indptr[0] == 0, std::string("slp_admm_many_create: the row pointer of the ") + what + " block must start at 0");
-            for (i64 r = 0; r < rows; ++r)
-                SLP_REQUIRE(indptr[r + 1] >= indptr[r], std::string("slp_admm_many_create: the row pointer of the ") + what + " block decreases");
-            SLP_REQUIRE(indptr[rows] == 0 || (indices && data), "slp_admm_many_create: NULL argument");
+            std::vector<ManyRows> of_lp;
             for (i64 k = 0; k < count; ++k) {
                 const AdmmmLp &lp = s->lps[(size_t)k];
-                const i64 r0 = ineq ? lp.in0 - Me : lp.eq0, r1 = r0 + (ineq ? lp.m_in : lp.m_eq);
-                const i64 lo = lp.col0, hi = lp.col0 + lp.n;
-                for (i64 q = indptr[r0]; q < indptr[r1]; ++q)
-                    if (indices[q] < lo || indices[q] >= hi)
-                        throw Error(std::string("slp_admm_many_create: a row of the ") + what + " block of LP " + std::to_string(k) +
-                                    " has the column index " + std::to_string(indices[q]) + " outside the LP's columns [" + std::to_string(lo) + ", " +
-                                    std::to_string(hi) + ")");
+                const i64 r0 = ineq ? lp.in0 - Me : lp.eq0;
+                of_lp.push_back({k, r0, r0 + (ineq ? lp.m_in : lp.m_eq), lp.col0, lp.col0 + lp.n});
             }
+            const std::string block = std::string("the ") + what + " block";
+            many_check_block({"slp_admm_many_create", "the row pointer of " + block, "decreases", block + " of ", false}, indptr, indices,
+                             indices && data, rows, of_lp);
         };
         if (Me) check_block("equality", eq_indptr, eq_indices, eq_data, Me, false);
         check_block("inequality", in_indptr, in_indices, in_data, Mi, true);
@@ -515,17 +467,12 @@ slp_admm_many *slp_admm_many_create(int64_t count, const int64_t *n, const int64
         {
             // both copies of A with the scratch of the chain, M twice (the plan's copy and the regrouped one) with the lane records
             // of the SpGEMM (at most the sum of squared row lengths entries), thirteen vectors over the columns and four over the rows
-            i64 free_b = 0, total_b = 0;
-            SLP_REQUIRE(slp_device_memory(&free_b, &total_b) == 0, slp_last_error());
             double nnz_a = (double)in_indptr[Mi] + (double)Mi + (Me ? (double)eq_indptr[Me] : 0.0), sq = 0.0;
             for (i64 i = 0; i < Mi; ++i) { const double l = (double)(in_indptr[i + 1] - in_indptr[i]) + 1.0; sq += l * l; }
             for (i64 i = 0; i < Me; ++i) { const double l = (double)(eq_indptr[i + 1] - eq_indptr[i]); sq += l * l; }
-            const double need = 64.0 * nnz_a + 52.0 * (sq + (double)N) + 8.0 * (13.0 * (double)N + 4.0 * (double)M) + 16.0 * 8.0 * (double)(N + M) +
-                                (double)count * (double)(sizeof(AdmmmLp) + sizeof(i32) + 3 * sizeof(double));
-            const double have = (double)free_b + (double)slp_cached_bytes();
-            if (need > have)
-                throw Error("slp_admm_many_create: " + std::to_string(count) + " LPs need " + std::to_string(need / 1e9) +
-                            " GB of device memory, " + std::to_string(have / 1e9) + " GB are free");
+            many_require_memory("slp_admm_many_create", count,
+                                64.0 * nnz_a + 52.0 * (sq + (double)N) + 8.0 * (13.0 * (double)N + 4.0 * (double)M) + 16.0 * 8.0 * (double)(N + M) +
+                                    (double)count * (double)(sizeof(AdmmmLp) + sizeof(i32) + 3 * sizeof(double)));
         }
         hipStream_t st = ctx().stream;
         // the whole chain once, on the composite (its x0 = [x0; A_ineq x0] block by block: the scaled block is block-diagonal too)
@@ -539,11 +486,8 @@ slp_admm_many *slp_admm_many_create(int64_t count, const int64_t *n, const int64
         const dim3 per_lp((unsigned)count);
         hipLaunchKernelGGL(k_admmm_localise, per_lp, dim3(kBlock), 0, st, s->table.p, A.ptr.p, A.idx.p, At.ptr.p, At.idx.p, nn, Me);
         SLP_HIP(hipGetLastError());
-        for (int g = 0; g < 2; ++g)
-            if (!s->group[g].ids.empty()) s->group[g].list.upload(s->group[g].ids.data(), s->group[g].ids.size());
-        if (s->group[0].lds_bytes > 48 * 1024)
-            SLP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_admmm_iterate<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)(kAdmmmLdsLimit * sizeof(double))));
+        many_upload_lists(s->group, s->list);
+        many_lds_opt_in(reinterpret_cast<const void *>(k_admmm_iterate<true>), s->group[0].lds_bytes, kAdmmmLdsLimit * sizeof(double));
         s->b.alloc((size_t)M); s->lam.alloc((size_t)M); s->lam.zero();
         for (DevBuf<double> *v : {&s->q, &s->c, &s->lb, &s->ub, &s->xp0, &s->x, &s->y}) v->alloc((size_t)N);
         s->y.zero();

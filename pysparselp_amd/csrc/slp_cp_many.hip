@@ -18,18 +18,10 @@
 // x, z, x4, c, lb, ub, T are concatenated LP by LP; y is kept LP by LP as [y_eq,k; y_ineq,k]; b and Sigma in the row order of K.
 // CpmLp, one per LP, holds its column range and its two row ranges.
 //
-// Two forms, the same arithmetic, chosen per LP from its shape only (SLP_CP_MANY_FORM=lds|global forces one):
-//   lds     2 n + m <= kCpmLdsLimit doubles: x, z, y live in LDS for the whole launch, loaded at its start and written back at its end;
-//   global  x, z, y stay in global memory and are re-read across the barriers with workgroup-scope relaxed loads, nothing kept in
-//           a register across a barrier (as k_admmb_tile, k_gs_sweep_one_block).
-// c, T, lb, ub, b, Sigma are read from global memory in both.  The LPs of each form are one launch; its workgroup has
-// W = the power of two >= max_k max(n_k, m_k) over the LPs of that form, clamped to 64 .. 1024 lanes (lanes loop beyond).
+// Forms, workgroup width and launch cap: slp_many_plan.h (switches SLP_CP_MANY_FORM, SLP_CP_MANY_KMAX).  Here the lds form holds
+// x, z, y (2 n + m <= kCpmLdsLimit doubles; the global form as k_admmb_tile, k_gs_sweep_one_block); c, T, lb, ub, b, Sigma are read
+// from global memory in both.  A launch wants max_k max(n_k, m_k) lanes, and a pass is the workgroup once over its columns or rows.
 // No atomics between workgroups, no spin waits, no grid barrier: a workgroup never waits for another.
-//
-// Launch cap.  A launch holds at most kCpmUnitsPerLaunch workgroup passes (a pass: the workgroup once over its columns or rows) per
-// compute unit: iterations per launch = kCpmUnitsPerLaunch / (passes per iteration of the largest LP * ceil(LPs / compute units)),
-// between 1 and 1024; longer runs are split.  SLP_CP_MANY_KMAX=<k> lowers the cap (1: one iteration per launch); the iterates do not
-// depend on it.
 //
 // Report, per LP, one workgroup of 256 lanes on the written-back state: lane t takes rows (columns) t, t + 256, ... in increasing
 // order -- per row the three chains K x, K x4, K z of one walk -- then block_reduce: a fixed order, a function of the shapes only.
@@ -38,9 +30,9 @@
 #include <memory>
 #include <type_traits>
 
-#include "slp_common.h"
 #include "slp_cp_shared.h"
 #include "slp_kernels.h"
+#include "slp_many.h"
 
 namespace slp {
 
@@ -51,8 +43,6 @@ constexpr int kCpmMaxBlock = 1024;
 // doubles of x, z, y an LP may hold in LDS: 160 000 of the compute unit's 163 840 bytes; the rest stays free for a kernel's static
 // scratch (block_reduce: 32 bytes)
 constexpr i64 kCpmLdsLimit = 20000;
-constexpr i64 kCpmUnitsPerLaunch = 8192;
-constexpr i64 kCpmMaxItersPerLaunch = 1024;
 
 struct CpmLp {
     i64 col0;      // first column: x, z, x4, c, lb, ub, T; rows of K^T
@@ -62,16 +52,13 @@ struct CpmLp {
     i32 form;      // 0 lds, 1 global
 };
 
-// row `r` of the LP (equality rows first) in the row order of K
-__device__ __forceinline__ i64 cpm_row(const CpmLp &lp, i32 r) { return r < lp.m_eq ? lp.eq0 + r : lp.in0 + (r - lp.m_eq); }
-
 // the index arrays of both orientations, global -> local to the LP; one workgroup per LP
 __global__ __launch_bounds__(kBlock) void k_cpm_localise(const CpmLp *__restrict__ lps, const i64 *__restrict__ ptr, i32 *__restrict__ idx,
                                                          const i64 *__restrict__ tptr, i32 *__restrict__ tidx, i64 m_eq_all) {
     const CpmLp lp = lps[blockIdx.x];
     const i32 m = lp.m_eq + lp.m_in;
     for (i32 r = threadIdx.x; r < m; r += kBlock) {
-        const i64 g = cpm_row(lp, r);
+        const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
         for (i64 q = ptr[g]; q < ptr[g + 1]; ++q) idx[q] = (i32)(idx[q] - lp.col0);
     }
     for (i32 j = threadIdx.x; j < lp.n; j += kBlock)
@@ -129,7 +116,7 @@ __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int ite
         }
         if (stages & 2) {
             for (i32 r = tid; r < m; r += W) {
-                const i64 g = cpm_row(lp, r);
+                const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
                 const double kz = cp_row_sum(a.ptr[g], a.ptr[g + 1], a.idx, a.val, zs, 1, ld);
                 ys[r] = cp_dual_point(kz, a.b[g], ld(ys + r), a.sigma[g], r >= lp.m_eq);
             }
@@ -150,7 +137,7 @@ __global__ __launch_bounds__(kBlock) void k_cpm_report(CpmArgs a, double *__rest
     const double *x = a.x + lp.col0, *x4 = a.x4 + lp.col0, *z = a.z + lp.col0, *y = a.y + lp.y0, *c = a.c + lp.col0;
     double s1 = 0.0, s2 = 0.0, veq = -__builtin_inf(), vin = -__builtin_inf(), veqx = -__builtin_inf(), c0 = 0.0, c1 = 0.0;
     for (i32 r = threadIdx.x; r < m; r += kBlock) {
-        const i64 g = cpm_row(lp, r);
+        const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
         double kx = 0.0, kx4 = 0.0, kz = 0.0;  // three chains in storage order
         for (i64 q = a.ptr[g]; q < a.ptr[g + 1]; ++q) {
             const i32 j = a.idx[q];
@@ -198,14 +185,8 @@ struct slp_cp_many {
     i64 count = 0, n = 0, m = 0, m_eq = 0;
     double alpha = 1, theta = 1;
     std::vector<CpmLp> lps;
-    // the LPs of each form: their list on the device, the workgroup, the dynamic LDS and the iterations one launch may hold
-    struct Group {
-        std::vector<i32> ids;
-        DevBuf<i32> list;
-        int block = kWave;
-        size_t lds_bytes = 0;
-        i64 kmax = 1;
-    } group[2];
+    ManyGroup group[2];  // the LPs of each form
+    DevBuf<i32> list[2];
     DevBuf<CpmLp> table;
     DevBuf<double> b, c, lb, ub, t, sigma, x, z, y, x4, out;
     ~slp_cp_many() { delete k; }
@@ -217,7 +198,7 @@ static CpmArgs cpm_args(const slp_cp_many *s, int g) {
     const CsrDev &a = s->k->a, &at = s->k->at;
     CpmArgs r;
     r.lps = s->table.p;
-    r.list = s->group[g].list.p;
+    r.list = s->list[g].p;
     r.ptr = a.ptr.p; r.tptr = at.ptr.p;
     r.idx = a.idx.p; r.tidx = at.idx.p;
     r.val = a.val.p; r.tval = at.val.p;
@@ -232,51 +213,31 @@ static CpmArgs cpm_args(const slp_cp_many *s, int g) {
 static void cpm_run(slp_cp_many *s, i64 k, int stages, bool store) {
     hipStream_t st = ctx().stream;
     for (int g = 0; g < 2; ++g) {
-        const slp_cp_many::Group &gr = s->group[g];
+        const ManyGroup &gr = s->group[g];
         if (gr.ids.empty()) continue;
         const CpmArgs a = cpm_args(s, g);
-        for (i64 done = 0; done < k;) {
-            const int it = (int)std::min<i64>(gr.kmax, k - done);
+        many_split(k, gr.kmax, [&](int it) {
             if (g == 0)
                 hipLaunchKernelGGL((k_cpm_iterate<true>), dim3((unsigned)gr.ids.size()), dim3(gr.block), gr.lds_bytes, st, a, it, stages,
                                    (int)store);
             else
                 hipLaunchKernelGGL((k_cpm_iterate<false>), dim3((unsigned)gr.ids.size()), dim3(gr.block), 0, st, a, it, stages, (int)store);
-            SLP_HIP(hipGetLastError());
-            done += it;
-        }
+            return it;
+        });
     }
 }
 
 // form per LP, workgroup, LDS and launch cap per form -- from the shapes (and the two environment switches) only
 static void cpm_plan(slp_cp_many *s) {
-    int force = -1;
-    if (const char *e = getenv("SLP_CP_MANY_FORM")) {
-        if (!strcmp(e, "lds")) force = 0;
-        else if (!strcmp(e, "global")) force = 1;
-        else if (e[0]) throw Error(std::string("SLP_CP_MANY_FORM must be lds or global, not ") + e);
-    }
-    i64 cap = kCpmMaxItersPerLaunch;
-    if (const char *e = getenv("SLP_CP_MANY_KMAX")) {
-        if (e[0]) {
-            const i64 v = atoll(e);
-            if (v < 1) throw Error(std::string("SLP_CP_MANY_KMAX must be a positive number of iterations, not ") + e);
-            cap = std::min(cap, v);
-        }
-    }
-    for (i64 k = 0; k < s->count; ++k) {
-        CpmLp &lp = s->lps[(size_t)k];
-        const i64 doubles = 2 * (i64)lp.n + lp.m_eq + lp.m_in;
-        const bool fits = doubles <= kCpmLdsLimit;
-        if (force == 0 && !fits)
-            throw Error("slp_cp_many_create: SLP_CP_MANY_FORM=lds, but LP " + std::to_string(k) + " needs " + std::to_string(doubles) +
-                        " doubles of LDS (2 n + m) and the form holds " + std::to_string(kCpmLdsLimit));
-        lp.form = force >= 0 ? force : (fits ? 0 : 1);
-        s->group[lp.form].ids.push_back((i32)k);
-    }
-    const i64 cus = std::max(1, ctx().num_cu);
+    const int force = many_form_switch("SLP_CP_MANY_FORM");
+    const i64 cap = many_kmax_switch("SLP_CP_MANY_KMAX", kManyMaxItersPerLaunch);
+    std::vector<i64> lds_doubles;
+    for (const CpmLp &lp : s->lps) lds_doubles.push_back(2 * (i64)lp.n + lp.m_eq + lp.m_in);
+    const std::vector<i32> form =
+        many_assign_forms(lds_doubles, kCpmLdsLimit, force, "slp_cp_many_create", "SLP_CP_MANY_FORM", "2 n + m", s->group);
+    for (size_t k = 0; k < form.size(); ++k) s->lps[k].form = form[k];
     for (int g = 0; g < 2; ++g) {
-        slp_cp_many::Group &gr = s->group[g];
+        ManyGroup &gr = s->group[g];
         if (gr.ids.empty()) continue;
         i64 widest = 1, doubles = 0;
         for (i32 k : gr.ids) {
@@ -284,8 +245,7 @@ static void cpm_plan(slp_cp_many *s) {
             widest = std::max<i64>(widest, std::max<i64>(lp.n, (i64)lp.m_eq + lp.m_in));
             doubles = std::max<i64>(doubles, 2 * (i64)lp.n + lp.m_eq + lp.m_in);
         }
-        int w = kWave;
-        while (w < widest && w < kCpmMaxBlock) w *= 2;
+        const int w = many_width(widest, kCpmMaxBlock);
         gr.block = w;
         gr.lds_bytes = g == 0 ? (size_t)doubles * sizeof(double) : 0;
         i64 passes = 1;
@@ -293,8 +253,7 @@ static void cpm_plan(slp_cp_many *s) {
             const CpmLp &lp = s->lps[(size_t)k];
             passes = std::max<i64>(passes, (lp.n + w - 1) / w + ((i64)lp.m_eq + lp.m_in + w - 1) / w);
         }
-        const i64 rounds = ((i64)gr.ids.size() + cus - 1) / cus;
-        gr.kmax = std::min(cap, std::max<i64>(1, kCpmUnitsPerLaunch / (passes * rounds)));
+        gr.kmax = many_launch_cap(kManyUnitsPerLaunch, passes, (i64)gr.ids.size(), ctx().num_cu, cap);
     }
 }
 
@@ -329,33 +288,20 @@ slp_cp_many *slp_cp_many_create(int64_t count, const int64_t *n, const int64_t *
         for (CpmLp &lp : s->lps) lp.in0 += Me;
         const i64 M = Me + Mi;
         s->n = N; s->m = M; s->m_eq = Me;
-        SLP_REQUIRE(indptr[0] == 0, "slp_cp_many_create: indptr must start at 0");
-        for (i64 r = 0; r < M; ++r) SLP_REQUIRE(indptr[r + 1] >= indptr[r], "slp_cp_many_create: indptr must be non-decreasing");
-        const i64 nnz = indptr[M];
-        SLP_REQUIRE(nnz == 0 || (indices && data), "slp_cp_many_create: NULL argument");
+        std::vector<ManyRows> rows;  // an LP's equality rows, then its inequality rows
         for (i64 k = 0; k < count; ++k) {
             const CpmLp &lp = s->lps[(size_t)k];
-            const i64 lo = lp.col0, hi = lp.col0 + lp.n;
-            const i64 q0[2] = {indptr[lp.eq0], indptr[lp.in0]}, q1[2] = {indptr[lp.eq0 + lp.m_eq], indptr[lp.in0 + lp.m_in]};
-            for (int part = 0; part < 2; ++part)
-                for (i64 q = q0[part]; q < q1[part]; ++q)
-                    if (indices[q] < lo || indices[q] >= hi)
-                        throw Error("slp_cp_many_create: a row of LP " + std::to_string(k) + " has the column index " + std::to_string(indices[q]) +
-                                    " outside the LP's columns [" + std::to_string(lo) + ", " + std::to_string(hi) + ")");
+            rows.push_back({k, lp.eq0, lp.eq0 + lp.m_eq, lp.col0, lp.col0 + lp.n});
+            rows.push_back({k, lp.in0, lp.in0 + lp.m_in, lp.col0, lp.col0 + lp.n});
         }
+        many_check_block({"slp_cp_many_create", "indptr", "must be non-decreasing", "", false}, indptr, indices, indices && data, M, rows);
+        const i64 nnz = indptr[M];
         cpm_plan(s.get());
-        {
-            // the CSR pair and the scratch of the device transposition, seven vectors over the columns (x, z, x4, c, lb, ub, T),
-            // three over the rows (y, b, Sigma), the table, the lists and the report
-            i64 free_b = 0, total_b = 0;
-            SLP_REQUIRE(slp_device_memory(&free_b, &total_b) == 0, slp_last_error());
-            const double need = 40.0 * (double)nnz + 16.0 * (double)(N + M + 2) + 8.0 * (7.0 * (double)N + 3.0 * (double)M) +
-                                (double)count * (double)(sizeof(CpmLp) + sizeof(i32) + 5 * sizeof(double));
-            const double have = (double)free_b + (double)slp_cached_bytes();
-            if (need > have)
-                throw Error("slp_cp_many_create: " + std::to_string(count) + " LPs need " + std::to_string(need / 1e9) +
-                            " GB of device memory, " + std::to_string(have / 1e9) + " GB are free");
-        }
+        // the CSR pair and the scratch of the device transposition, seven vectors over the columns (x, z, x4, c, lb, ub, T),
+        // three over the rows (y, b, Sigma), the table, the lists and the report
+        many_require_memory("slp_cp_many_create", count,
+                            40.0 * (double)nnz + 16.0 * (double)(N + M + 2) + 8.0 * (7.0 * (double)N + 3.0 * (double)M) +
+                                (double)count * (double)(sizeof(CpmLp) + sizeof(i32) + 5 * sizeof(double)));
         s->k = slp_matrix_create(M, N, indptr, indices, data);
         if (!s->k) throw Error(slp_last_error());
         require_csr(s->k, "slp_cp_many_create");
@@ -367,11 +313,8 @@ slp_cp_many *slp_cp_many_create(int64_t count, const int64_t *n, const int64_t *
         hipLaunchKernelGGL(k_cpm_localise, dim3((unsigned)count), dim3(kBlock), 0, ctx().stream, s->table.p, s->k->a.ptr.p, s->k->a.idx.p,
                            s->k->at.ptr.p, s->k->at.idx.p, Me);
         SLP_HIP(hipGetLastError());
-        for (int g = 0; g < 2; ++g)
-            if (!s->group[g].ids.empty()) s->group[g].list.upload(s->group[g].ids.data(), s->group[g].ids.size());
-        if (s->group[0].lds_bytes > 48 * 1024)
-            SLP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cpm_iterate<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)(kCpmLdsLimit * sizeof(double))));
+        many_upload_lists(s->group, s->list);
+        many_lds_opt_in(reinterpret_cast<const void *>(k_cpm_iterate<true>), s->group[0].lds_bytes, kCpmLdsLimit * sizeof(double));
         s->c.upload(c, (size_t)N);
         s->lb.upload(lb, (size_t)N);
         s->ub.upload(ub, (size_t)N);

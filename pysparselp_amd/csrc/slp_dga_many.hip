@@ -25,11 +25,9 @@
 //
 // Dynamic LDS: 16 reduction slots, then the search's fused_lds_bytes(npad) for the largest npad of the list.
 //
-// Launch cap.  A launch holds at most kDgmUnitsPerLaunch workgroup passes per compute unit (a pass: the workgroup once over its
-// columns, its rows, a round of the gradient pass or a stage of the sort): iterations per launch = kDgmUnitsPerLaunch / (passes per
-// iteration of the largest LP * ceil(LPs / compute units)), between 1 and 1024, and no more than the draws on the device allow
-// (two per iteration behind the furthest LP).  Longer runs are split; SLP_DGA_MANY_KMAX=<k> lowers the cap.  The iterates do not
-// depend on the split.
+// Launch cap: slp_many_plan.h (switch SLP_DGA_MANY_KMAX).  A pass is the workgroup once over its columns, its rows, a round of the
+// gradient pass or a stage of the sort (dgm_passes); a launch also holds no more iterations than the draws on the device allow
+// (two per iteration behind the furthest LP).
 //
 // Tie draws: all LPs read the one stream of uniform draws, LP k at its own position draw_offset_k + consumed_k (draw_offset_k: the
 // draws its default start took).  The device holds a window of the stream from the smallest position on.
@@ -39,16 +37,14 @@
 #include <cstring>
 #include <memory>
 
-#include "slp_common.h"
 #include "slp_kernels.h"
 #include "slp_dga_shared.h"
+#include "slp_many.h"
 
 using namespace slp;
 
 namespace {
 
-constexpr i64 kDgmUnitsPerLaunch = 8192;
-constexpr i64 kDgmMaxItersPerLaunch = 1024;
 constexpr size_t kDgmSlotBytes = 16 * sizeof(double);   // 4 reduction slots for each of the 4 virtual blocks
 
 struct DgmLp {
@@ -252,20 +248,10 @@ i64 dgm_passes(const DgmLp &lp) {
 }
 
 void dgm_plan(slp_many_dga *s) {
-    i64 cap = kDgmMaxItersPerLaunch;
-    if (const char *e = getenv("SLP_DGA_MANY_KMAX")) {
-        if (e[0]) {
-            char *end = nullptr;
-            const long long v = strtoll(e, &end, 10);
-            if (v < 1 || (end && *end)) throw Error(std::string("SLP_DGA_MANY_KMAX must be a positive number of iterations, not ") + e);
-            cap = std::min<i64>(cap, v);
-        }
-    }
+    const i64 cap = many_kmax_switch("SLP_DGA_MANY_KMAX", kManyMaxItersPerLaunch);
     i64 passes = 1;
     for (const DgmLp &lp : s->lps) passes = std::max(passes, dgm_passes(lp));
-    const i64 cus = std::max(1, ctx().num_cu);
-    const i64 waves = (s->count + cus - 1) / cus;
-    s->kmax = std::min(cap, std::max<i64>(1, kDgmUnitsPerLaunch / (passes * waves)));
+    s->kmax = many_launch_cap(kManyUnitsPerLaunch, passes, s->count, ctx().num_cu, cap);
 }
 
 size_t dgm_lds_bytes(const slp_many_dga *s) { return kDgmSlotBytes + fused_lds_bytes(s->max_npad); }
@@ -342,31 +328,20 @@ slp_many_dga *slp_many_dga_create(int64_t count, const int64_t *n, const int64_t
             s->max_npad = std::max(s->max_npad, npad);
         }
         s->n = N; s->m = M;
-        SLP_REQUIRE(indptr[0] == 0, "slp_many_dga_create: indptr must start at 0");
-        for (i64 r = 0; r < M; ++r) SLP_REQUIRE(indptr[r + 1] >= indptr[r], "slp_many_dga_create: indptr must be non-decreasing");
-        const i64 nnz = indptr[M];
-        SLP_REQUIRE(nnz < ((i64)1 << 31), "slp_many_dga_create: the list has 2^31 or more entries");
-        SLP_REQUIRE(nnz == 0 || (indices && data), "slp_many_dga_create: NULL argument");
+        std::vector<ManyRows> rows;
         for (i64 k = 0; k < count; ++k) {
             const DgmLp &lp = s->lps[(size_t)k];
-            for (i64 q = indptr[lp.row0]; q < indptr[lp.row0 + lp.m_eq + lp.m_in]; ++q)
-                if (indices[q] < 0 || indices[q] >= lp.n)
-                    throw Error("slp_many_dga_create: a row of LP " + std::to_string(k) + " has the column index " + std::to_string(indices[q]) +
-                                ", not local to the LP's " + std::to_string(lp.n) + " columns");
+            rows.push_back({k, lp.row0, lp.row0 + lp.m_eq + lp.m_in, 0, lp.n});
         }
+        many_check_block({"slp_many_dga_create", "indptr", "must be non-decreasing", "", true}, indptr, indices, indices && data, M, rows);
+        const i64 nnz = indptr[M];
+        SLP_REQUIRE(nnz < ((i64)1 << 31), "slp_many_dga_create: the list has 2^31 or more entries");
         dgm_plan(s.get());
-        {
-            // both orientations (20 B an entry), the pointers, ten vectors over the columns (c, lb, ub, x, c_bar, d and the report's
-            // two), seven over the rows, per LP the table, the controls and the partial results of the pass and of the report
-            i64 free_b = 0, total_b = 0;
-            SLP_REQUIRE(slp_device_memory(&free_b, &total_b) == 0, slp_last_error());
-            const double need = 24.0 * (double)nnz + 8.0 * (double)(N + M + 2) + 8.0 * (8.0 * (double)N + 7.0 * (double)M) +
-                                (double)count * (double)(sizeof(DgmLp) + sizeof(DgaCtl) + 8.0 * 7.0 * kDgaParts);
-            const double have = (double)free_b + (double)slp_cached_bytes();
-            if (need > have)
-                throw Error("slp_many_dga_create: " + std::to_string(count) + " LPs need " + std::to_string(need / 1e9) +
-                            " GB of device memory, " + std::to_string(have / 1e9) + " GB are free");
-        }
+        // both orientations (20 B an entry), the pointers, ten vectors over the columns (c, lb, ub, x, c_bar, d and the report's
+        // two), seven over the rows, per LP the table, the controls and the partial results of the pass and of the report
+        many_require_memory("slp_many_dga_create", count,
+                            24.0 * (double)nnz + 8.0 * (double)(N + M + 2) + 8.0 * (8.0 * (double)N + 7.0 * (double)M) +
+                                (double)count * (double)(sizeof(DgmLp) + sizeof(DgaCtl) + 8.0 * 7.0 * kDgaParts));
         // K_k^T on the host: a counting transposition per LP walks its rows in order, so rows increase inside a column
         std::vector<i64> tptr((size_t)N + 1, 0);
         std::vector<i32> tidx((size_t)nnz);
@@ -423,17 +398,16 @@ int slp_many_dga_iterate(slp_many_dga *s, int64_t k) {
     SLP_API_INT({
         SLP_REQUIRE(s && k >= 0, "slp_many_dga_iterate: bad arguments");
         hipStream_t st = ctx().stream;
-        for (i64 done = 0; done < k;) {
+        many_split(k, s->kmax, [&](int want) {
             // at most two tie draws per LP and iteration: iterations the buffer cannot run dry in
-            const int it = (int)s->draws.reserve(std::min<i64>(s->kmax, k - done));
-            if (it < 1) break;
+            const int it = (int)s->draws.reserve(want);
+            if (it < 1) return it;
             s->timer.mark(-1);
             hipLaunchKernelGGL(k_dgm_iterate, dim3((unsigned)s->count), dim3(kDgaFusedThreads), dgm_lds_bytes(s), st, dgm_args(s), it);
-            SLP_HIP(hipGetLastError());
             s->timer.mark(ST_FUSED);
-            done += it;
             s->iters += it;
-        }
+            return it;
+        });
     })
 }
 

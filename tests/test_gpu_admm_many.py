@@ -272,3 +272,13 @@ def test_solve_admm_many_equals_solve_per_lp():
         for name in ("pobj_curve", "dobj_curve"):
             np.testing.assert_allclose(getattr(lp, name), getattr(one, name), **ENERGY_TOL)
     assert len(solve_admm_many(lps[:2], get_timing=False, nb_iter=5)) == 2
+
+
+def test_the_launch_cap_switch_is_parsed_strictly(monkeypatch):
+    """A value that is not a positive number -- trailing text included -- is refused before anything is allocated."""
+    from pysparselp_amd import SlpError
+
+    for bad in ("0", "abc", "7x"):
+        monkeypatch.setenv("SLP_ADMM_MANY_KMAX", bad)
+        with pytest.raises(SlpError, match="SLP_ADMM_MANY_KMAX must be a positive number of iterations"):
+            _many_state([_problem("random0"), _problem("random1")])

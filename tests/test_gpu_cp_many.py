@@ -411,3 +411,15 @@ def test_refusals_return_the_library_error_and_allocate_nothing(form_env):
     form_env()
     h = _lib.check_handle(create(s))   # the same arguments, untouched, are accepted
     lib.slp_cp_many_destroy(h)
+
+
+def test_the_launch_cap_switch_is_parsed_strictly(form_env):
+    """A value that is not a positive number -- trailing text included -- is refused before anything is allocated."""
+    from pysparselp_amd import SlpError
+
+    CPManyState, prep = _mods()[0], _mods()[5]
+    lps = [prep(k, _fixture_problem(c)) for k, c in enumerate(("random0", "random1"))]
+    for bad in ("0", "abc", "7x"):
+        form_env(kmax=bad)
+        with pytest.raises(SlpError, match="SLP_CP_MANY_KMAX must be a positive number of iterations"):
+            CPManyState(lps)
