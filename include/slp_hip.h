@@ -299,6 +299,17 @@ int slp_cp_many_form(const slp_cp_many *s, int64_t k);
 int64_t slp_cp_many_lds_limit(void);
 /* As slp_cp_bench, per iteration of the whole set: ms[0] iteration, ms[1] primal half alone, ms[2] dual half alone. */
 int slp_cp_many_bench(slp_cp_many *s, int64_t k, double ms[3]);
+/* Per-LP stopping, tested inside the iteration kernel; no counterpart in the reference (no stopping test, one LP per call).
+ * Iterations of an LP count from 1 over its whole life.  At the end of an iteration t with t % check_every == 0 the LP stops
+ * iff max(max_j |x2_j - x_j|, max_r |y_r+ - y_r|) <= tol: the differences of iteration t alone, y after the clamp, the maximum as
+ * np.max (a NaN never stops).  A stopped LP keeps its x, z, y after t iterations and takes no part in later launches.
+ * tol >= 0 and finite with check_every >= 1 arms the test, tol < 0 turns it off (the state after create: the launch is then the
+ * kernel without the test); anything else is an error.  To be called between whole iterations.  Every call clears all stopped
+ * flags and keeps the counters: an LP that meets the new tolerance stops again at its next check iteration.  Synchronises. */
+int slp_many_cp_set_stop(slp_cp_many *s, double tol, int64_t check_every);
+/* Per LP: iterations completed (for a stopped LP its stopping iteration), 1 = stopped, the last evaluated step (+inf before
+ * the first test).  count values each; any pointer may be NULL.  Synchronises. */
+int slp_many_cp_stop_state(slp_cp_many *s, int64_t *iterations, int32_t *stopped, double *step);
 
 /* ---- projected Gauss-Seidel: replaces gaussSiedel.pyx ------------------- *
  * boundedGaussSeidelClass.__init__ (gaussSiedel.pyx:87-92) and .solve

@@ -438,24 +438,41 @@ class CPBatchState:
         return ms
 
 
-def _cp_report_loop(state, costs, has_ineq, slots, best, all_x, spread, nb_max_iter, nb_iter_plot, callback_func, max_time, start):
+def _cp_report_loop(state, costs, has_ineq, slots, best, all_x, spread, nb_max_iter, nb_iter_plot, callback_func, max_time, start,
+                    stopped_now=None):
     """``_cp_loop`` for a batched or a list state: same cadence; the report's numbers are arrays with one entry per LP of the
     state, ``max_time`` stops them all.  ``costs[i]`` and ``has_ineq[i]`` belong to the state's LP ``i``; its best feasible iterate
     (:284-291 with force_integer=False) goes to ``best[slots[i]]``.  ``all_x`` and ``spread(values, energy=False)`` map the
     state's iterates and numbers to what the callback sees: the identity for a batch, the whole list (LPs without rows
-    included) for a list.  Returns ``all_x`` of the final iterates."""
+    included) for a list.  Returns ``all_x`` of the final iterates.
+
+    ``stopped_now()`` (a state with a per-LP stopping test; ``None``: none) is asked before every report which of the state's LPs
+    are stopped, a bool array: when all are, the loop ends there, without a report; else a stopped LP's five numbers repeat the
+    last row it had while it was running, and it is no candidate for ``best`` any more."""
     best_energy = np.full(len(slots), np.inf)
     niter = 0
+    last = None
     while niter < nb_max_iter:
         if niter % nb_iter_plot == 0:
+            stopped = None if stopped_now is None else stopped_now()
+            if stopped is not None and stopped.all():
+                break
             state.primal_step()
             elapsed = time.perf_counter() - start
             if (max_time is not None) and collective_elapsed(elapsed) > max_time:  # the same decision on every rank
                 break
-            energy1, energy2, max_violated_equality, max_violated_inequality, max_eq_at_x = state.report().T.copy()
+            numbers = state.report()
+            if stopped is not None:
+                if last is not None:
+                    numbers[stopped] = last[stopped]
+                last = numbers
+            energy1, energy2, max_violated_equality, max_violated_inequality, max_eq_at_x = numbers.T.copy()
             max_violated_inequality[~has_ineq] = 0  # the reference dereferences a_ineq here (:283) and fails
             x = None
-            feasible = np.nonzero((max_eq_at_x == 0) & (max_violated_inequality <= 0))[0]
+            feasible = (max_eq_at_x == 0) & (max_violated_inequality <= 0)
+            if stopped is not None:
+                feasible &= ~stopped
+            feasible = np.nonzero(feasible)[0]
             if feasible.size:
                 x = state.x()
                 for i in feasible:
@@ -648,6 +665,25 @@ class CPManyState(_many.ManyState):
         _lib.check(self._l.slp_cp_many_report(self._h, _lib.ptr(out)))
         return out
 
+    def set_stop(self, tol, check_every=1):
+        """Arms the per-LP stopping test of the iteration kernel (``slp_many_cp_set_stop``): at the end of every iteration ``t``
+        of an LP with ``t % check_every == 0`` -- counted from 1 over the LP's life -- the LP stops iff ``max(max|x_t - x_{t-1}|,
+        max|y_t - y_{t-1}|) <= tol``; a stopped LP keeps its iterate and takes no part in later calls.  ``tol=None`` turns the test
+        off, the state after the constructor.  Between whole iterations only.  Every call clears the stopped flags and keeps the
+        counters."""
+        if tol is None:
+            tol, check_every = -1.0, 1
+        else:
+            tol, check_every = _many.check_stop(tol, check_every)
+        _lib.check(self._l.slp_many_cp_set_stop(self._h, tol, check_every))
+
+    def stop_state(self):
+        """``(iterations, stopped, step)`` per LP, int64, bool and float64 arrays: the iterations completed (for a stopped LP its
+        stopping iteration), whether it is stopped and the last evaluated step (``+inf`` before the first test)."""
+        iterations, stopped, step = np.zeros(self.count, dtype=np.int64), np.zeros(self.count, dtype=np.int32), np.zeros(self.count)
+        _lib.check(self._l.slp_many_cp_stop_state(self._h, _lib.ptr(iterations), _lib.ptr(stopped), _lib.ptr(step)))
+        return iterations, stopped.astype(bool), step
+
     def x(self):
         return self._per_lp("x", self.n)
 
@@ -693,6 +729,13 @@ def chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=100
     ``chambolle_pock_ppd`` as ONE LP computes the same bits per block in two launches per iteration; which of the two is faster at
     a given count is what ``tools/bench_cp_many.py`` measures -- not measured yet.
     """
+    xs, best, _ = _cp_many_run(problems, x0, alpha, theta, nb_max_iter, callback_func, max_time, nb_iter_plot, None)
+    return xs, best
+
+
+def _cp_many_run(problems, x0, alpha, theta, nb_max_iter, callback_func, max_time, nb_iter_plot, stop):
+    """``chambolle_pock_ppd_many`` (``stop`` None) and ``chambolle_pock_ppd_many_until`` (``stop`` the checked ``(tol,
+    check_every)``): ``(xs, best_integer_solutions, info)``, ``info`` None without a stopping test."""
     start = time.perf_counter()
     count = _many.count_problems(problems)
     lps = [_many_problem(k, p) for k, p in enumerate(problems)]
@@ -700,8 +743,9 @@ def chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=100
     solved = [k for k in range(count) if lps[k][3] is not None or lps[k][5] is not None]
     xs = [None if (lps[k][3] is not None or lps[k][5] is not None) else box_vertex(*lps[k][:3]) for k in range(count)]
     best = [None] * count
+    info = None if stop is None else _many.new_stop_info(count, solved)
     if not solved:
-        return xs, best
+        return xs, best, info
     costs = [lps[k][0] for k in solved]
     has_ineq = np.array([lps[k][5] is not None for k in solved])
     state = CPManyState([lps[k] for k in solved], None if x0 is None else [x0[k] for k in solved], alpha, theta)
@@ -719,8 +763,49 @@ def chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=100
             out[k] = v
         return out
 
+    def stopped_now():
+        now = state.stop_state()
+        _many.spread_stop_state(info, solved, now)
+        return now[1]
+
     try:
-        xs = _cp_report_loop(state, costs, has_ineq, solved, best, all_x, spread, nb_max_iter, nb_iter_plot, callback_func, max_time, start)
+        if stop is not None:
+            state.set_stop(*stop)
+            if callback_func is not None:
+                try:
+                    callback_func.info = info
+                except AttributeError:   # a bound method takes no attribute: wrap it in a function to read ``info``
+                    pass
+        xs = _cp_report_loop(state, costs, has_ineq, solved, best, all_x, spread, nb_max_iter, nb_iter_plot, callback_func, max_time, start,
+                             None if stop is None else stopped_now)
+        if stop is not None:
+            stopped_now()
     finally:
         state.close()
-    return xs, best
+    return xs, best, info
+
+
+def chambolle_pock_ppd_many_until(problems, tol, check_every=10, x0=None, alpha=1, theta=1, nb_max_iter=10000, callback_func=None,
+                                  max_time=None, nb_iter_plot=10):
+    """``chambolle_pock_ppd_many`` with a stopping test per LP (extension; the reference has no stopping test): the list runs until
+    every LP has stopped, at most ``nb_max_iter`` iterations.  Returns ``(xs, best_integer_solutions, info)``.
+
+    The test is made inside the iteration kernel (``CPManyState.set_stop``), at the end of every iteration ``t`` of an LP with ``t %
+    check_every == 0``, iterations counted from 1: the LP stops iff ``max(max|x_t - x_{t-1}|, max|y_t - y_{t-1}|) <= tol``, where
+    ``x_t`` is the primal iterate and ``y_t`` the clamped dual iterate after ``t`` iterations; a NaN among the differences never
+    stops.  A stopped LP keeps its iterate after ``t`` iterations, bit for bit that of ``chambolle_pock_ppd(...,
+    nb_max_iter=t, order=ORDER_SEQUENTIAL)``, while the others go on.  ``tol`` is a finite float ``>= 0``, ``check_every`` an int
+    ``>= 1``: a ``ValueError`` before the library is loaded otherwise, like every shape error.
+
+    ``info`` is a dict of arrays over the whole list: ``iterations`` (int64: completed, for a stopped LP its stopping iteration),
+    ``stopped`` (bool) and ``step`` (float64: the last evaluated step, ``+inf`` before the first test).  An LP without rows is
+    stopped after 0 iterations with step 0.0.
+
+    The cadence of reports is that of ``chambolle_pock_ppd_many``.  The loop ends at the first report index at which every LP is
+    stopped (no callback for that index), at ``nb_max_iter``, or at ``max_time``.  In a callback a stopped LP's ``xs[k]`` is its
+    final iterate, and its five numbers repeat the last row it had while it was running.  ``info`` is current at every callback:
+    the same dict, updated in place, is set as the ATTRIBUTE ``callback_func.info`` before the first call (a function or any
+    object that takes attributes; a bound method takes none and has to be wrapped in a function to read it).
+    """
+    stop = _many.check_stop(tol, check_every)
+    return _cp_many_run(problems, x0, alpha, theta, nb_max_iter, callback_func, max_time, nb_iter_plot, stop)

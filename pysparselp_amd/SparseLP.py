@@ -24,7 +24,8 @@ import numpy as np
 import scipy.sparse
 
 from .ADMM import lp_admm, lp_admm_batch
-from .ChambollePockPPD import chambolle_pock_ppd, chambolle_pock_ppd_batch, chambolle_pock_ppd_many
+from .ChambollePockPPD import chambolle_pock_ppd, chambolle_pock_ppd_batch, chambolle_pock_ppd_many, chambolle_pock_ppd_many_until
+from ._many import check_stop
 from ._batch import check_costs, require_one_sided
 from ._lib import ORDER_AUTO
 
@@ -708,6 +709,17 @@ def solve_many(lps, method="chambolle_pock_ppd", get_timing=True, nb_iter=10000,
     if len(lps) < 1:
         raise ValueError("an empty list of LPs")
     start = time.perf_counter()
+    problems, expand = _many_reduced(lps)
+    sols, _ = chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=nb_iter, callback_func=_list_recorder(lps, expand),
+                                      max_time=max_time, nb_iter_plot=nb_iter_plot)
+    xs = [expand(k, sol) for k, sol in enumerate(sols)]
+    elapsed = time.perf_counter() - start
+    return (xs, elapsed) if get_timing else xs
+
+
+def _many_reduced(lps):
+    """The preparation of ``solve_many``: every LP's curves reset and its fixed variables removed on a copy.  Returns the
+    solver's 8-tuples and ``expand(k, sol)``, the solver's iterate of LP ``k`` over the LP's own variables."""
     problems, maps = [], []
     for lp in lps:
         _reset_curves(lp)
@@ -726,9 +738,40 @@ def solve_many(lps, method="chambolle_pock_ppd", get_timing=True, nb_iter=10000,
         full[free_ids] = sol
         return full - shift
 
-    sols, _ = chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=nb_iter, callback_func=_list_recorder(lps, expand),
-                                      max_time=max_time, nb_iter_plot=nb_iter_plot)
+    return problems, expand
+
+
+def solve_many_until(lps, tol, check_every=10, get_timing=True, nb_iter=10000, max_time=None, nb_iter_plot=10):
+    """``solve_many`` with a stopping test per LP (``ChambollePockPPD.chambolle_pock_ppd_many_until``): every LP of the list stops
+    on its own at the first iteration ``t`` with ``t % check_every == 0`` whose step ``max(max|x_t - x_{t-1}|, max|y_t -
+    y_{t-1}|)`` is at most ``tol``, the others go on, at most ``nb_iter`` iterations.  Returns the list of ``x``, or ``(xs,
+    elapsed)`` with ``get_timing``; ``tol`` a finite float ``>= 0`` and ``check_every`` an int ``>= 1``, a ``ValueError`` otherwise.
+
+    The LPs are prepared as ``solve_many`` prepares them.  Sets ``lp.nb_iterations`` (iterations completed; for a stopped LP its
+    stopping iteration) and ``lp.stopped`` on every LP.  A stopped LP records nothing after it has stopped, so for every LP,
+    stopped or not, ``xs[k]`` and every curve apart from the times are bit for bit those of ``lps[k].solve(method=
+    "chambolle_pock_ppd", nb_iter=lp.nb_iterations, order=ORDER_SEQUENTIAL, setup="host")`` (the energies to the rounding of
+    another fixed summation order, as for ``solve_many``).  ``max_time`` stops all LPs at a report.
+    """
+    check_stop(tol, check_every)
+    lps = list(lps)
+    if len(lps) < 1:
+        raise ValueError("an empty list of LPs")
+    start = time.perf_counter()
+    problems, expand = _many_reduced(lps)
+    skip = np.zeros(len(lps), dtype=bool)
+    fill = _list_recorder(lps, expand, skip=skip)
+
+    def record(*report):
+        skip[:] = record.info["stopped"]   # current at every callback: chambolle_pock_ppd_many_until sets the attribute
+        fill(*report)
+
+    sols, _, info = chambolle_pock_ppd_many_until(problems, tol, check_every, x0=None, alpha=1, theta=1, nb_max_iter=nb_iter,
+                                                  callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
     xs = [expand(k, sol) for k, sol in enumerate(sols)]
+    for k, lp in enumerate(lps):
+        lp.nb_iterations = int(info["iterations"][k])
+        lp.stopped = bool(info["stopped"][k])
     elapsed = time.perf_counter() - start
     return (xs, elapsed) if get_timing else xs
 

@@ -101,6 +101,8 @@ _SIGNATURES = {
     "slp_cp_many_form": (c_int, [c_vp, c_i64]),
     "slp_cp_many_lds_limit": (c_i64, []),
     "slp_cp_many_bench": (c_int, [c_vp, c_i64, c_vp]),
+    "slp_many_cp_set_stop": (c_int, [c_vp, c_dbl, c_i64]),
+    "slp_many_cp_stop_state": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "slp_gs_create": (c_vp, [c_i64, c_vp, c_vp, c_vp]),
     "slp_gs_destroy": (None, [c_vp]),
     "slp_gs_num_levels": (c_i64, [c_vp]),

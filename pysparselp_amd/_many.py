@@ -2,6 +2,8 @@
 ``lp_admm_many``, ``dual_gradient_ascent_many``) share on the host: the checks of one LP of the list, the stacking of the LPs'
 matrices and the common part of the device states.  Private; numpy only, and nothing here loads the library -- every refusal
 below is a ``ValueError`` raised before a caller touches the GPU.  What the batched forms use too is in ``_batch.py``."""
+import numbers
+
 import numpy as np
 
 from . import _lib
@@ -97,6 +99,33 @@ def stack_blocks(blocks, col_offsets=None):
         val.append(v)
         entries += int(p[-1])
     return concat(ptr, np.int64), concat(idx, np.int32), concat(val, np.float64)
+
+
+def check_stop(tol, check_every):
+    """The tolerance and the cadence of a per-LP stopping test as ``(float, int)``: ``tol`` a finite number ``>= 0``,
+    ``check_every`` an int ``>= 1`` (iterations between two tests)."""
+    if isinstance(tol, bool) or not isinstance(tol, numbers.Real) or not np.isfinite(tol) or tol < 0:
+        raise ValueError(f"tol must be a finite float >= 0, not {tol!r}")
+    if isinstance(check_every, bool) or not isinstance(check_every, numbers.Integral) or check_every < 1:
+        raise ValueError(f"check_every must be an int >= 1, not {check_every!r}")
+    return float(tol), int(check_every)
+
+
+def new_stop_info(count, solved):
+    """The stop state of a whole list before its first iteration, a dict of arrays over the ``count`` LPs: ``iterations`` (int64),
+    ``stopped`` (bool), ``step`` (float64, the last evaluated step).  The LPs outside ``solved`` take no part in the iterations:
+    they are stopped after 0 iterations with step 0.0; the others run, their step ``+inf`` until the first test."""
+    info = dict(iterations=np.zeros(count, dtype=np.int64), stopped=np.ones(count, dtype=bool), step=np.zeros(count))
+    info["stopped"][solved] = False
+    info["step"][solved] = np.inf
+    return info
+
+
+def spread_stop_state(info, solved, state):
+    """``state`` -- ``(iterations, stopped, step)`` of the LPs ``solved``, as a device state's ``stop_state()`` returns them --
+    written into ``info`` (``new_stop_info``) in place: whoever holds the dict sees the current values."""
+    for name, values in zip(("iterations", "stopped", "step"), state):
+        info[name][solved] = values
 
 
 class ManyState:

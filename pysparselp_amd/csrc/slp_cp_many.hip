@@ -26,7 +26,22 @@
 // Report, per LP, one workgroup of 256 lanes on the written-back state: lane t takes rows (columns) t, t + 256, ... in increasing
 // order -- per row the three chains K x, K x4, K z of one walk -- then block_reduce: a fixed order, a function of the shapes only.
 // The maxima are exact.  x4 is written by the primal half of a reporting iteration.
+//
+// Stopping (slp_many_cp_set_stop; off after create).  CpmCtl, one per LP in device memory: iterations completed, the stopped flag,
+// the stopping iteration and the last evaluated step.  Iterations of an LP count from 1 over its whole life; at the end of an
+// iteration t with t % check_every == 0 the LP stops iff step = max(max_j |x2_j - x_j|, max_r |y_r+ - y_r|) <= tol, the differences
+// those of iteration t alone (a lane holds both values of what it updates) and the maximum NaN-propagating as np.max: exact in any
+// order, so the decision is that of a CPU restatement.  The test is the template parameter STOP of k_cpm_iterate: STOP = false is
+// the kernel without it -- no extra barrier, no word of the control record read or written (the host counts the iterations).
+// With STOP a wave reduces its lanes' maxima by shuffles into one LDS slot per wave and half before the barrier that ends the
+// half; after the dual half's barrier lane 0 folds the slots, writes the record and ONE LDS slot with the decision, and one more
+// barrier later every lane reads that slot: the break is uniform, and so is every barrier.  A stopped LP's workgroup returns before
+// its first barrier (the flag was written by an earlier launch: the same for every lane) and its x, z, y are never written again;
+// in the launch in which it stops it leaves the loop and, in the lds form, writes its iterates back.  Between primal_step and
+// dual_step the reduced dx waits in the record.  The count of an LP is read from the record at the start of a launch, so the
+// stopping iteration does not depend on how a run is split into launches.
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <type_traits>
 
@@ -68,6 +83,32 @@ __global__ __launch_bounds__(kBlock) void k_cpm_localise(const CpmLp *__restrict
         }
 }
 
+// per LP, in device memory; written by lane 0 of the LP's workgroup (STOP) and by the host between launches
+struct CpmCtl {
+    i64 done;       // whole iterations completed
+    i64 stop_iter;  // `done` when it stopped
+    double step;    // the last evaluated step, +inf before the first test
+    double dx;      // the primal half's maximum of a check iteration, carried from primal_step to dual_step
+    i32 stopped, pad;
+};
+
+struct CpmStop {
+    CpmCtl *ctl;
+    double tol;
+    i64 check_every;
+};
+
+// max as np.max: a NaN on either side stays
+__device__ __forceinline__ double cpm_nanmax(double m, double d) { return (d > m || d != d) ? d : m; }
+
+__device__ __forceinline__ double cpm_wave_nanmax(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = cpm_nanmax(v, __shfl_down(v, off, kWave));
+    return v;
+}
+
+constexpr int kCpmWaves = kCpmMaxBlock / kWave;
+
 struct CpmArgs {
     const CpmLp *lps;
     const i32 *list;  // the LPs of this launch
@@ -78,14 +119,24 @@ struct CpmArgs {
     double one_plus_theta, theta;
 };
 
-// `iters` times the stages of one LP (bit 0 primal half, bit 1 dual half); store: the primal half also writes x4 (:260-261)
-template <bool LDS>
-__global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int iters, int stages, int store) {
+// `iters` times the stages of one LP (bit 0 primal half, bit 1 dual half); store: the primal half also writes x4 (:260-261).
+// STOP: the stopping test of the header comment; `sp` is not looked at without it.
+template <bool LDS, bool STOP>
+__global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int iters, int stages, int store, CpmStop sp) {
     extern __shared__ __attribute__((aligned(16))) double cpm_lds[];
+    __shared__ double cpm_red[STOP ? 2 * kCpmWaves + 1 : 1];  // per wave the maxima of the two halves, then the decision
     using LD = typename std::conditional<LDS, CpLoadPlain, CpLoadWorkgroup>::type;
     const LD ld;
-    const CpmLp lp = a.lps[a.list[blockIdx.x]];
+    const i32 id = a.list[blockIdx.x];
+    const CpmLp lp = a.lps[id];
     const i32 n = lp.n, m = lp.m_eq + lp.m_in, W = (i32)blockDim.x, tid = (i32)threadIdx.x;
+    i64 done = 0, until = 0;  // STOP: iterations completed; iterations up to and including the next check
+    if (STOP) {
+        const CpmCtl *ctl = sp.ctl + id;
+        if (ctl->stopped) return;  // set before the launch: the same for every lane
+        done = ctl->done;          // lane 0 writes the record only behind a barrier that follows this load
+        until = sp.check_every - done % sp.check_every;
+    }
     const bool has_eq = lp.m_eq > 0, has_in = lp.m_in > 0;
     double *xg = a.x + lp.col0, *zg = a.z + lp.col0, *yg = a.y + lp.y0;
     double *xs = xg, *zs = zg, *ys = yg;
@@ -100,7 +151,9 @@ __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int ite
     const double *c = a.c + lp.col0, *t = a.t + lp.col0, *lb = a.lb + lp.col0, *ub = a.ub + lp.col0;
     const i64 *tptr = a.tptr + lp.col0;
     for (int it = 0; it < iters; ++it) {
+        const bool check = STOP && until == 1;  // uniform: a function of the record and of `it`
         if (stages & 1) {
+            double dx = 0.0;
             for (i32 j = tid; j < n; j += W) {
                 double se, si;
                 cp_column_sums(tptr[j], tptr[j + 1], a.tidx, a.tval, ys, 1, lp.m_eq, ld, &se, &si);
@@ -111,18 +164,65 @@ __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int ite
                 zs[j] = zn;
                 xs[j] = x2;
                 if (store) a.x4[lp.col0 + j] = (d < 0.0) ? u : l;
+                if (STOP) dx = cpm_nanmax(dx, fabs(x2 - xo));
+            }
+            if (check) {
+                dx = cpm_wave_nanmax(dx);
+                if ((tid & (kWave - 1)) == 0) cpm_red[tid / kWave] = dx;
             }
             __syncthreads();  // same compute unit: the stores of this half are visible to the next one
         }
+        if (STOP && !(stages & 2)) {  // primal_step: the reduced dx waits in the record for dual_step
+            if (check && tid == 0) {
+                double dx = cpm_red[0];
+                for (i32 w = 1; w < W / kWave; ++w) dx = cpm_nanmax(dx, cpm_red[w]);
+                sp.ctl[id].dx = dx;
+            }
+            continue;
+        }
         if (stages & 2) {
+            double dy = 0.0;
             for (i32 r = tid; r < m; r += W) {
                 const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
                 const double kz = cp_row_sum(a.ptr[g], a.ptr[g + 1], a.idx, a.val, zs, 1, ld);
-                ys[r] = cp_dual_point(kz, a.b[g], ld(ys + r), a.sigma[g], r >= lp.m_eq);
+                const double yo = ld(ys + r), yn = cp_dual_point(kz, a.b[g], yo, a.sigma[g], r >= lp.m_eq);
+                ys[r] = yn;
+                if (STOP) dy = cpm_nanmax(dy, fabs(yn - yo));
+            }
+            if (check) {
+                dy = cpm_wave_nanmax(dy);
+                if ((tid & (kWave - 1)) == 0) cpm_red[kCpmWaves + tid / kWave] = dy;
             }
             __syncthreads();
         }
+        if (STOP) {  // here an iteration is complete
+            ++done;
+            if (!check) {
+                --until;
+                continue;
+            }
+            until = sp.check_every;
+            if (tid == 0) {
+                CpmCtl *ctl = sp.ctl + id;
+                double dx = (stages & 1) ? cpm_red[0] : ctl->dx, dy = cpm_red[kCpmWaves];
+                for (i32 w = 1; w < W / kWave; ++w) {
+                    if (stages & 1) dx = cpm_nanmax(dx, cpm_red[w]);
+                    dy = cpm_nanmax(dy, cpm_red[kCpmWaves + w]);
+                }
+                const double step = cpm_nanmax(dx, dy);
+                const bool stop = step <= sp.tol;  // false for a NaN
+                ctl->step = step;
+                if (stop) {
+                    ctl->stopped = 1;
+                    ctl->stop_iter = done;
+                }
+                cpm_red[2 * kCpmWaves] = stop ? 1.0 : 0.0;
+            }
+            __syncthreads();  // the one barrier the test adds, in a check iteration only
+            if (cpm_red[2 * kCpmWaves] != 0.0) break;  // one slot, read by every lane: uniform
+        }
     }
+    if (STOP && (stages & 2) && tid == 0) sp.ctl[id].done = done;
     if (LDS) {
         for (i32 j = tid; j < n; j += W) { xg[j] = xs[j]; zg[j] = zs[j]; }
         for (i32 r = tid; r < m; r += W) yg[r] = ys[r];
@@ -189,6 +289,11 @@ struct slp_cp_many {
     DevBuf<i32> list[2];
     DevBuf<CpmLp> table;
     DevBuf<double> b, c, lb, ub, t, sigma, x, z, y, x4, out;
+    // stopping: off while tol < 0.  The kernel without the test touches no record, so the whole iterations run while it is off
+    // are counted here and added to every record when the test is armed (and when the state is read)
+    DevBuf<CpmCtl> ctl;
+    double tol = -1.0;
+    i64 check_every = 1, uncounted = 0;
     ~slp_cp_many() { delete k; }
 };
 
@@ -209,22 +314,38 @@ static CpmArgs cpm_args(const slp_cp_many *s, int g) {
     return r;
 }
 
-// `k` times the stages, in launches of at most kmax iterations per form
-static void cpm_run(slp_cp_many *s, i64 k, int stages, bool store) {
-    hipStream_t st = ctx().stream;
+template <bool LDS>
+static void cpm_launch(const slp_cp_many *s, const ManyGroup &gr, const CpmArgs &a, int it, int stages, bool store, bool stop) {
+    const CpmStop sp = {s->ctl.p, s->tol, s->check_every};
+    const dim3 grid((unsigned)gr.ids.size()), block(gr.block);
+    const size_t lds = LDS ? gr.lds_bytes : 0;
+    if (stop) hipLaunchKernelGGL((k_cpm_iterate<LDS, true>), grid, block, lds, ctx().stream, a, it, stages, (int)store, sp);
+    else hipLaunchKernelGGL((k_cpm_iterate<LDS, false>), grid, block, lds, ctx().stream, a, it, stages, (int)store, sp);
+}
+
+// `k` times the stages, in launches of at most kmax iterations per form; with the stopping test when it is armed, unless
+// `plain` (the half-iteration timings of slp_cp_many_bench, which are no iterations)
+static void cpm_run(slp_cp_many *s, i64 k, int stages, bool store, bool plain = false) {
+    const bool stop = s->tol >= 0.0 && !plain;
+    if (!stop && !plain && (stages & 2)) s->uncounted += k;
     for (int g = 0; g < 2; ++g) {
         const ManyGroup &gr = s->group[g];
         if (gr.ids.empty()) continue;
         const CpmArgs a = cpm_args(s, g);
         many_split(k, gr.kmax, [&](int it) {
-            if (g == 0)
-                hipLaunchKernelGGL((k_cpm_iterate<true>), dim3((unsigned)gr.ids.size()), dim3(gr.block), gr.lds_bytes, st, a, it, stages,
-                                   (int)store);
-            else
-                hipLaunchKernelGGL((k_cpm_iterate<false>), dim3((unsigned)gr.ids.size()), dim3(gr.block), 0, st, a, it, stages, (int)store);
+            if (g == 0) cpm_launch<true>(s, gr, a, it, stages, store, stop);
+            else cpm_launch<false>(s, gr, a, it, stages, store, stop);
             return it;
         });
     }
+}
+
+// the records with the iterations of the unarmed launches added; synchronises
+static std::vector<CpmCtl> cpm_read_ctl(slp_cp_many *s) {
+    std::vector<CpmCtl> h((size_t)s->count);
+    s->ctl.download(h.data(), h.size());
+    for (CpmCtl &c : h) c.done += s->uncounted;  // no LP is stopped while the test is off
+    return h;
 }
 
 // form per LP, workgroup, LDS and launch cap per form -- from the shapes (and the two environment switches) only
@@ -301,7 +422,7 @@ slp_cp_many *slp_cp_many_create(int64_t count, const int64_t *n, const int64_t *
         // three over the rows (y, b, Sigma), the table, the lists and the report
         many_require_memory("slp_cp_many_create", count,
                             40.0 * (double)nnz + 16.0 * (double)(N + M + 2) + 8.0 * (7.0 * (double)N + 3.0 * (double)M) +
-                                (double)count * (double)(sizeof(CpmLp) + sizeof(i32) + 5 * sizeof(double)));
+                                (double)count * (double)(sizeof(CpmLp) + sizeof(CpmCtl) + sizeof(i32) + 5 * sizeof(double)));
         s->k = slp_matrix_create(M, N, indptr, indices, data);
         if (!s->k) throw Error(slp_last_error());
         require_csr(s->k, "slp_cp_many_create");
@@ -314,7 +435,8 @@ slp_cp_many *slp_cp_many_create(int64_t count, const int64_t *n, const int64_t *
                            s->k->at.ptr.p, s->k->at.idx.p, Me);
         SLP_HIP(hipGetLastError());
         many_upload_lists(s->group, s->list);
-        many_lds_opt_in(reinterpret_cast<const void *>(k_cpm_iterate<true>), s->group[0].lds_bytes, kCpmLdsLimit * sizeof(double));
+        many_lds_opt_in(reinterpret_cast<const void *>(k_cpm_iterate<true, false>), s->group[0].lds_bytes, kCpmLdsLimit * sizeof(double));
+        many_lds_opt_in(reinterpret_cast<const void *>(k_cpm_iterate<true, true>), s->group[0].lds_bytes, kCpmLdsLimit * sizeof(double));
         s->c.upload(c, (size_t)N);
         s->lb.upload(lb, (size_t)N);
         s->ub.upload(ub, (size_t)N);
@@ -328,6 +450,8 @@ slp_cp_many *slp_cp_many_create(int64_t count, const int64_t *n, const int64_t *
         s->x4.alloc((size_t)N);
         s->x4.zero();
         s->out.alloc((size_t)5 * (size_t)count);
+        std::vector<CpmCtl> ctl((size_t)count, CpmCtl{0, 0, __builtin_inf(), 0.0, 0, 0});
+        s->ctl.upload(ctl.data(), ctl.size());
         SLP_HIP(hipStreamSynchronize(ctx().stream));
         return s.release();
     })
@@ -352,6 +476,32 @@ int slp_cp_many_report(slp_cp_many *s, double *out) {
         hipLaunchKernelGGL(k_cpm_report, dim3((unsigned)s->count), dim3(kBlock), 0, ctx().stream, cpm_args(s, 0), s->out.p);
         SLP_HIP(hipGetLastError());
         s->out.download(out, (size_t)5 * (size_t)s->count);
+    })
+}
+
+int slp_many_cp_set_stop(slp_cp_many *s, double tol, int64_t check_every) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_cp_set_stop: NULL handle");
+        SLP_REQUIRE(tol < 0.0 || (std::isfinite(tol) && check_every >= 1),
+                    "slp_many_cp_set_stop: tol must be finite and >= 0 with check_every >= 1 (tol < 0 turns the test off)");
+        std::vector<CpmCtl> h = cpm_read_ctl(s);
+        for (CpmCtl &c : h) c.stopped = 0;
+        s->ctl.upload(h.data(), h.size());
+        s->uncounted = 0;
+        s->tol = tol < 0.0 ? -1.0 : tol;
+        if (tol >= 0.0) s->check_every = check_every;
+    })
+}
+
+int slp_many_cp_stop_state(slp_cp_many *s, int64_t *iterations, int32_t *stopped, double *step) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_cp_stop_state: NULL handle");
+        const std::vector<CpmCtl> h = cpm_read_ctl(s);
+        for (size_t k = 0; k < h.size(); ++k) {
+            if (iterations) iterations[k] = h[k].stopped ? h[k].stop_iter : h[k].done;
+            if (stopped) stopped[k] = h[k].stopped;
+            if (step) step[k] = h[k].step;
+        }
     })
 }
 
@@ -384,7 +534,7 @@ int slp_cp_many_bench(slp_cp_many *s, int64_t k, double ms[3]) {
         for (int q = 0; q < 3; ++q) {
             float f = 0.f;
             SLP_HIP(hipEventRecord(c.ev0, c.stream));
-            cpm_run(s, k, stages[q], false);
+            cpm_run(s, k, stages[q], false, q > 0);
             SLP_HIP(hipEventRecord(c.ev1, c.stream));
             SLP_HIP(hipEventSynchronize(c.ev1));
             SLP_HIP(hipEventElapsedTime(&f, c.ev0, c.ev1));
