@@ -469,6 +469,21 @@ int64_t slp_admm_many_lds_limit(void);
 int64_t slp_admm_many_kmax(const slp_admm_many *s, int form);
 /* As slp_admm_bench: average GPU milliseconds per iteration of the whole list (:143-268 for all LPs) over k, by HIP events. */
 int slp_admm_many_bench(slp_admm_many *s, int64_t k, double *ms);
+/* Per-LP stopping, tested inside the iteration kernel; no counterpart in the reference (no stopping test, one LP per call).
+ * Iterations of an LP count from 1 over its whole life: iteration t is the right-hand side, the sweep (x_t) and the multiplier
+ * update (lambda_t).  At the end of an iteration t with t % check_every == 0 the LP stops iff
+ *   max_i |(A x_t)_i - b_i| <= tol_residual   (the m rows of its standard form, the value the multiplier update forms; 0 for m = 0)
+ *   max_j |x_t,j - x_{t-1},j| <= tol_step     (all N = n + m_ineq columns, slacks included; x_0 is the stored start)
+ * both maxima as np.max (a NaN never stops).  A stopped LP keeps its x, lambda after t iterations and takes no part in later
+ * launches.  tol_residual >= 0 and tol_step >= 0, both finite, with check_every >= 1 arm the test; tol_residual < 0 turns it off
+ * (the state after create: the launch is then the kernel without the test; the other two arguments are not looked at); anything
+ * else is an error.  Between whole iterations only: an error between slp_admm_many_sweep_step and _multiplier_step.  Every call
+ * clears all stopped flags and keeps the counters: an LP that meets the new tolerances stops again at its next check iteration.
+ * Synchronises. */
+int slp_many_admm_set_stop(slp_admm_many *s, double tol_residual, double tol_step, int64_t check_every);
+/* Per LP: iterations completed (for a stopped LP its stopping iteration), 1 = stopped, the last evaluated residual and step
+ * (+inf before the first test).  count values each; any pointer may be NULL.  Synchronises. */
+int slp_many_admm_stop_state(slp_admm_many *s, int64_t *iterations, int32_t *stopped, double *residual, double *step);
 
 /* ---- ADMM, matrix-free conjugate-gradient x-step ------------------------- *
  * The reference's own alternative x-step (ADMM.py:182-201 with

@@ -497,6 +497,29 @@ class ADMMManyState(_many.ManyState):
         _lib.check(self._l.slp_admm_many_report(self._h, _lib.ptr(out)))
         return out
 
+    def set_stop(self, tol_residual, tol_step, check_every=1):
+        """Arms the per-LP stopping test of the iteration kernel (``slp_many_admm_set_stop``): at the end of every iteration ``t``
+        of an LP with ``t % check_every == 0`` -- counted from 1 over the LP's life; an iteration is the right-hand side, the sweep
+        and the multiplier update -- the LP stops iff ``max|A x_t - b| <= tol_residual`` (the rows of its standard form) and
+        ``max|x_t - x_{t-1}| <= tol_step`` (all ``N`` columns, slacks included); a stopped LP keeps its iterate and takes no part in
+        later calls.  ``tol_residual=None`` turns the test off, the state after the constructor.  Between whole iterations only
+        (not between ``sweep_step`` and ``multiplier_step``).  Every call clears the stopped flags and keeps the counters."""
+        if tol_residual is None:
+            tol_residual, tol_step, check_every = -1.0, 0.0, 1
+        else:
+            tol_residual, check_every = _many.check_stop(tol_residual, check_every, "tol_residual")
+            tol_step, _ = _many.check_stop(tol_step, check_every, "tol_step")
+        _lib.check(self._l.slp_many_admm_set_stop(self._h, tol_residual, tol_step, check_every))
+
+    def stop_state(self):
+        """``(iterations, stopped, residual, step)`` per LP, int64, bool and two float64 arrays: the iterations completed (for a
+        stopped LP its stopping iteration), whether it is stopped and the last evaluated residual and step (``+inf`` before the
+        first test)."""
+        iterations, stopped = np.zeros(self.count, dtype=np.int64), np.zeros(self.count, dtype=np.int32)
+        residual, step = np.zeros(self.count), np.zeros(self.count)
+        _lib.check(self._l.slp_many_admm_stop_state(self._h, _lib.ptr(iterations), _lib.ptr(stopped), _lib.ptr(residual), _lib.ptr(step)))
+        return iterations, stopped.astype(bool), residual, step
+
     def x(self, full=False):
         """Per LP the first ``n_k`` entries of its iterate, or with ``full`` all ``N_k`` of its standard form."""
         return self._per_lp("x", self.N if full else self.n, int(bool(full)))
@@ -548,15 +571,39 @@ def lp_admm_many(
     Under a communicator every rank solves the whole list (a replica).  For LPs that share one matrix ``lp_admm_batch`` builds
     ``M`` and its plan once for all of them.
     """
-    _many.count_problems(problems)
+    xs, _ = _admm_many_run(problems, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time, use_preconditioning, nb_iter_plot, None)
+    return xs
+
+
+def _admm_many_run(problems, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time, use_preconditioning, nb_iter_plot, stop):
+    """``lp_admm_many`` (``stop`` None) and ``lp_admm_many_until`` (``stop`` the checked ``(tol_residual, tol_step,
+    check_every)``): ``(xs, info)``, ``info`` None without a stopping test."""
+    count = _many.count_problems(problems)
     lps = [_admm_many_problem(k, p) for k, p in enumerate(problems)]
     x0 = _admm_many_starts(x0, lps)
+    solved = np.arange(count)  # every LP has an inequality block: all take part
+    info = None if stop is None else _many.new_stop_info(count, solved, residual=True)
     state = ADMMManyState(lps, x0, gamma_eq, gamma_ineq, use_preconditioning)
+
+    def stopped_now():
+        now = state.stop_state()
+        _many.spread_stop_state(info, solved, now)
+        return now[1]
+
     try:
+        if stop is not None:
+            state.set_stop(*stop)
+            if callback_func is not None:
+                try:
+                    callback_func.info = info
+                except AttributeError:   # a bound method takes no attribute: wrap it in a function to read ``info``
+                    pass
         start = time.perf_counter()
         i = 0
         while i <= nb_iter:  # ADMM.py:143: nb_iter + 1 sweeps
             if i % nb_iter_plot == 0:
+                if stop is not None and stopped_now().all():
+                    break
                 state.sweep_step()
                 elapsed = time.perf_counter() - start
                 if max_time is not None and elapsed > max_time:
@@ -570,9 +617,53 @@ def lp_admm_many(
                 k = min(nb_iter_plot - i % nb_iter_plot, nb_iter + 1 - i)
                 state.iterate(k)
                 i += k
-        return state.x()
+        if stop is not None:
+            stopped_now()
+        return state.x(), info
     finally:
         state.close()
+
+
+def lp_admm_many_until(
+    problems,
+    tol_residual,
+    tol_step,
+    check_every=10,
+    x0=None,
+    gamma_eq=2,
+    gamma_ineq=3,
+    nb_iter=10000,
+    callback_func=None,
+    max_time=None,
+    use_preconditioning=True,
+    nb_iter_plot=10,
+):
+    """``lp_admm_many`` with a stopping test per LP (extension; the reference has no stopping test): the list runs until every LP
+    has stopped, at most ``nb_iter + 1`` sweeps.  Returns ``(xs, info)``.
+
+    The test is made inside the iteration kernel (``ADMMManyState.set_stop``), at the end of every iteration ``t`` of an LP with
+    ``t % check_every == 0``, iterations counted from 1 (an iteration is the right-hand side, the sweep that gives ``x_t`` and the
+    multiplier update that gives ``lambda_t``): the LP stops iff ``max|A x_t - b| <= tol_residual``, over the rows of its standard
+    form and with the very residual the multiplier update forms, and ``max|x_t - x_{t-1}| <= tol_step``, over all ``n + m_ineq``
+    columns of the standard form; a NaN in either never stops.  A stopped LP keeps ``x_t`` and ``lambda_t``, bit for bit those of
+    ``lp_admm(..., nb_iter=t - 1, order=ORDER_SEQUENTIAL)``, while the others go on.  ``tol_residual`` and ``tol_step`` are
+    finite floats ``>= 0``, ``check_every`` an int ``>= 1``: a ``ValueError`` that names the argument, before the library is
+    loaded, otherwise, like every shape error.
+
+    ``info`` is a dict of arrays over the list: ``iterations`` (int64: completed, for a stopped LP its stopping iteration),
+    ``stopped`` (bool), ``residual`` and ``step`` (float64: the last evaluated ones, ``+inf`` before the first test).
+
+    The loop and the cadence of reports are those of ``lp_admm_many``: a report at index ``i`` lies between sweep ``i + 1`` and its
+    multiplier update.  The loop ends at the first report index at which every LP is stopped (no callback for that index), at
+    ``nb_iter``, or at ``max_time``.  In a callback a stopped LP's ``xs[k]`` is its final iterate and its three numbers are the
+    report on that frozen state, so its ``max_violated_equality`` equals ``info["residual"][k]`` exactly.  ``info`` is current at
+    every callback: the same dict, updated in place, is set as the ATTRIBUTE ``callback_func.info`` before the first call (a
+    function or any object that takes attributes; a bound method takes none and has to be wrapped in a function to read it).
+    """
+    tol_residual, check_every = _many.check_stop(tol_residual, check_every, "tol_residual")
+    tol_step, _ = _many.check_stop(tol_step, check_every, "tol_step")
+    return _admm_many_run(problems, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time, use_preconditioning, nb_iter_plot,
+                          (tol_residual, tol_step, check_every))
 
 
 def lp_admm2(

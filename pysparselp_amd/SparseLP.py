@@ -821,12 +821,55 @@ def solve_admm_many(lps, get_timing=True, nb_iter=10000, max_time=None, nb_iter_
     if len(lps) < 1:
         raise ValueError("an empty list of LPs")
     start = time.perf_counter()
+    problems = _admm_many_prepared(lps)
+    xs = lp_admm_many(problems, nb_iter=nb_iter, callback_func=_list_recorder(lps), max_time=max_time, nb_iter_plot=nb_iter_plot)
+    elapsed = time.perf_counter() - start
+    return (xs, elapsed) if get_timing else xs
+
+
+def _admm_many_prepared(lps):
+    """The preparation of ``solve_admm_many``: every LP's curves reset; returns the solver's 8-tuples."""
     problems = []
     for lp in lps:
         _reset_curves(lp)
         a_ineq = lp.a_inequalities if (lp.a_inequalities is not None and lp.a_inequalities.shape[0] > 0) else None
         a_eq, b_eq = (lp.a_equalities, lp.b_equalities) if lp.a_equalities.shape[0] > 0 else (None, None)
         problems.append((lp.costsvector, a_eq, b_eq, a_ineq, lp.b_lower, lp.b_upper, lp.lower_bounds, lp.upper_bounds))
-    xs = lp_admm_many(problems, nb_iter=nb_iter, callback_func=_list_recorder(lps), max_time=max_time, nb_iter_plot=nb_iter_plot)
+    return problems
+
+
+def solve_admm_many_until(lps, tol_residual, tol_step, check_every=10, get_timing=True, nb_iter=10000, max_time=None, nb_iter_plot=10):
+    """``solve_admm_many`` with a stopping test per LP (``ADMM.lp_admm_many_until``): every LP of the list stops on its own at the
+    first iteration ``t`` with ``t % check_every == 0`` at which ``max|A x_t - b| <= tol_residual`` (the rows of its standard form)
+    and ``max|x_t - x_{t-1}| <= tol_step`` (all columns of it), the others go on, at most ``nb_iter + 1`` iterations.  Returns the
+    list of ``x``, or ``(xs, elapsed)`` with ``get_timing``; both tolerances finite floats ``>= 0`` and ``check_every`` an int
+    ``>= 1``, a ``ValueError`` otherwise.
+
+    The LPs are prepared as ``solve_admm_many`` prepares them.  Sets ``lp.nb_iterations`` (iterations completed; for a stopped LP
+    its stopping iteration) and ``lp.stopped`` on every LP.  A stopped LP records nothing after it has stopped, so ``xs[k]`` and
+    every curve apart from the times are those of ``lps[k].solve(method="admm", nb_iter=lp.nb_iterations - 1,
+    order=ORDER_SEQUENTIAL, setup="host")``: ``x`` and the violation curves bit for bit, the energies to the rounding of another
+    fixed summation order, as for ``solve_admm_many``.  ``max_time`` stops all LPs at a report."""
+    from .ADMM import lp_admm_many_until
+
+    tol_residual, check_every = check_stop(tol_residual, check_every, "tol_residual")
+    tol_step, _ = check_stop(tol_step, check_every, "tol_step")
+    lps = list(lps)
+    if len(lps) < 1:
+        raise ValueError("an empty list of LPs")
+    start = time.perf_counter()
+    problems = _admm_many_prepared(lps)
+    skip = np.zeros(len(lps), dtype=bool)
+    fill = _list_recorder(lps, skip=skip)
+
+    def record(*report):
+        skip[:] = record.info["stopped"]   # current at every callback: lp_admm_many_until sets the attribute
+        fill(*report)
+
+    xs, info = lp_admm_many_until(problems, tol_residual, tol_step, check_every, nb_iter=nb_iter, callback_func=record, max_time=max_time,
+                                  nb_iter_plot=nb_iter_plot)
+    for k, lp in enumerate(lps):
+        lp.nb_iterations = int(info["iterations"][k])
+        lp.stopped = bool(info["stopped"][k])
     elapsed = time.perf_counter() - start
     return (xs, elapsed) if get_timing else xs

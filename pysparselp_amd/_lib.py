@@ -151,6 +151,8 @@ _SIGNATURES = {
     "slp_admm_many_lds_limit": (c_i64, []),
     "slp_admm_many_kmax": (c_i64, [c_vp, c_int]),
     "slp_admm_many_bench": (c_int, [c_vp, c_i64, c_vp]),
+    "slp_many_admm_set_stop": (c_int, [c_vp, c_dbl, c_dbl, c_i64]),
+    "slp_many_admm_stop_state": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     "slp_admm_cg_create": (c_vp, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),
     "slp_admm_cg_create_on": (c_vp, [c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),
     "slp_admm_cg_create_on_mixed": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),

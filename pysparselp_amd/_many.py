@@ -101,30 +101,37 @@ def stack_blocks(blocks, col_offsets=None):
     return concat(ptr, np.int64), concat(idx, np.int32), concat(val, np.float64)
 
 
-def check_stop(tol, check_every):
+def check_stop(tol, check_every, name="tol"):
     """The tolerance and the cadence of a per-LP stopping test as ``(float, int)``: ``tol`` a finite number ``>= 0``,
-    ``check_every`` an int ``>= 1`` (iterations between two tests)."""
+    ``check_every`` an int ``>= 1`` (iterations between two tests).  ``name``: what a refusal calls the tolerance, for a test that
+    has more than one."""
     if isinstance(tol, bool) or not isinstance(tol, numbers.Real) or not np.isfinite(tol) or tol < 0:
-        raise ValueError(f"tol must be a finite float >= 0, not {tol!r}")
+        raise ValueError(f"{name} must be a finite float >= 0, not {tol!r}")
     if isinstance(check_every, bool) or not isinstance(check_every, numbers.Integral) or check_every < 1:
         raise ValueError(f"check_every must be an int >= 1, not {check_every!r}")
     return float(tol), int(check_every)
 
 
-def new_stop_info(count, solved):
+def new_stop_info(count, solved, residual=False):
     """The stop state of a whole list before its first iteration, a dict of arrays over the ``count`` LPs: ``iterations`` (int64),
-    ``stopped`` (bool), ``step`` (float64, the last evaluated step).  The LPs outside ``solved`` take no part in the iterations:
-    they are stopped after 0 iterations with step 0.0; the others run, their step ``+inf`` until the first test."""
+    ``stopped`` (bool), ``step`` (float64, the last evaluated step) and, with ``residual`` (a test on two quantities), ``residual``
+    (float64, the last evaluated residual).  The LPs outside ``solved`` take no part in the iterations: they are stopped after 0
+    iterations with step (and residual) 0.0; the others run, their step ``+inf`` until the first test."""
     info = dict(iterations=np.zeros(count, dtype=np.int64), stopped=np.ones(count, dtype=bool), step=np.zeros(count))
+    if residual:
+        info["residual"] = np.zeros(count)
     info["stopped"][solved] = False
-    info["step"][solved] = np.inf
+    for name in ("step", "residual")[:2 if residual else 1]:
+        info[name][solved] = np.inf
     return info
 
 
 def spread_stop_state(info, solved, state):
-    """``state`` -- ``(iterations, stopped, step)`` of the LPs ``solved``, as a device state's ``stop_state()`` returns them --
-    written into ``info`` (``new_stop_info``) in place: whoever holds the dict sees the current values."""
-    for name, values in zip(("iterations", "stopped", "step"), state):
+    """``state`` -- ``(iterations, stopped, step)`` of the LPs ``solved``, as a device state's ``stop_state()`` returns them, or
+    ``(iterations, stopped, residual, step)`` of a state that tests two quantities -- written into ``info`` (``new_stop_info``) in
+    place: whoever holds the dict sees the current values."""
+    names = ("iterations", "stopped", "step") if len(state) == 3 else ("iterations", "stopped", "residual", "step")
+    for name, values in zip(names, state):
         info[name][solved] = values
 
 

@@ -74,4 +74,15 @@ __device__ __forceinline__ double admm_mult_one(i64 s, i64 e, const i32 *__restr
     return ld(li) + gamma_eq * (ax - *bi);
 }
 
+// admm_mult_one that also hands out the residual (A x)_i - b_i it forms, for a caller that tests it (the stopping test of
+// slp_admm_many.hip): one walk, the same expressions, so lambda_i keeps its bits
+template <int STRIDE, class LD>
+__device__ __forceinline__ double admm_mult_res_one(i64 s, i64 e, const i32 *__restrict__ aidx, const double *__restrict__ aval, const double *x,
+                                                    const double *li, const double *bi, double gamma_eq, LD ld, double *res) {
+    const double ax = admm_dot<STRIDE>(s, e, aidx, aval, x, ld);
+    const double r = ax - *bi;
+    *res = r;
+    return ld(li) + gamma_eq * r;
+}
+
 }  // namespace slp

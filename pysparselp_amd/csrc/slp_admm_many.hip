@@ -39,7 +39,27 @@
 //
 // Report (:213-248), per LP, one workgroup of 256 lanes on the written-back state: lane t takes rows (columns) t, t + 256, ...
 // in increasing order, then block_reduce: a fixed order, a function of the shapes only.  The maxima are exact.
+//
+// Stopping (slp_many_admm_set_stop; off after create).  AdmmmCtl, one per LP in device memory: iterations completed, the stopped
+// flag, the stopping iteration, the last evaluated residual and step, and the reduced step of a sweep whose multiplier update has
+// not run yet.  Iterations of an LP count from 1 over its whole life; at the end of an iteration t with t % check_every == 0 the
+// LP stops iff  residual_t = max_i |(A x_t)_i - b_i| <= tol_residual  and  step_t = max_j |x_t,j - x_{t-1},j| <= tol_step: the
+// residual is the value the multiplier update forms (admm_mult_res_one; bit for bit column 1 of the report after t iterations),
+// the old x_j is the value the sweep loads, and both maxima are NaN-propagating as np.max -- exact in any order, so the decision
+// is that of a CPU restatement.  The test is the template parameter STOP of k_admmm_iterate: STOP = false is the kernel without
+// it -- no extra barrier, no extra LDS, no word of the control record read or written (the host counts the iterations).  With
+// STOP only a check iteration accumulates anything, in loops of its own: a lane its fabs over its rows of all levels and of the
+// multiplier pass, then a wave reduces by shuffles into one LDS slot per wave and quantity; after the multiplier pass's barrier
+// lane 0 folds the slots, writes the record and ONE LDS slot with the decision, and one more barrier later every lane reads that
+// slot: the break is uniform, and so is every barrier.  The sweep's slots are written behind the last level's barrier and read
+// behind the multiplier pass's; a sweep-only launch (sweep_step) has no such barrier and adds one, in a check iteration only,
+// before lane 0 writes the reduced step into the record, where it waits for multiplier_step.  A stopped LP's workgroup returns
+// before its first barrier (the flag was written by an earlier launch: the same for every lane) and its x, lambda are never
+// written again; in the launch in which it stops it leaves the loop and, in the lds form, writes them back.  The count of an LP
+// is read from the record at the start of a launch, so the stopping iteration does not depend on how a run is split into calls
+// and launches.
 #include <algorithm>
+#include <cmath>
 #include <memory>
 #include <type_traits>
 #include <utility>
@@ -149,14 +169,46 @@ struct AdmmmArgs {
     double gamma_eq, gamma_ineq;
 };
 
-// `iters` times the stages of one LP (bit 0 right-hand side + sweep, bit 1 multiplier); first: xp = xp0 in the first right-hand side
-template <bool LDS>
-__global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, int iters, int first, int stages) {
+// per LP, in device memory; written by lane 0 of the LP's workgroup (STOP) and by the host between launches
+struct AdmmmCtl {
+    i64 done;         // whole iterations completed
+    i64 stop_iter;    // `done` when it stopped
+    double residual;  // the last evaluated max |A x - b|, +inf before the first test
+    double step;      // the last evaluated max |x_t - x_{t-1}|, +inf before the first test
+    double dx;        // the sweep's maximum of a check iteration, carried from sweep_step to multiplier_step
+    i32 stopped, pad;
+};
+
+struct AdmmmStop {
+    AdmmmCtl *ctl;
+    double tol_residual, tol_step;
+    i64 check_every;
+};
+
+constexpr int kAdmmmWaves = kAdmmmMaxBlock / kWave;
+// per wave the maxima of the sweep and of the multiplier pass, then the decision
+constexpr int kAdmmmRed = 2 * kAdmmmWaves + 1;
+static_assert(kAdmmmRed * sizeof(double) + kAdmmmLdsLimit * sizeof(double) <= 160 * 1024,
+              "the slots of the stopping test and the iterates of the lds form share the compute unit's 160 KiB");
+
+// `iters` times the stages of one LP (bit 0 right-hand side + sweep, bit 1 multiplier); first: xp = xp0 in the first right-hand side.
+// STOP: the stopping test of the header comment; `sp` is not looked at without it.
+template <bool LDS, bool STOP>
+__global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, int iters, int first, int stages, AdmmmStop sp) {
     extern __shared__ __attribute__((aligned(16))) double admmm_lds[];
+    __shared__ double admmm_red[STOP ? kAdmmmRed : 1];  // unused without STOP: the compiler drops it
     using LD = typename std::conditional<LDS, AdmmLoadPlain, AdmmLoadWorkgroup>::type;
     const LD ld;
-    const AdmmmLp lp = a.lps[a.list[blockIdx.x]];
+    const i32 id = a.list[blockIdx.x];
+    const AdmmmLp lp = a.lps[id];
     const i32 N = lp.n + lp.m_in, m = lp.m_eq + lp.m_in, W = (i32)blockDim.x, tid = (i32)threadIdx.x;
+    i64 done = 0, until = 0;  // STOP: iterations completed; iterations up to and including the next check
+    if (STOP) {
+        const AdmmmCtl *ctl = sp.ctl + id;
+        if (ctl->stopped) return;  // set before the launch: the same for every lane
+        done = ctl->done;          // lane 0 writes the record only behind a barrier that follows this load
+        until = sp.check_every - done % sp.check_every;
+    }
     double *xg = a.x + lp.x0, *yg = a.y + lp.x0, *lg = a.lam + lp.lam0;
     double *xs = xg, *ys = yg, *ls = lg;
     if (LDS) {
@@ -172,6 +224,7 @@ __global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, i
     const double *ginvd = a.ginvd + lp.x0;
     const i32 *grows = a.grows + lp.x0;
     for (int it = 0; it < iters; ++it) {
+        const bool check = STOP && until == 1;  // uniform: a function of the record and of `it`
         if (stages & 1) {
             const bool use_xp0 = first && it == 0;
             for (i32 j = tid; j < N; j += W) {
@@ -179,23 +232,88 @@ __global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, i
                 ys[j] = admm_rhs_one<1>(a.tptr[g], a.tptr[g + 1], a.tidx, a.tval, ls, q + j, use_xp0 ? xp0 + j : xs + j, !use_xp0, a.gamma_ineq, ld);
             }
             __syncthreads();
+            double dx = 0.0;  // a lane without a row in any level contributes 0.0
             for (i32 l = 0; l < lp.nlevels; ++l) {
                 const i64 beg = lptr[l], end = lptr[l + 1];
-                for (i64 t = beg + tid; t < end; t += W) {
-                    const i32 i = grows[t];
-                    xs[i] = admm_sweep_one<1>(gptr[t], gptr[t + 1], a.gidx, a.gval, xs, ld(ys + i), ld(xs + i), ginvd[t], lb[i], ub[i], ld);
+                if (check) {  // a loop of its own, as in the multiplier pass: the other one stays the loop of the kernel without the test
+                    for (i64 t = beg + tid; t < end; t += W) {
+                        const i32 i = grows[t];
+                        const double yi = ld(ys + i), xi = ld(xs + i);
+                        const double v = admm_sweep_one<1>(gptr[t], gptr[t + 1], a.gidx, a.gval, xs, yi, xi, ginvd[t], lb[i], ub[i], ld);
+                        xs[i] = v;
+                        dx = many_nanmax(dx, fabs(v - xi));
+                    }
+                } else {
+                    for (i64 t = beg + tid; t < end; t += W) {
+                        const i32 i = grows[t];
+                        xs[i] = admm_sweep_one<1>(gptr[t], gptr[t + 1], a.gidx, a.gval, xs, ld(ys + i), ld(xs + i), ginvd[t], lb[i], ub[i], ld);
+                    }
                 }
                 __syncthreads();  // same compute unit: the stores of this level are visible to the next one
             }
+            if (check) {  // behind the last level's barrier; read behind the multiplier pass's, or behind the one below
+                dx = many_wave_nanmax(dx);
+                if ((tid & (kWave - 1)) == 0) admmm_red[tid / kWave] = dx;
+            }
+        }
+        if (STOP && !(stages & 2)) {  // sweep_step: the reduced step waits in the record for multiplier_step
+            if (check) {
+                __syncthreads();  // the slots of every wave are written
+                if (tid == 0) {
+                    double dx = admmm_red[0];
+                    for (i32 w = 1; w < W / kWave; ++w) dx = many_nanmax(dx, admmm_red[w]);
+                    sp.ctl[id].dx = dx;
+                }
+            }
+            continue;
         }
         if (stages & 2) {
-            for (i32 r = tid; r < m; r += W) {
-                const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
-                ls[r] = admm_mult_one<1>(a.aptr[g], a.aptr[g + 1], a.aidx, a.aval, xs, ls + r, b + r, a.gamma_eq, ld);
+            if (check) {
+                double dr = 0.0;  // 0.0 for an LP without rows, and from a lane without one
+                for (i32 r = tid; r < m; r += W) {
+                    const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
+                    double res;
+                    ls[r] = admm_mult_res_one<1>(a.aptr[g], a.aptr[g + 1], a.aidx, a.aval, xs, ls + r, b + r, a.gamma_eq, ld, &res);
+                    dr = many_nanmax(dr, fabs(res));
+                }
+                dr = many_wave_nanmax(dr);
+                if ((tid & (kWave - 1)) == 0) admmm_red[kAdmmmWaves + tid / kWave] = dr;
+            } else {
+                for (i32 r = tid; r < m; r += W) {
+                    const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
+                    ls[r] = admm_mult_one<1>(a.aptr[g], a.aptr[g + 1], a.aidx, a.aval, xs, ls + r, b + r, a.gamma_eq, ld);
+                }
             }
             __syncthreads();
         }
+        if (STOP) {  // here an iteration is complete
+            ++done;
+            if (!check) {
+                --until;
+                continue;
+            }
+            until = sp.check_every;
+            if (tid == 0) {
+                AdmmmCtl *ctl = sp.ctl + id;
+                double dx = (stages & 1) ? admmm_red[0] : ctl->dx, dr = admmm_red[kAdmmmWaves];
+                for (i32 w = 1; w < W / kWave; ++w) {
+                    if (stages & 1) dx = many_nanmax(dx, admmm_red[w]);
+                    dr = many_nanmax(dr, admmm_red[kAdmmmWaves + w]);
+                }
+                const bool stop = dr <= sp.tol_residual && dx <= sp.tol_step;  // false for a NaN
+                ctl->residual = dr;
+                ctl->step = dx;
+                if (stop) {
+                    ctl->stopped = 1;
+                    ctl->stop_iter = done;
+                }
+                admmm_red[2 * kAdmmmWaves] = stop ? 1.0 : 0.0;
+            }
+            __syncthreads();  // the one barrier the test adds to a whole iteration, in a check iteration only
+            if (admmm_red[2 * kAdmmmWaves] != 0.0) break;  // one slot, read by every lane: uniform
+        }
     }
+    if (STOP && (stages & 2) && tid == 0) sp.ctl[id].done = done;
     if (LDS) {
         for (i32 j = tid; j < N; j += W) xg[j] = xs[j];
         for (i32 r = tid; r < m; r += W) lg[r] = ls[r];
@@ -254,6 +372,12 @@ struct slp_admm_many {
     DevBuf<i32> gidx, grows;
     DevBuf<double> gval, ginvd;
     DevBuf<double> b, q, c, lb, ub, xp0, x, y, lam, out;
+    // stopping: off while tol_residual < 0.  The kernel without the test touches no record, so the whole iterations run while it is
+    // off are counted here and added to every record when the test is armed (and when the state is read)
+    DevBuf<AdmmmCtl> ctl;
+    double tol_residual = -1.0, tol_step = 0.0;
+    i64 check_every = 1, uncounted = 0;
+    bool mid_iteration = false;  // between sweep_step and multiplier_step
     ~slp_admm_many() { if (base) slp_admm_destroy(base); }
 };
 
@@ -273,10 +397,21 @@ static AdmmmArgs admmm_args(const slp_admm_many *s, int g) {
     return r;
 }
 
-// `k` times the stages, in launches of at most kmax iterations per form
+template <bool LDS>
+static void admmm_launch(const slp_admm_many *s, const ManyGroup &gr, const AdmmmArgs &a, int it, int first, int stages, bool stop) {
+    const AdmmmStop sp = {s->ctl.p, s->tol_residual, s->tol_step, s->check_every};
+    const dim3 grid((unsigned)gr.ids.size()), block(gr.block);
+    const size_t lds = LDS ? gr.lds_bytes : 0;
+    if (stop) hipLaunchKernelGGL((k_admmm_iterate<LDS, true>), grid, block, lds, ctx().stream, a, it, first, stages, sp);
+    else hipLaunchKernelGGL((k_admmm_iterate<LDS, false>), grid, block, lds, ctx().stream, a, it, first, stages, sp);
+}
+
+// `k` times the stages, in launches of at most kmax iterations per form; with the stopping test when it is armed
 static void admmm_run(slp_admm_many *s, i64 k, int stages) {
     if (k <= 0) return;
-    hipStream_t st = ctx().stream;
+    const bool stop = s->tol_residual >= 0.0;
+    if (!stop && (stages & 2)) s->uncounted += k;
+    s->mid_iteration = !(stages & 2);
     for (int g = 0; g < 2; ++g) {
         const ManyGroup &gr = s->group[g];
         if (gr.ids.empty()) continue;
@@ -284,15 +419,21 @@ static void admmm_run(slp_admm_many *s, i64 k, int stages) {
         bool xp_is_x = s->xp_is_x;
         many_split(k, gr.kmax, [&](int it) {
             const int first = ((stages & 1) && !xp_is_x) ? 1 : 0;
-            if (g == 0)
-                hipLaunchKernelGGL((k_admmm_iterate<true>), dim3((unsigned)gr.ids.size()), dim3(gr.block), gr.lds_bytes, st, a, it, first, stages);
-            else
-                hipLaunchKernelGGL((k_admmm_iterate<false>), dim3((unsigned)gr.ids.size()), dim3(gr.block), 0, st, a, it, first, stages);
+            if (g == 0) admmm_launch<true>(s, gr, a, it, first, stages, stop);
+            else admmm_launch<false>(s, gr, a, it, first, stages, stop);
             if (stages & 2) xp_is_x = true;  // :259
             return it;
         });
     }
     if (stages & 2) s->xp_is_x = true;
+}
+
+// the records with the iterations of the unarmed launches added; synchronises
+static std::vector<AdmmmCtl> admmm_read_ctl(slp_admm_many *s) {
+    std::vector<AdmmmCtl> h((size_t)s->count);
+    s->ctl.download(h.data(), h.size());
+    for (AdmmmCtl &c : h) c.done += s->uncounted;  // no LP is stopped while the test is off
+    return h;
 }
 
 // the two environment switches and the form per LP -- from the shapes only; needs no device, nothing is allocated yet
@@ -472,7 +613,7 @@ slp_admm_many *slp_admm_many_create(int64_t count, const int64_t *n, const int64
             for (i64 i = 0; i < Me; ++i) { const double l = (double)(eq_indptr[i + 1] - eq_indptr[i]); sq += l * l; }
             many_require_memory("slp_admm_many_create", count,
                                 64.0 * nnz_a + 52.0 * (sq + (double)N) + 8.0 * (13.0 * (double)N + 4.0 * (double)M) + 16.0 * 8.0 * (double)(N + M) +
-                                    (double)count * (double)(sizeof(AdmmmLp) + sizeof(i32) + 3 * sizeof(double)));
+                                    (double)count * (double)(sizeof(AdmmmLp) + sizeof(AdmmmCtl) + sizeof(i32) + 3 * sizeof(double)));
         }
         hipStream_t st = ctx().stream;
         // the whole chain once, on the composite (its x0 = [x0; A_ineq x0] block by block: the scaled block is block-diagonal too)
@@ -487,7 +628,8 @@ slp_admm_many *slp_admm_many_create(int64_t count, const int64_t *n, const int64
         hipLaunchKernelGGL(k_admmm_localise, per_lp, dim3(kBlock), 0, st, s->table.p, A.ptr.p, A.idx.p, At.ptr.p, At.idx.p, nn, Me);
         SLP_HIP(hipGetLastError());
         many_upload_lists(s->group, s->list);
-        many_lds_opt_in(reinterpret_cast<const void *>(k_admmm_iterate<true>), s->group[0].lds_bytes, kAdmmmLdsLimit * sizeof(double));
+        many_lds_opt_in(reinterpret_cast<const void *>(k_admmm_iterate<true, false>), s->group[0].lds_bytes, kAdmmmLdsLimit * sizeof(double));
+        many_lds_opt_in(reinterpret_cast<const void *>(k_admmm_iterate<true, true>), s->group[0].lds_bytes, kAdmmmLdsLimit * sizeof(double));
         s->b.alloc((size_t)M); s->lam.alloc((size_t)M); s->lam.zero();
         for (DevBuf<double> *v : {&s->q, &s->c, &s->lb, &s->ub, &s->xp0, &s->x, &s->y}) v->alloc((size_t)N);
         s->y.zero();
@@ -497,6 +639,8 @@ slp_admm_many *slp_admm_many_create(int64_t count, const int64_t *n, const int64
         hipLaunchKernelGGL(k_admmm_gather_rows, per_lp, dim3(kBlock), 0, st, s->table.p, s->sh.b, s->b.p);
         SLP_HIP(hipGetLastError());
         s->out.alloc((size_t)3 * (size_t)count);
+        std::vector<AdmmmCtl> ctl((size_t)count, AdmmmCtl{0, 0, __builtin_inf(), __builtin_inf(), 0.0, 0, 0});
+        s->ctl.upload(ctl.data(), ctl.size());
         SLP_HIP(hipStreamSynchronize(st));
         return s.release();
     })
@@ -518,6 +662,38 @@ int slp_admm_many_report(slp_admm_many *s, double *out) {
         hipLaunchKernelGGL(k_admmm_report, dim3((unsigned)s->count), dim3(kBlock), 0, ctx().stream, admmm_args(s, 0), s->xp_is_x ? 0 : 1, s->out.p);
         SLP_HIP(hipGetLastError());
         s->out.download(out, (size_t)3 * (size_t)s->count);
+    })
+}
+
+int slp_many_admm_set_stop(slp_admm_many *s, double tol_residual, double tol_step, int64_t check_every) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_admm_set_stop: NULL handle");
+        SLP_REQUIRE(tol_residual < 0.0 || (std::isfinite(tol_residual) && std::isfinite(tol_step) && tol_step >= 0.0 && check_every >= 1),
+                    "slp_many_admm_set_stop: tol_residual and tol_step must be finite and >= 0 with check_every >= 1 (tol_residual < 0 turns "
+                    "the test off)");
+        SLP_REQUIRE(!s->mid_iteration, "slp_many_admm_set_stop: called between sweep_step and multiplier_step (whole iterations only)");
+        std::vector<AdmmmCtl> h = admmm_read_ctl(s);
+        for (AdmmmCtl &c : h) c.stopped = 0;
+        s->ctl.upload(h.data(), h.size());
+        s->uncounted = 0;
+        s->tol_residual = tol_residual < 0.0 ? -1.0 : tol_residual;
+        if (tol_residual >= 0.0) {
+            s->tol_step = tol_step;
+            s->check_every = check_every;
+        }
+    })
+}
+
+int slp_many_admm_stop_state(slp_admm_many *s, int64_t *iterations, int32_t *stopped, double *residual, double *step) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_admm_stop_state: NULL handle");
+        const std::vector<AdmmmCtl> h = admmm_read_ctl(s);
+        for (size_t k = 0; k < h.size(); ++k) {
+            if (iterations) iterations[k] = h[k].stopped ? h[k].stop_iter : h[k].done;
+            if (stopped) stopped[k] = h[k].stopped;
+            if (residual) residual[k] = h[k].residual;
+            if (step) step[k] = h[k].step;
+        }
     })
 }
 

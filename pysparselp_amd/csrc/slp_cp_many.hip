@@ -98,15 +98,6 @@ struct CpmStop {
     i64 check_every;
 };
 
-// max as np.max: a NaN on either side stays
-__device__ __forceinline__ double cpm_nanmax(double m, double d) { return (d > m || d != d) ? d : m; }
-
-__device__ __forceinline__ double cpm_wave_nanmax(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = cpm_nanmax(v, __shfl_down(v, off, kWave));
-    return v;
-}
-
 constexpr int kCpmWaves = kCpmMaxBlock / kWave;
 
 struct CpmArgs {
@@ -164,10 +155,10 @@ __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int ite
                 zs[j] = zn;
                 xs[j] = x2;
                 if (store) a.x4[lp.col0 + j] = (d < 0.0) ? u : l;
-                if (STOP) dx = cpm_nanmax(dx, fabs(x2 - xo));
+                if (STOP) dx = many_nanmax(dx, fabs(x2 - xo));
             }
             if (check) {
-                dx = cpm_wave_nanmax(dx);
+                dx = many_wave_nanmax(dx);
                 if ((tid & (kWave - 1)) == 0) cpm_red[tid / kWave] = dx;
             }
             __syncthreads();  // same compute unit: the stores of this half are visible to the next one
@@ -175,7 +166,7 @@ __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int ite
         if (STOP && !(stages & 2)) {  // primal_step: the reduced dx waits in the record for dual_step
             if (check && tid == 0) {
                 double dx = cpm_red[0];
-                for (i32 w = 1; w < W / kWave; ++w) dx = cpm_nanmax(dx, cpm_red[w]);
+                for (i32 w = 1; w < W / kWave; ++w) dx = many_nanmax(dx, cpm_red[w]);
                 sp.ctl[id].dx = dx;
             }
             continue;
@@ -187,10 +178,10 @@ __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int ite
                 const double kz = cp_row_sum(a.ptr[g], a.ptr[g + 1], a.idx, a.val, zs, 1, ld);
                 const double yo = ld(ys + r), yn = cp_dual_point(kz, a.b[g], yo, a.sigma[g], r >= lp.m_eq);
                 ys[r] = yn;
-                if (STOP) dy = cpm_nanmax(dy, fabs(yn - yo));
+                if (STOP) dy = many_nanmax(dy, fabs(yn - yo));
             }
             if (check) {
-                dy = cpm_wave_nanmax(dy);
+                dy = many_wave_nanmax(dy);
                 if ((tid & (kWave - 1)) == 0) cpm_red[kCpmWaves + tid / kWave] = dy;
             }
             __syncthreads();
@@ -206,10 +197,10 @@ __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int ite
                 CpmCtl *ctl = sp.ctl + id;
                 double dx = (stages & 1) ? cpm_red[0] : ctl->dx, dy = cpm_red[kCpmWaves];
                 for (i32 w = 1; w < W / kWave; ++w) {
-                    if (stages & 1) dx = cpm_nanmax(dx, cpm_red[w]);
-                    dy = cpm_nanmax(dy, cpm_red[kCpmWaves + w]);
+                    if (stages & 1) dx = many_nanmax(dx, cpm_red[w]);
+                    dy = many_nanmax(dy, cpm_red[kCpmWaves + w]);
                 }
-                const double step = cpm_nanmax(dx, dy);
+                const double step = many_nanmax(dx, dy);
                 const bool stop = step <= sp.tol;  // false for a NaN
                 ctl->step = step;
                 if (stop) {

@@ -2,12 +2,23 @@
 // that need no device are in slp_many_plan.h.
 #pragma once
 #include "slp_common.h"
+#include "slp_kernels.h"
 #include "slp_many_plan.h"
 
 namespace slp {
 
 // row `r` of an LP (equality rows first) in a matrix that holds the equality rows of all LPs before their inequality rows
 __device__ __forceinline__ i64 many_row(i64 eq0, i64 in0, i32 m_eq, i32 r) { return r < m_eq ? eq0 + r : in0 + (r - m_eq); }
+
+// max as np.max: a NaN on either side stays (the per-LP stopping tests of slp_cp_many.hip and slp_admm_many.hip)
+__device__ __forceinline__ double many_nanmax(double m, double d) { return (d > m || d != d) ? d : m; }
+
+// the same over the 64 lanes of a wave, by shuffles: lane 0 holds the result
+__device__ __forceinline__ double many_wave_nanmax(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = many_nanmax(v, __shfl_down(v, off, kWave));
+    return v;
+}
 
 // the lists of the LPs of each form, on the device
 inline void many_upload_lists(const ManyGroup group[2], DevBuf<i32> list[2]) {
