@@ -33,8 +33,13 @@ def steps_of(xs, ys):
     """``step_t`` for ``t = 1 .. T`` from ``[x_0 .. x_T]`` and ``[y_0 .. y_T]``; entry ``t - 1`` belongs to iteration ``t``."""
     assert len(xs) == len(ys)
     with np.errstate(invalid="ignore"):
-        return np.array([max(np.max(np.abs(xs[t] - xs[t - 1])), np.max(np.abs(ys[t] - ys[t - 1])), key=_nan_first)
-                         for t in range(1, len(xs))])
+        return np.array([max(_max_abs(xs[t] - xs[t - 1]), _max_abs(ys[t] - ys[t - 1]), key=_nan_first)
+                         for t in range(1, len(xs))], dtype=np.float64)
+
+
+def _max_abs(v):
+    """``np.max|v|``, 0.0 for no entry (as ``admm_stop_cpu._max_abs``: a dual block whose only row was dropped); a NaN stays."""
+    return float(np.max(np.abs(v))) if v.size else 0.0
 
 
 def _nan_first(v):

@@ -2,7 +2,9 @@
 tools/fuzz_batched.py with the GPU test's own seed and case count: the dual-ascent LPs mostly run clean, some raise each of the
 two line-search errors in a way the device can be compared with, the horizons are worth comparing,
 HiGHS solves every clean one, and the Chambolle-Pock / ADMM LPs are accepted by the entry points and reach the wave, tile and
-padding sizes they are drawn for."""
+padding sizes they are drawn for.  For tests/test_gpu_fuzz_many_stop.py: under the drawn tolerances, by the numpy restatements
+alone, stopping and running LPs stand side by side in the lists -- in the long one, at every cadence, at the large sizes, warm and
+cold, with equality rows only -- the chosen LP mostly stops by exact equality, and one Chambolle-Pock list stops at a step of 0.0."""
 import os
 import sys
 
@@ -143,3 +145,73 @@ def test_cp_and_admm_lps_pass_validation_and_reach_the_edge_sizes():
     assert any(a["a_eq"] is None for a, _, _ in cp_batches) and any(a["a_eq"] is not None for a, _, _ in cp_batches)
     assert any(a["b_upper"] is not None and a["b_upper"].ndim == 2 for a, _, _ in cp_batches)   # per-instance right-hand sides
     assert any(a["lb"].ndim == 2 for a, _, _ in cp_batches) and any(a["lb"].ndim == 2 for a, _, _ in admm_batches)
+
+
+# ---- the per-LP stopping lists: what keeps tests/test_gpu_fuzz_many_stop.py from passing vacuously -------------------------------------
+
+def _stop_facts(cases):
+    """Per list ``dict(case, every, exact, early, tol, entries)`` from the restatement alone; ``entries``: one ``(stopped, n, warm,
+    equalities only, step)`` per LP of the list."""
+    out = []
+    for case in cases:
+        want = case.want()
+        iterations, stopped, step = want[0], want[1], want[-1]
+        entries = [(bool(stopped[k]), lp["c"].size, lp["x0"] is not None, lp["a_ineq"] is None, float(step[k])) for k, lp in enumerate(case.lps)]
+        k = case.k_star
+        out.append(dict(case=case, every=case.every, tol=case.tol, entries=entries, exact=bool(stopped[k]) and iterations[k] == case.t_star,
+                        early=bool(stopped[k]) and iterations[k] < case.t_star))
+        assert all(iterations[~stopped] == case.total) and all(iterations[stopped] % case.every == 0)
+        assert stopped[k] and iterations[k] <= case.t_star   # the LP the tolerances come from meets them at t_star at the latest
+    return out
+
+
+def _both(entries):
+    """Does a set of entries hold a stopping and a running LP?"""
+    kinds = {e[0] for e in entries}
+    return kinds == {True, False}
+
+
+def _assert_stop_conditions(family, cases):
+    from pysparselp_amd import _many
+
+    facts = _stop_facts(cases)
+    assert len(facts) == CASES
+    for f in facts:   # the draws: the horizon, the cadences, a check iteration in the last two thirds, tolerances the entry points take
+        case = f["case"]
+        assert case.total == 20 + case.its and case.every in (1, 3, 10) and 0 <= case.k_star < len(case.lps)
+        assert case.t_star % case.every == 0 and case.total // 3 <= case.t_star <= case.total
+        assert 1 <= case.after <= max(1, case.total // 3 - 1)
+        for tol in case.tol:
+            assert _many.check_stop(tol, case.every) == (tol, case.every)
+    everything = [e for f in facts for e in f["entries"]]
+    short = [e for f in facts if len(f["entries"]) <= 256 for e in f["entries"]]
+    long_lists = [f["entries"] for f in facts if len(f["entries"]) > 256]
+    stopping = [e for e in everything if e[0]]
+    large = [e for e in everything if e[1] >= 127]
+    print(f"{family}: {len(stopping)} of {len(everything)} list entries stop; without the long list {sum(e[0] for e in short)} of {len(short)}; "
+          f"{sum(_both(f['entries']) for f in facts)} of {len(facts)} lists hold both kinds; k_star stops exactly at t_star in "
+          f"{sum(f['exact'] for f in facts)} lists, earlier in {sum(f['early'] for f in facts)}; n >= 127: {sum(e[0] for e in large)} stop, "
+          f"{sum(not e[0] for e in large)} run; the long list: {[sum(e[0] for e in entries) for entries in long_lists]} of "
+          f"{[len(entries) for entries in long_lists]} stop; equalities only: {sum(e[0] and e[3] for e in everything)} stop, "
+          f"{sum(e[3] and not e[0] for e in everything)} run; tol == 0.0 in cases {[i for i, f in enumerate(facts) if f['tol'][-1] == 0.0]}")
+    for entries in (everything, short):
+        assert 4 * sum(e[0] for e in entries) >= len(entries) and 4 * sum(not e[0] for e in entries) >= len(entries)
+    assert 2 * sum(_both(f["entries"]) for f in facts) >= len(facts)
+    assert sum(f["exact"] for f in facts) >= 8 and sum(f["early"] for f in facts) >= 1
+    for every in (1, 3, 10):
+        assert _both([e for f in facts if f["every"] == every for e in f["entries"]]), every
+    assert _both(large)
+    assert {e[2] for e in stopping} == {True, False}
+    assert len(long_lists) == 1 and _both(long_lists[0])
+    return facts, everything
+
+
+def test_admm_stopping_lists_hold_stopping_and_running_lps_of_every_kind():
+    _assert_stop_conditions("admm", fuzz_batched.admm_stop_cases(CASES, SEED))
+
+
+def test_cp_stopping_lists_hold_stopping_and_running_lps_of_every_kind():
+    facts, everything = _assert_stop_conditions("cp", fuzz_batched.cp_stop_cases(CASES, SEED))
+    assert _both([e for e in everything if e[3]])   # among the LPs with equality rows only
+    # an exact fixed point: a tolerance of 0.0 under which an LP stops at a step of exactly 0.0
+    assert any(f["tol"] == (0.0,) and any(e[0] and e[4] == 0.0 for e in f["entries"]) for f in facts)

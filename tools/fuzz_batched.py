@@ -7,7 +7,14 @@ also against the single solver alone, the status bits of the LPs on which dga_cp
 The LPs have wave / tile / padding sizes (n in 1, 2, 3, 63, 64, 65, 127, 129, 255, 257), an empty row, an empty column, a row of
 more than 64 entries, one- / two-sided / mixed rows, infinite and equal bounds, warm starts and odd reporting cadences.
 
-    python tools/fuzz_batched.py [--cases 24] [--seed 0] [--family cp_batch,cp_many,admm_batch,admm_many,dga,dga_batch,dga_many]
+``cp_many_stop`` and ``admm_many_stop`` arm the per-LP stopping test of the two list solvers on the same lists (``set_stop`` /
+``stop_state``, ``chambolle_pock_ppd_many_until`` / ``lp_admm_many_until``): the tolerances are the reference step (and residual) of
+one LP of the list at a check iteration, so that ``<=`` decides by equality; the stopping iterations, flags, steps and residuals
+against the numpy restatements (tests/cp_stop_cpu.py, tests/admm_stop_cpu.py) and every LP's frozen iterate against the oracle's
+at that LP's own count, bit for bit.
+
+    python tools/fuzz_batched.py [--cases 24] [--seed 0]
+        [--family cp_batch,cp_many,admm_batch,admm_many,dga,dga_batch,dga_many,cp_many_stop,admm_many_stop]
 
 The generators and the CPU references need no GPU (tests/test_fuzz_batched_host.py checks on them that the GPU runs compare what
 they claim to); the ``run_*`` functions need one."""
@@ -36,6 +43,9 @@ LONG_LIST = 260    # more LPs than compute units (256), by cycling
 DGA_ITERS = 40
 DGA_STOPS = (0, 9, DGA_ITERS - 1)
 STATUS_BITS = {"negative step": 1, "empty breakpoint set": 2, "never changes sign": 16}
+STOP_EXTRA, STOP_EVERY = 20, (1, 3, 10)   # a stopping list runs 20 iterations longer than its list; the cadences of the test
+CP_STOP_OFFSET, ADMM_STOP_OFFSET = 8000, 7000   # the stopping draws' generators: RandomState(seed + offset)
+STOP_AFTER_OFFSET = 500   # on top of them: the generator of ``after``, so that the test's own draws do not depend on it
 TEST_SEED, TEST_CASES = 20, 24   # what tests/test_gpu_fuzz_batched.py runs and tests/test_fuzz_batched_host.py checks
 
 
@@ -205,6 +215,117 @@ def admm_many_cases(cases, seed):
             lps = [lps[k % len(lps)] for k in range(LONG_LIST)]
         out.append((lps, int(rng.randint(1, 61)), int(rng.choice(CADENCES))))
     return out
+
+
+# ---- the per-LP stopping test of the list solvers: draws and what the restatement expects -----------------------------------------
+
+class StopRef:
+    """The CPU reference of one LP of a stopping list (never modified): the oracle's iterates ``xs[t]`` and ``duals[t]`` after ``t = 0
+    .. total`` iterations (Chambolle-Pock: ``x_t``, ``[y_eq; y_ineq]_t``; ADMM: ``x_t`` over all ``N`` columns, ``lambda_t``;
+    ``xs[0]`` of ADMM is the stored start), the restatement's ``curves`` -- ``(step,)`` or ``(residual, step)``, entry ``t - 1`` of
+    iteration ``t`` -- the oracle's ``reports`` at the list's cadence over the same horizon, and ``eq_only``."""
+
+    def __init__(self, xs, duals, curves, reports, eq_only=False):
+        self.xs, self.duals, self.curves, self.reports, self.eq_only = xs, duals, curves, reports, eq_only
+
+
+class StopCase:
+    """One list with its stopping test: ``lps`` (``problems``, ``x0``), the list's own ``its`` and report cadence ``plot``, the
+    horizon ``total = 20 + its``, the cadence ``every`` of the test, the tolerances ``tol`` (a tuple: the reference curves of LP
+    ``k_star`` at iteration ``t_star``), ``after`` (the unarmed iterations of the run that is armed in mid-life) and one ``StopRef``
+    per distinct LP (``ref(k)``)."""
+
+    def __init__(self, family, lps, its, plot, rng, rng_after):
+        import admm_stop_cpu
+        import cp_stop_cpu
+
+        self.family, self.lps, self.its, self.plot = family, lps, its, plot
+        self.problems = [of_instance(lp, 0)[0] for lp in lps]
+        self.x0 = [lp["x0"] for lp in lps]
+        self.total = total = STOP_EXTRA + its
+        self.every = int(rng.choice(STOP_EVERY))
+        checks = [t for t in range(1, total + 1) if t % self.every == 0 and t >= total // 3]
+        self.t_star = int(rng.choice(checks))
+        self.k_star = int(rng.randint(len(lps)))
+        self.after = int(rng_after.randint(1, max(1, total // 3 - 1) + 1))
+        self._stop_cpu = cp_stop_cpu if family == "cp" else admm_stop_cpu
+        self._refs = {}
+        for k, lp in enumerate(lps):   # a cycled list repeats its LPs: one reference each
+            if id(lp) not in self._refs:
+                self._refs[id(lp)] = (cp_stop_reference if family == "cp" else admm_stop_reference)(self.problems[k], self.x0[k], total, plot)
+        self.tol = tuple(float(curve[self.t_star - 1]) for curve in self.ref(self.k_star).curves)
+
+    def ref(self, k):
+        return self._refs[id(self.lps[k])]
+
+    def distinct(self):
+        return len(self._refs)
+
+    def want(self, after=0):
+        """The restatement's ``stop_state`` columns over the list's entries after ``total`` iterations, the test armed after
+        ``after`` of them: ``(iterations, stopped, step)`` / ``(iterations, stopped, residual, step)``."""
+        rows = {key: self._stop_cpu.stop_state(*ref.curves, *self.tol, self.every, self.total, after=after) for key, ref in self._refs.items()}
+        return tuple(np.array(col) for col in zip(*[rows[id(lp)] for lp in self.lps]))
+
+
+def cp_stop_reference(problem, x0, total, plot):
+    """``StopRef`` of one Chambolle-Pock LP.  An LP without inequality rows goes through the oracle with the inert row of
+    ``cp_reference``; that row's multiplier (always 0.0) is dropped, so its dual maximum runs over the equality rows alone."""
+    import cp_stop_cpu
+
+    c, a_eq, beq, a_ineq, bl, bu, lb, ub = problem
+    eq_only = a_ineq is None
+    through = (c, a_eq, beq, scipy.sparse.csr_matrix((1, c.size)), None, np.ones(1), lb, ub) if eq_only else problem
+    xs, ys = cp_stop_cpu.oracle_iterates(through, total, x0)
+    if eq_only:
+        assert all(y[-1] == 0.0 for y in ys)
+        ys = [y[:-1] for y in ys]
+    with np.errstate(invalid="ignore"):   # an energy of the reports over an infinite bound
+        reports = cp_reference(problem, x0, total, plot)[0]
+    return StopRef(xs, ys, (cp_stop_cpu.steps_of(xs, ys),), reports, eq_only)
+
+
+def admm_stop_reference(problem, x0, total, plot):
+    """``StopRef`` of one ADMM LP: the curves of ``admm_stop_cpu.oracle_curves``, the iterates and the reports of one more run of
+    the oracle (``total + 1`` sweeps: call ``i`` of its hook sees ``x_{i+1}`` and ``lambda_i``)."""
+    import admm_stop_cpu
+    from oracle import oracle
+
+    curves = admm_stop_cpu.oracle_curves(problem, total, x0)
+    xs, lams, rec = [np.array(oracle.admm_setup(*problem, x0)["x0"], dtype=np.float64, copy=True)], [], _Reports()
+
+    def hook(i, x, x_all, lam):
+        xs.append(np.array(x_all, copy=True))
+        lams.append(np.array(lam, copy=True))
+
+    oracle.lp_admm(*problem, x0=x0, nb_iter=total, nb_iter_plot=plot, callback_func=rec, iterate_hook=hook)
+    assert len(lams) == total + 1 and np.array_equal(admm_stop_cpu.curves_of(xs[:total + 1], curves[0])[1], curves[1])
+    if rec.it[-1] == total:   # the driver's horizon is nb_iter = total - 1: no report at index total
+        for store in (rec.it, rec.x, rec.e1, rec.e2, rec.veq, rec.vineq):
+            store.pop()
+    return StopRef(xs[:total + 1], lams, curves, rec)
+
+
+_STOP_CASES = {}
+
+
+def _stop_cases(family, lists, offset, cases, seed):
+    key = (family, cases, seed)
+    if key not in _STOP_CASES:
+        rng, rng_after = np.random.RandomState(seed + offset), np.random.RandomState(seed + offset + STOP_AFTER_OFFSET)
+        _STOP_CASES[key] = [StopCase(family, lps, its, plot, rng, rng_after) for lps, its, plot in lists(cases, seed)]
+    return _STOP_CASES[key]
+
+
+def cp_stop_cases(cases, seed):
+    """``[StopCase]`` of ``run_cp_many_stop``: the lists of ``cp_many_cases`` with a stopping test each, drawn from a generator of
+    its own; the references are computed once and shared."""
+    return _stop_cases("cp", cp_many_cases, CP_STOP_OFFSET, cases, seed)
+
+
+def admm_stop_cases(cases, seed):
+    """``[StopCase]`` of ``run_admm_many_stop``: the lists of ``admm_many_cases`` with a stopping test each."""
+    return _stop_cases("admm", admm_many_cases, ADMM_STOP_OFFSET, cases, seed)
 
 
 # ---- dual gradient ascent: LPs, batches, lists and their CPU references -----------------------------------------------------------
@@ -726,6 +847,208 @@ def run_admm_many(cases, seed):
     return counts
 
 
+# ---- the per-LP stopping test of the two list solvers --------------------------------------------------------------------------------
+
+class _StopReports(_Reports):
+    """Also keeps the ``info`` the ``_until`` driver sets as an attribute of its callback, as it is at every call (copies)."""
+
+    def __init__(self):
+        super().__init__()
+        self.seen = []
+
+    def __call__(self, *report):
+        super().__call__(*report)
+        self.seen.append({name: np.array(values, copy=True) for name, values in self.info.items()})
+
+
+def _stop_where(case_no, seed, case, setting, forms):
+    """``where(k, run)``: the head of every message about LP ``k`` of the list in the run ``run``."""
+    def where(k, run):
+        n = case.problems[k][0].size
+        start = "cold" if case.x0[k] is None else "warm"
+        return (f"{case.family}_many_stop seed {seed} case {case_no} LP {k} of {len(case.lps)} (n {n}, {start} start, {case.total} iterations), "
+                f"setting {setting}, form {forms[k]}, every {case.every}, tolerances {case.tol!r} (LP {case.k_star} at iteration {case.t_star}), {run}")
+    return where
+
+
+def _stop_layer(case, k, count):
+    """Does the single solver agree with the oracle on LP ``k`` after ``count`` iterations?"""
+    ref = case.ref(k)
+    n = case.problems[k][0].size
+    if case.family == "cp":
+        return _cp_single_agrees(case.problems[k], case.x0[k], count, ref.xs[count])
+    return _admm_single_agrees(case.problems[k], case.x0[k], count - 1, ref.xs[count][:n])
+
+
+STOP_NAMES = {"cp": ("iterations", "stopped", "step"), "admm": ("iterations", "stopped", "residual", "step")}
+
+
+def _compare_stop(case, want, got, iterates, where, run):
+    """``got`` (the columns of ``stop_state``, or of the driver's ``info``) against the restatement's ``want`` with
+    ``np.array_equal``, and -- unless ``iterates`` is None -- every LP's primal and dual iterate against the oracle's at that LP's
+    own count, bit for bit."""
+    for name, g, w in zip(STOP_NAMES[case.family], got, want):
+        if not np.array_equal(g, w, equal_nan=(name not in ("iterations", "stopped"))):
+            k = next(k for k in range(len(w)) if not np.array_equal(g[k], w[k], equal_nan=True))
+            count = max(1, int(min(got[0][k], want[0][k], case.total)))
+            _require(False, where(k, run) + f": {name} {g[k]!r}, the restatement gives {w[k]!r}", _stop_layer(case, k, count))
+    if iterates is None:
+        return
+    for k in range(len(case.lps)):
+        ref, count = case.ref(k), int(want[0][k])
+        for name, g, r in (("x", iterates[0][k], ref.xs[count]), ("y" if case.family == "cp" else "lambda", iterates[1][k], ref.duals[count])):
+            _require(np.array_equal(g, r), where(k, run) + f": {name} differs from the oracle's after {count} iterations", _stop_layer(case, k, count))
+
+
+def _compare_stop_driver(case, want, xs, info, rec, where):
+    """The ``_until`` driver: ``info`` is the restatement, ``xs[k]`` the oracle's ``x`` at each LP's count; at every callback a stopped
+    LP has its final iterate and ``callback_func.info`` says so, a running one has the oracle's report (energies within
+    ``ENERGY_TOL``).  The loop ends at the first report index at which every LP is stopped."""
+    run = f"the driver with reports every {case.plot}"
+    _compare_stop(case, want, tuple(info[name] for name in STOP_NAMES[case.family]), None, where, run)
+    last = int(want[0].max()) if want[1].all() else case.total
+    reports = [i for i in range(0, case.total, case.plot) if i < last]
+    _require(rec.it == reports, where(0, run) + f": reports at {rec.it}, expected at {reports}")
+    for k in range(len(case.lps)):
+        ref, count = case.ref(k), int(want[0][k])
+        n = case.problems[k][0].size
+        layer = _stop_layer(case, k, count)
+        x_final = ref.xs[count][:n]
+        _require(np.array_equal(xs[k], x_final), where(k, run) + f": the returned x differs from the oracle's after {count} iterations", layer)
+        for i, it in enumerate(reports):
+            at = where(k, run) + f", report at iteration {it}"
+            stopped = bool(want[1][k]) and count <= it
+            _require(bool(rec.seen[i]["stopped"][k]) == stopped, at + f": info['stopped'] is {rec.seen[i]['stopped'][k]}, the restatement stops it at {count}")
+            _require(int(rec.seen[i]["iterations"][k]) == (count if stopped else it), at + f": info['iterations'] is {rec.seen[i]['iterations'][k]}")
+            if stopped:
+                _require(np.array_equal(rec.x[i][k], x_final), at + ": a stopped LP's x is not its final iterate", layer)
+                if case.family == "admm":   # the report on the frozen state: its residual is the recorded one
+                    _require(rec.veq[i][k] == want[2][k], at + f": max violated equality {rec.veq[i][k]!r}, recorded residual {want[2][k]!r}", layer)
+                continue
+            _require(ref.reports.it[i] == it, at + f": the oracle reports at {ref.reports.it[i]}")
+            _require(np.array_equal(rec.x[i][k], ref.reports.x[i]), at + ": x differs", layer)
+            _require(rec.veq[i][k] == ref.reports.veq[i], at + f": max violated equality {rec.veq[i][k]!r} != {ref.reports.veq[i]!r}", layer)
+            if ref.eq_only:
+                _require(rec.vineq[i][k] == 0, at + ": a violated inequality without inequality rows")
+            else:
+                _require(rec.vineq[i][k] == ref.reports.vineq[i], at + f": max violated inequality {rec.vineq[i][k]!r} != {ref.reports.vineq[i]!r}", layer)
+            for name, g, r in (("energy1", rec.e1[i][k], ref.reports.e1[i]), ("energy2", rec.e2[i][k], ref.reports.e2[i])):
+                _require(np.allclose(g, r, equal_nan=True, **ENERGY_TOL), at + f": {name} {g!r} != {r!r}", layer)
+
+
+def _run_many_stop(family, cases, seed):
+    """Both ``run_*_many_stop``: see there."""
+    if family == "cp":
+        from pysparselp_amd import CPManyState, chambolle_pock_ppd_many_until
+        from pysparselp_amd.ChambollePockPPD import _many_problem
+
+        settings, switches = CP_MANY_SETTINGS, ("SLP_CP_MANY_FORM", "SLP_CP_MANY_KMAX")
+        stop_cases = cp_stop_cases(cases, seed)
+
+        def create(case):
+            return CPManyState([_many_problem(k, p) for k, p in enumerate(case.problems)], case.x0)
+
+        def halves(state):
+            state.primal_step()
+            state.dual_step()
+
+        def iterates(state):
+            return state.x(), state.y()
+
+        def driver(case, rec):
+            xs, _, info = chambolle_pock_ppd_many_until(case.problems, *case.tol, case.every, x0=case.x0, nb_max_iter=case.total, callback_func=rec,
+                                                        nb_iter_plot=case.plot)
+            return xs, info
+    else:
+        from pysparselp_amd import ADMMManyState, lp_admm_many_until
+        from pysparselp_amd.ADMM import _admm_many_problem, _admm_many_starts
+
+        settings, switches = ADMM_MANY_SETTINGS, ("SLP_ADMM_MANY_FORM", "SLP_ADMM_MANY_KMAX")
+        stop_cases = admm_stop_cases(cases, seed)
+
+        def create(case):
+            checked = [_admm_many_problem(k, p) for k, p in enumerate(case.problems)]
+            return ADMMManyState(checked, _admm_many_starts(case.x0, checked))
+
+        def halves(state):
+            state.sweep_step()
+            state.multiplier_step()
+
+        def iterates(state):
+            return state.x(full=True), state.lam()
+
+        def driver(case, rec):   # nb_iter + 1 sweeps
+            return lp_admm_many_until(case.problems, *case.tol, case.every, x0=case.x0, nb_iter=case.total - 1, callback_func=rec,
+                                      nb_iter_plot=case.plot)
+
+    def armed_run(case, unarmed, split_at=None):
+        """A fresh state: ``unarmed`` iterations, ``set_stop``, the rest up to ``total`` (the iteration ``split_at`` in its two halves).
+        Returns ``(forms, stop_state, iterates, column 1 of the report)``."""
+        state = create(case)
+        try:
+            forms = [state.form(k) for k in range(state.count)]
+            for p in _pieces(unarmed):
+                state.iterate(p)
+            state.set_stop(*case.tol, case.every)
+            done = unarmed
+            if split_at is not None:
+                for p in _pieces(split_at - 1 - done):
+                    state.iterate(p)
+                halves(state)
+                done = split_at
+            for p in _pieces(case.total - done):
+                state.iterate(p)
+            return forms, state.stop_state(), iterates(state), (state.report()[:, 1] if family == "admm" else None)
+        finally:
+            state.close()
+
+    counts = dict(lists=0, lps=0, runs=0, stopped=0, running=0, longest=0)
+    for case_no, case in enumerate(stop_cases):
+        want = case.want()
+        for name, form, kmax in settings:
+            with environment(**dict(zip(switches, (form, kmax)))):
+                forms, got, its, residual = armed_run(case, 0)   # (a) armed from creation
+                where = _stop_where(case_no, seed, case, name, forms)
+                _require(form is None or set(forms) == {form}, f"{family}_many_stop seed {seed} case {case_no}: forms {set(forms)} under {switches[0]}={form}")
+                _compare_stop(case, want, got, its, where, "armed from creation")
+                if family == "admm":
+                    for k in np.nonzero(want[1])[0]:
+                        _require(residual[k] == want[2][k], where(k, "armed from creation") + f": the report's residual {residual[k]!r} of a stopped LP, "
+                                 f"recorded {want[2][k]!r}", _stop_layer(case, k, int(want[0][k])))
+                if name == "default":
+                    _, got, its, _ = armed_run(case, case.after)   # (b) armed in mid-life
+                    _compare_stop(case, case.want(after=case.after), got, its, where, f"armed after {case.after} iterations")
+                    _, got, its, _ = armed_run(case, 0, split_at=case.t_star)   # (c) the iteration t_star in its two halves
+                    _compare_stop(case, want, got, its, where, f"iteration {case.t_star} in two halves")
+                    rec = _StopReports()   # (d) the driver
+                    xs, info = driver(case, rec)
+                    _compare_stop_driver(case, want, xs, info, rec, where)
+            counts["runs"] += 1
+        counts["lists"] += 1
+        counts["lps"] += case.distinct()
+        counts["stopped"] += int(want[1].sum())
+        counts["running"] += int((~want[1]).sum())
+        counts["longest"] = max(counts["longest"], len(case.lps))
+    return counts
+
+
+def run_cp_many_stop(cases, seed):
+    """``CPManyState.set_stop`` / ``stop_state`` and ``chambolle_pock_ppd_many_until`` on the lists of ``run_cp_many``, each with a
+    stopping test whose tolerance is the reference step of one of its LPs at a check iteration (``<=`` decides by equality), 20
+    iterations longer.  Under the four settings of ``run_cp_many``, armed from creation: ``stop_state`` against the restatement
+    (tests/cp_stop_cpu.py) and every LP's ``x`` and ``y`` against the oracle's iterate at that LP's own count.  With the library's own
+    choice also: armed in mid-life, the chosen iteration in its two halves, and the driver with its callbacks.  Returns counts."""
+    return _run_many_stop("cp", cases, seed)
+
+
+def run_admm_many_stop(cases, seed):
+    """``ADMMManyState.set_stop`` / ``stop_state`` and ``lp_admm_many_until`` on the lists of ``run_admm_many``: as
+    ``run_cp_many_stop``, with the two tolerances the reference residual and step of one LP at a check iteration
+    (tests/admm_stop_cpu.py), ``x`` over all columns of the standard form, ``lambda``, and a stopped LP's report against its
+    recorded residual.  Returns counts."""
+    return _run_many_stop("admm", cases, seed)
+
+
 # ---- dual gradient ascent on the device -------------------------------------------------------------------------------------------------
 
 class _LP:
@@ -1030,7 +1353,7 @@ def run_dga_many(cases, seed):
 
 
 FAMILIES = {"cp_batch": run_cp_batch, "cp_many": run_cp_many, "admm_batch": run_admm_batch, "admm_many": run_admm_many, "dga": run_dga,
-            "dga_batch": run_dga_batch, "dga_many": run_dga_many}
+            "dga_batch": run_dga_batch, "dga_many": run_dga_many, "cp_many_stop": run_cp_many_stop, "admm_many_stop": run_admm_many_stop}
 
 
 def main():
