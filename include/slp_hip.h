@@ -768,6 +768,28 @@ int slp_many_dga_timing(slp_many_dga *s, int on);
 int slp_many_dga_timing_read(slp_many_dga *s, double out[5]);
 /* Replaces: nothing in the reference.  Iterations one launch holds at most: from the shapes, lowered by SLP_DGA_MANY_KMAX. */
 int64_t slp_many_dga_kmax(const slp_many_dga *s);
+/* Per-LP stopping, tested inside the iteration kernel; no counterpart in the reference (a fixed number of iterations, one LP per
+ * call).  Iterations of an LP count from 1 over its whole life; y_t = [y_eq; y_ineq] are its multipliers after iteration t, the
+ * inequality part after its clamp, y_0 the start.  step_t = max_r |y_t,r - y_{t-1},r| over all rows of the LP, as np.max (a NaN
+ * stays, so a NaN never stops an LP); a kind of rows that does not move in iteration t (its block predicate is false) contributes
+ * 0.  At the end of an iteration t with t % check_every == 0 the LP stops iff step_t <= tol, unless its status carries the NaN bit
+ * (a breakpoint or a step was NaN: its multipliers certify nothing, it runs on).  A stopped LP keeps y_t, its x (the dual argmin
+ * at the top of iteration t: what the reference returns after t iterations), its tie-draw count and its status bits, and takes no
+ * part in later launches; slp_many_dga_status, _get_x, _get_y and _report work on it as on any LP, and its report is the energy of
+ * its multipliers as they stand: its certified bound.  A frozen LP is never tested.  When every LP is stopped or frozen
+ * slp_many_dga_iterate launches nothing and leaves `iterations done` as it is.
+ * tol >= 0 and finite with check_every >= 1 arms the test, tol < 0 turns it off (the state after create: the launch is then the
+ * kernel without the test); anything else is an error.  Synchronises.
+ * NO RESUME -- the difference from slp_many_cp_set_stop, whose calls clear the stopped flags: a stopped LP is no reader of the
+ * stream of tie draws any more, so slp_many_dga_push_random drops the draws behind its position and it could not go on from
+ * there.  Every call keeps the stopped flags and the counters; a new tolerance or cadence applies to the LPs still moving, from
+ * their next check iteration; turning the test off leaves the stopped LPs stopped.
+ * (The two names are slp_many_dual_*, "dual" for dual ascent, beside slp_many_cp_set_stop and slp_many_admm_set_stop: slp_many_dga_*
+ * stays the set of entry points the list form was created with, and slp_dga_* is the single solver's.) */
+int slp_many_dual_set_stop(slp_many_dga *s, double tol, int64_t check_every);
+/* Per LP: iterations completed (for a stopped LP its stopping iteration, 0 for a frozen one), 1 = stopped, the last evaluated step
+ * (+inf before the first test).  count values each; any pointer may be NULL.  Synchronises. */
+int slp_many_dual_stop_state(slp_many_dga *s, int64_t *iterations, int32_t *stopped, double *step);
 
 /* ---- synthetic random LP on the device (randomLP.py:14-75) -------------- *
  * Row r of A_ineq (global row index row_offset + r): every entry is non-zero

@@ -8,6 +8,8 @@ lower bound on the LP's value.  ``DeviceDGABatch`` / ``dual_gradient_ascent_batc
 matrix and the right-hand sides together (csrc/slp_dga_batch.hip); instance k is bit for bit the single solve of its data.
 ``DeviceDGAMany`` / ``dual_gradient_ascent_many`` advance a list of LPs with matrices of their own, one workgroup per LP and whole
 iterations inside a launch (csrc/slp_dga_many.hip); LP k is bit for bit the single solve of ``lps[k]``.
+``DeviceDGAMany.set_stop`` / ``dual_gradient_ascent_many_until`` stop every LP of such a list on its own, by a test on the step of
+its multipliers inside the iteration kernel.
 """
 import os
 import time
@@ -190,22 +192,26 @@ def exact_dual_line_search(direction, a, b, c_bar, upper_bounds, lower_bounds, d
     return float(out[0])
 
 
-def _dga_drive(state, nb_max_iter, callback_func, max_time, start, all_frozen=False):
+def _dga_drive(state, nb_max_iter, callback_func, max_time, start, all_frozen=False, all_still=None):
     """The loop of the three forms: iteration ``niter`` with ``niter % 100 == 0`` is a launch of its own, followed by the status
     check, the callback with the x of the top of that iteration and the test of ``max_time``; the iterations between two such
-    are one call.  Nothing runs when every reader is frozen."""
+    are one call.  Nothing runs when every reader is frozen.  ``all_still()`` (a list with a stopping test), asked after every
+    call and before its callback: true once no LP moves any more, which ends the loop behind that callback."""
     i = 0
     while i < nb_max_iter and not all_frozen:
         k = 1 if i % 100 == 0 else min(100 - i % 100, nb_max_iter - i)
         state.iterate(k)
         i += k
         state.check()
+        still = all_still is not None and all_still()
         if (i - 1) % 100 == 0:
             elapsed = time.perf_counter() - start
             if callback_func is not None:
                 callback_func(i - 1, state.x(), 0, 0, elapsed, 0, 0)
             if max_time is not None and elapsed > max_time:
                 break
+        if still:
+            break
 
 
 def dual_gradient_ascent(x, lp, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None, nb_iter_plot=1):
@@ -553,6 +559,28 @@ class DeviceDGAMany(_DeviceDGA):
         _lib.check(self._l.slp_many_dga_report(self._h, _lib.ptr(out)))
         return out
 
+    def set_stop(self, tol, check_every=1):
+        """Arms the per-LP stopping test of the iteration kernel (``slp_many_dual_set_stop``): at the end of every iteration ``t``
+        of an LP with ``t % check_every == 0`` -- counted from 1 over the LP's life -- the LP stops iff ``max|y_t - y_{t-1}| <=
+        tol`` over all its multipliers (the inequality part after its clamp; a NaN never stops, nor does an LP whose status
+        carries the NaN bit); a stopped LP keeps its multipliers, its x, its tie-draw count and its flags and takes no part in
+        later calls.  ``tol=None`` turns the test off, the state after the constructor.  Unlike ``CPManyState.set_stop`` no call
+        clears a stopped flag: the tie draws behind a stopped LP are dropped, so it cannot be resumed; a new tolerance or
+        cadence applies to the LPs still moving, and with the test off the stopped LPs stay stopped."""
+        if tol is None:
+            tol, check_every = -1.0, 1
+        else:
+            tol, check_every = _many.check_stop(tol, check_every)
+        _lib.check(self._l.slp_many_dual_set_stop(self._h, tol, check_every))
+
+    def stop_state(self):
+        """``(iterations, stopped, step)`` per LP, int64, bool and float64 arrays: the iterations completed (for a stopped LP its
+        stopping iteration, 0 for a frozen one), whether it is stopped and the last evaluated step (``+inf`` before the first
+        test)."""
+        iterations, stopped, step = np.zeros(self.count, dtype=np.int64), np.zeros(self.count, dtype=np.int32), np.zeros(self.count)
+        _lib.check(self._l.slp_many_dual_stop_state(self._h, _lib.ptr(iterations), _lib.ptr(stopped), _lib.ptr(step)))
+        return iterations, stopped.astype(bool), step
+
 
 def dual_gradient_ascent_many(lps, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None):
     """``dual_gradient_ascent`` on every LP of ``lps`` -- LPs whose constraint matrices differ -- all advancing together on the
@@ -571,9 +599,35 @@ def dual_gradient_ascent_many(lps, nb_max_iter=1000, callback_func=None, y_eq=No
     return _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time)[:3]
 
 
-def _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, frozen_out=None):
-    """``dual_gradient_ascent_many`` plus, as a fourth value, the final ``DeviceDGAMany.report()``; ``frozen_out``: a list that
-    receives the frozen flags before the first iteration."""
+def dual_gradient_ascent_many_until(lps, tol, check_every=10, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None):
+    """``dual_gradient_ascent_many`` with a stopping test per LP (extension; the reference runs a fixed number of iterations): the
+    list runs until every LP has stopped or is frozen, at most ``nb_max_iter`` iterations.  Returns ``(xs, y_eqs, y_ineqs, info)``.
+
+    The test is made inside the iteration kernel (``DeviceDGAMany.set_stop``), at the end of every iteration ``t`` of an LP with
+    ``t % check_every == 0``, iterations counted from 1: the LP stops iff ``step_t = max|y_t - y_{t-1}| <= tol`` over all its
+    multipliers ``y_t = [y_eq; y_ineq]`` after ``t`` iterations (the inequality part after its clamp; a kind of rows that does not
+    move contributes 0; a NaN never stops).  A stopped LP keeps its multipliers and the x of the top of iteration ``t``, bit for bit
+    what ``dual_gradient_ascent(None, lps[k], nb_max_iter=t)`` returns, while the others go on.  ``tol`` is a finite float ``>= 0``,
+    ``check_every`` an int ``>= 1``: a ``ValueError`` before the library is loaded otherwise, like every shape error.
+
+    ``info`` is a dict of arrays over the list: ``iterations`` (int64: completed, for a stopped LP its stopping iteration, 0 for a
+    frozen one), ``stopped`` (bool; a frozen LP is not stopped), ``step`` (float64: the last evaluated step, ``+inf`` before the
+    first test) and ``lower_bound`` (float64: the dual energy of the returned multipliers, column 0 of the final report -- a
+    certified lower bound on the LP's value; NaN until the run has ended).
+
+    The cadence of callbacks and of the test of ``max_time`` is that of ``dual_gradient_ascent_many``: ``callback_func(niter, xs,
+    0, 0, elapsed, 0, 0)`` for ``niter % 100 == 0``, where ``xs[k]`` of an LP stopped at or before ``niter`` is its final x.
+    ``info`` is current at every callback: the same dict, updated in place, is set as the ATTRIBUTE ``callback_func.info`` before
+    every call (a function or any object that takes attributes; a bound method takes none)."""
+    stop = _many.check_stop(tol, check_every)
+    xs, y_eqs, y_ineqs, report, info = _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, stop=stop)
+    return xs, y_eqs, y_ineqs, info
+
+
+def _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, frozen_out=None, stop=None):
+    """``dual_gradient_ascent_many`` plus, as a fourth value, the final ``DeviceDGAMany.report()`` and, as a fifth, the ``info`` of
+    ``dual_gradient_ascent_many_until`` (``stop`` the checked ``(tol, check_every)``; None without a stopping test); ``frozen_out``:
+    a list that receives the frozen flags before the first iteration."""
     start = time.perf_counter()
     try:
         lps = list(lps)
@@ -589,8 +643,28 @@ def _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, froze
         frozen = state.frozen()
         if frozen_out is not None:
             frozen_out[:] = frozen.tolist()
-        _dga_drive(state, nb_max_iter, callback_func, max_time, start, all_frozen=frozen.all())
+        info, all_still = None, None
+        if stop is not None:
+            everyone = np.arange(state.count)
+            info = _many.new_stop_info(state.count, everyone)
+            info["lower_bound"] = np.full(state.count, np.nan)
+            state.set_stop(*stop)
+
+            def all_still():
+                _many.spread_stop_state(info, everyone, state.stop_state())
+                if callback_func is not None:
+                    try:
+                        callback_func.info = info
+                    except AttributeError:   # a bound method takes no attribute: wrap it in a function to read ``info``
+                        pass
+                return bool(np.all(info["stopped"] | frozen))
+
+        _dga_drive(state, nb_max_iter, callback_func, max_time, start, all_frozen=frozen.all(), all_still=all_still)
         yes, yis = state.y()
-        return state.x(), yes, [yi if h else None for yi, h in zip(yis, has_ineq)], state.report()
+        report = state.report()
+        if info is not None:
+            _many.spread_stop_state(info, everyone, state.stop_state())
+            info["lower_bound"][:] = report[:, 0]
+        return state.x(), yes, [yi if h else None for yi, h in zip(yis, has_ineq)], report, info
     finally:
         state.close()

@@ -796,10 +796,50 @@ def solve_dga_many(lps, get_timing=True, nb_iter=10000, max_time=None):
     for lp in lps:
         _reset_curves(lp)
     frozen = []   # a frozen LP records nothing: its single solve returns before the first report
-    xs, y_eqs, y_ineqs, report = _dga_many_run(lps, nb_iter, _list_recorder(lps, skip=frozen), None, None, max_time, frozen_out=frozen)
+    xs, y_eqs, y_ineqs, report, _ = _dga_many_run(lps, nb_iter, _list_recorder(lps, skip=frozen), None, None, max_time, frozen_out=frozen)
     for k, lp in enumerate(lps):
         lp.dual_multipliers = (y_eqs[k], y_ineqs[k])
         lp.dual_lower_bound = float(report[k, 0])
+    elapsed = time.perf_counter() - start
+    return (xs, elapsed) if get_timing else xs
+
+
+def solve_dga_many_until(lps, tol, check_every=10, get_timing=True, nb_iter=10000, max_time=None):
+    """``solve_dga_many`` with a stopping test per LP (``DualGradientAscent.dual_gradient_ascent_many_until``): every LP of the list
+    stops on its own at the first iteration ``t`` with ``t % check_every == 0`` whose step ``max|y_t - y_{t-1}|`` over its
+    multipliers is at most ``tol``, the others go on, at most ``nb_iter`` iterations.  Returns the list of ``x``, or ``(xs,
+    elapsed)`` with ``get_timing``; ``tol`` a finite float ``>= 0`` and ``check_every`` an int ``>= 1``, a ``ValueError`` otherwise.
+
+    Sets on every LP ``lp.nb_iterations`` (iterations completed; for a stopped LP its stopping iteration, 0 for an LP whose start
+    is dual infeasible), ``lp.stopped``, ``lp.dual_multipliers = (y_eq, y_ineq)`` and ``lp.dual_lower_bound``, the dual energy of
+    those multipliers: a certified lower bound on that LP's value.  A stopped LP records nothing after it has stopped, so for
+    every LP ``xs[k]`` and every curve apart from the times are bit for bit those of ``lps[k].solve(method=
+    "dual_gradient_ascent", nb_iter=lp.nb_iterations)``.  ``max_time`` stops all LPs at a report."""
+    from .DualGradientAscent import _dga_many_run
+
+    stop = check_stop(tol, check_every)
+    lps = list(lps)
+    if len(lps) < 1:
+        raise ValueError("an empty list of LPs")
+    start = time.perf_counter()
+    for lp in lps:
+        _reset_curves(lp)
+    frozen = []   # a frozen LP records nothing: its single solve returns before the first report
+    skip = np.zeros(len(lps), dtype=bool)
+    fill = _list_recorder(lps, skip=skip)
+
+    def record(niter, *report):
+        # the report of index niter belongs to iteration niter + 1: an LP that stopped before it has no such iteration
+        info = record.info   # current at every callback: the driver sets the attribute
+        skip[:] = np.asarray(frozen, dtype=bool) | (info["stopped"] & (info["iterations"] < niter + 1))
+        fill(niter, *report)
+
+    xs, y_eqs, y_ineqs, _, info = _dga_many_run(lps, nb_iter, record, None, None, max_time, frozen_out=frozen, stop=stop)
+    for k, lp in enumerate(lps):
+        lp.nb_iterations = int(info["iterations"][k])
+        lp.stopped = bool(info["stopped"][k])
+        lp.dual_multipliers = (y_eqs[k], y_ineqs[k])
+        lp.dual_lower_bound = float(info["lower_bound"][k])
     elapsed = time.perf_counter() - start
     return (xs, elapsed) if get_timing else xs
 

@@ -217,6 +217,8 @@ _SIGNATURES = {
     "slp_many_dga_timing": (c_int, [c_vp, c_int]),
     "slp_many_dga_timing_read": (c_int, [c_vp, c_vp]),
     "slp_many_dga_kmax": (c_i64, [c_vp]),
+    "slp_many_dual_set_stop": (c_int, [c_vp, c_dbl, c_i64]),
+    "slp_many_dual_stop_state": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "slp_admm_cg_create_on_two_sided": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int]),
     "slp_admm_cg_create_on_lp": (c_vp, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_dbl, c_int, c_int]),
     "slp_admm_cg_create_lp": (c_vp, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

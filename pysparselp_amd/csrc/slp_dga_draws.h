@@ -61,4 +61,26 @@ struct DgaDrawWindow {
     }
 };
 
+// The two positions the window takes from its readers.  `moves(k)`: reader k still takes draws; `position(k)`: where it stands in
+// the stream.  A reader that stands still for ever (a frozen start; in the list handle also an LP its stopping test has stopped)
+// must not count: as the furthest it would only ask for draws nobody reads, as the hindmost it would hold the front of the window
+// where it stands and the window would grow with every push.
+// observe(): the furthest moving reader, 0 when none moves.
+template <class Moves, class Position>
+inline uint64_t dga_furthest_reader(size_t count, Moves moves, Position position) {
+    uint64_t mx = 0;
+    for (size_t k = 0; k < count; ++k)
+        if (moves(k)) mx = std::max<uint64_t>(mx, position(k));
+    return mx;
+}
+
+// push(): what every moving reader has passed, ~0 when none moves.
+template <class Moves, class Position>
+inline uint64_t dga_passed_by_all(size_t count, Moves moves, Position position) {
+    uint64_t passed = ~(uint64_t)0;
+    for (size_t k = 0; k < count; ++k)
+        if (moves(k)) passed = std::min<uint64_t>(passed, position(k));
+    return passed;
+}
+
 }  // namespace slp

@@ -32,6 +32,27 @@
 // Tie draws: all LPs read the one stream of uniform draws, LP k at its own position draw_offset_k + consumed_k (draw_offset_k: the
 // draws its default start took).  The device holds a window of the stream from the smallest position on.
 // Report, frozen test and start are ordinary launches over (kDgaParts, count) with the shared energy bodies.
+//
+// Stopping (slp_many_dual_set_stop; off after create).  DgmStop, one per LP in device memory, in an array of its own beside DgaCtl
+// (whose layout the single and the batched solver share): iterations completed, the last evaluated step, the stopped flag.
+// Iterations of an LP count from 1 over its whole life; y_t = [y_eq; y_ineq] are its multipliers after iteration t, the inequality
+// part after its clamp.  step_t = max_r |y_t,r - y_{t-1},r| over all its rows, as np.max (a NaN stays); a kind of rows that does not
+// move in iteration t (block predicate false) contributes 0.  At the end of an iteration t with t % check_every == 0 the LP stops
+// iff step_t <= tol -- and its sticky NaN bit is down: an LP that has met a NaN breakpoint or step certifies nothing, it runs on.
+// The maximum is exact in any order, so the decision is that of a numpy restatement.  The test is the template parameter STOP of
+// k_dgm_iterate: STOP = false is the kernel without it, statement by statement, and touches no record (the host counts its
+// iterations).  With STOP only a check iteration accumulates anything, in an update loop of its own per kind: a lane the fabs over
+// its rows; behind the barrier of the last kind a wave reduces by shuffles into one of the 16 reduction slots, a barrier, lane 0
+// folds the slots and writes the step, the count and the flag with ordinary stores, a barrier, and every lane reads the flag with
+// a workgroup-scope load: the break is uniform, and so is every barrier.  A stopped LP's workgroup returns before its first
+// barrier, as a frozen one (the flag was written by an earlier launch, or behind the barrier before the break: the same for every
+// lane); its y, its x (the dual argmin at the top of its last iteration), its tie-draw count and its flags are never written
+// again.  The count is read from the record at the start of a launch, so the stopping iteration does not depend on how a run is
+// split into calls and launches.
+// A stopped LP stands still for ever, so it is no reader of the stream of draws (slp_dga_draws.h): the front of the window moves on
+// without it, and the draws behind its position may be gone.  Hence it cannot be resumed: unlike slp_many_cp_set_stop, no call of
+// slp_many_dual_set_stop clears a stopped flag.  While an LP is stopped and the test is off, the launch is the kernel with the test
+// and a cadence that never comes, so that the LP stays where it is.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -63,6 +84,19 @@ struct DgmArgs {
     DgaCtl *ctl;
     const double *rnd;
     unsigned long long rnd_base, rnd_count;
+};
+
+// per LP, in device memory; written by lane 0 of the LP's workgroup (STOP) and by the host between launches
+struct DgmStop {
+    i64 done;       // whole iterations completed (the kernel without the test does not count: slp_many_dga::uncounted)
+    double step;    // the last evaluated max |y_t - y_{t-1}|, +inf before the first test
+    i32 stopped, pad;
+};
+
+struct DgmStopArgs {
+    DgmStop *rec;
+    double tol;
+    i64 check_every;
 };
 
 // column j of the LP: the two masked sums of K^T y in storage order (k_dgab_cols), c_bar and the dual argmin
@@ -105,13 +139,21 @@ __device__ __forceinline__ double dgm_dot(i64 s, i64 e, const i32 *idx, const do
     return acc;
 }
 
-// `iters` iterations of the LP blockIdx.x
-__global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int iters) {
+// `iters` iterations of the LP blockIdx.x.  STOP: the stopping test of the header comment; `sp` is not looked at without it.
+template <bool STOP>
+__global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int iters, DgmStopArgs sp) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dgm_lds[];
     const DgaLoadWorkgroup ld;
     const DgmLp lp = a.lps[blockIdx.x];
     DgaCtl *ctl = a.ctl + blockIdx.x;
     if (ctl->frozen) return;   // set before the launch: the same for every lane
+    i64 done = 0, until = 0;   // STOP: iterations completed; iterations up to and including the next check
+    if (STOP) {
+        const DgmStop *rec = sp.rec + blockIdx.x;
+        if (rec->stopped) return;   // set before the launch: the same for every lane
+        done = rec->done;           // lane 0 writes the record only behind a barrier that follows this load
+        until = sp.check_every - done % sp.check_every;
+    }
     const i32 n = lp.n, m = lp.m_eq + lp.m_in, tid = (i32)threadIdx.x, group = tid >> 8, tl = tid & (kBlock - 1);
     double *slots = reinterpret_cast<double *>(dgm_lds) + 4 * group;
     unsigned char *search_lds = dgm_lds + kDgmSlotBytes;
@@ -135,6 +177,8 @@ __global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int
     const i32 tiles = (m + kBlock - 1) / kBlock, per = (tiles + kDgaParts - 1) / kDgaParts;
     const i32 rounds = ((tiles + per - 1) / per + 3) / 4;
     for (int it = 0; it < iters; ++it) {
+        const bool check = STOP && until == 1;   // uniform: a function of the record and of `it`
+        double dy = 0.0;                         // STOP: a lane's max |y_new - y_old| of a check iteration; 0.0 from a kind that stands
         for (i32 j = tid; j < n; j += kDgaFusedThreads) dgm_column(lp, j, tptr, a.tidx, a.tval, y, c, lb, ub, cbar, x, ld);
         __syncthreads();   // same compute unit: the stores of a stage are visible to the next one
         for (i32 i = tid; i < m; i += kDgaFusedThreads) ax[i] = dgm_dot(ptr[i], ptr[i + 1], a.idx, a.val, x, ld);
@@ -159,10 +203,42 @@ __global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int
             dga_fused_body(n, lp.npad, d, cbar, lb, ub, ctl, rnd, rnd_base, rnd_count, ineq, search_lds, ld);
             __syncthreads();
             const double t = ld(&ctl->t);
-            for (i32 i = r0 + tid; i < r1; i += kDgaFusedThreads) y[i] = dga_update_y(ld(y + i), t, ld(g + i), ineq);
+            if (check) {   // a loop of its own: the other one stays the loop of the kernel without the test
+                for (i32 i = r0 + tid; i < r1; i += kDgaFusedThreads) {
+                    const double yo = ld(y + i), yn = dga_update_y(yo, t, ld(g + i), ineq);
+                    y[i] = yn;
+                    dy = many_nanmax(dy, fabs(yn - yo));
+                }
+            } else {
+                for (i32 i = r0 + tid; i < r1; i += kDgaFusedThreads) y[i] = dga_update_y(ld(y + i), t, ld(g + i), ineq);
+            }
             __syncthreads();
         }
+        if (STOP) {   // here an iteration is complete; the last use of the slots lies behind a barrier
+            ++done;
+            if (!check) {
+                --until;
+                continue;
+            }
+            until = sp.check_every;
+            DgmStop *rec = sp.rec + blockIdx.x;
+            double *red = reinterpret_cast<double *>(dgm_lds);   // the 16 reduction slots: one per wave
+            dy = many_wave_nanmax(dy);
+            if ((tid & (kWave - 1)) == 0) red[tid / kWave] = dy;
+            __syncthreads();
+            if (tid == 0) {
+                double step = red[0];
+                for (int w = 1; w < kDgaFusedThreads / kWave; ++w) step = many_nanmax(step, red[w]);
+                const int stop = (step <= sp.tol && !(ctl->flags & DGA_NAN)) ? 1 : 0;   // false for a NaN
+                rec->step = step;
+                rec->done = done;
+                rec->stopped = stop;
+            }
+            __syncthreads();   // the two barriers the test adds, in a check iteration only
+            if (ld(&rec->stopped)) break;   // read by all lanes after the barrier: uniform
+        }
     }
+    if (STOP && tid == 0) sp.rec[blockIdx.x].done = done;
 }
 
 // ---- start, frozen test and report: ordinary launches over (.., count) --------------------------------------------------------
@@ -212,6 +288,12 @@ struct slp_many_dga {
     DgaDrawWindow draws;   // the host's view of rnd (slp_dga_draws.h)
     i64 iters = 0;
     StageTimer timer;
+    // stopping: off while tol < 0.  The kernel without the test touches no record, so the iterations it runs are counted here and
+    // added to the record of every moving LP when the test is armed (and when the state is read)
+    DevBuf<DgmStop> stop;
+    double tol = -1.0;
+    i64 check_every = 1, uncounted = 0;
+    bool any_stopped = false;   // from now on every launch is the kernel with the test: a stopped LP stays where it is
 };
 
 namespace {
@@ -279,14 +361,26 @@ void dgm_report(slp_many_dga *s, double *out) {
     for (size_t k = 0; k < sc; ++k) dga_report_finish(h.data() + k * 4 * kDgaParts, true, out + 3 * k);
 }
 
-// the controls of all LPs; refreshes the bound on the positions in the stream of draws
-void dgm_read_ctl(slp_many_dga *s, std::vector<DgaCtl> &h) {
+// the controls of all LPs and, in `r` if given, their stop records with the iterations of the launches without the test added;
+// refreshes the bound on the positions in the stream of draws.  A frozen LP and a stopped one stand still: no readers of the stream.
+void dgm_read_ctl(slp_many_dga *s, std::vector<DgaCtl> &h, std::vector<DgmStop> *r = nullptr) {
     h.resize((size_t)s->count);
     s->ctl.download(h.data(), (size_t)s->count);
-    unsigned long long mx = 0;
+    std::vector<DgmStop> own;
+    std::vector<DgmStop> &rec = r ? *r : own;
+    rec.resize((size_t)s->count);
+    s->stop.download(rec.data(), (size_t)s->count);
+    for (size_t k = 0; k < rec.size(); ++k)
+        if (!h[k].frozen && !rec[k].stopped) rec[k].done += s->uncounted;
+    s->draws.observe(dga_furthest_reader(
+        h.size(), [&](size_t k) { return !h[k].frozen && !rec[k].stopped; },
+        [&](size_t k) { return (uint64_t)(s->lps[k].draw_offset + h[k].consumed); }));
+}
+
+bool dgm_any_moves(const std::vector<DgaCtl> &h, const std::vector<DgmStop> &rec) {
     for (size_t k = 0; k < h.size(); ++k)
-        if (!h[k].frozen) mx = std::max(mx, s->lps[k].draw_offset + h[k].consumed);
-    s->draws.observe(mx);
+        if (!h[k].frozen && !rec[k].stopped) return true;
+    return false;
 }
 
 }  // namespace
@@ -341,7 +435,7 @@ slp_many_dga *slp_many_dga_create(int64_t count, const int64_t *n, const int64_t
         // two), seven over the rows, per LP the table, the controls and the partial results of the pass and of the report
         many_require_memory("slp_many_dga_create", count,
                             24.0 * (double)nnz + 8.0 * (double)(N + M + 2) + 8.0 * (8.0 * (double)N + 7.0 * (double)M) +
-                                (double)count * (double)(sizeof(DgmLp) + sizeof(DgaCtl) + 8.0 * 7.0 * kDgaParts));
+                                (double)count * (double)(sizeof(DgmLp) + sizeof(DgaCtl) + sizeof(DgmStop) + 8.0 * 7.0 * kDgaParts));
         // K_k^T on the host: a counting transposition per LP walks its rows in order, so rows increase inside a column
         std::vector<i64> tptr((size_t)N + 1, 0);
         std::vector<i32> tidx((size_t)nnz);
@@ -375,8 +469,12 @@ slp_many_dga *slp_many_dga_create(int64_t count, const int64_t *n, const int64_t
         s->rnd.alloc(1);
         s->ctl.alloc(sc);
         s->ctl.zero();
-        SLP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dgm_iterate), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(kDgmSlotBytes + fused_lds_bytes(kDgaFusedMax))));
+        for (const void *kernel : {reinterpret_cast<const void *>(k_dgm_iterate<false>), reinterpret_cast<const void *>(k_dgm_iterate<true>)})
+            SLP_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kDgmSlotBytes + fused_lds_bytes(kDgaFusedMax))));
+        {
+            const std::vector<DgmStop> rec(sc, DgmStop{0, __builtin_inf(), 0, 0});
+            s->stop.upload(rec.data(), sc);
+        }
         dgm_argmin(s.get(), s->cbar.p, s->x.p);   // the x of y0: what a frozen LP keeps
         // a start whose dual energy is -inf freezes its LP (the single solve returns at once, :133-139)
         std::vector<double> rep(3 * sc);
@@ -398,14 +496,26 @@ int slp_many_dga_iterate(slp_many_dga *s, int64_t k) {
     SLP_API_INT({
         SLP_REQUIRE(s && k >= 0, "slp_many_dga_iterate: bad arguments");
         hipStream_t st = ctx().stream;
+        // with the test: armed, or off with an LP that has to stay stopped (a cadence that never comes)
+        const bool stop = s->tol >= 0.0 || s->any_stopped;
+        const DgmStopArgs sp = {s->stop.p, s->tol, s->tol >= 0.0 ? s->check_every : INT64_MAX};
+        if (stop) {   // when every LP is stopped or frozen nothing is launched and the count of iterations stays
+            std::vector<DgaCtl> h;
+            std::vector<DgmStop> rec;
+            dgm_read_ctl(s, h, &rec);
+            if (!dgm_any_moves(h, rec)) return 0;
+        }
         many_split(k, s->kmax, [&](int want) {
             // at most two tie draws per LP and iteration: iterations the buffer cannot run dry in
             const int it = (int)s->draws.reserve(want);
             if (it < 1) return it;
+            const dim3 grid((unsigned)s->count), block(kDgaFusedThreads);
             s->timer.mark(-1);
-            hipLaunchKernelGGL(k_dgm_iterate, dim3((unsigned)s->count), dim3(kDgaFusedThreads), dgm_lds_bytes(s), st, dgm_args(s), it);
+            if (stop) hipLaunchKernelGGL(k_dgm_iterate<true>, grid, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp);
+            else hipLaunchKernelGGL(k_dgm_iterate<false>, grid, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp);
             s->timer.mark(ST_FUSED);
             s->iters += it;
+            if (!stop) s->uncounted += it;
             return it;
         });
     })
@@ -415,9 +525,11 @@ int slp_many_dga_push_random(slp_many_dga *s, const double *draws, int64_t count
     SLP_API_INT({
         SLP_REQUIRE(s && count >= 0 && (draws || count == 0), "slp_many_dga_push_random: bad arguments");
         std::vector<DgaCtl> h;
-        dgm_read_ctl(s, h);
+        std::vector<DgmStop> rec;
+        dgm_read_ctl(s, h, &rec);
         // (an LP never reaches what lies before its offset: the start of the stream went into the default starts)
-        dga_push_draws(h, [s](size_t k) { return s->lps[k].draw_offset; }, s->draws, s->rnd, draws, count, kAppendFirst);
+        dga_push_draws(h, [s](size_t k) { return s->lps[k].draw_offset; }, [&](size_t k) { return !h[k].frozen && !rec[k].stopped; }, s->draws,
+                       s->rnd, draws, count, kAppendFirst);
     })
 }
 
@@ -447,6 +559,37 @@ int slp_many_dga_report(slp_many_dga *s, double *out) {
     SLP_API_INT({
         SLP_REQUIRE(s && out, "slp_many_dga_report: NULL argument");
         dgm_report(s, out);
+    })
+}
+
+int slp_many_dual_set_stop(slp_many_dga *s, double tol, int64_t check_every) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_dual_set_stop: NULL handle");
+        SLP_REQUIRE(tol < 0.0 || (std::isfinite(tol) && check_every >= 1),
+                    "slp_many_dual_set_stop: tol must be finite and >= 0 with check_every >= 1 (tol < 0 turns the test off)");
+        std::vector<DgaCtl> h;
+        std::vector<DgmStop> rec;
+        dgm_read_ctl(s, h, &rec);   // synchronises; the iterations of the launches without the test are in the records now
+        s->stop.upload(rec.data(), rec.size());
+        s->uncounted = 0;
+        s->any_stopped = false;
+        for (const DgmStop &r : rec) s->any_stopped = s->any_stopped || r.stopped;   // the flags stay: a stopped LP cannot be resumed
+        s->tol = tol < 0.0 ? -1.0 : tol;
+        if (tol >= 0.0) s->check_every = check_every;
+    })
+}
+
+int slp_many_dual_stop_state(slp_many_dga *s, int64_t *iterations, int32_t *stopped, double *step) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_dual_stop_state: NULL handle");
+        std::vector<DgaCtl> h;
+        std::vector<DgmStop> rec;
+        dgm_read_ctl(s, h, &rec);
+        for (size_t k = 0; k < rec.size(); ++k) {
+            if (iterations) iterations[k] = rec[k].done;   // 0 for a frozen LP: its workgroup returns before it counts
+            if (stopped) stopped[k] = rec[k].stopped;
+            if (step) step[k] = rec[k].step;
+        }
     })
 }
 

@@ -602,15 +602,21 @@ inline void dga_frozen_out(const std::vector<DgaCtl> &h, int32_t *out) {
     for (size_t k = 0; k < h.size(); ++k) out[k] = h[k].frozen;
 }
 
-// what push_random does once the controls are read: `offset(k)` is where reader k's positions begin in the stream
+// what push_random does once the controls are read: `offset(k)` is where reader k's positions begin in the stream, `moves(k)`
+// whether it still takes draws (dga_passed_by_all: the draws every moving reader has passed are dropped from the front)
+template <class Offset, class Moves>
+inline void dga_push_draws(const std::vector<DgaCtl> &h, Offset offset, Moves moves, DgaDrawWindow &w, DevBuf<double> &rnd,
+                           const double *draws, int64_t count, DgaOverrun mode) {
+    const uint64_t passed = dga_passed_by_all(h.size(), moves, [&](size_t k) { return (uint64_t)(offset(k) + h[k].consumed); });
+    w.push(draws, count, passed, mode);
+    if (w.size()) rnd.upload(w.data(), (size_t)w.size());
+}
+
+// the same with the readers of the batch: every instance that is not frozen moves
 template <class Offset>
 inline void dga_push_draws(const std::vector<DgaCtl> &h, Offset offset, DgaDrawWindow &w, DevBuf<double> &rnd, const double *draws,
                            int64_t count, DgaOverrun mode) {
-    unsigned long long passed = ~0ull;   // the draws every moving reader has passed are dropped from the front
-    for (size_t k = 0; k < h.size(); ++k)
-        if (!h[k].frozen) passed = std::min(passed, offset(k) + h[k].consumed);
-    w.push(draws, count, passed, mode);
-    if (w.size()) rnd.upload(w.data(), (size_t)w.size());
+    dga_push_draws(h, offset, [&](size_t k) { return !h[k].frozen; }, w, rnd, draws, count, mode);
 }
 
 }  // namespace slp

@@ -11,10 +11,13 @@ more than 64 entries, one- / two-sided / mixed rows, infinite and equal bounds, 
 ``stop_state``, ``chambolle_pock_ppd_many_until`` / ``lp_admm_many_until``): the tolerances are the reference step (and residual) of
 one LP of the list at a check iteration, so that ``<=`` decides by equality; the stopping iterations, flags, steps and residuals
 against the numpy restatements (tests/cp_stop_cpu.py, tests/admm_stop_cpu.py) and every LP's frozen iterate against the oracle's
-at that LP's own count, bit for bit.
+at that LP's own count, bit for bit.  ``dga_many_stop`` does the same for dual gradient ascent on a list (``DeviceDGAMany.set_stop``
+/ ``stop_state``, ``dual_gradient_ascent_many_until``) on the lists of ``dga_many``, against tests/dga_stop_cpu.py on dga_cpu's
+states; an LP whose stop (or whose last iteration) lies behind its parity horizon is run but not compared, and such LPs are at
+most a quarter of a run.
 
     python tools/fuzz_batched.py [--cases 24] [--seed 0]
-        [--family cp_batch,cp_many,admm_batch,admm_many,dga,dga_batch,dga_many,cp_many_stop,admm_many_stop]
+        [--family cp_batch,cp_many,admm_batch,admm_many,dga,dga_batch,dga_many,cp_many_stop,admm_many_stop,dga_many_stop]
 
 The generators and the CPU references need no GPU (tests/test_fuzz_batched_host.py checks on them that the GPU runs compare what
 they claim to); the ``run_*`` functions need one."""
@@ -45,6 +48,11 @@ DGA_STOPS = (0, 9, DGA_ITERS - 1)
 STATUS_BITS = {"negative step": 1, "empty breakpoint set": 2, "never changes sign": 16}
 STOP_EXTRA, STOP_EVERY = 20, (1, 3, 10)   # a stopping list runs 20 iterations longer than its list; the cadences of the test
 CP_STOP_OFFSET, ADMM_STOP_OFFSET = 8000, 7000   # the stopping draws' generators: RandomState(seed + offset)
+# the same for the dual-ascent lists, which run their DGA_ITERS iterations.  The offset: 6000 was tried first and leaves 138 of the
+# 368 LPs of TEST_SEED / TEST_CASES out (the 260-LP list draws cadence 10 there, and a third of its LPs have a parity horizon of one
+# iteration); 6027 is the smallest offset from there on that satisfies DGA_STOP_LEFT_OUT on the CPU (51 of 368 left out)
+DGA_STOP_OFFSET, DGA_STOP_EVERY = 6027, (1, 2, 5, 10)
+DGA_STOP_LEFT_OUT = 0.25   # the largest share of the LPs of a run that may lie behind their parity horizon (not compared)
 STOP_AFTER_OFFSET = 500   # on top of them: the generator of ``after``, so that the test's own draws do not depend on it
 TEST_SEED, TEST_CASES = 20, 24   # what tests/test_gpu_fuzz_batched.py runs and tests/test_fuzz_batched_host.py checks
 
@@ -518,6 +526,73 @@ def dga_lists(cases, seed):
             lps = [lps[k % len(lps)] for k in range(LONG_LIST)]
         lists.append(lps)
     return lists
+
+
+class DgaStopCase:
+    """One list of ``dga_lists`` with the tolerance and the cadence of its stopping test, and per LP the restatement:
+
+    ``steps[k]``     ``step_t`` of LP ``k`` for the iterations inside its parity horizon (``horizon + 1`` of them: there dga_cpu's
+                     reference order is the device's bit for bit, and dga_cpu has not raised);
+    ``want[k]``      ``(iterations, stopped, step)`` as ``stop_state`` must report them after ``DGA_ITERS`` iterations, or None
+                     for an LP that is left out: it neither stops inside its horizon nor has a horizon that covers the run, so
+                     where it stops is not known from the CPU;
+    ``source``       ``(k, t)``: the tolerance is ``steps[k][t - 1]``, ``t`` a check iteration -- ``<=`` decides by equality there."""
+
+    def __init__(self, lps, rng):
+        import dga_stop_cpu
+
+        self.lps = lps
+        self.steps = [dga_stop_cpu.steps_of({it: lp.states[it] for it in range(-1, lp.horizon + 1)}) for lp in lps]
+        self.every = int(DGA_STOP_EVERY[rng.randint(len(DGA_STOP_EVERY))])
+        able = [k for k, s in enumerate(self.steps) if s.size >= 1]
+        if able and not any(self.steps[k].size >= self.every for k in able):
+            self.every = 1
+        able = [k for k in able if self.steps[k].size >= self.every]
+        self.source, self.tol = None, 1e-2
+        if able:
+            k = able[int(rng.randint(len(able)))]
+            t = self.every * int(rng.randint(1, self.steps[k].size // self.every + 1))
+            if np.isfinite(self.steps[k][t - 1]):
+                self.source, self.tol = (k, t), float(self.steps[k][t - 1])
+        self.want = []
+        for lp, steps in zip(lps, self.steps):
+            t = dga_stop_cpu.stopping_iteration(steps, self.tol, self.every)
+            if t is None and steps.size < DGA_ITERS:
+                self.want.append(None)
+            else:
+                self.want.append(dga_stop_cpu.stop_state(steps, self.tol, self.every, DGA_ITERS))
+
+    def compared(self):
+        return [k for k, w in enumerate(self.want) if w is not None]
+
+
+_DGA_STOP_CASES = {}
+
+
+def dga_stop_cases(cases, seed):
+    """``[DgaStopCase, ...]`` on the lists of ``dga_lists``; the draws of list ``case`` come from ``RandomState(seed +
+    DGA_STOP_OFFSET + case)``, so that a list's test does not depend on the lists before it."""
+    key = (cases, seed)
+    if key not in _DGA_STOP_CASES:
+        _DGA_STOP_CASES[key] = [DgaStopCase(lps, np.random.RandomState(seed + DGA_STOP_OFFSET + case))
+                                for case, lps in enumerate(dga_lists(cases, seed))]
+    return _DGA_STOP_CASES[key]
+
+
+def dga_stop_statistics(cases, seed):
+    """``dict(lps, left_out, stopped, running, lists_with_both, by_equality, longest)`` over the LPs of ``dga_stop_cases`` -- what
+    tests/test_fuzz_dga_stop_host.py asserts on and ``run_dga_many_stop`` asserts its cap with."""
+    out = dict(lps=0, left_out=0, stopped=0, running=0, lists_with_both=0, by_equality=0, longest=0)
+    for case in dga_stop_cases(cases, seed):
+        known = [w for w in case.want if w is not None]
+        out["lps"] += len(case.lps)
+        out["left_out"] += len(case.lps) - len(known)
+        out["stopped"] += sum(bool(w[1]) for w in known)
+        out["running"] += sum(not w[1] for w in known)
+        out["lists_with_both"] += any(w[1] for w in known) and any(not w[1] for w in known)
+        out["by_equality"] += case.source is not None and case.want[case.source[0]] is not None and case.want[case.source[0]][2] == case.tol
+        out["longest"] = max(out["longest"], len(case.lps))
+    return out
 
 
 def dga_statistics(cases, seed):
@@ -1352,8 +1427,61 @@ def run_dga_many(cases, seed):
     return counts
 
 
+def run_dga_many_stop(cases, seed):
+    """``DeviceDGAMany.set_stop`` / ``stop_state`` and ``dual_gradient_ascent_many_until`` on the lists of ``run_dga_many``, armed from
+    creation, with the launch length chosen by the library and with one iteration per launch: ``stop_state`` of every compared LP
+    with ``==`` against the restatement, its x, y, tie draws and flags against dga_cpu at that LP's own count, its report against
+    ``DeviceDGA`` alone where the single solver's walk has that count.  The LPs left out (``DgaStopCase``) are run, not compared;
+    their share is asserted.  Returns counts."""
+    from pysparselp_amd import dual_gradient_ascent_many_until
+
+    stats = dga_stop_statistics(cases, seed)
+    _require(stats["left_out"] <= DGA_STOP_LEFT_OUT * stats["lps"],
+             f"dga_many_stop seed {seed}: {stats['left_out']} of {stats['lps']} LPs lie behind their parity horizon, more than a quarter")
+    counts = dict(lists=0, runs=0, lps=0, compared=0, left_out=0, stopped=0, running=0, drivers=0, longest=0)
+    for no, case in enumerate(dga_stop_cases(cases, seed)):
+        lps, known = case.lps, case.compared()
+        for setting, kmax in (("default", None), ("kmax1", 1)):
+            with many_state(lps, kmax) as state:
+                state.set_stop(case.tol, case.every)
+                for p in _pieces(DGA_ITERS):
+                    state.iterate(p)
+                got, snap = state.stop_state(), _snapshot(state)
+            for k in known:
+                lp, want = lps[k], case.want[k]
+                where = (f"dga_many_stop seed {seed} list {no} LP {k} of {len(lps)} ({lp.name}), setting {setting}, tol {case.tol!r} "
+                         f"(from {case.source}), every {case.every}")
+                mine = (int(got[0][k]), bool(got[1][k]), float(got[2][k]))
+                _require(mine == (int(want[0]), bool(want[1]), float(want[2])), where + f": stop_state {mine} != {tuple(want)}",
+                         _dga_single_agrees(lp, "fused"))
+                _require(int(snap[4][k]) == 0, where + f": status flags {int(snap[4][k])}")
+                bad = _instance_equals(snap, k, lp.states[int(want[0]) - 1])
+                _require(not bad, where + f": {', '.join(bad)} differ from dga_cpu after {int(want[0])} iterations", _dga_single_agrees(lp, "fused"))
+            counts["runs"] += 1
+        if all(lp.clean and lp.device_fail is None for lp in lps):   # the driver checks the status of every LP after every call
+            xs, y_eqs, _, info = dual_gradient_ascent_many_until([_LP(*lp.args) for lp in lps], case.tol, case.every, nb_max_iter=DGA_ITERS)
+            for k in known:
+                want = case.want[k]
+                where = f"dga_many_stop seed {seed} list {no} LP {k} ({lps[k].name}), dual_gradient_ascent_many_until"
+                mine = (int(info["iterations"][k]), bool(info["stopped"][k]), float(info["step"][k]))
+                _require(mine == (int(want[0]), bool(want[1]), float(want[2])), where + f": info {mine} != {tuple(want)}")
+                ref = lps[k].states[int(want[0]) - 1]
+                _require(np.array_equal(xs[k], ref[0]) and np.array_equal(y_eqs[k], ref[1]), where + ": x or y_eq differ from dga_cpu")
+            counts["drivers"] += 1
+        counts["lists"] += 1
+        counts["lps"] += len(lps)
+        counts["compared"] += len(known)
+        counts["left_out"] += len(lps) - len(known)
+        counts["stopped"] += sum(bool(case.want[k][1]) for k in known)
+        counts["running"] += sum(not case.want[k][1] for k in known)
+        counts["longest"] = max(counts["longest"], len(lps))
+    _require(counts["left_out"] <= DGA_STOP_LEFT_OUT * counts["lps"], f"dga_many_stop seed {seed}: {counts['left_out']} of {counts['lps']} LPs left out")
+    return counts
+
+
 FAMILIES = {"cp_batch": run_cp_batch, "cp_many": run_cp_many, "admm_batch": run_admm_batch, "admm_many": run_admm_many, "dga": run_dga,
-            "dga_batch": run_dga_batch, "dga_many": run_dga_many, "cp_many_stop": run_cp_many_stop, "admm_many_stop": run_admm_many_stop}
+            "dga_batch": run_dga_batch, "dga_many": run_dga_many, "cp_many_stop": run_cp_many_stop, "admm_many_stop": run_admm_many_stop,
+            "dga_many_stop": run_dga_many_stop}
 
 
 def main():
