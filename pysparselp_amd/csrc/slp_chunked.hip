@@ -105,6 +105,12 @@ int slp_matrix_chunked_append(slp_matrix *g, slp_matrix *c) {
                 c->tall_block_multiple = ctx().num_cu / a;
             }
         }
+        // The first chunk settles the tall-cell geometry of the chunked matrix -- strip width, capacity of the value table, the row
+        // blocks of all chunks together (A) or the rows per block (A^T) -- and every later chunk builds with it: one launch over all
+        // chunks needs one LDS layout.  (A later chunk whose dictionary outgrows the capacity takes the whole table; the composite
+        // then runs chunk by chunk, tall_fuse.)
+        if (!c->tried_fa && !c->tried_fat)
+            for (int t = 0; t < 2; ++t) c->tall_carry[t] = g->tall_carry[t];
         // both product copies straight from the chunk's CSR
         const StripJds *f0 = fast_format(c, false), *f1 = fast_format(c, true);
         SLP_REQUIRE(f0 && f1, "slp_matrix_chunked_append: the chunk does not qualify for strip copies in both orientations (too small or "
@@ -113,6 +119,15 @@ int slp_matrix_chunked_append(slp_matrix *g, slp_matrix *c) {
             c->rowsq.alloc(2 * (size_t)c->a.nrow);
             matrix_row_squares(c->a, c->rowsq.p);
         }
+        if (g->chunks.empty())
+            for (int t = 0; t < 2; ++t) {
+                const StripJds *f = t ? f1 : f0;
+                if (f->tall && f->S == 1) {
+                    g->tall_carry[t].C = f->C; g->tall_carry[t].dcap = f->D > 0 ? f->tall_dcap : -1;
+                    g->tall_carry[t].R = f->tall_R; g->tall_carry[t].total = f->tall_total;
+                }
+            }
+        if (f0->tall) g->tall_carry[0].blocks += f0->B;   // (the next chunk of A takes what brings these up to the cumulative share)
         SLP_REQUIRE(slp_matrix_release_csr(c) == 0, slp_last_error());
         c->a.ptr.release();   // (a plain release keeps the row pointers for diagnostics; a chunk needs nothing of them)
         c->at.ptr.release();
@@ -162,6 +177,19 @@ int64_t slp_matrix_strip_width(slp_matrix *m, int transposed) {
         })
     }();
     return rc == 0 ? c : -1;
+}
+
+int64_t slp_matrix_tall_rows(slp_matrix *m, int transposed) {
+    if (!m) return -1;
+    int64_t r = 0;
+    const int rc = [&]() -> int {
+        SLP_API_INT({
+            const StripJds *f = fast_format(m, transposed != 0);
+            if (f && !m->chunks.empty() && !f->parts.empty()) f = f->parts[0];
+            r = (f && f->ok && f->tall) ? (int64_t)f->tall_R : 0;
+        })
+    }();
+    return rc == 0 ? r : -1;
 }
 
 int64_t slp_matrix_product_launches(const slp_matrix *g, int transposed) {

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/slp_hip.h"
+#include "slp_tall_plan.h"
 
 // Kernel-lab switches never reach libslp_hip.so.  Timing experiments with parts of a kernel removed (WRONG results by design)
 // exist only behind -DSLP_ABLATION (`make ablation` / `make variant`, separate objects, a library of its own that
@@ -260,9 +261,11 @@ struct StripJds {
     int rpl = 2;                  // sorted positions per lane: 2 (pairs, 2048-row blocks) or 4 (quads, 4096-row blocks)
     DevBuf<unsigned short> ent;   // [2 * nnz]
     const double *dict = nullptr; // [D] sorted distinct values (owned by the slp_matrix)
-    // tall cells (slp_tall.hip): row blocks of tall_R rows x strips of 4096 columns, packets of <= 1024 non-empty rows
+    // tall cells (slp_tall.hip): row blocks of tall_R rows x strips of C columns, packets of <= 1024 non-empty rows
     bool tall = false;
     int tall_R = 0;
+    int tall_dcap = 0;                               // capacity of the value table in the product kernel's LDS (slp_tall_plan.h)
+    i64 tall_total = 0;                              // a chunk that took its share of the row blocks of its chunked matrix: all of them
     DevBuf<TallWg> tall_wg;                          // [B * S] where every workgroup's packet stream lies
     std::vector<DevBuf<unsigned int>> tall_dir;      // 32-byte packet headers, one buffer per build pass
     std::vector<DevBuf<unsigned int>> tall_pay;      // payload words, one buffer per build pass
@@ -274,7 +277,6 @@ struct StripJds {
     bool parts_cols = false;          // the copy of A^T: the chunks cut its COLUMNS (x is sliced, the sums of a row continue)
     bool fused = false;               // tall_wg holds ONE descriptor table over all parts: a product is a single launch (tall_fuse)
 };
-constexpr int kTallRmax = 9984;       // most rows of a tall-cell row block (their running sums: 78 KB of LDS)
 // sorted distinct stored values of a matrix, when there are at most kDictMax of them
 struct ValueDict {
     int state = -1;                       // -1 not looked at, 0 too many distinct values, 1 available
@@ -300,8 +302,14 @@ void strip_spmv_abs_pow(const StripJds &f, double pw, const double *x, double *o
 // long rows that are sparse inside every LDS-sized window (slp_tall.hip); transposed: the question / the copy for A^T, taken
 // straight from the CSR of A (no transposed CSR is ever formed)
 bool tall_wanted(i64 nrow, i64 ncol, i64 nnz);
+// rows_total > 0: the chunk's share of the row blocks of a chunked matrix; carry: what the first chunk decided (slp_tall_plan.h)
+struct TallCarry {
+    int C = 0, dcap = -1, R = 0;
+    i64 total = 0;
+    i64 blocks = 0;   // row blocks of the chunks so far (A: the next chunk's share is counted from them)
+};
 bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *dict, i64 block_multiple = 0, i64 rows_before = 0,
-                i64 rows_total = 0);   // rows_total > 0: the chunk's share of the row blocks of a chunked matrix (tall_geometry)
+                i64 rows_total = 0, const TallCarry *carry = nullptr);
 void tall_spmv(const StripJds &f, const double *x, double *out, int accum);
 bool tall_fuse(StripJds &composite);                                          // one descriptor table over all chunks' copies, if they allow it
 void tall_spmv_fused(const StripJds &composite, const double *x, double *out);  // the whole product of a fused composite in ONE launch
@@ -332,6 +340,8 @@ struct slp_matrix {
     slp::i64 tall_block_multiple = 0;      // a chunk about to join a chunked matrix of K chunks: row blocks in multiples of CUs / gcd(CUs, K)
     slp::i64 tall_rows_before = 0, tall_rows_total = 0;   // ... or, when the chunked matrix knows its row count: the chunk's share of its row blocks
     slp::i64 expect_rows = 0;              // slp_matrix_chunked_expect_rows: rows of the whole chunked matrix (0: unknown)
+    // tall-cell geometry of a chunked matrix, by orientation: settled by its first chunk, handed to every later one (C > 0: set)
+    slp::TallCarry tall_carry[2];
     ~slp_matrix();
 };
 

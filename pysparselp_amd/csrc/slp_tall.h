@@ -5,18 +5,19 @@
 
 namespace slp {
 
-constexpr int kTallC = 4096;       // columns per strip (12-bit column inside the strip); 32 KB of x
+constexpr int kTallC = 4096;       // most columns per strip (12-bit column inside the strip); 32 KB of x
 constexpr int kTallT = 1024;       // threads per workgroup = lanes a cell's rows are dealt to
 constexpr int kTallSlots = 8;      // list positions per packet
 constexpr int kTallDepth = 4;      // packets of payload in flight per lane; headers run 2 x this ahead
-constexpr int kTallDictMax = 2048;
 constexpr int kTallBuckets = 6;    // rows are ordered by min(entries in the cell, 6), descending
 constexpr int kTallIdBits = 11, kTallColBits = 12, kTallRowBits = 14;
 constexpr int kTallCellShift = kTallIdBits + kTallColBits + kTallRowBits;  // sort key: cell | row | column | id
 static_assert(kTallBuckets * 32 == 3 * kWave, "k_tall_build scans the (count, bank class) buckets three per lane of one wave");
-static_assert(kTallRmax < (1 << kTallRowBits) && kTallC == (1 << kTallColBits) && kTallDictMax == (1 << kTallIdBits), "tall geometry");
-// LDS of the product kernel: sums (+ the scratch cell) + value table + two x-tiles
-static_assert((kTallRmax + 1) * 8 + kTallDictMax * 8 + 2 * kTallC * 8 <= 160 * 1024, "tall cells: LDS budget");
+static_assert(kTallRmax + 1 < (1 << kTallRowBits) && kTallC == (1 << kTallColBits) && kTallDictMax == (1 << kTallIdBits), "tall geometry");
+static_assert(kTallT == kTallPlanLanes && kTallC == kTallCmax, "the planner's constants (slp_tall_plan.h)");
+// LDS of the product kernel -- sums (+ the scratch cell) + value table + two x-tiles -- with a strip-range split; every other
+// copy's layout is the planner's (slp_tall_plan.h: tall_plan_layout)
+static_assert((kTallRmaxSplit + 1) * 8 + kTallDictMax * 8 + 2 * kTallC * 8 <= kTallLdsBytes, "tall cells: LDS budget");
 
 constexpr unsigned int kPktNewCell = 0x80000000u;  // first packet of a cell: barrier, then the other x-tile
 constexpr unsigned int kNoTile = 0x7fffffffu;

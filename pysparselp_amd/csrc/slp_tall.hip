@@ -6,8 +6,9 @@
 // Why another format: the LDS strips of slp_strip.hip pay 3 bytes of metadata per (row, strip) and a strip-JDS cell per
 // 2048 rows -- fine at >= 3 entries per (row, strip), hopeless at 0.4; the wide strips that replaced them there gather
 // every x from L2 (one 64-byte request per entry: 2e11 requests/s, 0.10 of the HBM peak).  Here the cell is TALL: a
-// workgroup owns R ~ 10^4 rows (their R running sums live in LDS, 78 KB) and walks strips of 4096 columns (the x-tile,
-// double-buffered, 64 KB of LDS), so that a cell holds ~4000 entries although a row has < 1.
+// workgroup owns R ~ 10^4 rows (their R running sums live in LDS) and walks strips of C <= 4096 columns (the x-tile,
+// double-buffered), so that a cell holds ~4000 entries although a row has < 1.  R, C and the LDS they share with the value
+// table are chosen together (slp_tall_plan.h): 13021 rows (102 KB) and 3072 columns (48 KB) at that density.
 //
 //   item (5 bytes)  = value id (11 bits) | column inside the strip (12 bits) << 11 | (local row + 1) (14 bits) << 23
 //                     -- self-describing: no per-row metadata, rows without entries in a cell cost nothing; row field 0 is
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(kBlock) void k_tall_sorted(i64 nnz, const i32 *__re
 }
 
 template <bool TR>
-__global__ __launch_bounds__(kBlock) void k_tall_keys(i64 r0, i64 nrow, int R, i64 T, int cshift, i64 b0, int D, const unsigned long long *__restrict__ dkeys,
+__global__ __launch_bounds__(kBlock) void k_tall_keys(i64 r0, i64 nrow, int R, i64 T, int C, i64 b0, int D, const unsigned long long *__restrict__ dkeys,
                                                       const i64 *__restrict__ ptr, const i32 *__restrict__ idx,
                                                       const double *__restrict__ val, const i64 *__restrict__ lo,
                                                       const i64 *__restrict__ opos, i64 obase, unsigned long long *__restrict__ keys,
@@ -121,7 +122,9 @@ __global__ __launch_bounds__(kBlock) void k_tall_keys(i64 r0, i64 nrow, int R, i
             }
             const i64 trow = TR ? (i64)j : r, tcol = TR ? r : (i64)j;  // row / column of the copy
             const unsigned long long b = (unsigned long long)(trow / R - b0), rl = (unsigned long long)(trow % R);
-            const unsigned long long t = (unsigned long long)(tcol >> cshift), cl = (unsigned long long)(tcol & (((i64)1 << cshift) - 1));
+            // (strips of C columns, C any multiple of 256: a 32-bit division -- a column is below 2^28, tall_build)
+            const unsigned int ts = (unsigned int)tcol / (unsigned int)C;
+            const unsigned long long t = ts, cl = (unsigned int)tcol - ts * (unsigned int)C;
             keys[o + (k - s)] = ((b * (unsigned long long)T + t) << kTallCellShift) | (rl << (kTallIdBits + kTallColBits)) | (cl << kTallIdBits) |
                                 (unsigned long long)id;
             if (kvals) kvals[o + (k - s)] = val[k];
@@ -237,7 +240,7 @@ __device__ __forceinline__ i64 tall_range_of(i64 t, i64 T, int S) {  // the stri
 
 // DICT: 5-byte items (value id inside); !DICT: 4-byte items (column | row << 12) + the fp64 value in a parallel array at the same offsets.
 template <bool DICT>
-__global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int cshift, i64 ncell, const unsigned long long *__restrict__ keys,
+__global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int C, i64 ncell, const unsigned long long *__restrict__ keys,
                                                        const double *__restrict__ svals, const i64 *__restrict__ cellptr, TallScan sc,
                                                        i64 cap_w, i64 cap_p, TallPkt *__restrict__ sdir,
                                                        unsigned int *__restrict__ spay, double *__restrict__ spayv) {
@@ -257,13 +260,19 @@ __global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int 
     __shared__ unsigned int lackx[(kTallBuckets - 1) * 32], sparex[(kTallBuckets - 1) * 33];
     __shared__ i64 s_cell, s_c0, s_tn;   // the workgroup's next cell, where its keys start, the strip after it (take_next)
     __shared__ int s_n;
-    __shared__ unsigned int s_dump[kTallT];   // where the touches of the next cell's keys land (never read)
+    __shared__ unsigned int s_dump[kWave];    // where the touches of the next cell's keys land (never read: one area for all waves)
     __shared__ unsigned long long s_before_w, s_before_p;
-    auto tile_of = [&](i64 t) -> unsigned int { return t >= 0 ? (unsigned int)(t << cshift) : kNoTile; };
+    // what the planner takes the kernel's LDS for (slp_tall_plan.h): 10 bytes per row and everything else
+    static_assert(sizeof(cnt) + sizeof(rstart) + sizeof(posrow) == (size_t)kTallBuildRowBytes * kTallRmax, "tall cells: builder LDS per row");
+    static_assert(sizeof(nlane) + sizeof(wtot) + sizeof(width) + sizeof(bcnt) + sizeof(bstart) + sizeof(cbuf) + sizeof(ctot) + sizeof(ccls) + sizeof(call) +
+                          sizeof(spare1x) + sizeof(lackx) + sizeof(sparex) + 3 * sizeof(i64) + sizeof(int) + sizeof(s_dump) + 2 * sizeof(unsigned long long) + 128 <=
+                      (size_t)kTallBuildFixed,
+                  "tall cells: builder LDS (128 bytes for the alignment of its parts)");
+    auto tile_of = [&](i64 t) -> unsigned int { return t >= 0 ? (unsigned int)(t * C) : kNoTile; };
     // The workgroup's NEXT cell, by one thread: the ticket (a cell without entries takes part in the scan with sizes of zero and
     // the next ticket is drawn), where the cell's keys lie, and the next strip of its stream with entries in the row block (its
     // x-tile rides on this cell's first packet).  cell = (row block b, strip t); the stream it belongs to: strip range sr of S
-    // (S > 1: few, tall row blocks whose strips are shared by S workgroups of the product kernel -- see tall_geometry).
+    // (S > 1: few, tall row blocks whose strips are shared by S workgroups of the product kernel -- see tall_plan).
     // Rounds 3-6a: drawn by thread 0 at the top of a cell with 1023 threads waiting, then every thread read cellptr[] itself
     // (3 dependent round trips to L2 in front of a cell's first key: 2 of its 19 us).  Now thread 64 draws it while wave 0 sums the
     // sizes of the cells before the current one, and the workgroup touches the next cell's keys (one dword per 128 bytes) while it
@@ -643,7 +652,7 @@ __global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int 
                 // every packet store before it, which nothing waits for otherwise)
                 if (s_cell < ncell && p * 16 < s_n) {
                     const unsigned int *g = reinterpret_cast<const unsigned int *>(keys + s_c0) + p * 32;
-                    const unsigned int lds = __builtin_amdgcn_readfirstlane((unsigned int)(size_t)(s_dump + (p & ~(kWave - 1))));
+                    const unsigned int lds = __builtin_amdgcn_readfirstlane((unsigned int)(size_t)s_dump);
                     unsigned int m0_saved;
                     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
                                  : "=&s"(m0_saved) : "s"(lds), "v"(g) : "memory");
@@ -742,7 +751,7 @@ __global__ void k_tall_streams(i64 V, i64 T, int S, const i64 *__restrict__ cell
 // The streams' packet directories: [leading packet without items: the x-tile of the stream's first cell] [the cells' packets,
 // payload offsets now relative to the stream] [packets without items up to a whole group of 2 x depth, then 2 x depth more that are
 // only ever prefetched].  A thread per cell, then a thread per stream for its ends.
-__global__ void k_tall_dir(i64 ncell, i64 V, i64 T, int S, int cshift, const i64 *__restrict__ cellptr, TallScan sc, const i64 *__restrict__ ext,
+__global__ void k_tall_dir(i64 ncell, i64 V, i64 T, int S, int C, const i64 *__restrict__ cellptr, TallScan sc, const i64 *__restrict__ ext,
                            const i64 *__restrict__ pkt_ptr, const TallPkt *__restrict__ sdir, TallPkt *__restrict__ dir) {
     const i64 i0 = (i64)blockIdx.x * blockDim.x + threadIdx.x, step = (i64)gridDim.x * blockDim.x;
     for (i64 c = i0; c < ncell; c += step) {
@@ -762,7 +771,7 @@ __global__ void k_tall_dir(i64 ncell, i64 V, i64 T, int S, int cshift, const i64
         for (i64 u = t_begin; u < t_end; ++u)
             if (cellptr[b * T + u + 1] > cellptr[b * T + u]) { first = u; break; }
         TallPkt h;
-        h.off = 0; h.xsrc = first >= 0 ? (unsigned int)(first << cshift) : kNoTile;
+        h.off = 0; h.xsrc = first >= 0 ? (unsigned int)(first * C) : kNoTile;
         h.c[0] = h.c[1] = h.c[2] = h.c[3] = 0; h.strip = 0; h.pad = 0;
         dir[pkt_ptr[v]] = h;
         h.off = (unsigned int)ext[4 * v + 1];
@@ -791,38 +800,12 @@ __global__ void k_tall_dir(i64 ncell, i64 V, i64 T, int S, int cshift, const i64
 // every chunk's blocks are as tall as the whole matrix's would be.  (The per-chunk multiple of round 5 assumes equal chunks: an LP
 // whose equality rows are cut off into chunks of their own came out with 2112 row blocks for 256 CUs -- a ninth round of the
 // grid a quarter full, A x 14 % slower -- and blocks of 8334 rows.)
-static void tall_geometry(i64 nrow, i64 T, double per_cell, i64 block_multiple, int *R_out, int *S_out, i64 rows_before = 0,
-                          i64 rows_total = 0) {
-    const i64 cus = block_multiple > 0 ? std::min<i64>(block_multiple, ctx().num_cu) : ctx().num_cu;
-    const double p2 = 1.0 - exp(-per_cell) * (1.0 + per_cell);
-    const i64 rcap = std::max<i64>(1024, std::min<i64>(kTallRmax, p2 > 0.0 ? (i64)(900.0 / p2) : kTallRmax));
-    const char *es = getenv("SLP_TALL_SPLIT");
-    const int want = es ? atoi(es) : 0;
-    const char *e = getenv("SLP_TALL_R");
-    if (rows_total > 0 && rows_before >= 0 && rows_before + nrow <= rows_total && want == 0 && !(e && atoi(e) > 0)) {
-        const i64 all = ctx().num_cu;
-        // (a margin of 1.5 % on the height: a chunk's share is a whole number of blocks)
-        const i64 total = std::max<i64>(1, (i64)ceil((double)rows_total / ((double)all * (double)rcap * 0.985))) * all;
-        auto upto = [&](i64 r) { return (i64)llround((double)total * (double)r / (double)rows_total); };
-        const i64 blocks = upto(rows_before + nrow) - upto(rows_before);
-        if (blocks > 0) {
-            const i64 R = (nrow + blocks - 1) / blocks;
-            if (R >= 1024 && R <= rcap && (nrow + R - 1) / R == blocks) { *S_out = 1; *R_out = (int)R; return; }
-        }
-    }
-    if (want != 0 && !(e && atoi(e) > 0)) {
-        const i64 R = std::min<i64>(rcap, std::max<i64>(nrow, 1)), B = (nrow + R - 1) / R;
-        i64 S = want > 0 ? want : std::max<i64>(1, cus / B);
-        S = std::max<i64>(1, std::min<i64>(S, std::max<i64>(1, T / 64)));  // at least 64 strips per range
-        if (S > 1) { *R_out = (int)R; *S_out = (int)S; return; }
-    }
-    *S_out = 1;
-    if (e && atoi(e) > 0) { *R_out = std::min(atoi(e), kTallRmax); return; }
-    i64 k = (nrow + cus * rcap - 1) / (cus * rcap);
-    if (k < 1) k = 1;
-    i64 R = (nrow + k * cus - 1) / (k * cus);
-    if (R < 1024) R = std::min<i64>(1024, std::max<i64>(nrow, 1));  // small matrices: fewer, still tall blocks
-    *R_out = (int)std::min<i64>(R, rcap);
+// All of this is decided by tall_plan (slp_tall_plan.h: host code without HIP, tested on the CPU) from the shape, the dictionary and
+// the switches read here: SLP_TALL_R (rows per block, capped by what the LDS of the two kernels holds), SLP_TALL_C (columns per strip:
+// a multiple of 256 from 1024 to 4096), SLP_TALL_SPLIT.
+static int tall_env(const char *name) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : 0;
 }
 
 // Entries per sort pass (SLP_TALL_PASS_NNZ): the keys of a pass and the sort's scratch are ~ 16 bytes per entry (32 with fp64
@@ -837,42 +820,34 @@ static i64 tall_pass_nnz() {
 
 // The tall-cell copy of `a` (transposed: of a^T) straight from the CSR of `a`.  Keys are drawn and sorted in passes over ranges
 // of the copy's row blocks (a pass's cells all precede the next pass's: the sorted ranges line up into the sorted whole).
-bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *dict, i64 block_multiple, i64 rows_before, i64 rows_total) {
+bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *dict, i64 block_multiple, i64 rows_before, i64 rows_total,
+                const TallCarry *carry) {
     Phase ph(transposed ? "tall_build (A^T from the CSR of A)" : "tall_build");
     hipStream_t st = ctx().stream;
     f = StripJds();
     if ((dict && (dict->D <= 0 || dict->D > kTallDictMax)) || a.nrow == 0 || a.ncol == 0 || a.nnz == 0) return false;
     const i64 nrowF = transposed ? a.ncol : a.nrow, ncolF = transposed ? a.nrow : a.ncol;
     if (ncolF * 8 >= ((i64)1 << 31)) return false;  // x is addressed through a buffer descriptor with 32-bit byte offsets
-    // Strip width (4096, 2048 or 1024 columns; items keep their 12-bit column field): the width whose cells the product kernel is
-    // predicted to walk fastest.  Per stored entry the kernel pays for the bytes of its item (4 + the fifth bytes' words: one per
-    // lane and four list positions) and for its share of the cell: a fixed part (barrier, pipeline, list ends) and the x-tile
-    // (8 C bytes) -- fitted on the 2.5e6-row slices of tools/tall_density_sweep.sh (ms per 2.49e9 entries: 0.393 per byte,
-    // 0.95 + 0.34 C / 4096 per cell of 4000 entries; predictions within 3 % of 10 of the 12 measured cases, 10 % low where a cell's lists
-    // are five items long).  What decides is the cell's size n = R x (entries per row and strip): R is what tall_geometry
-    // leaves of the LDS's 9984 rows once the row blocks are a multiple of the CU count and the rows with two or more entries fit one
-    // per lane, so a denser matrix keeps tall blocks only on narrower strips (density 2e-4 on the slice: 4096 columns -> R = 3256,
-    // 4.25 / 3.76 ms; 2048 -> R = 9766, 3.09 / 3.07 ms), while the metric's density stays on 4096 (0.41 entries per row and strip,
-    // n = 4000; 2048 would halve n: predicted 4.6 ms against 3.26).  SLP_TALL_C forces a width.
-    int cshift = kTallColBits;
-    {
-        double best = 0.0;
-        for (int cs = kTallColBits; cs >= kTallColBits - 2; --cs) {
-            const i64 Tc = (ncolF + ((i64)1 << cs) - 1) >> cs;
-            const double pc = (double)a.nnz / (double)nrowF / (double)Tc;
-            int Rc = 0, Sc = 1;
-            tall_geometry(nrowF, Tc, pc, transposed ? 0 : block_multiple, &Rc, &Sc, transposed ? 0 : rows_before, transposed ? 0 : rows_total);
-            const double n = std::max(1.0, (double)std::min<i64>(Rc, nrowF) * pc), tau = std::ceil(n / kTallT);
-            const double bytes = dict ? 4.0 + 4.0 * std::min(n, (double)kTallT) * std::ceil(tau / 4.0) / n : 12.0;
-            const double cost = 0.393 * bytes + (0.95 + 0.34 * (double)((i64)1 << cs) / kTallC) * 4000.0 / n;
-            if (cs == kTallColBits || cost < best) { best = cost; cshift = cs; }
-        }
-        if (const char *e = getenv("SLP_TALL_C")) { const int c = atoi(e); if (c == 4096 || c == 2048 || c == 1024) cshift = c == 4096 ? 12 : (c == 2048 ? 11 : 10); }
+    // Strip width and rows per block: the pair whose cells the product kernel is predicted to walk fastest (tall_plan_cost) among
+    // the widths C = 1024, 1280, ... 4096 with the tallest row blocks the LDS holds beside tiles of C columns and the table of this
+    // dictionary.  What decides is the cell's size n = R x (entries per row and strip) against the tile's 8 C bytes: the metric's
+    // LP (density 1e-4, a dictionary of ~1130 values) comes out at R = 13021, C = 3072 in both orientations (4000 entries per cell as
+    // with R = 9766, C = 4096 -- a quarter less x per item); twice the density takes C = 2048, 4.5 times 1024.
+    // A chunk of a chunked matrix follows what the first chunk decided (carry).
+    TallPlanIn pin;
+    pin.nrow = nrowF; pin.ncol = ncolF; pin.nnz = a.nnz; pin.D = dict ? dict->D : 0; pin.cus = ctx().num_cu;
+    if (!transposed) { pin.block_multiple = block_multiple; pin.rows_before = rows_before; pin.rows_total = rows_total; }
+    pin.env_R = std::max(0, tall_env("SLP_TALL_R")); pin.env_C = tall_env("SLP_TALL_C"); pin.env_split = tall_env("SLP_TALL_SPLIT");
+    if (carry && carry->C > 0) {
+        pin.carry_C = carry->C; pin.carry_dcap = carry->dcap; pin.carry_total = transposed ? 0 : carry->total;
+        pin.carry_R = transposed ? carry->R : 0;   // (the copy of A^T: the same row blocks in every chunk)
+        pin.carry_blocks = transposed ? 0 : carry->blocks;
     }
-    const i64 Cw = (i64)1 << cshift;
-    const i64 T = (ncolF + Cw - 1) / Cw;
-    int R = 0, S = 1;
-    tall_geometry(nrowF, T, (double)a.nnz / (double)nrowF / (double)T, transposed ? 0 : block_multiple, &R, &S, transposed ? 0 : rows_before, transposed ? 0 : rows_total);
+    const TallPlan plan = tall_plan(pin);
+    SLP_REQUIRE(plan.lds_bytes <= kTallLdsBytes && plan.build_lds_bytes <= kTallLdsBytes && plan.R >= 1 && plan.R <= kTallRmax,
+                "tall_build: the planned geometry does not fit the LDS");
+    const int R = plan.R, S = plan.S, Cw = plan.C;
+    const i64 T = plan.T;
     const i64 B = (nrowF + R - 1) / R, ncell = B * T, V = B * S;  // V workgroups: (row block, strip range)
     unsigned int cellbits = 1;
     while (((i64)1 << cellbits) < ncell) ++cellbits;
@@ -928,10 +903,10 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
             if (!dict && transposed) kvals.alloc((size_t)n_p);
             const i64 scan_rows = transposed ? a.nrow : f1 - f0, r0 = transposed ? 0 : f0;
             if (transposed)
-                hipLaunchKernelGGL((k_tall_keys<true>), dim3(grid_for(scan_rows * kWave, kBlock)), dim3(kBlock), 0, st, r0, scan_rows, R, T, cshift, (i64)0, D, dk,
+                hipLaunchKernelGGL((k_tall_keys<true>), dim3(grid_for(scan_rows * kWave, kBlock)), dim3(kBlock), 0, st, r0, scan_rows, R, T, Cw, (i64)0, D, dk,
                                    a.ptr.p, a.idx.p, a.val.p, lo.p, opos.p, obase, keys.p, kvals.p, bad.p);
             else
-                hipLaunchKernelGGL((k_tall_keys<false>), dim3(grid_for(scan_rows * kWave, kBlock)), dim3(kBlock), 0, st, r0, scan_rows, R, T, cshift, (i64)0, D, dk,
+                hipLaunchKernelGGL((k_tall_keys<false>), dim3(grid_for(scan_rows * kWave, kBlock)), dim3(kBlock), 0, st, r0, scan_rows, R, T, Cw, (i64)0, D, dk,
                                    a.ptr.p, a.idx.p, a.val.p, (const i64 *)nullptr, (const i64 *)nullptr, obase, keys.p, (double *)nullptr, bad.p);
             SLP_HIP(hipGetLastError());
             size_t bytes = 0;
@@ -992,9 +967,9 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
         SLP_HIP(hipMemsetAsync(scan.p, 0, (2 * (size_t)ncell + 1) * sizeof(unsigned long long), st));  // levels and the ticket
         // as many workgroups as the chip holds at once (the kernel's LDS: one per compute unit); each takes cells until none is left
         const unsigned grid = (unsigned)std::min<i64>(ncell, (i64)ctx().num_cu);
-        if (dict) hipLaunchKernelGGL((k_tall_build<true>), dim3(grid), dim3(kTallT), 0, st, R, T, S, cshift, ncell, sorted.p, (const double *)nullptr, cellptr.p, sc,
+        if (dict) hipLaunchKernelGGL((k_tall_build<true>), dim3(grid), dim3(kTallT), 0, st, R, T, S, Cw, ncell, sorted.p, (const double *)nullptr, cellptr.p, sc,
                                      cap_w, cap_p, reinterpret_cast<TallPkt *>(sdir.p), spay.p, (double *)nullptr);
-        else hipLaunchKernelGGL((k_tall_build<false>), dim3(grid), dim3(kTallT), 0, st, R, T, S, cshift, ncell, sorted.p, svals.p, cellptr.p, sc,
+        else hipLaunchKernelGGL((k_tall_build<false>), dim3(grid), dim3(kTallT), 0, st, R, T, S, Cw, ncell, sorted.p, svals.p, cellptr.p, sc,
                                 cap_w, cap_p, reinterpret_cast<TallPkt *>(sdir.p), spay.p, spayv.p);
         hipLaunchKernelGGL(k_tall_streams, dim3(grid_for(V, kBlock)), dim3(kBlock), 0, st, V, T, S, cellptr.p, sc, ext.p);
         SLP_HIP(hipGetLastError());
@@ -1037,7 +1012,7 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
     DevBuf<unsigned int> &dir = f.tall_dir.back(), &pay = f.tall_pay.back();
     double *vals = nullptr;
     if (!dict) { f.tall_val.emplace_back(std::move(spayv)); vals = f.tall_val.back().p; }
-    hipLaunchKernelGGL(k_tall_dir, dim3(grid_for(std::max<i64>(ncell, V), kBlock)), dim3(kBlock), 0, st, ncell, V, T, S, cshift, cellptr.p, sc, ext.p, dpkt.p,
+    hipLaunchKernelGGL(k_tall_dir, dim3(grid_for(std::max<i64>(ncell, V), kBlock)), dim3(kBlock), 0, st, ncell, V, T, S, Cw, cellptr.p, sc, ext.p, dpkt.p,
                        reinterpret_cast<const TallPkt *>(sdir.p), reinterpret_cast<TallPkt *>(dir.p));
     SLP_HIP(hipGetLastError());
     std::vector<TallWg> wg((size_t)V);
@@ -1081,6 +1056,8 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
     f.dict = dict ? dict->values.p : nullptr;
     f.tall = true;
     f.tall_R = R;
+    f.tall_dcap = plan.dcap;
+    f.tall_total = plan.total;
     f.S = S;
     if (S > 1) f.part.alloc((size_t)S * (size_t)nrowF);
     f.ok = true;

@@ -32,27 +32,35 @@ struct TallRegs {
 // matrix in one grid (A x in one launch); nseg = the chunks for the copy of A^T of a chunked matrix, where the workgroup of a
 // column block walks chunk 0, 1, ... in order and the column sums simply stay in LDS between them (A^T y in one launch: the chain
 // of additions of the unchunked product, as the chunk-by-chunk launches formed it through `out`).
-// C: columns per strip = doubles of an x-tile (4096, 2048 or 1024: the build halves the strips of denser matrices until a cell
-// holds ~0.3-0.6 entries per row -- the regime the dealing of a cell's rows to the lanes is made for; items keep their 12-bit
-// column field).
-template <bool DICT, bool ACC, bool POW = false, int C = kTallC>
+// C: columns per strip = doubles of an x-tile: a run-time multiple of 256 up to 4096 (slp_tall_plan.h: the width whose cells
+// the kernel is predicted to walk fastest; items keep their 12-bit column field).
+// LDS: one dynamic block -- the running sums (from 0: the item path's addresses need no base), the value table from double
+// `odv`, the two x-tiles from double `oxt` (both even: 16-byte stores) -- laid out by the planner for the copy's R, dictionary
+// and C; the same for every workgroup of a launch.
+// The tile's C / 2 16-byte pieces are dealt to the 1024 lanes in order: lane p carries piece p and, where the tile has it,
+// piece p + 1024 -- 4096 columns: two pieces on every lane; 3072: a second piece on the first 8 of the 16 waves; 2048 and
+// below: one piece on the first C / 2 lanes.  C / 2 is a multiple of 64, so either test is the same for a whole wave.
+// CT: the width as a constant (0: the argument `cw`) -- instantiated for the widths the benchmark's LP runs on, where the folded
+// tile tests and tile offsets are worth 1.2 % of a product (21.79 -> 22.05 ms with 4096 columns as an argument).
+template <bool DICT, bool ACC, bool POW = false, int CT = 0>
 __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__restrict__ wgs, const double *__restrict__ dict_arg,
-                                                      const double *__restrict__ x, double *__restrict__ out, double pw) {
+                                                      const double *__restrict__ x, double *__restrict__ out, double pw, const int cw,
+                                                      const int odv, const int oxt) {
+    const int C = CT ? CT : cw;
     constexpr int kDepth = DICT ? kTallDepth : 2;
     // acc[0] is a scratch cell: the row field of an item is its local row + 1, and whatever is not a lane's item -- a slot
     // beyond its list (the load past the buffer descriptor returns 0), a skip item -- decodes to row 0, value id 0, column 0
     // and adds into the scratch cell: no predicate on the stores, none on the sums
-    __shared__ double acc[kTallRmax + 1];
-    __shared__ double dv[kTallDictMax];
-    static_assert(C == 4096 || C == 2048 || C == 1024, "tall cells: strip width");
-    __shared__ double xt[2][C];
-    constexpr int kPieces = C / 2048 ? C / 2048 : 1;     // 16-byte pieces of a tile per lane
+    extern __shared__ __attribute__((aligned(16))) double tall_lds[];
+    double *const acc = tall_lds;
+    double *const dv = tall_lds + odv;
+    double *const xt = tall_lds + oxt;                   // tile buffers at xt and xt + C
     const int p = threadIdx.x;
-    const bool tile_lane = C >= 2048 || p < C / 2;       // (1024 columns: the first 512 lanes carry the tile)
     // (wave-uniform by construction; told to the compiler, so that tests on it are scalar branches, not EXEC masks)
     const unsigned int wbase = (unsigned int)__builtin_amdgcn_readfirstlane(p & ~(kWave - 1));
+    const bool piece0 = (int)wbase < (C >> 1), piece1 = (int)wbase + kTallT < (C >> 1);
     const int v = blockIdx.x;
-    int cur = 0;
+    int cur = 0;   // the tile buffer of the current cell: 0 or C (doubles from xt)
     TallWg wg = wgs[v];
     // ACC: the sums continue from what `out` holds -- a row chunk of a chunked matrix carrying on the column sums of the chunks
     // before it, launch by launch (the strip-range split takes it in k_tall_combine instead: its descriptors point into the
@@ -132,12 +140,13 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
     const unsigned int wbytes = wbase * 4u;   // (a wave takes slot k's items iff wbytes < w[k])
     unsigned int xwq[kDepth], c4q[kDepth];
 
-    // this lane's two 16-byte pieces of an x-tile (doubles 2p, 2p + 1 of each tile half).  A piece that straddles the end of x
+    // this lane's 16-byte pieces of an x-tile (pieces p and p + 1024: doubles 2p, 2p + 1 and 2048 + 2p, 2049 + 2p).  A piece that straddles the end of x
     // (odd width) may fetch the 8 bytes behind it: every device block carries 16 bytes of slack, and no item names that column
     auto load_tile = [&](TallRegs<DICT> &g, const unsigned int xo) {
 #pragma unroll
-        for (int i = 0; i < kPieces; ++i) {
-            const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_x, xo + (unsigned int)i * (unsigned int)(C * 4), 0, 0);
+        for (int i = 0; i < 2; ++i) {   // (a piece the lane does not carry: past the descriptor, no memory request)
+            const unsigned int o = (i == 0 ? piece0 : piece1) && xo != kOob ? xo + (unsigned int)i * (unsigned int)(kTallT * 16) : kOob;
+            const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_x, o, 0, 0);
             g.x[2 * i] = __hiloint2double((int)v[1], (int)v[0]);
             g.x[2 * i + 1] = __hiloint2double((int)v[3], (int)v[2]);
         }
@@ -175,11 +184,11 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
         if (part == 1) {   // the tile of the packet `depth` ahead: behind all of this packet's items
             // columns past ncol read 0: the displacement of each double is part of the voffset, which the descriptor's range check
             // covers
-            // lane p carries doubles 2p, 2p + 1 of the tile's first half and of its second half: consecutive lanes then write
+            // lane p carries doubles 2p, 2p + 1 of the tile and, where the tile has them, 2048 + 2p, 2049 + 2p: consecutive lanes then write
             // consecutive 16-byte pieces of the LDS tile (no bank conflicts; with 4p .. 4p + 3 per lane the two 16-byte writes of a
             // lane pair collided -- the tile write was the largest single item of the kernel's ablation, 0.9 of 4.1 ms)
             const unsigned int xs = t.xw & 0x7fffffffu;
-            const unsigned int xo = (xs == kNoTile || !tile_lane) ? kOob : (xs + 2u * (unsigned int)p) * 8u;
+            const unsigned int xo = xs == kNoTile ? kOob : (xs + 2u * (unsigned int)p) * 8u;
             load_tile(g, xo);
         }
     };
@@ -189,7 +198,7 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
         if (xw & kPktNewCell) {
             // sums of the previous cell (other lanes owned these rows there) and the x-tile: LDS only, loads stay in flight
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            cur ^= 1;
+            cur = C - cur;
         }
         auto stage_tile = [&]() {
             if ((xw & 0x7fffffffu) != kNoTile) {
@@ -197,9 +206,9 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
                 // measured: 4.71 ms against 3.99.  With two tile buffers the DMA can only start at the cell's barrier and must
                 // have landed by the next one, 1.6 us later; the register path issues the loads four cells ahead.  A third buffer
                 // does not fit beside 78 KB of running sums.)
-                double *dst = &xt[cur ^ 1][2 * p];
-                if (tile_lane) *reinterpret_cast<double2 *>(dst) = make_double2(g.x[0], g.x[1]);
-                if (kPieces == 2) *reinterpret_cast<double2 *>(dst + C / 2) = make_double2(g.x[2], g.x[3]);
+                double *dst = static_cast<double *>(__builtin_assume_aligned(xt + (C - cur) + 2 * p, 16));
+                if (piece0) *reinterpret_cast<double2 *>(dst) = make_double2(g.x[0], g.x[1]);
+                if (piece1) *reinterpret_cast<double2 *>(dst + 2 * kTallT) = make_double2(g.x[2], g.x[3]);
             }
         };
         // WHERE the wave stores its share of the NEXT cell's x-tile (it only has to be there by the next cell's barrier; lab
@@ -210,7 +219,7 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
         // gathers queued behind 32 KB of stores): with the shorter item code the stores are out of the way before the first
         // gathers are ready to issue, and they no longer sit between a packet's items and the next packet's.
         stage_tile();
-        const double *__restrict__ tile = xt[cur];
+        const double *__restrict__ tile = xt + cur;
         // Four slots at a time: all twelve LDS reads (running sums, values, x) are issued together, the products do not
         // depend on the sums, and a sum that the lane has just updated is carried in a register (a lane's items of one
         // row are consecutive) -- the LDS latency is paid once per group, not once per item.  The additions of a row
@@ -295,15 +304,25 @@ __global__ void k_tall_combine(i64 nrow, int S, const double *__restrict__ part,
     }
 }
 
-// the instantiation for the copy's strip width
+// One launch with the LDS layout of the copy (slp_tall_plan.h): R rows of sums, a table of dcap entries, tiles of C columns
 template <bool DICT, bool ACC, bool POW>
-static void tall_launch(int C, unsigned grid, int nseg, const TallWg *wgs, const double *dict, const double *x, double *out, double pw) {
-    switch (C) {
-    case 4096: hipLaunchKernelGGL((k_tall_spmv<DICT, ACC, POW, 4096>), dim3(grid), dim3(kTallT), 0, ctx().stream, nseg, wgs, dict, x, out, pw); break;
-    case 2048: hipLaunchKernelGGL((k_tall_spmv<DICT, ACC, POW, 2048>), dim3(grid), dim3(kTallT), 0, ctx().stream, nseg, wgs, dict, x, out, pw); break;
-    case 1024: hipLaunchKernelGGL((k_tall_spmv<DICT, ACC, POW, 1024>), dim3(grid), dim3(kTallT), 0, ctx().stream, nseg, wgs, dict, x, out, pw); break;
-    default: SLP_REQUIRE(false, "tall cells: strip width");
-    }
+static void tall_launch(const StripJds &f, unsigned grid, int nseg, const TallWg *wgs, const double *dict, const double *x, double *out, double pw) {
+    TallPlan lay;
+    lay.R = f.tall_R; lay.C = (int)f.C; lay.dcap = DICT ? f.tall_dcap : 0;
+    tall_plan_layout(lay);
+    SLP_REQUIRE(tall_width_ok(lay.C) && lay.R > 0 && lay.lds_bytes <= kTallLdsBytes && f.D <= lay.dcap, "tall cells: LDS layout");
+    auto go = [&](auto kernel, bool &raised) {
+        if (!raised) {
+            SLP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kTallLdsBytes));
+            raised = true;
+        }
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTallT), (size_t)lay.lds_bytes, ctx().stream, nseg, wgs, dict, x, out, pw, lay.C, lay.off_dv / 8,
+                           lay.off_xt / 8);
+    };
+    static bool raised[3] = {false, false, false};   // (per instantiation)
+    if (DICT && !POW && lay.C == 3072) go(k_tall_spmv<DICT, ACC, POW, (DICT && !POW) ? 3072 : 0>, raised[1]);
+    else if (DICT && !POW && lay.C == 4096) go(k_tall_spmv<DICT, ACC, POW, (DICT && !POW) ? 4096 : 0>, raised[2]);
+    else go(k_tall_spmv<DICT, ACC, POW, 0>, raised[0]);
 }
 
 void tall_spmv(const StripJds &f, const double *x, double *out, int accum) {
@@ -311,8 +330,8 @@ void tall_spmv(const StripJds &f, const double *x, double *out, int accum) {
     const unsigned grid = (unsigned)(f.B * f.S);
     const bool acc = accum && f.S == 1;
     const double *none = nullptr;
-    if (f.D > 0) { if (acc) tall_launch<true, true, false>((int)f.C, grid, 1, f.tall_wg.p, f.dict, x, dst, 0.0); else tall_launch<true, false, false>((int)f.C, grid, 1, f.tall_wg.p, f.dict, x, dst, 0.0); }
-    else { if (acc) tall_launch<false, true, false>((int)f.C, grid, 1, f.tall_wg.p, none, x, dst, 0.0); else tall_launch<false, false, false>((int)f.C, grid, 1, f.tall_wg.p, none, x, dst, 0.0); }
+    if (f.D > 0) { if (acc) tall_launch<true, true, false>(f, grid, 1, f.tall_wg.p, f.dict, x, dst, 0.0); else tall_launch<true, false, false>(f, grid, 1, f.tall_wg.p, f.dict, x, dst, 0.0); }
+    else { if (acc) tall_launch<false, true, false>(f, grid, 1, f.tall_wg.p, none, x, dst, 0.0); else tall_launch<false, false, false>(f, grid, 1, f.tall_wg.p, none, x, dst, 0.0); }
     if (f.S > 1)
         hipLaunchKernelGGL(k_tall_combine, dim3(grid_for(f.nrow, kBlock)), dim3(kBlock), 0, ctx().stream, f.nrow, f.S, f.part.p, out, accum);
     SLP_HIP(hipGetLastError());
@@ -325,8 +344,8 @@ void tall_spmv(const StripJds &f, const double *x, double *out, int accum) {
 void tall_spmv_fused(const StripJds &f, const double *x, double *out) {
     const int nseg = f.parts_cols ? (int)f.parts.size() : 1;
     const unsigned grid = (unsigned)(f.tall_wg.n / (size_t)nseg);
-    if (f.D > 0) tall_launch<true, false, false>((int)f.C, grid, nseg, f.tall_wg.p, nullptr, x, out, 0.0);
-    else tall_launch<false, false, false>((int)f.C, grid, nseg, f.tall_wg.p, nullptr, x, out, 0.0);
+    if (f.D > 0) tall_launch<true, false, false>(f, grid, nseg, f.tall_wg.p, nullptr, x, out, 0.0);
+    else tall_launch<false, false, false>(f, grid, nseg, f.tall_wg.p, nullptr, x, out, 0.0);
     SLP_HIP(hipGetLastError());
 }
 
@@ -340,7 +359,8 @@ bool tall_fuse(StripJds &f) {
     if (f.parts.empty()) return false;
     const StripJds &f0 = *f.parts[0];
     for (const StripJds *g : f.parts)
-        if (!g->ok || !g->tall || g->S != 1 || g->C != f0.C || (g->D > 0) != (f0.D > 0) || (f.parts_cols && (g->B != f0.B || g->tall_R != f0.tall_R || g->nrow != f0.nrow)))
+        if (!g->ok || !g->tall || g->S != 1 || g->C != f0.C || (g->D > 0) != (f0.D > 0) || g->tall_dcap != f0.tall_dcap ||
+            (f.parts_cols && (g->B != f0.B || g->tall_R != f0.tall_R || g->nrow != f0.nrow)))
             return false;
     std::vector<TallWg> all;
     for (size_t k = 0; k < f.parts.size(); ++k) {
@@ -355,7 +375,11 @@ bool tall_fuse(StripJds &f) {
         }
     }
     f.tall_wg.upload(all.data(), all.size());
+    // one LDS layout for the launch: the tallest row block's sums, the chunks' common table capacity and strip width
     f.C = f0.C;
+    f.tall_dcap = f0.tall_dcap;
+    f.tall_R = 0;
+    for (const StripJds *g : f.parts) f.tall_R = std::max(f.tall_R, g->tall_R);
     return true;
 }
 
@@ -364,8 +388,8 @@ void tall_spmv_pow(const StripJds &f, double pw, const double *x, double *out, i
     SLP_REQUIRE(f.ok && f.tall && f.D == 0, "tall_spmv_pow: not a tall-cell copy with fp64 entries");
     double *dst = f.S > 1 ? f.part.p : out;
     const unsigned grid = (unsigned)(f.B * f.S);
-    if (accum && f.S == 1) tall_launch<false, true, true>((int)f.C, grid, 1, f.tall_wg.p, nullptr, x, dst, pw);
-    else tall_launch<false, false, true>((int)f.C, grid, 1, f.tall_wg.p, nullptr, x, dst, pw);
+    if (accum && f.S == 1) tall_launch<false, true, true>(f, grid, 1, f.tall_wg.p, nullptr, x, dst, pw);
+    else tall_launch<false, false, true>(f, grid, 1, f.tall_wg.p, nullptr, x, dst, pw);
     if (f.S > 1)
         hipLaunchKernelGGL(k_tall_combine, dim3(grid_for(f.nrow, kBlock)), dim3(kBlock), 0, ctx().stream, f.nrow, f.S, f.part.p, out, accum);
     SLP_HIP(hipGetLastError());
