@@ -312,6 +312,25 @@ int slp_many_cp_set_stop(slp_cp_many *s, double tol, int64_t check_every);
 /* Per LP: iterations completed (for a stopped LP its stopping iteration), 1 = stopped, the last evaluated step (+inf before
  * the first test).  count values each; any pointer may be NULL.  Synchronises. */
 int slp_many_cp_stop_state(slp_cp_many *s, int64_t *iterations, int32_t *stopped, double *step);
+/* Per-LP stopping on a certified duality gap, the second test of the iteration kernel; the reference evaluates the same bound
+ * (energy2, :262-266) at its reports only and stops on nothing.  With K = [A_eq; A_ineq], x_t and y_t = [y_eq; y_ineq] after t
+ * whole iterations, at the end of an iteration t with t % check_every == 0:
+ *   d_j       = c_j + (K^T y_t)_j, the bits the next primal half computes;
+ *   primal    = sum_j c_j x_t,j;
+ *   bound     = sum_j [d_j != 0 ? min(d_j lb_j, d_j ub_j) : 0] - sum_r [y_r != 0 ? y_r b_r : 0]: y_t is dual feasible by
+ *               construction (free equality multipliers, clamped inequality multipliers), so this is a lower bound on the LP's
+ *               value, -inf where a free variable has d_j of the wrong sign;
+ *   violation = max(max_{r < m_eq} |(K x_t)_r - b_r|, max_{r >= m_eq} ((K x_t)_r - b_r), 0), exact in any order, NaN-propagating.
+ * The LP stops iff violation <= tol_feas and |primal - bound| <= tol_gap (1 + |primal| + |bound|) with |primal - bound| finite: a
+ * NaN or an infinite gap never stops.  The two sums are in a fixed order of their own (lane, wave, workgroup), a function of the
+ * shapes only.  A stopped LP behaves as under slp_many_cp_set_stop.  tol_gap, tol_feas >= 0 and finite with check_every >= 1
+ * arm the test and disarm the step test (slp_many_cp_set_stop disarms this one); tol_gap < 0 turns it off; anything else is an
+ * error.  Every call clears all stopped flags and keeps the counters.  To be called between whole iterations.  Synchronises. */
+int slp_many_cpgap_set_stop(slp_cp_many *s, double tol_gap, double tol_feas, int64_t check_every);
+/* Per LP: iterations completed (for a stopped LP its stopping iteration), 1 = stopped, and primal, bound, violation of the last
+ * evaluated certificate (+inf, -inf, +inf before the first).  count values each; any pointer may be NULL.  Synchronises.
+ * slp_many_cp_stop_state keeps reporting iterations and the flag while this test is armed; its step stays what it last was. */
+int slp_many_cpgap_state(slp_cp_many *s, int64_t *iterations, int32_t *stopped, double *primal, double *bound, double *violation);
 
 /* ---- projected Gauss-Seidel: replaces gaussSiedel.pyx ------------------- *
  * boundedGaussSeidelClass.__init__ (gaussSiedel.pyx:87-92) and .solve

@@ -684,6 +684,33 @@ class CPManyState(_many.ManyState):
         _lib.check(self._l.slp_many_cp_stop_state(self._h, _lib.ptr(iterations), _lib.ptr(stopped), _lib.ptr(step)))
         return iterations, stopped.astype(bool), step
 
+    def set_stop_gap(self, tol_gap, tol_feas, check_every=1):
+        """Arms the certificate as the per-LP stopping test of the iteration kernel (``slp_many_cpgap_set_stop``) and disarms the
+        step test of ``set_stop``: at the end of every iteration ``t`` of an LP with ``t % check_every == 0`` -- counted from 1
+        over the LP's life -- the kernel evaluates, for the LP the solver holds (``K = [A_eq; A_ineq]`` one-sided, ``y_t`` the
+        clamped multipliers), ``primal = c.x_t``, the lower bound ``sum_j min(d_j lb_j, d_j ub_j) - y_t.b`` with ``d = c + K^T
+        y_t`` (terms with ``d_j == 0`` or ``y_r == 0`` left out; ``-inf`` where a free variable has ``d_j`` of the wrong sign) and
+        ``violation = max(max|A_eq x_t - b_eq|, max(A_ineq x_t - b_ineq), 0)``; the LP stops iff ``violation <= tol_feas`` and
+        ``|primal - bound| <= tol_gap * (1 + |primal| + |bound|)`` with a finite left-hand side.  A NaN never stops.  A stopped LP
+        keeps its iterate and takes no part in later calls.  ``tol_gap=None`` turns the test off.  Between whole iterations only.
+        Every call clears the stopped flags and keeps the counters."""
+        if tol_gap is None:
+            tol_gap, tol_feas, check_every = -1.0, 0.0, 1
+        else:
+            tol_gap, check_every = _many.check_stop(tol_gap, check_every, "tol_gap")
+            tol_feas, _ = _many.check_stop(tol_feas, check_every, "tol_feas")
+        _lib.check(self._l.slp_many_cpgap_set_stop(self._h, tol_gap, tol_feas, check_every))
+
+    def gap_state(self):
+        """``(iterations, stopped, primal, bound, violation)`` per LP, int64, bool and three float64 arrays: the iterations
+        completed (for a stopped LP its stopping iteration), whether it is stopped, and the numbers of the last evaluated
+        certificate (``+inf``, ``-inf``, ``+inf`` before the first)."""
+        iterations, stopped = np.zeros(self.count, dtype=np.int64), np.zeros(self.count, dtype=np.int32)
+        primal, bound, violation = np.zeros(self.count), np.zeros(self.count), np.zeros(self.count)
+        _lib.check(self._l.slp_many_cpgap_state(self._h, _lib.ptr(iterations), _lib.ptr(stopped), _lib.ptr(primal), _lib.ptr(bound),
+                                                 _lib.ptr(violation)))
+        return iterations, stopped.astype(bool), primal, bound, violation
+
     def x(self):
         return self._per_lp("x", self.n)
 
@@ -733,9 +760,13 @@ def chambolle_pock_ppd_many(problems, x0=None, alpha=1, theta=1, nb_max_iter=100
     return xs, best
 
 
-def _cp_many_run(problems, x0, alpha, theta, nb_max_iter, callback_func, max_time, nb_iter_plot, stop):
-    """``chambolle_pock_ppd_many`` (``stop`` None) and ``chambolle_pock_ppd_many_until`` (``stop`` the checked ``(tol,
-    check_every)``): ``(xs, best_integer_solutions, info)``, ``info`` None without a stopping test."""
+_GAP_INFO = ("iterations", "stopped", "primal", "lower_bound", "violation")
+
+
+def _cp_many_run(problems, x0, alpha, theta, nb_max_iter, callback_func, max_time, nb_iter_plot, stop, gap=None):
+    """``chambolle_pock_ppd_many`` (``stop`` and ``gap`` None), ``chambolle_pock_ppd_many_until`` (``stop`` the checked ``(tol,
+    check_every)``) and ``chambolle_pock_ppd_many_certified`` (``gap`` the checked ``(tol_gap, tol_feas, check_every)``): ``(xs,
+    best_integer_solutions, info)``, ``info`` None without a stopping test."""
     start = time.perf_counter()
     count = _many.count_problems(problems)
     lps = [_many_problem(k, p) for k, p in enumerate(problems)]
@@ -743,13 +774,19 @@ def _cp_many_run(problems, x0, alpha, theta, nb_max_iter, callback_func, max_tim
     solved = [k for k in range(count) if lps[k][3] is not None or lps[k][5] is not None]
     xs = [None if (lps[k][3] is not None or lps[k][5] is not None) else box_vertex(*lps[k][:3]) for k in range(count)]
     best = [None] * count
+    free_energy = np.array([0.0 if xs[k] is None else lps[k][0].dot(xs[k]) for k in range(count)])
     info = None if stop is None else _many.new_stop_info(count, solved)
+    if gap is not None:   # an LP without rows: its vertex is optimal, primal and bound are its value
+        info = dict(iterations=np.zeros(count, dtype=np.int64), stopped=np.ones(count, dtype=bool), primal=free_energy.copy(),
+                    lower_bound=free_energy.copy(), violation=np.zeros(count))
+        info["stopped"][solved] = False
+        info["primal"][solved] = info["violation"][solved] = np.inf
+        info["lower_bound"][solved] = -np.inf
     if not solved:
         return xs, best, info
     costs = [lps[k][0] for k in solved]
     has_ineq = np.array([lps[k][5] is not None for k in solved])
     state = CPManyState([lps[k] for k in solved], None if x0 is None else [x0[k] for k in solved], alpha, theta)
-    free_energy = np.array([0.0 if xs[k] is None else lps[k][0].dot(xs[k]) for k in range(count)])
 
     def spread(values, energy=False):
         """Per-LP numbers of the solved LPs over the whole list."""
@@ -764,21 +801,29 @@ def _cp_many_run(problems, x0, alpha, theta, nb_max_iter, callback_func, max_tim
         return out
 
     def stopped_now():
+        if gap is not None:
+            now = state.gap_state()
+            for name, values in zip(_GAP_INFO, now):
+                info[name][solved] = values
+            return now[1]
         now = state.stop_state()
         _many.spread_stop_state(info, solved, now)
         return now[1]
 
     try:
-        if stop is not None:
-            state.set_stop(*stop)
+        if info is not None:
+            if gap is not None:
+                state.set_stop_gap(*gap)
+            else:
+                state.set_stop(*stop)
             if callback_func is not None:
                 try:
                     callback_func.info = info
                 except AttributeError:   # a bound method takes no attribute: wrap it in a function to read ``info``
                     pass
         xs = _cp_report_loop(state, costs, has_ineq, solved, best, all_x, spread, nb_max_iter, nb_iter_plot, callback_func, max_time, start,
-                             None if stop is None else stopped_now)
-        if stop is not None:
+                             None if info is None else stopped_now)
+        if info is not None:
             stopped_now()
     finally:
         state.close()
@@ -809,3 +854,32 @@ def chambolle_pock_ppd_many_until(problems, tol, check_every=10, x0=None, alpha=
     """
     stop = _many.check_stop(tol, check_every)
     return _cp_many_run(problems, x0, alpha, theta, nb_max_iter, callback_func, max_time, nb_iter_plot, stop)
+
+
+def chambolle_pock_ppd_many_certified(problems, tol_gap, tol_feas, check_every=10, x0=None, alpha=1, theta=1, nb_max_iter=10000,
+                                      callback_func=None, max_time=None, nb_iter_plot=10):
+    """``chambolle_pock_ppd_many`` with a certificate as the stopping test per LP (extension; the reference evaluates the same
+    lower bound, its ``energy2``, at its reports and stops on nothing): the list runs until every LP has stopped, at most
+    ``nb_max_iter`` iterations.  Returns ``(xs, best_integer_solutions, info)``.
+
+    The test is made inside the iteration kernel (``CPManyState.set_stop_gap``), at the end of every iteration ``t`` of an LP with
+    ``t % check_every == 0``, iterations counted from 1, on the LP the solver holds (inequalities one-sided, ``y_t`` the clamped
+    multipliers, dual feasible by construction): with ``primal = c.x_t``, ``lower_bound = sum_j min(d_j lb_j, d_j ub_j) - y_t.b``
+    for ``d = c + K^T y_t`` and ``violation = max(max|A_eq x_t - b_eq|, max(A_ineq x_t - b_ineq), 0)`` the LP stops iff ``violation
+    <= tol_feas`` and ``|primal - lower_bound| <= tol_gap * (1 + |primal| + |lower_bound|)`` with a finite left-hand side.  ``lower_bound`` is a bound on the
+    LP's value whatever ``x_t`` is; it is ``-inf`` while a variable without a finite bound has ``d_j`` of the wrong sign, and such an
+    LP, like one with a NaN, does not stop.  A stopped LP keeps its iterate after ``t`` iterations, bit for bit that of
+    ``chambolle_pock_ppd(..., nb_max_iter=t, order=ORDER_SEQUENTIAL)``, while the others go on.  ``tol_gap`` and ``tol_feas`` are
+    finite floats ``>= 0``, ``check_every`` an int ``>= 1``: a ``ValueError`` before the library is loaded otherwise, like every shape
+    error.
+
+    ``info`` is a dict of arrays over the whole list: ``iterations`` (int64: completed, for a stopped LP its stopping iteration),
+    ``stopped`` (bool), and ``primal``, ``lower_bound``, ``violation`` (float64: the last evaluated certificate; ``+inf``, ``-inf``,
+    ``+inf`` before the first).  The two sums are in the kernel's own fixed order.  An LP without rows is stopped after 0
+    iterations; its ``primal`` and ``lower_bound`` are both the cost of its box vertex and its ``violation`` is 0.
+
+    Reports, callbacks, ``callback_func.info`` and the end of the loop are those of ``chambolle_pock_ppd_many_until``.
+    """
+    tol_gap, every = _many.check_stop(tol_gap, check_every, "tol_gap")
+    tol_feas, _ = _many.check_stop(tol_feas, check_every, "tol_feas")
+    return _cp_many_run(problems, x0, alpha, theta, nb_max_iter, callback_func, max_time, nb_iter_plot, None, (tol_gap, tol_feas, every))

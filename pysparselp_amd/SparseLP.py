@@ -24,7 +24,8 @@ import numpy as np
 import scipy.sparse
 
 from .ADMM import lp_admm, lp_admm_batch
-from .ChambollePockPPD import chambolle_pock_ppd, chambolle_pock_ppd_batch, chambolle_pock_ppd_many, chambolle_pock_ppd_many_until
+from .ChambollePockPPD import (chambolle_pock_ppd, chambolle_pock_ppd_batch, chambolle_pock_ppd_many, chambolle_pock_ppd_many_certified,
+                               chambolle_pock_ppd_many_until)
 from ._many import check_stop
 from ._batch import check_costs, require_one_sided
 from ._lib import ORDER_AUTO
@@ -772,6 +773,52 @@ def solve_many_until(lps, tol, check_every=10, get_timing=True, nb_iter=10000, m
     for k, lp in enumerate(lps):
         lp.nb_iterations = int(info["iterations"][k])
         lp.stopped = bool(info["stopped"][k])
+    elapsed = time.perf_counter() - start
+    return (xs, elapsed) if get_timing else xs
+
+
+def solve_many_certified(lps, tol_gap, tol_feas, check_every=10, get_timing=True, nb_iter=10000, max_time=None, nb_iter_plot=10):
+    """``solve_many`` with a certificate as the stopping test per LP (``ChambollePockPPD.chambolle_pock_ppd_many_certified``): every
+    LP of the list stops on its own at the first iteration ``t`` with ``t % check_every == 0`` at which its violation is at most
+    ``tol_feas`` and the gap between its primal value and a valid lower bound is at most ``tol_gap * (1 + |primal| + |bound|)``;
+    the others go on, at most ``nb_iter`` iterations.  Returns the list of ``x``, or ``(xs, elapsed)`` with ``get_timing``;
+    ``tol_gap`` and ``tol_feas`` finite floats ``>= 0`` and ``check_every`` an int ``>= 1``, a ``ValueError`` otherwise.
+
+    The LPs are prepared as ``solve_many`` prepares them.  Sets on every LP ``lp.nb_iterations`` (iterations completed; for a
+    stopped LP its stopping iteration), ``lp.stopped``, and the last evaluated certificate: ``lp.primal_objective``,
+    ``lp.lower_bound`` and ``lp.max_violation``.  These three are the numbers of the LP the solver holds, AFTER
+    ``remove_fixed_variables``: the cost of the removed variables at their fixed values is not in them.  It is given separately
+    as ``lp.fixed_cost``; add it to ``lp.primal_objective`` and to ``lp.lower_bound`` for the value and the bound of the LP as it
+    was handed in.  As for ``solve_many_until`` a stopped LP records nothing after it has stopped, and ``xs[k]`` is bit for bit
+    ``lps[k].solve(method="chambolle_pock_ppd", nb_iter=lp.nb_iterations, order=ORDER_SEQUENTIAL, setup="host")``.  ``max_time``
+    stops all LPs at a report.
+    """
+    check_stop(tol_gap, check_every, "tol_gap")
+    check_stop(tol_feas, check_every, "tol_feas")
+    lps = list(lps)
+    if len(lps) < 1:
+        raise ValueError("an empty list of LPs")
+    start = time.perf_counter()
+    problems, expand = _many_reduced(lps)
+    skip = np.zeros(len(lps), dtype=bool)
+    fill = _list_recorder(lps, expand, skip=skip)
+
+    def record(*report):
+        skip[:] = record.info["stopped"]   # current at every callback: chambolle_pock_ppd_many_certified sets the attribute
+        fill(*report)
+
+    sols, _, info = chambolle_pock_ppd_many_certified(problems, tol_gap, tol_feas, check_every, x0=None, alpha=1, theta=1,
+                                                      nb_max_iter=nb_iter, callback_func=record, max_time=max_time,
+                                                      nb_iter_plot=nb_iter_plot)
+    xs = [expand(k, sol) for k, sol in enumerate(sols)]
+    for k, lp in enumerate(lps):
+        lp.nb_iterations = int(info["iterations"][k])
+        lp.stopped = bool(info["stopped"][k])
+        lp.primal_objective = float(info["primal"][k])
+        lp.lower_bound = float(info["lower_bound"][k])
+        lp.max_violation = float(info["violation"][k])
+        fixed = ~(lp.upper_bounds > lp.lower_bounds)
+        lp.fixed_cost = float(np.dot(lp.costsvector[fixed], lp.lower_bounds[fixed]))
     elapsed = time.perf_counter() - start
     return (xs, elapsed) if get_timing else xs
 

@@ -104,6 +104,8 @@ _SIGNATURES = {
     "slp_cp_many_bench": (c_int, [c_vp, c_i64, c_vp]),
     "slp_many_cp_set_stop": (c_int, [c_vp, c_dbl, c_i64]),
     "slp_many_cp_stop_state": (c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "slp_many_cpgap_set_stop": (c_int, [c_vp, c_dbl, c_dbl, c_i64]),
+    "slp_many_cpgap_state": (c_int, [c_vp] * 6),
     "slp_gs_create": (c_vp, [c_i64, c_vp, c_vp, c_vp]),
     "slp_gs_destroy": (None, [c_vp]),
     "slp_gs_num_levels": (c_i64, [c_vp]),

@@ -40,6 +40,23 @@
 // in the launch in which it stops it leaves the loop and, in the lds form, writes its iterates back.  Between primal_step and
 // dual_step the reduced dx waits in the record.  The count of an LP is read from the record at the start of a launch, so the
 // stopping iteration does not depend on how a run is split into launches.
+//
+// Stopping on a certified duality gap (slp_many_cpgap_set_stop; arming one test disarms the other).  y is dual feasible for a
+// box-bounded LP by construction (free equality multipliers, clamped inequality multipliers), so with d = c + K^T y_t -- the bits
+// the next primal half computes -- bound = sum_j [d_j != 0 ? min(d_j lb_j, d_j ub_j) : 0] - sum_r [y_r != 0 ? y_r b_r : 0] is a
+// lower bound on the LP's value (the reference's energy2, :262-266, evaluated there at reports only); primal = sum_j c_j x_t,j;
+// violation = max(max_{r < m_eq} |(K x_t)_r - b_r|, max_{r >= m_eq} ((K x_t)_r - b_r), 0) with K x_t a single-accumulator chain
+// in storage order and the maximum NaN-propagating: exact in any order.  At the end of an iteration t with t % check_every == 0 the LP
+// stops iff violation <= tol_feas and |primal - bound| <= tol_gap (1 + |primal| + |bound|) with a finite left-hand side (inf <=
+// tol_gap * inf holds in IEEE arithmetic; a bound of -inf must not stop).  k_cpm_iterate_gap is the third kind of k_cpm_iterate, a
+// template of its own so that the two above stay textually what they were.  An iteration that is no check is the text of STOP =
+// false plus two scalar counters.  A check iteration has its own copy of the dual loop -- K x beside K z in one row walk, per lane
+// sum y_r b_r over its rows in increasing order and the nan-max of the violation -- then, behind the dual half's barrier, one pass over
+// the columns (d_j, its term of the bound, c_j x_j).  A wave reduces its lanes by shuffles in a fixed order (many_wave_sum,
+// many_wave_nanmax) into one LDS slot per quantity; behind one more barrier lane 0 folds the waves in increasing order, writes
+// the record CpmGap (primal, bound, violation: +inf, -inf, +inf before the first check) and ONE decision slot, and a last barrier
+// later every lane reads it.  The two sums are in that fixed order, a function of the shapes only.  done, stopped and stop_iter of
+// CpmCtl are shared with the step test; nothing waits in a record between primal_step and dual_step.
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -220,6 +237,177 @@ __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int ite
     }
 }
 
+// per LP, beside CpmCtl: the numbers of the last evaluated certificate (+inf, -inf, +inf before the first); written by lane 0 of
+// the LP's workgroup in a check iteration of k_cpm_iterate_gap only
+struct CpmGap {
+    double primal, bound, violation;
+};
+
+struct CpmGapStop {
+    CpmCtl *ctl;  // done, stopped, stop_iter: shared with the step test; step and dx are not touched
+    CpmGap *rec;
+    double tol_gap, tol_feas;
+    i64 check_every;
+};
+
+// min as np.minimum: a NaN on either side stays
+__device__ __forceinline__ double cpm_nanmin(double a, double b) { return (b < a || b != b) ? b : a; }
+
+// cp_row_sum with a second chain beside it: K z and K x of one row in one walk, each a single accumulator in storage order
+template <class LD>
+__device__ __forceinline__ void cpm_row_sums2(i64 s, i64 e, const i32 *__restrict__ idx, const double *__restrict__ val, const double *__restrict__ z,
+                                              const double *__restrict__ x, LD ld, double *kz_out, double *kx_out) {
+    double kz = 0.0, kx = 0.0;
+    for (i64 q0 = s; q0 < e; q0 += 4) {
+        i32 j[4];
+        double a[4], g[4], h[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const i64 qq = (q0 + q < e) ? q0 + q : e - 1;
+            j[q] = idx[qq];
+            a[q] = val[qq];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            g[q] = ld(z + j[q]);
+            h[q] = ld(x + j[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (q0 + q < e) {
+                kz += a[q] * g[q];
+                kx += a[q] * h[q];
+            }
+    }
+    *kz_out = kz;
+    *kx_out = kx;
+}
+
+// The third kind of k_cpm_iterate: the iteration of STOP = false with the duality-gap certificate as the per-LP stopping test
+// (header comment).  A kernel of its own, so that the two instantiations above stay what they are; the iteration outside a check
+// is the text of STOP = false plus two scalar counters, and a check iteration has its own copy of the dual loop.  Every branch
+// around a barrier is on `stages`, `check`, the record or the decision slot: uniform.
+template <bool LDS>
+__global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate_gap(CpmArgs a, int iters, int stages, int store, CpmGapStop sp) {
+    extern __shared__ __attribute__((aligned(16))) double cpm_lds[];
+    __shared__ double cpm_red[4 * kCpmWaves + 1];  // per wave: sum y b, violation, c x, the bound's column terms; then the decision
+    using LD = typename std::conditional<LDS, CpLoadPlain, CpLoadWorkgroup>::type;
+    const LD ld;
+    const i32 id = a.list[blockIdx.x];
+    const CpmLp lp = a.lps[id];
+    const i32 n = lp.n, m = lp.m_eq + lp.m_in, W = (i32)blockDim.x, tid = (i32)threadIdx.x;
+    const CpmCtl *ctl0 = sp.ctl + id;
+    if (ctl0->stopped) return;  // set before the launch: the same for every lane
+    i64 done = ctl0->done;      // lane 0 writes the record only behind a barrier that follows this load
+    i64 until = sp.check_every - done % sp.check_every;
+    const bool has_eq = lp.m_eq > 0, has_in = lp.m_in > 0;
+    double *xg = a.x + lp.col0, *zg = a.z + lp.col0, *yg = a.y + lp.y0;
+    double *xs = xg, *zs = zg, *ys = yg;
+    if (LDS) {
+        xs = cpm_lds;
+        zs = xs + n;
+        ys = zs + n;
+        for (i32 j = tid; j < n; j += W) { xs[j] = xg[j]; zs[j] = zg[j]; }
+        for (i32 r = tid; r < m; r += W) ys[r] = yg[r];
+        __syncthreads();
+    }
+    const double *c = a.c + lp.col0, *t = a.t + lp.col0, *lb = a.lb + lp.col0, *ub = a.ub + lp.col0;
+    const i64 *tptr = a.tptr + lp.col0;
+    for (int it = 0; it < iters; ++it) {
+        if (stages & 1) {
+            for (i32 j = tid; j < n; j += W) {
+                double se, si;
+                cp_column_sums(tptr[j], tptr[j + 1], a.tidx, a.tval, ys, 1, lp.m_eq, ld, &se, &si);
+                const double d = cp_direction(c[j], se, si, has_eq, has_in);
+                const double xo = ld(xs + j), l = lb[j], u = ub[j];
+                double x2, zn;
+                cp_primal_point(d, xo, t[j], l, u, a.one_plus_theta, a.theta, &x2, &zn);
+                zs[j] = zn;
+                xs[j] = x2;
+                if (store) a.x4[lp.col0 + j] = (d < 0.0) ? u : l;
+            }
+            __syncthreads();  // same compute unit: the stores of this half are visible to the next one
+        }
+        if (!(stages & 2)) continue;  // primal_step: the certificate needs nothing of this half but x itself
+        if (until != 1) {             // no check: the dual half of STOP = false
+            for (i32 r = tid; r < m; r += W) {
+                const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
+                const double kz = cp_row_sum(a.ptr[g], a.ptr[g + 1], a.idx, a.val, zs, 1, ld);
+                ys[r] = cp_dual_point(kz, a.b[g], ld(ys + r), a.sigma[g], r >= lp.m_eq);
+            }
+            __syncthreads();
+            ++done;
+            --until;
+            continue;
+        }
+        // a check iteration: the dual half with K x beside K z, then the certificate pass over the columns
+        double yb = 0.0, viol = 0.0;
+        for (i32 r = tid; r < m; r += W) {
+            const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
+            double kz, kx;
+            cpm_row_sums2(a.ptr[g], a.ptr[g + 1], a.idx, a.val, zs, xs, ld, &kz, &kx);
+            const double bi = a.b[g], yn = cp_dual_point(kz, bi, ld(ys + r), a.sigma[g], r >= lp.m_eq);
+            ys[r] = yn;
+            if (yn != 0.0) yb += yn * bi;  // the guard keeps 0 * inf out (a row without a finite bound has y = 0)
+            const double v = kx - bi;
+            viol = many_nanmax(viol, r < lp.m_eq ? fabs(v) : v);
+        }
+        yb = many_wave_sum(yb);
+        viol = many_wave_nanmax(viol);
+        if ((tid & (kWave - 1)) == 0) {
+            cpm_red[tid / kWave] = yb;
+            cpm_red[kCpmWaves + tid / kWave] = viol;
+        }
+        __syncthreads();  // the barrier that ends the dual half: y is the y of this iteration
+        double cx = 0.0, bt = 0.0;
+        for (i32 j = tid; j < n; j += W) {
+            double se, si;
+            cp_column_sums(tptr[j], tptr[j + 1], a.tidx, a.tval, ys, 1, lp.m_eq, ld, &se, &si);
+            const double d = cp_direction(c[j], se, si, has_eq, has_in);  // the bits the next primal half computes
+            cx += c[j] * ld(xs + j);
+            if (d != 0.0) bt += cpm_nanmin(d * lb[j], d * ub[j]);
+        }
+        cx = many_wave_sum(cx);
+        bt = many_wave_sum(bt);
+        if ((tid & (kWave - 1)) == 0) {
+            cpm_red[2 * kCpmWaves + tid / kWave] = cx;
+            cpm_red[3 * kCpmWaves + tid / kWave] = bt;
+        }
+        __syncthreads();  // the slots of every wave are written
+        ++done;
+        until = sp.check_every;
+        if (tid == 0) {
+            double sy = cpm_red[0], vmax = cpm_red[kCpmWaves], primal = cpm_red[2 * kCpmWaves], cols = cpm_red[3 * kCpmWaves];
+            for (i32 w = 1; w < W / kWave; ++w) {  // the waves in increasing order
+                sy += cpm_red[w];
+                vmax = many_nanmax(vmax, cpm_red[kCpmWaves + w]);
+                primal += cpm_red[2 * kCpmWaves + w];
+                cols += cpm_red[3 * kCpmWaves + w];
+            }
+            const double bound = cols - sy, gap = fabs(primal - bound);
+            // false for a NaN; an infinite gap (bound = -inf) never stops, whatever tol_gap * inf would say
+            const bool stop = vmax <= sp.tol_feas && gap < __builtin_inf() && gap <= sp.tol_gap * (1.0 + fabs(primal) + fabs(bound));
+            CpmGap *rec = sp.rec + id;
+            rec->primal = primal;
+            rec->bound = bound;
+            rec->violation = vmax;
+            if (stop) {
+                CpmCtl *ctl = sp.ctl + id;
+                ctl->stopped = 1;
+                ctl->stop_iter = done;
+            }
+            cpm_red[4 * kCpmWaves] = stop ? 1.0 : 0.0;
+        }
+        __syncthreads();
+        if (cpm_red[4 * kCpmWaves] != 0.0) break;  // one slot, read by every lane: uniform
+    }
+    if ((stages & 2) && tid == 0) sp.ctl[id].done = done;
+    if (LDS) {
+        for (i32 j = tid; j < n; j += W) { xg[j] = xs[j]; zg[j] = zs[j]; }
+        for (i32 r = tid; r < m; r += W) yg[r] = ys[r];
+    }
+}
+
 // out[5 k + 0..4] as slp_cp_report; one workgroup per LP
 __global__ __launch_bounds__(kBlock) void k_cpm_report(CpmArgs a, double *__restrict__ out) {
     __shared__ double lds[kBlock / kWave];
@@ -285,6 +473,9 @@ struct slp_cp_many {
     DevBuf<CpmCtl> ctl;
     double tol = -1.0;
     i64 check_every = 1, uncounted = 0;
+    // the certificate (slp_many_cpgap_set_stop): off while tol_gap < 0; at most one of the two tests is armed
+    DevBuf<CpmGap> gap;
+    double tol_gap = -1.0, tol_feas = 0.0;
     ~slp_cp_many() { delete k; }
 };
 
@@ -306,18 +497,21 @@ static CpmArgs cpm_args(const slp_cp_many *s, int g) {
 }
 
 template <bool LDS>
-static void cpm_launch(const slp_cp_many *s, const ManyGroup &gr, const CpmArgs &a, int it, int stages, bool store, bool stop) {
+static void cpm_launch(const slp_cp_many *s, const ManyGroup &gr, const CpmArgs &a, int it, int stages, bool store, int stop) {
     const CpmStop sp = {s->ctl.p, s->tol, s->check_every};
     const dim3 grid((unsigned)gr.ids.size()), block(gr.block);
     const size_t lds = LDS ? gr.lds_bytes : 0;
-    if (stop) hipLaunchKernelGGL((k_cpm_iterate<LDS, true>), grid, block, lds, ctx().stream, a, it, stages, (int)store, sp);
+    if (stop == 2) {
+        const CpmGapStop gp = {s->ctl.p, s->gap.p, s->tol_gap, s->tol_feas, s->check_every};
+        hipLaunchKernelGGL((k_cpm_iterate_gap<LDS>), grid, block, lds, ctx().stream, a, it, stages, (int)store, gp);
+    } else if (stop) hipLaunchKernelGGL((k_cpm_iterate<LDS, true>), grid, block, lds, ctx().stream, a, it, stages, (int)store, sp);
     else hipLaunchKernelGGL((k_cpm_iterate<LDS, false>), grid, block, lds, ctx().stream, a, it, stages, (int)store, sp);
 }
 
-// `k` times the stages, in launches of at most kmax iterations per form; with the stopping test when it is armed, unless
-// `plain` (the half-iteration timings of slp_cp_many_bench, which are no iterations)
+// `k` times the stages, in launches of at most kmax iterations per form; with the stopping test that is armed (1 the step, 2 the
+// certificate), unless `plain` (the half-iteration timings of slp_cp_many_bench, which are no iterations)
 static void cpm_run(slp_cp_many *s, i64 k, int stages, bool store, bool plain = false) {
-    const bool stop = s->tol >= 0.0 && !plain;
+    const int stop = plain ? 0 : (s->tol_gap >= 0.0 ? 2 : (s->tol >= 0.0 ? 1 : 0));
     if (!stop && !plain && (stages & 2)) s->uncounted += k;
     for (int g = 0; g < 2; ++g) {
         const ManyGroup &gr = s->group[g];
@@ -413,7 +607,7 @@ slp_cp_many *slp_cp_many_create(int64_t count, const int64_t *n, const int64_t *
         // three over the rows (y, b, Sigma), the table, the lists and the report
         many_require_memory("slp_cp_many_create", count,
                             40.0 * (double)nnz + 16.0 * (double)(N + M + 2) + 8.0 * (7.0 * (double)N + 3.0 * (double)M) +
-                                (double)count * (double)(sizeof(CpmLp) + sizeof(CpmCtl) + sizeof(i32) + 5 * sizeof(double)));
+                                (double)count * (double)(sizeof(CpmLp) + sizeof(CpmCtl) + sizeof(CpmGap) + sizeof(i32) + 5 * sizeof(double)));
         s->k = slp_matrix_create(M, N, indptr, indices, data);
         if (!s->k) throw Error(slp_last_error());
         require_csr(s->k, "slp_cp_many_create");
@@ -428,6 +622,7 @@ slp_cp_many *slp_cp_many_create(int64_t count, const int64_t *n, const int64_t *
         many_upload_lists(s->group, s->list);
         many_lds_opt_in(reinterpret_cast<const void *>(k_cpm_iterate<true, false>), s->group[0].lds_bytes, kCpmLdsLimit * sizeof(double));
         many_lds_opt_in(reinterpret_cast<const void *>(k_cpm_iterate<true, true>), s->group[0].lds_bytes, kCpmLdsLimit * sizeof(double));
+        many_lds_opt_in(reinterpret_cast<const void *>(k_cpm_iterate_gap<true>), s->group[0].lds_bytes, kCpmLdsLimit * sizeof(double));
         s->c.upload(c, (size_t)N);
         s->lb.upload(lb, (size_t)N);
         s->ub.upload(ub, (size_t)N);
@@ -443,6 +638,8 @@ slp_cp_many *slp_cp_many_create(int64_t count, const int64_t *n, const int64_t *
         s->out.alloc((size_t)5 * (size_t)count);
         std::vector<CpmCtl> ctl((size_t)count, CpmCtl{0, 0, __builtin_inf(), 0.0, 0, 0});
         s->ctl.upload(ctl.data(), ctl.size());
+        std::vector<CpmGap> gap((size_t)count, CpmGap{__builtin_inf(), -__builtin_inf(), __builtin_inf()});
+        s->gap.upload(gap.data(), gap.size());
         SLP_HIP(hipStreamSynchronize(ctx().stream));
         return s.release();
     })
@@ -480,7 +677,43 @@ int slp_many_cp_set_stop(slp_cp_many *s, double tol, int64_t check_every) {
         s->ctl.upload(h.data(), h.size());
         s->uncounted = 0;
         s->tol = tol < 0.0 ? -1.0 : tol;
+        s->tol_gap = -1.0;  // arming one test disarms the other
         if (tol >= 0.0) s->check_every = check_every;
+    })
+}
+
+int slp_many_cpgap_set_stop(slp_cp_many *s, double tol_gap, double tol_feas, int64_t check_every) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_cpgap_set_stop: NULL handle");
+        SLP_REQUIRE(tol_gap < 0.0 || (std::isfinite(tol_gap) && std::isfinite(tol_feas) && tol_feas >= 0.0 && check_every >= 1),
+                    "slp_many_cpgap_set_stop: tol_gap and tol_feas must be finite and >= 0 with check_every >= 1 (tol_gap < 0 turns the "
+                    "test off)");
+        std::vector<CpmCtl> h = cpm_read_ctl(s);
+        for (CpmCtl &c : h) c.stopped = 0;
+        s->ctl.upload(h.data(), h.size());
+        s->uncounted = 0;
+        s->tol = -1.0;  // arming one test disarms the other
+        s->tol_gap = tol_gap < 0.0 ? -1.0 : tol_gap;
+        if (tol_gap >= 0.0) {
+            s->tol_feas = tol_feas;
+            s->check_every = check_every;
+        }
+    })
+}
+
+int slp_many_cpgap_state(slp_cp_many *s, int64_t *iterations, int32_t *stopped, double *primal, double *bound, double *violation) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_cpgap_state: NULL handle");
+        const std::vector<CpmCtl> h = cpm_read_ctl(s);
+        std::vector<CpmGap> g(h.size());
+        s->gap.download(g.data(), g.size());
+        for (size_t k = 0; k < h.size(); ++k) {
+            if (iterations) iterations[k] = h[k].stopped ? h[k].stop_iter : h[k].done;
+            if (stopped) stopped[k] = h[k].stopped;
+            if (primal) primal[k] = g[k].primal;
+            if (bound) bound[k] = g[k].bound;
+            if (violation) violation[k] = g[k].violation;
+        }
     })
 }
 

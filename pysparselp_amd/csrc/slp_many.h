@@ -20,6 +20,14 @@ __device__ __forceinline__ double many_wave_nanmax(double v) {
     return v;
 }
 
+// the sum over the 64 lanes of a wave, by shuffles in a fixed order (32, 16, ..., 1): lane 0 holds the result, a function of the
+// lanes' values only (the certificate of slp_cp_many.hip)
+__device__ __forceinline__ double many_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+    return v;
+}
+
 // the lists of the LPs of each form, on the device
 inline void many_upload_lists(const ManyGroup group[2], DevBuf<i32> list[2]) {
     for (int g = 0; g < 2; ++g)
