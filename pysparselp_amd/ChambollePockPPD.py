@@ -437,6 +437,38 @@ class CPBatchState:
         _lib.check(self._l.slp_cp_batch_bench(self._h, int(k), _lib.ptr(ms)))
         return ms
 
+    def set_stop_gap(self, tol_gap, tol_feas, check_every=1):
+        """Arms the certificate as the per-instance stopping test (``slp_cp_batch_set_stop_gap``, include/slp_hip_ext.h); the
+        certificate is that of ``CPManyState.set_stop_gap``.  The state counts its whole iterations ``t`` from 1 over its life,
+        those before the arming included.  At the end of every iteration ``t`` with ``t % check_every == 0`` each running instance
+        evaluates, for the LP the solver holds (``K = [A_eq; A_ineq]`` one-sided, ``y_t`` the clamped multipliers), ``primal =
+        c.x_t``, the lower bound ``sum_j min(d_j lb_j, d_j ub_j) - y_t.b`` with ``d = c + K^T y_t`` (terms with ``d_j == 0`` or ``y_r
+        == 0`` left out; ``-inf`` where a free variable has ``d_j`` of the wrong sign) and ``violation = max(max|A_eq x_t - b_eq|,
+        max(A_ineq x_t - b_ineq), 0)``; it stops iff ``violation <= tol_feas`` and ``|primal - bound| <= tol_gap * (1 + |primal| +
+        |bound|)`` with a finite left-hand side.  A NaN never stops.  A stopped instance keeps its iterate -- bit for bit that of
+        the batch without a test after as many iterations -- while the others go on.
+
+        Unlike an LP of a list, a stopped instance STAYS stopped for the life of the state: the batch has one iteration counter.
+        Calling this again changes the tolerances and the cadence for the running instances and keeps the flags.  ``tol_gap=None``
+        disarms: the running instances go on untested, the stopped ones stay frozen.  Once every instance is stopped ``iterate``
+        and ``dual_step`` do nothing and the count of iterations stays.  Between whole iterations only."""
+        if tol_gap is None:
+            tol_gap, tol_feas, check_every = -1.0, 0.0, 1
+        else:
+            tol_gap, check_every = _many.check_stop(tol_gap, check_every, "tol_gap")
+            tol_feas, _ = _many.check_stop(tol_feas, check_every, "tol_feas")
+        _lib.check(self._l.slp_cp_batch_set_stop_gap(self._h, tol_gap, tol_feas, check_every))
+
+    def gap_state(self):
+        """``(iterations, stopped, primal, bound, violation)`` per instance, int64, bool and three float64 arrays: the iterations
+        completed (for a stopped instance its stopping iteration), whether it is stopped, and the numbers of the last evaluated
+        certificate (``+inf``, ``-inf``, ``+inf`` before the first).  A stopped instance stays stopped for the life of the state."""
+        iterations, stopped = np.zeros(self.batch, dtype=np.int64), np.zeros(self.batch, dtype=np.int32)
+        primal, bound, violation = np.zeros(self.batch), np.zeros(self.batch), np.zeros(self.batch)
+        _lib.check(self._l.slp_cp_batch_gap_state(self._h, _lib.ptr(iterations), _lib.ptr(stopped), _lib.ptr(primal), _lib.ptr(bound),
+                                                  _lib.ptr(violation)))
+        return iterations, stopped.astype(bool), primal, bound, violation
+
 
 def _cp_report_loop(state, costs, has_ineq, slots, best, all_x, spread, nb_max_iter, nb_iter_plot, callback_func, max_time, start,
                     stopped_now=None):
@@ -528,6 +560,16 @@ def chambolle_pock_ppd_batch(
 
     Under a communicator every rank solves the whole batch (a replica): the rows are not partitioned.
     """
+    x, best, _ = _cp_batch_run(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, alpha, theta, nb_max_iter, callback_func, max_time,
+                               nb_iter_plot)
+    return x if best is None else (x, best)
+
+
+def _cp_batch_run(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, alpha, theta, nb_max_iter, callback_func, max_time, nb_iter_plot,
+                  gap=None):
+    """``chambolle_pock_ppd_batch`` (``gap`` None) and ``chambolle_pock_ppd_batch_certified`` (``gap`` the checked ``(tol_gap,
+    tol_feas, check_every)``): ``(X, best_integer_solutions, info)``; ``best_integer_solutions`` is None for a batch without
+    constraint rows, ``info`` None without a stopping test."""
     start = time.perf_counter()
     c = np.asarray(c, dtype=np.float64)
     if c.ndim != 2:
@@ -553,7 +595,13 @@ def chambolle_pock_ppd_batch(
     if a_eq is not None:
         beq, _ = shared_or_batched("beq", beq, batch, a_eq.shape[0])
     if a_eq is None and a_ineq is None:  # reference :147-151: no constraints, a vertex of the box per instance
-        return box_vertex(c, lb, ub)
+        x = box_vertex(c, lb, ub)
+        info = None
+        if gap is not None:   # the vertex is optimal: primal and bound are its value
+            value = np.array([c[k].dot(x[k]) for k in range(batch)])
+            info = dict(iterations=np.zeros(batch, dtype=np.int64), stopped=np.ones(batch, dtype=bool), primal=value,
+                        lower_bound=value.copy(), violation=np.zeros(batch))
+        return x, None, info
     ineq, b_ineq = (None, None)
     if a_ineq is not None:
         rows = a_ineq.shape[0]
@@ -563,14 +611,68 @@ def chambolle_pock_ppd_batch(
         ineq, b_ineq = one_sided_system_batch(a_ineq, b_lower, b_upper)
         assert b_ineq.shape[-1] == ineq[3]
 
+    info = None
+    if gap is not None:
+        info = dict(iterations=np.zeros(batch, dtype=np.int64), stopped=np.zeros(batch, dtype=bool), primal=np.full(batch, np.inf),
+                    lower_bound=np.full(batch, -np.inf), violation=np.full(batch, np.inf))
     state = CPBatchState(c, a_eq, beq, ineq, b_ineq, lb, ub, x0, alpha, theta)
     best = [None] * batch
+
+    def stopped_now():
+        now = state.gap_state()
+        for name, values in zip(_GAP_INFO, now):
+            info[name][:] = values
+        return now[1]
+
     try:
+        if gap is not None:
+            state.set_stop_gap(*gap)
+            if callback_func is not None:
+                try:
+                    callback_func.info = info
+                except AttributeError:   # a bound method takes no attribute: wrap it in a function to read ``info``
+                    pass
         x = _cp_report_loop(state, c, np.full(batch, a_ineq is not None), range(batch), best, lambda x: x,
-                            lambda values, energy=False: values, nb_max_iter, nb_iter_plot, callback_func, max_time, start)
+                            lambda values, energy=False: values, nb_max_iter, nb_iter_plot, callback_func, max_time, start,
+                            None if gap is None else stopped_now)
+        if gap is not None:
+            stopped_now()
     finally:
         state.close()
-    return x, best
+    return x, best, info
+
+
+def chambolle_pock_ppd_batch_certified(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, tol_gap, tol_feas, check_every=10, x0=None,
+                                       alpha=1, theta=1, nb_max_iter=10000, callback_func=None, max_time=None, nb_iter_plot=10):
+    """``chambolle_pock_ppd_batch`` with a certificate as the stopping test per instance (extension; the reference evaluates the
+    same lower bound, its ``energy2``, at its reports and stops on nothing): the batch runs until every instance has stopped, at
+    most ``nb_max_iter`` iterations.  Returns ``(X, best_integer_solutions, info)``.
+
+    The test is that of ``chambolle_pock_ppd_many_certified``, made on the device after the dual half of every iteration ``t``
+    with ``t % check_every == 0``, iterations counted from 1 (``CPBatchState.set_stop_gap``), on the LP the solver holds: with
+    ``primal = c[k].x_t``, ``lower_bound = sum_j min(d_j lb_j, d_j ub_j) - y_t.b`` for ``d = c[k] + K^T y_t`` and ``violation =
+    max(max|A_eq x_t - b_eq|, max(A_ineq x_t - b_ineq), 0)`` instance ``k`` stops iff ``violation <= tol_feas`` and ``|primal -
+    lower_bound| <= tol_gap * (1 + |primal| + |lower_bound|)`` with a finite left-hand side; an instance with a lower bound of
+    ``-inf`` or a NaN does not stop.  A stopped instance keeps its iterate after ``t`` iterations, bit for bit that of
+    ``chambolle_pock_ppd(..., nb_max_iter=t, order=ORDER_SEQUENTIAL)``, while the others go on; it stays stopped.  ``tol_gap`` and
+    ``tol_feas`` are finite floats ``>= 0``, ``check_every`` an int ``>= 1``: a ``ValueError`` before the library is loaded
+    otherwise, like every shape error.
+
+    ``info`` is a dict of arrays of length B: ``iterations`` (int64: completed, for a stopped instance its stopping iteration),
+    ``stopped`` (bool), and ``primal``, ``lower_bound``, ``violation`` (float64: the last evaluated certificate; ``+inf``, ``-inf``,
+    ``+inf`` before the first).  The two sums are in the device's own fixed order.  Without any constraint row every instance is
+    stopped after 0 iterations at its box vertex: ``primal`` and ``lower_bound`` are both its cost, ``violation`` is 0 and
+    ``best_integer_solutions`` is a list of ``None``.
+
+    Reports, callbacks, ``callback_func.info`` (the same dict, updated in place, current at every callback) and the end of the
+    loop are those of ``chambolle_pock_ppd_many_until``: the loop ends at the first report index at which every instance is
+    stopped, at ``nb_max_iter``, or at ``max_time``; a stopped instance's five numbers repeat the last row it had while it ran.
+    """
+    tol_gap, every = _many.check_stop(tol_gap, check_every, "tol_gap")
+    tol_feas, _ = _many.check_stop(tol_feas, check_every, "tol_feas")
+    x, best, info = _cp_batch_run(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, alpha, theta, nb_max_iter, callback_func, max_time,
+                                  nb_iter_plot, (tol_gap, tol_feas, every))
+    return x, ([None] * x.shape[0] if best is None else best), info
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -24,8 +24,8 @@ import numpy as np
 import scipy.sparse
 
 from .ADMM import lp_admm, lp_admm_batch
-from .ChambollePockPPD import (chambolle_pock_ppd, chambolle_pock_ppd_batch, chambolle_pock_ppd_many, chambolle_pock_ppd_many_certified,
-                               chambolle_pock_ppd_many_until)
+from .ChambollePockPPD import (chambolle_pock_ppd, chambolle_pock_ppd_batch, chambolle_pock_ppd_batch_certified, chambolle_pock_ppd_many,
+                               chambolle_pock_ppd_many_certified, chambolle_pock_ppd_many_until)
 from ._many import check_stop
 from ._batch import check_costs, require_one_sided
 from ._lib import ORDER_AUTO
@@ -607,6 +607,62 @@ class SparseLP:
                                        reduced.b_lower, reduced.b_upper, reduced.lower_bounds, reduced.upper_bounds, x0=None, alpha=1,
                                        theta=1, nb_max_iter=nb_iter, callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
         x = expand(res[0] if isinstance(res, tuple) else res)
+        elapsed = time.perf_counter() - start
+        return (x, elapsed) if get_timing else x
+
+    def solve_batch_certified(
+        self,
+        costs,
+        tol_gap,
+        tol_feas,
+        check_every=10,
+        get_timing=True,
+        nb_iter=10000,
+        max_time=None,
+        nb_iter_plot=10,
+        ground_truth=None,
+        ground_truth_indices=None,
+    ):
+        """``solve_batch`` with a certificate as the stopping test per instance
+        (``ChambollePockPPD.chambolle_pock_ppd_batch_certified``): every instance stops on its own at the first iteration ``t`` with
+        ``t % check_every == 0`` at which its violation is at most ``tol_feas`` and the gap between its primal value and a valid
+        lower bound is at most ``tol_gap * (1 + |primal| + |bound|)``; the others go on, at most ``nb_iter`` iterations.  Returns
+        ``(X, elapsed)`` or ``X``; ``tol_gap`` and ``tol_feas`` finite floats ``>= 0`` and ``check_every`` an int ``>= 1``, a
+        ``ValueError`` otherwise.
+
+        The reduction (``remove_fixed_variables``, once for all instances) and the curves are those of ``solve_batch``; the loop
+        ends at the first report at which every instance is stopped, and a stopped instance's curve entries repeat its last
+        running row.  ``X[k]`` is bit for bit ``solve_batch(costs, nb_iter=batch_info["iterations"][k])[k]``.
+
+        Sets ``self.batch_info``, a dict of arrays of length B: ``iterations`` (completed; for a stopped instance its stopping
+        iteration), ``stopped``, and the last evaluated certificate ``primal``, ``lower_bound``, ``violation``.  These three are
+        the numbers of the LP the solver holds, AFTER ``remove_fixed_variables``: the cost of the removed variables at their
+        fixed values is not in them.  It is given separately as ``fixed_cost`` (per instance, from its row of ``costs``); add it
+        to ``primal`` and to ``lower_bound`` for the value and the bound of the LP as it was handed in.
+        """
+        check_stop(tol_gap, check_every, "tol_gap")
+        check_stop(tol_feas, check_every, "tol_feas")
+        costs, batch = check_costs(costs, self.nb_variables)
+        start = time.perf_counter()
+        _reset_curves(self)
+        reduced = copy.deepcopy(self)
+        free, shift = reduced.remove_fixed_variables()
+        free_ids = np.nonzero(free)[0]
+
+        def expand(sol):
+            # reference :1259,:1288 per instance: x = m_change * sol - shift (note the sign it applies to the fixed values)
+            full = np.zeros((sol.shape[0], free.size))
+            full[:, free_ids] = sol
+            return full - shift
+
+        record = _batch_recorder(self, batch, ground_truth, ground_truth_indices, expand=expand)
+        sol, _, info = chambolle_pock_ppd_batch_certified(
+            costs[:, free], reduced.a_equalities, reduced.b_equalities, reduced.a_inequalities, reduced.b_lower, reduced.b_upper,
+            reduced.lower_bounds, reduced.upper_bounds, tol_gap, tol_feas, check_every, x0=None, alpha=1, theta=1, nb_max_iter=nb_iter,
+            callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
+        x = expand(sol)
+        fixed = ~(self.upper_bounds > self.lower_bounds)
+        self.batch_info = dict(info, fixed_cost=costs[:, fixed].dot(self.lower_bounds[fixed]))
         elapsed = time.perf_counter() - start
         return (x, elapsed) if get_timing else x
 

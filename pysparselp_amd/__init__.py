@@ -5,7 +5,9 @@ signature (modules mirror the reference's: ``SparseLP``, ``ADMM``, ``ChambollePo
 ``gaussSiedel``, ``MPSparser``, ``netlib``, ``tools``; ``device`` / ``scale`` / ``problems`` / ``parallel`` hold the
 device-resident, at-scale and multi-GPU entry points); the inner loops run in hand-written HIP kernels (libslp_hip.so,
 C ABI in include/slp_hip.h).  ``SparseLP.solve_batch`` / ``chambolle_pock_ppd_batch`` solve many cost vectors over one
-constraint matrix together (Chambolle-Pock, all instances per launch); ``SparseLP.solve_admm_batch`` / ``lp_admm_batch``
+constraint matrix together (Chambolle-Pock, all instances per launch; ``SparseLP.solve_batch_certified`` /
+``chambolle_pock_ppd_batch_certified`` stop every instance on its own, by a certified duality gap and the primal violation evaluated on
+the device, both handed back); ``SparseLP.solve_admm_batch`` / ``lp_admm_batch``
 do the same for ADMM with the projected Gauss-Seidel x-step, ``SparseLP.solve_dga_batch`` / ``dual_gradient_ascent_batch`` for dual
 gradient ascent (certified lower bounds of B LPs over one matrix); ``solve_many`` / ``chambolle_pock_ppd_many`` solve a list of
 LPs whose matrices differ, one workgroup per LP (Chambolle-Pock; ``solve_many_until`` / ``chambolle_pock_ppd_many_until`` stop every
@@ -19,8 +21,8 @@ library and a HIP device every solver call raises ``SlpError``.
 """
 from ._lib import ORDER_AUTO, ORDER_SEQUENTIAL, ORDER_TREE, SlpError  # noqa: F401
 from .ADMM import ADMMBatchState, ADMMManyState, lp_admm_batch, lp_admm_many, lp_admm_many_until  # noqa: F401
-from .ChambollePockPPD import (CPBatchState, CPManyState, chambolle_pock_ppd_batch, chambolle_pock_ppd_many,  # noqa: F401
-                               chambolle_pock_ppd_many_certified, chambolle_pock_ppd_many_until)
+from .ChambollePockPPD import (CPBatchState, CPManyState, chambolle_pock_ppd_batch, chambolle_pock_ppd_batch_certified,  # noqa: F401
+                               chambolle_pock_ppd_many, chambolle_pock_ppd_many_certified, chambolle_pock_ppd_many_until)
 from .DualGradientAscent import (DeviceDGABatch, DeviceDGAMany, dual_gradient_ascent_batch, dual_gradient_ascent_many,  # noqa: F401
                                  dual_gradient_ascent_many_until)
 from .SparseLP import solve_admm_many, solve_admm_many_until, solve_dga_many, solve_dga_many_until, solve_many, solve_many_until  # noqa: F401
@@ -30,4 +32,5 @@ __all__ = ["ORDER_AUTO", "ORDER_SEQUENTIAL", "ORDER_TREE", "SlpError", "CPBatchS
            "ADMMBatchState", "lp_admm_batch", "DeviceDGABatch", "dual_gradient_ascent_batch", "CPManyState", "chambolle_pock_ppd_many",
            "solve_many", "DeviceDGAMany", "dual_gradient_ascent_many", "solve_dga_many", "ADMMManyState", "lp_admm_many",
            "solve_admm_many", "chambolle_pock_ppd_many_until", "solve_many_until", "lp_admm_many_until", "solve_admm_many_until",
-           "dual_gradient_ascent_many_until", "solve_dga_many_until", "chambolle_pock_ppd_many_certified", "solve_many_certified"]
+           "dual_gradient_ascent_many_until", "solve_dga_many_until", "chambolle_pock_ppd_many_certified", "solve_many_certified",
+           "chambolle_pock_ppd_batch_certified"]

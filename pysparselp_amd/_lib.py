@@ -1,4 +1,4 @@
-"""ctypes binding of libslp_hip.so (include/slp_hip.h).
+"""ctypes binding of libslp_hip.so (include/slp_hip.h and include/slp_hip_ext.h).
 
 The library is the only execution path: if it is missing, cannot be loaded, or
 finds no HIP device, every solver entry point raises -- there is no CPU
@@ -251,6 +251,14 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# name -> (restype, argtypes); mirrors include/slp_hip_ext.h one to one: the entry points beyond include/slp_hip.h
+_EXT_SIGNATURES = {
+    "slp_cp_batch_set_stop_gap": (c_int, [c_vp, c_dbl, c_dbl, c_i64]),
+    "slp_cp_batch_gap_state": (c_int, [c_vp] * 6),
+}
+
+EXT_SYMBOLS = tuple(_EXT_SIGNATURES)
+
 # int fn(double *buf, int64_t count, int op, void *user): the host all-reduce of slp_comm_init_host
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, ctypes.POINTER(c_dbl), c_i64, c_int, c_vp)
 
@@ -273,7 +281,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as e:
         raise SlpError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -23,6 +23,24 @@
 // pass c.x, c.x4; row r (column j) belongs to slice r mod S, S = the number of row groups of the launch (<= 1024, a
 // function of the shapes only); a slice adds its terms in increasing r, and one lane per instance adds the S slice sums
 // in increasing slice order (maxima are exact in any order).  x4 is written by the primal half of a reporting iteration.
+//
+// Stopping on a certified duality gap, per instance (slp_cp_batch_set_stop_gap, include/slp_hip_ext.h; the certificate of
+// slp_cp_many.hip).  The state counts its whole iterations t on the host.  From the first arming on it launches
+// k_cpb_primal_masked / k_cpb_dual_masked: the same arithmetic through the same slp_cp_shared.h functions, but a lane reads
+// stopped[instance] first and returns before any other load.  No barrier anywhere, so a wavefront whose instances are all stopped
+// retires at once: with Bt = 64 a wholly stopped tile costs its launch slots only.  Padding instances are marked stopped.
+// After the dual half of an iteration t with t % check_every == 0 three launches follow: k_cpb_gap_cols (c.x and the bound's
+// column terms, d = c + K^T y by cp_column_sums + cp_direction: the bits of the next primal half), k_cpb_gap_rows (the y.b
+// terms and the two violation maxima, K x one accumulator in storage order) -- both sliced as the report's passes (entry r in
+// slice r mod S, a slice in increasing r), in rowparts / colparts, which are free between reports on the one stream; a batch of
+// fewer than 256 instances gets up to 4096 slices, in scratch allocated at the first arming (kCpbGapLanes) -- and k_cpb_gap_final, one lane per running instance and quantity: the slice
+// sums in increasing slice order, the decision, the record, the flag, and a device count of the instances that go on.  Nothing is
+// read back while iterations are enqueued; an armed iterate / dual_step begins with one read of that count and enqueues
+// nothing when it is 0.  One counter for the whole batch: a stopped instance stays stopped for the life of the state.
+#include <cmath>
+#include <vector>
+
+#include "../../include/slp_hip_ext.h"
 #include "slp_common.h"
 #include "slp_cp_shared.h"
 #include "slp_kernels.h"
@@ -33,6 +51,12 @@ namespace slp {
 void cp_preconditioners_csr(slp_matrix *k, i64 m_eq, double alpha, double *t, double *sigma);
 
 constexpr int kCpbMaxSlices = 1024;
+// the certificate's passes: with 1024 slices a batch of one tile fills an eighth of the device's wave slots and a pass is a chain of
+// memory latencies (measured: DESIGN.md section 7), so a narrow batch gets up to 4096 slices in scratch of the test's own --
+// kCpbGapLanes lanes per pass where the batch allows; a batch of 256 or more instances keeps the report's 1024 and its scratch
+constexpr int kCpbGapMaxSlices = 4096;
+constexpr i64 kCpbGapLanes = 262144;
+constexpr int kCpbGapAhead = 16;
 
 // the row (column) a lane group works on; with a full tile it is the same for the whole wavefront: scalar registers
 template <int BT>
@@ -204,6 +228,174 @@ __global__ void k_cpb_report_final(i64 Bp, i64 srows, const double *__restrict__
     out[inst * 5 + 4] = (veqx == -__builtin_inf()) ? 0.0 : veqx;
 }
 
+// ---- per-instance stopping on a certified duality gap (header comment; slp_cp_batch_set_stop_gap) ----
+// Kernels of their own: the five above are what a never-armed state launches, untouched.
+
+// max / min as np.max / np.minimum: a NaN on either side stays
+__device__ __forceinline__ double cpb_nanmax(double m, double d) { return (d > m || d != d) ? d : m; }
+__device__ __forceinline__ double cpb_nanmin(double a, double b) { return (b < a || b != b) ? b : a; }
+
+// k_cpb_primal for a state with stopped instances: a lane reads its instance's flag first and returns before any other load
+template <int BT, bool STORE>
+__global__ __launch_bounds__(kBlock) void k_cpb_primal_masked(i64 n, i64 m, const i64 *__restrict__ tptr, const i32 *__restrict__ tidx,
+                                                              const double *__restrict__ tval, const double *__restrict__ y,
+                                                              const double *__restrict__ c, const double *__restrict__ t,
+                                                              const double *__restrict__ lb, const double *__restrict__ ub,
+                                                              double *__restrict__ x, double *__restrict__ z, double *__restrict__ x4,
+                                                              i32 m_eq, i64 m_ineq, double one_plus_theta, double theta,
+                                                              const i32 *__restrict__ stopped) {
+    const int k = threadIdx.x & (BT - 1);
+    const i64 tile = blockIdx.y;
+    if (stopped[tile * BT + k]) return;
+    const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT;
+    const i64 ngroups = (i64)gridDim.x * kBlock / BT;
+    const double *__restrict__ yt = y + tile * m * BT + k;
+    for (i64 jj = group; jj < n; jj += ngroups) {
+        const i64 j = cpb_uniform<BT>(jj);  // the first ACTIVE lane's: every lane of the wave has the same column
+        const i64 s = tptr[j], e = tptr[j + 1];
+        double se, si;
+        cp_column_sums(s, e, tidx, tval, yt, BT, m_eq, CpLoadPlain(), &se, &si);
+        const i64 o = (tile * n + j) * BT + k;
+        const double d = cp_direction(c[o], se, si, m_eq > 0, m_ineq > 0);
+        const double xo = x[o], l = lb[o], u = ub[o];
+        double x2, zn;
+        cp_primal_point(d, xo, t[j], l, u, one_plus_theta, theta, &x2, &zn);
+        z[o] = zn;
+        x[o] = x2;
+        if (STORE) x4[o] = (d < 0.0) ? u : l;
+    }
+}
+
+// k_cpb_dual for a state with stopped instances
+template <int BT>
+__global__ __launch_bounds__(kBlock) void k_cpb_dual_masked(i64 n, i64 m, const i64 *__restrict__ ptr, const i32 *__restrict__ idx,
+                                                            const double *__restrict__ val, const double *__restrict__ z,
+                                                            const double *__restrict__ b, const double *__restrict__ sigma,
+                                                            double *__restrict__ y, i64 m_eq, const i32 *__restrict__ stopped) {
+    const int k = threadIdx.x & (BT - 1);
+    const i64 tile = blockIdx.y;
+    if (stopped[tile * BT + k]) return;
+    const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT;
+    const i64 ngroups = (i64)gridDim.x * kBlock / BT;
+    const double *__restrict__ zt = z + tile * n * BT + k;
+    for (i64 ii = group; ii < m; ii += ngroups) {
+        const i64 i = cpb_uniform<BT>(ii);
+        const i64 s = ptr[i], e = ptr[i + 1];
+        const double kz = cp_row_sum(s, e, idx, val, zt, BT, CpLoadPlain());
+        const i64 o = (tile * m + i) * BT + k;
+        y[o] = cp_dual_point(kz, b[o], y[o], sigma[i], i >= m_eq);
+    }
+}
+
+// certificate, column pass (the report's slices).  part[(q * S + slice) * Bp + instance]: q = 0 sum c_j x_j, 1 the bound's column
+// terms sum [d_j != 0 ? min(d_j lb_j, d_j ub_j) : 0] with d = c + K^T y as the next primal half forms it
+template <int BT>
+__global__ __launch_bounds__(kBlock) void k_cpb_gap_cols(i64 n, i64 m, const i64 *__restrict__ tptr, const i32 *__restrict__ tidx,
+                                                         const double *__restrict__ tval, const double *__restrict__ y,
+                                                         const double *__restrict__ c, const double *__restrict__ lb,
+                                                         const double *__restrict__ ub, const double *__restrict__ x, i32 m_eq, i64 m_ineq,
+                                                         i64 Bp, const i32 *__restrict__ stopped, double *__restrict__ part) {
+    const int k = threadIdx.x & (BT - 1);
+    const i64 tile = blockIdx.y;
+    const i64 inst = tile * BT + k;
+    if (stopped[inst]) return;
+    const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT;
+    const i64 ngroups = (i64)gridDim.x * kBlock / BT;
+    const double *__restrict__ yt = y + tile * m * BT + k;
+    double cx = 0.0, terms = 0.0;
+    for (i64 jj = group; jj < n; jj += ngroups) {
+        const i64 j = cpb_uniform<BT>(jj);
+        double se, si;
+        cp_column_sums(tptr[j], tptr[j + 1], tidx, tval, yt, BT, m_eq, CpLoadPlain(), &se, &si);
+        const i64 o = (tile * n + j) * BT + k;
+        const double cj = c[o];
+        const double d = cp_direction(cj, se, si, m_eq > 0, m_ineq > 0);
+        cx += cj * x[o];
+        if (d != 0.0) terms += cpb_nanmin(d * lb[o], d * ub[o]);  // the guard keeps 0 * inf out
+    }
+    part[(0 * ngroups + group) * Bp + inst] = cx;
+    part[(1 * ngroups + group) * Bp + inst] = terms;
+}
+
+// certificate, row pass.  part[(q * S + slice) * Bp + instance]: q = 0 sum [y_r != 0 ? y_r b_r : 0],
+// 1 max_{r < m_eq} |(K x)_r - b_r| and 2 max_{r >= m_eq} ((K x)_r - b_r), each with 0 (K x: one accumulator in storage order)
+template <int BT>
+__global__ __launch_bounds__(kBlock) void k_cpb_gap_rows(i64 n, i64 m, const i64 *__restrict__ ptr, const i32 *__restrict__ idx,
+                                                         const double *__restrict__ val, const double *__restrict__ x,
+                                                         const double *__restrict__ b, const double *__restrict__ y, i64 m_eq, i64 Bp,
+                                                         const i32 *__restrict__ stopped, double *__restrict__ part) {
+    const int k = threadIdx.x & (BT - 1);
+    const i64 tile = blockIdx.y;
+    const i64 inst = tile * BT + k;
+    if (stopped[inst]) return;
+    const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT;
+    const i64 ngroups = (i64)gridDim.x * kBlock / BT;
+    const double *__restrict__ xt = x + tile * n * BT + k;
+    double yb = 0.0, veq = 0.0, vin = 0.0;
+    for (i64 ii = group; ii < m; ii += ngroups) {
+        const i64 i = cpb_uniform<BT>(ii);
+        const double kx = cp_row_sum(ptr[i], ptr[i + 1], idx, val, xt, BT, CpLoadPlain());
+        const i64 o = (tile * m + i) * BT + k;
+        const double bi = b[o], yi = y[o];
+        if (yi != 0.0) yb += yi * bi;  // a row without a finite side has y = 0
+        const double v = kx - bi;
+        if (i < m_eq) veq = cpb_nanmax(veq, fabs(v));
+        else vin = cpb_nanmax(vin, v);
+    }
+    part[(0 * ngroups + group) * Bp + inst] = yb;
+    part[(1 * ngroups + group) * Bp + inst] = veq;
+    part[(2 * ngroups + group) * Bp + inst] = vin;
+}
+
+// one workgroup of five wavefronts per 64 instances, wavefront q folding quantity q of a running real instance over the slices in
+// increasing slice order (q = 0 sum y b, 1 and 2 the violation maxima: the row pass; 3 c.x, 4 the bound's column terms: the
+// column pass), kCpbGapAhead slices loaded before they are added; behind the barrier wavefront 0 decides and writes the record
+// rec[3 inst + 0..2] = primal, bound, violation, the flag with the stopping iteration `t`, and counts the instances that go on
+// (`running` is zeroed on the stream before this launch).  Every lane reaches the barrier.
+constexpr int kCpbGapQuantities = 5;
+__global__ __launch_bounds__(kCpbGapQuantities *kWave) void k_cpb_gap_final(i64 B, i64 Bp, i64 srows, const double *__restrict__ rp, i64 scols,
+                                                                            const double *__restrict__ cp, double tol_gap, double tol_feas,
+                                                                            i64 t, i32 *__restrict__ stopped, i64 *__restrict__ stop_iter,
+                                                                            double *__restrict__ rec, i32 *__restrict__ running) {
+    __shared__ double folded[kCpbGapQuantities][kWave];
+    const int q = (int)threadIdx.x / kWave, lane = (int)threadIdx.x % kWave;
+    const i64 inst = (i64)blockIdx.x * kWave + lane;
+    const bool live = inst < B && !stopped[inst];
+    double acc = 0.0;
+    if (live) {
+        const bool rows = q < 3, is_max = q == 1 || q == 2;
+        const i64 S = rows ? srows : scols;
+        const double *__restrict__ p = (rows ? rp + (i64)q * srows * Bp : cp + (i64)(q - 3) * scols * Bp) + inst;
+        for (i64 g0 = 0; g0 < S; g0 += kCpbGapAhead) {
+            double a[kCpbGapAhead];
+#pragma unroll
+            for (int u = 0; u < kCpbGapAhead; ++u) {
+                const i64 g = (g0 + u < S) ? g0 + u : S - 1;
+                a[u] = p[g * Bp];
+            }
+#pragma unroll
+            for (int u = 0; u < kCpbGapAhead; ++u)
+                if (g0 + u < S) acc = is_max ? cpb_nanmax(acc, a[u]) : acc + a[u];
+        }
+    }
+    folded[q][lane] = acc;
+    __syncthreads();
+    if (q != 0 || !live) return;
+    const double sy = folded[0][lane], viol = cpb_nanmax(folded[1][lane], folded[2][lane]), primal = folded[3][lane], cols = folded[4][lane];
+    const double bound = cols - sy, gap = fabs(primal - bound);
+    // false for a NaN; an infinite gap (bound = -inf) never stops, whatever tol_gap * inf would say
+    const bool stop = viol <= tol_feas && gap < __builtin_inf() && gap <= tol_gap * (1.0 + fabs(primal) + fabs(bound));
+    rec[inst * 3 + 0] = primal;
+    rec[inst * 3 + 1] = bound;
+    rec[inst * 3 + 2] = viol;
+    if (stop) {
+        stopped[inst] = 1;
+        stop_iter[inst] = t;
+    } else {
+        atomicAdd(running, 1);
+    }
+}
+
 }  // namespace slp
 
 using namespace slp;
@@ -215,6 +407,17 @@ struct slp_cp_batch {
     int Bt = 1;
     double alpha = 1, theta = 1;
     DevBuf<double> b, c, lb, ub, t, sigma, x, z, y, x4, rowparts, colparts, out;
+    i64 iters = 0;  // whole iterations over the state's life: bumped where a dual half is enqueued
+    // the certificate test (slp_cp_batch_set_stop_gap); its buffers exist from the first arming on, and from then on the state
+    // launches the masked kernels.  Off while tol_gap < 0.
+    bool masked = false;
+    double tol_gap = -1.0, tol_feas = 0.0;
+    i64 check_every = 1;
+    DevBuf<i32> stopped, running;  // per padded instance; the count of real instances that still run
+    DevBuf<i64> stop_iter;
+    DevBuf<double> rec;  // primal, bound, violation of the last evaluated certificate, per instance
+    i64 gap_slices = kCpbMaxSlices;  // at most this many slices per certificate pass
+    DevBuf<double> gapparts;         // 5 * gap_slices * Bp slice sums where gap_slices exceeds the report's
     ~slp_cp_batch() { delete k; }
 };
 
@@ -249,7 +452,17 @@ static void cpb_primal(slp_cp_batch *s, bool store) {
     const CsrDev &at = s->k->at;
     const double opt = 1.0 + s->theta;
     const dim3 grid = cpb_grid(s, s->n);
-    if (store) {
+    if (s->masked) {
+        if (store) {
+            SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_primal_masked<BT, true>), grid, dim3(kBlock), 0, st, s->n, s->m, at.ptr.p,
+                                                        at.idx.p, at.val.p, s->y.p, s->c.p, s->t.p, s->lb.p, s->ub.p, s->x.p, s->z.p,
+                                                        s->x4.p, (i32)s->m_eq, s->m_ineq, opt, s->theta, s->stopped.p));
+        } else {
+            SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_primal_masked<BT, false>), grid, dim3(kBlock), 0, st, s->n, s->m, at.ptr.p,
+                                                        at.idx.p, at.val.p, s->y.p, s->c.p, s->t.p, s->lb.p, s->ub.p, s->x.p, s->z.p,
+                                                        s->x4.p, (i32)s->m_eq, s->m_ineq, opt, s->theta, s->stopped.p));
+        }
+    } else if (store) {
         SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_primal<BT, true>), grid, dim3(kBlock), 0, st, s->n, s->m, at.ptr.p, at.idx.p,
                                                     at.val.p, s->y.p, s->c.p, s->t.p, s->lb.p, s->ub.p, s->x.p, s->z.p, s->x4.p,
                                                     (i32)s->m_eq, s->m_ineq, opt, s->theta));
@@ -263,9 +476,67 @@ static void cpb_primal(slp_cp_batch *s, bool store) {
 
 static void cpb_dual(slp_cp_batch *s) {
     const CsrDev &a = s->k->a;
-    SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_dual<BT>), cpb_grid(s, s->m), dim3(kBlock), 0, ctx().stream, s->n, s->m, a.ptr.p,
-                                                a.idx.p, a.val.p, s->z.p, s->b.p, s->sigma.p, s->y.p, s->m_eq));
+    if (s->masked) {
+        SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_dual_masked<BT>), cpb_grid(s, s->m), dim3(kBlock), 0, ctx().stream, s->n, s->m,
+                                                    a.ptr.p, a.idx.p, a.val.p, s->z.p, s->b.p, s->sigma.p, s->y.p, s->m_eq, s->stopped.p));
+    } else {
+        SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_dual<BT>), cpb_grid(s, s->m), dim3(kBlock), 0, ctx().stream, s->n, s->m, a.ptr.p,
+                                                    a.idx.p, a.val.p, s->z.p, s->b.p, s->sigma.p, s->y.p, s->m_eq));
+    }
     SLP_HIP(hipGetLastError());
+    ++s->iters;  // the dual half ends an iteration
+}
+
+// blocks of a certificate pass: at most s->gap_slices row groups
+static dim3 cpb_gap_grid(const slp_cp_batch *s, i64 rows) {
+    const i64 per_block = kBlock / s->Bt;
+    i64 g = (rows + per_block - 1) / per_block;
+    const i64 cap = std::max<i64>(1, s->gap_slices / per_block);
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return dim3((unsigned)g, (unsigned)s->ntiles);
+}
+
+// the certificate of iteration s->iters for every running instance, enqueued behind its dual half; nothing is read back
+static void cpb_certificate(slp_cp_batch *s) {
+    hipStream_t st = ctx().stream;
+    const CsrDev &a = s->k->a, &at = s->k->at;
+    const dim3 gr = cpb_gap_grid(s, s->m), gc = cpb_gap_grid(s, s->n);
+    const i64 srows = (i64)gr.x * kBlock / s->Bt, scols = (i64)gc.x * kBlock / s->Bt;
+    // 3 * srows * Bp and 2 * scols * Bp slice sums: the report's scratch holds 5 and 2 times 1024 * Bp
+    const bool own = s->gap_slices > kCpbMaxSlices;
+    double *rowparts = own ? s->gapparts.p : s->rowparts.p;
+    double *colparts = own ? s->gapparts.p + (size_t)3 * (size_t)s->gap_slices * (size_t)s->Bp : s->colparts.p;
+    SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_gap_cols<BT>), gc, dim3(kBlock), 0, st, s->n, s->m, at.ptr.p, at.idx.p, at.val.p,
+                                                s->y.p, s->c.p, s->lb.p, s->ub.p, s->x.p, (i32)s->m_eq, s->m_ineq, s->Bp, s->stopped.p,
+                                                colparts));
+    SLP_HIP(hipGetLastError());
+    SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_gap_rows<BT>), gr, dim3(kBlock), 0, st, s->n, s->m, a.ptr.p, a.idx.p, a.val.p,
+                                                s->x.p, s->b.p, s->y.p, s->m_eq, s->Bp, s->stopped.p, rowparts));
+    SLP_HIP(hipGetLastError());
+    s->running.zero();
+    hipLaunchKernelGGL(k_cpb_gap_final, dim3((unsigned)((s->B + kWave - 1) / kWave)), dim3(kCpbGapQuantities * kWave), 0, st, s->B, s->Bp, srows,
+                       rowparts, scols, colparts, s->tol_gap, s->tol_feas, s->iters, s->stopped.p, s->stop_iter.p, s->rec.p,
+                       s->running.p);
+    SLP_HIP(hipGetLastError());
+}
+
+// an armed state asks once per call whether anything is left to run
+static bool cpb_all_stopped(slp_cp_batch *s) {
+    if (!s->masked) return false;
+    i32 running = 0;
+    s->running.download(&running, 1);
+    return running == 0;
+}
+
+// whole iterations; the host knows the count, so it knows where the certificate is due
+static void cpb_iterations(slp_cp_batch *s, i64 k, bool with_primal) {
+    if (cpb_all_stopped(s)) return;
+    for (i64 it = 0; it < k; ++it) {
+        if (with_primal) cpb_primal(s, false);
+        cpb_dual(s);
+        if (s->tol_gap >= 0.0 && s->iters % s->check_every == 0) cpb_certificate(s);
+    }
 }
 
 // host vector(s) -> tiled device layout through `stage`
@@ -365,13 +636,13 @@ void slp_cp_batch_destroy(slp_cp_batch *s) { delete s; }
 int slp_cp_batch_iterate(slp_cp_batch *s, int64_t k) {
     SLP_API_INT({
         SLP_REQUIRE(s && k >= 0, "slp_cp_batch_iterate: bad arguments");
-        for (i64 it = 0; it < k; ++it) { cpb_primal(s, false); cpb_dual(s); }
+        cpb_iterations(s, k, true);
     })
 }
 
 int slp_cp_batch_primal_step(slp_cp_batch *s) { SLP_API_INT({ SLP_REQUIRE(s, "NULL handle"); cpb_primal(s, true); }) }
 
-int slp_cp_batch_dual_step(slp_cp_batch *s) { SLP_API_INT({ SLP_REQUIRE(s, "NULL handle"); cpb_dual(s); }) }
+int slp_cp_batch_dual_step(slp_cp_batch *s) { SLP_API_INT({ SLP_REQUIRE(s, "NULL handle"); cpb_iterations(s, 1, false); }) }
 
 int slp_cp_batch_report(slp_cp_batch *s, double *out) {
     SLP_API_INT({
@@ -428,6 +699,63 @@ int slp_cp_batch_bench(slp_cp_batch *s, int64_t k, double ms[3]) {
         SLP_HIP(hipEventSynchronize(c.ev1));
         SLP_HIP(hipEventElapsedTime(&f, c.ev0, c.ev1));
         ms[2] = (double)f / (double)k;
+    })
+}
+
+int slp_cp_batch_set_stop_gap(slp_cp_batch *s, double tol_gap, double tol_feas, int64_t check_every) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_cp_batch_set_stop_gap: NULL handle");
+        SLP_REQUIRE(tol_gap < 0.0 || (std::isfinite(tol_gap) && std::isfinite(tol_feas) && tol_feas >= 0.0 && check_every >= 1),
+                    "slp_cp_batch_set_stop_gap: tol_gap and tol_feas must be finite and >= 0 with check_every >= 1 (tol_gap < 0 turns the "
+                    "test off)");
+        if (tol_gap >= 0.0 && !s->masked) {  // the first arming: flags (padding instances stopped), records, the count
+            const size_t bp = (size_t)s->Bp;
+            std::vector<i32> flags(bp, 0);
+            for (size_t k = (size_t)s->B; k < bp; ++k) flags[k] = 1;
+            std::vector<double> rec(3 * bp);
+            for (size_t k = 0; k < bp; ++k) {
+                rec[3 * k + 0] = __builtin_inf();
+                rec[3 * k + 1] = -__builtin_inf();
+                rec[3 * k + 2] = __builtin_inf();
+            }
+            const std::vector<i64> none(bp, 0);
+            const i32 running = (i32)std::min<i64>(s->B, 0x7fffffff);
+            const i64 slices = std::min<i64>(kCpbGapMaxSlices, std::max<i64>(kCpbMaxSlices, kCpbGapLanes / s->Bp));
+            if (slices > kCpbMaxSlices) s->gapparts.alloc((size_t)5 * (size_t)slices * bp);
+            s->gap_slices = slices;
+            s->stopped.upload(flags.data(), bp);
+            s->stop_iter.upload(none.data(), bp);
+            s->rec.upload(rec.data(), 3 * bp);
+            s->running.upload(&running, 1);
+            s->masked = true;
+        }
+        s->tol_gap = tol_gap < 0.0 ? -1.0 : tol_gap;
+        if (tol_gap >= 0.0) {
+            s->tol_feas = tol_feas;
+            s->check_every = check_every;
+        }
+    })
+}
+
+int slp_cp_batch_gap_state(slp_cp_batch *s, int64_t *iterations, int32_t *stopped, double *primal, double *bound, double *violation) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_cp_batch_gap_state: NULL handle");
+        const size_t count = (size_t)s->B;
+        std::vector<i32> flags(count, 0);
+        std::vector<i64> at(count, 0);
+        std::vector<double> rec(3 * count);
+        if (s->masked) {
+            s->stopped.download(flags.data(), count);
+            s->stop_iter.download(at.data(), count);
+            s->rec.download(rec.data(), 3 * count);
+        }
+        for (size_t k = 0; k < count; ++k) {
+            if (iterations) iterations[k] = flags[k] ? at[k] : s->iters;
+            if (stopped) stopped[k] = flags[k];
+            if (primal) primal[k] = s->masked ? rec[3 * k + 0] : __builtin_inf();
+            if (bound) bound[k] = s->masked ? rec[3 * k + 1] : -__builtin_inf();
+            if (violation) violation[k] = s->masked ? rec[3 * k + 2] : __builtin_inf();
+        }
     })
 }
 
