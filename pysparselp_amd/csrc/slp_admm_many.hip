@@ -40,7 +40,9 @@
 // Report (:213-248), per LP, one workgroup of 256 lanes on the written-back state: lane t takes rows (columns) t, t + 256, ...
 // in increasing order, then block_reduce: a fixed order, a function of the shapes only.  The maxima are exact.
 //
-// Stopping (slp_many_admm_set_stop; off after create).  AdmmmCtl, one per LP in device memory: iterations completed, the stopped
+// Stopping (slp_many_admm_set_stop; off after create), by the protocol slp_many.h holds once for this file and slp_cp_many.hip:
+// the head of the record, entering from it, a wave's slot, lane 0's fold, the decision slot with its barrier, and on the host the
+// read-out and the re-arming.  AdmmmCtl, one per LP in device memory: iterations completed, the stopped
 // flag, the stopping iteration, the last evaluated residual and step, and the reduced step of a sweep whose multiplier update has
 // not run yet.  Iterations of an LP count from 1 over its whole life; at the end of an iteration t with t % check_every == 0 the
 // LP stops iff  residual_t = max_i |(A x_t)_i - b_i| <= tol_residual  and  step_t = max_j |x_t,j - x_{t-1},j| <= tol_step: the
@@ -169,14 +171,11 @@ struct AdmmmArgs {
     double gamma_eq, gamma_ineq;
 };
 
-// per LP, in device memory; written by lane 0 of the LP's workgroup (STOP) and by the host between launches
-struct AdmmmCtl {
-    i64 done;         // whole iterations completed
-    i64 stop_iter;    // `done` when it stopped
+// per LP, in device memory: the head of slp_many.h and what the test evaluates
+struct AdmmmCtl : ManyCtl {
     double residual;  // the last evaluated max |A x - b|, +inf before the first test
     double step;      // the last evaluated max |x_t - x_{t-1}|, +inf before the first test
     double dx;        // the sweep's maximum of a check iteration, carried from sweep_step to multiplier_step
-    i32 stopped, pad;
 };
 
 struct AdmmmStop {
@@ -192,7 +191,7 @@ static_assert(kAdmmmRed * sizeof(double) + kAdmmmLdsLimit * sizeof(double) <= 16
               "the slots of the stopping test and the iterates of the lds form share the compute unit's 160 KiB");
 
 // `iters` times the stages of one LP (bit 0 right-hand side + sweep, bit 1 multiplier); first: xp = xp0 in the first right-hand side.
-// STOP: the stopping test of the header comment; `sp` is not looked at without it.
+// STOP: the stopping test of the header comment, by the protocol of slp_many.h; `sp` is not looked at without it.
 template <bool LDS, bool STOP>
 __global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, int iters, int first, int stages, AdmmmStop sp) {
     extern __shared__ __attribute__((aligned(16))) double admmm_lds[];
@@ -203,12 +202,7 @@ __global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, i
     const AdmmmLp lp = a.lps[id];
     const i32 N = lp.n + lp.m_in, m = lp.m_eq + lp.m_in, W = (i32)blockDim.x, tid = (i32)threadIdx.x;
     i64 done = 0, until = 0;  // STOP: iterations completed; iterations up to and including the next check
-    if (STOP) {
-        const AdmmmCtl *ctl = sp.ctl + id;
-        if (ctl->stopped) return;  // set before the launch: the same for every lane
-        done = ctl->done;          // lane 0 writes the record only behind a barrier that follows this load
-        until = sp.check_every - done % sp.check_every;
-    }
+    if (STOP && !many_enter(sp.ctl + id, sp.check_every, &done, &until)) return;
     double *xg = a.x + lp.x0, *yg = a.y + lp.x0, *lg = a.lam + lp.lam0;
     double *xs = xg, *ys = yg, *ls = lg;
     if (LDS) {
@@ -241,7 +235,7 @@ __global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, i
                         const double yi = ld(ys + i), xi = ld(xs + i);
                         const double v = admm_sweep_one<1>(gptr[t], gptr[t + 1], a.gidx, a.gval, xs, yi, xi, ginvd[t], lb[i], ub[i], ld);
                         xs[i] = v;
-                        dx = many_nanmax(dx, fabs(v - xi));
+                        dx = nan_max(dx, fabs(v - xi));
                     }
                 } else {
                     for (i64 t = beg + tid; t < end; t += W) {
@@ -251,17 +245,15 @@ __global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, i
                 }
                 __syncthreads();  // same compute unit: the stores of this level are visible to the next one
             }
-            if (check) {  // behind the last level's barrier; read behind the multiplier pass's, or behind the one below
-                dx = many_wave_nanmax(dx);
-                if ((tid & (kWave - 1)) == 0) admmm_red[tid / kWave] = dx;
-            }
+            // behind the last level's barrier; read behind the multiplier pass's, or behind the one below
+            if (check) many_post<1, 1>(admmm_red, kAdmmmWaves, tid, &dx);
         }
         if (STOP && !(stages & 2)) {  // sweep_step: the reduced step waits in the record for multiplier_step
             if (check) {
                 __syncthreads();  // the slots of every wave are written
                 if (tid == 0) {
-                    double dx = admmm_red[0];
-                    for (i32 w = 1; w < W / kWave; ++w) dx = many_nanmax(dx, admmm_red[w]);
+                    double dx;
+                    many_fold<1, 1>(admmm_red, kAdmmmWaves, W, &dx);
                     sp.ctl[id].dx = dx;
                 }
             }
@@ -274,10 +266,9 @@ __global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, i
                     const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
                     double res;
                     ls[r] = admm_mult_res_one<1>(a.aptr[g], a.aptr[g + 1], a.aidx, a.aval, xs, ls + r, b + r, a.gamma_eq, ld, &res);
-                    dr = many_nanmax(dr, fabs(res));
+                    dr = nan_max(dr, fabs(res));
                 }
-                dr = many_wave_nanmax(dr);
-                if ((tid & (kWave - 1)) == 0) admmm_red[kAdmmmWaves + tid / kWave] = dr;
+                many_post<1, 1>(admmm_red + kAdmmmWaves, kAdmmmWaves, tid, &dr);
             } else {
                 for (i32 r = tid; r < m; r += W) {
                     const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
@@ -295,22 +286,16 @@ __global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, i
             until = sp.check_every;
             if (tid == 0) {
                 AdmmmCtl *ctl = sp.ctl + id;
-                double dx = (stages & 1) ? admmm_red[0] : ctl->dx, dr = admmm_red[kAdmmmWaves];
-                for (i32 w = 1; w < W / kWave; ++w) {
-                    if (stages & 1) dx = many_nanmax(dx, admmm_red[w]);
-                    dr = many_nanmax(dr, admmm_red[kAdmmmWaves + w]);
-                }
-                const bool stop = dr <= sp.tol_residual && dx <= sp.tol_step;  // false for a NaN
-                ctl->residual = dr;
-                ctl->step = dx;
-                if (stop) {
-                    ctl->stopped = 1;
-                    ctl->stop_iter = done;
-                }
-                admmm_red[2 * kAdmmmWaves] = stop ? 1.0 : 0.0;
+                // the sweep's step, the residual.  multiplier_step: the step waited in the record (as in k_cpm_iterate, named up
+                // front; the compiler sinks the load into that case)
+                double f[2] = {ctl->dx, 0.0};
+                if (stages & 1) many_fold<2, 3>(admmm_red, kAdmmmWaves, W, f);
+                else many_fold<1, 1>(admmm_red + kAdmmmWaves, kAdmmmWaves, W, f + 1);
+                ctl->residual = f[1];
+                ctl->step = f[0];
+                many_decide(ctl, done, f[1] <= sp.tol_residual && f[0] <= sp.tol_step, admmm_red + 2 * kAdmmmWaves);  // false for a NaN
             }
-            __syncthreads();  // the one barrier the test adds to a whole iteration, in a check iteration only
-            if (admmm_red[2 * kAdmmmWaves] != 0.0) break;  // one slot, read by every lane: uniform
+            if (many_decided(admmm_red + 2 * kAdmmmWaves)) break;  // the one barrier the test adds to a whole iteration
         }
     }
     if (STOP && (stages & 2) && tid == 0) sp.ctl[id].done = done;
@@ -426,14 +411,6 @@ static void admmm_run(slp_admm_many *s, i64 k, int stages) {
         });
     }
     if (stages & 2) s->xp_is_x = true;
-}
-
-// the records with the iterations of the unarmed launches added; synchronises
-static std::vector<AdmmmCtl> admmm_read_ctl(slp_admm_many *s) {
-    std::vector<AdmmmCtl> h((size_t)s->count);
-    s->ctl.download(h.data(), h.size());
-    for (AdmmmCtl &c : h) c.done += s->uncounted;  // no LP is stopped while the test is off
-    return h;
 }
 
 // the two environment switches and the form per LP -- from the shapes only; needs no device, nothing is allocated yet
@@ -639,7 +616,7 @@ slp_admm_many *slp_admm_many_create(int64_t count, const int64_t *n, const int64
         hipLaunchKernelGGL(k_admmm_gather_rows, per_lp, dim3(kBlock), 0, st, s->table.p, s->sh.b, s->b.p);
         SLP_HIP(hipGetLastError());
         s->out.alloc((size_t)3 * (size_t)count);
-        std::vector<AdmmmCtl> ctl((size_t)count, AdmmmCtl{0, 0, __builtin_inf(), __builtin_inf(), 0.0, 0, 0});
+        std::vector<AdmmmCtl> ctl((size_t)count, AdmmmCtl{{0, 0, 0, 0}, __builtin_inf(), __builtin_inf(), 0.0});
         s->ctl.upload(ctl.data(), ctl.size());
         SLP_HIP(hipStreamSynchronize(st));
         return s.release();
@@ -672,10 +649,7 @@ int slp_many_admm_set_stop(slp_admm_many *s, double tol_residual, double tol_ste
                     "slp_many_admm_set_stop: tol_residual and tol_step must be finite and >= 0 with check_every >= 1 (tol_residual < 0 turns "
                     "the test off)");
         SLP_REQUIRE(!s->mid_iteration, "slp_many_admm_set_stop: called between sweep_step and multiplier_step (whole iterations only)");
-        std::vector<AdmmmCtl> h = admmm_read_ctl(s);
-        for (AdmmmCtl &c : h) c.stopped = 0;
-        s->ctl.upload(h.data(), h.size());
-        s->uncounted = 0;
+        many_rearm(s->ctl, s->count, &s->uncounted);
         s->tol_residual = tol_residual < 0.0 ? -1.0 : tol_residual;
         if (tol_residual >= 0.0) {
             s->tol_step = tol_step;
@@ -687,10 +661,9 @@ int slp_many_admm_set_stop(slp_admm_many *s, double tol_residual, double tol_ste
 int slp_many_admm_stop_state(slp_admm_many *s, int64_t *iterations, int32_t *stopped, double *residual, double *step) {
     SLP_API_INT({
         SLP_REQUIRE(s, "slp_many_admm_stop_state: NULL handle");
-        const std::vector<AdmmmCtl> h = admmm_read_ctl(s);
+        const std::vector<AdmmmCtl> h = many_read_ctl(s->ctl, s->count, s->uncounted);
         for (size_t k = 0; k < h.size(); ++k) {
-            if (iterations) iterations[k] = h[k].stopped ? h[k].stop_iter : h[k].done;
-            if (stopped) stopped[k] = h[k].stopped;
+            many_state_head(h[k], k, iterations, stopped);
             if (residual) residual[k] = h[k].residual;
             if (step) step[k] = h[k].step;
         }

@@ -25,8 +25,8 @@
 // in increasing slice order (maxima are exact in any order).  x4 is written by the primal half of a reporting iteration.
 //
 // Stopping on a certified duality gap, per instance (slp_cp_batch_set_stop_gap, include/slp_hip_ext.h; the certificate of
-// slp_cp_many.hip).  The state counts its whole iterations t on the host.  From the first arming on it launches
-// k_cpb_primal_masked / k_cpb_dual_masked: the same arithmetic through the same slp_cp_shared.h functions, but a lane reads
+// slp_cp_many.hip, its scalar arithmetic shared through slp_cp_gap.h).  The state counts its whole iterations t on the host.  From
+// the first arming on it launches the MASKED instantiations of k_cpb_primal / k_cpb_dual: the same kernel text, but a lane reads
 // stopped[instance] first and returns before any other load.  No barrier anywhere, so a wavefront whose instances are all stopped
 // retires at once: with Bt = 64 a wholly stopped tile costs its launch slots only.  Padding instances are marked stopped.
 // After the dual half of an iteration t with t % check_every == 0 three launches follow: k_cpb_gap_cols (c.x and the bound's
@@ -42,6 +42,7 @@
 
 #include "../../include/slp_hip_ext.h"
 #include "slp_common.h"
+#include "slp_cp_gap.h"
 #include "slp_cp_shared.h"
 #include "slp_kernels.h"
 
@@ -88,21 +89,25 @@ __global__ void k_cpb_gather(i64 len, i64 B, int BT, const double *__restrict__ 
     }
 }
 
-// primal half-iteration: one lane per (column j, instance k); STORE: also x4_j = ub_j if d_j < 0 else lb_j (:260-261)
-template <int BT, bool STORE>
+// primal half-iteration: one lane per (column j, instance k); STORE: also x4_j = ub_j if d_j < 0 else lb_j (:260-261).
+// MASKED, for a state with stopped instances: a lane reads its instance's flag first and returns before any other load;
+// `stopped` is not looked at without it.
+template <int BT, bool STORE, bool MASKED>
 __global__ __launch_bounds__(kBlock) void k_cpb_primal(i64 n, i64 m, const i64 *__restrict__ tptr, const i32 *__restrict__ tidx,
                                                        const double *__restrict__ tval, const double *__restrict__ y,
                                                        const double *__restrict__ c, const double *__restrict__ t,
                                                        const double *__restrict__ lb, const double *__restrict__ ub,
                                                        double *__restrict__ x, double *__restrict__ z, double *__restrict__ x4,
-                                                       i32 m_eq, i64 m_ineq, double one_plus_theta, double theta) {
+                                                       i32 m_eq, i64 m_ineq, double one_plus_theta, double theta,
+                                                       const i32 *__restrict__ stopped) {
     const int k = threadIdx.x & (BT - 1);
     const i64 tile = blockIdx.y;
+    if (MASKED && stopped[tile * BT + k]) return;
     const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT;
     const i64 ngroups = (i64)gridDim.x * kBlock / BT;
     const double *__restrict__ yt = y + tile * m * BT + k;
     for (i64 jj = group; jj < n; jj += ngroups) {
-        const i64 j = cpb_uniform<BT>(jj);
+        const i64 j = cpb_uniform<BT>(jj);  // MASKED: the first ACTIVE lane's; every lane of the wave has the same column
         const i64 s = tptr[j], e = tptr[j + 1];
         // storage order, equality and inequality partial sums apart (slp_cp_shared.h: the set solver runs the same functions)
         double se, si;
@@ -118,14 +123,15 @@ __global__ __launch_bounds__(kBlock) void k_cpb_primal(i64 n, i64 m, const i64 *
     }
 }
 
-// dual half-iteration: one lane per (row i, instance k)
-template <int BT>
+// dual half-iteration: one lane per (row i, instance k); MASKED as in k_cpb_primal
+template <int BT, bool MASKED>
 __global__ __launch_bounds__(kBlock) void k_cpb_dual(i64 n, i64 m, const i64 *__restrict__ ptr, const i32 *__restrict__ idx,
                                                      const double *__restrict__ val, const double *__restrict__ z,
                                                      const double *__restrict__ b, const double *__restrict__ sigma,
-                                                     double *__restrict__ y, i64 m_eq) {
+                                                     double *__restrict__ y, i64 m_eq, const i32 *__restrict__ stopped) {
     const int k = threadIdx.x & (BT - 1);
     const i64 tile = blockIdx.y;
+    if (MASKED && stopped[tile * BT + k]) return;
     const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT;
     const i64 ngroups = (i64)gridDim.x * kBlock / BT;
     const double *__restrict__ zt = z + tile * n * BT + k;
@@ -229,63 +235,7 @@ __global__ void k_cpb_report_final(i64 Bp, i64 srows, const double *__restrict__
 }
 
 // ---- per-instance stopping on a certified duality gap (header comment; slp_cp_batch_set_stop_gap) ----
-// Kernels of their own: the five above are what a never-armed state launches, untouched.
-
-// max / min as np.max / np.minimum: a NaN on either side stays
-__device__ __forceinline__ double cpb_nanmax(double m, double d) { return (d > m || d != d) ? d : m; }
-__device__ __forceinline__ double cpb_nanmin(double a, double b) { return (b < a || b != b) ? b : a; }
-
-// k_cpb_primal for a state with stopped instances: a lane reads its instance's flag first and returns before any other load
-template <int BT, bool STORE>
-__global__ __launch_bounds__(kBlock) void k_cpb_primal_masked(i64 n, i64 m, const i64 *__restrict__ tptr, const i32 *__restrict__ tidx,
-                                                              const double *__restrict__ tval, const double *__restrict__ y,
-                                                              const double *__restrict__ c, const double *__restrict__ t,
-                                                              const double *__restrict__ lb, const double *__restrict__ ub,
-                                                              double *__restrict__ x, double *__restrict__ z, double *__restrict__ x4,
-                                                              i32 m_eq, i64 m_ineq, double one_plus_theta, double theta,
-                                                              const i32 *__restrict__ stopped) {
-    const int k = threadIdx.x & (BT - 1);
-    const i64 tile = blockIdx.y;
-    if (stopped[tile * BT + k]) return;
-    const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT;
-    const i64 ngroups = (i64)gridDim.x * kBlock / BT;
-    const double *__restrict__ yt = y + tile * m * BT + k;
-    for (i64 jj = group; jj < n; jj += ngroups) {
-        const i64 j = cpb_uniform<BT>(jj);  // the first ACTIVE lane's: every lane of the wave has the same column
-        const i64 s = tptr[j], e = tptr[j + 1];
-        double se, si;
-        cp_column_sums(s, e, tidx, tval, yt, BT, m_eq, CpLoadPlain(), &se, &si);
-        const i64 o = (tile * n + j) * BT + k;
-        const double d = cp_direction(c[o], se, si, m_eq > 0, m_ineq > 0);
-        const double xo = x[o], l = lb[o], u = ub[o];
-        double x2, zn;
-        cp_primal_point(d, xo, t[j], l, u, one_plus_theta, theta, &x2, &zn);
-        z[o] = zn;
-        x[o] = x2;
-        if (STORE) x4[o] = (d < 0.0) ? u : l;
-    }
-}
-
-// k_cpb_dual for a state with stopped instances
-template <int BT>
-__global__ __launch_bounds__(kBlock) void k_cpb_dual_masked(i64 n, i64 m, const i64 *__restrict__ ptr, const i32 *__restrict__ idx,
-                                                            const double *__restrict__ val, const double *__restrict__ z,
-                                                            const double *__restrict__ b, const double *__restrict__ sigma,
-                                                            double *__restrict__ y, i64 m_eq, const i32 *__restrict__ stopped) {
-    const int k = threadIdx.x & (BT - 1);
-    const i64 tile = blockIdx.y;
-    if (stopped[tile * BT + k]) return;
-    const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT;
-    const i64 ngroups = (i64)gridDim.x * kBlock / BT;
-    const double *__restrict__ zt = z + tile * n * BT + k;
-    for (i64 ii = group; ii < m; ii += ngroups) {
-        const i64 i = cpb_uniform<BT>(ii);
-        const i64 s = ptr[i], e = ptr[i + 1];
-        const double kz = cp_row_sum(s, e, idx, val, zt, BT, CpLoadPlain());
-        const i64 o = (tile * m + i) * BT + k;
-        y[o] = cp_dual_point(kz, b[o], y[o], sigma[i], i >= m_eq);
-    }
-}
+// The arithmetic per column, per row and of the decision is slp_cp_gap.h's; an armed state iterates with MASKED.
 
 // certificate, column pass (the report's slices).  part[(q * S + slice) * Bp + instance]: q = 0 sum c_j x_j, 1 the bound's column
 // terms sum [d_j != 0 ? min(d_j lb_j, d_j ub_j) : 0] with d = c + K^T y as the next primal half forms it
@@ -311,7 +261,7 @@ __global__ __launch_bounds__(kBlock) void k_cpb_gap_cols(i64 n, i64 m, const i64
         const double cj = c[o];
         const double d = cp_direction(cj, se, si, m_eq > 0, m_ineq > 0);
         cx += cj * x[o];
-        if (d != 0.0) terms += cpb_nanmin(d * lb[o], d * ub[o]);  // the guard keeps 0 * inf out
+        terms += cp_gap_col_term(d, lb[o], ub[o]);
     }
     part[(0 * ngroups + group) * Bp + inst] = cx;
     part[(1 * ngroups + group) * Bp + inst] = terms;
@@ -336,11 +286,10 @@ __global__ __launch_bounds__(kBlock) void k_cpb_gap_rows(i64 n, i64 m, const i64
         const i64 i = cpb_uniform<BT>(ii);
         const double kx = cp_row_sum(ptr[i], ptr[i + 1], idx, val, xt, BT, CpLoadPlain());
         const i64 o = (tile * m + i) * BT + k;
-        const double bi = b[o], yi = y[o];
-        if (yi != 0.0) yb += yi * bi;  // a row without a finite side has y = 0
-        const double v = kx - bi;
-        if (i < m_eq) veq = cpb_nanmax(veq, fabs(v));
-        else vin = cpb_nanmax(vin, v);
+        const double bi = b[o];
+        yb += cp_gap_row_term(y[o], bi);
+        if (i < m_eq) veq = cp_gap_violation(veq, kx - bi, true);
+        else vin = cp_gap_violation(vin, kx - bi, false);
     }
     part[(0 * ngroups + group) * Bp + inst] = yb;
     part[(1 * ngroups + group) * Bp + inst] = veq;
@@ -375,16 +324,15 @@ __global__ __launch_bounds__(kCpbGapQuantities *kWave) void k_cpb_gap_final(i64 
             }
 #pragma unroll
             for (int u = 0; u < kCpbGapAhead; ++u)
-                if (g0 + u < S) acc = is_max ? cpb_nanmax(acc, a[u]) : acc + a[u];
+                if (g0 + u < S) acc = is_max ? nan_max(acc, a[u]) : acc + a[u];
         }
     }
     folded[q][lane] = acc;
     __syncthreads();
     if (q != 0 || !live) return;
-    const double sy = folded[0][lane], viol = cpb_nanmax(folded[1][lane], folded[2][lane]), primal = folded[3][lane], cols = folded[4][lane];
-    const double bound = cols - sy, gap = fabs(primal - bound);
-    // false for a NaN; an infinite gap (bound = -inf) never stops, whatever tol_gap * inf would say
-    const bool stop = viol <= tol_feas && gap < __builtin_inf() && gap <= tol_gap * (1.0 + fabs(primal) + fabs(bound));
+    const double viol = nan_max(folded[1][lane], folded[2][lane]), primal = folded[3][lane];
+    double bound;
+    const bool stop = cp_gap_decide(primal, folded[4][lane], folded[0][lane], viol, tol_gap, tol_feas, &bound);
     rec[inst * 3 + 0] = primal;
     rec[inst * 3 + 1] = bound;
     rec[inst * 3 + 2] = viol;
@@ -409,7 +357,7 @@ struct slp_cp_batch {
     DevBuf<double> b, c, lb, ub, t, sigma, x, z, y, x4, rowparts, colparts, out;
     i64 iters = 0;  // whole iterations over the state's life: bumped where a dual half is enqueued
     // the certificate test (slp_cp_batch_set_stop_gap); its buffers exist from the first arming on, and from then on the state
-    // launches the masked kernels.  Off while tol_gap < 0.
+    // launches the MASKED kernels.  Off while tol_gap < 0.
     bool masked = false;
     double tol_gap = -1.0, tol_feas = 0.0;
     i64 check_every = 1;
@@ -437,71 +385,48 @@ namespace slp {
 
 static dim3 cpb_grid(const slp_cp_batch *s, i64 rows) { return dim3((unsigned)grid_for(rows * s->Bt, kBlock), (unsigned)s->ntiles); }
 
-// blocks of a report pass: at most kCpbMaxSlices row groups
-static dim3 cpb_report_grid(const slp_cp_batch *s, i64 rows) {
+// blocks of a sliced pass (the report's: kCpbMaxSlices; the certificate's: s->gap_slices): at most `max_slices` row groups
+static dim3 cpb_slice_grid(const slp_cp_batch *s, i64 rows, i64 max_slices) {
     const i64 per_block = kBlock / s->Bt;
     i64 g = (rows + per_block - 1) / per_block;
-    const i64 cap = std::max<i64>(1, kCpbMaxSlices / per_block);
+    const i64 cap = std::max<i64>(1, max_slices / per_block);
     if (g > cap) g = cap;
     if (g < 1) g = 1;
     return dim3((unsigned)g, (unsigned)s->ntiles);
 }
 
-static void cpb_primal(slp_cp_batch *s, bool store) {
-    hipStream_t st = ctx().stream;
+template <bool STORE, bool MASKED>
+static void cpb_launch_primal(slp_cp_batch *s) {
     const CsrDev &at = s->k->at;
-    const double opt = 1.0 + s->theta;
-    const dim3 grid = cpb_grid(s, s->n);
-    if (s->masked) {
-        if (store) {
-            SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_primal_masked<BT, true>), grid, dim3(kBlock), 0, st, s->n, s->m, at.ptr.p,
-                                                        at.idx.p, at.val.p, s->y.p, s->c.p, s->t.p, s->lb.p, s->ub.p, s->x.p, s->z.p,
-                                                        s->x4.p, (i32)s->m_eq, s->m_ineq, opt, s->theta, s->stopped.p));
-        } else {
-            SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_primal_masked<BT, false>), grid, dim3(kBlock), 0, st, s->n, s->m, at.ptr.p,
-                                                        at.idx.p, at.val.p, s->y.p, s->c.p, s->t.p, s->lb.p, s->ub.p, s->x.p, s->z.p,
-                                                        s->x4.p, (i32)s->m_eq, s->m_ineq, opt, s->theta, s->stopped.p));
-        }
-    } else if (store) {
-        SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_primal<BT, true>), grid, dim3(kBlock), 0, st, s->n, s->m, at.ptr.p, at.idx.p,
-                                                    at.val.p, s->y.p, s->c.p, s->t.p, s->lb.p, s->ub.p, s->x.p, s->z.p, s->x4.p,
-                                                    (i32)s->m_eq, s->m_ineq, opt, s->theta));
-    } else {
-        SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_primal<BT, false>), grid, dim3(kBlock), 0, st, s->n, s->m, at.ptr.p, at.idx.p,
-                                                    at.val.p, s->y.p, s->c.p, s->t.p, s->lb.p, s->ub.p, s->x.p, s->z.p, s->x4.p,
-                                                    (i32)s->m_eq, s->m_ineq, opt, s->theta));
-    }
+    SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_primal<BT, STORE, MASKED>), cpb_grid(s, s->n), dim3(kBlock), 0, ctx().stream, s->n, s->m,
+                                                at.ptr.p, at.idx.p, at.val.p, s->y.p, s->c.p, s->t.p, s->lb.p, s->ub.p, s->x.p, s->z.p, s->x4.p,
+                                                (i32)s->m_eq, s->m_ineq, 1.0 + s->theta, s->theta, s->stopped.p));
+    SLP_HIP(hipGetLastError());
+}
+
+static void cpb_primal(slp_cp_batch *s, bool store) {
+    if (s->masked) store ? cpb_launch_primal<true, true>(s) : cpb_launch_primal<false, true>(s);
+    else store ? cpb_launch_primal<true, false>(s) : cpb_launch_primal<false, false>(s);
+}
+
+template <bool MASKED>
+static void cpb_launch_dual(slp_cp_batch *s) {
+    const CsrDev &a = s->k->a;
+    SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_dual<BT, MASKED>), cpb_grid(s, s->m), dim3(kBlock), 0, ctx().stream, s->n, s->m, a.ptr.p,
+                                                a.idx.p, a.val.p, s->z.p, s->b.p, s->sigma.p, s->y.p, s->m_eq, s->stopped.p));
     SLP_HIP(hipGetLastError());
 }
 
 static void cpb_dual(slp_cp_batch *s) {
-    const CsrDev &a = s->k->a;
-    if (s->masked) {
-        SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_dual_masked<BT>), cpb_grid(s, s->m), dim3(kBlock), 0, ctx().stream, s->n, s->m,
-                                                    a.ptr.p, a.idx.p, a.val.p, s->z.p, s->b.p, s->sigma.p, s->y.p, s->m_eq, s->stopped.p));
-    } else {
-        SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_dual<BT>), cpb_grid(s, s->m), dim3(kBlock), 0, ctx().stream, s->n, s->m, a.ptr.p,
-                                                    a.idx.p, a.val.p, s->z.p, s->b.p, s->sigma.p, s->y.p, s->m_eq));
-    }
-    SLP_HIP(hipGetLastError());
+    s->masked ? cpb_launch_dual<true>(s) : cpb_launch_dual<false>(s);
     ++s->iters;  // the dual half ends an iteration
-}
-
-// blocks of a certificate pass: at most s->gap_slices row groups
-static dim3 cpb_gap_grid(const slp_cp_batch *s, i64 rows) {
-    const i64 per_block = kBlock / s->Bt;
-    i64 g = (rows + per_block - 1) / per_block;
-    const i64 cap = std::max<i64>(1, s->gap_slices / per_block);
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return dim3((unsigned)g, (unsigned)s->ntiles);
 }
 
 // the certificate of iteration s->iters for every running instance, enqueued behind its dual half; nothing is read back
 static void cpb_certificate(slp_cp_batch *s) {
     hipStream_t st = ctx().stream;
     const CsrDev &a = s->k->a, &at = s->k->at;
-    const dim3 gr = cpb_gap_grid(s, s->m), gc = cpb_gap_grid(s, s->n);
+    const dim3 gr = cpb_slice_grid(s, s->m, s->gap_slices), gc = cpb_slice_grid(s, s->n, s->gap_slices);
     const i64 srows = (i64)gr.x * kBlock / s->Bt, scols = (i64)gc.x * kBlock / s->Bt;
     // 3 * srows * Bp and 2 * scols * Bp slice sums: the report's scratch holds 5 and 2 times 1024 * Bp
     const bool own = s->gap_slices > kCpbMaxSlices;
@@ -649,7 +574,7 @@ int slp_cp_batch_report(slp_cp_batch *s, double *out) {
         SLP_REQUIRE(s && out, "slp_cp_batch_report: NULL argument");
         hipStream_t st = ctx().stream;
         const CsrDev &a = s->k->a;
-        const dim3 gr = cpb_report_grid(s, s->m), gc = cpb_report_grid(s, s->n);
+        const dim3 gr = cpb_slice_grid(s, s->m, kCpbMaxSlices), gc = cpb_slice_grid(s, s->n, kCpbMaxSlices);
         const i64 srows = (i64)gr.x * kBlock / s->Bt, scols = (i64)gc.x * kBlock / s->Bt;
         SLP_DISPATCH_TILE(s->Bt, hipLaunchKernelGGL((k_cpb_report_cols<BT>), gc, dim3(kBlock), 0, st, s->n, s->c.p, s->x.p, s->x4.p, s->Bp,
                                                     s->colparts.p));
@@ -680,25 +605,22 @@ int slp_cp_batch_bench(slp_cp_batch *s, int64_t k, double ms[3]) {
     SLP_API_INT({
         SLP_REQUIRE(s && k > 0 && ms, "slp_cp_batch_bench: bad arguments");
         Context &c = ctx();
-        float f = 0.f;
-        SLP_HIP(hipEventRecord(c.ev0, c.stream));
-        for (i64 it = 0; it < k; ++it) { cpb_primal(s, false); cpb_dual(s); }
-        SLP_HIP(hipEventRecord(c.ev1, c.stream));
-        SLP_HIP(hipEventSynchronize(c.ev1));
-        SLP_HIP(hipEventElapsedTime(&f, c.ev0, c.ev1));
-        ms[0] = (double)f / (double)k;
-        SLP_HIP(hipEventRecord(c.ev0, c.stream));
-        for (i64 it = 0; it < k; ++it) cpb_primal(s, false);
-        SLP_HIP(hipEventRecord(c.ev1, c.stream));
-        SLP_HIP(hipEventSynchronize(c.ev1));
-        SLP_HIP(hipEventElapsedTime(&f, c.ev0, c.ev1));
-        ms[1] = (double)f / (double)k;
-        SLP_HIP(hipEventRecord(c.ev0, c.stream));
-        for (i64 it = 0; it < k; ++it) cpb_dual(s);
-        SLP_HIP(hipEventRecord(c.ev1, c.stream));
-        SLP_HIP(hipEventSynchronize(c.ev1));
-        SLP_HIP(hipEventElapsedTime(&f, c.ev0, c.ev1));
-        ms[2] = (double)f / (double)k;
+        // milliseconds per repetition of `k` times the halves in `stages` (bit 0 primal, bit 1 dual)
+        auto timed = [&](int stages) {
+            float f = 0.f;
+            SLP_HIP(hipEventRecord(c.ev0, c.stream));
+            for (i64 it = 0; it < k; ++it) {
+                if (stages & 1) cpb_primal(s, false);
+                if (stages & 2) cpb_dual(s);
+            }
+            SLP_HIP(hipEventRecord(c.ev1, c.stream));
+            SLP_HIP(hipEventSynchronize(c.ev1));
+            SLP_HIP(hipEventElapsedTime(&f, c.ev0, c.ev1));
+            return (double)f / (double)k;
+        };
+        ms[0] = timed(3);
+        ms[1] = timed(1);
+        ms[2] = timed(2);
     })
 }
 

@@ -27,6 +27,12 @@
 // order -- per row the three chains K x, K x4, K z of one walk -- then block_reduce: a fixed order, a function of the shapes only.
 // The maxima are exact.  x4 is written by the primal half of a reporting iteration.
 //
+// One text per piece.  cpm_open (the view of an LP, with the LDS fill) and cpm_close (the write-back), cpm_direction (d_j),
+// cpm_primal_half<STEP> and cpm_dual_half<STEP> (a half without its barrier; STEP: the lane's nan-max of what it changed) are
+// device functions used by every iterate kernel below.  The stopping protocol -- the head of the record (ManyCtl), entering from
+// it, a wave's slot, lane 0's fold, the decision slot with its barrier -- is slp_many.h's, shared with slp_admm_many.hip; the
+// scalar arithmetic of the certificate is slp_cp_gap.h's, shared with slp_cp_batch.hip and compiled for the host by a test.
+//
 // Stopping (slp_many_cp_set_stop; off after create).  CpmCtl, one per LP in device memory: iterations completed, the stopped flag,
 // the stopping iteration and the last evaluated step.  Iterations of an LP count from 1 over its whole life; at the end of an
 // iteration t with t % check_every == 0 the LP stops iff step = max(max_j |x2_j - x_j|, max_r |y_r+ - y_r|) <= tol, the differences
@@ -48,15 +54,15 @@
 // violation = max(max_{r < m_eq} |(K x_t)_r - b_r|, max_{r >= m_eq} ((K x_t)_r - b_r), 0) with K x_t a single-accumulator chain
 // in storage order and the maximum NaN-propagating: exact in any order.  At the end of an iteration t with t % check_every == 0 the LP
 // stops iff violation <= tol_feas and |primal - bound| <= tol_gap (1 + |primal| + |bound|) with a finite left-hand side (inf <=
-// tol_gap * inf holds in IEEE arithmetic; a bound of -inf must not stop).  k_cpm_iterate_gap is the third kind of k_cpm_iterate, a
-// template of its own so that the two above stay textually what they were.  An iteration that is no check is the text of STOP =
-// false plus two scalar counters.  A check iteration has its own copy of the dual loop -- K x beside K z in one row walk, per lane
+// tol_gap * inf holds in IEEE arithmetic; a bound of -inf must not stop).  k_cpm_iterate_gap is the third kind of k_cpm_iterate.  An
+// iteration that is no check is cpm_primal_half<false> and cpm_dual_half<false>, the halves of STOP = false, plus two scalar
+// counters.  A check iteration has a dual loop of its own -- K x beside K z in one row walk (cp_row_sums2), per lane
 // sum y_r b_r over its rows in increasing order and the nan-max of the violation -- then, behind the dual half's barrier, one pass over
-// the columns (d_j, its term of the bound, c_j x_j).  A wave reduces its lanes by shuffles in a fixed order (many_wave_sum,
-// many_wave_nanmax) into one LDS slot per quantity; behind one more barrier lane 0 folds the waves in increasing order, writes
-// the record CpmGap (primal, bound, violation: +inf, -inf, +inf before the first check) and ONE decision slot, and a last barrier
-// later every lane reads it.  The two sums are in that fixed order, a function of the shapes only.  done, stopped and stop_iter of
-// CpmCtl are shared with the step test; nothing waits in a record between primal_step and dual_step.
+// the columns (d_j, its term of the bound, c_j x_j).  A wave reduces its lanes by shuffles in a fixed order (many_wave_reduce:
+// two quantities side by side) into one LDS slot per quantity; behind one more barrier lane 0 folds each quantity over the waves in increasing
+// order (many_fold: one loop, four chains), writes the record CpmGap (primal, bound, violation: +inf, -inf, +inf before the first check) and ONE decision slot, and a
+// last barrier later every lane reads it.  The two sums are in that fixed order, a function of the shapes only.  The head of
+// CpmCtl is shared with the step test; nothing waits in a record between primal_step and dual_step.
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -100,13 +106,10 @@ __global__ __launch_bounds__(kBlock) void k_cpm_localise(const CpmLp *__restrict
         }
 }
 
-// per LP, in device memory; written by lane 0 of the LP's workgroup (STOP) and by the host between launches
-struct CpmCtl {
-    i64 done;       // whole iterations completed
-    i64 stop_iter;  // `done` when it stopped
-    double step;    // the last evaluated step, +inf before the first test
-    double dx;      // the primal half's maximum of a check iteration, carried from primal_step to dual_step
-    i32 stopped, pad;
+// per LP, in device memory: the head of slp_many.h and what the step test evaluates
+struct CpmCtl : ManyCtl {
+    double step;  // the last evaluated step, +inf before the first test
+    double dx;    // the primal half's maximum of a check iteration, carried from primal_step to dual_step
 };
 
 struct CpmStop {
@@ -127,8 +130,88 @@ struct CpmArgs {
     double one_plus_theta, theta;
 };
 
-// `iters` times the stages of one LP (bit 0 primal half, bit 1 dual half); store: the primal half also writes x4 (:260-261).
-// STOP: the stopping test of the header comment; `sp` is not looked at without it.
+// What the lanes of an LP's workgroup work on: where its iterates lie (xs, zs, ys: LDS in the lds form, else the global
+// xg, zg, yg) and its columns' data.
+struct CpmView {
+    CpmLp lp;
+    i32 n, m, W, tid;
+    double *xg, *zg, *yg, *xs, *zs, *ys;
+    const double *c, *t, *lb, *ub;
+    const i64 *tptr;
+};
+
+// the view of LP `id`; LDS: x, z, y are copied into `lds`, and a barrier follows
+template <bool LDS>
+__device__ __forceinline__ CpmView cpm_open(const CpmArgs &a, i32 id, double *lds) {
+    CpmView v;
+    v.lp = a.lps[id];
+    v.n = v.lp.n, v.m = v.lp.m_eq + v.lp.m_in, v.W = (i32)blockDim.x, v.tid = (i32)threadIdx.x;
+    v.xg = a.x + v.lp.col0, v.zg = a.z + v.lp.col0, v.yg = a.y + v.lp.y0;
+    v.xs = v.xg, v.zs = v.zg, v.ys = v.yg;
+    if (LDS) {
+        v.xs = lds;
+        v.zs = v.xs + v.n;
+        v.ys = v.zs + v.n;
+        for (i32 j = v.tid; j < v.n; j += v.W) { v.xs[j] = v.xg[j]; v.zs[j] = v.zg[j]; }
+        for (i32 r = v.tid; r < v.m; r += v.W) v.ys[r] = v.yg[r];
+        __syncthreads();
+    }
+    v.c = a.c + v.lp.col0, v.t = a.t + v.lp.col0, v.lb = a.lb + v.lp.col0, v.ub = a.ub + v.lp.col0;
+    v.tptr = a.tptr + v.lp.col0;
+    return v;
+}
+
+// the lds form writes its iterates back, at the end of a launch
+template <bool LDS>
+__device__ __forceinline__ void cpm_close(const CpmView &v) {
+    if (LDS) {
+        for (i32 j = v.tid; j < v.n; j += v.W) { v.xg[j] = v.xs[j]; v.zg[j] = v.zs[j]; }
+        for (i32 r = v.tid; r < v.m; r += v.W) v.yg[r] = v.ys[r];
+    }
+}
+
+// d_j = c_j + (K^T y)_j of column j, the bits the primal half computes
+template <class LD>
+__device__ __forceinline__ double cpm_direction(const CpmArgs &a, const CpmView &v, LD ld, i32 j) {
+    double se, si;
+    cp_column_sums(v.tptr[j], v.tptr[j + 1], a.tidx, a.tval, v.ys, 1, v.lp.m_eq, ld, &se, &si);
+    return cp_direction(v.c[j], se, si, v.lp.m_eq > 0, v.lp.m_in > 0);
+}
+
+// The primal half without its barrier: a lane walks its columns; store: it also writes x4 (:260-261).  STEP: returns the lane's
+// nan-max of |x+ - x| over its columns, 0.0 without it.
+template <bool STEP, class LD>
+__device__ __forceinline__ double cpm_primal_half(const CpmArgs &a, const CpmView &v, LD ld, int store) {
+    double dx = 0.0;
+    for (i32 j = v.tid; j < v.n; j += v.W) {
+        const double d = cpm_direction(a, v, ld, j);
+        const double xo = ld(v.xs + j), l = v.lb[j], u = v.ub[j];
+        double x2, zn;
+        cp_primal_point(d, xo, v.t[j], l, u, a.one_plus_theta, a.theta, &x2, &zn);
+        v.zs[j] = zn;
+        v.xs[j] = x2;
+        if (store) a.x4[v.lp.col0 + j] = (d < 0.0) ? u : l;
+        if (STEP) dx = nan_max(dx, fabs(x2 - xo));
+    }
+    return dx;
+}
+
+// The dual half without its barrier: a lane walks its rows.  STEP: returns the lane's nan-max of |y+ - y|, 0.0 without it.
+template <bool STEP, class LD>
+__device__ __forceinline__ double cpm_dual_half(const CpmArgs &a, const CpmView &v, LD ld) {
+    double dy = 0.0;
+    for (i32 r = v.tid; r < v.m; r += v.W) {
+        const i64 g = many_row(v.lp.eq0, v.lp.in0, v.lp.m_eq, r);
+        const double kz = cp_row_sum(a.ptr[g], a.ptr[g + 1], a.idx, a.val, v.zs, 1, ld);
+        const double yo = ld(v.ys + r), yn = cp_dual_point(kz, a.b[g], yo, a.sigma[g], r >= v.lp.m_eq);
+        v.ys[r] = yn;
+        if (STEP) dy = nan_max(dy, fabs(yn - yo));
+    }
+    return dy;
+}
+
+// `iters` times the stages of one LP (bit 0 primal half, bit 1 dual half); store: the primal half also writes x4.
+// STOP: the step test of the header comment, by the protocol of slp_many.h; `sp` is not looked at without it.
 template <bool LDS, bool STOP>
 __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int iters, int stages, int store, CpmStop sp) {
     extern __shared__ __attribute__((aligned(16))) double cpm_lds[];
@@ -136,71 +219,27 @@ __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int ite
     using LD = typename std::conditional<LDS, CpLoadPlain, CpLoadWorkgroup>::type;
     const LD ld;
     const i32 id = a.list[blockIdx.x];
-    const CpmLp lp = a.lps[id];
-    const i32 n = lp.n, m = lp.m_eq + lp.m_in, W = (i32)blockDim.x, tid = (i32)threadIdx.x;
-    i64 done = 0, until = 0;  // STOP: iterations completed; iterations up to and including the next check
-    if (STOP) {
-        const CpmCtl *ctl = sp.ctl + id;
-        if (ctl->stopped) return;  // set before the launch: the same for every lane
-        done = ctl->done;          // lane 0 writes the record only behind a barrier that follows this load
-        until = sp.check_every - done % sp.check_every;
-    }
-    const bool has_eq = lp.m_eq > 0, has_in = lp.m_in > 0;
-    double *xg = a.x + lp.col0, *zg = a.z + lp.col0, *yg = a.y + lp.y0;
-    double *xs = xg, *zs = zg, *ys = yg;
-    if (LDS) {
-        xs = cpm_lds;
-        zs = xs + n;
-        ys = zs + n;
-        for (i32 j = tid; j < n; j += W) { xs[j] = xg[j]; zs[j] = zg[j]; }
-        for (i32 r = tid; r < m; r += W) ys[r] = yg[r];
-        __syncthreads();
-    }
-    const double *c = a.c + lp.col0, *t = a.t + lp.col0, *lb = a.lb + lp.col0, *ub = a.ub + lp.col0;
-    const i64 *tptr = a.tptr + lp.col0;
+    i64 done = 0, until = 0;
+    if (STOP && !many_enter(sp.ctl + id, sp.check_every, &done, &until)) return;
+    const CpmView v = cpm_open<LDS>(a, id, cpm_lds);
     for (int it = 0; it < iters; ++it) {
         const bool check = STOP && until == 1;  // uniform: a function of the record and of `it`
         if (stages & 1) {
-            double dx = 0.0;
-            for (i32 j = tid; j < n; j += W) {
-                double se, si;
-                cp_column_sums(tptr[j], tptr[j + 1], a.tidx, a.tval, ys, 1, lp.m_eq, ld, &se, &si);
-                const double d = cp_direction(c[j], se, si, has_eq, has_in);
-                const double xo = ld(xs + j), l = lb[j], u = ub[j];
-                double x2, zn;
-                cp_primal_point(d, xo, t[j], l, u, a.one_plus_theta, a.theta, &x2, &zn);
-                zs[j] = zn;
-                xs[j] = x2;
-                if (store) a.x4[lp.col0 + j] = (d < 0.0) ? u : l;
-                if (STOP) dx = many_nanmax(dx, fabs(x2 - xo));
-            }
-            if (check) {
-                dx = many_wave_nanmax(dx);
-                if ((tid & (kWave - 1)) == 0) cpm_red[tid / kWave] = dx;
-            }
+            double dx = cpm_primal_half<STOP>(a, v, ld, store);
+            if (check) many_post<1, 1>(cpm_red, kCpmWaves, v.tid, &dx);
             __syncthreads();  // same compute unit: the stores of this half are visible to the next one
         }
         if (STOP && !(stages & 2)) {  // primal_step: the reduced dx waits in the record for dual_step
-            if (check && tid == 0) {
-                double dx = cpm_red[0];
-                for (i32 w = 1; w < W / kWave; ++w) dx = many_nanmax(dx, cpm_red[w]);
+            if (check && v.tid == 0) {
+                double dx;
+                many_fold<1, 1>(cpm_red, kCpmWaves, v.W, &dx);
                 sp.ctl[id].dx = dx;
             }
             continue;
         }
         if (stages & 2) {
-            double dy = 0.0;
-            for (i32 r = tid; r < m; r += W) {
-                const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
-                const double kz = cp_row_sum(a.ptr[g], a.ptr[g + 1], a.idx, a.val, zs, 1, ld);
-                const double yo = ld(ys + r), yn = cp_dual_point(kz, a.b[g], yo, a.sigma[g], r >= lp.m_eq);
-                ys[r] = yn;
-                if (STOP) dy = many_nanmax(dy, fabs(yn - yo));
-            }
-            if (check) {
-                dy = many_wave_nanmax(dy);
-                if ((tid & (kWave - 1)) == 0) cpm_red[kCpmWaves + tid / kWave] = dy;
-            }
+            double dy = cpm_dual_half<STOP>(a, v, ld);
+            if (check) many_post<1, 1>(cpm_red + kCpmWaves, kCpmWaves, v.tid, &dy);
             __syncthreads();
         }
         if (STOP) {  // here an iteration is complete
@@ -210,31 +249,22 @@ __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int ite
                 continue;
             }
             until = sp.check_every;
-            if (tid == 0) {
+            if (v.tid == 0) {
                 CpmCtl *ctl = sp.ctl + id;
-                double dx = (stages & 1) ? cpm_red[0] : ctl->dx, dy = cpm_red[kCpmWaves];
-                for (i32 w = 1; w < W / kWave; ++w) {
-                    if (stages & 1) dx = many_nanmax(dx, cpm_red[w]);
-                    dy = many_nanmax(dy, cpm_red[kCpmWaves + w]);
-                }
-                const double step = many_nanmax(dx, dy);
-                const bool stop = step <= sp.tol;  // false for a NaN
+                // dx, dy.  dual_step: dx waited in the record.  It is named up front and the compiler sinks the load into that
+                // case; read inside the `else` the lds form takes 49 VGPRs for the parent's 48
+                double f[2] = {ctl->dx, 0.0};
+                if (stages & 1) many_fold<2, 3>(cpm_red, kCpmWaves, v.W, f);
+                else many_fold<1, 1>(cpm_red + kCpmWaves, kCpmWaves, v.W, f + 1);
+                const double step = nan_max(f[0], f[1]);
                 ctl->step = step;
-                if (stop) {
-                    ctl->stopped = 1;
-                    ctl->stop_iter = done;
-                }
-                cpm_red[2 * kCpmWaves] = stop ? 1.0 : 0.0;
+                many_decide(ctl, done, step <= sp.tol, cpm_red + 2 * kCpmWaves);  // false for a NaN
             }
-            __syncthreads();  // the one barrier the test adds, in a check iteration only
-            if (cpm_red[2 * kCpmWaves] != 0.0) break;  // one slot, read by every lane: uniform
+            if (many_decided(cpm_red + 2 * kCpmWaves)) break;
         }
     }
-    if (STOP && (stages & 2) && tid == 0) sp.ctl[id].done = done;
-    if (LDS) {
-        for (i32 j = tid; j < n; j += W) { xg[j] = xs[j]; zg[j] = zs[j]; }
-        for (i32 r = tid; r < m; r += W) yg[r] = ys[r];
-    }
+    if (STOP && (stages & 2) && v.tid == 0) sp.ctl[id].done = done;
+    cpm_close<LDS>(v);
 }
 
 // per LP, beside CpmCtl: the numbers of the last evaluated certificate (+inf, -inf, +inf before the first); written by lane 0 of
@@ -244,49 +274,15 @@ struct CpmGap {
 };
 
 struct CpmGapStop {
-    CpmCtl *ctl;  // done, stopped, stop_iter: shared with the step test; step and dx are not touched
+    CpmCtl *ctl;  // the head is shared with the step test; step and dx are not touched
     CpmGap *rec;
     double tol_gap, tol_feas;
     i64 check_every;
 };
 
-// min as np.minimum: a NaN on either side stays
-__device__ __forceinline__ double cpm_nanmin(double a, double b) { return (b < a || b != b) ? b : a; }
-
-// cp_row_sum with a second chain beside it: K z and K x of one row in one walk, each a single accumulator in storage order
-template <class LD>
-__device__ __forceinline__ void cpm_row_sums2(i64 s, i64 e, const i32 *__restrict__ idx, const double *__restrict__ val, const double *__restrict__ z,
-                                              const double *__restrict__ x, LD ld, double *kz_out, double *kx_out) {
-    double kz = 0.0, kx = 0.0;
-    for (i64 q0 = s; q0 < e; q0 += 4) {
-        i32 j[4];
-        double a[4], g[4], h[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const i64 qq = (q0 + q < e) ? q0 + q : e - 1;
-            j[q] = idx[qq];
-            a[q] = val[qq];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            g[q] = ld(z + j[q]);
-            h[q] = ld(x + j[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (q0 + q < e) {
-                kz += a[q] * g[q];
-                kx += a[q] * h[q];
-            }
-    }
-    *kz_out = kz;
-    *kx_out = kx;
-}
-
-// The third kind of k_cpm_iterate: the iteration of STOP = false with the duality-gap certificate as the per-LP stopping test
-// (header comment).  A kernel of its own, so that the two instantiations above stay what they are; the iteration outside a check
-// is the text of STOP = false plus two scalar counters, and a check iteration has its own copy of the dual loop.  Every branch
-// around a barrier is on `stages`, `check`, the record or the decision slot: uniform.
+// k_cpm_iterate with the duality-gap certificate (slp_cp_gap.h) as the per-LP stopping test (header comment).  An iteration that
+// is no check is the two halves above plus two scalar counters; a check iteration has its own dual loop and the certificate's
+// pass over the columns.  Every branch around a barrier is on `stages`, `until`, the record or the decision slot: uniform.
 template <bool LDS>
 __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate_gap(CpmArgs a, int iters, int stages, int store, CpmGapStop sp) {
     extern __shared__ __attribute__((aligned(16))) double cpm_lds[];
@@ -294,118 +290,58 @@ __global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate_gap(CpmArgs a, int
     using LD = typename std::conditional<LDS, CpLoadPlain, CpLoadWorkgroup>::type;
     const LD ld;
     const i32 id = a.list[blockIdx.x];
-    const CpmLp lp = a.lps[id];
-    const i32 n = lp.n, m = lp.m_eq + lp.m_in, W = (i32)blockDim.x, tid = (i32)threadIdx.x;
-    const CpmCtl *ctl0 = sp.ctl + id;
-    if (ctl0->stopped) return;  // set before the launch: the same for every lane
-    i64 done = ctl0->done;      // lane 0 writes the record only behind a barrier that follows this load
-    i64 until = sp.check_every - done % sp.check_every;
-    const bool has_eq = lp.m_eq > 0, has_in = lp.m_in > 0;
-    double *xg = a.x + lp.col0, *zg = a.z + lp.col0, *yg = a.y + lp.y0;
-    double *xs = xg, *zs = zg, *ys = yg;
-    if (LDS) {
-        xs = cpm_lds;
-        zs = xs + n;
-        ys = zs + n;
-        for (i32 j = tid; j < n; j += W) { xs[j] = xg[j]; zs[j] = zg[j]; }
-        for (i32 r = tid; r < m; r += W) ys[r] = yg[r];
-        __syncthreads();
-    }
-    const double *c = a.c + lp.col0, *t = a.t + lp.col0, *lb = a.lb + lp.col0, *ub = a.ub + lp.col0;
-    const i64 *tptr = a.tptr + lp.col0;
+    i64 done, until;
+    if (!many_enter(sp.ctl + id, sp.check_every, &done, &until)) return;
+    const CpmView v = cpm_open<LDS>(a, id, cpm_lds);
     for (int it = 0; it < iters; ++it) {
         if (stages & 1) {
-            for (i32 j = tid; j < n; j += W) {
-                double se, si;
-                cp_column_sums(tptr[j], tptr[j + 1], a.tidx, a.tval, ys, 1, lp.m_eq, ld, &se, &si);
-                const double d = cp_direction(c[j], se, si, has_eq, has_in);
-                const double xo = ld(xs + j), l = lb[j], u = ub[j];
-                double x2, zn;
-                cp_primal_point(d, xo, t[j], l, u, a.one_plus_theta, a.theta, &x2, &zn);
-                zs[j] = zn;
-                xs[j] = x2;
-                if (store) a.x4[lp.col0 + j] = (d < 0.0) ? u : l;
-            }
+            cpm_primal_half<false>(a, v, ld, store);
             __syncthreads();  // same compute unit: the stores of this half are visible to the next one
         }
         if (!(stages & 2)) continue;  // primal_step: the certificate needs nothing of this half but x itself
-        if (until != 1) {             // no check: the dual half of STOP = false
-            for (i32 r = tid; r < m; r += W) {
-                const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
-                const double kz = cp_row_sum(a.ptr[g], a.ptr[g + 1], a.idx, a.val, zs, 1, ld);
-                ys[r] = cp_dual_point(kz, a.b[g], ld(ys + r), a.sigma[g], r >= lp.m_eq);
-            }
+        if (until != 1) {             // no check
+            cpm_dual_half<false>(a, v, ld);
             __syncthreads();
             ++done;
             --until;
             continue;
         }
         // a check iteration: the dual half with K x beside K z, then the certificate pass over the columns
-        double yb = 0.0, viol = 0.0;
-        for (i32 r = tid; r < m; r += W) {
-            const i64 g = many_row(lp.eq0, lp.in0, lp.m_eq, r);
+        double rows[2] = {0.0, 0.0};  // sum y b, violation
+        for (i32 r = v.tid; r < v.m; r += v.W) {
+            const i64 g = many_row(v.lp.eq0, v.lp.in0, v.lp.m_eq, r);
             double kz, kx;
-            cpm_row_sums2(a.ptr[g], a.ptr[g + 1], a.idx, a.val, zs, xs, ld, &kz, &kx);
-            const double bi = a.b[g], yn = cp_dual_point(kz, bi, ld(ys + r), a.sigma[g], r >= lp.m_eq);
-            ys[r] = yn;
-            if (yn != 0.0) yb += yn * bi;  // the guard keeps 0 * inf out (a row without a finite bound has y = 0)
-            const double v = kx - bi;
-            viol = many_nanmax(viol, r < lp.m_eq ? fabs(v) : v);
+            cp_row_sums2(a.ptr[g], a.ptr[g + 1], a.idx, a.val, v.zs, v.xs, ld, &kz, &kx);
+            const double bi = a.b[g], yn = cp_dual_point(kz, bi, ld(v.ys + r), a.sigma[g], r >= v.lp.m_eq);
+            v.ys[r] = yn;
+            rows[0] += cp_gap_row_term(yn, bi);
+            rows[1] = cp_gap_violation(rows[1], kx - bi, r < v.lp.m_eq);
         }
-        yb = many_wave_sum(yb);
-        viol = many_wave_nanmax(viol);
-        if ((tid & (kWave - 1)) == 0) {
-            cpm_red[tid / kWave] = yb;
-            cpm_red[kCpmWaves + tid / kWave] = viol;
-        }
+        many_post<2, 2>(cpm_red, kCpmWaves, v.tid, rows);
         __syncthreads();  // the barrier that ends the dual half: y is the y of this iteration
-        double cx = 0.0, bt = 0.0;
-        for (i32 j = tid; j < n; j += W) {
-            double se, si;
-            cp_column_sums(tptr[j], tptr[j + 1], a.tidx, a.tval, ys, 1, lp.m_eq, ld, &se, &si);
-            const double d = cp_direction(c[j], se, si, has_eq, has_in);  // the bits the next primal half computes
-            cx += c[j] * ld(xs + j);
-            if (d != 0.0) bt += cpm_nanmin(d * lb[j], d * ub[j]);
+        double cols[2] = {0.0, 0.0};  // c x, the bound's column terms
+        for (i32 j = v.tid; j < v.n; j += v.W) {
+            cols[0] += v.c[j] * ld(v.xs + j);
+            cols[1] += cp_gap_col_term(cpm_direction(a, v, ld, j), v.lb[j], v.ub[j]);  // d_j as the next primal half computes it
         }
-        cx = many_wave_sum(cx);
-        bt = many_wave_sum(bt);
-        if ((tid & (kWave - 1)) == 0) {
-            cpm_red[2 * kCpmWaves + tid / kWave] = cx;
-            cpm_red[3 * kCpmWaves + tid / kWave] = bt;
-        }
+        many_post<2, 0>(cpm_red + 2 * kCpmWaves, kCpmWaves, v.tid, cols);
         __syncthreads();  // the slots of every wave are written
         ++done;
         until = sp.check_every;
-        if (tid == 0) {
-            double sy = cpm_red[0], vmax = cpm_red[kCpmWaves], primal = cpm_red[2 * kCpmWaves], cols = cpm_red[3 * kCpmWaves];
-            for (i32 w = 1; w < W / kWave; ++w) {  // the waves in increasing order
-                sy += cpm_red[w];
-                vmax = many_nanmax(vmax, cpm_red[kCpmWaves + w]);
-                primal += cpm_red[2 * kCpmWaves + w];
-                cols += cpm_red[3 * kCpmWaves + w];
-            }
-            const double bound = cols - sy, gap = fabs(primal - bound);
-            // false for a NaN; an infinite gap (bound = -inf) never stops, whatever tol_gap * inf would say
-            const bool stop = vmax <= sp.tol_feas && gap < __builtin_inf() && gap <= sp.tol_gap * (1.0 + fabs(primal) + fabs(bound));
+        if (v.tid == 0) {
+            double f[4], bound;  // sum y b, violation, c x, column terms: each over the waves in increasing order
+            many_fold<4, 2>(cpm_red, kCpmWaves, v.W, f);
+            const bool stop = cp_gap_decide(f[2], f[3], f[0], f[1], sp.tol_gap, sp.tol_feas, &bound);
             CpmGap *rec = sp.rec + id;
-            rec->primal = primal;
+            rec->primal = f[2];
             rec->bound = bound;
-            rec->violation = vmax;
-            if (stop) {
-                CpmCtl *ctl = sp.ctl + id;
-                ctl->stopped = 1;
-                ctl->stop_iter = done;
-            }
-            cpm_red[4 * kCpmWaves] = stop ? 1.0 : 0.0;
+            rec->violation = f[1];
+            many_decide(sp.ctl + id, done, stop, cpm_red + 4 * kCpmWaves);
         }
-        __syncthreads();
-        if (cpm_red[4 * kCpmWaves] != 0.0) break;  // one slot, read by every lane: uniform
+        if (many_decided(cpm_red + 4 * kCpmWaves)) break;
     }
-    if ((stages & 2) && tid == 0) sp.ctl[id].done = done;
-    if (LDS) {
-        for (i32 j = tid; j < n; j += W) { xg[j] = xs[j]; zg[j] = zs[j]; }
-        for (i32 r = tid; r < m; r += W) yg[r] = ys[r];
-    }
+    if ((stages & 2) && v.tid == 0) sp.ctl[id].done = done;
+    cpm_close<LDS>(v);
 }
 
 // out[5 k + 0..4] as slp_cp_report; one workgroup per LP
@@ -525,12 +461,28 @@ static void cpm_run(slp_cp_many *s, i64 k, int stages, bool store, bool plain = 
     }
 }
 
-// the records with the iterations of the unarmed launches added; synchronises
-static std::vector<CpmCtl> cpm_read_ctl(slp_cp_many *s) {
-    std::vector<CpmCtl> h((size_t)s->count);
-    s->ctl.download(h.data(), h.size());
-    for (CpmCtl &c : h) c.done += s->uncounted;  // no LP is stopped while the test is off
-    return h;
+// what both set_stop calls do behind their argument checks: clear the flags, move the uncounted iterations into the records and
+// arm at most one of the two tests (a negative tolerance: off)
+static void cpm_arm(slp_cp_many *s, double tol, double tol_gap, double tol_feas, i64 check_every) {
+    many_rearm(s->ctl, s->count, &s->uncounted);
+    s->tol = tol < 0.0 ? -1.0 : tol;
+    s->tol_gap = tol_gap < 0.0 ? -1.0 : tol_gap;
+    if (tol >= 0.0 || tol_gap >= 0.0) s->check_every = check_every;
+    if (tol_gap >= 0.0) s->tol_feas = tol_feas;
+}
+
+// what both *_state calls read out; any pointer may be NULL.  Synchronises.
+static void cpm_state(slp_cp_many *s, int64_t *iterations, int32_t *stopped, double *step, double *primal, double *bound, double *violation) {
+    const std::vector<CpmCtl> h = many_read_ctl(s->ctl, s->count, s->uncounted);
+    std::vector<CpmGap> g(h.size());
+    if (primal || bound || violation) s->gap.download(g.data(), g.size());
+    for (size_t k = 0; k < h.size(); ++k) {
+        many_state_head(h[k], k, iterations, stopped);
+        if (step) step[k] = h[k].step;
+        if (primal) primal[k] = g[k].primal;
+        if (bound) bound[k] = g[k].bound;
+        if (violation) violation[k] = g[k].violation;
+    }
 }
 
 // form per LP, workgroup, LDS and launch cap per form -- from the shapes (and the two environment switches) only
@@ -636,7 +588,7 @@ slp_cp_many *slp_cp_many_create(int64_t count, const int64_t *n, const int64_t *
         s->x4.alloc((size_t)N);
         s->x4.zero();
         s->out.alloc((size_t)5 * (size_t)count);
-        std::vector<CpmCtl> ctl((size_t)count, CpmCtl{0, 0, __builtin_inf(), 0.0, 0, 0});
+        std::vector<CpmCtl> ctl((size_t)count, CpmCtl{{0, 0, 0, 0}, __builtin_inf(), 0.0});
         s->ctl.upload(ctl.data(), ctl.size());
         std::vector<CpmGap> gap((size_t)count, CpmGap{__builtin_inf(), -__builtin_inf(), __builtin_inf()});
         s->gap.upload(gap.data(), gap.size());
@@ -672,13 +624,7 @@ int slp_many_cp_set_stop(slp_cp_many *s, double tol, int64_t check_every) {
         SLP_REQUIRE(s, "slp_many_cp_set_stop: NULL handle");
         SLP_REQUIRE(tol < 0.0 || (std::isfinite(tol) && check_every >= 1),
                     "slp_many_cp_set_stop: tol must be finite and >= 0 with check_every >= 1 (tol < 0 turns the test off)");
-        std::vector<CpmCtl> h = cpm_read_ctl(s);
-        for (CpmCtl &c : h) c.stopped = 0;
-        s->ctl.upload(h.data(), h.size());
-        s->uncounted = 0;
-        s->tol = tol < 0.0 ? -1.0 : tol;
-        s->tol_gap = -1.0;  // arming one test disarms the other
-        if (tol >= 0.0) s->check_every = check_every;
+        cpm_arm(s, tol, -1.0, 0.0, check_every);  // arming one test disarms the other
     })
 }
 
@@ -688,44 +634,21 @@ int slp_many_cpgap_set_stop(slp_cp_many *s, double tol_gap, double tol_feas, int
         SLP_REQUIRE(tol_gap < 0.0 || (std::isfinite(tol_gap) && std::isfinite(tol_feas) && tol_feas >= 0.0 && check_every >= 1),
                     "slp_many_cpgap_set_stop: tol_gap and tol_feas must be finite and >= 0 with check_every >= 1 (tol_gap < 0 turns the "
                     "test off)");
-        std::vector<CpmCtl> h = cpm_read_ctl(s);
-        for (CpmCtl &c : h) c.stopped = 0;
-        s->ctl.upload(h.data(), h.size());
-        s->uncounted = 0;
-        s->tol = -1.0;  // arming one test disarms the other
-        s->tol_gap = tol_gap < 0.0 ? -1.0 : tol_gap;
-        if (tol_gap >= 0.0) {
-            s->tol_feas = tol_feas;
-            s->check_every = check_every;
-        }
+        cpm_arm(s, -1.0, tol_gap, tol_feas, check_every);
     })
 }
 
 int slp_many_cpgap_state(slp_cp_many *s, int64_t *iterations, int32_t *stopped, double *primal, double *bound, double *violation) {
     SLP_API_INT({
         SLP_REQUIRE(s, "slp_many_cpgap_state: NULL handle");
-        const std::vector<CpmCtl> h = cpm_read_ctl(s);
-        std::vector<CpmGap> g(h.size());
-        s->gap.download(g.data(), g.size());
-        for (size_t k = 0; k < h.size(); ++k) {
-            if (iterations) iterations[k] = h[k].stopped ? h[k].stop_iter : h[k].done;
-            if (stopped) stopped[k] = h[k].stopped;
-            if (primal) primal[k] = g[k].primal;
-            if (bound) bound[k] = g[k].bound;
-            if (violation) violation[k] = g[k].violation;
-        }
+        cpm_state(s, iterations, stopped, nullptr, primal, bound, violation);
     })
 }
 
 int slp_many_cp_stop_state(slp_cp_many *s, int64_t *iterations, int32_t *stopped, double *step) {
     SLP_API_INT({
         SLP_REQUIRE(s, "slp_many_cp_stop_state: NULL handle");
-        const std::vector<CpmCtl> h = cpm_read_ctl(s);
-        for (size_t k = 0; k < h.size(); ++k) {
-            if (iterations) iterations[k] = h[k].stopped ? h[k].stop_iter : h[k].done;
-            if (stopped) stopped[k] = h[k].stopped;
-            if (step) step[k] = h[k].step;
-        }
+        cpm_state(s, iterations, stopped, step, nullptr, nullptr, nullptr);
     })
 }
 

@@ -68,6 +68,37 @@ __device__ __forceinline__ double cp_row_sum(i64 s, i64 e, const i32 *__restrict
     return kz;
 }
 
+// cp_row_sum with a second chain beside it: K z and K x of one row in one walk, each a single accumulator in storage order
+// (the certificate's check iteration in slp_cp_many.hip)
+template <class LD>
+__device__ __forceinline__ void cp_row_sums2(i64 s, i64 e, const i32 *__restrict__ idx, const double *__restrict__ val, const double *__restrict__ z,
+                                             const double *__restrict__ x, LD ld, double *kz_out, double *kx_out) {
+    double kz = 0.0, kx = 0.0;
+    for (i64 q0 = s; q0 < e; q0 += 4) {
+        i32 j[4];
+        double a[4], g[4], h[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const i64 qq = (q0 + q < e) ? q0 + q : e - 1;
+            j[q] = idx[qq];
+            a[q] = val[qq];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            g[q] = ld(z + j[q]);
+            h[q] = ld(x + j[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (q0 + q < e) {
+                kz += a[q] * g[q];
+                kx += a[q] * h[q];
+            }
+    }
+    *kz_out = kz;
+    *kx_out = kx;
+}
+
 // d = (c + y_eq * a_eq) + y_ineq * a_ineq (:206,216), or the form of an LP with one kind of rows
 __device__ __forceinline__ double cp_direction(double cj, double se, double si, bool has_eq, bool has_ineq) {
     if (has_eq && has_ineq) return (cj + se) + si;

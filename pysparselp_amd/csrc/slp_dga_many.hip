@@ -207,7 +207,7 @@ __global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int
                 for (i32 i = r0 + tid; i < r1; i += kDgaFusedThreads) {
                     const double yo = ld(y + i), yn = dga_update_y(yo, t, ld(g + i), ineq);
                     y[i] = yn;
-                    dy = many_nanmax(dy, fabs(yn - yo));
+                    dy = nan_max(dy, fabs(yn - yo));
                 }
             } else {
                 for (i32 i = r0 + tid; i < r1; i += kDgaFusedThreads) y[i] = dga_update_y(ld(y + i), t, ld(g + i), ineq);
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int
             __syncthreads();
             if (tid == 0) {
                 double step = red[0];
-                for (int w = 1; w < kDgaFusedThreads / kWave; ++w) step = many_nanmax(step, red[w]);
+                for (int w = 1; w < kDgaFusedThreads / kWave; ++w) step = nan_max(step, red[w]);
                 const int stop = (step <= sp.tol && !(ctl->flags & DGA_NAN)) ? 1 : 0;   // false for a NaN
                 rec->step = step;
                 rec->done = done;

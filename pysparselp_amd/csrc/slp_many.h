@@ -1,7 +1,9 @@
 // slp_many.h -- what the list solvers (slp_cp_many.hip, slp_admm_many.hip, slp_dga_many.hip) share on the HIP side; the decisions
-// that need no device are in slp_many_plan.h.
+// that need no device are in slp_many_plan.h.  The NaN-propagating nan_max / nan_min of every per-LP stopping test are in
+// slp_cp_gap.h, included here: that header compiles without HIP, so the host test of the certificate pins the same text.
 #pragma once
 #include "slp_common.h"
+#include "slp_cp_gap.h"
 #include "slp_kernels.h"
 #include "slp_many_plan.h"
 
@@ -10,22 +12,107 @@ namespace slp {
 // row `r` of an LP (equality rows first) in a matrix that holds the equality rows of all LPs before their inequality rows
 __device__ __forceinline__ i64 many_row(i64 eq0, i64 in0, i32 m_eq, i32 r) { return r < m_eq ? eq0 + r : in0 + (r - m_eq); }
 
-// max as np.max: a NaN on either side stays (the per-LP stopping tests of slp_cp_many.hip and slp_admm_many.hip)
-__device__ __forceinline__ double many_nanmax(double m, double d) { return (d > m || d != d) ? d : m; }
-
-// the same over the 64 lanes of a wave, by shuffles: lane 0 holds the result
-__device__ __forceinline__ double many_wave_nanmax(double v) {
+// Q values over the 64 lanes of a wave, by shuffles in a fixed order (32, 16, ..., 1) -- bit q of MAXES: v[q] by nan_max
+// (slp_cp_gap.h), else a sum, a function of the lanes' values only -- the Q chains side by side: lane 0 holds the results
+template <int Q, unsigned MAXES>
+__device__ __forceinline__ void many_wave_reduce(double *v) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = many_nanmax(v, __shfl_down(v, off, kWave));
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const double o = __shfl_down(v[q], off, kWave);
+            v[q] = ((MAXES >> q) & 1) ? nan_max(v[q], o) : v[q] + o;
+        }
+    }
+}
+// one nan-max (slp_dga_many.hip)
+__device__ __forceinline__ double many_wave_nanmax(double v) {
+    many_wave_reduce<1, 1>(&v);
     return v;
 }
 
-// the sum over the 64 lanes of a wave, by shuffles in a fixed order (32, 16, ..., 1): lane 0 holds the result, a function of the
-// lanes' values only (the certificate of slp_cp_many.hip)
-__device__ __forceinline__ double many_wave_sum(double v) {
+// ---- the per-LP stopping protocol of a list kernel that can be resumed (k_cpm_iterate with either test, k_admmm_iterate) ----
+// The head of an LP's control record in device memory; a solver's record derives from it and adds what its test evaluates.
+// Written by lane 0 of the LP's workgroup and by the host between launches; the unarmed kernels touch no word of it.
+struct ManyCtl {
+    i64 done;       // whole iterations completed
+    i64 stop_iter;  // `done` when it stopped
+    i32 stopped, pad;
+};
+
+// Entering a launch: false for an LP that stopped in an earlier launch (the same for every lane: the workgroup returns before
+// its first barrier).  *done: iterations completed; *until: iterations up to and including the next check.  Lane 0 writes the
+// record only behind a barrier that follows these loads.
+__device__ __forceinline__ bool many_enter(const ManyCtl *ctl, i64 check_every, i64 *done, i64 *until) {
+    if (ctl->stopped) return false;
+    *done = ctl->done;
+    *until = check_every - *done % check_every;
+    return true;
+}
+
+// a wave's many_wave_reduce of v[0..Q) into its slots, slots[q * stride + wave]; read behind a later barrier.  The Q reductions
+// run side by side before the one guarded block of stores (one after the other, each with its store, they cost 4 % of an iteration
+// of k_cpm_iterate_gap at check_every = 1: profiles/cp_fold_ab.json)
+template <int Q, unsigned MAXES>
+__device__ __forceinline__ void many_post(double *slots, int stride, i32 tid, double *v) {
+    many_wave_reduce<Q, MAXES>(v);
+    if ((tid & (kWave - 1)) == 0) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;
+        for (int q = 0; q < Q; ++q) slots[q * stride + tid / kWave] = v[q];
+    }
+}
+
+// lane 0: Q quantities of a workgroup of W lanes, quantity q in slots[q * stride + wave], each folded over the waves in
+// increasing order -- bit q of MAXES: by nan_max, else a sum -- in ONE loop, so that the Q chains of LDS loads overlap (a loop per
+// quantity cost 4 % of an iteration of k_cpm_iterate<., true> and 7 % of one of k_cpm_iterate_gap at check_every = 1:
+// profiles/cp_fold_ab.json)
+template <int Q, unsigned MAXES>
+__device__ __forceinline__ void many_fold(const double *slots, int stride, i32 W, double *out) {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) out[q] = slots[q * stride];
+    for (i32 w = 1; w < W / kWave; ++w) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) out[q] = ((MAXES >> q) & 1) ? nan_max(out[q], slots[q * stride + w]) : out[q] + slots[q * stride + w];
+    }
+}
+
+// lane 0, at the end of check iteration `done`: the record's head and the ONE decision slot
+__device__ __forceinline__ void many_decide(ManyCtl *ctl, i64 done, bool stop, double *slot) {
+    if (stop) {
+        ctl->stopped = 1;
+        ctl->stop_iter = done;
+    }
+    *slot = stop ? 1.0 : 0.0;
+}
+
+// every lane: the barrier the test adds to a check iteration, then the slot -- read by every lane, so the break is uniform
+__device__ __forceinline__ bool many_decided(const double *slot) {
+    __syncthreads();
+    return *slot != 0.0;
+}
+
+// host: the records with the iterations of the unarmed launches added (no LP is stopped while the test is off); synchronises
+template <class Ctl>
+std::vector<Ctl> many_read_ctl(const DevBuf<Ctl> &ctl, i64 count, i64 uncounted) {
+    std::vector<Ctl> h((size_t)count);
+    ctl.download(h.data(), h.size());
+    for (Ctl &c : h) c.done += uncounted;
+    return h;
+}
+
+// host: every flag cleared and the uncounted iterations moved into the records, for a set_stop call
+template <class Ctl>
+void many_rearm(DevBuf<Ctl> &ctl, i64 count, i64 *uncounted) {
+    std::vector<Ctl> h = many_read_ctl(ctl, count, *uncounted);
+    for (Ctl &c : h) c.stopped = 0;
+    ctl.upload(h.data(), h.size());
+    *uncounted = 0;
+}
+
+// host: what every *_state call reports from the head of record k
+inline void many_state_head(const ManyCtl &c, size_t k, int64_t *iterations, int32_t *stopped) {
+    if (iterations) iterations[k] = c.stopped ? c.stop_iter : c.done;
+    if (stopped) stopped[k] = c.stopped;
 }
 
 // the lists of the LPs of each form, on the device
