@@ -18,6 +18,10 @@ the violation alone refuses it, the gap is not finite, or ``|primal - bound|`` i
 
 The decision: ``violation <= tol_feas`` and ``|primal - bound| <= tol_gap (1 + |primal| + |bound|)`` with a finite left-hand
 side -- a NaN or an infinite gap (``bound = -inf``: a free variable with ``d_j`` of the wrong sign) never stops.
+
+All of the above repeats the device's formula in the device's order on purpose, so an error of the formula itself would stand on
+both sides.  Two references that share nothing with it: ``exact_bound``, the bound of a given ``y`` in exact rational arithmetic in
+no particular order, and ``highs_optimum``, the LP's optimum from HiGHS, which no lower bound may exceed.
 """
 import collections
 
@@ -183,6 +187,74 @@ def gap_state(cert, tol_gap, tol_feas, check_every, total, after=0, before=(np.i
         return (t, True) + tuple(col[t - 1] for col in cert[:3])
     last = total - total % check_every
     return (total, False) + (tuple(col[last - 1] for col in cert[:3]) if last > after else tuple(before))
+
+
+_EXACT = {}
+
+
+def exact_bound(problem, y):
+    """The certificate's lower bound ``sum_j min(d_j lb_j, d_j ub_j) - y.b`` with ``d = c + K^T y`` of the LP the solver holds, in
+    exact rational arithmetic (every float converts exactly), rounded to a float once at the end: no order of sums, no rounded
+    ``d_j``.  ``-inf`` where a variable without a finite bound on that side has ``d_j`` of the wrong sign.  A row without a finite
+    side (``b_r = +inf``) has ``y_r = 0`` and no term."""
+    from fractions import Fraction
+
+    if id(problem) not in _EXACT:   # the LP's own numbers are converted once
+        lp = held_lp(problem)
+        exact = {name: [Fraction(v) if np.isfinite(v) else v for v in lp[name].tolist()] for name in ("c", "lb", "ub", "b", "vals")}
+        _EXACT[id(problem)] = (problem, dict(exact, rows=lp["rows"].tolist(), cols=lp["cols"].tolist(), m=lp["m"]))
+    lp = _EXACT[id(problem)][1]
+    ys = [Fraction(float(v)) for v in y]
+    assert len(ys) == lp["m"]
+    d = list(lp["c"])
+    for r, j, v in zip(lp["rows"], lp["cols"], lp["vals"]):
+        if ys[r] != 0:
+            d[j] += v * ys[r]
+    total = Fraction(0)
+    for dj, lo, hi in zip(d, lp["lb"], lp["ub"]):
+        if dj == 0:
+            continue
+        side = lo if dj > 0 else hi   # min(d lb, d ub) with lb <= ub
+        if not isinstance(side, Fraction):
+            return -np.inf
+        total += dj * side
+    for yr, br in zip(ys, lp["b"]):
+        if yr != 0:
+            assert isinstance(br, Fraction)
+            total -= yr * br
+    return float(total)
+
+
+_HIGHS = {}
+
+
+def highs_optimum(problem):
+    """``scipy.optimize.linprog(method="highs")`` on the 8-tuple ``problem``, cached per LP (by identity; the LP is kept alive):
+    the equality rows, and one inequality row per finite side of a two-sided row.  HiGHS's presolve answers "infeasible" where it
+    has found the LP infeasible OR unbounded (seen on a feasible, unbounded LP of 65 free-sided variables); an answer of
+    "infeasible" is therefore asked again without presolve, and that answer is returned."""
+    import scipy.optimize
+
+    if id(problem) not in _HIGHS:
+        c, a_eq, beq, a_ineq, bl, bu, lb, ub = problem
+        a_ub, b_ub = None, None
+        if a_ineq is not None and a_ineq.shape[0] > 0:
+            blocks, sides = [a_ineq], [np.asarray(bu, dtype=np.float64)]
+            if bl is not None:
+                blocks.append(-a_ineq)
+                sides.append(-np.asarray(bl, dtype=np.float64))
+            rhs = np.concatenate(sides)
+            finite = np.isfinite(rhs)
+            a_ub, b_ub = scipy.sparse.vstack(blocks).tocsr()[finite], rhs[finite]
+        has_eq = a_eq is not None and a_eq.shape[0] > 0
+        solve = lambda **options: scipy.optimize.linprog(  # noqa: E731
+            c, A_ub=a_ub, b_ub=b_ub, A_eq=a_eq if has_eq else None, b_eq=beq if has_eq else None, bounds=np.column_stack((lb, ub)),
+            method="highs", options=options)
+        res = solve()
+        if res.status == 2:
+            res = solve(presolve=False)
+        _HIGHS[id(problem)] = (problem, res)
+    return _HIGHS[id(problem)][1]
 
 
 def random_list(seed, count=24):

@@ -4,11 +4,16 @@ two line-search errors in a way the device can be compared with, the horizons ar
 HiGHS solves every clean one, and the Chambolle-Pock / ADMM LPs are accepted by the entry points and reach the wave, tile and
 padding sizes they are drawn for.  For tests/test_gpu_fuzz_many_stop.py: under the drawn tolerances, by the numpy restatements
 alone, stopping and running LPs stand side by side in the lists -- in the long one, at every cadence, at the large sizes, warm and
-cold, with equality rows only -- the chosen LP mostly stops by exact equality, and one Chambolle-Pock list stops at a step of 0.0."""
+cold, with equality rows only -- the chosen LP mostly stops by exact equality, and one Chambolle-Pock list stops at a step of 0.0.
+For tests/test_gpu_fuzz_cp_gap.py: boxing an LP changes its bounds and nothing else; the certificate's lists and batches have a
+finite bound at every edge size, hold stopping and running LPs of every kind, unbounded LPs and boxed LPs that never stop, and
+almost no undecidable check; HiGHS solves every LP or calls it unbounded, and the restatement's own bounds are lower bounds by
+HiGHS and agree with the formula in exact rational arithmetic."""
 import os
 import sys
 
 import numpy as np
+import scipy.sparse
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import fuzz_batched  # noqa: E402
@@ -215,3 +220,120 @@ def test_cp_stopping_lists_hold_stopping_and_running_lps_of_every_kind():
     assert _both([e for e in everything if e[3]])   # among the LPs with equality rows only
     # an exact fixed point: a tolerance of 0.0 under which an LP stops at a step of exactly 0.0
     assert any(f["tol"] == (0.0,) and any(e[0] and e[4] == 0.0 for e in f["entries"]) for f in facts)
+
+
+# ---- the certified stopping test: what keeps tests/test_gpu_fuzz_cp_gap.py from passing vacuously -------------------------------------
+
+def test_a_boxed_lp_is_the_same_lp_with_its_finite_bounds():
+    """``random_lp(..., boxed=True)`` consumes the draws of ``boxed=False``: from equal generator states the two LPs differ in
+    ``lb`` / ``ub`` only -- there only where the unboxed one is infinite -- and leave the generator in the same state."""
+    infinite = 0
+    for family in ("cp", "admm", "dga"):
+        for seed, n in ((1, None), (2, 65), (3, 1), (4, 257), (5, None), (6, 2)):
+            plain_rng, boxed_rng = np.random.RandomState(seed), np.random.RandomState(seed)
+            plain, boxed = fuzz_batched.random_lp(plain_rng, family, n), fuzz_batched.random_lp(boxed_rng, family, n, boxed=True)
+            for a, b in zip(plain_rng.get_state(), boxed_rng.get_state()):
+                assert np.array_equal(a, b)
+            assert sorted(plain) == sorted(boxed)
+            for name in plain:
+                p, b = plain[name], boxed[name]
+                if name in ("lb", "ub"):
+                    assert np.all(np.isfinite(b)) and np.array_equal(p[np.isfinite(p)], b[np.isfinite(p)]), (family, seed, name)
+                    infinite += int(np.isinf(p).sum())
+                elif p is None or b is None:
+                    assert p is None and b is None, (family, seed, name)
+                elif scipy.sparse.issparse(p):
+                    assert p.shape == b.shape and (p != b).nnz == 0, (family, seed, name)
+                else:
+                    assert np.array_equal(p, b), (family, seed, name)
+            assert np.all(boxed["lb"] <= boxed["ub"])
+    assert infinite > 0
+
+
+def _gap_lp_shape(problem):
+    """(n, the longest row, an empty row?, an empty column over both blocks?) of an 8-tuple."""
+    blocks = [a for a in (problem[1], problem[3]) if a is not None and a.shape[0]]
+    n = problem[0].size
+    used = np.zeros(n, dtype=bool)
+    for a in blocks:
+        used[a.indices] = True
+    return (n, max(int(np.diff(a.indptr).max()) for a in blocks), any(np.any(np.diff(a.indptr) == 0) for a in blocks), not used.all())
+
+
+def _assert_gap_conditions(family, cases, large):
+    """(a) .. (f) of the certificate's randomised cases, on the restatement alone.  ``large``: the number of entries of the long
+    list / the tile-edge batch.  Returns the statistics."""
+    import cp_gap_cpu
+
+    assert len(cases) == CASES
+    stats = fuzz_batched.gap_statistics(cases)
+    print(family, stats)
+    entries, shapes, highs_checked = [], [], 0
+    for no, case in enumerate(cases):
+        want, keep = case.want(), case.keep()
+        assert case.total == fuzz_batched.STOP_EXTRA + case.its and case.every in fuzz_batched.STOP_EVERY
+        assert case.t_star % case.every == 0 and case.total // 3 <= case.t_star <= case.total
+        assert 1 <= case.after <= max(1, case.total // 3 - 1)
+        assert all(want[0][~want[1]] == case.total) and all(want[0][want[1]] % case.every == 0)
+        if case.k_star is None:
+            assert case.tol == fuzz_batched.NEVER_TOL and not any(ref.finite_checks(case.every, case.total, case.t_star) for ref in case.entries)
+        else:   # (d) the LP the tolerances come from meets them at t_star at the latest, and its check there is decidable
+            star = case.entries[case.k_star]
+            assert case.tol[1] == star.cert.violation[case.t_star - 1]
+            assert cp_gap_cpu.decidable(star.cert, case.t_star, *case.tol), no
+            assert cp_gap_cpu.decision(star.cert.primal[case.t_star - 1], star.cert.bound[case.t_star - 1], star.cert.violation[case.t_star - 1], *case.tol)
+            assert want[1][case.k_star] and want[0][case.k_star] <= case.t_star, no
+        entries += [(bool(want[1][k]), ref.n, ref.warm, ref.eq_only, case.every, len(case.entries)) for k, ref in enumerate(case.entries)]
+        for ref in case.distinct():
+            if ref.finite_checks(case.every, case.total):   # (a)
+                shapes.append(_gap_lp_shape(ref.problem))
+            res, cert = ref.highs(), ref.cert
+            stops = [bool(want[1][k]) for k, other in enumerate(case.entries) if other is ref]
+            assert res.status in (0, 3), (no, res.status, res.message)   # (e)
+            if res.status == 3:
+                assert np.all(np.isneginf(cert.bound)) and not any(stops), no
+                continue
+            finite = np.isfinite(cert.bound)
+            assert np.all(cert.bound[finite] <= res.fun + fuzz_batched.gap_highs_slack(cert.band[finite], res.fun)), no
+            highs_checked += int(finite.sum())
+            if any(stops):
+                t = int(want[0][[other is ref for other in case.entries].index(True)])
+                if cert.violation[t - 1] == 0.0:
+                    assert cert.primal[t - 1] >= res.fun - fuzz_batched.gap_highs_slack(cert.band[t - 1], res.fun), no
+        done = {}
+        for k, (ref, record) in enumerate(zip(case.entries, fuzz_batched.gap_final_records(case))):   # (f)
+            if record is not None and (id(ref), record[0]) not in done:
+                kind = fuzz_batched.gap_bound_kind(record[1].bound, fuzz_batched.gap_exact_bound(ref, record[2]), record[1].band)
+                assert kind is not None, (no, k, record[1])
+                done[(id(ref), record[0])] = kind
+    # (a)
+    ns = {s[0] for s in shapes}
+    print(family, "with a finite bound at a check: n", sorted(ns), "longest row", max(s[1] for s in shapes))
+    assert set(fuzz_batched.EDGE_N) <= ns and max(s[1] for s in shapes) > 64 and any(s[2] for s in shapes) and any(s[3] for s in shapes)
+    # (b)
+    assert stats["entries"] == len(entries) and stats["stopped"] == sum(e[0] for e in entries)
+    assert 4 * stats["stopped"] >= stats["entries"] and 4 * stats["running"] >= stats["entries"]
+    assert large in [e[5] for e in entries] and _both([e for e in entries if e[5] == large])
+    for every in fuzz_batched.STOP_EVERY:
+        assert _both([e for e in entries if e[4] == every]), every
+    assert _both([e for e in entries if e[1] >= 127])
+    assert _both([e for e in entries if e[2]]) and _both([e for e in entries if not e[2]]) and _both([e for e in entries if e[3]])
+    # (c)
+    assert stats["unbounded"] >= 1 and stats["boxed_never"] >= 1
+    # (d)
+    assert stats["left_out"] <= fuzz_batched.GAP_LEFT_OUT * stats["entries"]
+    assert stats["left_out_late"] <= fuzz_batched.GAP_LEFT_OUT * stats["entries"]
+    # (e): the allowance for HiGHS's own tolerances is ten times the measured excess, at least 1e-9
+    assert highs_checked == stats["finite_records"] > 0
+    assert fuzz_batched.HIGHS_ALLOWANCE >= max(10 * stats["highs_excess"], fuzz_batched.ENERGY_TOL["rtol"])
+    return stats
+
+
+def test_cp_list_certificate_cases_hold_what_the_gpu_test_claims():
+    stats = _assert_gap_conditions("cp_many_gap", fuzz_batched.cp_gap_cases(CASES, SEED), fuzz_batched.LONG_LIST)
+    assert stats["rounded_to_zero"] == fuzz_batched.CP_GAP_ROUNDED_TO_ZERO
+
+
+def test_cp_batch_certificate_cases_hold_what_the_gpu_test_claims():
+    stats = _assert_gap_conditions("cp_batch_gap", fuzz_batched.cp_batch_gap_cases(CASES, SEED), fuzz_batched.CP_TILE_EDGE)
+    assert stats["rounded_to_zero"] == fuzz_batched.CP_BATCH_GAP_ROUNDED_TO_ZERO

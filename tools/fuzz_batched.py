@@ -16,8 +16,19 @@ at that LP's own count, bit for bit.  ``dga_many_stop`` does the same for dual g
 states; an LP whose stop (or whose last iteration) lies behind its parity horizon is run but not compared, and such LPs are at
 most a quarter of a run.
 
+``cp_many_gap`` and ``cp_batch_gap`` arm the certified stopping test of the Chambolle-Pock list solver and of the batched one
+(``set_stop_gap`` / ``gap_state``, ``chambolle_pock_ppd_many_certified`` / ``chambolle_pock_ppd_batch_certified``) on lists and batches
+of their own, of the same shapes, in which three LPs of four keep their finite bounds (``random_lp(..., boxed=True)``: with a fifth
+of either side infinite the bound is ``-inf`` at every size above a dozen variables and nothing stops).  The tolerances are the
+violation (``<=`` decides by equality) and the relative gap, with a margin, of one LP at a check iteration; iterations, flags and
+records against the numpy restatement (tests/cp_gap_cpu.py), every frozen iterate against the oracle's at its own count, bit for
+bit; an LP with a check too close to its threshold to be decided in another order of sums is run, its stopping iteration not
+compared (at most 5 % of a family).  The recorded bound is also checked against the formula in exact rational arithmetic on the
+device's own ``y`` and, as a lower bound, against HiGHS.
+
     python tools/fuzz_batched.py [--cases 24] [--seed 0]
-        [--family cp_batch,cp_many,admm_batch,admm_many,dga,dga_batch,dga_many,cp_many_stop,admm_many_stop,dga_many_stop]
+        [--family cp_batch,cp_many,admm_batch,admm_many,dga,dga_batch,dga_many,cp_many_stop,admm_many_stop,dga_many_stop,
+                  cp_many_gap,cp_batch_gap]
 
 The generators and the CPU references need no GPU (tests/test_fuzz_batched_host.py checks on them that the GPU runs compare what
 they claim to); the ``run_*`` functions need one."""
@@ -54,7 +65,23 @@ CP_STOP_OFFSET, ADMM_STOP_OFFSET = 8000, 7000   # the stopping draws' generators
 DGA_STOP_OFFSET, DGA_STOP_EVERY = 6027, (1, 2, 5, 10)
 DGA_STOP_LEFT_OUT = 0.25   # the largest share of the LPs of a run that may lie behind their parity horizon (not compared)
 STOP_AFTER_OFFSET = 500   # on top of them: the generator of ``after``, so that the test's own draws do not depend on it
-TEST_SEED, TEST_CASES = 20, 24   # what tests/test_gpu_fuzz_batched.py runs and tests/test_fuzz_batched_host.py checks
+# the certified stopping test (``cp_many_gap`` / ``cp_batch_gap``): the generators of the lists and of the batches, and on top of
+# them those of the coin that boxes an LP (with probability GAP_BOXED) and of the test's own draws.  The lists' offset 9000 meets
+# the conditions of tests/test_fuzz_batched_host.py at once.  The batches': 10000 was tried first; 10109 is the smallest offset from
+# there on that meets them on the CPU.  Of the 109 before it 91 draw an instance that HiGHS calls infeasible (``batch_of`` moves
+# the right-hand sides of the equality rows by 0.01 N(0, 1), which a block of 5 or 12 rows on few variables does not survive), the
+# 14 miss an edge size among the LPs with a finite bound, and 4 lack stopping or running instances of one of the kinds
+CP_GAP_OFFSET, CP_BATCH_GAP_OFFSET = 9000, 10109
+GAP_BOX_OFFSET, GAP_DRAW_OFFSET, GAP_BOXED = 250, 750, 0.75
+NEVER_TOL = (1e-2, 1e-2)   # the tolerances of a case none of whose LPs has a finite bound in the last two thirds of its horizon
+GAP_LEFT_OUT = 0.05   # the largest share of the entries of a family that may have an undecidable check (run, not compared)
+# how far HiGHS's own tolerances may put its optimum below a valid bound, relative to 1 + |optimum|: ten times the largest excess of
+# the restatement's finite bounds over the optimum on the draws of TEST_SEED / TEST_CASES, at least ENERGY_TOL's 1e-9.  Measured on
+# the CPU: lists 0.0 over 4469 finite records, batches 0.0 over 6245 -- so the floor, 1e-9
+HIGHS_ALLOWANCE = 1e-9
+# the final records (of the entries that are compared) with a finite bound over an exact -inf, on the restatement
+CP_GAP_ROUNDED_TO_ZERO, CP_BATCH_GAP_ROUNDED_TO_ZERO = 0, 0
+TEST_SEED, TEST_CASES = 20, 24  # what tests/test_gpu_fuzz_batched.py runs and tests/test_fuzz_batched_host.py checks
 
 
 # ---- generators ----------------------------------------------------------------------------------------------------------------
@@ -63,11 +90,12 @@ def _decimal(rng, size):
     return np.round(rng.randn(size) * 100) / 100
 
 
-def random_lp(rng, family, n=None):
+def random_lp(rng, family, n=None, boxed=False):
     """A small LP as a dict ``c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0`` (``a_eq`` None without equality rows), feasible
     at a point ``xf``.  ``family``: ``"cp"`` (any rows; now and then equality rows only), ``"admm"`` (always an inequality block),
     ``"dga"`` (one-sided rows, finite bounds, no start).  ``n``: the number of variables, drawn when None.  Stored values are
-    multiples of 0.01 plus 0.005: no stored zero."""
+    multiples of 0.01 plus 0.005: no stored zero.  ``boxed``: the LP keeps the finite ``lb``, ``ub`` it has before a fifth of
+    either side is made infinite; the draws consumed are the same, so nothing else about the LP changes."""
     drawn = int(rng.choice(EDGE_N)) if rng.rand() < 0.5 else int(rng.randint(2, 71))
     n = drawn if n is None else n
     me = int(rng.choice([0, 0, 1, 5, 12]))
@@ -107,12 +135,15 @@ def random_lp(rng, family, n=None):
     t = np.abs(rng.randn(n)) + 0.1
     t[rng.rand(n) < 0.15] = 0.0    # fixed variables: lb == ub
     lb, ub = xf - t, xf + t
+    box = lb.copy(), ub.copy()
     x0 = None
     if family != "dga":
         lb[rng.rand(n) < 0.2] = -np.inf
         ub[rng.rand(n) < 0.2] = np.inf
         x0 = None if rng.rand() < 0.5 else np.round(rng.randn(n), 2)
     eq_only = me > 0 and rng.rand() < (0.25 if family == "cp" else 0.1 if family == "dga" else 0.0)
+    if boxed:
+        lb, ub = box
     lp = dict(c=c, a_eq=ae if me else None, beq=be if me else None, a_ineq=ai, b_lower=bl, b_upper=bu, lb=lb, ub=ub, x0=x0)
     if eq_only:
         lp.update(a_ineq=None, b_lower=None, b_upper=None)
@@ -334,6 +365,216 @@ def cp_stop_cases(cases, seed):
 def admm_stop_cases(cases, seed):
     """``[StopCase]`` of ``run_admm_many_stop``: the lists of ``admm_many_cases`` with a stopping test each."""
     return _stop_cases("admm", admm_many_cases, ADMM_STOP_OFFSET, cases, seed)
+
+
+# ---- the certified stopping test of the two Chambolle-Pock families: draws and what the restatement expects ------------------------
+
+class GapRef:
+    """The CPU reference of one LP (or batch instance) of a certificate case, never modified: ``problem`` and ``x0``, the oracle's
+    iterates ``xs[t]`` (``xs[0]`` the start) and ``ys[t]`` after ``t = 0 .. total`` iterations, the restatement ``restated``
+    (``cp_gap_cpu.Restatement``) and its ``cert`` (``cp_gap_cpu.Certificate`` of arrays, entry ``t - 1`` of iteration ``t``), the
+    oracle's ``reports`` at the case's cadence, ``eq_only``, ``boxed``."""
+
+    def __init__(self, problem, x0, total, plot, boxed):
+        import cp_gap_cpu
+
+        self.problem, self.x0, self.boxed, self.eq_only = problem, x0, boxed, problem[3] is None
+        with np.errstate(invalid="ignore", over="ignore"):
+            self.xs, self.ys = cp_gap_cpu.iterates(problem, total, x0)
+            self.cert = cp_gap_cpu.certificates(problem, self.xs, self.ys)
+            self.reports = cp_reference(problem, x0, total, plot)[0]
+        self.restated = cp_gap_cpu.Restatement(problem)
+        for v in self.xs + self.ys:
+            v.setflags(write=False)
+        self.n, self.warm = problem[0].size, x0 is not None
+
+    def finite_checks(self, every, total, first=1):
+        """The check iterations ``first <= t <= total`` at which primal and bound are finite."""
+        return [t for t in range(first, total + 1) if t % every == 0 and np.isfinite(self.cert.primal[t - 1]) and np.isfinite(self.cert.bound[t - 1])]
+
+    def highs(self):
+        import cp_gap_cpu
+
+        return cp_gap_cpu.highs_optimum(self.problem)
+
+
+class GapCase:
+    """One list (``family == "many"``) or one batch (``"batch"``) with its certified stopping test.  ``entries``: one ``GapRef``
+    per LP of the list (a cycled list repeats them) or per instance; ``args`` the batch; ``its`` and ``plot`` the case's own
+    iterations and report cadence, ``total = 20 + its`` the horizon, ``every`` the cadence of the test, ``after`` the unarmed
+    iterations of the run that is armed in mid-life.  The tolerances ``tol = (tol_gap, tol_feas)`` come from the record of entry
+    ``k_star`` at check iteration ``t_star >= total // 3``, drawn among the pairs whose primal and bound are finite there:
+    ``tol_feas`` is that record's violation (a maximum, the device's bits: ``<=`` decides by equality), ``tol_gap`` its relative
+    gap times ``1 + 2^-20`` plus ``2^-30`` (the sums depend on the order: the margin puts that check far outside the undecidable
+    band, the additive term covers a gap of exactly 0).  A case without such a pair has ``k_star = None`` and ``NEVER_TOL``."""
+
+    def __init__(self, family, entries, its, plot, rng, rng_after, args=None):
+        self.family, self.entries, self.its, self.plot, self.args = family, entries, its, plot, args
+        self.total = total = STOP_EXTRA + its
+        self.every = int(rng.choice(STOP_EVERY))
+        self.after = int(rng_after.randint(1, max(1, total // 3 - 1) + 1))
+        first = next(t for t in range(max(1, total // 3), total + 1) if t % self.every == 0)
+        pairs, seen = [], set()
+        for k, ref in enumerate(entries):   # a cycled list repeats its LPs: each distinct LP once
+            if id(ref) not in seen:
+                seen.add(id(ref))
+                pairs += [(k, t) for t in ref.finite_checks(self.every, total, first)]
+        self.k_star, self.t_star, self.tol = None, first, NEVER_TOL
+        if pairs:
+            self.k_star, self.t_star = pairs[int(rng.randint(len(pairs)))]
+            p, b, v, _ = (float(col[self.t_star - 1]) for col in entries[self.k_star].cert)
+            self.tol = (abs(p - b) / (1.0 + abs(p) + abs(b)) * (1.0 + 2.0 ** -20) + 2.0 ** -30, v)
+
+    def distinct(self):
+        out = {}
+        for ref in self.entries:
+            out.setdefault(id(ref), ref)
+        return list(out.values())
+
+    def want(self, after=0):
+        """The restatement's ``gap_state`` columns over the entries after ``total`` iterations, the test armed after ``after``."""
+        import cp_gap_cpu
+
+        rows = {id(ref): cp_gap_cpu.gap_state(ref.cert, *self.tol, self.every, self.total, after=after) for ref in self.distinct()}
+        return tuple(np.array(col) for col in zip(*[rows[id(ref)] for ref in self.entries]))
+
+    def keep(self, after=0):
+        """Per entry: is every check it evaluates decidable?  The others are run; their stopping iteration is not compared."""
+        import cp_gap_cpu
+
+        able = {id(ref): cp_gap_cpu.all_decidable(ref.cert, *self.tol, self.every, self.total, after=after) for ref in self.distinct()}
+        return np.array([able[id(ref)] for ref in self.entries])
+
+
+def _gap_generators(offset, seed):
+    return [np.random.RandomState(seed + offset + extra) for extra in (0, GAP_BOX_OFFSET, GAP_DRAW_OFFSET, STOP_AFTER_OFFSET)]
+
+
+_GAP_CASES = {}
+
+
+def cp_gap_cases(cases, seed):
+    """``[GapCase]`` of ``run_cp_many_gap``: lists shaped as those of ``cp_many_cases`` (the first LP of cases 0 .. 9 at the edge
+    sizes, ``large_case`` cycled to ``LONG_LIST``, 1 to 9 LPs otherwise) from a generator of their own; the coin that boxes an LP
+    (probability ``GAP_BOXED``), the draws of the test and ``after`` come from three further generators, so that none depends on
+    another.  The references are computed once and shared."""
+    key = ("many", cases, seed)
+    if key not in _GAP_CASES:
+        rng, rng_box, rng_draw, rng_after = _gap_generators(CP_GAP_OFFSET, seed)
+        out = []
+        for case in range(cases):
+            lps = []
+            for k in range(int(rng.randint(1, 10))):
+                boxed = bool(rng_box.rand() < GAP_BOXED)
+                lps.append((random_lp(rng, "cp", edge_n(case) if k == 0 else None, boxed=boxed), boxed))
+            its, plot = int(rng.randint(1, 61)), int(rng.choice(CADENCES))
+            refs = [GapRef(of_instance(lp, 0)[0], lp["x0"], STOP_EXTRA + its, plot, boxed) for lp, boxed in lps]
+            if case == large_case(cases):
+                refs = [refs[k % len(refs)] for k in range(LONG_LIST)]
+            out.append(GapCase("many", refs, its, plot, rng_draw, rng_after))
+        _GAP_CASES[key] = out
+    return _GAP_CASES[key]
+
+
+def cp_batch_gap_cases(cases, seed):
+    """``[GapCase]`` of ``run_cp_batch_gap``: batches as those of ``cp_batch_cases`` (``batch_of`` over one LP, ``large_case`` with
+    ``CP_TILE_EDGE`` instances) from generators of their own; the LP under a batch is boxed, or not, by the same coin."""
+    key = ("batch", cases, seed)
+    if key not in _GAP_CASES:
+        rng, rng_box, rng_draw, rng_after = _gap_generators(CP_BATCH_GAP_OFFSET, seed)
+        sizes = batch_sizes(rng, cases, CP_TILE_EDGE)
+        out = []
+        for case, b in enumerate(sizes):
+            boxed = bool(rng_box.rand() < GAP_BOXED)
+            args = batch_of(rng, random_lp(rng, "cp", edge_n(case), boxed=boxed), b, "cp")
+            its, plot = int(rng.randint(1, 61)), int(rng.choice(CADENCES))
+            refs = [GapRef(*of_instance(args, k), STOP_EXTRA + its, plot, boxed) for k in range(b)]
+            out.append(GapCase("batch", refs, its, plot, rng_draw, rng_after, args))
+        _GAP_CASES[key] = out
+    return _GAP_CASES[key]
+
+
+def gap_final_records(case):
+    """Per entry of ``case`` the final record of the run armed from creation, on the restatement: ``(t, Certificate, y_t)`` -- the
+    stopping iteration or the last check -- or None before the first check."""
+    want = case.want()
+    out = []
+    for k, ref in enumerate(case.entries):
+        t = int(want[0][k]) if want[1][k] else case.total - case.total % case.every
+        out.append(None if t < 1 else (t, type(ref.cert)(*(float(col[t - 1]) for col in ref.cert)), ref.ys[t]))
+    return out
+
+
+_GAP_EXACT = {}
+
+
+def gap_exact_bound(ref, y):
+    """``cp_gap_cpu.exact_bound`` of the LP of ``ref`` at ``y``, computed once per ``(LP, y)``: the device's ``y`` is the oracle's bit
+    for bit, and a cycled list repeats its LPs."""
+    import cp_gap_cpu
+
+    key = (id(ref), y.tobytes())
+    if key not in _GAP_EXACT:
+        _GAP_EXACT[key] = cp_gap_cpu.exact_bound(ref.problem, y)
+    return _GAP_EXACT[key]
+
+
+def gap_bound_kind(bound, exact, band):
+    """A bound in the device's or the restatement's arithmetic against ``cp_gap_cpu.exact_bound`` on the same ``y``: ``"close"``
+    (both finite, within ``band``), ``"both -inf"``, ``"rounded to zero"`` (finite over an exact ``-inf``: a rounded ``d_j == 0.0``
+    on a free side whose exact ``d_j`` is not zero; counted, no failure), or None: a mismatch."""
+    if np.isfinite(bound) and np.isfinite(exact):
+        return "close" if abs(bound - exact) <= band else None
+    if bound == -np.inf and exact == -np.inf:
+        return "both -inf"
+    return "rounded to zero" if np.isfinite(bound) and exact == -np.inf else None
+
+
+def gap_highs_slack(band, opt):
+    """How far a bound of rounding band ``band`` may exceed the optimum ``opt`` HiGHS reports (in the manner of
+    ``DgaLP.bound_slack``, plus HiGHS's own tolerances)."""
+    return band + HIGHS_ALLOWANCE * (1.0 + abs(opt))
+
+
+_GAP_STATISTICS = {}
+
+
+def gap_statistics(cases):
+    """``dict(entries, lps, stopped, running, left_out, left_out_late, never_lists, unbounded, boxed_never, rounded_to_zero,
+    highs_excess, finite_records)`` of a list of ``GapCase`` on the restatement alone -- what tests/test_fuzz_batched_host.py
+    asserts on and the GPU runs compare their counts with.  ``rounded_to_zero`` counts the final records of the kept entries;
+    ``highs_excess`` is the largest ``(bound - opt) / (1 + |opt|)`` over all finite records of the LPs HiGHS solves."""
+    if id(cases) in _GAP_STATISTICS:   # computed once per list of cases
+        return dict(_GAP_STATISTICS[id(cases)][1])
+    out = dict(entries=0, lps=0, stopped=0, running=0, left_out=0, left_out_late=0, never_lists=0, unbounded=0, boxed_never=0,
+               rounded_to_zero=0, highs_excess=-np.inf, finite_records=0)
+    for case in cases:
+        want, keep = case.want(), case.keep()
+        out["entries"] += len(case.entries)
+        out["lps"] += len(case.distinct())
+        out["stopped"] += int(want[1].sum())
+        out["running"] += int((~want[1]).sum())
+        out["left_out"] += int((~keep).sum())
+        out["left_out_late"] += int((~case.keep(case.after)).sum())
+        out["never_lists"] += case.k_star is None
+        out["boxed_never"] += sum(ref.boxed and not want[1][k] for k, ref in enumerate(case.entries))
+        for ref in case.distinct():
+            res = ref.highs()
+            finite = np.isfinite(ref.cert.bound)
+            out["unbounded"] += res.status == 3
+            if res.status == 0 and finite.any():
+                out["finite_records"] += int(finite.sum())
+                out["highs_excess"] = max(out["highs_excess"], float(np.max(ref.cert.bound[finite] - res.fun)) / (1.0 + abs(res.fun)))
+        cache = {}
+        for k, (ref, record) in enumerate(zip(case.entries, gap_final_records(case))):
+            if record is None or not keep[k]:
+                continue
+            key = (id(ref), record[0])
+            if key not in cache:
+                cache[key] = gap_bound_kind(record[1].bound, gap_exact_bound(ref, record[2]), record[1].band)
+            out["rounded_to_zero"] += cache[key] == "rounded to zero"
+    _GAP_STATISTICS[id(cases)] = (cases, out)
+    return dict(out)
 
 
 # ---- dual gradient ascent: LPs, batches, lists and their CPU references -----------------------------------------------------------
@@ -1124,6 +1365,264 @@ def run_admm_many_stop(cases, seed):
     return _run_many_stop("admm", cases, seed)
 
 
+# ---- the certified stopping test of the Chambolle-Pock list solver and of the batched one ------------------------------------------------
+
+GAP_NAMES = ("iterations", "stopped", "primal", "lower_bound", "violation")
+
+
+def _gap_where(name, case_no, seed, case, setting, forms):
+    """``where(k, run)``: the head of every message about entry ``k`` of the case in the run ``run``."""
+    def where(k, run):
+        ref = case.entries[k]
+        what = f"LP {k} of {len(case.entries)}" if case.family == "many" else f"instance {k} of {len(case.entries)}"
+        return (f"{name} seed {seed} case {case_no} {what} (n {ref.n}, {'warm' if ref.warm else 'cold'} start, {'boxed' if ref.boxed else 'as drawn'}, "
+                f"{case.total} iterations), setting {setting}, form {forms[k]}, every {case.every}, tolerances {case.tol!r} "
+                f"(entry {case.k_star} at iteration {case.t_star}), {run}")
+    return where
+
+
+def _gap_layer(case, k, count):
+    """Does the single solver agree with the oracle on entry ``k`` after ``count`` iterations?"""
+    ref = case.entries[k]
+    count = max(1, min(int(count), case.total))
+    return _cp_single_agrees(ref.problem, ref.x0, count, ref.xs[count])
+
+
+def _compare_gap(case, want, keep, got, iterates, where, run):
+    """``got`` (the columns of ``gap_state``, or of the driver's ``info``) against the restatement's ``want``: iterations and flags
+    with ``np.array_equal`` on the kept entries, and where both sides evaluated the same check last the violation exactly, primal
+    and bound within ``ENERGY_TOL``.  Unless ``iterates`` is None every entry's ``x`` and ``y`` against the oracle's at that entry's
+    own count (a left-out entry: at the device's count), bit for bit.  Returns the counts the iterates were compared at."""
+    same = keep | (got[0] == want[0])
+    for name, g, w in zip(GAP_NAMES, got, want):
+        with np.errstate(invalid="ignore"):
+            if name in ("iterations", "stopped"):
+                bad = keep & (g != w)
+            elif name == "violation":
+                bad = same & ~((g == w) | (np.isnan(g) & np.isnan(w)))
+            else:
+                bad = same & ~np.isclose(g, w, equal_nan=True, **ENERGY_TOL)
+        if bad.any():
+            k = int(np.nonzero(bad)[0][0])
+            _require(False, where(k, run) + f": {name} {g[k]!r}, the restatement gives {w[k]!r}", _gap_layer(case, k, min(got[0][k], want[0][k])))
+    counts = np.where(keep, want[0], got[0])
+    _require(bool(np.all((counts >= 0) & (counts <= case.total))), where(0, run) + f": iteration counts {got[0]} outside the run")
+    if iterates is not None:
+        for k, ref in enumerate(case.entries):
+            count = int(counts[k])
+            for name, g, r in (("x", iterates[0][k], ref.xs[count]), ("y", iterates[1][k], ref.ys[count])):
+                _require(np.array_equal(g, r), where(k, run) + f": {name} differs from the oracle's after {count} iterations", _gap_layer(case, k, count))
+    return counts
+
+
+def _compare_gap_driver(case, want, keep, xs, info, rec, where):
+    """The ``_certified`` driver: ``info`` is the restatement, ``xs[k]`` the oracle's ``x`` at each entry's count; at every callback a
+    stopped entry has its final iterate and ``callback_func.info`` says so, a running one has the oracle's report (energies within
+    ``ENERGY_TOL``).  The loop ends at the first report index at which every entry is stopped.  A left-out entry is followed at
+    the device's own count."""
+    run = f"the driver with reports every {case.plot}"
+    got = tuple(info[name] for name in GAP_NAMES)
+    counts = _compare_gap(case, want, keep, got, None, where, run)
+    stops = np.where(keep, want[1], got[1])
+    last = int(counts.max()) if stops.all() else case.total
+    reports = [i for i in range(0, case.total, case.plot) if i < last]
+    _require(rec.it == reports, where(0, run) + f": reports at {rec.it}, expected at {reports}")
+    for k, ref in enumerate(case.entries):
+        count = int(counts[k])
+        layer = _gap_layer(case, k, count)
+        _require(np.array_equal(xs[k], ref.xs[count]), where(k, run) + f": the returned x differs from the oracle's after {count} iterations", layer)
+        for i, it in enumerate(reports):
+            at = where(k, run) + f", report at iteration {it}"
+            stopped = bool(stops[k]) and count <= it
+            _require(bool(rec.seen[i]["stopped"][k]) == stopped, at + f": info['stopped'] is {rec.seen[i]['stopped'][k]}, it stops at {count}")
+            _require(int(rec.seen[i]["iterations"][k]) == (count if stopped else it), at + f": info['iterations'] is {rec.seen[i]['iterations'][k]}")
+            if stopped:
+                _require(np.array_equal(rec.x[i][k], ref.xs[count]), at + ": a stopped entry's x is not its final iterate", layer)
+                continue
+            _require(ref.reports.it[i] == it, at + f": the oracle reports at {ref.reports.it[i]}")
+            _require(np.array_equal(rec.x[i][k], ref.reports.x[i]), at + ": x differs", layer)
+            _require(rec.veq[i][k] == ref.reports.veq[i], at + f": max violated equality {rec.veq[i][k]!r} != {ref.reports.veq[i]!r}", layer)
+            if ref.eq_only:
+                _require(rec.vineq[i][k] == 0, at + ": a violated inequality without inequality rows")
+            else:
+                _require(rec.vineq[i][k] == ref.reports.vineq[i], at + f": max violated inequality {rec.vineq[i][k]!r} != {ref.reports.vineq[i]!r}", layer)
+            for name, g, r in (("energy1", rec.e1[i][k], ref.reports.e1[i]), ("energy2", rec.e2[i][k], ref.reports.e2[i])):
+                _require(np.allclose(g, r, equal_nan=True, **ENERGY_TOL), at + f": {name} {g!r} != {r!r}", layer)
+
+
+def _check_gap_bounds(counts, case, keep, got, iterates, where):
+    """The final record of every entry of the run armed from creation, taken where the last check was the last iteration (so
+    that the device's ``y`` is the record's): the device's bound against ``cp_gap_cpu.exact_bound`` on the device's own ``y``, and
+    bound and primal against HiGHS."""
+    run, cache = "the final record", {}
+    for k, ref in enumerate(case.entries):
+        t, stopped, primal, bound, violation = (col[k] for col in got)
+        x, y = iterates[0][k], iterates[1][k]
+        key = (id(ref), int(t), float(bound), y.tobytes())
+        if key not in cache:   # a cycled list repeats its LPs
+            with np.errstate(invalid="ignore", over="ignore"):
+                cache[key] = gap_exact_bound(ref, y), ref.restated.at(x, y).band
+        exact, band = cache[key]
+        kind = gap_bound_kind(bound, exact, band)
+        layer = _gap_layer(case, k, t)
+        _require(kind is not None, where(k, run) + f" after {t} iterations: lower bound {bound!r}, exactly {exact!r} on the device's y (band {band!r})", layer)
+        counts["bounds_checked"] += 1
+        counts["rounded_to_zero"] += bool(keep[k]) and kind == "rounded to zero"
+        res = ref.highs()
+        if res.status == 3:
+            _require(bound == -np.inf and not stopped, where(k, run) + f": HiGHS calls the LP unbounded; lower bound {bound!r}, stopped {stopped}", layer)
+            counts["unbounded"] += 1
+            continue
+        if res.status == 2:   # a perturbed right-hand side (``batch_of``) can leave no feasible point: every bound is valid then
+            counts["infeasible"] += 1
+            continue
+        _require(res.status == 0, where(k, run) + f": linprog status {res.status} ({res.message})")
+        slack = gap_highs_slack(band, res.fun)
+        if np.isfinite(bound):
+            _require(bound <= res.fun + slack, where(k, run) + f": the lower bound {bound!r} exceeds the optimum {res.fun!r} by more than {slack!r}", layer)
+            counts["bounds_below_optimum"] += 1
+        if stopped and violation == 0.0:
+            _require(primal >= res.fun - slack, where(k, run) + f": primal {primal!r} of a feasible iterate lies below the optimum {res.fun!r} by more "
+                     f"than {slack!r}", layer)
+            counts["primals_above_optimum"] += 1
+
+
+def _run_gap(name, cases, seed, stop_cases, settings, switches, create, rows, driver, split):
+    """Both certificate runs: see ``run_cp_many_gap`` and ``run_cp_batch_gap``.  ``create(case)``: a fresh state; ``rows(state)``:
+    ``(forms, x, y)`` with one row per entry; ``driver(case, rec)``: ``(xs, info)``; ``split``: also the iteration ``t_star`` in
+    its two halves."""
+    def armed_run(case, unarmed, split_at=None, pause_at=None):
+        """A fresh state: ``unarmed`` iterations, ``set_stop_gap``, the rest up to ``total`` (the iteration ``split_at`` in its two
+        halves).  Returns ``(forms, gap_state, stop_state()[:2] or None, (x, y), the same three after pause_at iterations)``."""
+        state = create(case)
+        try:
+            for p in _pieces(unarmed):
+                state.iterate(p)
+            state.set_stop_gap(*case.tol, case.every)
+            done, paused = unarmed, None
+            if split_at is not None:
+                for p in _pieces(split_at - 1 - done):
+                    state.iterate(p)
+                state.primal_step()
+                state.dual_step()
+                done = split_at
+            if pause_at is not None and pause_at < case.total:
+                for p in _pieces(pause_at - done):
+                    state.iterate(p)
+                done = pause_at
+                paused = state.gap_state(), rows(state)[1:]
+            for p in _pieces(case.total - done):
+                state.iterate(p)
+            forms, x, y = rows(state)
+            got = state.gap_state()
+            return forms, got, (state.stop_state()[:2] if hasattr(state, "stop_state") else None), (x, y), paused or (got, (x, y))
+        finally:
+            state.close()
+
+    left_out = sum(int((~case.keep()).sum()) for case in stop_cases)
+    entries = sum(len(case.entries) for case in stop_cases)
+    _require(left_out <= GAP_LEFT_OUT * entries, f"{name} seed {seed}: {left_out} of {entries} entries have an undecidable check, more than 5 %")
+    counts = dict(lists=0, lps=0, runs=0, stopped=0, running=0, left_out=0, longest=0, bounds_checked=0, bounds_below_optimum=0,
+                  primals_above_optimum=0, unbounded=0, infeasible=0, rounded_to_zero=0)
+    for case_no, case in enumerate(stop_cases):
+        want, keep = case.want(), case.keep()
+        for setting, form, kmax in settings:
+            with environment(**dict(zip(switches, (form, kmax)))):
+                default = setting == "default"
+                last_check = case.total - case.total % case.every
+                forms, got, flags, its, paused = armed_run(case, 0, pause_at=last_check if default else None)   # (a) armed from creation
+                where = _gap_where(name, case_no, seed, case, setting, forms)
+                _require(form is None or set(forms) == {form}, f"{name} seed {seed} case {case_no}: forms {set(forms)} under {switches[0]}={form}")
+                _compare_gap(case, want, keep, got, its, where, "armed from creation")
+                if flags is not None:
+                    _require(np.array_equal(flags[0], got[0]) and np.array_equal(flags[1], got[1]), where(0, "armed from creation") +
+                             f": stop_state gives {flags[0]}, {flags[1]}, gap_state {got[0]}, {got[1]}")
+                if default:
+                    _check_gap_bounds(counts, case, keep, *paused, where)
+                    late, keep_late = case.want(after=case.after), case.keep(case.after)   # (b) armed in mid-life
+                    _, got, _, its, _ = armed_run(case, case.after)
+                    _compare_gap(case, late, keep_late, got, its, where, f"armed after {case.after} iterations")
+                    if split:   # (c) the iteration t_star in its two halves
+                        _, got, _, its, _ = armed_run(case, 0, split_at=case.t_star)
+                        _compare_gap(case, want, keep, got, its, where, f"iteration {case.t_star} in two halves")
+                    rec = _StopReports()   # (d) the driver
+                    xs, info = driver(case, rec)
+                    _compare_gap_driver(case, want, keep, xs, info, rec, where)
+            counts["runs"] += 1
+        counts["lists"] += 1
+        counts["lps"] += len(case.distinct())
+        counts["stopped"] += int((want[1] & keep).sum())
+        counts["running"] += int((~want[1] & keep).sum())
+        counts["left_out"] += int((~keep).sum())
+        counts["longest"] = max(counts["longest"], len(case.entries))
+    return counts
+
+
+def run_cp_many_gap(cases, seed):
+    """``CPManyState.set_stop_gap`` / ``gap_state`` and ``chambolle_pock_ppd_many_certified`` on the lists of ``cp_gap_cases`` (three
+    quarters of the LPs keep their finite bounds, so that the certificate's sums are finite at the sizes the lists are drawn for).
+    The tolerances are the violation and the relative gap of one LP at a check iteration (``GapCase``).  Under the four settings of
+    ``run_cp_many``, armed from creation: ``gap_state`` against the restatement (tests/cp_gap_cpu.py) -- iterations and flags with
+    ``np.array_equal`` for every LP all of whose checks are decidable, the violation exactly, primal and bound within ``ENERGY_TOL``
+    -- ``stop_state`` in agreement with it, and every LP's ``x`` and ``y`` against the oracle's at that LP's own count.  With the
+    library's own choice also: armed in mid-life, the drawn iteration in its two halves, the driver with its callbacks, and at the
+    last check of the run every LP's recorded bound against ``cp_gap_cpu.exact_bound`` on the device's own ``y`` (within the band
+    of rounding; a finite bound over an exact ``-inf`` is counted) and against HiGHS: no finite bound above the optimum, no
+    feasible stopped iterate below it, ``-inf`` and running where the LP is unbounded.  Returns counts."""
+    from pysparselp_amd import CPManyState, chambolle_pock_ppd_many_certified
+    from pysparselp_amd.ChambollePockPPD import _many_problem
+
+    def create(case):
+        return CPManyState([_many_problem(k, ref.problem) for k, ref in enumerate(case.entries)], [ref.x0 for ref in case.entries])
+
+    def rows(state):
+        return [state.form(k) for k in range(state.count)], state.x(), state.y()
+
+    def driver(case, rec):
+        xs, _, info = chambolle_pock_ppd_many_certified([ref.problem for ref in case.entries], *case.tol, case.every, x0=[ref.x0 for ref in case.entries],
+                                                        nb_max_iter=case.total, callback_func=rec, nb_iter_plot=case.plot)
+        return xs, info
+
+    stop_cases = cp_gap_cases(cases, seed)
+    counts = _run_gap("cp_many_gap", cases, seed, stop_cases, CP_MANY_SETTINGS, ("SLP_CP_MANY_FORM", "SLP_CP_MANY_KMAX"), create, rows, driver, True)
+    want = gap_statistics(stop_cases)["rounded_to_zero"]
+    _require(counts["rounded_to_zero"] == want, f"cp_many_gap seed {seed}: {counts['rounded_to_zero']} final records have a finite bound over an exact "
+             f"-inf, the restatement has {want}")
+    return counts
+
+
+def run_cp_batch_gap(cases, seed):
+    """``CPBatchState.set_stop_gap`` / ``gap_state`` and ``chambolle_pock_ppd_batch_certified`` on the batches of
+    ``cp_batch_gap_cases``: as ``run_cp_many_gap`` with one setting -- armed from creation, armed in mid-life, the driver, the
+    recorded bounds against ``cp_gap_cpu.exact_bound`` and HiGHS -- every instance's ``x`` and ``y`` against the oracle's at that
+    instance's own count.  In the counts ``lists`` are batches and ``lps`` instances.  Returns counts."""
+    from pysparselp_amd import CPBatchState, chambolle_pock_ppd_batch_certified
+    from pysparselp_amd.ChambollePockPPD import one_sided_system_batch
+
+    def create(case):
+        a = case.args
+        ineq, b_ineq = (None, None) if a["a_ineq"] is None else one_sided_system_batch(a["a_ineq"], a["b_lower"], a["b_upper"])
+        return CPBatchState(a["c"], a["a_eq"], a["beq"], ineq, b_ineq, a["lb"], a["ub"], a["x0"], 1, 1)
+
+    def rows(state):
+        return ["batch"] * state.batch, state.x(), state.y()
+
+    def driver(case, rec):
+        a = case.args
+        xs, _, info = chambolle_pock_ppd_batch_certified(a["c"], a["a_eq"], a["beq"], a["a_ineq"], a["b_lower"], a["b_upper"], a["lb"], a["ub"],
+                                                         *case.tol, case.every, x0=a["x0"], nb_max_iter=case.total, callback_func=rec,
+                                                         nb_iter_plot=case.plot)
+        return xs, info
+
+    stop_cases = cp_batch_gap_cases(cases, seed)
+    counts = _run_gap("cp_batch_gap", cases, seed, stop_cases, (("default", None, None),), ("SLP_CP_MANY_FORM", "SLP_CP_MANY_KMAX"), create, rows, driver,
+                      False)
+    want = gap_statistics(stop_cases)["rounded_to_zero"]
+    _require(counts["rounded_to_zero"] == want, f"cp_batch_gap seed {seed}: {counts['rounded_to_zero']} final records have a finite bound over an exact "
+             f"-inf, the restatement has {want}")
+    return counts
+
+
 # ---- dual gradient ascent on the device -------------------------------------------------------------------------------------------------
 
 class _LP:
@@ -1481,7 +1980,7 @@ def run_dga_many_stop(cases, seed):
 
 FAMILIES = {"cp_batch": run_cp_batch, "cp_many": run_cp_many, "admm_batch": run_admm_batch, "admm_many": run_admm_many, "dga": run_dga,
             "dga_batch": run_dga_batch, "dga_many": run_dga_many, "cp_many_stop": run_cp_many_stop, "admm_many_stop": run_admm_many_stop,
-            "dga_many_stop": run_dga_many_stop}
+            "dga_many_stop": run_dga_many_stop, "cp_many_gap": run_cp_many_gap, "cp_batch_gap": run_cp_batch_gap}
 
 
 def main():
