@@ -10,6 +10,8 @@
 #include <stdint.h>
 
 #include "slp_hip.h"
+/* per-instance stopping of the batched ADMM solver: declared in a header of its own, which this one brings along */
+#include "slp_hip_ext_admm_batch.h"
 
 #ifdef __cplusplus
 extern "C" {

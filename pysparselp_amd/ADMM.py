@@ -299,6 +299,31 @@ class ADMMBatchState:
         _lib.check(self._l.slp_admm_batch_report(self._h, _lib.ptr(out)))
         return out
 
+    def set_stop(self, tol_residual, tol_step, check_every=1):
+        """Arms the per-instance stopping test of the iteration kernels (``slp_admm_batch_set_stop``): at the end of every
+        iteration ``t`` of the state with ``t % check_every == 0`` -- counted from 1 over the state's life; an iteration is the
+        right-hand side, the sweep and the multiplier update -- a running instance stops iff ``max|A x_t - b| <= tol_residual``
+        (the rows of the standard form) and ``max|x_t - x_{t-1}| <= tol_step`` (all ``N`` columns, slacks included); it keeps its
+        iterate while the others go on.  The batch has one iteration counter, so a stopped instance stays stopped for the life of
+        the state: a further call changes tolerances and cadence for the running instances and keeps the flags, and
+        ``tol_residual=None`` turns the test off for them.  Between whole iterations only (not between ``sweep_step`` and
+        ``multiplier_step``)."""
+        if tol_residual is None:
+            tol_residual, tol_step, check_every = -1.0, 0.0, 1
+        else:
+            tol_residual, check_every = _many.check_stop(tol_residual, check_every, "tol_residual")
+            tol_step, _ = _many.check_stop(tol_step, check_every, "tol_step")
+        _lib.check(self._l.slp_admm_batch_set_stop(self._h, tol_residual, tol_step, check_every))
+
+    def stop_state(self):
+        """``(iterations, stopped, residual, step)`` per instance, int64, bool and two float64 arrays: the iterations completed
+        (for a stopped instance its stopping iteration), whether it is stopped -- for the life of the state -- and the last
+        evaluated residual and step (``+inf`` before the first test)."""
+        iterations, stopped = np.zeros(self.batch, dtype=np.int64), np.zeros(self.batch, dtype=np.int32)
+        residual, step = np.zeros(self.batch), np.zeros(self.batch)
+        _lib.check(self._l.slp_admm_batch_stop_state(self._h, _lib.ptr(iterations), _lib.ptr(stopped), _lib.ptr(residual), _lib.ptr(step)))
+        return iterations, stopped.astype(bool), residual, step
+
     def x(self, count=None):
         count = self.N if count is None else int(count)
         out = np.empty((self.batch, count))
@@ -357,13 +382,39 @@ def lp_admm_batch(
 
     Under a communicator every rank solves the whole batch (a replica).
     """
+    X, _ = _admm_batch_run(cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
+                           use_preconditioning, nb_iter_plot, None)
+    return X
+
+
+def _admm_batch_run(cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
+                    use_preconditioning, nb_iter_plot, stop):
+    """``lp_admm_batch`` (``stop`` None) and ``lp_admm_batch_until`` (``stop`` the checked ``(tol_residual, tol_step,
+    check_every)``): ``(X, info)``, ``info`` None without a stopping test."""
     state = ADMMBatchState(cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, use_preconditioning)
     n = state.n
+    solved = np.arange(state.batch)  # every instance takes part
+    info = None if stop is None else _many.new_stop_info(state.batch, solved, residual=True)
+
+    def stopped_now():
+        now = state.stop_state()
+        _many.spread_stop_state(info, solved, now)
+        return now[1]
+
     try:
+        if stop is not None:
+            state.set_stop(*stop)
+            if callback_func is not None:
+                try:
+                    callback_func.info = info
+                except AttributeError:   # a bound method takes no attribute: wrap it in a function to read ``info``
+                    pass
         start = time.perf_counter()
         i = 0
         while i <= nb_iter:  # ADMM.py:143: nb_iter + 1 sweeps
             if i % nb_iter_plot == 0:
+                if stop is not None and stopped_now().all():
+                    break
                 state.sweep_step()
                 elapsed = time.perf_counter() - start
                 if max_time is not None and elapsed > max_time:
@@ -377,9 +428,61 @@ def lp_admm_batch(
                 k = min(nb_iter_plot - i % nb_iter_plot, nb_iter + 1 - i)
                 state.iterate(k)
                 i += k
-        return state.x(n)
+        if stop is not None:
+            stopped_now()
+        return state.x(n), info
     finally:
         state.close()
+
+
+def lp_admm_batch_until(
+    cs,
+    a_eq,
+    beq,
+    a_ineq,
+    b_lower,
+    b_upper,
+    lb,
+    ub,
+    tol_residual,
+    tol_step,
+    check_every=10,
+    x0=None,
+    gamma_eq=2,
+    gamma_ineq=3,
+    nb_iter=10000,
+    callback_func=None,
+    max_time=None,
+    use_preconditioning=True,
+    nb_iter_plot=10,
+):
+    """``lp_admm_batch`` with a stopping test per instance (extension; the reference has no stopping test): the batch runs until
+    every instance has stopped, at most ``nb_iter + 1`` sweeps.  Returns ``(X, info)``.
+
+    The test is made inside the iteration kernels (``ADMMBatchState.set_stop``), at the end of every iteration ``t`` of the batch
+    with ``t % check_every == 0``, iterations counted from 1: an instance stops iff ``max|A x_t - b| <= tol_residual``, over the
+    rows of the standard form and with the very residual the multiplier update forms, and ``max|x_t - x_{t-1}| <= tol_step``,
+    over all ``n + m_ineq`` columns of the standard form; a NaN in either never stops.  A stopped instance keeps ``x_t`` and
+    ``lambda_t``, bit for bit those of ``lp_admm(..., nb_iter=t - 1, order=ORDER_SEQUENTIAL)``, while the others go on.
+    ``tol_residual`` and ``tol_step`` are finite floats ``>= 0``, ``check_every`` an int ``>= 1``: a ``ValueError`` that names
+    the argument, before the library is loaded, otherwise, like every shape error.
+
+    ``info`` is the dict of ``lp_admm_many_until``, of arrays over the batch: ``iterations`` (int64: completed, for a stopped
+    instance its stopping iteration), ``stopped`` (bool), ``residual`` and ``step`` (float64: the last evaluated ones, ``+inf``
+    before the first test).
+
+    The loop and the cadence of reports are those of ``lp_admm_batch``: a report at index ``i`` lies between sweep ``i + 1`` and
+    its multiplier update.  The loop ends at the first report index at which every instance is stopped (no callback for that
+    index), at ``nb_iter``, or at ``max_time``.  In a callback a stopped instance's row of ``X`` is its final iterate and its
+    three numbers are the report on that frozen state, so its ``max_violated_equality`` equals ``info["residual"][k]`` exactly.
+    ``info`` is current at every callback: the same dict, updated in place, is set as the ATTRIBUTE ``callback_func.info`` before
+    the first call (a function or any object that takes attributes; a bound method takes none and has to be wrapped in a
+    function to read it).
+    """
+    tol_residual, check_every = _many.check_stop(tol_residual, check_every, "tol_residual")
+    tol_step, _ = _many.check_stop(tol_step, check_every, "tol_step")
+    return _admm_batch_run(cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
+                           use_preconditioning, nb_iter_plot, (tol_residual, tol_step, check_every))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -23,7 +23,7 @@ import numpy as np
 
 import scipy.sparse
 
-from .ADMM import lp_admm, lp_admm_batch
+from .ADMM import lp_admm, lp_admm_batch, lp_admm_batch_until
 from .ChambollePockPPD import (chambolle_pock_ppd, chambolle_pock_ppd_batch, chambolle_pock_ppd_batch_certified, chambolle_pock_ppd_many,
                                chambolle_pock_ppd_many_certified, chambolle_pock_ppd_many_until)
 from ._many import check_stop
@@ -691,6 +691,12 @@ class SparseLP:
         (and, with ``ground_truth``, the two distance curves) are lists of arrays of length B.  ``max_time`` stops the whole
         batch.  Under a communicator every rank solves the whole batch (a replica).
         """
+        out = self._solve_admm_batch(costs, None, get_timing, nb_iter, max_time, nb_iter_plot, ground_truth, ground_truth_indices)
+        return out[:2] if get_timing else out[0]
+
+    def _solve_admm_batch(self, costs, stop, get_timing, nb_iter, max_time, nb_iter_plot, ground_truth, ground_truth_indices):
+        """``solve_admm_batch`` (``stop`` None) and ``solve_admm_batch_until`` (``stop`` its ``(tol_residual, tol_step,
+        check_every)``): what ``solve_admm_batch`` returns as a tuple, with ``info`` (None without a test) appended."""
         costs, batch = check_costs(costs, self.nb_variables)
         a_ineq = self.a_inequalities if (self.a_inequalities is not None and self.a_inequalities.shape[0] > 0) else None
         a_eq, b_eq = (self.a_equalities, self.b_equalities) if self.a_equalities.shape[0] > 0 else (None, None)
@@ -698,10 +704,40 @@ class SparseLP:
         _reset_curves(self)
 
         record = _batch_recorder(self, batch, ground_truth, ground_truth_indices)
-        x = lp_admm_batch(costs, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds, self.upper_bounds, nb_iter=nb_iter,
-                          callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
+        args = (costs, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds, self.upper_bounds)
+        kw = dict(nb_iter=nb_iter, callback_func=record, max_time=max_time, nb_iter_plot=nb_iter_plot)
+        x, info = (lp_admm_batch(*args, **kw), None) if stop is None else lp_admm_batch_until(*args, *stop, **kw)
         elapsed = time.perf_counter() - start
-        return (x, elapsed) if get_timing else x
+        return (x, elapsed, info) if get_timing else (x, info)
+
+    def solve_admm_batch_until(
+        self,
+        costs,
+        tol_residual,
+        tol_step,
+        check_every=10,
+        get_timing=True,
+        nb_iter=10000,
+        max_time=None,
+        nb_iter_plot=10,
+        ground_truth=None,
+        ground_truth_indices=None,
+    ):
+        """``solve_admm_batch`` with a stopping test per instance (``ADMM.lp_admm_batch_until``): every instance stops on its own at
+        the first iteration ``t`` with ``t % check_every == 0`` at which ``max|A x_t - b| <= tol_residual`` and
+        ``max|x_t - x_{t-1}| <= tol_step`` (standard form, slacks included); the others go on, at most ``nb_iter + 1`` sweeps.
+        Returns ``(X, elapsed, info)`` or ``(X, info)``: what ``solve_admm_batch`` returns, plus ``info``, the dict of arrays of
+        length B of ``lp_admm_batch_until`` (``iterations``, ``stopped``, ``residual``, ``step``).  ``tol_residual`` and ``tol_step``
+        finite floats ``>= 0`` and ``check_every`` an int ``>= 1``, a ``ValueError`` that names the argument otherwise.
+
+        The LP is handed over as ``solve_admm_batch`` hands it over (no variable is removed) and the curves are filled alike, one
+        entry per report; the loop ends at the first report index at which every instance is stopped.  A stopped instance's entries
+        are the report on its final iterate.
+        """
+        check_stop(tol_residual, check_every, "tol_residual")
+        check_stop(tol_step, check_every, "tol_step")
+        return self._solve_admm_batch(costs, (tol_residual, tol_step, check_every), get_timing, nb_iter, max_time, nb_iter_plot,
+                                      ground_truth, ground_truth_indices)
 
     def solve_dga_batch(
         self,

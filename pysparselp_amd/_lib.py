@@ -1,4 +1,4 @@
-"""ctypes binding of libslp_hip.so (include/slp_hip.h and include/slp_hip_ext.h).
+"""ctypes binding of libslp_hip.so (include/slp_hip.h, include/slp_hip_ext.h and include/slp_hip_ext_admm_batch.h).
 
 The library is the only execution path: if it is missing, cannot be loaded, or
 finds no HIP device, every solver entry point raises -- there is no CPU
@@ -259,6 +259,14 @@ _EXT_SIGNATURES = {
 
 EXT_SYMBOLS = tuple(_EXT_SIGNATURES)
 
+# name -> (restype, argtypes); mirrors include/slp_hip_ext_admm_batch.h (which slp_hip_ext.h includes) one to one
+_EXT_ADMM_BATCH_SIGNATURES = {
+    "slp_admm_batch_set_stop": (c_int, [c_vp, c_dbl, c_dbl, c_i64]),
+    "slp_admm_batch_stop_state": (c_int, [c_vp] * 5),
+}
+
+EXT_ADMM_BATCH_SYMBOLS = tuple(_EXT_ADMM_BATCH_SIGNATURES)
+
 # int fn(double *buf, int64_t count, int op, void *user): the host all-reduce of slp_comm_init_host
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, ctypes.POINTER(c_dbl), c_i64, c_int, c_vp)
 
@@ -281,7 +289,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as e:
         raise SlpError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_EXT_ADMM_BATCH_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

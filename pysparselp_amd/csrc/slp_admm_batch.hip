@@ -29,13 +29,40 @@
 // Report (:213-248), per instance: row pass r = A x - b -> sum r^2, sum lambda r, max |r|; column pass -> c.x, sum (x - xp)^2,
 // max -x.  Row i (column j) belongs to slice i mod S; a slice adds its terms in increasing i, one lane per instance adds the S
 // slice sums in increasing slice order (k_cpb_report_*); maxima are exact in any order.
+//
+// Stopping per instance (slp_admm_batch_set_stop, slp_hip_ext_admm_batch.h): the rule of slp_many_admm_set_stop with the batch
+// semantics of slp_cp_batch_set_stop_gap.  The state counts its whole iterations t on the host (bumped where a multiplier half
+// is enqueued) and hands the count to every launch, so whether an iteration is a check iteration is uniform over a launch's
+// lanes and the stopping iteration does not depend on how a run is split into launches or calls.  AdmmbCtl, one per padded
+// instance in device memory: the stopped flag (set for padding instances at the first arming), the stopping iteration, the last
+// evaluated residual and step, and the reduced step of a sweep whose multiplier half has not run yet.  The test is the template
+// parameter STOP of the iteration kernels: STOP = false is the kernel without the test, the only one a never-armed state
+// launches.  With STOP a lane reads its instance's flag first and does no other load for a stopped instance, and only a check
+// iteration accumulates anything, in loops of its own: fabs(new - old) over the lane's rows of all levels, fabs((A x)_i - b_i)
+// -- the value the multiplier update forms -- over its rows of the multiplier pass, both by nan_max (slp_cp_gap.h), exact in
+// any order.
+//   tile    the lanes of an instance lie BT apart in a wave: shuffles down to BT, one LDS slot per (wave, instance), and behind
+//           the multiplier pass's barrier lane k of wave 0 folds the 16 slots of instance k, writes the record and decides.
+//           Wave 0 then posts who goes on (one flag per instance, one for the tile) and every lane reads both behind the ONE
+//           barrier the test adds to a check iteration; a tile without a running instance returns (uniform: no barrier is
+//           left behind), as it does at the start of a launch.
+//   levels  in a check iteration every workgroup of a level (of the multiplier pass) reduces its lanes the same way and lane k
+//           folds the result into (writes) slot part[(q S + blockIdx.x) Bp + instance], q = 0 step, 1 residual -- a slot belongs
+//           to one workgroup index, the launches of a stream follow each other, so no atomic is needed; the step slots are
+//           zeroed on the stream before the sweep.  k_admmb_decide, one workgroup per instance behind the multiplier kernel,
+//           folds the slots, writes the record and decides.
+// `running` counts the real instances that go on (an integer atomic decrement where one stops): an armed state reads it once
+// at the start of iterate / multiplier_step and enqueues nothing when it is 0.  Nothing else is read back.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "slp_common.h"
+#include "slp_cp_gap.h"
 #include "slp_kernels.h"
 #include "slp_admm_iter.h"
 #include "slp_admm_shared.h"
+#include "../../include/slp_hip_ext_admm_batch.h"
 
 namespace slp {
 
@@ -55,6 +82,19 @@ struct AdmmbArgs {
     double gamma_eq, gamma_ineq;
 };
 
+// the record of one (padded) instance and what a launch of a STOP kernel is told about the test (header comment)
+struct AdmmbCtl {
+    i64 stop_iter;               // t when it stopped
+    i32 stopped, pad;            // padding instances: stopped from the first arming on
+    double residual, step, dx;   // the last evaluated ones; the reduced step of a sweep that waits for its multiplier half
+};
+struct AdmmbStop {
+    AdmmbCtl *ctl;
+    i32 *running;                // real instances that still run
+    i64 t0, check_every;         // whole iterations completed when the launch starts; 0: no iteration is a check iteration
+    double tol_residual, tol_step;
+};
+
 // the workgroup-scope relaxed load of slp_admm_iter.h: a value another lane of the workgroup may have stored before the last barrier
 __device__ __forceinline__ double admmb_ld(const double *p) { return AdmmLoadWorkgroup()(p); }
 
@@ -67,13 +107,16 @@ __device__ __forceinline__ void admmb_rhs_one(const AdmmbArgs &a, i64 tile, int 
                               AdmmLoadWorkgroup());  // :148
 }
 
+// returns |new - old| of the row, for a check iteration of the stopping test
 template <int BT>
-__device__ __forceinline__ void admmb_sweep_one(const AdmmbArgs &a, i64 tile, int k, i64 t) {
+__device__ __forceinline__ double admmb_sweep_one(const AdmmbArgs &a, i64 tile, int k, i64 t) {
     const i64 i = a.grows[t];
     const i64 o = (tile * a.N + i) * BT + k;
     const double bi = admmb_ld(a.y + o), xi = admmb_ld(a.x + o), inv = a.ginvd[t];
     const double l = a.lb[a.lb_b ? o : i], u = a.ub[a.ub_b ? o : i];
-    a.x[o] = admm_sweep_one<BT>(a.gptr[t], a.gptr[t + 1], a.gidx, a.gval, a.x + tile * a.N * BT + k, bi, xi, inv, l, u, AdmmLoadWorkgroup());
+    const double v = admm_sweep_one<BT>(a.gptr[t], a.gptr[t + 1], a.gidx, a.gval, a.x + tile * a.N * BT + k, bi, xi, inv, l, u, AdmmLoadWorkgroup());
+    a.x[o] = v;
+    return fabs(v - xi);
 }
 
 template <int BT>
@@ -83,60 +126,220 @@ __device__ __forceinline__ void admmb_mult_one(const AdmmbArgs &a, i64 tile, int
                                  AdmmLoadWorkgroup());  // :261-263
 }
 
-// ---- tile form: `iters` iterations of one tile in one workgroup.  stages: bit 0 right-hand side + sweep, bit 1 multiplier.
+// admmb_mult_one of a check iteration: the same lambda_i; returns |(A x)_i - b_i| as the update forms it
 template <int BT>
-__global__ __launch_bounds__(kAdmmbBlock) void k_admmb_tile(AdmmbArgs a, int iters, int first, int stages) {
+__device__ __forceinline__ double admmb_mult_res_one(const AdmmbArgs &a, i64 tile, int k, i64 i) {
+    const i64 o = (tile * a.m + i) * BT + k;
+    double res;
+    a.lam[o] = admm_mult_res_one<BT>(a.aptr[i], a.aptr[i + 1], a.aidx, a.aval, a.x + tile * a.N * BT + k, a.lam + o, a.b + i, a.gamma_eq,
+                                     AdmmLoadWorkgroup(), &res);
+    return fabs(res);
+}
+
+// ---- the reductions of the stopping test.  The lanes of instance k of a tile are those with threadIdx.x % BT == k: in a wave
+// they lie BT apart, so shuffles down to BT leave lane k < BT with the wave's nan_max for instance k; slots[wave * BT + k].
+// Every lane of the workgroup calls it (a lane without a row, or of a stopped instance, with 0.0); read behind a later barrier.
+template <int BT>
+__device__ __forceinline__ void admmb_post(double *slots, double v) {
+#pragma unroll
+    for (int off = kWave / 2; off >= BT; off >>= 1) v = nan_max(v, __shfl_down(v, off, kWave));
+    const int lane = threadIdx.x & (kWave - 1);
+    if (lane < BT) slots[(threadIdx.x / kWave) * BT + lane] = v;
+}
+
+// the slots of instance k folded over the NW waves of the workgroup
+template <int BT, int NW>
+__device__ __forceinline__ double admmb_fold(const double *slots, int k) {
+    double v = slots[k];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) v = nan_max(v, slots[w * BT + k]);
+    return v;
+}
+
+// lane 0 of a workgroup's deciding lanes for one instance, at the end of check iteration t: the record, and one instance fewer
+// runs when it stops.  False for a NaN on either side.
+__device__ __forceinline__ bool admmb_decide(const AdmmbStop &sp, AdmmbCtl *ctl, i64 t, double residual, double step) {
+    ctl->residual = residual;
+    ctl->step = step;
+    const bool stop = residual <= sp.tol_residual && step <= sp.tol_step;
+    if (stop) {
+        ctl->stopped = 1;
+        ctl->stop_iter = t;
+        atomicSub(sp.running, 1);
+    }
+    return stop;
+}
+
+// wave 0 of the tile form (lane k < BT speaks for instance k) posts go[k] = `goes` and go[BT] = any of them; every lane reads
+// them behind the barrier: false when no instance of the tile runs, the same for every lane
+template <int BT>
+__device__ __forceinline__ bool admmb_post_go(int *go, bool goes) {
+    if (threadIdx.x < kWave) {
+        const bool mine = threadIdx.x < BT && goes;
+        if (threadIdx.x < BT) go[threadIdx.x] = mine;
+        const bool any = __any(mine);
+        if (threadIdx.x == 0) go[BT] = any;
+    }
+    __syncthreads();
+    return go[BT] != 0;
+}
+
+// ---- tile form: `iters` iterations of one tile in one workgroup.  stages: bit 0 right-hand side + sweep, bit 1 multiplier.
+// STOP: the stopping test of the header comment; `sp` is not looked at without it.
+template <int BT, bool STOP>
+__global__ __launch_bounds__(kAdmmbBlock) void k_admmb_tile(AdmmbArgs a, int iters, int first, int stages, AdmmbStop sp) {
+    constexpr int kWaves = kAdmmbBlock / kWave;
+    __shared__ double red[STOP ? 2 * kWaves * BT : 1];  // step, residual: a slot per (wave, instance).  Unused without STOP: dropped
+    __shared__ int go[STOP ? BT + 1 : 1];
     const int k = threadIdx.x & (BT - 1);
     const i64 tile = blockIdx.x;
     const i64 g = threadIdx.x / BT;
     constexpr i64 ng = kAdmmbBlock / BT;
-    const bool active = tile * BT + k < a.B;
+    bool active = STOP ? !sp.ctl[tile * BT + k].stopped : tile * BT + k < a.B;
+    if (STOP && !admmb_post_go<BT>(go, active)) return;
     for (int it = 0; it < iters; ++it) {
+        const bool check = STOP && sp.check_every > 0 && (sp.t0 + it + 1) % sp.check_every == 0;  // uniform over the launch
         if (stages & 1) {
             if (active)
                 for (i64 j = g; j < a.N; j += ng) admmb_rhs_one<BT>(a, tile, k, j, first && it == 0);
             __syncthreads();
+            double dx = 0.0;  // a lane without a row in any level contributes 0.0
             for (i64 l = 0; l < a.nlevels; ++l) {
                 const i64 beg = a.lptr[l], end = a.lptr[l + 1];
-                if (active)
-                    for (i64 t = beg + g; t < end; t += ng) admmb_sweep_one<BT>(a, tile, k, t);
+                if (check) {  // a loop of its own: the other one stays the loop of the kernel without the test
+                    if (active)
+                        for (i64 t = beg + g; t < end; t += ng) dx = nan_max(dx, admmb_sweep_one<BT>(a, tile, k, t));
+                } else {
+                    if (active)
+                        for (i64 t = beg + g; t < end; t += ng) admmb_sweep_one<BT>(a, tile, k, t);
+                }
                 __syncthreads();  // same compute unit: the stores of this level are visible to the next one
             }
+            if (check) admmb_post<BT>(red, dx);  // read behind the multiplier pass's barrier, or behind the one below
+        }
+        if (STOP && !(stages & 2)) {  // sweep_step: the reduced step waits in the record for multiplier_step
+            if (check) {
+                __syncthreads();
+                if (threadIdx.x < BT && active) sp.ctl[tile * BT + k].dx = admmb_fold<BT, kWaves>(red, k);
+            }
+            continue;
         }
         if (stages & 2) {
-            if (active)
-                for (i64 i = g; i < a.m; i += ng) admmb_mult_one<BT>(a, tile, k, i);
+            if (check) {
+                double dr = 0.0;  // 0.0 without rows
+                if (active)
+                    for (i64 i = g; i < a.m; i += ng) dr = nan_max(dr, admmb_mult_res_one<BT>(a, tile, k, i));
+                admmb_post<BT>(red + kWaves * BT, dr);
+            } else {
+                if (active)
+                    for (i64 i = g; i < a.m; i += ng) admmb_mult_one<BT>(a, tile, k, i);
+            }
             __syncthreads();
+        }
+        if (STOP && check) {  // here iteration t0 + it + 1 is complete
+            bool goes = false;
+            if (threadIdx.x < BT && active) {  // lane k of wave 0 decides for instance k
+                AdmmbCtl *ctl = sp.ctl + tile * BT + k;
+                const double step = (stages & 1) ? admmb_fold<BT, kWaves>(red, k) : ctl->dx;
+                goes = !admmb_decide(sp, ctl, sp.t0 + it + 1, admmb_fold<BT, kWaves>(red + kWaves * BT, k), step);
+            }
+            if (!admmb_post_go<BT>(go, goes)) return;  // the one barrier the test adds to a whole iteration
+            active = go[k] != 0;
         }
     }
 }
 
-// ---- levels form: lanes over (row, instance) of all tiles; blockIdx.y is the tile
-template <int BT>
-__global__ __launch_bounds__(kBlock) void k_admmb_rhs(AdmmbArgs a, int first) {
+// ---- levels form: lanes over (row, instance) of all tiles; blockIdx.y is the tile.  STOP: a lane of a stopped instance returns
+// before its first load; `ctl` is not looked at without it.
+template <int BT, bool STOP>
+__global__ __launch_bounds__(kBlock) void k_admmb_rhs(AdmmbArgs a, int first, const AdmmbCtl *__restrict__ ctl) {
     const int k = threadIdx.x & (BT - 1);
     const i64 tile = blockIdx.y;
-    if (tile * BT + k >= a.B) return;
+    if (STOP ? ctl[tile * BT + k].stopped != 0 : tile * BT + k >= a.B) return;
     const i64 ng = (i64)gridDim.x * kBlock / BT;
     for (i64 j = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; j < a.N; j += ng) admmb_rhs_one<BT>(a, tile, k, j, first != 0);
 }
 
+// a check iteration's workgroup: the lanes' `v` reduced per instance of the tile; lane k < BT returns true with the result in *out.
+// Every lane of the workgroup calls it
 template <int BT>
-__global__ __launch_bounds__(kBlock) void k_admmb_level(AdmmbArgs a, i64 beg, i64 end) {
-    const int k = threadIdx.x & (BT - 1);
-    const i64 tile = blockIdx.y;
-    if (tile * BT + k >= a.B) return;
-    const i64 ng = (i64)gridDim.x * kBlock / BT;
-    for (i64 t = beg + ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; t < end; t += ng) admmb_sweep_one<BT>(a, tile, k, t);
+__device__ __forceinline__ bool admmb_block_nanmax(double v, double *out) {
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ double slots[kWaves * BT];
+    admmb_post<BT>(slots, v);
+    __syncthreads();
+    if (threadIdx.x >= BT) return false;
+    *out = admmb_fold<BT, kWaves>(slots, (int)threadIdx.x);
+    return true;
 }
 
-template <int BT>
-__global__ __launch_bounds__(kBlock) void k_admmb_mult(AdmmbArgs a) {
+// part: NULL outside a check iteration; else the step slots [gridDim.x of the widest level x Bp], zeroed before the sweep
+template <int BT, bool STOP>
+__global__ __launch_bounds__(kBlock) void k_admmb_level(AdmmbArgs a, i64 beg, i64 end, const AdmmbCtl *__restrict__ ctl, i64 Bp,
+                                                        double *part) {
     const int k = threadIdx.x & (BT - 1);
     const i64 tile = blockIdx.y;
-    if (tile * BT + k >= a.B) return;
     const i64 ng = (i64)gridDim.x * kBlock / BT;
-    for (i64 i = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; i < a.m; i += ng) admmb_mult_one<BT>(a, tile, k, i);
+    if (!STOP || !part) {
+        if (STOP ? ctl[tile * BT + k].stopped != 0 : tile * BT + k >= a.B) return;
+        for (i64 t = beg + ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; t < end; t += ng) admmb_sweep_one<BT>(a, tile, k, t);
+        return;
+    }
+    const bool live = !ctl[tile * BT + k].stopped;  // every lane stays for the barrier
+    double dx = 0.0;
+    if (live)
+        for (i64 t = beg + ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; t < end; t += ng) dx = nan_max(dx, admmb_sweep_one<BT>(a, tile, k, t));
+    double v;
+    if (admmb_block_nanmax<BT>(dx, &v) && live) {
+        double *slot = part + (i64)blockIdx.x * Bp + tile * BT + k;  // this workgroup index's own, level after level
+        *slot = nan_max(*slot, v);
+    }
+}
+
+// part: NULL outside a check iteration; else the residual slots [gridDim.x x Bp]
+template <int BT, bool STOP>
+__global__ __launch_bounds__(kBlock) void k_admmb_mult(AdmmbArgs a, const AdmmbCtl *__restrict__ ctl, i64 Bp, double *__restrict__ part) {
+    const int k = threadIdx.x & (BT - 1);
+    const i64 tile = blockIdx.y;
+    const i64 ng = (i64)gridDim.x * kBlock / BT;
+    if (!STOP || !part) {
+        if (STOP ? ctl[tile * BT + k].stopped != 0 : tile * BT + k >= a.B) return;
+        for (i64 i = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; i < a.m; i += ng) admmb_mult_one<BT>(a, tile, k, i);
+        return;
+    }
+    const bool live = !ctl[tile * BT + k].stopped;
+    double dr = 0.0;
+    if (live)
+        for (i64 i = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; i < a.m; i += ng) dr = nan_max(dr, admmb_mult_res_one<BT>(a, tile, k, i));
+    double v;
+    if (admmb_block_nanmax<BT>(dr, &v) && live) part[(i64)blockIdx.x * Bp + tile * BT + k] = v;
+}
+
+// one workgroup per real instance, behind the multiplier kernel of a check iteration t (sp.t0) -- or behind the sweep of a
+// sweep_step, where the folded step goes into the record and waits: the nstep step slots and the nres residual slots (at `res`)
+// folded by nan_max, the record, the decision.  stages as in admmb_run.
+__global__ __launch_bounds__(kBlock) void k_admmb_decide(i64 Bp, i64 nstep, const double *__restrict__ step, i64 nres,
+                                                         const double *__restrict__ res, int stages, AdmmbStop sp) {
+    constexpr int kWaves = kBlock / kWave;
+    __shared__ double slots[2 * kWaves];
+    const i64 inst = blockIdx.x;
+    AdmmbCtl *ctl = sp.ctl + inst;
+    if (ctl->stopped) return;  // the same for every lane
+    double dx = 0.0, dr = 0.0;
+    if (stages & 1)
+        for (i64 g = threadIdx.x; g < nstep; g += kBlock) dx = nan_max(dx, step[g * Bp + inst]);
+    if (stages & 2)
+        for (i64 g = threadIdx.x; g < nres; g += kBlock) dr = nan_max(dr, res[g * Bp + inst]);
+    admmb_post<1>(slots, dx);
+    admmb_post<1>(slots + kWaves, dr);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    dx = admmb_fold<1, kWaves>(slots, 0);
+    if (!(stages & 2)) {
+        ctl->dx = dx;
+        return;
+    }
+    admmb_decide(sp, ctl, sp.t0, admmb_fold<1, kWaves>(slots + kWaves, 0), (stages & 1) ? dx : ctl->dx);
 }
 
 // ---- report.  part[(q * S + slice) * Bp + instance], S = gridDim.x * 256 / BT slices
@@ -260,6 +463,17 @@ struct slp_admm_batch {
     DevBuf<i64> lptr;
     DevBuf<double> c, q, lb, ub, x, xp0, y, lam, rowparts, colparts, out;
     bool lb_b = false, ub_b = false, x0_b = false;
+    i64 iters = 0;             // whole iterations over the state's life: bumped where a multiplier half is enqueued
+    bool mid = false;          // between sweep_step and multiplier_step
+    // the stopping test (slp_admm_batch_set_stop); its buffers exist from the first arming on, and from then on the state
+    // launches the STOP kernels.  Off while tol_residual < 0.
+    bool armed = false;
+    double tol_residual = -1.0, tol_step = 0.0;
+    i64 check_every = 1;
+    DevBuf<AdmmbCtl> ctl;      // per padded instance
+    DevBuf<i32> running;       // the count of real instances that still run
+    i64 stop_slices = 0;       // levels form: workgroups along x of its widest launch
+    DevBuf<double> stopparts;  // levels form: 2 * stop_slices * Bp slots, the step's before the residual's
     ~slp_admm_batch() { if (base) slp_admm_destroy(base); }
 };
 
@@ -320,38 +534,90 @@ static AdmmbArgs admmb_args(const slp_admm_batch *s) {
 
 static dim3 admmb_grid(const slp_admm_batch *s, i64 rows) { return dim3((unsigned)grid_for(rows * s->Bt, kBlock), (unsigned)s->ntiles); }
 
-// stages: bit 0 right-hand side + sweep, bit 1 multiplier; `iters` whole iterations when both are set
-static void admmb_run(slp_admm_batch *s, i64 iters, int stages) {
-    if (s->N == 0 || iters <= 0) return;
-    hipStream_t st = ctx().stream;
-    const AdmmbArgs a = admmb_args(s);
-    if (s->form == 0) {
-        while (iters > 0) {
-            const i64 k = std::min(iters, s->kmax);
-            const int first = ((stages & 1) && !s->xp_is_x) ? 1 : 0;
-            SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_tile<BT>), dim3((unsigned)s->ntiles), dim3(kAdmmbBlock), 0, st, a, (int)k, first,
-                                                     stages));
-            SLP_HIP(hipGetLastError());
-            if (stages & 2) s->xp_is_x = true;  // :259
-            iters -= k;
+// what a launch of a STOP kernel is told: the count so far, and the cadence only where the test is to be evaluated
+static AdmmbStop admmb_stop(const slp_admm_batch *s, bool test) {
+    AdmmbStop sp;
+    sp.ctl = s->ctl.p;
+    sp.running = s->running.p;
+    sp.t0 = s->iters;
+    sp.check_every = (test && s->tol_residual >= 0.0) ? s->check_every : 0;
+    sp.tol_residual = s->tol_residual;
+    sp.tol_step = s->tol_step;
+    return sp;
+}
+
+template <bool STOP>
+static void admmb_run_tile(slp_admm_batch *s, const AdmmbArgs &a, i64 iters, int stages, bool test) {
+    while (iters > 0) {
+        const i64 k = std::min(iters, s->kmax);
+        const int first = ((stages & 1) && !s->xp_is_x) ? 1 : 0;
+        SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_tile<BT, STOP>), dim3((unsigned)s->ntiles), dim3(kAdmmbBlock), 0, ctx().stream, a,
+                                                 (int)k, first, stages, admmb_stop(s, test)));
+        SLP_HIP(hipGetLastError());
+        if (stages & 2) {
+            s->xp_is_x = true;  // :259
+            s->iters += k;
         }
-        return;
+        iters -= k;
     }
+}
+
+template <bool STOP>
+static void admmb_run_levels(slp_admm_batch *s, const AdmmbArgs &a, i64 iters, int stages, bool test) {
+    hipStream_t st = ctx().stream;
+    const AdmmbCtl *ctl = s->ctl.p;
+    double *steps = s->stopparts.p, *residuals = s->stopparts.p + s->stop_slices * s->Bp;
     for (i64 it = 0; it < iters; ++it) {
+        AdmmbStop sp = admmb_stop(s, test);
+        sp.t0 = s->iters + 1;  // the iteration these launches belong to
+        const bool check = STOP && sp.check_every > 0 && sp.t0 % sp.check_every == 0;
+        i64 nstep = 0, nres = 0;
         if (stages & 1) {
-            SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_rhs<BT>), admmb_grid(s, s->N), dim3(kBlock), 0, st, a, s->xp_is_x ? 0 : 1));
+            if (check) SLP_HIP(hipMemsetAsync(steps, 0, (size_t)(s->stop_slices * s->Bp) * sizeof(double), st));
+            SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_rhs<BT, STOP>), admmb_grid(s, s->N), dim3(kBlock), 0, st, a, s->xp_is_x ? 0 : 1,
+                                                     ctl));
             for (i64 l = 0; l < s->sh.nlevels; ++l) {
                 const i64 beg = s->sh.lptr[(size_t)l], end = s->sh.lptr[(size_t)l + 1];
                 if (end <= beg) continue;
-                SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_level<BT>), admmb_grid(s, end - beg), dim3(kBlock), 0, st, a, beg, end));
+                const dim3 grid = admmb_grid(s, end - beg);
+                nstep = std::max<i64>(nstep, grid.x);
+                SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_level<BT, STOP>), grid, dim3(kBlock), 0, st, a, beg, end, ctl, s->Bp,
+                                                         check ? steps : nullptr));
             }
         }
         if (stages & 2) {
             s->xp_is_x = true;
-            if (s->m > 0) SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_mult<BT>), admmb_grid(s, s->m), dim3(kBlock), 0, st, a));
+            ++s->iters;
+            if (s->m > 0) {
+                const dim3 grid = admmb_grid(s, s->m);
+                nres = grid.x;
+                SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_mult<BT, STOP>), grid, dim3(kBlock), 0, st, a, ctl, s->Bp,
+                                                         check ? residuals : nullptr));
+            }
+        }
+        if (check) {
+            SLP_REQUIRE(nstep <= s->stop_slices && nres <= s->stop_slices, "slp_admm_batch: the stopping test's slots are too few");
+            hipLaunchKernelGGL(k_admmb_decide, dim3((unsigned)s->B), dim3(kBlock), 0, st, s->Bp, nstep, steps, nres, residuals, stages, sp);
         }
         SLP_HIP(hipGetLastError());
     }
+}
+
+// stages: bit 0 right-hand side + sweep, bit 1 multiplier; `iters` whole iterations when both are set.  test: evaluate the
+// stopping test where it is armed (not in slp_admm_batch_bench).  An armed state asks once per call that ends iterations
+// whether anything is left to run.
+static void admmb_run(slp_admm_batch *s, i64 iters, int stages, bool test = true) {
+    if (stages & 2) s->mid = false;
+    else s->mid = true;
+    if (s->N == 0 || iters <= 0) return;
+    if (s->armed && test && (stages & 2)) {
+        i32 running = 0;
+        s->running.download(&running, 1);
+        if (running == 0) return;
+    }
+    const AdmmbArgs a = admmb_args(s);
+    if (s->form == 0) s->armed ? admmb_run_tile<true>(s, a, iters, stages, test) : admmb_run_tile<false>(s, a, iters, stages, test);
+    else s->armed ? admmb_run_levels<true>(s, a, iters, stages, test) : admmb_run_levels<false>(s, a, iters, stages, test);
 }
 
 static dim3 admmb_report_grid(const slp_admm_batch *s, i64 rows) {
@@ -564,12 +830,60 @@ int slp_admm_batch_bench(slp_admm_batch *s, int64_t k, double *ms) {
         SLP_REQUIRE(s && k > 0 && ms, "slp_admm_batch_bench: bad arguments");
         Context &c = ctx();
         SLP_HIP(hipEventRecord(c.ev0, c.stream));
-        admmb_run(s, k, 3);
+        admmb_run(s, k, 3, false);
         SLP_HIP(hipEventRecord(c.ev1, c.stream));
         SLP_HIP(hipEventSynchronize(c.ev1));
         float f = 0.f;
         SLP_HIP(hipEventElapsedTime(&f, c.ev0, c.ev1));
         *ms = (double)f / (double)k;
+    })
+}
+
+int slp_admm_batch_set_stop(slp_admm_batch *s, double tol_residual, double tol_step, int64_t check_every) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_admm_batch_set_stop: NULL handle");
+        SLP_REQUIRE(tol_residual < 0.0 || (std::isfinite(tol_residual) && std::isfinite(tol_step) && tol_step >= 0.0 && check_every >= 1),
+                    "slp_admm_batch_set_stop: tol_residual and tol_step must be finite and >= 0 with check_every >= 1 (tol_residual < 0 "
+                    "turns the test off)");
+        SLP_REQUIRE(!s->mid, "slp_admm_batch_set_stop: called between sweep_step and multiplier_step (whole iterations only)");
+        if (tol_residual >= 0.0 && !s->armed) {  // the first arming: records (padding instances stopped), the count, the slots
+            const size_t bp = (size_t)s->Bp;
+            std::vector<AdmmbCtl> ctl(bp);
+            for (size_t k = 0; k < bp; ++k) ctl[k] = AdmmbCtl{0, k < (size_t)s->B ? 0 : 1, 0, __builtin_inf(), __builtin_inf(), 0.0};
+            const i32 running = (i32)std::min<i64>(s->B, 0x7fffffff);
+            if (s->form == 1) {
+                i64 slices = admmb_grid(s, s->m).x;
+                for (i64 l = 0; l < s->sh.nlevels; ++l)
+                    slices = std::max<i64>(slices, admmb_grid(s, s->sh.lptr[(size_t)l + 1] - s->sh.lptr[(size_t)l]).x);
+                s->stop_slices = slices;
+                s->stopparts.alloc((size_t)2 * (size_t)slices * bp);
+            }
+            s->ctl.upload(ctl.data(), bp);
+            s->running.upload(&running, 1);
+            s->armed = true;
+        }
+        s->tol_residual = tol_residual < 0.0 ? -1.0 : tol_residual;
+        if (tol_residual >= 0.0) {
+            s->tol_step = tol_step;
+            s->check_every = check_every;
+        }
+        SLP_HIP(hipStreamSynchronize(ctx().stream));
+    })
+}
+
+int slp_admm_batch_stop_state(slp_admm_batch *s, int64_t *iterations, int32_t *stopped, double *residual, double *step) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_admm_batch_stop_state: NULL handle");
+        const size_t count = (size_t)s->B;
+        std::vector<AdmmbCtl> ctl(count, AdmmbCtl{0, 0, 0, __builtin_inf(), __builtin_inf(), 0.0});
+        if (s->armed) s->ctl.download(ctl.data(), count);
+        else SLP_HIP(hipStreamSynchronize(ctx().stream));
+        for (size_t k = 0; k < count; ++k) {
+            if (iterations) iterations[k] = ctl[k].stopped ? ctl[k].stop_iter : s->iters;
+            if (stopped) stopped[k] = ctl[k].stopped;
+            if (residual) residual[k] = ctl[k].residual;
+            if (step) step[k] = ctl[k].step;
+        }
     })
 }
 
