@@ -8,6 +8,7 @@ import functools
 import inspect
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -20,6 +21,9 @@ from pysparselp_amd.ADMM import ADMMBatchState
 from pysparselp_amd.SparseLP import SparseLP
 from test_cp_many_stop_host import BAD_EVERY, BAD_TOL, no_library  # noqa: F401  (the fixture and the two lists of the CP form)
 from test_gpu_admm_batch import _instances, _of_instance
+
+sys.path.insert(0, os.path.join(REPO, "tools"))
+import fuzz_batched  # noqa: E402
 
 BATCH = 5
 EVERY = 10
@@ -49,6 +53,51 @@ def batch_stops(name, batch=BATCH):
     """Per instance its stopping iteration under the restatement, ``None``: still running at the end of the run."""
     _, _, tol, total = BATCHES[name]
     return admm_batch_stop_cpu.stopping_iterations(batch_curves(name, batch), *tol, EVERY, total)
+
+
+# the batch with an instance whose arithmetic overflows: the entry points refuse a cost or a start that is not finite, so the NaN
+# has to arise in the iteration.  A cost of +-1e308 on a variable with an infinite bound that inequality rows meet, on the side of
+# that bound, drives the variable to about 1e307 in the first sweep, the row sums to infinity in the next ones and inf - inf to NaN.
+NAN_SEED, NAN_BATCH, NAN_INSTANCE, NAN_WITHIN = 5, 5, 2, 10   # instance 2: in the middle of the first tile of four
+NAN_TOL, NAN_EVERY, NAN_TOTAL = (0.1, 0.1), (1, 3), 40       # generous: a record of 0.0 in place of a dropped NaN would stop at once
+
+
+def _nan_candidate(rng):
+    """A batch of ``NAN_BATCH`` over a ``random_lp(rng, "admm", 12)`` whose instance ``NAN_INSTANCE`` has the LP's own costs with
+    +-1e308 on the first variable that has an infinite bound and an entry in an inequality row; None without such a variable."""
+    lp = fuzz_batched.random_lp(rng, "admm", 12)
+    met = np.diff(lp["a_ineq"].tocsc().indptr) > 0
+    free = [j for j in range(12) if met[j] and (np.isinf(lp["ub"][j]) or np.isinf(lp["lb"][j]))]
+    if not free:
+        return None
+    args = fuzz_batched.batch_of(rng, lp, NAN_BATCH, "admm")
+    args["cs"] = args.pop("c")
+    args["cs"][NAN_INSTANCE] = lp["c"]
+    args["cs"][NAN_INSTANCE, free[0]] = -1e308 if np.isinf(lp["ub"][free[0]]) else 1e308
+    return args
+
+
+def _nan_condition(curves):
+    """The NaN instance's residual and step are NaN from some iteration within ``NAN_WITHIN`` on, its batch-mates' stay finite."""
+    mates = all(np.all(np.isfinite(c)) for k, pair in enumerate(curves) if k != NAN_INSTANCE for c in pair)
+    bad = [np.isnan(c) for c in curves[NAN_INSTANCE]]
+    return mates and all(b[NAN_WITHIN - 1:].all() for b in bad)
+
+
+@functools.lru_cache(maxsize=None)
+def nan_batch():
+    """``(args, curves over NAN_TOTAL iterations)`` of the first of twelve draws of ``RandomState(NAN_SEED)`` that meets
+    ``_nan_condition`` (shared, never modified)."""
+    rng = np.random.RandomState(NAN_SEED)
+    for _ in range(12):
+        args = _nan_candidate(rng)
+        if args is None:
+            continue
+        with np.errstate(over="ignore", invalid="ignore"):
+            curves = admm_batch_stop_cpu.batch_curves(args, NAN_TOTAL, _of_instance)
+        if _nan_condition(curves):
+            return args, curves
+    raise AssertionError("no draw overflows")
 
 
 class _NoState(ADMMBatchState):
@@ -224,3 +273,25 @@ def test_a_reordered_batch_has_a_tile_that_stops_long_before_the_other():
     assert all(t is not None for t in stops), stops
     order = np.argsort(stops, kind="stable")
     assert stops[order[3]] + 2 * EVERY <= stops[order[-1]], stops
+
+
+def test_the_nan_batch_overflows_in_one_instance_only():
+    """What makes the GPU case a test: the seeded search finds a batch whose instance ``NAN_INSTANCE`` -- in the middle of a tile of
+    four -- has NaN curves within ``NAN_WITHIN`` iterations, after at least one finite check, while its four batch-mates stay finite
+    and all stop under ``NAN_TOL`` at either cadence, not all at one iteration.  The restatement never stops the NaN instance and
+    keeps the NaN in its record."""
+    args, curves = nan_batch()
+    assert args["cs"].shape == (NAN_BATCH, 12) and np.all(np.isfinite(args["cs"])) and np.abs(args["cs"][NAN_INSTANCE]).max() == 1e308
+    assert _nan_condition(curves) and NAN_INSTANCE % 4 in (1, 2) and NAN_INSTANCE < 4 < NAN_BATCH
+    residual, step = curves[NAN_INSTANCE]
+    first = int(np.argmax(np.isnan(residual) | np.isnan(step))) + 1
+    print("the NaN instance:", residual[:first], step[:first], "NaN from iteration", first)
+    assert 2 <= first <= NAN_WITHIN and np.all(np.isnan(residual[first - 1:])) and np.all(np.isnan(step[first - 1:]))
+    for every in NAN_EVERY:
+        stops = admm_batch_stop_cpu.stopping_iterations(curves, *NAN_TOL, every, NAN_TOTAL)
+        print("every", every, "stops", stops)
+        assert stops[NAN_INSTANCE] is None and all(t is not None for k, t in enumerate(stops) if k != NAN_INSTANCE), stops
+        assert len({t for t in stops if t is not None}) >= 2 and min(t for t in stops if t is not None) > first
+        want = admm_batch_stop_cpu.stop_state(curves, NAN_TOL + (every,), NAN_TOTAL)
+        assert want[0][NAN_INSTANCE] == NAN_TOTAL and not want[1][NAN_INSTANCE]
+        assert np.isnan(want[2][NAN_INSTANCE]) and np.isnan(want[3][NAN_INSTANCE])

@@ -8,7 +8,10 @@ cold, with equality rows only -- the chosen LP mostly stops by exact equality, a
 For tests/test_gpu_fuzz_cp_gap.py: boxing an LP changes its bounds and nothing else; the certificate's lists and batches have a
 finite bound at every edge size, hold stopping and running LPs of every kind, unbounded LPs and boxed LPs that never stop, and
 almost no undecidable check; HiGHS solves every LP or calls it unbounded, and the restatement's own bounds are lower bounds by
-HiGHS and agree with the formula in exact rational arithmetic."""
+HiGHS and agree with the formula in exact rational arithmetic.  For tests/test_gpu_fuzz_admm_batch_stop.py: the batches reach every
+edge size and the sizes 1, 65 and 260, hold stopping and running instances side by side, tiles that hold both and tiles that
+are wholly stopped early under the drawn width and under 64, per-instance bounds and starts, and share their references; and
+the draws of the families that were there before are what they were."""
 import os
 import sys
 
@@ -337,3 +340,113 @@ def test_cp_list_certificate_cases_hold_what_the_gpu_test_claims():
 def test_cp_batch_certificate_cases_hold_what_the_gpu_test_claims():
     stats = _assert_gap_conditions("cp_batch_gap", fuzz_batched.cp_batch_gap_cases(CASES, SEED), fuzz_batched.CP_TILE_EDGE)
     assert stats["rounded_to_zero"] == fuzz_batched.CP_BATCH_GAP_ROUNDED_TO_ZERO
+
+
+# ---- the batched ADMM stopping test: what keeps tests/test_gpu_fuzz_admm_batch_stop.py from passing vacuously -------------------------
+
+def test_admm_batch_stopping_cases_hold_what_the_gpu_test_claims():
+    import time
+
+    from pysparselp_amd import _many
+    from pysparselp_amd.ADMM import _validate_batch
+
+    fuzz_batched._STOP_CASES.pop(("admm_batch", CASES, SEED), None)
+    start = time.perf_counter()
+    cases = fuzz_batched.admm_batch_stop_cases(CASES, SEED)
+    elapsed = time.perf_counter() - start
+    assert len(cases) == CASES and elapsed < 30, elapsed   # the references are shared by the cycled instances
+    sizes = [len(case.lps) for case in cases]
+    assert [case.args["c"].shape[1] for case in cases[:len(fuzz_batched.EDGE_N)]] == list(fuzz_batched.EDGE_N)
+    assert {1, 65, fuzz_batched.LONG_LIST} <= set(sizes) and sizes[fuzz_batched.large_case(CASES)] == fuzz_batched.LONG_LIST
+    assert set(sizes) <= set(fuzz_batched.ADMM_BATCH_STOP_SIZES) | {fuzz_batched.LONG_LIST}
+    both = spread = stopped = running = 0
+    tiles = {"drawn": [0, 0], "64": [0, 0]}
+    stops = []
+    for case in cases:
+        a, want = case.args, case.want()
+        _validate_batch(a["c"], a["a_eq"], a["beq"], a["a_ineq"], a["b_lower"], a["b_upper"], a["lb"], a["ub"], a["x0"])
+        assert case.distinct() == min(len(case.lps), fuzz_batched.ADMM_BATCH_DISTINCT) == case.distinct_args["c"].shape[0]
+        assert all(case.ref(k) is case.ref(k % case.distinct()) for k in range(len(case.lps)))
+        assert case.total == fuzz_batched.STOP_EXTRA + case.its and case.every in fuzz_batched.STOP_EVERY and case.plot in fuzz_batched.CADENCES
+        assert case.t_star % case.every == 0 and case.total // 3 <= case.t_star <= case.total and 0 <= case.k_star < len(case.lps)
+        assert 1 <= case.after <= max(1, case.total // 3 - 1) and case.width in fuzz_batched.ADMM_BATCH_WIDTHS
+        assert 1 <= case.rearm < case.t_star and case.rearm < case.off <= case.total
+        assert case.rearm % case.every == 0 or case.t_star == case.every   # a check, where one lies before t_star
+        for tol in case.tol:
+            assert _many.check_stop(tol, case.every) == (tol, case.every)
+        assert case.tol == tuple(float(curve[case.t_star - 1]) for curve in case.ref(case.k_star).curves)
+        assert want[1][case.k_star] and want[0][case.k_star] <= case.t_star   # the instance the tolerances come from stops by then
+        assert all(want[0][~want[1]] == case.total) and all(want[0][want[1]] % case.every == 0)
+        for col, dtype in zip(want, (np.int64, bool, np.float64, np.float64)):
+            assert col.dtype == dtype and col.shape == (len(case.lps),)
+        stopped += int(want[1].sum())
+        running += int((~want[1]).sum())
+        both += bool(want[1].any() and not want[1].all())
+        spread += len(set(want[0][want[1]])) >= 3
+        stops += list(want[0][want[1]])
+        for name, width in (("drawn", case.width), ("64", 64)):
+            mixed, dead = fuzz_batched.stop_tiles(want, width, case.every)
+            tiles[name][0] += mixed
+            tiles[name][1] += dead
+    print(f"admm_batch_stop: {sum(sizes)} instances, {stopped} stop and {running} run; {both} of {CASES} batches hold both kinds, {spread} stop at "
+          f"three or more distinct iterations; stopping iterations {min(stops)} .. {max(stops)}; (mixed, dead) tiles {tiles}; restated in {elapsed:.1f} s")
+    assert 3 * both >= CASES and spread >= 1
+    assert all(count >= 1 for pair in tiles.values() for count in pair), tiles
+    # a levels launch with several workgroups along x and several tiles: more than 256 (row, instance) lanes in the widest pass
+    assert any(case.ref(0).xs[0].size * case.width > 256 and len(case.lps) > case.width for case in cases)
+    lps = [case.distinct_args for case in cases]
+    ns, longest, empty_row, empty_col = _shape_facts(lps)
+    assert set(fuzz_batched.EDGE_N) <= ns and longest > 64 and empty_row and empty_col
+    assert any(np.ndim(lp["lb"]) == 2 for lp in lps) and any(np.ndim(lp["x0"]) == 2 for lp in lps)
+    assert any(np.any(np.isinf(lp["lb"])) for lp in lps) and any(np.any(lp["lb"] == lp["ub"]) for lp in lps)
+
+
+def test_stop_tiles_on_hand_made_states():
+    want = (np.array([10, 20, 40, 40, 10, 10, 40, 30]), np.array([True, True, False, False, True, True, False, True]))
+    assert fuzz_batched.stop_tiles(want, 2, 10) == (1, 2)   # tiles (10, 20) and (10, 10) are dead, (40 running, 30) is mixed
+    assert fuzz_batched.stop_tiles(want, 4, 10) == (2, 0)
+    assert fuzz_batched.stop_tiles(want, 8, 10) == (1, 0)
+    all_stop = (np.array([10, 10, 20, 25]), np.ones(4, dtype=bool))
+    assert fuzz_batched.stop_tiles(all_stop, 2, 10) == (0, 1)   # the first tile stops a check before the second one
+    assert fuzz_batched.stop_tiles(all_stop, 2, 20) == (0, 0) and fuzz_batched.stop_tiles(all_stop, 64, 1) == (0, 0)
+    assert fuzz_batched.stop_tiles(want, 1, 10)[0] == 0
+
+
+def _digest(cases):
+    """sha256 over everything a family's generator returns: every array with type and shape, every matrix, every number."""
+    import hashlib
+
+    h = hashlib.sha256()
+
+    def feed(v):
+        if isinstance(v, dict):
+            for key in sorted(v):
+                h.update(key.encode())
+                feed(v[key])
+        elif isinstance(v, (list, tuple)):
+            h.update(b"[%d" % len(v))
+            for item in v:
+                feed(item)
+        elif scipy.sparse.issparse(v):
+            v = v.tocsr()
+            feed([np.asarray(v.shape), v.indptr.astype(np.int64), v.indices.astype(np.int64), v.data])
+        elif v is None:
+            h.update(b"None")
+        elif isinstance(v, np.ndarray):
+            h.update(str((v.dtype.str, v.shape)).encode())
+            h.update(np.ascontiguousarray(v).tobytes())
+        else:
+            h.update(repr(v).encode())
+
+    feed(cases)
+    return h.hexdigest()
+
+
+def test_the_draws_of_the_existing_families_are_untouched():
+    """The digests of the commit before the batched ADMM stopping family, for ``TEST_SEED`` / ``TEST_CASES``."""
+    before = {"admm_batch_cases": "e65595c8598c6fd2d14050914a6fa807284bda09e397da13fbd0af0935d717e5",
+              "admm_many_cases": "86591dc894861a5331138b20bab4d3f874d413a3dafecb1d0b261eda73b1eb48",
+              "cp_batch_cases": "3fbf0c7742a276a6472c421c6e13af765b46e5a1dd2341eb4fcef457c8fff750"}
+    fuzz_batched.admm_batch_stop_cases(CASES, SEED)   # drawing the new family changes none of them
+    for name, digest in before.items():
+        assert _digest(getattr(fuzz_batched, name)(CASES, SEED)) == digest, name

@@ -7,7 +7,8 @@ conditions that make them a test are those of tests/test_admm_batch_stop_host.py
 (``np.array_equal``): the stopping iterations, the last evaluated residual and step, ``x`` over all ``N`` columns and ``lambda`` of a
 stopped instance against the single-instance solver in SEQUENTIAL order after exactly its stopping iteration, a running
 instance against the same batch without a test.  The one exception is the report's energy, a sum in another fixed order:
-``ENERGY_TOL`` of tests/test_gpu_admm_batch.py.  Needs a real MI355X: run with ``-m gpu``.
+``ENERGY_TOL`` of tests/test_gpu_admm_batch.py.  An instance whose arithmetic overflows to NaN (section 3b) is compared with the oracle's
+iterates, NaN for NaN.  Needs a real MI355X: run with ``-m gpu``.
 """
 import functools
 
@@ -16,7 +17,8 @@ import pytest
 
 import admm_batch_stop_cpu
 from conftest import load_golden, lp_from_golden
-from test_admm_batch_stop_host import BATCHES, EVERY, batch_args, batch_curves, batch_stops
+from test_admm_batch_stop_host import (BATCHES, EVERY, NAN_EVERY, NAN_INSTANCE, NAN_TOL, NAN_TOTAL, batch_args, batch_curves, batch_stops, fuzz_batched,
+                                       nan_batch)
 from test_gpu_admm_batch import ENERGY_TOL, FORMS, _mods, _of_instance, _state, _take
 
 pytestmark = pytest.mark.gpu
@@ -44,10 +46,11 @@ def _expected(name, schedule=None, total=None, batch=5, order=None):
     return admm_batch_stop_cpu.stop_state(curves, tol + (EVERY,) if schedule is None else schedule, run if total is None else total)
 
 
-def _same_state(got, want):
+def _same_state(got, want, nan=False):
+    """``nan``: the restatement itself holds a NaN, which the device must hold in the same place."""
     assert got[0].dtype == np.int64 and got[1].dtype == bool and got[2].dtype == np.float64 and got[3].dtype == np.float64
     for g, w, what in zip(got, want, ("iterations", "stopped", "residual", "step")):
-        assert np.array_equal(g, w), (what, g, w)
+        assert np.array_equal(g, w, equal_nan=nan and g.dtype == np.float64), (what, g, w)
 
 
 @functools.lru_cache(maxsize=None)
@@ -208,6 +211,52 @@ def test_a_tile_that_stops_long_before_another(form, tile4):
             _check_iterates(st, name, want, total, batch=batch, order=order)
         finally:
             st.close()
+
+
+# ------------------------------------------------------------------ 3b. a NaN never stops
+@functools.lru_cache(maxsize=None)
+def _nan_references():
+    """Per instance of the NaN batch the oracle's iterates over ``NAN_TOTAL`` iterations (``fuzz_batched.StopRef``; shared, read
+    only)."""
+    args, _ = nan_batch()
+    with np.errstate(over="ignore", invalid="ignore"):
+        return tuple(fuzz_batched.admm_stop_reference(*_of_instance(args, k), NAN_TOTAL, 10 ** 9) for k in range(args["cs"].shape[0]))
+
+
+@pytest.mark.parametrize("every", NAN_EVERY)
+def test_an_instance_that_overflows_never_stops_and_leaves_its_tile_mates_alone(every, form, tile4):
+    """Instance 2 of five -- in the middle of a full tile of four, with a tile of one instance behind it -- has a cost of 1e308 on
+    a variable without an upper bound: its residual and step are about 1e307, then infinite, then NaN (the conditions are those
+    of tests/test_admm_batch_stop_host.py).  The maxima keep a NaN through the shuffles, the LDS slots and the slots of the levels
+    form, so the instance never stops under tolerances that a record of 0.0 would meet at once: it runs to the end with the
+    NaN in its record from the first check behind it, its iterate the oracle's, NaN for NaN.  The four others stop where the
+    restatement says with the oracle's iterates of their own stopping iterations, bit for bit."""
+    args, curves = nan_batch()
+    bad = np.isnan(curves[NAN_INSTANCE][0]) | np.isnan(curves[NAN_INSTANCE][1])
+    first_check = -(-(int(np.argmax(bad)) + 1) // every) * every   # the first check iteration with the NaN
+    st = _armed(args, NAN_TOL, every)
+    try:
+        assert st.form() == form
+        st.iterate(first_check)
+        got = st.stop_state()
+        print(form, every, first_check, got)
+        assert np.isnan(got[2][NAN_INSTANCE]) and np.isnan(got[3][NAN_INSTANCE]) and not got[1].any()
+        _same_state(got, admm_batch_stop_cpu.stop_state(curves, NAN_TOL + (every,), first_check), nan=True)
+        st.iterate(NAN_TOTAL - first_check)
+        want = admm_batch_stop_cpu.stop_state(curves, NAN_TOL + (every,), NAN_TOTAL)
+        got = st.stop_state()
+        print(got)
+        assert want[1].sum() == 4 and not got[1][NAN_INSTANCE] and got[0][NAN_INSTANCE] == NAN_TOTAL
+        assert np.isnan(got[2][NAN_INSTANCE]) and np.isnan(got[3][NAN_INSTANCE])
+        _same_state(got, want, nan=True)
+        x, lam = st.x(), st.lam()
+        for k, ref in enumerate(_nan_references()):
+            t = int(want[0][k])
+            assert np.array_equal(x[k], ref.xs[t], equal_nan=k == NAN_INSTANCE), k
+            assert np.array_equal(lam[k], ref.duals[t], equal_nan=k == NAN_INSTANCE), k
+        assert np.isnan(x[NAN_INSTANCE]).any() and np.all(np.isfinite(np.delete(x, NAN_INSTANCE, axis=0)))
+    finally:
+        st.close()
 
 
 # ------------------------------------------------------------------ 4. re-arming, turning off, nothing left to run

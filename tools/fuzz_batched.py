@@ -26,9 +26,16 @@ bit; an LP with a check too close to its threshold to be decided in another orde
 compared (at most 5 % of a family).  The recorded bound is also checked against the formula in exact rational arithmetic on the
 device's own ``y`` and, as a lower bound, against HiGHS.
 
+``admm_batch_stop`` arms the per-instance stopping test of the batched ADMM solver (``ADMMBatchState.set_stop`` / ``stop_state``,
+``lp_admm_batch_until``) on batches of its own of 1 to 65 instances and one of 260 (at most nine distinct instances, cycled), in
+both forms of the iteration and with tile widths 1 to 64 (``SLP_ADMM_BATCH_FORM``, ``SLP_ADMM_BATCH_TILE``): the tolerances are the
+restated residual and step of one instance at a check iteration; ``stop_state`` against tests/admm_batch_stop_cpu.py, also armed
+in mid-life, armed again and turned off, and every instance's ``x`` and ``lambda`` against the oracle's at its own count, bit for
+bit.  No instance is left out.
+
     python tools/fuzz_batched.py [--cases 24] [--seed 0]
         [--family cp_batch,cp_many,admm_batch,admm_many,dga,dga_batch,dga_many,cp_many_stop,admm_many_stop,dga_many_stop,
-                  cp_many_gap,cp_batch_gap]
+                  cp_many_gap,cp_batch_gap,admm_batch_stop]
 
 The generators and the CPU references need no GPU (tests/test_fuzz_batched_host.py checks on them that the GPU runs compare what
 they claim to); the ``run_*`` functions need one."""
@@ -65,6 +72,12 @@ CP_STOP_OFFSET, ADMM_STOP_OFFSET = 8000, 7000   # the stopping draws' generators
 DGA_STOP_OFFSET, DGA_STOP_EVERY = 6027, (1, 2, 5, 10)
 DGA_STOP_LEFT_OUT = 0.25   # the largest share of the LPs of a run that may lie behind their parity horizon (not compared)
 STOP_AFTER_OFFSET = 500   # on top of them: the generator of ``after``, so that the test's own draws do not depend on it
+# the stopping test of the batched ADMM solver (``admm_batch_stop``): batches of their own from RandomState(seed + offset), at most
+# ADMM_BATCH_DISTINCT distinct instances each (a larger batch cycles them), ``large_case`` with LONG_LIST instances; every case draws
+# one tile width.  The offset: 11000 was tried first and draws no batch of one instance for TEST_SEED / TEST_CASES (it meets every other
+# condition of tests/test_fuzz_batched_host.py); 11001 is the smallest offset from there on that meets them all on the CPU
+ADMM_BATCH_STOP_OFFSET = 11001
+ADMM_BATCH_STOP_SIZES, ADMM_BATCH_DISTINCT, ADMM_BATCH_WIDTHS = (1, 2, 3, 5, 8, 17, 33, 65), 9, (2, 4, 8, 16, 32)
 # the certified stopping test (``cp_many_gap`` / ``cp_batch_gap``): the generators of the lists and of the batches, and on top of
 # them those of the coin that boxes an LP (with probability GAP_BOXED) and of the test's own draws.  The lists' offset 9000 meets
 # the conditions of tests/test_fuzz_batched_host.py at once.  The batches': 10000 was tried first; 10109 is the smallest offset from
@@ -206,9 +219,9 @@ def large_case(cases):
     return min(len(EDGE_N), cases - 1)
 
 
-def batch_sizes(rng, cases, edge):
-    """One size per case from ``BATCH_SIZES``; ``large_case`` has the family's tile-edge size."""
-    sizes = [int(rng.choice(BATCH_SIZES)) for _ in range(cases)]
+def batch_sizes(rng, cases, edge, among=BATCH_SIZES):
+    """One size per case from ``among``; ``large_case`` has the family's tile-edge size."""
+    sizes = [int(rng.choice(among)) for _ in range(cases)]
     sizes[large_case(cases)] = edge
     return sizes
 
@@ -338,7 +351,7 @@ def admm_stop_reference(problem, x0, total, plot):
         lams.append(np.array(lam, copy=True))
 
     oracle.lp_admm(*problem, x0=x0, nb_iter=total, nb_iter_plot=plot, callback_func=rec, iterate_hook=hook)
-    assert len(lams) == total + 1 and np.array_equal(admm_stop_cpu.curves_of(xs[:total + 1], curves[0])[1], curves[1])
+    assert len(lams) == total + 1 and np.array_equal(admm_stop_cpu.curves_of(xs[:total + 1], curves[0])[1], curves[1], equal_nan=True)
     if rec.it[-1] == total:   # the driver's horizon is nb_iter = total - 1: no report at index total
         for store in (rec.it, rec.x, rec.e1, rec.e2, rec.veq, rec.vineq):
             store.pop()
@@ -365,6 +378,89 @@ def cp_stop_cases(cases, seed):
 def admm_stop_cases(cases, seed):
     """``[StopCase]`` of ``run_admm_many_stop``: the lists of ``admm_many_cases`` with a stopping test each."""
     return _stop_cases("admm", admm_many_cases, ADMM_STOP_OFFSET, cases, seed)
+
+
+class BatchStopCase(StopCase):
+    """One batch of ``lp_admm_batch`` with its stopping test: a ``StopCase`` of family ``"admm"`` whose ``lps`` are the instances of
+    the batch taken singly.  ``distinct_args`` holds the distinct instances (``batch_of``), ``args`` the ``batch`` instances the
+    device gets: instance ``k`` is distinct instance ``k % distinct``, so a larger batch cycles them and shares their references.
+    Beyond ``StopCase``'s draws: the tile ``width`` of the forced settings and, for the run with a schedule, ``rearm`` -- a check
+    before ``t_star`` (any iteration before it where there is no such check) at which the test is armed again with both
+    tolerances halved -- and ``off``, a later iteration at which it is turned off."""
+
+    def __init__(self, distinct_args, batch, its, plot, rng, rng_after):
+        distinct = distinct_args["c"].shape[0]
+        singles = []
+        for j in range(distinct):
+            problem, x0 = of_instance(distinct_args, j)
+            singles.append(dict(zip(("c", "a_eq", "beq", "a_ineq", "b_lower", "b_upper", "lb", "ub"), problem), x0=x0))
+        pick = np.arange(batch) % distinct
+        super().__init__("admm", [singles[j] for j in pick], its, plot, rng, rng_after)
+        self.distinct_args = distinct_args
+        self.args = {name: v[pick] if (name in ("c", "lb", "ub", "x0") and np.ndim(v) == 2) else v for name, v in distinct_args.items()}
+        self.width = int(rng.choice(ADMM_BATCH_WIDTHS))
+        before = list(range(self.every, self.t_star, self.every)) or list(range(1, self.t_star))
+        self.rearm = int(rng.choice(before))
+        self.off = int(rng.randint(self.rearm + 1, self.total + 1))
+
+    def curves(self):
+        return tuple(self.ref(k).curves for k in range(len(self.lps)))
+
+    def schedule(self):
+        """Armed from creation, armed again at ``rearm`` with halved tolerances, off at ``off``."""
+        return [(0, *self.tol, self.every), (self.rearm, *(tol / 2 for tol in self.tol), self.every), (self.off, None, None, 1)]
+
+    def want(self, after=0, schedule=None, total=None):
+        """``admm_batch_stop_cpu.stop_state`` over the instances after ``total`` iterations (the case's, when None) of a state armed
+        by ``schedule`` -- when None: once, with the case's tolerances, after ``after`` iterations."""
+        import admm_batch_stop_cpu
+
+        schedule = [(after, *self.tol, self.every)] if schedule is None else schedule
+        return admm_batch_stop_cpu.stop_state(self.curves(), schedule, self.total if total is None else total)
+
+
+def admm_batch_stop_cases(cases, seed):
+    """``[BatchStopCase]`` of ``run_admm_batch_stop``: batches made as those of ``admm_batch_cases`` (cases 0 .. 9 at the edge sizes)
+    from generators of their own, with 1 to 65 instances and ``LONG_LIST`` in ``large_case``; the references are computed once per
+    distinct instance and shared."""
+    key = ("admm_batch", cases, seed)
+    if key not in _STOP_CASES:
+        rng = np.random.RandomState(seed + ADMM_BATCH_STOP_OFFSET)
+        rng_after = np.random.RandomState(seed + ADMM_BATCH_STOP_OFFSET + STOP_AFTER_OFFSET)
+        out = []
+        for case, b in enumerate(batch_sizes(rng, cases, LONG_LIST, ADMM_BATCH_STOP_SIZES)):
+            args = batch_of(rng, random_lp(rng, "admm", edge_n(case)), min(b, ADMM_BATCH_DISTINCT), "admm")
+            out.append(BatchStopCase(args, b, int(rng.randint(1, 61)), int(rng.choice(CADENCES)), rng, rng_after))
+        _STOP_CASES[key] = out
+    return _STOP_CASES[key]
+
+
+def admm_batch_width(form, batch):
+    """The tile width the library chooses for a batch ("Batched ADMM")."""
+    if form == "tile":
+        return 1 if batch <= 256 else 4 if batch <= 1024 else 16
+    return 1 if batch == 1 else 4 if batch <= 4 else 16
+
+
+def admm_batch_stop_settings(width):
+    """``(name, SLP_ADMM_BATCH_FORM, SLP_ADMM_BATCH_TILE)`` of the six runs of a case whose drawn tile width is ``width``."""
+    return (("default", None, None), ("tile, drawn width", "tile", width), ("levels, drawn width", "levels", width),
+            ("tile, width 64", "tile", 64), ("levels, width 64", "levels", 64), ("levels, width 1", "levels", 1))
+
+
+def stop_tiles(want, width, every):
+    """``(mixed, dead)`` of one run, from the restatement's ``want`` and the tile width: the tiles (``width`` consecutive instances)
+    that hold a stopped and a running instance at the end, and the tiles that are wholly stopped at least one check before an
+    instance of another tile stops or, still running, reaches the end of the run -- such a tile's workgroup returns at once while
+    the others work."""
+    iterations, stopped = want[0], want[1]
+    mixed = dead = 0
+    for start in range(0, len(stopped), width):
+        mine = np.zeros(len(stopped), dtype=bool)
+        mine[start:start + width] = True
+        mixed += bool(stopped[mine].any() and not stopped[mine].all())
+        dead += bool(stopped[mine].all() and not mine.all() and iterations[~mine].max() >= iterations[mine].max() + every)
+    return mixed, dead
 
 
 # ---- the certified stopping test of the two Chambolle-Pock families: draws and what the restatement expects ------------------------
@@ -1177,12 +1273,16 @@ class _StopReports(_Reports):
         self.seen.append({name: np.array(values, copy=True) for name, values in self.info.items()})
 
 
-def _stop_where(case_no, seed, case, setting, forms):
-    """``where(k, run)``: the head of every message about LP ``k`` of the list in the run ``run``."""
+def _stop_where(case_no, seed, case, setting, forms, width=None):
+    """``where(k, run)``: the head of every message about LP ``k`` of the list (instance ``k`` of the batch, run with tiles of
+    ``width`` instances) in the run ``run``."""
     def where(k, run):
         n = case.problems[k][0].size
         start = "cold" if case.x0[k] is None else "warm"
-        return (f"{case.family}_many_stop seed {seed} case {case_no} LP {k} of {len(case.lps)} (n {n}, {start} start, {case.total} iterations), "
+        who = f"{case.family}_many_stop seed {seed} case {case_no} LP {k} of {len(case.lps)}"
+        if width is not None:
+            who = f"admm_batch_stop seed {seed} case {case_no} instance {k} of B = {len(case.lps)}, tile width {width}"
+        return (f"{who} (n {n}, {start} start, {case.total} iterations), "
                 f"setting {setting}, form {forms[k]}, every {case.every}, tolerances {case.tol!r} (LP {case.k_star} at iteration {case.t_star}), {run}")
     return where
 
@@ -1199,11 +1299,13 @@ def _stop_layer(case, k, count):
 STOP_NAMES = {"cp": ("iterations", "stopped", "step"), "admm": ("iterations", "stopped", "residual", "step")}
 
 
-def _compare_stop(case, want, got, iterates, where, run):
+def _compare_stop(case, want, got, iterates, where, run, dtypes=False):
     """``got`` (the columns of ``stop_state``, or of the driver's ``info``) against the restatement's ``want`` with
     ``np.array_equal``, and -- unless ``iterates`` is None -- every LP's primal and dual iterate against the oracle's at that LP's
-    own count, bit for bit."""
+    own count, bit for bit.  A NaN equals a NaN, so a column differs wherever the restatement holds none and the device one.
+    ``dtypes``: the columns also have the restatement's types."""
     for name, g, w in zip(STOP_NAMES[case.family], got, want):
+        _require(not dtypes or g.dtype == w.dtype, where(0, run) + f": {name} has type {g.dtype}, the restatement's has {w.dtype}")
         if not np.array_equal(g, w, equal_nan=(name not in ("iterations", "stopped"))):
             k = next(k for k in range(len(w)) if not np.array_equal(g[k], w[k], equal_nan=True))
             count = max(1, int(min(got[0][k], want[0][k], case.total)))
@@ -1253,12 +1355,17 @@ def _compare_stop_driver(case, want, xs, info, rec, where):
 
 
 def _run_many_stop(family, cases, seed):
-    """Both ``run_*_many_stop``: see there."""
+    """Both ``run_*_many_stop`` and, with ``family == "admm_batch"``, ``run_admm_batch_stop``: see there."""
+    batched = family == "admm_batch"
+
+    def forms_of(state):   # a batch has one form
+        return [state.form()] * state.batch if batched else [state.form(k) for k in range(state.count)]
+
     if family == "cp":
         from pysparselp_amd import CPManyState, chambolle_pock_ppd_many_until
         from pysparselp_amd.ChambollePockPPD import _many_problem
 
-        settings, switches = CP_MANY_SETTINGS, ("SLP_CP_MANY_FORM", "SLP_CP_MANY_KMAX")
+        settings, switches = (lambda case: CP_MANY_SETTINGS), ("SLP_CP_MANY_FORM", "SLP_CP_MANY_KMAX")
         stop_cases = cp_stop_cases(cases, seed)
 
         def create(case):
@@ -1275,11 +1382,34 @@ def _run_many_stop(family, cases, seed):
             xs, _, info = chambolle_pock_ppd_many_until(case.problems, *case.tol, case.every, x0=case.x0, nb_max_iter=case.total, callback_func=rec,
                                                         nb_iter_plot=case.plot)
             return xs, info
+    elif batched:
+        from pysparselp_amd import ADMMBatchState, lp_admm_batch_until
+
+        settings, switches = (lambda case: admm_batch_stop_settings(case.width)), ("SLP_ADMM_BATCH_FORM", "SLP_ADMM_BATCH_TILE")
+        stop_cases = admm_batch_stop_cases(cases, seed)
+
+        def blocks(case):
+            a = case.args
+            return a["c"], a["a_eq"], a["beq"], a["a_ineq"], a["b_lower"], a["b_upper"], a["lb"], a["ub"]
+
+        def create(case):
+            return ADMMBatchState(*blocks(case), case.args["x0"])
+
+        def halves(state):
+            state.sweep_step()
+            state.multiplier_step()
+
+        def iterates(state):
+            return state.x(), state.lam()
+
+        def driver(case, rec):   # nb_iter + 1 sweeps
+            return lp_admm_batch_until(*blocks(case), *case.tol, case.every, x0=case.args["x0"], nb_iter=case.total - 1, callback_func=rec,
+                                       nb_iter_plot=case.plot)
     else:
         from pysparselp_amd import ADMMManyState, lp_admm_many_until
         from pysparselp_amd.ADMM import _admm_many_problem, _admm_many_starts
 
-        settings, switches = ADMM_MANY_SETTINGS, ("SLP_ADMM_MANY_FORM", "SLP_ADMM_MANY_KMAX")
+        settings, switches = (lambda case: ADMM_MANY_SETTINGS), ("SLP_ADMM_MANY_FORM", "SLP_ADMM_MANY_KMAX")
         stop_cases = admm_stop_cases(cases, seed)
 
         def create(case):
@@ -1297,55 +1427,79 @@ def _run_many_stop(family, cases, seed):
             return lp_admm_many_until(case.problems, *case.tol, case.every, x0=case.x0, nb_iter=case.total - 1, callback_func=rec,
                                       nb_iter_plot=case.plot)
 
-    def armed_run(case, unarmed, split_at=None):
-        """A fresh state: ``unarmed`` iterations, ``set_stop``, the rest up to ``total`` (the iteration ``split_at`` in its two halves).
-        Returns ``(forms, stop_state, iterates, column 1 of the report)``."""
+    def armed_run(case, unarmed, split_at=None, calls=()):
+        """A fresh state: ``unarmed`` iterations, ``set_stop``, the rest up to ``total`` (the iteration ``split_at`` in its two halves;
+        a further ``set_stop(*arguments)`` once ``at`` iterations are complete for each ``(at, arguments)`` of ``calls``).  Returns
+        ``(forms, stop_state, iterates, column 1 of the report, [(at, stop_state before the call, after it)])``."""
         state = create(case)
         try:
-            forms = [state.form(k) for k in range(state.count)]
+            forms = forms_of(state)
             for p in _pieces(unarmed):
                 state.iterate(p)
             state.set_stop(*case.tol, case.every)
-            done = unarmed
+            done, marks = unarmed, []
             if split_at is not None:
                 for p in _pieces(split_at - 1 - done):
                     state.iterate(p)
                 halves(state)
                 done = split_at
+            for at, arguments in calls:
+                for p in _pieces(at - done):
+                    state.iterate(p)
+                done, before = at, state.stop_state()
+                state.set_stop(*arguments)
+                marks.append((at, before, state.stop_state()))
             for p in _pieces(case.total - done):
                 state.iterate(p)
-            return forms, state.stop_state(), iterates(state), (state.report()[:, 1] if family == "admm" else None)
+            return forms, state.stop_state(), iterates(state), (None if family == "cp" else state.report()[:, 1]), marks
         finally:
             state.close()
 
-    counts = dict(lists=0, lps=0, runs=0, stopped=0, running=0, longest=0)
+    counts = dict(lists=0, entries=0, lps=0, runs=0, stopped=0, running=0, longest=0, mixed_tiles=0, dead_tiles=0)
     for case_no, case in enumerate(stop_cases):
         want = case.want()
-        for name, form, kmax in settings:
+        for name, form, kmax in settings(case):
             with environment(**dict(zip(switches, (form, kmax)))):
-                forms, got, its, residual = armed_run(case, 0)   # (a) armed from creation
-                where = _stop_where(case_no, seed, case, name, forms)
-                _require(form is None or set(forms) == {form}, f"{family}_many_stop seed {seed} case {case_no}: forms {set(forms)} under {switches[0]}={form}")
-                _compare_stop(case, want, got, its, where, "armed from creation")
-                if family == "admm":
+                forms, got, its, residual, _ = armed_run(case, 0)   # (a) armed from creation
+                _require(form is None or set(forms) == {form}, f"{'admm_batch' if batched else family + '_many'}_stop seed {seed} case {case_no}: forms {set(forms)} under {switches[0]}={form}")
+                width = (kmax or admm_batch_width(forms[0], len(case.lps))) if batched else None
+                where = _stop_where(case_no, seed, case, name, forms, width)
+                _compare_stop(case, want, got, its, where, "armed from creation", dtypes=batched)
+                if family != "cp":
                     for k in np.nonzero(want[1])[0]:
                         _require(residual[k] == want[2][k], where(k, "armed from creation") + f": the report's residual {residual[k]!r} of a stopped LP, "
                                  f"recorded {want[2][k]!r}", _stop_layer(case, k, int(want[0][k])))
+                if batched:
+                    mixed, dead = stop_tiles(want, width, case.every)
+                    counts["mixed_tiles"] += mixed
+                    counts["dead_tiles"] += dead
                 if name == "default":
-                    _, got, its, _ = armed_run(case, case.after)   # (b) armed in mid-life
-                    _compare_stop(case, case.want(after=case.after), got, its, where, f"armed after {case.after} iterations")
-                    _, got, its, _ = armed_run(case, 0, split_at=case.t_star)   # (c) the iteration t_star in its two halves
-                    _compare_stop(case, want, got, its, where, f"iteration {case.t_star} in two halves")
-                    rec = _StopReports()   # (d) the driver
+                    _, got, its, _, _ = armed_run(case, case.after)   # (b) armed in mid-life
+                    _compare_stop(case, case.want(after=case.after), got, its, where, f"armed after {case.after} iterations", dtypes=batched)
+                    _, got, its, _, _ = armed_run(case, 0, split_at=case.t_star)   # (c) the iteration t_star in its two halves
+                    _compare_stop(case, want, got, its, where, f"iteration {case.t_star} in two halves", dtypes=batched)
+                    if batched:   # (d) armed again with halved tolerances, then off: the flags and the last evaluated numbers stay
+                        schedule = case.schedule()
+                        run = f"armed again at {case.rearm} with halved tolerances, off at {case.off}"
+                        _, got, its, _, marks = armed_run(case, 0, calls=[(case.rearm, schedule[1][1:]), (case.off, (None, None))])
+                        for i, (at, before, after) in enumerate(marks):
+                            _compare_stop(case, case.want(schedule=schedule[:i + 1], total=at), before, None, where, run + f", after {at} iterations", dtypes=True)
+                            _compare_stop(case, before, after, None, where, run + f", after the call of set_stop at {at}", dtypes=True)
+                        _compare_stop(case, case.want(schedule=schedule), got, its, where, run, dtypes=True)
+                    rec = _StopReports()   # the driver
                     xs, info = driver(case, rec)
                     _compare_stop_driver(case, want, xs, info, rec, where)
             counts["runs"] += 1
         counts["lists"] += 1
+        counts["entries"] += len(case.lps)
         counts["lps"] += case.distinct()
         counts["stopped"] += int(want[1].sum())
         counts["running"] += int((~want[1]).sum())
         counts["longest"] = max(counts["longest"], len(case.lps))
-    return counts
+    if batched:
+        return dict(batches=counts["lists"], instances=counts["entries"], distinct=counts["lps"],
+                    **{name: counts[name] for name in ("runs", "stopped", "running", "longest", "mixed_tiles", "dead_tiles")})
+    return {name: counts[name] for name in ("lists", "lps", "runs", "stopped", "running", "longest")}
 
 
 def run_cp_many_stop(cases, seed):
@@ -1363,6 +1517,19 @@ def run_admm_many_stop(cases, seed):
     (tests/admm_stop_cpu.py), ``x`` over all columns of the standard form, ``lambda``, and a stopped LP's report against its
     recorded residual.  Returns counts."""
     return _run_many_stop("admm", cases, seed)
+
+
+def run_admm_batch_stop(cases, seed):
+    """``ADMMBatchState.set_stop`` / ``stop_state`` and ``lp_admm_batch_until`` on the batches of ``admm_batch_stop_cases``, as
+    ``run_admm_many_stop`` does for the lists; no instance is left out.  Under six settings -- the library's own choice, the tile and
+    the levels form with the case's drawn tile width and with width 64, the levels form with width 1 -- armed from creation:
+    ``stop_state`` with ``np.array_equal`` and its types against tests/admm_batch_stop_cpu.py, ``x`` over all columns of the standard form and
+    ``lambda`` of every instance against the oracle's at that instance's own count, bit for bit, a stopped instance's report against
+    its recorded residual.  With the library's own choice also: armed in mid-life; the drawn iteration in its two halves; armed
+    again at a check before it with both tolerances halved and turned off later (``stop_state`` before and after either call and
+    at the end); the driver with its callbacks.  Returns counts; ``mixed_tiles`` and ``dead_tiles`` (``stop_tiles``) are summed
+    over the runs armed from creation."""
+    return _run_many_stop("admm_batch", cases, seed)
 
 
 # ---- the certified stopping test of the Chambolle-Pock list solver and of the batched one ------------------------------------------------
@@ -1980,7 +2147,8 @@ def run_dga_many_stop(cases, seed):
 
 FAMILIES = {"cp_batch": run_cp_batch, "cp_many": run_cp_many, "admm_batch": run_admm_batch, "admm_many": run_admm_many, "dga": run_dga,
             "dga_batch": run_dga_batch, "dga_many": run_dga_many, "cp_many_stop": run_cp_many_stop, "admm_many_stop": run_admm_many_stop,
-            "dga_many_stop": run_dga_many_stop, "cp_many_gap": run_cp_many_gap, "cp_batch_gap": run_cp_batch_gap}
+            "dga_many_stop": run_dga_many_stop, "cp_many_gap": run_cp_many_gap, "cp_batch_gap": run_cp_batch_gap,
+            "admm_batch_stop": run_admm_batch_stop}
 
 
 def main():
