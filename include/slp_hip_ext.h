@@ -12,6 +12,8 @@
 #include "slp_hip.h"
 /* per-instance stopping of the batched ADMM solver: declared in a header of its own, which this one brings along */
 #include "slp_hip_ext_admm_batch.h"
+/* per-instance stopping of the batched dual gradient ascent: likewise */
+#include "slp_hip_ext_dga_batch.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -9,7 +9,8 @@ matrix and the right-hand sides together (csrc/slp_dga_batch.hip); instance k is
 ``DeviceDGAMany`` / ``dual_gradient_ascent_many`` advance a list of LPs with matrices of their own, one workgroup per LP and whole
 iterations inside a launch (csrc/slp_dga_many.hip); LP k is bit for bit the single solve of ``lps[k]``.
 ``DeviceDGAMany.set_stop`` / ``dual_gradient_ascent_many_until`` stop every LP of such a list on its own, by a test on the step of
-its multipliers inside the iteration kernel.
+its multipliers inside the iteration kernel.  ``DeviceDGABatch.set_stop`` / ``dual_gradient_ascent_batch_until`` stop every instance
+of a batch on its own, on that step or once its certified lower bound has reached a cut-off, tested on the device.
 """
 import os
 import time
@@ -18,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from . import _many
-from ._batch import check_costs, concat, first_offsets, require_one_sided, shared_or_batched, split_by
+from ._batch import check_costs, check_targets, concat, first_offsets, require_one_sided, shared_or_batched, split_by
 
 PATHS = {"auto": 0, "fused": 1, "general": 2}
 FUSED_MAX = 8192    # most variables of the fused search (one workgroup, breakpoints in LDS)
@@ -342,6 +343,43 @@ class DeviceDGABatch(_DeviceDGA):
         _lib.check(self._l.slp_batch_dga_report(self._h, _lib.ptr(out)))
         return out
 
+    def set_stop(self, tol, targets=None, check_every=1):
+        """Arms the per-instance stopping test (``slp_batch_dga_set_stop``): at the end of every iteration ``t`` with
+        ``t % check_every == 0`` -- counted from 1 over the life of the state, the same number for every instance that moves -- an
+        instance that is neither frozen nor stopped stops iff ``max|y_t - y_{t-1}| <= tol`` over all its multipliers (the
+        inequality part after its clamp; a kind of rows that does not move contributes 0) or its dual energy, bit for bit
+        ``report()[k, 0]`` after ``t`` iterations, is ``>= targets[k]``.  ``tol`` None: no step test; ``targets`` None: no bound
+        test, else a scalar or one cut-off per instance, ``+inf`` for an instance without one (a NaN or ``-inf`` is a
+        ``ValueError``).  A NaN in either quantity never stops, nor does an instance whose status carries the NaN bit.  A stopped
+        instance keeps its multipliers, the x of the top of iteration ``t``, its tie-draw count and its flags and takes no part in
+        later launches; ``frozen()`` stays False for it.  ``set_stop(None)`` turns the test off, the state after the constructor.
+        No call clears a stopped mark: the tie draws behind a stopped instance are dropped, so it cannot be resumed; a new
+        rule applies to the instances still moving, and with the test off the stopped ones stay stopped."""
+        if tol is None and targets is None:
+            check_every = 1
+        else:
+            tol, targets, check_every = _check_batch_stop(tol, targets, check_every, self.batch)
+        _lib.check(self._l.slp_batch_dga_set_stop(self._h, -1.0 if tol is None else tol, _lib.ptr(targets), check_every))
+
+    def stop_state(self):
+        """``(iterations, stopped, step, bound, reason)`` per instance -- int64, bool, float64, float64 and int32 arrays: the
+        iterations completed (for a stopped instance its stopping iteration, 0 for a frozen one), whether it is stopped, the last
+        evaluated step (``+inf`` before the first check) and bound (``-inf`` before the first check with cut-offs: always a valid
+        lower bound) and why it stopped, a bit mask: 0 = moving or frozen, 1 = step, 2 = bound, 3 = both at the same check."""
+        iterations, reason = np.zeros(self.batch, dtype=np.int64), np.zeros(self.batch, dtype=np.int32)
+        step, bound = np.zeros(self.batch), np.zeros(self.batch)
+        _lib.check(self._l.slp_batch_dga_stop_state(self._h, _lib.ptr(iterations), _lib.ptr(reason), _lib.ptr(step), _lib.ptr(bound)))
+        return iterations, reason != 0, step, bound, reason
+
+
+def _check_batch_stop(tol, targets, check_every, batch):
+    """The rule of the batch's stopping test, checked without the library: ``(tol, targets, check_every)`` with ``tol`` a float
+    or None (no step test), ``targets`` a float64 array of shape ``(batch,)`` or None (no bound test); at least one is given."""
+    if tol is None and targets is None:
+        raise ValueError("a stopping test needs tol, targets or both: both are None")
+    checked, check_every = _many.check_stop(0.0 if tol is None else tol, check_every)
+    return (None if tol is None else checked), check_targets(targets, batch), check_every
+
 
 def dual_gradient_ascent_batch(lp, costs, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None, lower_bounds=None,
                                upper_bounds=None, path=None):
@@ -360,8 +398,38 @@ def dual_gradient_ascent_batch(lp, costs, nb_max_iter=1000, callback_func=None, 
     return _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path)[:3]
 
 
-def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path):
-    """``dual_gradient_ascent_batch`` plus, as a fourth value, the final ``DeviceDGABatch.report()``."""
+def dual_gradient_ascent_batch_until(lp, costs, tol=None, targets=None, check_every=10, nb_max_iter=1000, callback_func=None, y_eq=None,
+                                     y_ineq=None, max_time=None, lower_bounds=None, upper_bounds=None, path=None):
+    """``dual_gradient_ascent_batch`` with a stopping test per instance (extension; the reference runs a fixed number of
+    iterations): the batch runs until every instance has stopped or is frozen, at most ``nb_max_iter`` iterations.  Returns
+    ``(X, Y_eq, Y_ineq, info)``.
+
+    The test is made on the device (``DeviceDGABatch.set_stop``), at the end of every iteration ``t`` with ``t % check_every == 0``,
+    iterations counted from 1: an instance stops iff ``step_t = max|y_t - y_{t-1}| <= tol`` over all its multipliers (the
+    inequality part after its clamp; a kind of rows that does not move contributes 0) or its certified lower bound, the dual
+    energy of ``y_t``, has reached its cut-off, ``bound_t >= targets[k]``; a NaN never stops.  At least one of ``tol`` (a finite
+    float ``>= 0``) and ``targets`` (a scalar or shape ``(B,)``; ``+inf``: no cut-off for that instance; no NaN, no ``-inf``) is
+    required, ``check_every`` is an int ``>= 1``: a ``ValueError`` before the library is loaded otherwise, like every shape
+    error.  A stopped instance keeps its multipliers and the x of the top of iteration ``t``, bit for bit what
+    ``dual_gradient_ascent`` returns for its data with ``nb_max_iter=t``, takes no part in later launches and costs nothing
+    more, while the others go on, their iterates unchanged.
+
+    ``info`` is a dict of arrays over the batch: ``iterations`` (int64: completed, for a stopped instance its stopping iteration,
+    0 for a frozen one), ``stopped`` (bool; a frozen instance is not stopped), ``reason`` (int32 bit mask: 0 moving or frozen,
+    1 step, 2 bound, 3 both at the same check), ``step`` (float64: the last evaluated step, ``+inf`` before the first check) and
+    ``lower_bound`` (float64: the dual energy of the returned multipliers, column 0 of the final report -- a certified lower
+    bound on the instance's LP value; NaN until the run has ended).
+
+    The cadence of callbacks and of the test of ``max_time`` is that of ``dual_gradient_ascent_batch``.  ``info`` is current at
+    every callback: the same dict, updated in place, is set as the ATTRIBUTE ``callback_func.info`` before every call (a function
+    or any object that takes attributes; a bound method takes none)."""
+    stop = _check_batch_stop(tol, targets, check_every, check_costs(costs, np.size(lp.costsvector))[1])
+    return _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path, stop=stop)
+
+
+def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path, stop=None):
+    """``dual_gradient_ascent_batch`` plus, as a fourth value, the final ``DeviceDGABatch.report()``; with ``stop`` (the checked
+    ``(tol, targets, check_every)`` of ``dual_gradient_ascent_batch_until``) what that function returns."""
     require_one_sided(getattr(lp, "b_lower", None))
     from .device import DeviceMatrix
     from .tools import CsrArrays
@@ -398,8 +466,32 @@ def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time
 
     try:
         state = DeviceDGABatch(mat, b, costs, lb, ub, y0, m_eq=m_eq, draws=rs.random_sample, path=path)
-        _dga_drive(state, nb_max_iter, callback_func, max_time, start, all_frozen=state.frozen().all())
-        return result()
+        frozen = state.frozen()
+        if stop is None:
+            _dga_drive(state, nb_max_iter, callback_func, max_time, start, all_frozen=frozen.all())
+            return result()
+        info = _many.new_stop_info(batch, np.arange(batch))
+        info["reason"] = np.zeros(batch, dtype=np.int32)
+        info["lower_bound"] = np.full(batch, np.nan)
+        state.set_stop(*stop)
+
+        def refresh():
+            info["iterations"][:], info["stopped"][:], info["step"][:], _, info["reason"][:] = state.stop_state()
+
+        def all_still():
+            refresh()
+            if callback_func is not None:
+                try:
+                    callback_func.info = info
+                except AttributeError:   # a bound method takes no attribute: wrap it in a function to read ``info``
+                    pass
+            return bool(np.all(info["stopped"] | frozen))
+
+        _dga_drive(state, nb_max_iter, callback_func, max_time, start, all_frozen=frozen.all(), all_still=all_still)
+        x, ye, yi, report = result()
+        refresh()
+        info["lower_bound"][:] = report[:, 0]
+        return x, ye, yi, info
     finally:
         if state is not None:
             state.close()

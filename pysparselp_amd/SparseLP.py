@@ -781,6 +781,49 @@ class SparseLP:
         elapsed = time.perf_counter() - start
         return (x, elapsed) if get_timing else x
 
+    def solve_dga_batch_until(
+        self,
+        costs,
+        tol=None,
+        targets=None,
+        check_every=10,
+        get_timing=True,
+        nb_iter=10000,
+        max_time=None,
+        nb_iter_plot=10,
+        ground_truth=None,
+        ground_truth_indices=None,
+        lower_bounds=None,
+        upper_bounds=None,
+    ):
+        """``solve_dga_batch`` with a stopping test per instance (``DualGradientAscent.dual_gradient_ascent_batch_until``): every
+        instance stops on its own at the first iteration ``t`` with ``t % check_every == 0`` at which the step
+        ``max|y_t - y_{t-1}|`` over its multipliers is at most ``tol`` or its certified lower bound, the dual energy of ``y_t``, has
+        reached its cut-off ``targets[k]``; the others go on, at most ``nb_iter`` iterations.  Returns ``(X, elapsed)`` or ``X``.
+        At least one of ``tol`` (a finite float ``>= 0``) and ``targets`` (a scalar or shape ``(B,)``, ``+inf`` for an instance
+        without a cut-off) is required and ``check_every`` is an int ``>= 1``: a ``ValueError`` otherwise.
+
+        Sets ``self.dual_multipliers`` and ``self.dual_lower_bounds`` as ``solve_dga_batch`` does, and ``self.stop_info``, the
+        ``info`` of ``dual_gradient_ascent_batch_until``: a dict of arrays of length B, ``iterations``, ``stopped``, ``reason``,
+        ``step`` and ``lower_bound``.  The curves are filled as by ``solve_dga_batch``, arrays of length B per report; the loop ends
+        behind the first call after which no instance moves, and a stopped instance's entries are those of its final iterate.
+        """
+        from .DualGradientAscent import _check_batch_stop, _dga_batch_run
+
+        costs, batch = check_costs(costs, self.nb_variables)
+        stop = _check_batch_stop(tol, targets, check_every, batch)
+        require_one_sided(self.b_lower)
+        start = time.perf_counter()
+        _reset_curves(self)
+
+        record = _batch_recorder(self, batch, ground_truth, ground_truth_indices, mean=_mean_each)
+        x, y_eq, y_ineq, info = _dga_batch_run(self, costs, nb_iter, record, None, None, max_time, lower_bounds, upper_bounds, None, stop=stop)
+        self.dual_multipliers = (y_eq, y_ineq)
+        self.dual_lower_bounds = info["lower_bound"].copy()
+        self.stop_info = info
+        elapsed = time.perf_counter() - start
+        return (x, elapsed) if get_timing else x
+
 
 def solve_many(lps, method="chambolle_pock_ppd", get_timing=True, nb_iter=10000, max_time=None, nb_iter_plot=10):
     """Solve a list of ``SparseLP`` objects whose matrices differ in ONE call, every LP one workgroup on the GPU (extension: the

@@ -27,6 +27,26 @@ def check_costs(costs, n):
     return costs, costs.shape[0]
 
 
+def check_targets(targets, batch):
+    """The cut-offs of a per-instance bound test as a contiguous float64 array of shape ``(batch,)``: ``targets`` is a real scalar
+    (the same cut-off for every instance) or has shape ``(batch,)``; ``+inf`` means that an instance has none, a NaN or ``-inf`` is
+    refused.  None stays None (no bound test)."""
+    if targets is None:
+        return None
+    try:
+        t = np.asarray(targets)
+        if t.dtype == bool or t.dtype.kind not in "iuf":
+            raise TypeError
+        t = t.astype(np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"targets must be a real number or an array of {batch} real numbers, not {targets!r}") from None
+    if t.shape not in ((), (batch,)):
+        raise ValueError(f"targets has shape {t.shape}: expected a scalar or ({batch},), one cut-off per instance")
+    if np.any(np.isnan(t)) or np.any(t == -np.inf):
+        raise ValueError("targets holds a NaN or -inf: a cut-off is a number or +inf (no cut-off for that instance)")
+    return _lib.f64(np.broadcast_to(t, (batch,)).copy())
+
+
 def require_one_sided(b_lower, prefix=""):
     """Dual gradient ascent takes ``a x <= b_upper`` only (the reference's assert, DualGradientAscent.py:82)."""
     if b_lower is not None and np.size(b_lower) > 0 and np.max(b_lower) != -np.inf:

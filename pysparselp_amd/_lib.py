@@ -1,4 +1,5 @@
-"""ctypes binding of libslp_hip.so (include/slp_hip.h, include/slp_hip_ext.h and include/slp_hip_ext_admm_batch.h).
+"""ctypes binding of libslp_hip.so (include/slp_hip.h, include/slp_hip_ext.h, include/slp_hip_ext_admm_batch.h and
+include/slp_hip_ext_dga_batch.h).
 
 The library is the only execution path: if it is missing, cannot be loaded, or
 finds no HIP device, every solver entry point raises -- there is no CPU
@@ -267,6 +268,14 @@ _EXT_ADMM_BATCH_SIGNATURES = {
 
 EXT_ADMM_BATCH_SYMBOLS = tuple(_EXT_ADMM_BATCH_SIGNATURES)
 
+# name -> (restype, argtypes); mirrors include/slp_hip_ext_dga_batch.h (which slp_hip_ext.h includes) one to one
+_EXT_DGA_BATCH_SIGNATURES = {
+    "slp_batch_dga_set_stop": (c_int, [c_vp, c_dbl, c_vp, c_i64]),
+    "slp_batch_dga_stop_state": (c_int, [c_vp] * 5),
+}
+
+EXT_DGA_BATCH_SYMBOLS = tuple(_EXT_DGA_BATCH_SIGNATURES)
+
 # int fn(double *buf, int64_t count, int op, void *user): the host all-reduce of slp_comm_init_host
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, ctypes.POINTER(c_dbl), c_i64, c_int, c_vp)
 
@@ -289,7 +298,8 @@ def load():
         lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     except OSError as e:
         raise SlpError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_EXT_ADMM_BATCH_SIGNATURES.items()):
+    for name, (res, args) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_EXT_ADMM_BATCH_SIGNATURES.items())
+                              + list(_EXT_DGA_BATCH_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -9,7 +9,7 @@
 // of n, which is what the segmented sort needs.  A launch is a grid of (the single solver's blocks, B): blockIdx.y is the
 // instance, and the kernel body runs on that instance's segments exactly as the single solver's kernel runs on its vectors.
 // One DgaCtl per instance carries the step, g.b, the min ratio, the draws consumed, `active`, nb, the sticky flags and `frozen`.
-// Nothing is read back inside slp_batch_dga_iterate.
+// Nothing is read back inside slp_batch_dga_iterate (with a stopping test: the controls once, before its first launch).
 //
 // One iteration = column pass (both partial sums of K^T y, c_bar and the dual argmin, fused), row pass (K x), then per block of
 // rows: gradient pass with its 256 partial results, the block's scalars, d = K^T g, the search, the update.  The search is
@@ -22,6 +22,27 @@
 // holds the window min(consumed) .. of that stream and the host keeps it two draws per iteration ahead of max(consumed).
 // An instance whose start has dual energy -inf (what makes the single solve return at once, :133-139) is frozen: its x stays the
 // start's dual argmin, its y the start, and the others go on.
+//
+// Stopping per instance (slp_batch_dga_set_stop, include/slp_hip_ext_dga_batch.h; off after create).  Iterations t count from 1
+// over the life of the state.  At the end of an iteration t with t % check_every == 0 -- the host knows them from `iters`, the
+// iterations in between are launched as without the test -- every instance that is neither frozen nor stopped evaluates
+//   step_t  = max |y_t - y_{t-1}| over its m multipliers, as np.max (a NaN stays), the inequality part after its clamp, 0 from a
+//             kind of rows whose block predicate was off: the update pass of a check iteration (k_dgab_update_step) reduces it
+//             per workgroup, with ordinary stores into slots of its own, for both blocks of rows;
+//   bound_t = the dual energy of y_t, only when cut-offs were given: one column pass over the live instances into the report's
+//             buffers (the instance's own x and c_bar stay), then the report's two reductions without the K x product and the
+//             violations (dga_energy_x_body, the y . b chain of dga_energy_y_body<false>) and, by one lane, the report's
+//             sequential sum of the 256 partial results (dga_bound_finish): bit for bit column 0 of slp_batch_dga_report;
+// and stops iff step_t <= tol (tol >= 0) or bound_t >= targets[k] (targets[k] < +inf) -- never on a NaN, nor while its sticky
+// DGA_NAN bit is up.  k_dgab_decide, one workgroup per instance, folds the slots, writes the instance's record (DgabStop, an
+// array of its own beside DgaCtl, whose layout the single and the list solver share: stopping iteration, reason, last evaluated
+// step and bound) and retires the instance by the second non-zero value of DgaCtl::frozen, kDgaStopped: every kernel here
+// tests that field for truth, so a stopped instance runs no column or row pass, has an empty sort segment, does no search and no
+// update, and the hot kernels are those of the state without a test.  slp_batch_dga_frozen reports the value 1 only.  A stopped
+// instance keeps y_t, the x and c_bar of the top of iteration t, its draws taken and its flags.  It is no reader of the stream of
+// draws any more (slp_dga_draws.h), so it cannot be resumed: no call clears the mark.  On a state that was ever armed
+// slp_batch_dga_iterate first reads the controls (one synchronising read) and launches nothing, leaving `iters`, when no instance
+// moves; nothing else is read back, so a stopping iteration does not depend on how a run is split into calls.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -30,11 +51,21 @@
 
 #include "slp_common.h"
 #include "slp_kernels.h"
+#include "slp_many.h"
 #include "slp_dga_shared.h"
+#include "../../include/slp_hip_ext_dga_batch.h"
 
 using namespace slp;
 
 namespace {
+
+// the stopping test's record of an instance
+struct DgabStop {
+    i64 done;       // its stopping iteration, 0 while it is not stopped
+    double step;    // the last evaluated max |y_t - y_{t-1}|, +inf before the first test
+    double bound;   // the last evaluated dual energy, -inf before the first
+    i32 reason, pad;   // bit 0: the step met tol, bit 1: the bound met the cut-off; 0 while it is not stopped
+};
 
 // column pass: one lane per (column j, instance): the two masked sums of K^T y in storage order (the single solver's two
 // SEQUENTIAL products over y with the other kind of rows set to 0.0), c_bar = (c + s_eq) + s_ineq, x = the dual argmin
@@ -114,6 +145,95 @@ __global__ void k_dgab_update(i64 m, i64 r0, i64 r1, int ineq, const DgaCtl *__r
     const double t = ctl[inst].t;
     for (i64 i = r0 + (i64)blockIdx.x * blockDim.x + threadIdx.x; i < r1; i += (i64)gridDim.x * blockDim.x)
         y[inst * m + i] = dga_update_y(y[inst * m + i], t, g[inst * m + i], ineq);
+}
+
+// a workgroup's nan-max of one value per lane, valid in thread 0.  red: kBlock / kWave doubles.  Two barriers.
+__device__ __forceinline__ double dgab_block_nanmax(double v, double *red) {
+    v = many_wave_nanmax(v);
+    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x == 0) {
+        r = red[0];
+        for (int w = 1; w < kBlock / kWave; ++w) r = nan_max(r, red[w]);
+    }
+    __syncthreads();
+    return r;
+}
+
+// k_dgab_update of a check iteration: the same update, and the workgroup's max |y_new - y_old| into its slot `off + blockIdx.x` of
+// the instance's `parts` slots; 0.0 from an instance whose block predicate is off.  Frozen and stopped instances write nothing:
+// k_dgab_decide does not look at their slots.
+__global__ __launch_bounds__(kBlock) void k_dgab_update_step(i64 m, i64 r0, i64 r1, int ineq, const DgaCtl *__restrict__ ctl,
+                                                             const double *__restrict__ g, double *__restrict__ y,
+                                                             double *__restrict__ step_part, int parts, int off) {
+    __shared__ double red[kBlock / kWave];
+    const i64 inst = blockIdx.y;
+    if (ctl[inst].frozen) return;
+    double dy = 0.0;
+    if (ctl[inst].active) {
+        const double t = ctl[inst].t;
+        for (i64 i = r0 + (i64)blockIdx.x * blockDim.x + threadIdx.x; i < r1; i += (i64)gridDim.x * blockDim.x) {
+            const double yo = y[inst * m + i], yn = dga_update_y(yo, t, g[inst * m + i], ineq);
+            y[inst * m + i] = yn;
+            dy = nan_max(dy, fabs(yn - yo));
+        }
+    }
+    dy = dgab_block_nanmax(dy, red);
+    if (threadIdx.x == 0) step_part[inst * parts + off + blockIdx.x] = dy;
+}
+
+// ---- the stopping test: the bound of the live instances, then the decision --------------------------------------------------------
+
+// k_dgab_energy_x / the y . b of k_dgab_energy_y over the instances that still move
+__global__ __launch_bounds__(kBlock) void k_dgab_bound_x(i64 n, const double *__restrict__ cbar, const double *__restrict__ lb, i64 lb_stride,
+                                                         const double *__restrict__ ub, i64 ub_stride, const DgaCtl *__restrict__ ctl,
+                                                         double *__restrict__ part) {
+    __shared__ double red[kBlock / kWave];
+    const i64 inst = blockIdx.y;
+    if (ctl[inst].frozen) return;
+    dga_energy_x_body(n, cbar + inst * n, lb + inst * lb_stride, ub + inst * ub_stride, part + inst * 4 * kDgaParts, red);
+}
+
+__global__ __launch_bounds__(kBlock) void k_dgab_bound_y(i64 m, i64 m_eq, const double *__restrict__ y, const double *__restrict__ b,
+                                                         const DgaCtl *__restrict__ ctl, double *__restrict__ part) {
+    __shared__ double red[kBlock / kWave];
+    const i64 inst = blockIdx.y;
+    if (ctl[inst].frozen) return;
+    dga_energy_y_body<false>(m, m_eq, y + inst * m, b, nullptr, part + inst * 4 * kDgaParts + kDgaParts, red);
+}
+
+// One workgroup per instance, at the end of check iteration `done`: the step from the instance's slots, the bound from the 4
+// kDgaParts partial results (targets != NULL: the bound is armed), the record, and the mark that retires the instance.
+__global__ __launch_bounds__(kBlock) void k_dgab_decide(DgaCtl *__restrict__ ctl, DgabStop *__restrict__ rec, i64 done, double tol,
+                                                        const double *__restrict__ targets, const double *__restrict__ step_part,
+                                                        int parts, const double *__restrict__ rpart) {
+    __shared__ double red[kBlock / kWave];
+    __shared__ double h[4 * kDgaParts];
+    const i64 inst = blockIdx.x;
+    if (ctl[inst].frozen) return;
+    double dy = 0.0;
+    for (int i = (int)threadIdx.x; i < parts; i += kBlock) dy = nan_max(dy, step_part[inst * parts + i]);
+    const double step = dgab_block_nanmax(dy, red);
+    if (targets) {
+        for (int i = (int)threadIdx.x; i < 4 * kDgaParts; i += kBlock) h[i] = rpart[inst * 4 * kDgaParts + i];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    int reason = 0;
+    const bool sound = !(ctl[inst].flags & DGA_NAN);   // an instance that has met a NaN breakpoint or step certifies nothing
+    rec[inst].step = step;
+    if (sound && tol >= 0.0 && step <= tol) reason |= 1;   // false for a NaN
+    if (targets) {
+        const double bound = dga_bound_finish(h), target = targets[inst];
+        rec[inst].bound = bound;
+        if (sound && target < __builtin_inf() && bound >= target) reason |= 2;   // false for a NaN
+    }
+    if (reason) {
+        rec[inst].done = done;
+        rec[inst].reason = reason;
+        ctl[inst].frozen = kDgaStopped;
+    }
 }
 
 // ---- the search, general form: grids of (.., B) over B segments of n ---------------------------------------------------------
@@ -239,6 +359,13 @@ struct slp_batch_dga {
     DevBuf<double> rnd;
     DgaDrawWindow draws;   // the host's view of rnd (slp_dga_draws.h)
     i64 iters = 0;
+    // the stopping test: off while !armed.  Its buffers are allocated at the first arming.
+    bool armed = false, ever_armed = false, has_targets = false;
+    double tol = -1.0;      // < 0: the step does not stop
+    i64 check_every = 1;
+    int step_parts_ineq = 0, step_parts_eq = 0;   // workgroups (= step slots) of the update pass per block of rows
+    DevBuf<DgabStop> stop;
+    DevBuf<double> targets, step_part;
     StageTimer timer;
 };
 
@@ -316,7 +443,8 @@ void dgab_argmin(slp_batch_dga *s, double *cbar, double *x, int skip_frozen) {
     SLP_HIP(hipGetLastError());
 }
 
-void dgab_block(slp_batch_dga *s, i64 r0, i64 r1, int ineq) {
+// `check`: the update pass of a check iteration, which also leaves the step in the block's slots
+void dgab_block(slp_batch_dga *s, i64 r0, i64 r1, int ineq, bool check) {
     hipStream_t st = ctx().stream;
     const CsrDev &at = s->k->at;
     const i64 n = s->n, m = s->m, B = s->B;
@@ -370,12 +498,33 @@ void dgab_block(slp_batch_dga *s, i64 r0, i64 r1, int ineq) {
         SLP_HIP(hipGetLastError());
         s->timer.mark(ST_REST);
     }
-    hipLaunchKernelGGL(k_dgab_update, grid2(r1 - r0, B), dim3(kBlock), 0, st, m, r0, r1, ineq, s->ctl.p, s->g.p, s->y.p);
+    if (check)
+        hipLaunchKernelGGL(k_dgab_update_step, grid2(r1 - r0, B), dim3(kBlock), 0, st, m, r0, r1, ineq, s->ctl.p, s->g.p, s->y.p, s->step_part.p,
+                           s->step_parts_ineq + s->step_parts_eq, ineq ? 0 : s->step_parts_ineq);
+    else
+        hipLaunchKernelGGL(k_dgab_update, grid2(r1 - r0, B), dim3(kBlock), 0, st, m, r0, r1, ineq, s->ctl.p, s->g.p, s->y.p);
     SLP_HIP(hipGetLastError());
     s->timer.mark(ST_REST);
 }
 
-void dgab_iteration(slp_batch_dga *s) {
+// behind the updates of check iteration `done`: the bound of the live instances when cut-offs were given, then the decision
+void dgab_check(slp_batch_dga *s, i64 done) {
+    hipStream_t st = ctx().stream;
+    const unsigned int ub = (unsigned int)s->B;
+    if (s->has_targets) {
+        dgab_argmin(s, s->rcbar.p, s->rx.p, 1);
+        s->timer.mark(ST_PRODUCTS);
+        hipLaunchKernelGGL(k_dgab_bound_x, dim3(kDgaParts, ub), dim3(kBlock), 0, st, s->n, s->rcbar.p, s->lb.p, s->lb_stride, s->ub.p, s->ub_stride,
+                           s->ctl.p, s->rpart.p);
+        hipLaunchKernelGGL(k_dgab_bound_y, dim3(kDgaParts, ub), dim3(kBlock), 0, st, s->m, s->m_eq, s->y.p, s->b.p, s->ctl.p, s->rpart.p);
+    }
+    hipLaunchKernelGGL(k_dgab_decide, dim3(ub), dim3(kBlock), 0, st, s->ctl.p, s->stop.p, done, s->tol, s->has_targets ? s->targets.p : nullptr,
+                       s->step_part.p, s->step_parts_ineq + s->step_parts_eq, s->rpart.p);
+    SLP_HIP(hipGetLastError());
+    s->timer.mark(ST_REST);
+}
+
+void dgab_iteration(slp_batch_dga *s, bool check = false) {
     const CsrDev &a = s->k->a;
     s->timer.mark(-1);
     dgab_argmin(s, s->cbar.p, s->x.p, 1);
@@ -383,17 +532,17 @@ void dgab_iteration(slp_batch_dga *s) {
                        0, s->ax.p);
     SLP_HIP(hipGetLastError());
     s->timer.mark(ST_PRODUCTS);
-    if (s->m > s->m_eq) dgab_block(s, s->m_eq, s->m, 1);
-    if (s->m_eq > 0) dgab_block(s, 0, s->m_eq, 0);
+    if (s->m > s->m_eq) dgab_block(s, s->m_eq, s->m, 1, check);
+    if (s->m_eq > 0) dgab_block(s, 0, s->m_eq, 0, check);
+    if (check) dgab_check(s, s->iters + 1);
 }
 
 // the controls of all instances; refreshes the bound on the draws taken
 void dgab_read_ctl(slp_batch_dga *s, std::vector<DgaCtl> &h) {
     h.resize((size_t)s->B);
     s->ctl.download(h.data(), (size_t)s->B);
-    unsigned long long mx = 0;
-    for (const DgaCtl &c : h) mx = std::max(mx, c.consumed);
-    s->draws.observe(mx);
+    // a frozen instance and a stopped one stand still: no readers of the stream (slp_dga_draws.h)
+    s->draws.observe(dga_furthest_reader(h.size(), [&](size_t k) { return !h[k].frozen; }, [&](size_t k) { return (uint64_t)h[k].consumed; }));
 }
 
 void dgab_report(slp_batch_dga *s, double *out) {
@@ -514,8 +663,13 @@ int slp_batch_dga_sort(const slp_batch_dga *s) { return s ? (s->fused ? 0 : (s->
 int slp_batch_dga_iterate(slp_batch_dga *s, int64_t k) {
     SLP_API_INT({
         SLP_REQUIRE(s && k >= 0, "slp_batch_dga_iterate: bad arguments");
+        if (s->ever_armed) {   // when every instance is stopped or frozen nothing is launched and the count of iterations stays
+            std::vector<DgaCtl> h;
+            dgab_read_ctl(s, h);
+            if (std::all_of(h.begin(), h.end(), [](const DgaCtl &c) { return c.frozen != 0; })) return 0;
+        }
         for (i64 it = 0; it < k && s->draws.reserve(1); ++it) {   // at most two tie draws per instance and iteration
-            dgab_iteration(s);
+            dgab_iteration(s, s->armed && (s->iters + 1) % s->check_every == 0);
             ++s->iters;
         }
     })
@@ -546,7 +700,7 @@ int slp_batch_dga_frozen(slp_batch_dga *s, int32_t *out) {
         SLP_REQUIRE(s && out, "slp_batch_dga_frozen: NULL argument");
         std::vector<DgaCtl> h;
         dgab_read_ctl(s, h);
-        dga_frozen_out(h, out);
+        for (size_t k = 0; k < h.size(); ++k) out[k] = h[k].frozen == 1;   // (kDgaStopped: retired by the stopping test, not frozen)
     })
 }
 
@@ -562,6 +716,51 @@ int slp_batch_dga_report(slp_batch_dga *s, double *out) {
     SLP_API_INT({
         SLP_REQUIRE(s && out, "slp_batch_dga_report: NULL argument");
         dgab_report(s, out);
+    })
+}
+
+int slp_batch_dga_set_stop(slp_batch_dga *s, double tol, const double *targets, int64_t check_every) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_batch_dga_set_stop: NULL handle");
+        SLP_REQUIRE(std::isfinite(tol), "slp_batch_dga_set_stop: tol must be finite (tol < 0 turns the step test off)");
+        const bool arm = tol >= 0.0 || targets;
+        SLP_REQUIRE(!arm || check_every >= 1, "slp_batch_dga_set_stop: check_every must be at least 1");
+        const size_t sb = (size_t)s->B;
+        for (size_t k = 0; targets && k < sb; ++k)
+            SLP_REQUIRE(targets[k] == targets[k] && targets[k] != -INFINITY,
+                        "slp_batch_dga_set_stop: a cut-off is NaN or -inf (+inf: the instance has none)");
+        SLP_HIP(hipStreamSynchronize(ctx().stream));
+        if (arm && !s->stop.p) {   // the records and the step slots, at the first arming
+            const std::vector<DgabStop> rec(sb, DgabStop{0, __builtin_inf(), -__builtin_inf(), 0, 0});
+            s->stop.upload(rec.data(), sb);
+            s->step_parts_ineq = s->m > s->m_eq ? grid_for(s->m - s->m_eq, kBlock) : 0;
+            s->step_parts_eq = s->m_eq > 0 ? grid_for(s->m_eq, kBlock) : 0;
+            s->step_part.alloc((size_t)(s->step_parts_ineq + s->step_parts_eq) * sb);
+            s->ever_armed = true;
+        }
+        if (targets) s->targets.upload(targets, sb);
+        // the marks stay: a stopped instance cannot be resumed
+        s->armed = arm;
+        s->has_targets = targets != nullptr;
+        s->tol = tol < 0.0 ? -1.0 : tol;
+        if (arm) s->check_every = check_every;
+    })
+}
+
+int slp_batch_dga_stop_state(slp_batch_dga *s, int64_t *iterations, int32_t *reason, double *step, double *bound) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_batch_dga_stop_state: NULL handle");
+        std::vector<DgaCtl> h;
+        dgab_read_ctl(s, h);   // synchronises
+        std::vector<DgabStop> rec((size_t)s->B, DgabStop{0, __builtin_inf(), -__builtin_inf(), 0, 0});
+        if (s->stop.p) s->stop.download(rec.data(), rec.size());
+        for (size_t k = 0; k < rec.size(); ++k) {
+            const bool stopped = h[k].frozen == kDgaStopped;
+            if (iterations) iterations[k] = stopped ? rec[k].done : (h[k].frozen ? 0 : s->iters);   // 0 for a frozen instance
+            if (reason) reason[k] = stopped ? rec[k].reason : 0;
+            if (step) step[k] = rec[k].step;
+            if (bound) bound[k] = rec[k].bound;
+        }
     })
 }
 

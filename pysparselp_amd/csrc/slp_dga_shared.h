@@ -34,8 +34,11 @@ struct DgaCtl {
     int active;                    // the block's predicate: any g < 0 / any g != 0
     int nb;                        // breakpoints of the search in flight (columns with d_j != 0)
     unsigned int flags;            // sticky, DGA_*
-    int frozen;                    // batch only: the instance's start is dual infeasible (energy -inf), it stands still
+    int frozen;                    // batch and list: 1 = the start is dual infeasible (energy -inf), it stands still; batch only:
+                                   // kDgaStopped = its stopping test has retired the instance (every kernel tests the field for truth)
 };
+
+constexpr int kDgaStopped = 2;
 
 struct DgaLoadPlain {   // written by an earlier launch
     __device__ __forceinline__ double operator()(const double *p) const { return *p; }
@@ -507,37 +510,54 @@ __device__ __forceinline__ void dga_energy_x_body(i64 n, const double *__restric
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
-// per workgroup: y . b, the largest violation (a_i x - b_i on inequality rows, |a_i x - b_i| on equality rows) and their sum
+// per workgroup: y . b and, with VIOL, the largest violation (a_i x - b_i on inequality rows, |a_i x - b_i| on equality rows) and
+// their sum; without VIOL (the bound alone: the batch's stopping test) `ax` is not looked at and only the first slot is written
+template <bool VIOL = true>
 __device__ __forceinline__ void dga_energy_y_body(i64 m, i64 m_eq, const double *__restrict__ y, const double *__restrict__ b,
                                                   const double *__restrict__ ax, double *__restrict__ part, double *red) {
     double yb = 0.0, mx = -__builtin_inf(), sum = 0.0;
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (i64)gridDim.x * blockDim.x) {
         if (y[i] != 0.0) yb += y[i] * b[i];
-        double r = ax[i] - b[i];
-        if (i < m_eq) r = fabs(r);
-        mx = (r > mx) ? r : mx;
-        if (r > 0.0) sum += r;
+        if (VIOL) {
+            double r = ax[i] - b[i];
+            if (i < m_eq) r = fabs(r);
+            mx = (r > mx) ? r : mx;
+            if (r > 0.0) sum += r;
+        }
     }
     yb = block_reduce<false>(yb, red);
-    mx = block_reduce<true>(mx, red);
-    sum = block_reduce<false>(sum, red);
+    if (VIOL) {
+        mx = block_reduce<true>(mx, red);
+        sum = block_reduce<false>(sum, red);
+    }
     if (threadIdx.x == 0) {
         part[3 * blockIdx.x] = yb;
-        part[3 * blockIdx.x + 1] = mx;
-        part[3 * blockIdx.x + 2] = sum;
+        if (VIOL) {
+            part[3 * blockIdx.x + 1] = mx;
+            part[3 * blockIdx.x + 2] = sum;
+        }
     }
+}
+
+// the dual energy from the kDgaParts partial results of both passes (h[0 .. parts): energy_x, h[parts + 3 i]: the y . b of
+// energy_y), each summed in order: the report's on the host and, for the batch's stopping test, one lane's on the device
+__host__ __device__ inline double dga_bound_finish(const double *h) {
+    double e = 0.0, yb = 0.0;
+    for (int i = 0; i < kDgaParts; ++i) {
+        e += h[(size_t)i];
+        yb += h[(size_t)(kDgaParts + 3 * i)];
+    }
+    return e - yb;
 }
 
 // host: the kDgaParts partial results of both passes (h[0 .. parts): energy_x, h[parts .. 4 parts): energy_y) in order
 inline void dga_report_finish(const double *h, bool has_rows, double out[3]) {
-    double e = 0.0, yb = 0.0, mx = -__builtin_inf(), sum = 0.0;
+    double mx = -__builtin_inf(), sum = 0.0;
     for (int i = 0; i < kDgaParts; ++i) {
-        e += h[(size_t)i];
-        yb += h[(size_t)(kDgaParts + 3 * i)];
         mx = std::max(mx, h[(size_t)(kDgaParts + 3 * i + 1)]);
         sum += h[(size_t)(kDgaParts + 3 * i + 2)];
     }
-    out[0] = e - yb;
+    out[0] = dga_bound_finish(h);
     out[1] = has_rows ? mx : 0.0;
     out[2] = sum;
 }
