@@ -2,6 +2,7 @@
 // the format itself is described at the top of slp_tall.hip.
 #pragma once
 #include "slp_common.h"
+#include "slp_tall_item.h"
 
 namespace slp {
 
@@ -10,9 +11,10 @@ constexpr int kTallT = 1024;       // threads per workgroup = lanes a cell's row
 constexpr int kTallSlots = 8;      // list positions per packet
 constexpr int kTallDepth = 4;      // packets of payload in flight per lane; headers run 2 x this ahead
 constexpr int kTallBuckets = 6;    // rows are ordered by min(entries in the cell, 6), descending
-constexpr int kTallIdBits = 11, kTallColBits = 12, kTallRowBits = 14;
+// (kTallIdBits = 11, kTallColBits = 12, kTallRowBits = 14 and the stored item: slp_tall_item.h)
 constexpr int kTallCellShift = kTallIdBits + kTallColBits + kTallRowBits;  // sort key: cell | row | column | id
 static_assert(kTallBuckets * 32 == 3 * kWave, "k_tall_build scans the (count, bank class) buckets three per lane of one wave");
+static_assert(1 + kTallDictMax + kTallRmax <= (1 << kTallRowBits), "an item's sum field: scratch cell, value table, the block's rows (slp_tall_item.h)");
 static_assert(kTallRmax + 1 < (1 << kTallRowBits) && kTallC == (1 << kTallColBits) && kTallDictMax == (1 << kTallIdBits), "tall geometry");
 static_assert(kTallT == kTallPlanLanes && kTallC == kTallCmax, "the planner's constants (slp_tall_plan.h)");
 // LDS of the product kernel -- sums (+ the scratch cell) + value table + two x-tiles -- with a strip-range split; every other

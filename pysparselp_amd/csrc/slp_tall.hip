@@ -10,10 +10,14 @@
 // double-buffered), so that a cell holds ~4000 entries although a row has < 1.  R, C and the LDS they share with the value
 // table are chosen together (slp_tall_plan.h): 13021 rows (102 KB) and 3072 columns (48 KB) at that density.
 //
-//   item (5 bytes)  = value id (11 bits) | column inside the strip (12 bits) << 11 | (local row + 1) (14 bits) << 23
-//                     -- self-describing: no per-row metadata, rows without entries in a cell cost nothing; row field 0 is
-//                     the product kernel's scratch cell: a skip item, and the zero word a lane outside a slot loads, need
-//                     no predicate anywhere
+//   item (5 bytes)  = value id (11 bits) << 3 | column inside the strip (12 bits) << 14 | SUM FIELD (14 bits): low 6 bits << 26,
+//                     upper 8 bits in the fifth byte -- every field where the product kernel's LDS byte address wants it
+//                     (slp_tall_item.h: packing and decoding, one text for builder and kernel).  The sum field is the index of the
+//                     row's running sum among the doubles of the kernel's LDS: 1 + capacity of the value table + local row (the
+//                     scratch cell and the table lie in front of the sums).  Self-describing: no per-row metadata, rows
+//                     without entries in a cell cost nothing; sum field 0 is the product kernel's scratch cell: a skip item,
+//                     and the zero word a lane outside a slot loads, need no predicate anywhere.
+//                     With fp64 values (4 bytes + the value in a parallel array): sum field << 3 | column << 17.
 //   cell            = the items of its non-empty rows, every row handed WHOLE to one of the 1024 lanes (rows sorted by
 //                     their entry count, dealt round by round: lane p takes sorted positions p, p + 1024, ...), so a
 //                     lane's list is its rows' entries in storage order and list lengths never increase with p
@@ -238,9 +242,10 @@ __device__ __forceinline__ i64 tall_range_of(i64 t, i64 T, int S) {  // the stri
     return s;
 }
 
-// DICT: 5-byte items (value id inside); !DICT: 4-byte items (column | row << 12) + the fp64 value in a parallel array at the same offsets.
+// DICT: 5-byte items (value id inside); !DICT: 4-byte items (sum field | column) + the fp64 value in a parallel array at the same offsets
+// (slp_tall_item.h).  sum0: the sum field of local row 0.
 template <bool DICT>
-__global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int C, i64 ncell, const unsigned long long *__restrict__ keys,
+__global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int C, unsigned int sum0, i64 ncell, const unsigned long long *__restrict__ keys,
                                                        const double *__restrict__ svals, const i64 *__restrict__ cellptr, TallScan sc,
                                                        i64 cap_w, i64 cap_p, TallPkt *__restrict__ sdir,
                                                        unsigned int *__restrict__ spay, double *__restrict__ spayv) {
@@ -671,12 +676,17 @@ __global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int 
                     if ((unsigned)p < wd[j]) {
                         unsigned int item = 0u, hib = 0u;
                         if (have >> j & 1u) {
-                            const unsigned int r1 = ((unsigned int)(key[j] >> (kTallIdBits + kTallColBits)) & ((1u << kTallRowBits) - 1)) + 1u;  // local row + 1
+                            // the sum field: where the local row's running sum lies in the product kernel's LDS (sum0: behind the
+                            // scratch cell and the table)
+                            const unsigned int r1 = ((unsigned int)(key[j] >> (kTallIdBits + kTallColBits)) & ((1u << kTallRowBits) - 1)) + sum0;
+                            // the key's fields go where the kernel's LDS addresses want them (slp_tall_item.h)
+                            const unsigned int cl = (unsigned int)(key[j] >> kTallIdBits) & (kTallC - 1);
                             if (DICT) {
-                                item = ((unsigned int)key[j] & ((1u << (kTallIdBits + kTallColBits)) - 1)) | ((r1 & 0x1ffu) << 23);
-                                hib = r1 >> 9;
+                                const TallItem it = tall_item_encode((unsigned int)key[j] & ((1u << kTallIdBits) - 1), cl, r1);
+                                item = it.word;
+                                hib = it.fifth;
                             } else {
-                                item = ((unsigned int)(key[j] >> kTallIdBits) & (kTallC - 1)) | (r1 << kTallColBits);
+                                item = tall_item64_encode(cl, r1);
                             }
                         }
                         base[so + p] = item;
@@ -848,6 +858,10 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
                 "tall_build: the planned geometry does not fit the LDS");
     const int R = plan.R, S = plan.S, Cw = plan.C;
     const i64 T = plan.T;
+    // where the items' sum fields start: behind the scratch cell and the table of plan.dcap entries (the copy keeps that capacity:
+    // tall_launch lays the kernel's LDS out with it, and the chunks fused into one launch all have the same)
+    const unsigned int sum0 = tall_item_sum_base(plan.dcap);
+    SLP_REQUIRE(sum0 + (unsigned int)R <= (1u << kTallRowBits), "tall_build: sum field");
     const i64 B = (nrowF + R - 1) / R, ncell = B * T, V = B * S;  // V workgroups: (row block, strip range)
     unsigned int cellbits = 1;
     while (((i64)1 << cellbits) < ncell) ++cellbits;
@@ -967,9 +981,9 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
         SLP_HIP(hipMemsetAsync(scan.p, 0, (2 * (size_t)ncell + 1) * sizeof(unsigned long long), st));  // levels and the ticket
         // as many workgroups as the chip holds at once (the kernel's LDS: one per compute unit); each takes cells until none is left
         const unsigned grid = (unsigned)std::min<i64>(ncell, (i64)ctx().num_cu);
-        if (dict) hipLaunchKernelGGL((k_tall_build<true>), dim3(grid), dim3(kTallT), 0, st, R, T, S, Cw, ncell, sorted.p, (const double *)nullptr, cellptr.p, sc,
+        if (dict) hipLaunchKernelGGL((k_tall_build<true>), dim3(grid), dim3(kTallT), 0, st, R, T, S, Cw, sum0, ncell, sorted.p, (const double *)nullptr, cellptr.p, sc,
                                      cap_w, cap_p, reinterpret_cast<TallPkt *>(sdir.p), spay.p, (double *)nullptr);
-        else hipLaunchKernelGGL((k_tall_build<false>), dim3(grid), dim3(kTallT), 0, st, R, T, S, Cw, ncell, sorted.p, svals.p, cellptr.p, sc,
+        else hipLaunchKernelGGL((k_tall_build<false>), dim3(grid), dim3(kTallT), 0, st, R, T, S, Cw, sum0, ncell, sorted.p, svals.p, cellptr.p, sc,
                                 cap_w, cap_p, reinterpret_cast<TallPkt *>(sdir.p), spay.p, spayv.p);
         hipLaunchKernelGGL(k_tall_streams, dim3(grid_for(V, kBlock)), dim3(kBlock), 0, st, V, T, S, cellptr.p, sc, ext.p);
         SLP_HIP(hipGetLastError());

@@ -2,12 +2,14 @@
 // capacity of the value table and where the three LDS areas of the product kernel (slp_tall_spmv.hip) lie.  Pure host code: no
 // HIP, no device buffer, no context, no environment -- the compute units and the SLP_TALL_* switches are arguments.
 //
-// The product kernel's workgroup keeps in LDS, in this order,
+// The product kernel's workgroup keeps in LDS
 //   the running sums of its R rows and the scratch cell      8 (R + 1) bytes, rounded up to 16
 //   the value table                                          8 dcap bytes  (dcap: D rounded up to 64 entries, then whatever the sums
 //                                                                           of the tallest planned block leave; 0 with fp64 items)
 //   two x-tiles                                              16 C bytes
-// and all of it has to fit 160 KB.  The per-cell frame of the kernel moves 8 C bytes of x for the R C density items of a cell,
+// and all of it has to fit 160 KB.  The tiles start at off_xt; inside the off_xt bytes in front of them the kernel puts the scratch
+// cell first, the table behind it and the sums behind the table (slp_tall_item.h: an item's sum field counts from LDS address 0) --
+// off_dv is the size of the sums' share, not where the table lies.  The per-cell frame of the kernel moves 8 C bytes of x for the R C density items of a cell,
 // 8 / (R density) bytes per item whatever C is: at a given cell size the tile's share falls with taller blocks on narrower
 // strips, so the table takes what its dictionary needs, not a fixed 16 KB, and C is any multiple of 256 (the item's 12-bit
 // column field needs C <= 4096).  The builder's workgroup needs 10 bytes per row beside kTallBuildFixed bytes of its own: that
@@ -52,7 +54,7 @@ struct TallPlan {
     int R = 0, C = 0, S = 1, dcap = 0;
     int64_t T = 0;             // strips
     int64_t total = 0;         // row blocks of all chunks together, when the chunk took its share of them (else 0)
-    int off_dv = 0, off_xt = 0, lds_bytes = 0;   // product kernel: byte offsets of the value table and the x-tiles, all of its LDS
+    int off_dv = 0, off_xt = 0, lds_bytes = 0;   // product kernel: bytes of the sums' share, byte offset of the x-tiles, all of its LDS
     int build_lds_bytes = 0;   // the builder's need at this R
 };
 

@@ -34,9 +34,15 @@ struct TallRegs {
 // of additions of the unchunked product, as the chunk-by-chunk launches formed it through `out`).
 // C: columns per strip = doubles of an x-tile: a run-time multiple of 256 up to 4096 (slp_tall_plan.h: the width whose cells
 // the kernel is predicted to walk fastest; items keep their 12-bit column field).
-// LDS: one dynamic block -- the running sums (from 0: the item path's addresses need no base), the value table from double
-// `odv`, the two x-tiles from double `oxt` (both even: 16-byte stores) -- laid out by the planner for the copy's R, dictionary
-// and C; the same for every workgroup of a launch.
+// LDS: one dynamic block of the size the planner laid out for the copy's R, dictionary and C (slp_tall_plan.h), the same for every
+// workgroup of a launch; inside it, from LDS address 0 (the kernel has no other LDS, checked once below):
+//   [scratch cell: 8 bytes] [value table: `dcap` doubles from byte 8] [running sums of the block's rows] ... [two x-tiles from double `oxt`]
+// An item's SUM FIELD is the index of its running sum among these doubles (1 + dcap + local row: the builder knows the table's
+// capacity), its fields are stored as byte offsets (slp_tall_item.h), so the address of a running sum is the field under a mask
+// with NO base and that of a value the field under a mask with the constant 8 in the instruction's offset; only the tile's base
+// (which alternates per cell) is a register.  With the sums first and the table behind them -- the order up to here -- the
+// table's base was one v_add_u32 per item: the sums are up to 104 KB, beyond the 16 bits of a DS offset, and as long as the
+// planner sizes both areas per copy only one of them can start at a fixed place.  Same bytes as the planner's budget: R is unchanged.
 // The tile's C / 2 16-byte pieces are dealt to the 1024 lanes in order: lane p carries piece p and, where the tile has it,
 // piece p + 1024 -- 4096 columns: two pieces on every lane; 3072: a second piece on the first 8 of the 16 waves; 2048 and
 // below: one piece on the first C / 2 lanes.  C / 2 is a multiple of 64, so either test is the same for a whole wave.
@@ -45,16 +51,22 @@ struct TallRegs {
 template <bool DICT, bool ACC, bool POW = false, int CT = 0>
 __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__restrict__ wgs, const double *__restrict__ dict_arg,
                                                       const double *__restrict__ x, double *__restrict__ out, double pw, const int cw,
-                                                      const int odv, const int oxt) {
+                                                      const int dcap, const int oxt) {
     const int C = CT ? CT : cw;
     constexpr int kDepth = DICT ? kTallDepth : 2;
-    // acc[0] is a scratch cell: the row field of an item is its local row + 1, and whatever is not a lane's item -- a slot
-    // beyond its list (the load past the buffer descriptor returns 0), a skip item -- decodes to row 0, value id 0, column 0
-    // and adds into the scratch cell: no predicate on the stores, none on the sums
+    // LDS address 0 is a scratch cell: whatever is not a lane's item -- a slot beyond its list (the load past the buffer
+    // descriptor returns 0), a skip item -- decodes to sum field 0, value id 0, column 0 and adds into the
+    // scratch cell: no predicate on the stores, none on the sums
     extern __shared__ __attribute__((aligned(16))) double tall_lds[];
-    double *const acc = tall_lds;
-    double *const dv = tall_lds + odv;
+    double *const dv = tall_lds + kTallItemTableByte / 8;
+    double *const acc = tall_lds + tall_item_sum_base(dcap);   // acc[r]: local row r
     double *const xt = tall_lds + oxt;                   // tile buffers at xt and xt + C
+    // the item path (consume()) works on LDS byte addresses (32-bit, address space 3)
+    typedef __attribute__((address_space(3))) double lds_double;
+    auto lds_at = [](unsigned int a) -> lds_double & { return *(lds_double *)(unsigned long long)a; };
+    const unsigned int lds0 = (unsigned int)(unsigned long long)(lds_double *)tall_lds;
+    if (lds0 != 0u) __builtin_trap();   // (the block's address is a link-time constant: this kernel declares no other LDS)
+    const unsigned int xtb = 8u * (unsigned int)oxt;
     const int p = threadIdx.x;
     // (wave-uniform by construction; told to the compiler, so that tests on it are scalar branches, not EXEC masks)
     const unsigned int wbase = (unsigned int)__builtin_amdgcn_readfirstlane(p & ~(kWave - 1));
@@ -66,7 +78,8 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
     // before it, launch by launch (the strip-range split takes it in k_tall_combine instead: its descriptors point into the
     // partial-sum array).  A template parameter: loads under a run-time condition in front of the pipeline made the compiler
     // wait for vmcnt(0) in the loop.
-    for (int r = p; r <= wg.nrows; r += kTallT) acc[r] = (ACC && r > 0) ? out[wg.row0 + r - 1] : 0.0;
+    if (p == 0) tall_lds[0] = 0.0;
+    for (int r = p; r < wg.nrows; r += kTallT) acc[r] = ACC ? out[wg.row0 + r] : 0.0;
   for (int seg = 0; seg < nseg; ++seg) {
     if (seg > 0) wg = wgs[(i64)seg * gridDim.x + v];
     if (DICT) {
@@ -219,40 +232,40 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
         // gathers queued behind 32 KB of stores): with the shorter item code the stores are out of the way before the first
         // gathers are ready to issue, and they no longer sit between a packet's items and the next packet's.
         stage_tile();
-        const double *__restrict__ tile = xt + cur;
+        // the tile's first byte: the scalar that an item's column `* 8` is added onto in one v_lshl_add_u32
+        const unsigned int tileb = xtb + 8u * (unsigned int)cur;
         // Four slots at a time: all twelve LDS reads (running sums, values, x) are issued together, the products do not
         // depend on the sums, and a sum that the lane has just updated is carried in a register (a lane's items of one
         // row are consecutive) -- the LDS latency is paid once per group, not once per item.  The additions of a row
         // stay one chain in list order.
         auto group = [&](const int k0) {
-            unsigned int w[4], hb[4], row[4];
+            unsigned int w[4], sa[4];   // sa: LDS address of the item's running sum (0: the scratch cell)
             double ar[4], pr[4], t[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 w[k] = g.lo[k0 + k];
-                if (DICT) {
-                    hb[k] = (g.hi[DICT ? (k0 >> 2) : 0] >> (8 * k)) & 0xffu;
-                    row[k] = (w[k] >> 23) | (hb[k] << 9);          // local row + 1; 0 = the scratch cell
-                } else {
-                    hb[k] = 0;
-                    row[k] = w[k] >> kTallColBits;
-                }
+                sa[k] = (DICT ? tall_item_sum_bytes(w[k], g.hi[DICT ? (k0 >> 2) : 0] >> (8 * k)) : tall_item64_sum_bytes(w[k]));
             }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) ar[k] = acc[row[k]];
+            for (int k = 0; k < 4; ++k) ar[k] = lds_at(sa[k]);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                pr[k] = DICT ? dv[w[k] & ((1u << kTallIdBits) - 1)] * tile[(w[k] >> kTallIdBits) & (kTallC - 1)]
-                             : (POW ? abs_pow(g.val[DICT ? 0 : k0 + k], pw) * 1.0 : g.val[DICT ? 0 : k0 + k]) * tile[w[k] & (kTallC - 1)];
+                // (the column stays an index in a register of its own -- the empty asm keeps the compiler from folding its `* 8` into
+                // the extraction as shift, mask and add: three instructions for v_bfe_u32 and v_lshl_add_u32)
+                unsigned int col = DICT ? tall_item_column(w[k]) : tall_item64_column(w[k]);
+                asm("" : "+v"(col));
+                const double xv = lds_at((col << 3) + tileb);
+                pr[k] = DICT ? lds_at(tall_item_value_bytes(w[k]) + kTallItemTableByte) * xv
+                             : (POW ? abs_pow(g.val[DICT ? 0 : k0 + k], pw) * 1.0 : g.val[DICT ? 0 : k0 + k]) * xv;
             }
             t[0] = ar[0] + pr[0];
 #pragma unroll
-            for (int k = 1; k < 4; ++k) t[k] = ((row[k] == row[k - 1]) ? t[k - 1] : ar[k]) + pr[k];
-            // Unconditional stores, no predicate at all: what is not this lane's item lands in the scratch cell acc[0] by its own
+            for (int k = 1; k < 4; ++k) t[k] = ((sa[k] == sa[k - 1]) ? t[k - 1] : ar[k]) + pr[k];
+            // Unconditional stores, no predicate at all: what is not this lane's item lands in the scratch cell by its own
             // decoding -- a packet's items stay ONE basic block, which the instruction scheduler may interleave with the loads of
             // the packets ahead (rounds 3-4: a branch, then a select, per store: 3 vector instructions per item more)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) acc[row[k]] = t[k];
+            for (int k = 0; k < 4; ++k) lds_at(sa[k]) = t[k];
         };
         group(0);   // (a wave without items -- nearly never -- reads cell 0 of the arrays and stores into the scratch cell)
         between();
@@ -292,7 +305,7 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
     __syncthreads();   // (every wave is done with this segment's tiles and value table)
   }
     // (S > 1: row0 points into the partial-sum array -- the sums of this strip range, added up in range order by k_tall_combine)
-    for (int r = p; r < wg.nrows; r += kTallT) out[wg.row0 + r] = acc[r + 1];
+    for (int r = p; r < wg.nrows; r += kTallT) out[wg.row0 + r] = acc[r];
 }
 
 
@@ -316,7 +329,7 @@ static void tall_launch(const StripJds &f, unsigned grid, int nseg, const TallWg
             SLP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kTallLdsBytes));
             raised = true;
         }
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTallT), (size_t)lay.lds_bytes, ctx().stream, nseg, wgs, dict, x, out, pw, lay.C, lay.off_dv / 8,
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTallT), (size_t)lay.lds_bytes, ctx().stream, nseg, wgs, dict, x, out, pw, lay.C, lay.dcap,
                            lay.off_xt / 8);
     };
     static bool raised[3] = {false, false, false};   // (per instantiation)

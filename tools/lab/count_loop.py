@@ -3,7 +3,7 @@
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-sched-strategy=max-ilp \
           --cuda-device-only -S pysparselp_amd/csrc/slp_tall_spmv.hip -o tall.s
-    python tools/lab/count_loop.py tall.s k_tall_spmvILb1ELb0ELb0ELi4096
+    python tools/lab/count_loop.py tall.s k_tall_spmvILb1ELb0ELb0ELi4096E
 
 The main loop is found by the compiler's own loop annotations of the basic blocks (blocks the layout moved behind the loop
 included): the largest loop that holds no inner loop of half its size (the loop over segments is around the packet loop).
@@ -17,7 +17,8 @@ import sys
 def main():
     path, key = sys.argv[1], sys.argv[2]
     lines = open(path).read().split("\n")
-    start = next(i for i, l in enumerate(lines) if l.startswith("_ZN") and key in l and l.split(":")[0].endswith("d"))
+    # (the symbol's own label line "<mangled name>:", whatever the kernel's argument list mangles to)
+    start = next(i for i, l in enumerate(lines) if l.startswith("_ZN") and key in l.split(":")[0] and ":" in l)
     end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith("s_endpgm"))
     # every basic block carries the compiler's loop annotation ("in Loop: Header=BBn_m Depth=d"; the header itself "Parent Loop"
     # / "This ... Loop Header" on its own line and the next): the main loop is the innermost-or-not loop with the most instructions
