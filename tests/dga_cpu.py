@@ -186,6 +186,43 @@ def dual_energy(c, a_eq, b_eq, a_ineq, b_upper, lb, ub, y_eq, y_ineq):
     return e
 
 
+def _device_parts(terms, parts=256, lanes=256):
+    """The ``parts`` partial results of dga_energy_x_body / dga_energy_y_body over one term per column / row: term ``j`` is lane
+    ``j % lanes`` of workgroup ``j // lanes`` (the grid-stride loop, at most one term per lane: ``acc = 0.0 + term``), a workgroup's
+    sum is block_reduce -- the 64-lane tree per wave, the four waves added in order.  Only the workgroups that hold a term are
+    formed: the others' lanes hold +0.0 and so do their sums, exactly."""
+    assert terms.ndim == 1 and terms.size <= parts * lanes and lanes == 4 * 64
+    used = -(-terms.size // lanes)
+    w = 0.0 + np.concatenate((terms, np.zeros(used * lanes - terms.size))).reshape(used, 4, 64)
+    for off in (32, 16, 8, 4, 2, 1):
+        w = w[:, :, :off] + w[:, :, off:2 * off]
+    w = w[:, :, 0]
+    return np.concatenate((((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3], np.zeros(parts - used)))
+
+
+def device_energy(c, a_eq, b_eq, a_ineq, b_upper, lb, ub, y_eq, y_ineq):
+    """``dual_energy`` in the device's order of sums (k_dgab_energy_x / k_dgab_energy_y + dga_bound_finish in
+    csrc/slp_dga_shared.h, the same text as the bound of the batch's stopping test): the column terms ``min(c_bar ub, c_bar lb)``
+    where ``c_bar != 0``, else 0; the row terms ``y_i b_i`` where ``y_i != 0``, else 0, over all rows, equalities first; each vector
+    dealt to 256 workgroups of 256 lanes (``_device_parts``); the 256 partial results of each pass summed in order from 0.0, and
+    ``e - yb``.  ``n, m <= 65536``: a lane holds at most one term, so neither the loop's order nor an FMA contraction can matter."""
+    c_bar, _ = dual_argmin(c, a_eq, a_ineq, lb, ub, y_eq, y_ineq)
+    y = np.asarray(y_eq, dtype=np.float64) if a_eq is not None else np.zeros(0)
+    b = np.asarray(b_eq, dtype=np.float64) if a_eq is not None else np.zeros(0)
+    if a_ineq is not None:
+        y, b = np.concatenate((y, y_ineq)), np.concatenate((b, b_upper))
+    assert c_bar.size <= 65536 and y.size <= 65536 and y.size == b.size
+    with np.errstate(invalid="ignore"):
+        u, low = c_bar * ub, c_bar * lb
+        cols = np.where(c_bar != 0, np.where(u < low, u, low), 0.0)   # (u < l) ? u : l
+        rows = np.where(y != 0, y * b, 0.0)
+        e = yb = 0.0
+        for pe, py in zip(_device_parts(cols), _device_parts(rows)):
+            e += pe
+            yb += py
+        return float(e - yb)
+
+
 def dga_cpu(c, a_eq, b_eq, a_ineq, b_upper, lb, ub, nb_max_iter, order="reference", block=64, keep=None, y_eq=None, y_ineq=None,
             on_search=None):
     """Runs ``nb_max_iter`` iterations; returns ``{it: (x, y_eq, y_ineq, draws)}`` for ``it`` in ``keep`` (default: the last one):

@@ -78,6 +78,20 @@ def test_the_restatement_on_hand_made_curves():
          [0.25, 4.0, 0.25, 9.0, nan, 1.0], [-inf, 3.0, -inf, -0.5, 4.0, nan], [1, 2, 1, 0, 0, 0])
     same(state([(0, 0.25, None, 1), (5, None, None, 1)], 10), [4, 10, 4, 10, 10, 10], [True, False, True, False, False, False],
          [0.25, 4.0, 0.25, 9.0, nan, 1.0], [-inf] * 6, [1, 0, 1, 0, 0, 0])
+    # three rules -- armed in mid-life, armed again with other cut-offs and another cadence, turned off: rule 1 (after 2, checks 3, 4)
+    # stops 0 and 2 by their step at 4 and records 1.0 for instance 1; rule 2 (after 4, cadence 2: the check 6) stops 1 by its new
+    # cut-off 3.0 and 5 by the looser tolerance 1.0; rule 3 (after 7) evaluates nothing, every record stays
+    t2 = np.array([inf, 3.0, inf, inf, inf, inf])
+    rules = [(2, 0.25, TARGETS, 1), (4, 1.0, t2, 2), (7, None, None, 1)]
+    same(state(rules, 2), [2] * 6, [False] * 6, [inf] * 6, [-inf] * 6, [0] * 6)
+    same(state(rules, 4), [4, 4, 4, 4, 4, 4], [True, False, True, False, False, False],
+         [0.25, 4.0, 0.25, 9.0, nan, 1.0], [-2.0, 1.0, 7.0, -6.0, -2.0, nan], [1, 0, 3, 0, 0, 0])
+    for total in (7, 10):
+        same(state(rules, total), [4, 6, 4, total, total, 6], [True, True, True, False, False, True],
+             [0.25, 4.0, 0.25, 9.0, nan, 1.0], [-2.0, 3.0, 7.0, -4.0, 0.0, nan], [1, 2, 3, 0, 0, 1])
+    # ... with a frozen instance in the middle: no iteration, no record, under every rule
+    got = state(rules, 10, frozen=[False, False, True, False, False, False])
+    assert (got[0][2], got[1][2], got[2][2], got[3][2], got[4][2]) == (0, False, inf, -inf, 0) and got[0][[0, 1, 5]].tolist() == [4, 6, 6]
     # a scalar cut-off is every instance's
     assert state([(0, None, 2.5, 1)], 10)[0].tolist() == [10, 6, 4, 10, 9, 10]
 

@@ -33,9 +33,23 @@ restated residual and step of one instance at a check iteration; ``stop_state`` 
 in mid-life, armed again and turned off, and every instance's ``x`` and ``lambda`` against the oracle's at its own count, bit for
 bit.  No instance is left out.
 
+``dga_batch_stop`` arms the per-instance stopping test of the batched dual gradient ascent (``DeviceDGABatch.set_stop`` /
+``stop_state``, ``dual_gradient_ascent_batch_until``) on batches of its own of 1 to 65 instances and one of 260 (at most nine distinct
+instances, cycled: identical data under different cut-offs; in every third batch one constructed frozen instance), on all three
+paths.  The yardstick is the CPU, not the unarmed device: the step curve from dga_cpu's multipliers and the bound curve from
+``dga_cpu.device_energy``, the report's order of sums restated in numpy.  The tolerance is the restated step of one instance at a
+check; the cut-offs are, per instance, none, the restated bound of its own curve at a check (``>=`` decides by equality), the next
+float above it, or one the curve never reaches.  Armed from creation, and on the fused path also armed in mid-life, armed again with
+other cut-offs and another cadence and turned off: ``stop_state`` against tests/dga_batch_stop_cpu.py with its types, every
+instance's x, y, tie draws and flags against dga_cpu at its own count and ``report()[k, 0]`` against ``device_energy`` there, bit for
+bit, a record that met its cut-off against HiGHS.  An instance that neither stops inside its parity horizon nor has a horizon that
+covers the run -- those on which dga_cpu raises before they stop among them -- is run as a neighbour, not compared; such
+instance-schedules are at most a quarter of a run.  One more batch of three instances has 65533 variables: the last workgroup of
+the bound's column pass holds terms only from 65281 on.
+
     python tools/fuzz_batched.py [--cases 24] [--seed 0]
         [--family cp_batch,cp_many,admm_batch,admm_many,dga,dga_batch,dga_many,cp_many_stop,admm_many_stop,dga_many_stop,
-                  cp_many_gap,cp_batch_gap,admm_batch_stop]
+                  cp_many_gap,cp_batch_gap,admm_batch_stop,dga_batch_stop]
 
 The generators and the CPU references need no GPU (tests/test_fuzz_batched_host.py checks on them that the GPU runs compare what
 they claim to); the ``run_*`` functions need one."""
@@ -78,6 +92,18 @@ STOP_AFTER_OFFSET = 500   # on top of them: the generator of ``after``, so that 
 # condition of tests/test_fuzz_batched_host.py); 11001 is the smallest offset from there on that meets them all on the CPU
 ADMM_BATCH_STOP_OFFSET = 11001
 ADMM_BATCH_STOP_SIZES, ADMM_BATCH_DISTINCT, ADMM_BATCH_WIDTHS = (1, 2, 3, 5, 8, 17, 33, 65), 9, (2, 4, 8, 16, 32)
+# the stopping test of the batched dual ascent (``dga_batch_stop``): batches of their own from RandomState(seed + offset), at most
+# DGA_BATCH_DISTINCT distinct instances each (a larger batch cycles them), ``large_case`` with LONG_LIST instances; DGA_ITERS
+# iterations, the cadences of DGA_STOP_EVERY, the cap DGA_STOP_LEFT_OUT on the instance-schedules behind their parity horizon.
+# The offset: 12000 was tried first; 12010 is the smallest offset from there on that meets every condition of
+# tests/test_fuzz_dga_batch_stop_host.py for TEST_SEED / TEST_CASES on the CPU.  Of the ten before it nine compare no instance at one
+# of the sizes n = 1, 2, 3 (the batches of cases 0 .. 2 have 1, 2 and 3 instances, and so small an LP often leaves its parity horizon
+# or raises within a few iterations), 12003, 12006, 12007 and 12008 also break the cap (the batch of 260 lies mostly behind its
+# horizons there; 12006 misses nothing else), 12000 and 12007 decide by equality in too few cases, 12003 and 12005 stop no instance
+# over an LP without inequality rows
+DGA_BATCH_STOP_OFFSET = 12010
+DGA_BATCH_STOP_SIZES, DGA_BATCH_DISTINCT = (1, 2, 3, 5, 8, 17, 33, 64, 65), 9
+DGA_BATCH_STOP_LARGE_N = 65536 - 3   # ``dga_batch_stop_large_case``: the largest size ``dga_cpu.device_energy`` restates is 65536
 # the certified stopping test (``cp_many_gap`` / ``cp_batch_gap``): the generators of the lists and of the batches, and on top of
 # them those of the coin that boxes an LP (with probability GAP_BOXED) and of the test's own draws.  The lists' offset 9000 meets
 # the conditions of tests/test_fuzz_batched_host.py at once.  The batches': 10000 was tried first; 10109 is the smallest offset from
@@ -929,6 +955,247 @@ def dga_stop_statistics(cases, seed):
         out["lists_with_both"] += any(w[1] for w in known) and any(not w[1] for w in known)
         out["by_equality"] += case.source is not None and case.want[case.source[0]] is not None and case.want[case.source[0]][2] == case.tol
         out["longest"] = max(out["longest"], len(case.lps))
+    return out
+
+
+# ---- the per-instance stopping test of the batched dual ascent: batches of their own, rules, what the restatement expects ----------
+
+def _frozen_args(rng, args):
+    """``args`` with one finite bound of one variable opened to +-inf on the side the start's ``c_bar`` pushes it to (the
+    construction of tests/test_gpu_dga_batch.py::_sc50a_with_an_unbounded_instance): ``dual_energy`` of the start is ``-inf``, so
+    the instance is frozen at creation.  None when the start's ``c_bar`` is zero everywhere."""
+    from dga_cpu import dual_energy
+
+    c, a_eq, b_eq, a_ineq, b_upper, lb, ub = args
+    rs = np.random.RandomState(0)
+    y_eq = -rs.rand(a_eq.shape[0])
+    y_ineq = np.abs(rs.rand(a_ineq.shape[0])) if a_ineq is not None else None
+    c_bar, _ = dual_argmin(c, a_eq, a_ineq, lb, ub, y_eq, y_ineq)
+    able = np.flatnonzero(c_bar != 0)
+    if able.size == 0:
+        return None
+    j = int(able[rng.randint(able.size)])
+    lb, ub = lb.copy(), ub.copy()
+    if c_bar[j] < 0:
+        ub[j] = np.inf
+    else:
+        lb[j] = -np.inf
+    assert dual_energy(c, a_eq, b_eq, a_ineq, b_upper, lb, ub, y_eq, y_ineq) == -np.inf
+    return c, a_eq, b_eq, a_ineq, b_upper, lb, ub
+
+
+class DgaBatchStopCase:
+    """One batch of ``DeviceDGABatch`` with the rules of its stopping test.
+
+    ``lps``           one ``DgaLP`` per instance: instance ``k`` is distinct instance ``k % len(distinct)`` (at most
+                      ``DGA_BATCH_DISTINCT`` of them; a larger batch cycles them and shares their references), but for
+                      ``frozen_at`` (None, or the position of the constructed frozen instance: its neighbour's data with one
+                      bound opened, ``_frozen_args``);
+    ``steps(k)``,     the restated curves of instance ``k`` inside its parity horizon, ``horizon + 1`` entries (none for the frozen
+    ``bounds(k)``     instance): ``dga_stop_cpu.steps_of`` and ``dga_cpu.device_energy`` on ``lp.states``, once per distinct LP;
+    ``every, tol,     the rule of schedule A, armed from creation.  ``source = (k, t)``: ``tol`` is ``steps(k)[t - 1]``, ``t`` a check
+    targets``         -- ``<=`` decides by equality (None: no such instance, or no step test).  ``kinds[k] = (kind, t)`` tells where
+                      ``targets[k]`` comes from: ``"none"`` (``+inf``), ``"equal"`` (``bounds(k)[t - 1]``: ``>=`` decides by equality),
+                      ``"above"`` (``np.nextafter`` of it upward: not met at that check) or ``"never"`` (the curve's maximum + 1);
+                      ``both``: the source instance has the cut-off of its own bound at the check of ``tol`` (reason 3);
+    ``rules_b``       schedule B: ``(after, tol, targets, every)``, ``(after2, tol / 2 or None, targets2, every2)`` with cut-offs
+                      and a cadence drawn afresh, ``(after3, None, None, 1)``: armed in mid-life, armed again, turned off."""
+
+    def __init__(self, no, distinct, batch, frozen_at, frozen_lp, rng):
+        import dga_cpu as cpu
+        import dga_stop_cpu
+
+        self.no, self.distinct, self.frozen_at = no, distinct, frozen_at
+        self.lps = [distinct[k % len(distinct)] for k in range(batch)]
+        if frozen_at is not None:
+            self.lps[frozen_at] = frozen_lp
+        self.frozen = np.array([k == frozen_at for k in range(batch)])
+        self._curves = {}
+        for lp in distinct + ([] if frozen_lp is None else [frozen_lp]):
+            inside = {it: lp.states[it] for it in range(-1, lp.horizon + 1)}
+            bounds = np.array([cpu.device_energy(*lp.args, inside[it][1], inside[it][2]) for it in range(lp.horizon + 1)])
+            self._curves[id(lp)] = (dga_stop_cpu.steps_of(inside), bounds)
+            for curve in self._curves[id(lp)]:
+                curve.setflags(write=False)
+        live = [k for k in range(batch) if not self.frozen[k]]
+        self.every = int(DGA_STOP_EVERY[rng.randint(len(DGA_STOP_EVERY))])
+        if not any(self.steps(k).size >= self.every for k in live):
+            self.every = 1
+        able = [k for k in live if self.steps(k).size >= self.every]
+        want_tol, want_targets = no % 5 != 4, no % 5 != 2   # one case of five without a step test, another without cut-offs
+        self.source, self.tol, self.both = None, None, False
+        pick, at, coin = rng.randint(2 ** 31), rng.rand(), rng.rand()   # consumed in every case: the later draws do not shift
+        if want_tol or not able:
+            self.tol = 1e-2
+            if able:
+                k = able[pick % len(able)]
+                t = self.every * (1 + int(at * (self.steps(k).size // self.every)))
+                if np.isfinite(self.steps(k)[t - 1]):
+                    self.source, self.tol = (k, t), float(self.steps(k)[t - 1])
+        self.targets, self.kinds = self.draw_targets(rng, self.every) if want_targets or self.tol is None else (None, None)
+        if self.targets is not None and self.source is not None and coin < 0.5:
+            k, t = self.source
+            if np.isfinite(self.bounds(k)[t - 1]):
+                self.targets[k], self.kinds[k], self.both = self.bounds(k)[t - 1], ("equal", t), True
+        after = int(rng.randint(1, 10))
+        after2 = int(rng.randint(after + 1, 26))
+        every2 = int(DGA_STOP_EVERY[rng.randint(len(DGA_STOP_EVERY))])
+        targets2, self.kinds2 = self.draw_targets(rng, every2)
+        after3 = int(rng.randint(after2 + 1, 36))
+        self.rules_a = [(0, self.tol, self.targets, self.every)]
+        self.rules_b = [(after, self.tol, self.targets, self.every), (after2, None if self.tol is None else self.tol / 2, targets2, every2),
+                        (after3, None, None, 1)]
+        self._want = {}
+
+    def steps(self, k):
+        return self._curves[id(self.lps[k])][0]
+
+    def bounds(self, k):
+        return self._curves[id(self.lps[k])][1]
+
+    def draw_targets(self, rng, every):
+        """One cut-off per instance of the batch, of one of the four kinds drawn uniformly, on the instance's own curve at a drawn
+        check of cadence ``every``; an instance without such a check (the frozen one among them) has none: ``+inf``."""
+        kinds = ("none", "equal", "above", "never")
+        targets, drawn = np.full(len(self.lps), np.inf), []
+        for k in range(len(self.lps)):
+            kind, at = kinds[rng.randint(4)], rng.rand()
+            bounds = self.bounds(k)
+            t = every * (1 + int(at * (bounds.size // every))) if bounds.size >= every else 0
+            value = {"none": np.inf, "equal": bounds[t - 1], "above": np.nextafter(bounds[t - 1], np.inf),
+                     "never": np.max(bounds) + 1.0}[kind] if t else np.inf
+            if not np.isfinite(value):
+                kind, t, value = "none", 0, np.inf
+            targets[k] = value
+            drawn.append((kind, t))
+        return targets, drawn
+
+    def schedule(self, name):
+        return self.rules_a if name == "A" else self.rules_b
+
+    def want(self, name, total=DGA_ITERS):
+        """``(stop_state of dga_batch_stop_cpu, known)`` of schedule ``name`` after ``total`` iterations of the state's life, on the
+        curves restricted to the horizons (behind them NaN, which meets nothing).  ``known[k]``: the instance is frozen, stops
+        inside its horizon, or its horizon covers the ``total`` iterations -- the others are run as neighbours, not compared."""
+        import dga_batch_stop_cpu
+
+        if (name, total) not in self._want:
+            pad = lambda v: np.concatenate((v, np.full(max(0, DGA_ITERS - v.size), np.nan)))  # noqa: E731
+            batch = range(len(self.lps))
+            state = dga_batch_stop_cpu.stop_state([pad(self.steps(k)) for k in batch], [pad(self.bounds(k)) for k in batch],
+                                                  self.schedule(name), total, frozen=self.frozen)
+            known = self.frozen | state[1] | np.array([self.steps(k).size >= total for k in batch])
+            self._want[(name, total)] = (state, known)
+        return self._want[(name, total)]
+
+    def phases(self, name):
+        """The iteration counts at which a run of schedule ``name`` is compared: A at its end; B when each of its rules is armed
+        (the end of the unarmed run and of the first two rules) and at its end."""
+        return [DGA_ITERS] if name == "A" else [rule[0] for rule in self.rules_b] + [DGA_ITERS]
+
+    def start_bound(self, k):
+        import dga_cpu as cpu
+
+        start = self.lps[k].states[-1]
+        return cpu.device_energy(*self.lps[k].args, start[1], start[2])
+
+    def rule_text(self, name):
+        rules = "; ".join(f"after {a}: tol {tol!r}, targets {'None' if tg is None else 'given'}, every {ev}" for a, tol, tg, ev in self.schedule(name))
+        return f"schedule {name} ({rules}; tol from {self.source})"
+
+
+_DGA_BATCH_STOP_CASES = {}
+
+
+def dga_batch_stop_cases(cases, seed):
+    """``[DgaBatchStopCase]`` of ``run_dga_batch_stop``: batches of their own from ``RandomState(seed + DGA_BATCH_STOP_OFFSET)``,
+    integer- and decimal-valued in turn, cases 0 .. 9 at the edge sizes, the batch sizes of ``DGA_BATCH_STOP_SIZES`` in turn and
+    ``LONG_LIST`` in ``large_case``; in every third case, from three instances on, one instance at a drawn position is the constructed
+    frozen one.  The rule of case ``i`` comes from ``RandomState(seed + DGA_BATCH_STOP_OFFSET + STOP_AFTER_OFFSET + i)``."""
+    key = (cases, seed)
+    if key not in _DGA_BATCH_STOP_CASES:
+        rng = np.random.RandomState(seed + DGA_BATCH_STOP_OFFSET)
+        out = []
+        for case in range(cases):
+            batch = LONG_LIST if case == large_case(cases) else DGA_BATCH_STOP_SIZES[case % len(DGA_BATCH_STOP_SIZES)]
+            kind = ("integer", "decimal")[case % 2]
+            args = _integer_dga_args(rng, edge_n(case)) if kind == "integer" else _decimal_dga_args(rng, edge_n(case))
+            name = f"seed {seed} case {case} ({kind}, n {args[0].size}) distinct instance "
+            distinct = [DgaLP(a, kind, name + str(j)) for j, a in enumerate(perturbed(rng, args, kind, min(batch, DGA_BATCH_DISTINCT)))]
+            frozen_at = frozen_lp = None
+            if case % 3 == 2 and batch >= 3:
+                at = int(rng.randint(batch))
+                opened = _frozen_args(rng, distinct[at % len(distinct)].args)
+                if opened is not None:
+                    frozen_at, frozen_lp = at, DgaLP(opened, kind, name + f"{at % len(distinct)} with a bound opened (frozen)")
+                    assert sorted(frozen_lp.states) == [-1] and frozen_lp.horizon == -1
+            out.append(DgaBatchStopCase(case, distinct, batch, frozen_at, frozen_lp,
+                                        np.random.RandomState(seed + DGA_BATCH_STOP_OFFSET + STOP_AFTER_OFFSET + case)))
+        _DGA_BATCH_STOP_CASES[key] = out
+    return _DGA_BATCH_STOP_CASES[key]
+
+
+def dga_batch_stop_large_case(seed):
+    """One ``DgaBatchStopCase`` of three integer-valued instances with ``DGA_BATCH_STOP_LARGE_N`` variables (more than the fused
+    search takes): the last of the 256 workgroups of the bound's column pass holds terms, which no size below 65281 reaches, and
+    the size is no multiple of the workgroup.  Generators of its own, behind those of the rules of the cases."""
+    key = ("large", seed)
+    if key not in _DGA_BATCH_STOP_CASES:
+        rng = np.random.RandomState(seed + DGA_BATCH_STOP_OFFSET + 2 * STOP_AFTER_OFFSET)
+        args = _integer_dga_args(rng, DGA_BATCH_STOP_LARGE_N)
+        name = f"seed {seed} large case (integer, n {DGA_BATCH_STOP_LARGE_N}) distinct instance "
+        distinct = [DgaLP(a, "integer", name + str(j)) for j, a in enumerate(perturbed(rng, args, "integer", 3))]
+        _DGA_BATCH_STOP_CASES[key] = DgaBatchStopCase(0, distinct, 3, None, None, np.random.RandomState(seed + DGA_BATCH_STOP_OFFSET + 2 * STOP_AFTER_OFFSET + 1))
+    return _DGA_BATCH_STOP_CASES[key]
+
+
+def dga_batch_stop_statistics(cases, seed):
+    """Counts over ``dga_batch_stop_cases`` on the restatement alone -- what tests/test_fuzz_dga_batch_stop_host.py asserts on and
+    ``run_dga_batch_stop`` asserts its cap with.  ``instance_schedules`` = ``compared + left_out`` over both schedules;
+    ``by_step`` / ``by_bound`` / ``by_both`` / ``running`` split the compared ones by reason; the others are documented there."""
+    out = dict(instance_schedules=0, compared=0, left_out=0, by_step=0, by_bound=0, by_both=0, running=0, batches_with_both=0,
+               step_by_equality=0, bound_by_equality=0, above_not_met=0, sizes=set(), edge_sizes=set(), stopped_without_ineq=0,
+               stopped_without_eq=0, frozen=0, frozen_between=0, b_first_phase=0, b_second_phase=0, b_survive_off=0, twins_apart=0, longest=0,
+               idle_batches=0, driver_batches=0)
+    for case in dga_batch_stop_cases(cases, seed):
+        batch = len(case.lps)
+        out["driver_batches"] += case.frozen_at is None and all(lp.clean and lp.device_fail is None for lp in case.lps)
+        out["sizes"].add(batch)
+        out["longest"] = max(out["longest"], batch)
+        out["frozen"] += case.frozen_at is not None
+        out["frozen_between"] += case.frozen_at is not None and 0 < case.frozen_at < batch - 1
+        for name in ("A", "B"):
+            (iterations, stopped, step, bound, reason), known = case.want(name)
+            out["instance_schedules"] += batch
+            out["compared"] += int(known.sum())
+            out["left_out"] += int((~known).sum())
+            live = known & ~case.frozen
+            for bit, label in ((1, "by_step"), (2, "by_bound"), (3, "by_both")):
+                out[label] += int((live & (reason == bit)).sum())
+            out["running"] += int((live & ~stopped).sum())
+            out["edge_sizes"] |= {case.lps[k].args[0].size for k in np.flatnonzero(live)}
+            for k in np.flatnonzero(live & stopped):
+                out["stopped_without_ineq"] += case.lps[k].rows[1] == 0
+                out["stopped_without_eq"] += case.lps[k].rows[0] == 0
+            if name == "B":
+                (a1, _, _, _), (a2, _, _, _), (a3, _, _, _) = case.rules_b
+                done = iterations[live & stopped]
+                out["b_first_phase"] += int(((done > a1) & (done <= a2)).sum())
+                out["b_second_phase"] += int(((done > a2) & (done <= a3)).sum())
+                out["b_survive_off"] += int(done.size)
+                continue
+            out["batches_with_both"] += bool((live & stopped).any() and (live & ~stopped).any())
+            out["idle_batches"] += bool(known.all() and (stopped | case.frozen).all())
+            met = [k for k in np.flatnonzero(live & stopped)]
+            out["step_by_equality"] += any(reason[k] & 1 and step[k] == case.tol for k in met)
+            out["bound_by_equality"] += any(reason[k] & 2 and bound[k] == case.targets[k] for k in met)
+            if case.kinds is not None:   # the check of the cut-off is reached alive, and the bound there lies below it
+                out["above_not_met"] += sum(case.kinds[k][0] == "above" and iterations[k] >= case.kinds[k][1]
+                                            and case.bounds(k)[case.kinds[k][1] - 1] < case.targets[k] for k in np.flatnonzero(live))
+            twins = {}
+            for k in met:
+                twins.setdefault(id(case.lps[k]), set()).add(int(iterations[k]))
+            out["twins_apart"] += sum(len(v) > 1 for v in twins.values())
     return out
 
 
@@ -2145,17 +2412,150 @@ def run_dga_many_stop(cases, seed):
     return counts
 
 
+DGAB_STOP_NAMES = (("iterations", np.int64), ("stopped", np.bool_), ("step", np.float64), ("bound", np.float64), ("reason", np.int32))
+
+
+def _dgab_read(state):
+    """Everything ``run_dga_batch_stop`` compares of a state: ``(stop_state, snapshot, report, frozen, iterations done)``."""
+    return state.stop_state(), _snapshot(state), state.report(), state.frozen(), state.status()[3]
+
+
+def _dgab_same(p, q):
+    return (all(np.array_equal(a, b, equal_nan=True) for a, b in zip(p[0], q[0])) and all(np.array_equal(a, b) for a, b in zip(p[1], q[1]))
+            and np.array_equal(p[2], q[2], equal_nan=True) and np.array_equal(p[3], q[3]) and p[4] == q[4])
+
+
+def _dgab_compare(counts, case, name, total, read, where, path, final):
+    """The instances of ``case`` that are known after ``total`` iterations of schedule ``name`` against the restatement and
+    dga_cpu: ``stop_state`` with dtypes, x, y, tie draws and flags at the instance's own count, the report's bound against
+    ``device_energy`` there, ``frozen()``; a clean LP's record that met its cut-off against HiGHS."""
+    got, snap, report, frozen, _ = read
+    want, known = case.want(name, total)
+    for g, (label, dtype) in zip(got, DGAB_STOP_NAMES):
+        _require(g.dtype == dtype and g.shape == (len(case.lps),), f"{where}: {label} has dtype {g.dtype}, shape {g.shape}")
+    _require(np.array_equal(frozen, case.frozen), f"{where}: frozen() is {np.flatnonzero(frozen).tolist()}, constructed {case.frozen_at}")
+    one = path.partition("-")[0]
+    for k in np.flatnonzero(known):
+        lp = case.lps[k]
+        at = f"{where}, instance {k} of {len(case.lps)} ({lp.name}, horizon {lp.horizon}), after {total} iterations"
+        layer = None if case.frozen[k] else _dga_single_agrees(lp, one)
+        for g, w, (label, _) in zip(got, want, DGAB_STOP_NAMES):
+            _require(np.array_equal(g[k], w[k], equal_nan=True), at + f": {label} {g[k]!r}, restated {w[k]!r} (stop_state "
+                     f"{tuple(g[k] for g in got)}, restated {tuple(w[k] for w in want)}, first cut-off "
+                     f"{None if case.schedule(name)[0][2] is None else case.schedule(name)[0][2][k]!r})", layer)
+        done = int(want[0][k])
+        _require(int(snap[4][k]) == 0, at + f": status flags {int(snap[4][k])}", layer)
+        bad = _instance_equals(snap, k, lp.states[done - 1])
+        _require(not bad, at + f": {', '.join(bad)} differ from dga_cpu after {done} iterations", layer)
+        energy = case.bounds(k)[done - 1] if done > 0 else case.start_bound(k)
+        _require(np.array_equal(report[k, 0], energy, equal_nan=True),
+                 at + f": report()[{k}, 0] = {report[k, 0]!r} after {done} iterations, device_energy {energy!r}", layer)
+        counts["reports"] += 1
+        if final and want[4][k] & 2:
+            _check_bound(counts, lp, snap[4][k], got[3][k], snap[1][k], snap[2][k], at)
+    return want, known
+
+
+def run_dga_batch_stop(cases, seed, paths=BATCH_PATHS):
+    """``DeviceDGABatch.set_stop`` / ``stop_state`` and ``dual_gradient_ascent_batch_until`` on batches of their own
+    (``dga_batch_stop_cases``), against tests/dga_batch_stop_cpu.py on curves restated on the CPU -- the steps from dga_cpu's
+    multipliers, the bounds from ``dga_cpu.device_energy`` on them: schedule A (armed from creation) on each of ``paths``, schedule B
+    (armed in mid-life, armed again with other cut-offs and cadence, turned off) on ``fused``.  Every instance inside its parity
+    horizon: ``stop_state`` bit for bit with dtypes, x, y, tie draws and flags against dga_cpu at its own count, ``report()[k, 0]``
+    against ``device_energy`` there, ``frozen()``, a record that met its cut-off against HiGHS.  The instances left out
+    (``DgaBatchStopCase.want``) are run as neighbours; their share is asserted.  Returns counts."""
+    stats = dga_batch_stop_statistics(cases, seed)
+    _require(stats["left_out"] <= DGA_STOP_LEFT_OUT * stats["instance_schedules"],
+             f"dga_batch_stop seed {seed}: {stats['left_out']} of {stats['instance_schedules']} instance-schedules lie behind their parity "
+             "horizon, more than a quarter")
+    counts = _dgab_counts()
+    for case in dga_batch_stop_cases(cases, seed):
+        _dgab_run_case(counts, case, seed, paths, "fused")
+    _require(counts["left_out"] <= DGA_STOP_LEFT_OUT * counts["instances"],
+             f"dga_batch_stop seed {seed}: {counts['left_out']} of {counts['instances']} instance-schedules left out")
+    return counts
+
+
+def run_dga_batch_stop_large(seed, paths=("general-segmented", "general-global")):
+    """The same comparisons on ``dga_batch_stop_large_case``, by the general search (schedule B under ``general-global``): the bound
+    of the check and of the report where the last workgroup of the column pass holds terms.  Returns counts; no cap."""
+    counts = _dgab_counts()
+    _dgab_run_case(counts, dga_batch_stop_large_case(seed), seed, paths, "general-global")
+    return counts
+
+
+def _dgab_counts():
+    return dict(batches=0, runs=0, instances=0, compared=0, left_out=0, stopped=0, running=0, frozen=0, longest=0, drivers=0, reports=0,
+                idle=0, bounds=0, bounds_skipped=0)
+
+
+def _dgab_run_case(counts, case, seed, paths, both_on):
+    """One case of ``run_dga_batch_stop``: schedule A on every path of ``paths``, schedule B on the path ``both_on``, the driver."""
+    from pysparselp_amd import dual_gradient_ascent_batch_until
+
+    lps = case.lps
+    for path in paths:
+        for name in ("A", "B") if path == both_on else ("A",):
+            where = f"dga_batch_stop seed {seed} case {case.no}, path {path}, {case.rule_text(name)}"
+            rules, phases, done = list(case.schedule(name)), case.phases(name), 0
+            with batch_state(lps, path) as state:
+                for total in phases:
+                    if rules and rules[0][0] == done:
+                        _, tol, targets, every = rules.pop(0)
+                        state.set_stop(tol, targets, every)
+                    for p in _pieces(total - done):
+                        state.iterate(p)
+                    done = total
+                    read = _dgab_read(state)
+                    want, known = _dgab_compare(counts, case, name, total, read, where, path, total == DGA_ITERS)
+                live = known & ~case.frozen
+                if name == "A" and path == both_on and known.all() and (want[1] | case.frozen).all():
+                    state.iterate(5)   # nothing moves: no launch, and `iters` stays
+                    _require(_dgab_same(read, _dgab_read(state)), f"{where}: iterate(5) on a batch in which nothing moves changed it")
+                    counts["idle"] += 1
+            counts["runs"] += 1
+            counts["instances"] += len(lps)
+            counts["compared"] += int(known.sum())
+            counts["left_out"] += int((~known).sum())
+            counts["stopped"] += int((live & want[1]).sum())
+            counts["running"] += int((live & ~want[1]).sum())
+            counts["frozen"] += int((known & case.frozen).sum())
+        # the driver checks the status of every instance after every call, and a frozen instance needs no driver
+        if case.frozen_at is None and all(lp.clean and lp.device_fail is None for lp in lps):
+            one, _, sort = path.partition("-")
+            (want, known), (_, tol, targets, every) = case.want("A"), case.rules_a[0]
+            with environment(SLP_DGA_BATCH_SORT=sort or None):
+                xs, y_eqs, y_ineqs, info = dual_gradient_ascent_batch_until(
+                    _LP(*lps[0].args), np.array([lp.args[0] for lp in lps]), tol, targets, every, nb_max_iter=DGA_ITERS,
+                    lower_bounds=np.array([lp.args[5] for lp in lps]), upper_bounds=np.array([lp.args[6] for lp in lps]), path=one)
+            for k in np.flatnonzero(known):
+                at = f"dga_batch_stop seed {seed} case {case.no} instance {k} ({lps[k].name}), path {path}, dual_gradient_ascent_batch_until, {case.rule_text('A')}"
+                mine = (info["iterations"][k], info["stopped"][k], info["step"][k], info["reason"][k])
+                theirs = (want[0][k], want[1][k], want[2][k], want[4][k])
+                _require(all(np.array_equal(g, w, equal_nan=True) for g, w in zip(mine, theirs)), at + f": info {mine} != {theirs}")
+                ref = lps[k].states[int(want[0][k]) - 1]
+                _require(np.array_equal(xs[k], ref[0]) and np.array_equal(y_eqs[k], ref[1])
+                         and (ref[2] is None or np.array_equal(y_ineqs[k], ref[2])), at + ": x or y differ from dga_cpu")
+                energy = case.bounds(k)[int(want[0][k]) - 1]
+                _require(np.array_equal(info["lower_bound"][k], energy, equal_nan=True),
+                         at + f": lower_bound {info['lower_bound'][k]!r}, device_energy {energy!r}")
+            counts["drivers"] += 1
+    counts["batches"] += 1
+    counts["longest"] = max(counts["longest"], len(lps))
+
+
 FAMILIES = {"cp_batch": run_cp_batch, "cp_many": run_cp_many, "admm_batch": run_admm_batch, "admm_many": run_admm_many, "dga": run_dga,
             "dga_batch": run_dga_batch, "dga_many": run_dga_many, "cp_many_stop": run_cp_many_stop, "admm_many_stop": run_admm_many_stop,
             "dga_many_stop": run_dga_many_stop, "cp_many_gap": run_cp_many_gap, "cp_batch_gap": run_cp_batch_gap,
-            "admm_batch_stop": run_admm_batch_stop}
+            "admm_batch_stop": run_admm_batch_stop,
+            "dga_batch_stop": lambda cases, seed: dict(run_dga_batch_stop(cases, seed), large_case=run_dga_batch_stop_large(seed))}
 
 
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--cases", type=int, default=TEST_CASES)
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--family", default=",".join(FAMILIES))
+    p.add_argument("--family", default=",".join(FAMILIES), help="comma-separated, among " + ", ".join(FAMILIES) + " (default: all)")
     args = p.parse_args()
     failed = 0
     for name in args.family.split(","):
