@@ -17,6 +17,7 @@
 // It is the 8-rank row partition of DESIGN.md section 5 minus the wire: rank k's block = chunk k.
 #include "slp_common.h"
 #include "slp_kernels.h"
+#include "../../include/slp_hip_ext_tall.h"
 
 slp_matrix::~slp_matrix() {
     for (slp_matrix *c : chunks) delete c;
@@ -125,6 +126,7 @@ int slp_matrix_chunked_append(slp_matrix *g, slp_matrix *c) {
                 if (f->tall && f->S == 1) {
                     g->tall_carry[t].C = f->C; g->tall_carry[t].dcap = f->D > 0 ? f->tall_dcap : -1;
                     g->tall_carry[t].R = f->tall_R; g->tall_carry[t].total = f->tall_total;
+                    g->tall_carry[t].records = f->tall_records ? 1 : 0;
                 }
             }
         if (f0->tall) g->tall_carry[0].blocks += f0->B;   // (the next chunk of A takes what brings these up to the cumulative share)
@@ -187,6 +189,19 @@ int64_t slp_matrix_tall_rows(slp_matrix *m, int transposed) {
             const StripJds *f = fast_format(m, transposed != 0);
             if (f && !m->chunks.empty() && !f->parts.empty()) f = f->parts[0];
             r = (f && f->ok && f->tall) ? (int64_t)f->tall_R : 0;
+        })
+    }();
+    return rc == 0 ? r : -1;
+}
+
+int64_t slp_matrix_tall_records(slp_matrix *m, int transposed) {
+    if (!m) return -1;
+    int64_t r = 0;
+    const int rc = [&]() -> int {
+        SLP_API_INT({
+            const StripJds *f = fast_format(m, transposed != 0);
+            if (f && !m->chunks.empty() && !f->parts.empty()) f = f->parts[0];
+            r = (f && f->ok && f->tall && f->tall_records) ? 1 : 0;
         })
     }();
     return rc == 0 ? r : -1;

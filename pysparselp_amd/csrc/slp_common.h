@@ -265,6 +265,7 @@ struct StripJds {
     bool tall = false;
     int tall_R = 0;
     int tall_dcap = 0;                               // capacity of the value table in the product kernel's LDS (slp_tall_plan.h)
+    bool tall_records = false;                       // the packets' form: lane-major records for slots 0-3 (slp_tall_item.h; the planner's choice)
     i64 tall_total = 0;                              // a chunk that took its share of the row blocks of its chunked matrix: all of them
     DevBuf<TallWg> tall_wg;                          // [B * S] where every workgroup's packet stream lies
     std::vector<DevBuf<unsigned int>> tall_dir;      // 32-byte packet headers, one buffer per build pass
@@ -305,6 +306,7 @@ bool tall_wanted(i64 nrow, i64 ncol, i64 nnz);
 // rows_total > 0: the chunk's share of the row blocks of a chunked matrix; carry: what the first chunk decided (slp_tall_plan.h)
 struct TallCarry {
     int C = 0, dcap = -1, R = 0;
+    int records = -1;   // the packets' form of the first chunk's copy (-1: nothing carried)
     i64 total = 0;
     i64 blocks = 0;   // row blocks of the chunks so far (A: the next chunk's share is counted from them)
 };

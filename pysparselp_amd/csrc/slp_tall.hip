@@ -15,16 +15,27 @@
 //                     (slp_tall_item.h: packing and decoding, one text for builder and kernel).  The sum field is the index of the
 //                     row's running sum among the doubles of the kernel's LDS: 1 + capacity of the value table + local row (the
 //                     scratch cell and the table lie in front of the sums).  Self-describing: no per-row metadata, rows
-//                     without entries in a cell cost nothing; sum field 0 is the product kernel's scratch cell: a skip item,
-//                     and the zero word a lane outside a slot loads, need no predicate anywhere.
+//                     without entries in a cell cost nothing; sum field 0 is the product kernel's scratch cell: a skip item, a
+//                     padding word of a record, and the zero word a lane outside a slot loads, need no predicate anywhere.
 //                     With fp64 values (4 bytes + the value in a parallel array): sum field << 3 | column << 17.
 //   cell            = the items of its non-empty rows, every row handed WHOLE to one of the 1024 lanes (rows sorted by
 //                     their entry count, dealt round by round: lane p takes sorted positions p, p + 1024, ...), so a
 //                     lane's list is its rows' entries in storage order and list lengths never increase with p
 //   packet          = 8 consecutive list positions ("slots") of all lanes: slot k holds item k of every lane whose
-//                     list is longer than k -- a prefix of the lanes -- so lane p reads word p of the slot: coalesced,
-//                     no lengths stored.  Low 4 bytes of the items slot by slot, then the fifth bytes, four slots to
-//                     a word.  32-byte header: payload offset, the 8 slot widths, the x-tile it carries.
+//                     list is longer than k -- a prefix of the lanes, w[k] of them; no lengths stored.  32-byte header: payload
+//                     offset, the 8 slot widths, the x-tile it carries.  The payload comes in TWO FORMS, one per copy
+//                     (slp_tall_item.h: both layouts' offsets and sizes, one text for builder, kernel and planner):
+//                       slot-major  [slot 0: w[0] words, lane p's low 4 bytes at p] ... [slot 7] [w[0] words: the fifth bytes
+//                                   of slots 0-3, four slots to a word] [w[4] words: those of slots 4-7] -- a word per item
+//                                   that exists: the compact form, four 4-byte loads per lane for slots 0-3
+//                       records     [w[0] records of 4 words: lane p's items of slots 0-3 at 4 p, zero words where its list
+//                                   is shorter] [w[0] words: their fifth bytes] [slot 4] .. [slot 7] [w[4] words: their
+//                                   fifth bytes] -- the first four list positions LANE-MAJOR: one 16-byte load per lane;
+//                                   a lane with fewer than four items in the group pays for four
+//                     WHO CHOOSES: the planner (slp_tall_plan.h: tall_plan_records), per copy, from the growth in bytes it
+//                     predicts for the planned cell -- records where lists are four (or 5-8) long, slot-major where cells
+//                     are small or lists short, and for fp64 items always; SLP_TALL_RECORDS=0|1 forces the form; the chunks of a chunked matrix follow
+//                     their first chunk.  StripJds::tall_records says which, and picks the product kernel's instantiation.
 //
 // A lane adds its items into the running sums in order: `acc[row] += value * x[col]`, one row after the other, so every
 // row is accumulated by ONE lane per cell, cells in strip order: the result is the sequential single-accumulator CSR
@@ -243,8 +254,10 @@ __device__ __forceinline__ i64 tall_range_of(i64 t, i64 T, int S) {  // the stri
 }
 
 // DICT: 5-byte items (value id inside); !DICT: 4-byte items (sum field | column) + the fp64 value in a parallel array at the same offsets
-// (slp_tall_item.h).  sum0: the sum field of local row 0.
-template <bool DICT>
+// (slp_tall_item.h).  sum0: the sum field of local row 0.  REC: the packets' form (records for slots 0-3) -- a template parameter
+// although the builder is not on any timed path: the kernel stands at all 128 vector registers without scratch (REGISTERS above), and the
+// slot-major instantiation stays the code it was.
+template <bool DICT, bool REC>
 __global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int C, unsigned int sum0, i64 ncell, const unsigned long long *__restrict__ keys,
                                                        const double *__restrict__ svals, const i64 *__restrict__ cellptr, TallScan sc,
                                                        i64 cap_w, i64 cap_p, TallPkt *__restrict__ sdir,
@@ -556,12 +569,12 @@ __global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int 
         nlane[p] = cover;
         // The cell's sizes from the envelope alone: slot k is as wide as the lanes whose envelope exceeds k, so the slots of all
         // packets hold sum_p cover[p] words; the fifth bytes take a word per lane of slot 8 g and of slot 8 g + 4 of every packet g.
+        // Records: a lane of slot 8 g has four words in packet g whatever its list -- tall_packet_lane_words (slp_tall_item.h).
         // A cell's payload is rounded up to 16 bytes (every stream then starts 16-byte aligned).  (The waves' sums cross the same
         // barrier as the envelope itself.)
         unsigned long long cw = 0;
         {
-            unsigned long long w = cover;
-            if (DICT) w += (cover + 7u) / 8u + (cover > 4u ? (cover - 4u + 7u) / 8u : 0u);
+            unsigned long long w = tall_packet_lane_words(cover, DICT, REC);
             w = tall_lane_sums<kWave>(w);
             if ((p & (kWave - 1)) == kWave - 1) wtot[p / kWave] = w;
         }
@@ -592,10 +605,10 @@ __global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int 
             }
             __syncthreads();
             SLP_TB_PROF(8);
-            unsigned int wd[kTallSlots], words = 0;
-            for (int j = 0; j < kTallSlots; ++j) { wd[j] = width[j]; words += wd[j]; }
-            const unsigned int hi0 = words, hi1 = words + wd[0];
-            if (DICT) words += wd[0] + wd[4];
+            unsigned int wd[kTallSlots];
+            for (int j = 0; j < kTallSlots; ++j) wd[j] = width[j];
+            const TallPacketLayout lay = tall_packet_layout(wd, DICT, REC);   // where the slots, the records and the fifth bytes lie
+            const unsigned int words = lay.words;
             // The lane's items of this packet in three steps, so that their keys are fetched TOGETHER (one after the other, each
             // waited for before the cursor moved on, they were 5-8 dependent L2 round trips per cell): where the keys lie (the
             // cursor's walk: LDS only), the loads, the items.  A lane inside a slot whose list has ended stores a skip item: row
@@ -670,10 +683,11 @@ __global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int 
             if (!fits) break;   // (the host repeats the pass with the exact sizes; the scan itself is complete)
             {
                 unsigned int *base = pay + woff;
-                unsigned int hb0 = 0, hb1 = 0, so = 0;
+                unsigned int hb0 = 0, hb1 = 0;
 #pragma unroll
                 for (int j = 0; j < kTallSlots; ++j) {
-                    if ((unsigned)p < wd[j]) {
+                    // (records: a lane of slot 0 writes its whole record -- zero words, the scratch cell, where its list has ended)
+                    if ((unsigned)p < wd[REC && j < 4 ? 0 : j]) {
                         unsigned int item = 0u, hib = 0u;
                         if (have >> j & 1u) {
                             // the sum field: where the local row's running sum lies in the product kernel's LDS (sum0: behind the
@@ -689,15 +703,15 @@ __global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int 
                                 item = tall_item64_encode(cl, r1);
                             }
                         }
-                        base[so + p] = item;
-                        if (!DICT) payv[woff + so + p] = value[j];
+                        const unsigned int at = tall_packet_item_word(lay, REC, (unsigned)p, j);
+                        base[at] = item;
+                        if (!DICT) payv[woff + at] = value[j];
                         if (j < 4) hb0 |= hib << (8 * j);
                         else hb1 |= hib << (8 * (j - 4));
                     }
-                    so += wd[j];
                 }
-                if (DICT && (unsigned)p < wd[0]) base[hi0 + p] = hb0;
-                if (DICT && (unsigned)p < wd[4]) base[hi1 + p] = hb1;
+                if (DICT && (unsigned)p < wd[0]) base[lay.fifth0 + p] = hb0;
+                if (DICT && (unsigned)p < wd[4]) base[lay.fifth1 + p] = hb1;
                 if (p == 0) {
                     TallPkt h;
                     h.off = woff;   // (inside the cell: k_tall_dir adds where the cell lies in its stream)
@@ -718,16 +732,18 @@ __global__ __launch_bounds__(kTallT) void k_tall_build(int R, i64 T, int S, int 
 
 // What the single pass is given room for: per cell of n entries its n items and the fifth bytes' words of min(n, 1024) lists of
 // ceil(n / 1024) items (what the dealing aims at; rows longer than that and the envelope's skip items -- 2-3 % on the benchmark's
-// LPs -- come out of the margin the host adds).
+// LPs -- come out of the margin the host adds).  Records (a uniform flag): the words of 1024 lists of n / 1024 items, one more on
+// the first n % 1024 of them -- tall_packet_balanced_words, the planner's own prediction.
 template <bool DICT>
-__global__ __launch_bounds__(kBlock) void k_tall_estimate(i64 ncell, const i64 *__restrict__ cellptr, unsigned long long *__restrict__ est) {
+__global__ __launch_bounds__(kBlock) void k_tall_estimate(i64 ncell, const i64 *__restrict__ cellptr, int records, unsigned long long *__restrict__ est) {
     unsigned long long w = 0, k = 0;
     for (i64 c = (i64)blockIdx.x * kBlock + threadIdx.x; c < ncell; c += (i64)gridDim.x * kBlock) {
         const unsigned long long n = (unsigned long long)(cellptr[c + 1] - cellptr[c]);
         if (!n) continue;
         const unsigned long long L = n < (unsigned)kTallT ? n : (unsigned)kTallT, tau = (n + kTallT - 1) / kTallT;
-        unsigned long long cw = n;
-        if (DICT) cw += L * ((tau + 7) / 8 + (tau > 4 ? (tau - 4 + 7) / 8 : 0));
+        // (slot-major: the lane's words beside its items are those of its fifth bytes)
+        const unsigned long long cw = records ? tall_packet_balanced_words(n, kTallT, DICT, true)
+                                              : n + L * (tall_packet_lane_words((unsigned int)tau, DICT, false) - tau);
         w += (cw + 3ull) & ~3ull;
         k += (tau + kTallSlots - 1) / kTallSlots;
     }
@@ -812,7 +828,7 @@ __global__ void k_tall_dir(i64 ncell, i64 V, i64 T, int S, int C, const i64 *__r
 // grid a quarter full, A x 14 % slower -- and blocks of 8334 rows.)
 // All of this is decided by tall_plan (slp_tall_plan.h: host code without HIP, tested on the CPU) from the shape, the dictionary and
 // the switches read here: SLP_TALL_R (rows per block, capped by what the LDS of the two kernels holds), SLP_TALL_C (columns per strip:
-// a multiple of 256 from 1024 to 4096), SLP_TALL_SPLIT.
+// a multiple of 256 from 1024 to 4096), SLP_TALL_SPLIT, SLP_TALL_RECORDS (0 / 1: the packets' form, else the planner's rule).
 static int tall_env(const char *name) {
     const char *e = getenv(name);
     return e ? atoi(e) : 0;
@@ -848,7 +864,9 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
     pin.nrow = nrowF; pin.ncol = ncolF; pin.nnz = a.nnz; pin.D = dict ? dict->D : 0; pin.cus = ctx().num_cu;
     if (!transposed) { pin.block_multiple = block_multiple; pin.rows_before = rows_before; pin.rows_total = rows_total; }
     pin.env_R = std::max(0, tall_env("SLP_TALL_R")); pin.env_C = tall_env("SLP_TALL_C"); pin.env_split = tall_env("SLP_TALL_SPLIT");
+    if (const char *e = getenv("SLP_TALL_RECORDS")) pin.env_records = atoi(e) != 0 ? 1 : 0;   // (tests, and an A/B within one library)
     if (carry && carry->C > 0) {
+        pin.carry_records = carry->records;
         pin.carry_C = carry->C; pin.carry_dcap = carry->dcap; pin.carry_total = transposed ? 0 : carry->total;
         pin.carry_R = transposed ? carry->R : 0;   // (the copy of A^T: the same row blocks in every chunk)
         pin.carry_blocks = transposed ? 0 : carry->blocks;
@@ -857,6 +875,7 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
     SLP_REQUIRE(plan.lds_bytes <= kTallLdsBytes && plan.build_lds_bytes <= kTallLdsBytes && plan.R >= 1 && plan.R <= kTallRmax,
                 "tall_build: the planned geometry does not fit the LDS");
     const int R = plan.R, S = plan.S, Cw = plan.C;
+    const bool records = plan.records;
     const i64 T = plan.T;
     // where the items' sum fields start: behind the scratch cell and the table of plan.dcap entries (the copy keeps that capacity:
     // tall_launch lays the kernel's LDS out with it, and the chunks fused into one launch all have the same)
@@ -950,8 +969,8 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
     TallScan sc;
     sc.w = scan.p; sc.p = scan.p + ncell; sc.ticket = scan.p + 2 * ncell; sc.before_w = sc.ticket + 1; sc.before_p = sc.before_w + ncell;
     est.zero();
-    if (dict) hipLaunchKernelGGL((k_tall_estimate<true>), dim3(grid_for(ncell, kBlock)), dim3(kBlock), 0, st, ncell, cellptr.p, est.p);
-    else hipLaunchKernelGGL((k_tall_estimate<false>), dim3(grid_for(ncell, kBlock)), dim3(kBlock), 0, st, ncell, cellptr.p, est.p);
+    if (dict) hipLaunchKernelGGL((k_tall_estimate<true>), dim3(grid_for(ncell, kBlock)), dim3(kBlock), 0, st, ncell, cellptr.p, records ? 1 : 0, est.p);
+    else hipLaunchKernelGGL((k_tall_estimate<false>), dim3(grid_for(ncell, kBlock)), dim3(kBlock), 0, st, ncell, cellptr.p, records ? 1 : 0, est.p);
     SLP_HIP(hipGetLastError());
     unsigned long long hest[2];
     est.download(hest, 2);
@@ -961,8 +980,9 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
     // benchmark's LPs; kept per orientation and item form) + 0.3 %; the first copy gets + 10 %.  A pass that did not fit is repeated into buffers of the exact size; a buffer
     // more than 1 % too large (the first copy; an LP unlike the last) is exchanged for one of the exact size.  The directory is 32 bytes
     // per ~20 KB cell.
-    static std::atomic<double> last_needs[2][2];   // by orientation and item form: the two copies of a chunk differ by ~1 % (zero: none yet)
-    std::atomic<double> &last_need_slot = last_needs[transposed ? 1 : 0][dict ? 1 : 0];
+    // by orientation, item form and packet form: the two copies of a chunk differ by ~1 % (zero: none yet)
+    static std::atomic<double> last_needs[2][2][2];
+    std::atomic<double> &last_need_slot = last_needs[transposed ? 1 : 0][dict ? 1 : 0][records ? 1 : 0];
     const double last_need = last_need_slot.load();
     const double room = (last_need > 0.5 && last_need < 2.0) ? last_need * 1.003 : 1.10;
     i64 cap_w = (i64)((double)hest[0] * room) + 65536, cap_p = 2 * (i64)hest[1] + 4096;
@@ -981,10 +1001,12 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
         SLP_HIP(hipMemsetAsync(scan.p, 0, (2 * (size_t)ncell + 1) * sizeof(unsigned long long), st));  // levels and the ticket
         // as many workgroups as the chip holds at once (the kernel's LDS: one per compute unit); each takes cells until none is left
         const unsigned grid = (unsigned)std::min<i64>(ncell, (i64)ctx().num_cu);
-        if (dict) hipLaunchKernelGGL((k_tall_build<true>), dim3(grid), dim3(kTallT), 0, st, R, T, S, Cw, sum0, ncell, sorted.p, (const double *)nullptr, cellptr.p, sc,
-                                     cap_w, cap_p, reinterpret_cast<TallPkt *>(sdir.p), spay.p, (double *)nullptr);
-        else hipLaunchKernelGGL((k_tall_build<false>), dim3(grid), dim3(kTallT), 0, st, R, T, S, Cw, sum0, ncell, sorted.p, svals.p, cellptr.p, sc,
-                                cap_w, cap_p, reinterpret_cast<TallPkt *>(sdir.p), spay.p, spayv.p);
+        auto build = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTallT), 0, st, R, T, S, Cw, sum0, ncell, sorted.p, dict ? (const double *)nullptr : svals.p, cellptr.p, sc,
+                               cap_w, cap_p, reinterpret_cast<TallPkt *>(sdir.p), spay.p, dict ? (double *)nullptr : spayv.p);
+        };
+        if (dict) { if (records) build(k_tall_build<true, true>); else build(k_tall_build<true, false>); }
+        else { if (records) build(k_tall_build<false, true>); else build(k_tall_build<false, false>); }
         hipLaunchKernelGGL(k_tall_streams, dim3(grid_for(V, kBlock)), dim3(kBlock), 0, st, V, T, S, cellptr.p, sc, ext.p);
         SLP_HIP(hipGetLastError());
         ext.download(hext.data(), hext.size());
@@ -1071,6 +1093,7 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
     f.tall = true;
     f.tall_R = R;
     f.tall_dcap = plan.dcap;
+    f.tall_records = records;
     f.tall_total = plan.total;
     f.S = S;
     if (S > 1) f.part.alloc((size_t)S * (size_t)nrowF);

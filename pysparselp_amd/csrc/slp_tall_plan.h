@@ -23,6 +23,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "slp_tall_item.h"
+
 namespace slp {
 
 constexpr int kTallLdsBytes = 160 * 1024;   // LDS of one workgroup
@@ -48,10 +50,13 @@ struct TallPlanIn {
     int carry_C = 0, carry_dcap = -1, carry_R = 0;
     int64_t carry_total = 0;
     int64_t carry_blocks = 0;              // row blocks the chunks in front came out with (beside carry_total)
+    int env_records = -1;                  // SLP_TALL_RECORDS: 0 / 1 forces the packets' form (-1: unset)
+    int carry_records = -1;                // the form of the first chunk's copy (-1: nothing carried)
 };
 
 struct TallPlan {
     int R = 0, C = 0, S = 1, dcap = 0;
+    bool records = false;      // the packets' form: the first four list positions as one 16-byte record per lane (slp_tall_item.h)
     int64_t T = 0;             // strips
     int64_t total = 0;         // row blocks of all chunks together, when the chunk took its share of them (else 0)
     int off_dv = 0, off_xt = 0, lds_bytes = 0;   // product kernel: bytes of the sums' share, byte offset of the x-tiles, all of its LDS
@@ -105,6 +110,38 @@ inline double tall_plan_cost(int64_t nrow, int R, int C, double per_cell, bool d
 inline bool tall_plan_admits(int64_t nrow, int R, int C, double per_cell) {
     if (C == 4096 || C == 2048 || C == 1024) return true;
     return (double)std::min<int64_t>(R, nrow) * per_cell / kTallPlanLanes <= kTallListMax;
+}
+
+// ---- the packets' form (slp_tall_item.h) ------------------------------------------------------------------------------------
+// Records save the product kernel three of a packet's four loads of slots 0-3 (and their scalar offsets and ends of range) and
+// cost a zero word for every list position below four that a lane of slot 0 lacks.  The rule is a condition on the copy's SIZE,
+// not a tuned speed: records iff the planned cell -- n = min(R, nrow) x per_cell items dealt in balance over the 1024 lanes --
+// grows by at most kTallRecordGrowth.  The two measurements there are put break-even at 11-14 % growth (+2.2 % bytes came with
+// -2.3 % time on the benchmark's LP; bytes alone cost about 0.2 % of time per % of bytes: DESIGN.md section 3 (ix)); 1/16 is
+// half of that.  It may be lowered; it may not be raised without an A/B at the new edge.
+// Lists of four from >= 3795 items and mean lists of 5-8 take records; mean lists <= 3, lists of exactly 9 (the second packet's
+// record holds one item: + 25 %) and the small cells of a finely chunked matrix (~140 items in lists of one: + 150 %, more bytes
+// than the CSR) stay slot-major.
+constexpr double kTallRecordGrowth = 1.0 / 16;
+inline int64_t tall_plan_cell_items(int64_t nrow, int R, double per_cell) {
+    return std::max<int64_t>(1, std::llround((double)std::min<int64_t>(R, nrow) * per_cell));
+}
+// predicted words of the planned cell in the one form over the other, minus one
+inline double tall_plan_record_growth(int64_t nrow, int R, double per_cell, bool dict) {
+    const uint64_t n = (uint64_t)tall_plan_cell_items(nrow, R, per_cell);
+    return (double)tall_packet_balanced_words(n, kTallPlanLanes, dict, true) / (double)tall_packet_balanced_words(n, kTallPlanLanes, dict, false) - 1.0;
+}
+// Items with an fp64 value never take records by the rule: their kernel runs at 0.77-0.78 of the HBM peak, where the records'
+// bytes cost what they weigh -- measured on the benchmark's LP with the dictionary ruled out, 4.88 / 4.78 ms per product
+// slot-major against 5.39 / 5.34 ms with records (+ 2.9 % bytes, + 10-12 % time).  The switch reaches
+// them.
+// The switch, then what the first chunk of a chunked matrix decided (one launch over all chunks runs one kernel), then the rule
+inline bool tall_plan_records(const TallPlanIn &in, int R, double per_cell, bool dict) {
+    if (in.env_records >= 0) return in.env_records != 0;
+    // (a chunk whose item kind differs from the first chunk's -- carry_dcap >= 0: that one had a value table -- cannot share its
+    // launch anyway, tall_fuse: it goes by its own rule)
+    if (in.carry_records >= 0 && dict == (in.carry_dcap >= 0)) return in.carry_records != 0;
+    return dict && tall_plan_record_growth(in.nrow, R, per_cell, dict) <= kTallRecordGrowth;
 }
 
 inline bool tall_width_ok(int c) { return c >= kTallCmin && c <= kTallCmax && c % kTallCstep == 0; }
@@ -172,6 +209,7 @@ inline TallPlan tall_plan(const TallPlanIn &in) {
         tall_plan_split_geometry(in, T, per_row / (double)T, &R, &S);
         if (S > 1) {
             best.R = R; best.C = C; best.S = S; best.T = T; best.dcap = dict ? kTallDictMax : 0;
+            best.records = tall_plan_records(in, R, per_row / (double)T, dict);
             tall_plan_layout(best);
             return best;
         }
@@ -203,6 +241,7 @@ inline TallPlan tall_plan(const TallPlanIn &in) {
         const int room = (kTallLdsBytes - tall_sums_bytes(std::max(keep, best.R)) - 16 * best.C) / 8;
         best.dcap = std::min(kTallDictMax, std::max(best.dcap, room / 64 * 64));
     }
+    best.records = tall_plan_records(in, best.R, per_row / (double)best.T, dict);
     tall_plan_layout(best);
     return best;
 }

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "slp_common.h"
@@ -48,14 +49,17 @@ struct TallRegs {
 // below: one piece on the first C / 2 lanes.  C / 2 is a multiple of 64, so either test is the same for a whole wave.
 // CT: the width as a constant (0: the argument `cw`) -- instantiated for the widths the benchmark's LP runs on, where the folded
 // tile tests and tile offsets are worth 1.2 % of a product (21.79 -> 22.05 ms with 4096 columns as an argument).
-template <bool DICT, bool ACC, bool POW = false, int CT = 0>
+// REC: the copy's packets hold the first four list positions as one 16-byte record per lane (slp_tall_item.h; the planner's
+// choice per copy, StripJds::tall_records) -- one load where the slot-major form takes four.  REC = false is the kernel as it
+// was before the form existed, instruction for instruction.
+template <bool DICT, bool ACC, bool POW = false, int CT = 0, bool REC = false>
 __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__restrict__ wgs, const double *__restrict__ dict_arg,
                                                       const double *__restrict__ x, double *__restrict__ out, double pw, const int cw,
                                                       const int dcap, const int oxt) {
     const int C = CT ? CT : cw;
     constexpr int kDepth = DICT ? kTallDepth : 2;
     // LDS address 0 is a scratch cell: whatever is not a lane's item -- a slot beyond its list (the load past the buffer
-    // descriptor returns 0), a skip item -- decodes to sum field 0, value id 0, column 0 and adds into the
+    // descriptor returns 0), a skip item, a padding word of a record -- decodes to sum field 0, value id 0, column 0 and adds into the
     // scratch cell: no predicate on the stores, none on the sums
     extern __shared__ __attribute__((aligned(16))) double tall_lds[];
     double *const dv = tall_lds + kTallItemTableByte / 8;
@@ -95,7 +99,8 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
     const __amdgpu_buffer_rsrc_t rs_x =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(x + wg.x0), 0, (int)(wg.ncol * 8), 0x00020000);
 
-    // A slot is `width` words from word `so` of the payload.  ONE descriptor per segment (the payload's; the fp64 values'): a
+    // A slot is `width` words from word `so` of the payload (so are a packet's records, four words per lane, and its words of
+    // fifth bytes; slp_tall_item.h: the order).  ONE descriptor per segment (the payload's; the fp64 values'): a
     // slot's load differs from its neighbour's in the scalar offset (the slot's first byte) and in num_records (the slot's LAST
     // byte + 1) only, so the four descriptor words stay in one register quad whose third word is rewritten in front of each
     // load -- with the sum the next slot's offset needs anyway.  The range check of a raw buffer on this hardware covers the
@@ -175,9 +180,26 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
         // compiler then counts the loads in flight by the path without them (vmcnt(24-26) instead of 36-41): exact for those
         // packets, a shorter prefetch distance behind a packet that has the second group.  3.30 / 3.30 -> 3.25 / 3.22 ms on the
         // slice, unchanged where lists are five long (profiles/r05_tall_half_packets.log).
-        if (part == 0 || wbytes < t.w[4]) {   // (per wave: the waves past the fifth items' lanes skip them too)
+        if (REC && part == 0) {
+            // slots 0-3 of a copy with records: the lane's four items (16 bytes at 16 p of the packet's first 4 w[0] words) in ONE
+            // load, and its word of fifth bytes behind the records -- lanes past w[0] lie behind the descriptor's end, a list
+            // shorter than four has zero words (the scratch cell) in its record
+            const unsigned int so = t.off, end = so + 4u * t.w[0];   // (bytes)
+            const auto v = __builtin_amdgcn_raw_buffer_load_b128(slot_pay(end), 4u * mine, (int)so, 2);   // streamed once
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g.lo[k] = v[k];
+            if (!DICT) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {   // the four values: double i of the parallel array belongs to word i
+                    const auto u = __builtin_amdgcn_raw_buffer_load_b128(slot_val(end), 8u * mine + 16u * (unsigned int)h, (int)(2u * so), 2);
+                    g.val[DICT ? 0 : 2 * h] = __hiloint2double((int)u[1], (int)u[0]);
+                    g.val[DICT ? 0 : 2 * h + 1] = __hiloint2double((int)u[3], (int)u[2]);
+                }
+            }
+            if (DICT) g.hi[0] = __builtin_amdgcn_raw_buffer_load_b32(slot_pay(end + t.w[0]), mine, (int)end, 2);
+        } else if (part == 0 || wbytes < t.w[4]) {   // (per wave: the waves past the fifth items' lanes skip them too)
             unsigned int so = t.off;   // (bytes)
-            if (part == 1) so += t.w[0] + t.w[1] + t.w[2] + t.w[3];
+            if (part == 1) so += tall_packet_group1_word(t.w, DICT, REC);   // (slot-major: w[0] + w[1] + w[2] + w[3])
 #pragma unroll
             for (int k = 4 * part; k < 4 * part + 4; ++k) {
                 const unsigned int end = so + t.w[k];   // (= the next slot's first byte)
@@ -190,7 +212,7 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
             }
             if (DICT) {
                 if (part == 0) so += t.w[4] + t.w[5] + t.w[6] + t.w[7];   // the fifth bytes follow the eight slots: slots 0-3, then slots 4-7
-                else so += t.w[0];
+                else if (!REC) so += t.w[0];                              // (records: those of slots 4-7 follow slot 7 directly)
                 g.hi[DICT ? part : 0] = __builtin_amdgcn_raw_buffer_load_b32(slot_pay(so + t.w[4 * part]), mine, (int)so, 2);
             }
         }
@@ -332,10 +354,15 @@ static void tall_launch(const StripJds &f, unsigned grid, int nseg, const TallWg
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTallT), (size_t)lay.lds_bytes, ctx().stream, nseg, wgs, dict, x, out, pw, lay.C, lay.dcap,
                            lay.off_xt / 8);
     };
-    static bool raised[3] = {false, false, false};   // (per instantiation)
-    if (DICT && !POW && lay.C == 3072) go(k_tall_spmv<DICT, ACC, POW, (DICT && !POW) ? 3072 : 0>, raised[1]);
-    else if (DICT && !POW && lay.C == 4096) go(k_tall_spmv<DICT, ACC, POW, (DICT && !POW) ? 4096 : 0>, raised[2]);
-    else go(k_tall_spmv<DICT, ACC, POW, 0>, raised[0]);
+    static bool raised[2][3] = {{false, false, false}, {false, false, false}};   // (per instantiation: the packets' form, the width)
+    auto by_width = [&](auto rec) {   // rec: the packets' form as a constant
+        constexpr bool REC = decltype(rec)::value;
+        if (DICT && !POW && lay.C == 3072) go(k_tall_spmv<DICT, ACC, POW, (DICT && !POW) ? 3072 : 0, REC>, raised[REC][1]);
+        else if (DICT && !POW && lay.C == 4096) go(k_tall_spmv<DICT, ACC, POW, (DICT && !POW) ? 4096 : 0, REC>, raised[REC][2]);
+        else go(k_tall_spmv<DICT, ACC, POW, 0, REC>, raised[REC][0]);
+    };
+    if (f.tall_records) by_width(std::true_type());
+    else by_width(std::false_type());
 }
 
 void tall_spmv(const StripJds &f, const double *x, double *out, int accum) {
@@ -373,6 +400,7 @@ bool tall_fuse(StripJds &f) {
     const StripJds &f0 = *f.parts[0];
     for (const StripJds *g : f.parts)
         if (!g->ok || !g->tall || g->S != 1 || g->C != f0.C || (g->D > 0) != (f0.D > 0) || g->tall_dcap != f0.tall_dcap ||
+            g->tall_records != f0.tall_records ||   // (one launch runs one instantiation of the kernel)
             (f.parts_cols && (g->B != f0.B || g->tall_R != f0.tall_R || g->nrow != f0.nrow)))
             return false;
     std::vector<TallWg> all;
@@ -391,6 +419,7 @@ bool tall_fuse(StripJds &f) {
     // one LDS layout for the launch: the tallest row block's sums, the chunks' common table capacity and strip width
     f.C = f0.C;
     f.tall_dcap = f0.tall_dcap;
+    f.tall_records = f0.tall_records;
     f.tall_R = 0;
     for (const StripJds *g : f.parts) f.tall_R = std::max(f.tall_R, g->tall_R);
     return true;
