@@ -14,6 +14,8 @@
 #include "slp_hip_ext_admm_batch.h"
 /* per-instance stopping of the batched dual gradient ascent: likewise */
 #include "slp_hip_ext_dga_batch.h"
+/* a cut-off for the bound of each LP of the dual-ascent list solver: likewise */
+#include "slp_hip_ext_dga_many.h"
 /* which packet form a tall-cell product copy has: likewise */
 #include "slp_hip_ext_tall.h"
 

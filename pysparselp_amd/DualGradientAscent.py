@@ -9,7 +9,8 @@ matrix and the right-hand sides together (csrc/slp_dga_batch.hip); instance k is
 ``DeviceDGAMany`` / ``dual_gradient_ascent_many`` advance a list of LPs with matrices of their own, one workgroup per LP and whole
 iterations inside a launch (csrc/slp_dga_many.hip); LP k is bit for bit the single solve of ``lps[k]``.
 ``DeviceDGAMany.set_stop`` / ``dual_gradient_ascent_many_until`` stop every LP of such a list on its own, by a test on the step of
-its multipliers inside the iteration kernel.  ``DeviceDGABatch.set_stop`` / ``dual_gradient_ascent_batch_until`` stop every instance
+its multipliers inside the iteration kernel; ``DeviceDGAMany.set_cutoff`` / ``dual_gradient_ascent_many_cutoff`` also once its
+certified lower bound has reached a cut-off, evaluated in the same kernel.  ``DeviceDGABatch.set_stop`` / ``dual_gradient_ascent_batch_until`` stop every instance
 of a batch on its own, on that step or once its certified lower bound has reached a cut-off, tested on the device.
 """
 import os
@@ -673,6 +674,33 @@ class DeviceDGAMany(_DeviceDGA):
         _lib.check(self._l.slp_many_dual_stop_state(self._h, _lib.ptr(iterations), _lib.ptr(stopped), _lib.ptr(step)))
         return iterations, stopped.astype(bool), step
 
+    def set_cutoff(self, tol, check_every=1, targets=None):
+        """``set_stop`` with a cut-off for each LP's bound as well (``slp_many_dual_set_cutoff``): at the end of every iteration
+        ``t`` of an LP with ``t % check_every == 0`` the LP stops iff ``max|y_t - y_{t-1}| <= tol`` or its dual energy, bit for bit
+        ``report()[k, 0]`` after ``t`` iterations, is ``>= targets[k]``; both are looked at.  ``tol`` None: no step test (the step is
+        still recorded); ``targets`` None: no bound test -- ``set_cutoff(tol, check_every)`` is ``set_stop(tol, check_every)`` --
+        else a scalar or one cut-off per LP, ``+inf`` for an LP without one (a NaN or ``-inf`` is a ``ValueError``); both None turn
+        the test off.  While cut-offs are armed the bound of every moving LP is evaluated and recorded at every check, inside the
+        iteration kernel.  A NaN in either quantity never stops, nor does an LP whose status carries the NaN bit.  With cut-offs
+        an LP of more than 65536 rows is refused (``SlpError``).  As with ``set_stop`` a stopped LP keeps its multipliers, the x
+        of the top of iteration ``t``, its tie-draw count and its flags, takes no part in later launches and cannot be resumed;
+        a new rule applies to the LPs still moving."""
+        if tol is None and targets is None:
+            check_every = 1
+        else:
+            tol, targets, check_every = _check_batch_stop(tol, targets, check_every, self.count)
+        _lib.check(self._l.slp_many_dual_set_cutoff(self._h, -1.0 if tol is None else tol, _lib.ptr(targets), check_every))
+
+    def stop_state_full(self):
+        """``(iterations, stopped, step, bound, reason)`` per LP -- int64, bool, float64, float64 and int32 arrays, as
+        ``DeviceDGABatch.stop_state``: the first three are ``stop_state()``, ``bound`` is the last evaluated bound (``-inf`` before
+        the first check with cut-offs: always a valid lower bound) and ``reason`` why the LP stopped, a bit mask: 0 = moving or
+        frozen, 1 = step, 2 = bound, 3 = both at the same check."""
+        iterations, reason = np.zeros(self.count, dtype=np.int64), np.zeros(self.count, dtype=np.int32)
+        step, bound = np.zeros(self.count), np.zeros(self.count)
+        _lib.check(self._l.slp_many_dual_cutoff_state(self._h, _lib.ptr(iterations), _lib.ptr(reason), _lib.ptr(step), _lib.ptr(bound)))
+        return iterations, reason != 0, step, bound, reason
+
 
 def dual_gradient_ascent_many(lps, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None):
     """``dual_gradient_ascent`` on every LP of ``lps`` -- LPs whose constraint matrices differ -- all advancing together on the
@@ -716,10 +744,38 @@ def dual_gradient_ascent_many_until(lps, tol, check_every=10, nb_max_iter=1000, 
     return xs, y_eqs, y_ineqs, info
 
 
-def _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, frozen_out=None, stop=None):
+def dual_gradient_ascent_many_cutoff(lps, tol, check_every=10, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None,
+                                     targets=None):
+    """``dual_gradient_ascent_many_until`` with a cut-off for each LP's certified lower bound as well -- nodes of a branch and bound,
+    whose matrices differ: an LP whose bound has passed the incumbent is pruned and costs nothing more.  Returns ``(xs, y_eqs,
+    y_ineqs, info)``.
+
+    At the end of every iteration ``t`` of an LP with ``t % check_every == 0``, inside the iteration kernel
+    (``DeviceDGAMany.set_cutoff``), the LP stops iff ``step_t = max|y_t - y_{t-1}| <= tol`` or ``bound_t``, the dual energy of
+    ``y_t``, is ``>= targets[k]``; both are looked at, a NaN never stops.  At least one of ``tol`` (a finite float ``>= 0``, or None:
+    no step test) and ``targets`` (a scalar or one value per LP; ``+inf``: no cut-off for that LP; no NaN, no ``-inf``; or None: no
+    bound test, which is ``dual_gradient_ascent_many_until``) is required, ``check_every`` is an int ``>= 1``: a ``ValueError`` before
+    the library is loaded otherwise.  With ``targets`` every LP has at most 65536 rows.
+
+    ``info`` is that of ``dual_gradient_ascent_many_until`` and, with ``targets``, also has ``bound`` (float64: the last bound
+    evaluated at a check, ``-inf`` before the first) and ``reason`` (int32 bit mask: 0 moving or frozen, 1 step, 2 bound, 3 both at
+    the same check).  For an LP stopped at a check with cut-offs ``info["lower_bound"][k] == info["bound"][k]``, bit for bit."""
+    try:
+        lps = list(lps)
+    except TypeError:
+        raise ValueError("lps must be a sequence of LP objects") from None
+    if targets is None and tol is not None:
+        return dual_gradient_ascent_many_until(lps, tol, check_every, nb_max_iter, callback_func, y_eq, y_ineq, max_time)
+    cutoff = _check_batch_stop(tol, targets, check_every, len(lps))
+    xs, y_eqs, y_ineqs, report, info = _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, cutoff=cutoff)
+    return xs, y_eqs, y_ineqs, info
+
+
+def _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, frozen_out=None, stop=None, cutoff=None):
     """``dual_gradient_ascent_many`` plus, as a fourth value, the final ``DeviceDGAMany.report()`` and, as a fifth, the ``info`` of
-    ``dual_gradient_ascent_many_until`` (``stop`` the checked ``(tol, check_every)``; None without a stopping test); ``frozen_out``:
-    a list that receives the frozen flags before the first iteration."""
+    ``dual_gradient_ascent_many_until`` (``stop`` the checked ``(tol, check_every)``) or of ``dual_gradient_ascent_many_cutoff``
+    (``cutoff`` the checked ``(tol, targets, check_every)``); None without a stopping test.  ``frozen_out``: a list that receives
+    the frozen flags before the first iteration."""
     start = time.perf_counter()
     try:
         lps = list(lps)
@@ -736,14 +792,25 @@ def _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, froze
         if frozen_out is not None:
             frozen_out[:] = frozen.tolist()
         info, all_still = None, None
-        if stop is not None:
+        if stop is not None or cutoff is not None:
             everyone = np.arange(state.count)
             info = _many.new_stop_info(state.count, everyone)
             info["lower_bound"] = np.full(state.count, np.nan)
-            state.set_stop(*stop)
+            if cutoff is not None:
+                info["bound"] = np.full(state.count, -np.inf)
+                info["reason"] = np.zeros(state.count, dtype=np.int32)
+                state.set_cutoff(cutoff[0], cutoff[2], cutoff[1])
+            else:
+                state.set_stop(*stop)
+
+            def refresh():
+                if cutoff is None:
+                    _many.spread_stop_state(info, everyone, state.stop_state())
+                else:
+                    info["iterations"][:], info["stopped"][:], info["step"][:], info["bound"][:], info["reason"][:] = state.stop_state_full()
 
             def all_still():
-                _many.spread_stop_state(info, everyone, state.stop_state())
+                refresh()
                 if callback_func is not None:
                     try:
                         callback_func.info = info
@@ -755,7 +822,7 @@ def _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, froze
         yes, yis = state.y()
         report = state.report()
         if info is not None:
-            _many.spread_stop_state(info, everyone, state.stop_state())
+            refresh()
             info["lower_bound"][:] = report[:, 0]
         return state.x(), yes, [yi if h else None for yi, h in zip(yis, has_ineq)], report, info
     finally:

@@ -997,10 +997,32 @@ def solve_dga_many_until(lps, tol, check_every=10, get_timing=True, nb_iter=1000
     those multipliers: a certified lower bound on that LP's value.  A stopped LP records nothing after it has stopped, so for
     every LP ``xs[k]`` and every curve apart from the times are bit for bit those of ``lps[k].solve(method=
     "dual_gradient_ascent", nb_iter=lp.nb_iterations)``.  ``max_time`` stops all LPs at a report."""
-    from .DualGradientAscent import _dga_many_run
+    check_stop(tol, check_every)
+    return _solve_dga_many_stopping(lps, tol, check_every, get_timing, nb_iter, max_time, None)
 
-    stop = check_stop(tol, check_every)
+
+def solve_dga_many_cutoff(lps, tol, check_every=10, get_timing=True, nb_iter=10000, max_time=None, targets=None):
+    """``solve_dga_many_until`` with a cut-off for each LP's certified lower bound as well
+    (``DualGradientAscent.dual_gradient_ascent_many_cutoff``): an LP also stops at the first check at which the dual energy of its
+    multipliers is ``>= targets[k]``.  ``tol`` may be None (no step test) when ``targets`` -- a scalar or one value per LP, ``+inf``
+    for an LP without a cut-off -- is given; with ``targets`` None it is ``solve_dga_many_until``.  Bad arguments raise
+    ``ValueError`` before the library is loaded.
+
+    With ``targets`` it also sets ``lp.stop_reason`` (int bit mask: 0 not stopped, 1 step, 2 bound, 3 both at the same check).
+    ``lp.dual_lower_bound`` stays the energy of the returned multipliers; for an LP stopped at a check with cut-offs it is, bit for
+    bit, the bound that check evaluated."""
+    return _solve_dga_many_stopping(lps, tol, check_every, get_timing, nb_iter, max_time, targets)
+
+
+def _solve_dga_many_stopping(lps, tol, check_every, get_timing, nb_iter, max_time, targets):
+    """``solve_dga_many_until`` (``targets`` None) and ``solve_dga_many_cutoff``."""
+    from .DualGradientAscent import _check_batch_stop, _dga_many_run
+
     lps = list(lps)
+    if targets is None and tol is not None:
+        stop, cutoff = check_stop(tol, check_every), None
+    else:   # (both None: the refusal of _check_batch_stop)
+        stop, cutoff = None, _check_batch_stop(tol, targets, check_every, len(lps))
     if len(lps) < 1:
         raise ValueError("an empty list of LPs")
     start = time.perf_counter()
@@ -1016,10 +1038,12 @@ def solve_dga_many_until(lps, tol, check_every=10, get_timing=True, nb_iter=1000
         skip[:] = np.asarray(frozen, dtype=bool) | (info["stopped"] & (info["iterations"] < niter + 1))
         fill(niter, *report)
 
-    xs, y_eqs, y_ineqs, _, info = _dga_many_run(lps, nb_iter, record, None, None, max_time, frozen_out=frozen, stop=stop)
+    xs, y_eqs, y_ineqs, _, info = _dga_many_run(lps, nb_iter, record, None, None, max_time, frozen_out=frozen, stop=stop, cutoff=cutoff)
     for k, lp in enumerate(lps):
         lp.nb_iterations = int(info["iterations"][k])
         lp.stopped = bool(info["stopped"][k])
+        if cutoff is not None:
+            lp.stop_reason = int(info["reason"][k])
         lp.dual_multipliers = (y_eqs[k], y_ineqs[k])
         lp.dual_lower_bound = float(info["lower_bound"][k])
     elapsed = time.perf_counter() - start

@@ -1,5 +1,5 @@
 """ctypes binding of libslp_hip.so (include/slp_hip.h, include/slp_hip_ext.h, include/slp_hip_ext_admm_batch.h,
-include/slp_hip_ext_dga_batch.h and include/slp_hip_ext_tall.h).
+include/slp_hip_ext_dga_batch.h, include/slp_hip_ext_dga_many.h and include/slp_hip_ext_tall.h).
 
 The library is the only execution path: if it is missing, cannot be loaded, or
 finds no HIP device, every solver entry point raises -- there is no CPU
@@ -276,6 +276,14 @@ _EXT_DGA_BATCH_SIGNATURES = {
 
 EXT_DGA_BATCH_SYMBOLS = tuple(_EXT_DGA_BATCH_SIGNATURES)
 
+# name -> (restype, argtypes); mirrors include/slp_hip_ext_dga_many.h (which slp_hip_ext.h includes) one to one
+_EXT_DGA_MANY_SIGNATURES = {
+    "slp_many_dual_set_cutoff": (c_int, [c_vp, c_dbl, c_vp, c_i64]),
+    "slp_many_dual_cutoff_state": (c_int, [c_vp] * 5),
+}
+
+EXT_DGA_MANY_SYMBOLS = tuple(_EXT_DGA_MANY_SIGNATURES)
+
 # name -> (restype, argtypes); mirrors include/slp_hip_ext_tall.h (which slp_hip_ext.h includes) one to one
 _EXT_TALL_SIGNATURES = {
     "slp_matrix_tall_records": (c_i64, [c_vp, c_int]),
@@ -306,7 +314,8 @@ def load():
     except OSError as e:
         raise SlpError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_EXT_ADMM_BATCH_SIGNATURES.items())
-                              + list(_EXT_DGA_BATCH_SIGNATURES.items()) + list(_EXT_TALL_SIGNATURES.items())):
+                              + list(_EXT_DGA_BATCH_SIGNATURES.items()) + list(_EXT_DGA_MANY_SIGNATURES.items())
+                              + list(_EXT_TALL_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -27,14 +27,18 @@
 //
 // Launch cap: slp_many_plan.h (switch SLP_DGA_MANY_KMAX).  A pass is the workgroup once over its columns, its rows, a round of the
 // gradient pass or a stage of the sort (dgm_passes); a launch also holds no more iterations than the draws on the device allow
-// (two per iteration behind the furthest LP).
+// (two per iteration behind the furthest LP).  The cap is a function of the shapes only, whatever test is armed: a check iteration
+// with the bound test (below) adds at most one pass over the columns and one over the rows -- ceil((ceil(n / 256) + ceil(m / 256))
+// / 4) rounds of 1024 lanes, a lane one column or one row each -- to an iteration that has at least a column and a row pass of its
+// own and, per kind of rows, a further column pass, a row pass, the gradient pass, the sort and the scans: less than doubles
+// dgm_passes' smallest term, at check iterations only.
 //
 // Tie draws: all LPs read the one stream of uniform draws, LP k at its own position draw_offset_k + consumed_k (draw_offset_k: the
 // draws its default start took).  The device holds a window of the stream from the smallest position on.
 // Report, frozen test and start are ordinary launches over (kDgaParts, count) with the shared energy bodies.
 //
 // Stopping (slp_many_dual_set_stop; off after create).  DgmStop, one per LP in device memory, in an array of its own beside DgaCtl
-// (whose layout the single and the batched solver share): iterations completed, the last evaluated step, the stopped flag.
+// (whose layout the single and the batched solver share): iterations completed, the last evaluated step (and bound), the stopped flag (`reason`).
 // Iterations of an LP count from 1 over its whole life; y_t = [y_eq; y_ineq] are its multipliers after iteration t, the inequality
 // part after its clamp.  step_t = max_r |y_t,r - y_{t-1},r| over all its rows, as np.max (a NaN stays); a kind of rows that does not
 // move in iteration t (block predicate false) contributes 0.  At the end of an iteration t with t % check_every == 0 the LP stops
@@ -53,6 +57,18 @@
 // without it, and the draws behind its position may be gone.  Hence it cannot be resumed: unlike slp_many_cp_set_stop, no call of
 // slp_many_dual_set_stop clears a stopped flag.  While an LP is stopped and the test is off, the launch is the kernel with the test
 // and a cadence that never comes, so that the LP stays where it is.
+//
+// A cut-off for the bound (slp_many_dual_set_cutoff, include/slp_hip_ext_dga_many.h): the second template parameter, BOUND.
+// <false, false> and <true, false> are the two kernels above.  <true, true>, launched while cut-offs are armed, also evaluates at
+// every check of every moving LP bound_t = the dual energy of y_t, bit for bit column 0 of slp_many_dga_report after t iterations,
+// and the LP stops iff step_t <= tol (tol >= 0) or bound_t >= targets[k] (targets[k] < +inf) -- the rule of k_dgab_decide; the
+// record's `reason` names which (bit 0 step, bit 1 bound), and "stopped" is reason != 0.  The report sums a term per column,
+// min(c_bar ub, c_bar lb) where c_bar != 0, and a term per row, y b where y != 0, each alone in lane j % 256 of workgroup j / 256
+// of a (kDgaParts, count) x 256 launch (n <= 8192; m <= 65536, which arming with cut-offs checks), block_reduce per workgroup and
+// the kDgaParts results added in order on the host.  The kernel forms the same parts with its four virtual blocks, four parts per
+// round of dga_block_reduce, and lane 0 adds them in order.  The column terms come from a walk of K^T over the new y that stores
+// nothing: x and c_bar stay those of the top of the iteration, which is what a stopped LP keeps.  The parts go through part_min
+// (columns) and part_gb (rows), dead behind the last kind's search; no LDS is added, no atomic, no wait.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -61,6 +77,7 @@
 #include "slp_kernels.h"
 #include "slp_dga_shared.h"
 #include "slp_many.h"
+#include "../../include/slp_hip_ext_dga_many.h"
 
 using namespace slp;
 
@@ -90,19 +107,21 @@ struct DgmArgs {
 struct DgmStop {
     i64 done;       // whole iterations completed (the kernel without the test does not count: slp_many_dga::uncounted)
     double step;    // the last evaluated max |y_t - y_{t-1}|, +inf before the first test
-    i32 stopped, pad;
+    double bound;   // the last evaluated dual energy (BOUND), -inf before the first
+    i32 reason, pad;   // bit 0: the step met tol, bit 1: the bound met the cut-off; 0 while the LP is not stopped
 };
 
 struct DgmStopArgs {
     DgmStop *rec;
-    double tol;
+    double tol;               // < 0: the step is evaluated and recorded, not tested (BOUND only)
+    const double *targets;    // BOUND: a cut-off per LP, +inf for none
     i64 check_every;
 };
 
-// column j of the LP: the two masked sums of K^T y in storage order (k_dgab_cols), c_bar and the dual argmin
+// c_bar of column j of the LP: the two masked sums of K^T y in storage order (k_dgab_cols), then (c + s_eq) + s_ineq
 template <class LD>
-__device__ __forceinline__ void dgm_column(const DgmLp &lp, i32 j, const i64 *tptr, const i32 *tidx, const double *tval, const double *y,
-                                           const double *c, const double *lb, const double *ub, double *cbar, double *x, LD ld) {
+__device__ __forceinline__ double dgm_cbar(const DgmLp &lp, i32 j, const i64 *tptr, const i32 *tidx, const double *tval, const double *y,
+                                           const double *c, LD ld) {
     double se = 0.0, si = 0.0;
     for (i64 q = tptr[j]; q < tptr[j + 1]; ++q) {
         const i32 r = tidx[q];
@@ -113,6 +132,14 @@ __device__ __forceinline__ void dgm_column(const DgmLp &lp, i32 j, const i64 *tp
     double cb = c[j];
     if (lp.m_eq > 0) cb = cb + se;
     if (lp.m_in > 0) cb = cb + si;
+    return cb;
+}
+
+// column j of the LP: c_bar and the dual argmin
+template <class LD>
+__device__ __forceinline__ void dgm_column(const DgmLp &lp, i32 j, const i64 *tptr, const i32 *tidx, const double *tval, const double *y,
+                                           const double *c, const double *lb, const double *ub, double *cbar, double *x, LD ld) {
+    const double cb = dgm_cbar(lp, j, tptr, tidx, tval, y, c, ld);
     cbar[j] = cb;
     x[j] = dga_argmin_x(cb, lb[j], ub[j]);
 }
@@ -140,7 +167,8 @@ __device__ __forceinline__ double dgm_dot(i64 s, i64 e, const i32 *idx, const do
 }
 
 // `iters` iterations of the LP blockIdx.x.  STOP: the stopping test of the header comment; `sp` is not looked at without it.
-template <bool STOP>
+// BOUND (with STOP only): a check iteration also evaluates the bound and tests it against the LP's cut-off.
+template <bool STOP, bool BOUND>
 __global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int iters, DgmStopArgs sp) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dgm_lds[];
     const DgaLoadWorkgroup ld;
@@ -150,7 +178,7 @@ __global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int
     i64 done = 0, until = 0;   // STOP: iterations completed; iterations up to and including the next check
     if (STOP) {
         const DgmStop *rec = sp.rec + blockIdx.x;
-        if (rec->stopped) return;   // set before the launch: the same for every lane
+        if (rec->reason) return;    // set before the launch: the same for every lane
         done = rec->done;           // lane 0 writes the record only behind a barrier that follows this load
         until = sp.check_every - done % sp.check_every;
     }
@@ -223,19 +251,69 @@ __global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int
             until = sp.check_every;
             DgmStop *rec = sp.rec + blockIdx.x;
             double *red = reinterpret_cast<double *>(dgm_lds);   // the 16 reduction slots: one per wave
+            const i32 cparts = (n + kBlock - 1) / kBlock, parts = cparts + (m + kBlock - 1) / kBlock;
+            if (BOUND) {
+                // The dual energy of the new y as the report sums it.  There term j of the columns (i of the rows) is alone in lane
+                // j % 256 of workgroup j / 256 (n <= 8192 and m <= 65536 = kDgaParts * kBlock, which arming has checked): the
+                // lane's 0.0 + term, a block_reduce per workgroup, the workgroups' results added in order from 0.0.  Here a part
+                // is one virtual block's dga_block_reduce, four parts per round: first the column parts (the walk of dgm_column on
+                // the new y; nothing is stored to x or c_bar, which stay those of the top of this iteration), then the row parts.
+                // part_min and part_gb of the gradient pass are dead here -- every iteration writes all of them before it reads
+                // one -- and take the column and the row parts.  The loop is bounded by the shape: uniform, and so are its barriers.
+                for (i32 p0 = 0; p0 < parts; p0 += 4) {
+                    const i32 p = p0 + group;
+                    double term = 0.0;
+                    if (p < cparts) {
+                        const i32 j = p * kBlock + tl;
+                        if (j < n) {
+                            const double cb = dgm_cbar(lp, j, tptr, a.tidx, a.tval, y, c, ld);
+                            if (cb != 0.0) {
+                                const double u = cb * ub[j], l = cb * lb[j];
+                                term = 0.0 + ((u < l) ? u : l);   // the report's lane starts from acc = 0.0: a term of -0.0 becomes +0.0
+                            }
+                        }
+                    } else if (p < parts) {
+                        const i32 i = (p - cparts) * kBlock + tl;
+                        if (i < m) {
+                            const double yi = ld(y + i);
+                            if (yi != 0.0) term = 0.0 + yi * b[i];
+                        }
+                    }
+                    const double s = dga_block_reduce<false>(term, tl, slots);
+                    if (tl == 0 && p < cparts) part_min[p] = s;
+                    else if (tl == 0 && p < parts) part_gb[p - cparts] = s;
+                }
+            }
             dy = many_wave_nanmax(dy);
             if ((tid & (kWave - 1)) == 0) red[tid / kWave] = dy;
             __syncthreads();
             if (tid == 0) {
                 double step = red[0];
                 for (int w = 1; w < kDgaFusedThreads / kWave; ++w) step = nan_max(step, red[w]);
-                const int stop = (step <= sp.tol && !(ctl->flags & DGA_NAN)) ? 1 : 0;   // false for a NaN
-                rec->step = step;
-                rec->done = done;
-                rec->stopped = stop;
+                if (BOUND) {
+                    // the report's sequential sums of its kDgaParts partial results (dga_bound_finish).  Its parts past the last
+                    // term are +0.0, and a sum that starts at +0.0 is never -0.0 (no term is), so adding them changes no bit: the
+                    // fold ends at the last used part.
+                    double e = 0.0, yb = 0.0;
+                    for (i32 p = 0; p < cparts; ++p) e += ld(part_min + p);
+                    for (i32 p = 0; p < parts - cparts; ++p) yb += ld(part_gb + p);
+                    const double bound = e - yb, target = sp.targets[blockIdx.x];
+                    const bool sound = !(ctl->flags & DGA_NAN);   // an LP that has met a NaN breakpoint or step certifies nothing
+                    int reason = (sound && sp.tol >= 0.0 && step <= sp.tol) ? 1 : 0;            // false for a NaN
+                    if (sound && target < __builtin_inf() && bound >= target) reason |= 2;      // false for a NaN
+                    rec->step = step;
+                    rec->bound = bound;
+                    rec->done = done;
+                    rec->reason = reason;
+                } else {
+                    const int stop = (step <= sp.tol && !(ctl->flags & DGA_NAN)) ? 1 : 0;   // false for a NaN
+                    rec->step = step;
+                    rec->done = done;
+                    rec->reason = stop;
+                }
             }
             __syncthreads();   // the two barriers the test adds, in a check iteration only
-            if (ld(&rec->stopped)) break;   // read by all lanes after the barrier: uniform
+            if (ld(&rec->reason)) break;   // read by all lanes after the barrier: uniform
         }
     }
     if (STOP && tid == 0) sp.rec[blockIdx.x].done = done;
@@ -288,10 +366,13 @@ struct slp_many_dga {
     DgaDrawWindow draws;   // the host's view of rnd (slp_dga_draws.h)
     i64 iters = 0;
     StageTimer timer;
-    // stopping: off while tol < 0.  The kernel without the test touches no record, so the iterations it runs are counted here and
-    // added to the record of every moving LP when the test is armed (and when the state is read)
+    // stopping: the step test is off while tol < 0, the bound test while has_targets is false; off when both are.  The kernel
+    // without the test touches no record, so the iterations it runs are counted here and added to the record of every moving LP
+    // when the test is armed (and when the state is read)
     DevBuf<DgmStop> stop;
+    DevBuf<double> targets;   // a cut-off per LP, allocated at the first arming with cut-offs
     double tol = -1.0;
+    bool has_targets = false;
     i64 check_every = 1, uncounted = 0;
     bool any_stopped = false;   // from now on every launch is the kernel with the test: a stopped LP stays where it is
 };
@@ -371,16 +452,31 @@ void dgm_read_ctl(slp_many_dga *s, std::vector<DgaCtl> &h, std::vector<DgmStop> 
     rec.resize((size_t)s->count);
     s->stop.download(rec.data(), (size_t)s->count);
     for (size_t k = 0; k < rec.size(); ++k)
-        if (!h[k].frozen && !rec[k].stopped) rec[k].done += s->uncounted;
+        if (!h[k].frozen && !rec[k].reason) rec[k].done += s->uncounted;
     s->draws.observe(dga_furthest_reader(
-        h.size(), [&](size_t k) { return !h[k].frozen && !rec[k].stopped; },
+        h.size(), [&](size_t k) { return !h[k].frozen && !rec[k].reason; },
         [&](size_t k) { return (uint64_t)(s->lps[k].draw_offset + h[k].consumed); }));
 }
 
 bool dgm_any_moves(const std::vector<DgaCtl> &h, const std::vector<DgmStop> &rec) {
     for (size_t k = 0; k < h.size(); ++k)
-        if (!h[k].frozen && !rec[k].stopped) return true;
+        if (!h[k].frozen && !rec[k].reason) return true;
     return false;
+}
+
+// the rule of the stopping test from now on: tol < 0 = no step test, targets == NULL = no bound test; both checked by the caller
+void dgm_set_rule(slp_many_dga *s, double tol, const double *targets, i64 check_every) {
+    std::vector<DgaCtl> h;
+    std::vector<DgmStop> rec;
+    dgm_read_ctl(s, h, &rec);   // synchronises; the iterations of the launches without the test are in the records now
+    s->stop.upload(rec.data(), rec.size());
+    s->uncounted = 0;
+    s->any_stopped = false;
+    for (const DgmStop &r : rec) s->any_stopped = s->any_stopped || r.reason;   // the marks stay: a stopped LP cannot be resumed
+    if (targets) s->targets.upload(targets, (size_t)s->count);
+    s->has_targets = targets != nullptr;
+    s->tol = tol < 0.0 ? -1.0 : tol;
+    if (tol >= 0.0 || targets) s->check_every = check_every;
 }
 
 }  // namespace
@@ -469,10 +565,11 @@ slp_many_dga *slp_many_dga_create(int64_t count, const int64_t *n, const int64_t
         s->rnd.alloc(1);
         s->ctl.alloc(sc);
         s->ctl.zero();
-        for (const void *kernel : {reinterpret_cast<const void *>(k_dgm_iterate<false>), reinterpret_cast<const void *>(k_dgm_iterate<true>)})
+        for (const void *kernel : {reinterpret_cast<const void *>(k_dgm_iterate<false, false>), reinterpret_cast<const void *>(k_dgm_iterate<true, false>),
+                                   reinterpret_cast<const void *>(k_dgm_iterate<true, true>)})
             SLP_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kDgmSlotBytes + fused_lds_bytes(kDgaFusedMax))));
         {
-            const std::vector<DgmStop> rec(sc, DgmStop{0, __builtin_inf(), 0, 0});
+            const std::vector<DgmStop> rec(sc, DgmStop{0, __builtin_inf(), -__builtin_inf(), 0, 0});
             s->stop.upload(rec.data(), sc);
         }
         dgm_argmin(s.get(), s->cbar.p, s->x.p);   // the x of y0: what a frozen LP keeps
@@ -497,8 +594,8 @@ int slp_many_dga_iterate(slp_many_dga *s, int64_t k) {
         SLP_REQUIRE(s && k >= 0, "slp_many_dga_iterate: bad arguments");
         hipStream_t st = ctx().stream;
         // with the test: armed, or off with an LP that has to stay stopped (a cadence that never comes)
-        const bool stop = s->tol >= 0.0 || s->any_stopped;
-        const DgmStopArgs sp = {s->stop.p, s->tol, s->tol >= 0.0 ? s->check_every : INT64_MAX};
+        const bool armed = s->tol >= 0.0 || s->has_targets, stop = armed || s->any_stopped;
+        const DgmStopArgs sp = {s->stop.p, s->tol, s->targets.p, armed ? s->check_every : INT64_MAX};
         if (stop) {   // when every LP is stopped or frozen nothing is launched and the count of iterations stays
             std::vector<DgaCtl> h;
             std::vector<DgmStop> rec;
@@ -511,8 +608,9 @@ int slp_many_dga_iterate(slp_many_dga *s, int64_t k) {
             if (it < 1) return it;
             const dim3 grid((unsigned)s->count), block(kDgaFusedThreads);
             s->timer.mark(-1);
-            if (stop) hipLaunchKernelGGL(k_dgm_iterate<true>, grid, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp);
-            else hipLaunchKernelGGL(k_dgm_iterate<false>, grid, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp);
+            if (s->has_targets) hipLaunchKernelGGL((k_dgm_iterate<true, true>), grid, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp);
+            else if (stop) hipLaunchKernelGGL((k_dgm_iterate<true, false>), grid, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp);
+            else hipLaunchKernelGGL((k_dgm_iterate<false, false>), grid, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp);
             s->timer.mark(ST_FUSED);
             s->iters += it;
             if (!stop) s->uncounted += it;
@@ -528,7 +626,7 @@ int slp_many_dga_push_random(slp_many_dga *s, const double *draws, int64_t count
         std::vector<DgmStop> rec;
         dgm_read_ctl(s, h, &rec);
         // (an LP never reaches what lies before its offset: the start of the stream went into the default starts)
-        dga_push_draws(h, [s](size_t k) { return s->lps[k].draw_offset; }, [&](size_t k) { return !h[k].frozen && !rec[k].stopped; }, s->draws,
+        dga_push_draws(h, [s](size_t k) { return s->lps[k].draw_offset; }, [&](size_t k) { return !h[k].frozen && !rec[k].reason; }, s->draws,
                        s->rnd, draws, count, kAppendFirst);
     })
 }
@@ -567,15 +665,26 @@ int slp_many_dual_set_stop(slp_many_dga *s, double tol, int64_t check_every) {
         SLP_REQUIRE(s, "slp_many_dual_set_stop: NULL handle");
         SLP_REQUIRE(tol < 0.0 || (std::isfinite(tol) && check_every >= 1),
                     "slp_many_dual_set_stop: tol must be finite and >= 0 with check_every >= 1 (tol < 0 turns the test off)");
-        std::vector<DgaCtl> h;
-        std::vector<DgmStop> rec;
-        dgm_read_ctl(s, h, &rec);   // synchronises; the iterations of the launches without the test are in the records now
-        s->stop.upload(rec.data(), rec.size());
-        s->uncounted = 0;
-        s->any_stopped = false;
-        for (const DgmStop &r : rec) s->any_stopped = s->any_stopped || r.stopped;   // the flags stay: a stopped LP cannot be resumed
-        s->tol = tol < 0.0 ? -1.0 : tol;
-        if (tol >= 0.0) s->check_every = check_every;
+        dgm_set_rule(s, tol, nullptr, check_every);
+    })
+}
+
+int slp_many_dual_set_cutoff(slp_many_dga *s, double tol, const double *targets, int64_t check_every) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_dual_set_cutoff: NULL handle");
+        SLP_REQUIRE(tol < 0.0 || std::isfinite(tol), "slp_many_dual_set_cutoff: tol must be finite (tol < 0: no step test)");
+        SLP_REQUIRE((tol < 0.0 && !targets) || check_every >= 1, "slp_many_dual_set_cutoff: check_every must be at least 1");
+        if (targets) {   // nothing is launched or changed before the cut-offs and the shapes are known to be in range
+            for (i64 k = 0; k < s->count; ++k) {
+                SLP_REQUIRE(targets[k] == targets[k] && targets[k] != -INFINITY,
+                            "slp_many_dual_set_cutoff: a cut-off is a number or +inf (none for that LP), not NaN or -inf");
+                const i64 m = (i64)s->lps[(size_t)k].m_eq + s->lps[(size_t)k].m_in;
+                if (m > (i64)kDgaParts * kBlock)
+                    throw Error("slp_many_dual_set_cutoff: LP " + std::to_string(k) + " has " + std::to_string(m) + " rows; the bound test holds at most " +
+                                std::to_string(kDgaParts * kBlock) + " per LP (the step test alone has no such limit)");
+            }
+        }
+        dgm_set_rule(s, tol, targets, check_every);
     })
 }
 
@@ -587,8 +696,23 @@ int slp_many_dual_stop_state(slp_many_dga *s, int64_t *iterations, int32_t *stop
         dgm_read_ctl(s, h, &rec);
         for (size_t k = 0; k < rec.size(); ++k) {
             if (iterations) iterations[k] = rec[k].done;   // 0 for a frozen LP: its workgroup returns before it counts
-            if (stopped) stopped[k] = rec[k].stopped;
+            if (stopped) stopped[k] = rec[k].reason != 0;
             if (step) step[k] = rec[k].step;
+        }
+    })
+}
+
+int slp_many_dual_cutoff_state(slp_many_dga *s, int64_t *iterations, int32_t *reason, double *step, double *bound) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_dual_cutoff_state: NULL handle");
+        std::vector<DgaCtl> h;
+        std::vector<DgmStop> rec;
+        dgm_read_ctl(s, h, &rec);
+        for (size_t k = 0; k < rec.size(); ++k) {
+            if (iterations) iterations[k] = rec[k].done;   // 0 for a frozen LP: its workgroup returns before it counts
+            if (reason) reason[k] = rec[k].reason;
+            if (step) step[k] = rec[k].step;
+            if (bound) bound[k] = rec[k].bound;
         }
     })
 }
