@@ -9,7 +9,30 @@ namespace slp {
 constexpr int kTallC = 4096;       // most columns per strip (12-bit column inside the strip); 32 KB of x
 constexpr int kTallT = 1024;       // threads per workgroup = lanes a cell's rows are dealt to
 constexpr int kTallSlots = 8;      // list positions per packet
+// The product kernel's prefetch depths, in packets (slp_tall_spmv.hip).  Items -- payload words, fp64 values -- are loaded
+// kTallDepth packets before they are taken, headers 2 x kTallDepth; the x-tile pieces a packet carries for the next cell
+// kTallTileDepth <= kTallDepth packets before they are stored (their source column waits in the header ring either way).
+// kTallAhead: the first four items of the NEXT packet are decoded and their values read from the table in front of its barrier.
+// Kernel-lab builds (`make variant`, -DSLP_LAB_VARIANT) may override the three; the shipped text has no switch.
+#if defined(SLP_LAB_VARIANT) && defined(SLP_TALL_DI)
+constexpr int kTallDepth = SLP_TALL_DI;
+#else
 constexpr int kTallDepth = 4;      // packets of payload in flight per lane; headers run 2 x this ahead
+#endif
+#if defined(SLP_LAB_VARIANT) && defined(SLP_TALL_DT)
+constexpr int kTallTileDepth = SLP_TALL_DT;
+#else
+constexpr int kTallTileDepth = 2;   // (a tile comes from L2 / MALL -- x is re-read by every row block -- not from the HBM stream the items' depth is sized for)
+#endif
+#if defined(SLP_LAB_VARIANT) && defined(SLP_TALL_AHEAD)
+constexpr bool kTallAhead = SLP_TALL_AHEAD != 0;
+#else
+constexpr bool kTallAhead = true;
+#endif
+static_assert(kTallTileDepth >= 1 && kTallTileDepth <= kTallDepth, "a tile's source column is taken from the header ring: its packet's header must be unpacked");
+constexpr int tall_lcm(int a, int b) { int m = a; while (m % b) m += a; return m; }
+// packets per turn of the kernel's unrolled loop (every ring index a constant): a workgroup's packets are padded to whole turns
+constexpr int kTallTurn = tall_lcm(2 * kTallDepth, kTallTileDepth);
 constexpr int kTallBuckets = 6;    // rows are ordered by min(entries in the cell, 6), descending
 // (kTallIdBits = 11, kTallColBits = 12, kTallRowBits = 14 and the stored item: slp_tall_item.h)
 constexpr int kTallCellShift = kTallIdBits + kTallColBits + kTallRowBits;  // sort key: cell | row | column | id

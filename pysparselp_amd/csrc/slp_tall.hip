@@ -1024,8 +1024,8 @@ bool tall_build(const CsrDev &a, bool transposed, StripJds &f, const ValueDict *
     for (i64 v = 0; v < V; ++v) {
         if (hext[4 * v + 1] >= limit) return false;  // a workgroup's payload outgrows its 32-bit byte offsets: another format serves
         hbase[v] = hext[4 * v];
-        const i64 np = 1 + hext[4 * v + 3];  // whole groups of 2 x depth packets, then 2 x depth more that are only ever prefetched
-        hpkt[v + 1] = hpkt[v] + (np + 2 * kTallDepth - 1) / (2 * kTallDepth) * (2 * kTallDepth) + 2 * kTallDepth;
+        const i64 np = 1 + hext[4 * v + 3];  // whole turns of the kernel's loop (2 x depth packets), then 2 x depth more that are only ever prefetched
+        hpkt[v + 1] = hpkt[v] + (np + kTallTurn - 1) / kTallTurn * kTallTurn + 2 * kTallDepth;
     }
     hbase[V] = tot_w;
     DevBuf<i64> dpkt;

@@ -22,10 +22,35 @@ struct TallRegs {
     unsigned int lo[kTallSlots];
     unsigned int hi[DICT ? 2 : 1];
     double val[DICT ? 1 : kTallSlots];
+};
+// this lane's 16-byte pieces of an x-tile: a ring of its own (kTallTileDepth), shorter than the items'
+struct TallTile {
     double x[4];
+};
+// the first four items of a packet, decoded: LDS address of the running sum, column, the value (DICT: read from the table)
+struct TallAheadItems {
+    unsigned int sa[4], col[4];
+    double v[4];
 };
 
 // DICT: depth 4 (20 KB of payload per packet); fp64 entries: depth 2 (48 KB per packet, 16 more registers per packet)
+// THE PIPELINE of a wave, packet j of its stream (constants: slp_tall.h; measurements: DESIGN.md section 3 (x)):
+//   header of packet j + 2 depth     loaded (one dword per lane)                       behind packet j's items
+//   header of packet j + depth       unpacked to scalars; its tile word and fifth-item  behind packet j's first four items
+//                                    width wait in rings of `depth` scalars (xwq, c4q)
+//   items of packet j + depth        loaded into the item ring (regs[depth])            first four: with the unpack; rest: behind all items
+//   x-tile pieces of packet          loaded into a ring of their OWN (tiles[tile depth], behind packet j's items; the tile word comes
+//     j + tile depth                 tile depth = 2 <= depth) -- the tile comes from    from the header ring: no header is read twice
+//                                    L2 / MALL, its lead need not be the HBM stream's
+//   first four items of packet j + 1 DICT: decoded (sum address, column, value offset)  behind packet j's first four sum stores, IN FRONT
+//                                    and their four values read from the table, held    of packet j + 1's barrier (`ahead`)
+//                                    in 16 registers
+//   packet j                         [barrier if it opens a cell] tile stores, sum reads and x gathers of the items taken ahead,
+//                                    chain, sum stores; then the second group of four, whole, where a wave has fifth items
+// Loads complete in issue order (vmcnt), so the wait for a tile issued `tile depth` steps ago also covers every item load issued
+// before it: with tile depth 2 the loop waits at vmcnt(5 .. 9) where depth 4 for both waited at vmcnt(15 .. 17) -- an item has had
+// tile depth + 1 steps to land instead of depth; measured no slower (config 4), and the 16 registers pay for the items held ahead.
+// fp64 entries keep one depth (2) for both and take nothing ahead: those bodies are the instructions they were.
 // POW (fp64 entries only): every stored value v enters as |v|^pw * 1.0 -- the sums behind the Chambolle-Pock preconditioners
 // (slp_cp.hip, strip_spmv_abs_pow) over a copy without a value table; the same chain of additions as the CSR walk.
 // A workgroup runs `nseg` packet streams one after the other over ONE set of running sums (descriptor of segment s of workgroup v:
@@ -50,14 +75,18 @@ struct TallRegs {
 // CT: the width as a constant (0: the argument `cw`) -- instantiated for the widths the benchmark's LP runs on, where the folded
 // tile tests and tile offsets are worth 1.2 % of a product (21.79 -> 22.05 ms with 4096 columns as an argument).
 // REC: the copy's packets hold the first four list positions as one 16-byte record per lane (slp_tall_item.h; the planner's
-// choice per copy, StripJds::tall_records) -- one load where the slot-major form takes four.  REC = false is the kernel as it
-// was before the form existed, instruction for instruction.
+// choice per copy, StripJds::tall_records) -- one load where the slot-major form takes four.  REC = false keeps the slot-major
+// loads of before the form existed; the pipeline above is the same for both.
 template <bool DICT, bool ACC, bool POW = false, int CT = 0, bool REC = false>
 __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__restrict__ wgs, const double *__restrict__ dict_arg,
                                                       const double *__restrict__ x, double *__restrict__ out, double pw, const int cw,
                                                       const int dcap, const int oxt) {
     const int C = CT ? CT : cw;
     constexpr int kDepth = DICT ? kTallDepth : 2;
+    constexpr int kTileDepth = kTallTileDepth < kDepth ? kTallTileDepth : kDepth;
+    constexpr int kTurn = tall_lcm(2 * kDepth, kTileDepth);   // packets per turn of the unrolled loop
+    constexpr bool AHEAD = DICT && kTallAhead;
+    static_assert(kTallTurn % kTurn == 0, "a workgroup's packets are whole turns of the loop (slp_tall.hip pads to kTallTurn)");
     // LDS address 0 is a scratch cell: whatever is not a lane's item -- a slot beyond its list (the load past the buffer
     // descriptor returns 0), a skip item, a padding word of a record -- decodes to sum field 0, value id 0, column 0 and adds into the
     // scratch cell: no predicate on the stores, none on the sums
@@ -130,6 +159,7 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
     auto slot_val = [&](unsigned int end) { dval[2] = 2u * end; return as_rsrc(dval); };
 
     TallRegs<DICT> regs[kDepth];
+    TallTile tiles[kTileDepth];
     unsigned int hw[kDepth];        // this lane's dword of the headers of the packets depth .. 2 depth - 1 ahead
 
     // A packet's header is read ONCE, when its payload is about to be issued (`depth` packets before its items are taken):
@@ -160,7 +190,7 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
 
     // this lane's 16-byte pieces of an x-tile (pieces p and p + 1024: doubles 2p, 2p + 1 and 2048 + 2p, 2049 + 2p).  A piece that straddles the end of x
     // (odd width) may fetch the 8 bytes behind it: every device block carries 16 bytes of slack, and no item names that column
-    auto load_tile = [&](TallRegs<DICT> &g, const unsigned int xo) {
+    auto load_tile = [&](TallTile &g, const unsigned int xo) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {   // (a piece the lane does not carry: past the descriptor, no memory request)
             const unsigned int o = (i == 0 ? piece0 : piece1) && xo != kOob ? xo + (unsigned int)i * (unsigned int)(kTallT * 16) : kOob;
@@ -216,20 +246,49 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
                 g.hi[DICT ? part : 0] = __builtin_amdgcn_raw_buffer_load_b32(slot_pay(so + t.w[4 * part]), mine, (int)so, 2);
             }
         }
-        if (part == 1) {   // the tile of the packet `depth` ahead: behind all of this packet's items
-            // columns past ncol read 0: the displacement of each double is part of the voffset, which the descriptor's range check
-            // covers
-            // lane p carries doubles 2p, 2p + 1 of the tile and, where the tile has them, 2048 + 2p, 2049 + 2p: consecutive lanes then write
-            // consecutive 16-byte pieces of the LDS tile (no bank conflicts; with 4p .. 4p + 3 per lane the two 16-byte writes of a
-            // lane pair collided -- the tile write was the largest single item of the kernel's ablation, 0.9 of 4.1 ms)
-            const unsigned int xs = t.xw & 0x7fffffffu;
-            const unsigned int xo = xs == kNoTile ? kOob : (xs + 2u * (unsigned int)p) * 8u;
-            load_tile(g, xo);
+    };
+    // The tile that the packet with tile word `txw` carries (the packet `kTileDepth` ahead): issued behind all of the current
+    // packet's items (issue_part(..., 1)).  Its word is the header's own where the tile runs as far ahead as the items, and waits
+    // in the header ring (xwq) where it runs shorter.
+    auto issue_tile = [&](TallTile &g, const unsigned int txw) {
+        // columns past ncol read 0: the displacement of each double is part of the voffset, which the descriptor's range check
+        // covers
+        // lane p carries doubles 2p, 2p + 1 of the tile and, where the tile has them, 2048 + 2p, 2049 + 2p: consecutive lanes then write
+        // consecutive 16-byte pieces of the LDS tile (no bank conflicts; with 4p .. 4p + 3 per lane the two 16-byte writes of a
+        // lane pair collided -- the tile write was the largest single item of the kernel's ablation, 0.9 of 4.1 ms)
+        const unsigned int xs = txw & 0x7fffffffu;
+        const unsigned int xo = xs == kNoTile ? kOob : (xs + 2u * (unsigned int)p) * 8u;
+        load_tile(g, xo);
+    };
+
+    // AHEAD (items with a value id): what a packet's first four items need that does NOT depend on the cell's barrier -- the
+    // decode of the sum address, column and value offset (the words landed `depth` packets ago) and the four reads of the value
+    // table (constant within a segment) -- is done one packet early, behind the first group's sum stores of the packet before,
+    // and held across the barrier (16 registers); behind the barrier remain the sum reads (other waves' stores) and the x
+    // gathers (the tile).  Same products, same chains: the sums are the same bits.
+    //   * the first packet of a segment is taken ahead behind the prologue's __syncthreads (the segment's table is in LDS);
+    //   * the last real packet takes a prefetch-target packet ahead: zero words, entry 0 of the table, never used;
+    //   * that read stands in front of the segment-end __syncthreads in program order, the next segment's table is written
+    //     behind it: no read reaches another segment's table;
+    //   * a continuation packet (no barrier) takes the same path; the second group of four stays where it was.
+    // fp64 items (DICT = false) stay as they were: they have no table read to move, and their decode is two instructions per
+    // item that the scheduler already places freely inside the block behind the barrier.
+    auto ahead = [&](const TallRegs<DICT> &g, TallAheadItems &d) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned int w = g.lo[k];
+            d.sa[k] = tall_item_sum_bytes(w, g.hi[0] >> (8 * k));
+            unsigned int col = tall_item_column(w);
+            asm("" : "+v"(col));   // (as in group(): the column stays an index)
+            d.col[k] = col;
+            d.v[k] = lds_at(tall_item_value_bytes(w) + kTallItemTableByte);
         }
     };
 
-    // (xw, c4: the packet's tile word and the bytes of its lanes with a fifth item, as its header's unpack() left them)
-    auto consume = [&](TallRegs<DICT> &g, const unsigned int xw, const unsigned int c4, auto &&between) {
+    // (xw, c4: the packet's tile word and the bytes of its lanes with a fifth item, as its header's unpack() left them;
+    // AHEAD: nx holds the packet's first four items on entry and those of the next packet, whose registers are gn, on return)
+    auto consume = [&](TallRegs<DICT> &g, const TallRegs<DICT> &gn, TallAheadItems &nx, const TallTile &tile, const unsigned int xw,
+                       const unsigned int c4, auto &&between) {
         if (xw & kPktNewCell) {
             // sums of the previous cell (other lanes owned these rows there) and the x-tile: LDS only, loads stay in flight
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -239,11 +298,11 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
             if ((xw & 0x7fffffffu) != kNoTile) {
                 // (Bringing the tile in by LDS-DMA -- __builtin_amdgcn_global_load_lds, no registers, no ds_write -- was built and
                 // measured: 4.71 ms against 3.99.  With two tile buffers the DMA can only start at the cell's barrier and must
-                // have landed by the next one, 1.6 us later; the register path issues the loads four cells ahead.  A third buffer
+                // have landed by the next one, 1.6 us later; the register path issued the loads four cells ahead (now: kTallTileDepth).  A third buffer
                 // does not fit beside 78 KB of running sums.)
                 double *dst = static_cast<double *>(__builtin_assume_aligned(xt + (C - cur) + 2 * p, 16));
-                if (piece0) *reinterpret_cast<double2 *>(dst) = make_double2(g.x[0], g.x[1]);
-                if (piece1) *reinterpret_cast<double2 *>(dst + 2 * kTallT) = make_double2(g.x[2], g.x[3]);
+                if (piece0) *reinterpret_cast<double2 *>(dst) = make_double2(tile.x[0], tile.x[1]);
+                if (piece1) *reinterpret_cast<double2 *>(dst + 2 * kTallT) = make_double2(tile.x[2], tile.x[3]);
             }
         };
         // WHERE the wave stores its share of the NEXT cell's x-tile (it only has to be there by the next cell's barrier; lab
@@ -289,7 +348,25 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
 #pragma unroll
             for (int k = 0; k < 4; ++k) lds_at(sa[k]) = t[k];
         };
-        group(0);   // (a wave without items -- nearly never -- reads cell 0 of the arrays and stores into the scratch cell)
+        // the first group of a packet taken ahead: sum reads, x gathers, the chain and the stores of group()
+        auto group_taken = [&]() {
+            double ar[4], pr[4], t[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ar[k] = lds_at(nx.sa[k]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) pr[k] = nx.v[k] * lds_at((nx.col[k] << 3) + tileb);
+            t[0] = ar[0] + pr[0];
+#pragma unroll
+            for (int k = 1; k < 4; ++k) t[k] = ((nx.sa[k] == nx.sa[k - 1]) ? t[k - 1] : ar[k]) + pr[k];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) lds_at(nx.sa[k]) = t[k];
+        };
+        if (AHEAD) {
+            group_taken();
+            ahead(gn, nx);   // the next packet's, behind this group's sum stores and in front of the next barrier
+        } else {
+            group(0);   // (a wave without items -- nearly never -- reads cell 0 of the arrays and stores into the scratch cell)
+        }
         between();
         if (wbytes < c4) group(4);
     };
@@ -302,25 +379,31 @@ __global__ __launch_bounds__(kTallT) void k_tall_spmv(int nseg, const TallWg *__
         c4q[u] = t.w[4];
         issue_part(regs[u], t, 0);
         issue_part(regs[u], t, 1);
+        if (u < kTileDepth) issue_tile(tiles[u], t.xw);   // (the tiles of the first `tile depth` packets only)
         hw[u] = hd[(i64)(u + kDepth) * 8];
     }
     __syncthreads();
-    for (int jj = 0; jj < npk; jj += 2 * kDepth) {
+    TallAheadItems nx;   // AHEAD: the first four items of the packet about to be taken
+    if (AHEAD) ahead(regs[0], nx);   // (behind the barrier: this segment's value table is in LDS)
+    for (int jj = 0; jj < npk; jj += kTurn) {
 #pragma unroll
-        for (int u = 0; u < 2 * kDepth; ++u) {
-            const int i = u % kDepth;
+        for (int u = 0; u < kTurn; ++u) {
+            const int i = u % kDepth, it = u % kTileDepth;
             const unsigned int xw = xwq[i], c4 = c4q[i];                     // packet jj + u
             // header of packet jj + u + depth: unpacked BEHIND this packet's first items, in the shadow of their LDS reads.  In
             // front of the cell's barrier the same instructions made A x 0.2 and 0.35 ms slower (mean of three alternating runs) on the
             // two boxes where both places were timed side by side
             TallHdr t;
-            consume(regs[i], xw, c4, [&]() {
+            consume(regs[i], regs[(u + 1) % kDepth], nx, tiles[it], xw, c4, [&]() {
                 t = unpack(hw[i]);
                 xwq[i] = t.xw;
                 c4q[i] = t.w[4];
                 issue_part(regs[i], t, 0);
             });
             issue_part(regs[i], t, 1);
+            // the tile of packet jj + u + tile depth into the registers this packet's tile has just left: its word was unpacked
+            // depth - tile depth steps ago (tile depth = depth: just now)
+            issue_tile(tiles[it], kTileDepth == kDepth ? t.xw : xwq[(u + kTileDepth) % kDepth]);
             hw[i] = hd[(i64)(jj + u + 2 * kDepth) * 8];                      // header of packet jj + u + 2 depth
         }
     }
