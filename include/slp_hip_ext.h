@@ -16,6 +16,8 @@
 #include "slp_hip_ext_dga_batch.h"
 /* a cut-off for the bound of each LP of the dual-ascent list solver: likewise */
 #include "slp_hip_ext_dga_many.h"
+/* the dual-ascent list solver over the list of its live LPs (compaction): likewise */
+#include "slp_hip_ext_dga_many_live.h"
 /* which packet form a tall-cell product copy has: likewise */
 #include "slp_hip_ext_tall.h"
 

@@ -10,7 +10,8 @@ matrix and the right-hand sides together (csrc/slp_dga_batch.hip); instance k is
 iterations inside a launch (csrc/slp_dga_many.hip); LP k is bit for bit the single solve of ``lps[k]``.
 ``DeviceDGAMany.set_stop`` / ``dual_gradient_ascent_many_until`` stop every LP of such a list on its own, by a test on the step of
 its multipliers inside the iteration kernel; ``DeviceDGAMany.set_cutoff`` / ``dual_gradient_ascent_many_cutoff`` also once its
-certified lower bound has reached a cut-off, evaluated in the same kernel.  ``DeviceDGABatch.set_stop`` / ``dual_gradient_ascent_batch_until`` stop every instance
+certified lower bound has reached a cut-off, evaluated in the same kernel; ``DeviceDGAMany.set_compaction`` /
+``dual_gradient_ascent_many_compact`` hand the LPs still moving consecutive workgroups in every launch.  ``DeviceDGABatch.set_stop`` / ``dual_gradient_ascent_batch_until`` stop every instance
 of a batch on its own, on that step or once its certified lower bound has reached a cut-off, tested on the device.
 """
 import os
@@ -701,6 +702,27 @@ class DeviceDGAMany(_DeviceDGA):
         _lib.check(self._l.slp_many_dual_cutoff_state(self._h, _lib.ptr(iterations), _lib.ptr(reason), _lib.ptr(step), _lib.ptr(bound)))
         return iterations, reason != 0, step, bound, reason
 
+    def set_compaction(self, on=True):
+        """Turns compaction on or off (``slp_many_dual_set_compaction``; off after the constructor).  While it is on, every
+        iteration launch of a call on a state that is armed, or has a stopped or a frozen LP, runs over a list of the live LPs --
+        neither frozen nor stopped -- that the device builds in front of it: the live LPs get consecutive workgroups, the grid is
+        the number of LPs live when the call began, and the iterations one launch holds are those of that many workgroups.  Every
+        LP's x, y, tie draws, flags, stop record and report are bit for bit those of the state without it."""
+        if not isinstance(on, (bool, int, np.integer)) or int(on) not in (0, 1):
+            raise ValueError(f"on must be True or False, not {on!r}")
+        _lib.check(self._l.slp_many_dual_set_compaction(self._h, int(on)))
+
+    def live_state(self):
+        """``(live, order, launched, cap)`` (``slp_many_dual_live_state``): the number of live LPs, their numbers in the order of the
+        device's list (an int32 array of length ``live``, increasing), the number of workgroups of the last iteration launch and the
+        iterations per launch the last ``iterate`` call that launched anything was held to (both 0 before the first).  Works with
+        compaction on or off; reading it synchronises."""
+        live, launched, cap = (np.zeros(1, dtype=np.int64) for _ in range(3))
+        order = np.zeros(self.count, dtype=np.int32)
+        _lib.check(self._l.slp_many_dual_live_state(self._h, _lib.ptr(live), _lib.ptr(order), _lib.ptr(launched), _lib.ptr(cap)))
+        assert np.all(order[int(live[0]):] == -1)
+        return int(live[0]), order[:int(live[0])].copy(), int(launched[0]), int(cap[0])
+
 
 def dual_gradient_ascent_many(lps, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None):
     """``dual_gradient_ascent`` on every LP of ``lps`` -- LPs whose constraint matrices differ -- all advancing together on the
@@ -760,22 +782,40 @@ def dual_gradient_ascent_many_cutoff(lps, tol, check_every=10, nb_max_iter=1000,
     ``info`` is that of ``dual_gradient_ascent_many_until`` and, with ``targets``, also has ``bound`` (float64: the last bound
     evaluated at a check, ``-inf`` before the first) and ``reason`` (int32 bit mask: 0 moving or frozen, 1 step, 2 bound, 3 both at
     the same check).  For an LP stopped at a check with cut-offs ``info["lower_bound"][k] == info["bound"][k]``, bit for bit."""
+    return _dga_many_stopping(lps, tol, check_every, nb_max_iter, callback_func, y_eq, y_ineq, max_time, targets, False)
+
+
+def dual_gradient_ascent_many_compact(lps, tol, check_every=10, nb_max_iter=1000, callback_func=None, y_eq=None, y_ineq=None, max_time=None,
+                                      targets=None):
+    """``dual_gradient_ascent_many_cutoff`` with compaction on (``DeviceDGAMany.set_compaction``): the same arguments, the same
+    refusals before the library is loaded, and ``(xs, y_eqs, y_ineqs, info)`` bit for bit the same.  The LPs still moving are handed
+    consecutive workgroups in every launch, so a list in which LPs are retired here and there -- the pruned nodes of a branch and
+    bound -- keeps the whole device busy, launches only as many workgroups as LPs are left and holds more iterations per launch
+    as the list thins out."""
+    return _dga_many_stopping(lps, tol, check_every, nb_max_iter, callback_func, y_eq, y_ineq, max_time, targets, True)
+
+
+def _dga_many_stopping(lps, tol, check_every, nb_max_iter, callback_func, y_eq, y_ineq, max_time, targets, compact):
+    """``dual_gradient_ascent_many_cutoff`` and ``dual_gradient_ascent_many_compact``: the checks and the run they share (with
+    ``targets`` None the test is that of ``dual_gradient_ascent_many_until``)."""
     try:
         lps = list(lps)
     except TypeError:
         raise ValueError("lps must be a sequence of LP objects") from None
     if targets is None and tol is not None:
-        return dual_gradient_ascent_many_until(lps, tol, check_every, nb_max_iter, callback_func, y_eq, y_ineq, max_time)
-    cutoff = _check_batch_stop(tol, targets, check_every, len(lps))
-    xs, y_eqs, y_ineqs, report, info = _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, cutoff=cutoff)
+        stop, cutoff = _many.check_stop(tol, check_every), None
+    else:
+        stop, cutoff = None, _check_batch_stop(tol, targets, check_every, len(lps))
+    xs, y_eqs, y_ineqs, report, info = _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, stop=stop, cutoff=cutoff,
+                                                     compact=compact)
     return xs, y_eqs, y_ineqs, info
 
 
-def _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, frozen_out=None, stop=None, cutoff=None):
+def _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, frozen_out=None, stop=None, cutoff=None, compact=False):
     """``dual_gradient_ascent_many`` plus, as a fourth value, the final ``DeviceDGAMany.report()`` and, as a fifth, the ``info`` of
     ``dual_gradient_ascent_many_until`` (``stop`` the checked ``(tol, check_every)``) or of ``dual_gradient_ascent_many_cutoff``
     (``cutoff`` the checked ``(tol, targets, check_every)``); None without a stopping test.  ``frozen_out``: a list that receives
-    the frozen flags before the first iteration."""
+    the frozen flags before the first iteration.  ``compact``: the run is made with ``DeviceDGAMany.set_compaction`` on."""
     start = time.perf_counter()
     try:
         lps = list(lps)
@@ -788,6 +828,8 @@ def _dga_many_run(lps, nb_max_iter, callback_func, y_eq, y_ineq, max_time, froze
     has_ineq = [getattr(lp, "a_inequalities", None) is not None for lp in lps]
     state = DeviceDGAMany(forms, y0s, offsets, draws=np.random.RandomState(0).random_sample)
     try:
+        if compact:
+            state.set_compaction(True)
         frozen = state.frozen()
         if frozen_out is not None:
             frozen_out[:] = frozen.tolist()

@@ -1014,8 +1014,16 @@ def solve_dga_many_cutoff(lps, tol, check_every=10, get_timing=True, nb_iter=100
     return _solve_dga_many_stopping(lps, tol, check_every, get_timing, nb_iter, max_time, targets)
 
 
-def _solve_dga_many_stopping(lps, tol, check_every, get_timing, nb_iter, max_time, targets):
-    """``solve_dga_many_until`` (``targets`` None) and ``solve_dga_many_cutoff``."""
+def solve_dga_many_compact(lps, tol, check_every=10, get_timing=True, nb_iter=10000, max_time=None, targets=None):
+    """``solve_dga_many_cutoff`` with compaction on (``DualGradientAscent.dual_gradient_ascent_many_compact``): the LPs still
+    moving are handed consecutive workgroups in every launch.  The same arguments, the same refusals before the library is loaded,
+    the same ``xs`` and the same attributes on every LP, bit for bit; what changes is the time of a list in which LPs are retired
+    here and there."""
+    return _solve_dga_many_stopping(lps, tol, check_every, get_timing, nb_iter, max_time, targets, compact=True)
+
+
+def _solve_dga_many_stopping(lps, tol, check_every, get_timing, nb_iter, max_time, targets, compact=False):
+    """``solve_dga_many_until`` (``targets`` None), ``solve_dga_many_cutoff`` and, with ``compact``, ``solve_dga_many_compact``."""
     from .DualGradientAscent import _check_batch_stop, _dga_many_run
 
     lps = list(lps)
@@ -1038,7 +1046,8 @@ def _solve_dga_many_stopping(lps, tol, check_every, get_timing, nb_iter, max_tim
         skip[:] = np.asarray(frozen, dtype=bool) | (info["stopped"] & (info["iterations"] < niter + 1))
         fill(niter, *report)
 
-    xs, y_eqs, y_ineqs, _, info = _dga_many_run(lps, nb_iter, record, None, None, max_time, frozen_out=frozen, stop=stop, cutoff=cutoff)
+    xs, y_eqs, y_ineqs, _, info = _dga_many_run(lps, nb_iter, record, None, None, max_time, frozen_out=frozen, stop=stop, cutoff=cutoff,
+                                             compact=compact)
     for k, lp in enumerate(lps):
         lp.nb_iterations = int(info["iterations"][k])
         lp.stopped = bool(info["stopped"][k])

@@ -18,7 +18,8 @@ LP on its own, by a test on the step inside the kernel; ``solve_many_certified``
 certified duality gap and the primal violation, both handed back), ``solve_dga_many`` / ``dual_gradient_ascent_many`` do the same
 for dual gradient ascent (a certified lower bound per LP; ``solve_dga_many_until`` / ``dual_gradient_ascent_many_until`` stop every
 LP on its own, by a test on the step of its multipliers inside the kernel; ``solve_dga_many_cutoff`` /
-``dual_gradient_ascent_many_cutoff`` also once its bound has reached a cut-off), ``solve_admm_many`` / ``lp_admm_many`` for ADMM with the projected
+``dual_gradient_ascent_many_cutoff`` also once its bound has reached a cut-off; ``solve_dga_many_compact`` /
+``dual_gradient_ascent_many_compact`` are those with the LPs still moving handed consecutive workgroups in every launch), ``solve_admm_many`` / ``lp_admm_many`` for ADMM with the projected
 Gauss-Seidel x-step (``solve_admm_many_until`` / ``lp_admm_many_until`` stop every LP on its own, by a test on the residual and
 the step inside the kernel).  There is no CPU fallback: without the built
 library and a HIP device every solver call raises ``SlpError``.
@@ -28,9 +29,10 @@ from .ADMM import ADMMBatchState, ADMMManyState, lp_admm_batch, lp_admm_batch_un
 from .ChambollePockPPD import (CPBatchState, CPManyState, chambolle_pock_ppd_batch, chambolle_pock_ppd_batch_certified,  # noqa: F401
                                chambolle_pock_ppd_many, chambolle_pock_ppd_many_certified, chambolle_pock_ppd_many_until)
 from .DualGradientAscent import (DeviceDGABatch, DeviceDGAMany, dual_gradient_ascent_batch, dual_gradient_ascent_batch_until,  # noqa: F401
-                                 dual_gradient_ascent_many, dual_gradient_ascent_many_cutoff, dual_gradient_ascent_many_until)
+                                 dual_gradient_ascent_many, dual_gradient_ascent_many_compact, dual_gradient_ascent_many_cutoff,
+                                 dual_gradient_ascent_many_until)
 from .SparseLP import solve_admm_many, solve_admm_many_until, solve_dga_many, solve_dga_many_until, solve_many, solve_many_until  # noqa: F401
-from .SparseLP import solve_dga_many_cutoff, solve_many_certified  # noqa: F401
+from .SparseLP import solve_dga_many_compact, solve_dga_many_cutoff, solve_many_certified  # noqa: F401
 
 __all__ = ["ORDER_AUTO", "ORDER_SEQUENTIAL", "ORDER_TREE", "SlpError", "CPBatchState", "chambolle_pock_ppd_batch",
            "ADMMBatchState", "lp_admm_batch", "DeviceDGABatch", "dual_gradient_ascent_batch", "CPManyState", "chambolle_pock_ppd_many",
@@ -38,4 +40,4 @@ __all__ = ["ORDER_AUTO", "ORDER_SEQUENTIAL", "ORDER_TREE", "SlpError", "CPBatchS
            "solve_admm_many", "chambolle_pock_ppd_many_until", "solve_many_until", "lp_admm_many_until", "solve_admm_many_until",
            "dual_gradient_ascent_many_until", "solve_dga_many_until", "chambolle_pock_ppd_many_certified", "solve_many_certified",
            "chambolle_pock_ppd_batch_certified", "lp_admm_batch_until", "dual_gradient_ascent_batch_until",
-           "dual_gradient_ascent_many_cutoff", "solve_dga_many_cutoff"]
+           "dual_gradient_ascent_many_cutoff", "solve_dga_many_cutoff", "dual_gradient_ascent_many_compact", "solve_dga_many_compact"]

@@ -69,6 +69,17 @@
 // round of dga_block_reduce, and lane 0 adds them in order.  The column terms come from a walk of K^T over the new y that stores
 // nothing: x and c_bar stay those of the top of the iteration, which is what a stopped LP keeps.  The parts go through part_min
 // (columns) and part_gb (rows), dead behind the last kind's search; no LDS is added, no atomic, no wait.
+//
+// Compaction (slp_many_dual_set_compaction, include/slp_hip_ext_dga_many_live.h; off after create): the third template parameter,
+// LIVE.  Without it a retired LP keeps its workgroup index, and the hardware deals the workgroups of a launch to its eight XCDs in
+// turn: with every second LP retired all the live ones sit on four of them.  With compaction on, and an LP that may stand still
+// (armed, a stopped LP, or a frozen one), every launch of a call is preceded by k_many_live<DgmIsLive> (slp_many.h: one workgroup
+// writes the numbers of the LPs neither frozen nor stopped, in increasing order, and their count) and is <., ., true> over as many
+// workgroups as LPs were live when the call began -- the read-back an armed call starts with gives the number; workgroup i takes
+// LP ids[i], a workgroup at or past the count returns before its first barrier.  LPs that stop within the call leave the list at
+// the next launch, so the survivors stay on consecutive indices.  The cap of the call is that of the live number of workgroups
+// (many_live_cap).  An LP's iterations read and write its own data only, so which workgroup runs them changes no bit.
+// <., ., false> takes blockIdx.x and never looks at the list: the three kernels above.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -78,6 +89,7 @@
 #include "slp_dga_shared.h"
 #include "slp_many.h"
 #include "../../include/slp_hip_ext_dga_many.h"
+#include "../../include/slp_hip_ext_dga_many_live.h"
 
 using namespace slp;
 
@@ -116,6 +128,18 @@ struct DgmStopArgs {
     double tol;               // < 0: the step is evaluated and recorded, not tested (BOUND only)
     const double *targets;    // BOUND: a cut-off per LP, +inf for none
     i64 check_every;
+};
+
+// LIVE: the live LPs in increasing order and their number, written by k_many_live<DgmIsLive> in front of the launch
+struct DgmLiveArgs {
+    const i32 *ids, *n;
+};
+
+// an LP is live when it is neither frozen nor stopped: the readers of the stream of draws (dgm_read_ctl, dgm_any_moves)
+struct DgmIsLive {
+    const DgaCtl *ctl;
+    const DgmStop *rec;
+    __device__ bool operator()(i32 k) const { return !ctl[k].frozen && !rec[k].reason; }
 };
 
 // c_bar of column j of the LP: the two masked sums of K^T y in storage order (k_dgab_cols), then (c + s_eq) + s_ineq
@@ -168,16 +192,20 @@ __device__ __forceinline__ double dgm_dot(i64 s, i64 e, const i32 *idx, const do
 
 // `iters` iterations of the LP blockIdx.x.  STOP: the stopping test of the header comment; `sp` is not looked at without it.
 // BOUND (with STOP only): a check iteration also evaluates the bound and tests it against the LP's cut-off.
-template <bool STOP, bool BOUND>
-__global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int iters, DgmStopArgs sp) {
+// LIVE: the LP is lv.ids[blockIdx.x], the list k_many_live wrote in front of this launch; a workgroup past its end returns before
+// its first barrier (*lv.n is the same for every lane).  `lv` is not looked at without it.
+template <bool STOP, bool BOUND, bool LIVE>
+__global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int iters, DgmStopArgs sp, DgmLiveArgs lv) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dgm_lds[];
     const DgaLoadWorkgroup ld;
-    const DgmLp lp = a.lps[blockIdx.x];
-    DgaCtl *ctl = a.ctl + blockIdx.x;
+    if (LIVE && blockIdx.x >= (unsigned)*lv.n) return;
+    const unsigned k = LIVE ? (unsigned)lv.ids[blockIdx.x] : blockIdx.x;   // the LP of this workgroup
+    const DgmLp lp = a.lps[k];
+    DgaCtl *ctl = a.ctl + k;
     if (ctl->frozen) return;   // set before the launch: the same for every lane
     i64 done = 0, until = 0;   // STOP: iterations completed; iterations up to and including the next check
     if (STOP) {
-        const DgmStop *rec = sp.rec + blockIdx.x;
+        const DgmStop *rec = sp.rec + k;
         if (rec->reason) return;    // set before the launch: the same for every lane
         done = rec->done;           // lane 0 writes the record only behind a barrier that follows this load
         until = sp.check_every - done % sp.check_every;
@@ -189,8 +217,8 @@ __global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int
     double *x = a.x + lp.col0, *cbar = a.cbar + lp.col0, *d = a.d + lp.col0;
     double *y = a.y + lp.row0, *ax = a.ax + lp.row0, *g = a.g + lp.row0;
     const i64 *ptr = a.ptr + lp.row0, *tptr = a.tptr + lp.col0;
-    double *part_gb = a.part_gb + (i64)blockIdx.x * kDgaParts, *part_min = a.part_min + (i64)blockIdx.x * kDgaParts;
-    int *part_any = a.part_any + (i64)blockIdx.x * kDgaParts;
+    double *part_gb = a.part_gb + (i64)k * kDgaParts, *part_min = a.part_min + (i64)k * kDgaParts;
+    int *part_any = a.part_any + (i64)k * kDgaParts;
     // the window of draws as this LP's positions see it: its draw `consumed` is rnd[draw_offset + consumed - rnd_base]
     const double *rnd = a.rnd;
     unsigned long long rnd_base = 0, rnd_count = a.rnd_count;
@@ -249,7 +277,7 @@ __global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int
                 continue;
             }
             until = sp.check_every;
-            DgmStop *rec = sp.rec + blockIdx.x;
+            DgmStop *rec = sp.rec + k;
             double *red = reinterpret_cast<double *>(dgm_lds);   // the 16 reduction slots: one per wave
             const i32 cparts = (n + kBlock - 1) / kBlock, parts = cparts + (m + kBlock - 1) / kBlock;
             if (BOUND) {
@@ -297,7 +325,7 @@ __global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int
                     double e = 0.0, yb = 0.0;
                     for (i32 p = 0; p < cparts; ++p) e += ld(part_min + p);
                     for (i32 p = 0; p < parts - cparts; ++p) yb += ld(part_gb + p);
-                    const double bound = e - yb, target = sp.targets[blockIdx.x];
+                    const double bound = e - yb, target = sp.targets[k];
                     const bool sound = !(ctl->flags & DGA_NAN);   // an LP that has met a NaN breakpoint or step certifies nothing
                     int reason = (sound && sp.tol >= 0.0 && step <= sp.tol) ? 1 : 0;            // false for a NaN
                     if (sound && target < __builtin_inf() && bound >= target) reason |= 2;      // false for a NaN
@@ -316,7 +344,7 @@ __global__ __launch_bounds__(kDgaFusedThreads) void k_dgm_iterate(DgmArgs a, int
             if (ld(&rec->reason)) break;   // read by all lanes after the barrier: uniform
         }
     }
-    if (STOP && tid == 0) sp.rec[blockIdx.x].done = done;
+    if (STOP && tid == 0) sp.rec[k].done = done;
 }
 
 // ---- start, frozen test and report: ordinary launches over (.., count) --------------------------------------------------------
@@ -354,6 +382,7 @@ struct slp_many_dga {
     i64 count = 0, n = 0, m = 0;   // LPs, all columns, all rows
     i32 max_n = 1, max_m = 1, max_npad = 64;
     i64 kmax = 1;                  // iterations one launch may hold
+    i64 passes = 1, kmax_switch = 1;   // what kmax was made of: the passes of the largest LP, the SLP_DGA_MANY_KMAX switch
     std::vector<DgmLp> lps;
     DevBuf<DgmLp> table;
     DevBuf<i64> ptr, tptr;
@@ -375,6 +404,10 @@ struct slp_many_dga {
     bool has_targets = false;
     i64 check_every = 1, uncounted = 0;
     bool any_stopped = false;   // from now on every launch is the kernel with the test: a stopped LP stays where it is
+    // compaction (slp_many_dual_set_compaction; off after create): the launches of a call run over the list of the live LPs
+    DevBuf<i32> live, live_n;   // allocated at the first use: `count` entries and one
+    bool compact = false, any_frozen = false;
+    i64 launched = 0, call_cap = 0;   // the grid of the last iteration launch, the cap of the last iterate call that launched
 };
 
 namespace {
@@ -415,6 +448,8 @@ void dgm_plan(slp_many_dga *s) {
     i64 passes = 1;
     for (const DgmLp &lp : s->lps) passes = std::max(passes, dgm_passes(lp));
     s->kmax = many_launch_cap(kManyUnitsPerLaunch, passes, s->count, ctx().num_cu, cap);
+    s->passes = passes;
+    s->kmax_switch = cap;
 }
 
 size_t dgm_lds_bytes(const slp_many_dga *s) { return kDgmSlotBytes + fused_lds_bytes(s->max_npad); }
@@ -477,6 +512,29 @@ void dgm_set_rule(slp_many_dga *s, double tol, const double *targets, i64 check_
     s->has_targets = targets != nullptr;
     s->tol = tol < 0.0 ? -1.0 : tol;
     if (tol >= 0.0 || targets) s->check_every = check_every;
+}
+
+void dgm_live_alloc(slp_many_dga *s) {
+    if (s->live.p) return;
+    s->live.alloc((size_t)s->count);
+    s->live_n.alloc(1);
+}
+
+// the list of the live LPs from the flags as they are on the device, behind everything enqueued so far
+void dgm_live_list(slp_many_dga *s) {
+    dgm_live_alloc(s);
+    hipLaunchKernelGGL(k_many_live<DgmIsLive>, dim3(1), dim3(kManyLiveLanes), 0, ctx().stream, DgmIsLive{s->ctl.p, s->stop.p}, (i32)s->count,
+                       s->live.p, s->live_n.p);
+}
+
+template <bool LIVE>
+void dgm_launch(slp_many_dga *s, bool stop, i64 grid, int it, const DgmStopArgs &sp) {
+    const dim3 g((unsigned)grid), block(kDgaFusedThreads);
+    const DgmLiveArgs lv = {s->live.p, s->live_n.p};
+    hipStream_t st = ctx().stream;
+    if (s->has_targets) hipLaunchKernelGGL((k_dgm_iterate<true, true, LIVE>), g, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp, lv);
+    else if (stop) hipLaunchKernelGGL((k_dgm_iterate<true, false, LIVE>), g, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp, lv);
+    else hipLaunchKernelGGL((k_dgm_iterate<false, false, LIVE>), g, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp, lv);
 }
 
 }  // namespace
@@ -565,8 +623,10 @@ slp_many_dga *slp_many_dga_create(int64_t count, const int64_t *n, const int64_t
         s->rnd.alloc(1);
         s->ctl.alloc(sc);
         s->ctl.zero();
-        for (const void *kernel : {reinterpret_cast<const void *>(k_dgm_iterate<false, false>), reinterpret_cast<const void *>(k_dgm_iterate<true, false>),
-                                   reinterpret_cast<const void *>(k_dgm_iterate<true, true>)})
+        for (const void *kernel :
+             {reinterpret_cast<const void *>(k_dgm_iterate<false, false, false>), reinterpret_cast<const void *>(k_dgm_iterate<true, false, false>),
+              reinterpret_cast<const void *>(k_dgm_iterate<true, true, false>), reinterpret_cast<const void *>(k_dgm_iterate<false, false, true>),
+              reinterpret_cast<const void *>(k_dgm_iterate<true, false, true>), reinterpret_cast<const void *>(k_dgm_iterate<true, true, true>)})
             SLP_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kDgmSlotBytes + fused_lds_bytes(kDgaFusedMax))));
         {
             const std::vector<DgmStop> rec(sc, DgmStop{0, __builtin_inf(), -__builtin_inf(), 0, 0});
@@ -579,6 +639,7 @@ slp_many_dga *slp_many_dga_create(int64_t count, const int64_t *n, const int64_t
         std::vector<DgaCtl> h(sc);
         memset(h.data(), 0, sc * sizeof(DgaCtl));
         for (size_t k = 0; k < sc; ++k) h[k].frozen = rep[3 * k] == -INFINITY;
+        for (size_t k = 0; k < sc; ++k) s->any_frozen = s->any_frozen || h[k].frozen;
         s->ctl.upload(h.data(), sc);
         dgm_read_ctl(s.get(), h);
         return s.release();
@@ -592,26 +653,42 @@ int64_t slp_many_dga_kmax(const slp_many_dga *s) { return s ? s->kmax : -1; }
 int slp_many_dga_iterate(slp_many_dga *s, int64_t k) {
     SLP_API_INT({
         SLP_REQUIRE(s && k >= 0, "slp_many_dga_iterate: bad arguments");
-        hipStream_t st = ctx().stream;
         // with the test: armed, or off with an LP that has to stay stopped (a cadence that never comes)
         const bool armed = s->tol >= 0.0 || s->has_targets, stop = armed || s->any_stopped;
+        // over the list of the live LPs: compaction is on and an LP may stand still
+        bool live = s->compact && (stop || s->any_frozen);
         const DgmStopArgs sp = {s->stop.p, s->tol, s->targets.p, armed ? s->check_every : INT64_MAX};
-        if (stop) {   // when every LP is stopped or frozen nothing is launched and the count of iterations stays
+        i64 grid = s->count, cap = s->kmax;
+        if (stop || live) {   // when every LP is stopped or frozen nothing is launched and the count of iterations stays
             std::vector<DgaCtl> h;
             std::vector<DgmStop> rec;
             dgm_read_ctl(s, h, &rec);
-            if (!dgm_any_moves(h, rec)) return 0;
+            if (!dgm_any_moves(h, rec)) {
+                if (stop) return 0;
+                live = false;   // never armed and every LP frozen: the launches of a state without compaction, which count
+            }
+            if (live) {
+                // the LPs live now: the grid of every launch of this call (an LP that stops in it is known here at the next call;
+                // its workgroup index goes to the survivors, the surplus workgroups return at the list's end) and its cap
+                grid = 0;
+                for (size_t j = 0; j < h.size(); ++j) grid += !h[j].frozen && !rec[j].reason;
+                cap = many_live_cap(s->passes, grid, ctx().num_cu, s->kmax_switch);
+            }
         }
-        many_split(k, s->kmax, [&](int want) {
+        s->call_cap = cap;
+        many_split(k, cap, [&](int want) {
             // at most two tie draws per LP and iteration: iterations the buffer cannot run dry in
             const int it = (int)s->draws.reserve(want);
             if (it < 1) return it;
-            const dim3 grid((unsigned)s->count), block(kDgaFusedThreads);
             s->timer.mark(-1);
-            if (s->has_targets) hipLaunchKernelGGL((k_dgm_iterate<true, true>), grid, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp);
-            else if (stop) hipLaunchKernelGGL((k_dgm_iterate<true, false>), grid, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp);
-            else hipLaunchKernelGGL((k_dgm_iterate<false, false>), grid, block, dgm_lds_bytes(s), st, dgm_args(s), it, sp);
+            if (live) {
+                dgm_live_list(s);
+                dgm_launch<true>(s, stop, grid, it, sp);
+            } else {
+                dgm_launch<false>(s, stop, grid, it, sp);
+            }
             s->timer.mark(ST_FUSED);
+            s->launched = grid;
             s->iters += it;
             if (!stop) s->uncounted += it;
             return it;
@@ -714,6 +791,33 @@ int slp_many_dual_cutoff_state(slp_many_dga *s, int64_t *iterations, int32_t *re
             if (step) step[k] = rec[k].step;
             if (bound) bound[k] = rec[k].bound;
         }
+    })
+}
+
+int slp_many_dual_set_compaction(slp_many_dga *s, int on) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_dual_set_compaction: NULL handle");
+        SLP_REQUIRE(on == 0 || on == 1, "slp_many_dual_set_compaction: on must be 0 or 1");
+        if (on) dgm_live_alloc(s);
+        s->compact = on != 0;
+    })
+}
+
+int slp_many_dual_live_state(slp_many_dga *s, int64_t *live, int32_t *order, int64_t *launched, int64_t *cap) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_dual_live_state: NULL handle");
+        dgm_live_list(s);
+        SLP_HIP(hipGetLastError());
+        i32 n = 0;
+        s->live_n.download(&n, 1);   // synchronises
+        SLP_REQUIRE(n >= 0 && n <= s->count, "slp_many_dual_live_state: the device's count of live LPs is out of range");
+        if (live) *live = n;
+        if (order) {
+            s->live.download(order, (size_t)n);
+            std::fill(order + n, order + s->count, -1);
+        }
+        if (launched) *launched = s->launched;
+        if (cap) *cap = s->call_cap;
     })
 }
 

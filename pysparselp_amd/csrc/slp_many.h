@@ -91,6 +91,38 @@ __device__ __forceinline__ bool many_decided(const double *slot) {
     return *slot != 0.0;
 }
 
+// ---- the list of the live LPs, built on the device in front of a launch that runs over it (slp_dga_many.hip) ----
+// ONE workgroup of kManyLiveLanes lanes; `pred(k)` says whether LP k is live.  live[0 .. *live_n) receives the live LPs in
+// increasing order, the rest of live[] (`count` entries) stays as it was.  The chunk of a lane, its count and its stores are
+// slp_many_plan.h's; here is the exclusive prefix of the 1024 counts: inclusive over the wave by shuffles, the 16 wave totals
+// through LDS, one fold that gives a lane the waves in front of it and the total.  Integers only, so the order of additions is
+// free.  No atomic, no wait; both loops of a lane are bounded by `count`; the one barrier is reached by every lane.  The flags
+// `pred` reads are written by earlier launches on the same stream only, so a lane's two passes see the same values.
+template <class Pred>
+__global__ __launch_bounds__(kManyLiveLanes) void k_many_live(Pred pred, i32 count, i32 *__restrict__ live, i32 *__restrict__ live_n) {
+    __shared__ i32 totals[kManyLiveLanes / kWave];
+    const i32 tid = (i32)threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const ManyLiveRange r = many_live_range(count, tid);
+    const i32 mine = many_live_count(r, pred);
+    i32 upto = mine;   // inclusive over the wave
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const i32 o = __shfl_up(upto, off, kWave);
+        if (lane >= off) upto += o;
+    }
+    if (lane == kWave - 1) totals[wave] = upto;
+    __syncthreads();
+    i32 before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kManyLiveLanes / kWave; ++w) {
+        const i32 t = totals[w];
+        before += w < wave ? t : 0;
+        all += t;
+    }
+    many_live_write(r, before + upto - mine, live, pred);
+    if (tid == 0) *live_n = all;
+}
+
 // host: the records with the iterations of the unarmed launches added (no LP is stopped while the test is off); synchronises
 template <class Ctl>
 std::vector<Ctl> many_read_ctl(const DevBuf<Ctl> &ctl, i64 count, i64 uncounted) {

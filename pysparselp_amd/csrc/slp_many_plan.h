@@ -89,6 +89,43 @@ inline int64_t many_launch_cap(int64_t units, int64_t passes, int64_t workgroups
     return std::min(cap, std::max<int64_t>(1, units / (passes * rounds)));
 }
 
+// ---- the list of the live LPs (k_many_live, slp_many.h): one workgroup of kManyLiveLanes lanes, lane t owns the LPs
+// [t per, min((t + 1) per, count)) with per = ceil(count / kManyLiveLanes), counts its live ones and writes their numbers, in
+// increasing order, from the exclusive prefix of the counts on.  The arithmetic below is the kernel's and the host test's one text
+// (constexpr: host and device alike under hipcc).
+constexpr int32_t kManyLiveLanes = 1024;
+
+struct ManyLiveRange {
+    int32_t lo, hi;   // lo == hi: a lane past the end owns nothing
+};
+
+constexpr int32_t many_live_per(int32_t count) { return (count + kManyLiveLanes - 1) / kManyLiveLanes; }
+
+constexpr ManyLiveRange many_live_range(int32_t count, int32_t lane) {
+    const int64_t per = many_live_per(count), lo = per * lane, hi = lo + per;   // 64 bits: 1023 per may pass count by far
+    return ManyLiveRange{(int32_t)(lo < count ? lo : count), (int32_t)(hi < count ? hi : count)};
+}
+
+// a lane's live LPs; `live(k)` is the solver's predicate
+template <class Pred>
+constexpr int32_t many_live_count(ManyLiveRange r, const Pred &live) {
+    int32_t n = 0;
+    for (int32_t k = r.lo; k < r.hi; ++k) n += live(k) ? 1 : 0;
+    return n;
+}
+
+// the lane's live LPs into out[at], out[at + 1], ...: `at` is the number of live LPs of the lanes before it
+template <class Pred>
+constexpr void many_live_write(ManyLiveRange r, int32_t at, int32_t *out, const Pred &live) {
+    for (int32_t k = r.lo; k < r.hi; ++k)
+        if (live(k)) out[at++] = k;
+}
+
+// iterations a launch of a call may hold when `live` LPs are live at its start: the cap of that many workgroups
+inline int64_t many_live_cap(int64_t passes, int64_t live, int64_t cus, int64_t cap) {
+    return many_launch_cap(kManyUnitsPerLaunch, passes, std::max<int64_t>(1, live), cus, cap);
+}
+
 // rows r0 <= r < r1 of a CSR block belong to LP `lp`, whose column indices there lie in lo <= j < hi
 struct ManyRows {
     int64_t lp, r0, r1, lo, hi;
