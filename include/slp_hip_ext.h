@@ -18,6 +18,8 @@
 #include "slp_hip_ext_dga_many.h"
 /* the dual-ascent list solver over the list of its live LPs (compaction): likewise */
 #include "slp_hip_ext_dga_many_live.h"
+/* the Chambolle-Pock and the ADMM list solver over the lists of their live LPs (compaction): likewise */
+#include "slp_hip_ext_many_live.h"
 /* which packet form a tall-cell product copy has: likewise */
 #include "slp_hip_ext_tall.h"
 

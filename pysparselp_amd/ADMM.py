@@ -567,6 +567,7 @@ class ADMMManyState(_many.ManyState):
     returns it."""
 
     _PREFIX = "slp_admm_many"
+    _LIVE = "slp_many_admm"
 
     def __init__(self, lps, x0=None, gamma_eq=2, gamma_ineq=3, use_preconditioning=True):
         if len(lps) < 1:

@@ -736,6 +736,7 @@ class CPManyState(_many.ManyState):
     ``_many_problem`` returns them, each with at least one row; ``x0``: ``None`` or one start (or ``None``: zeros) per LP."""
 
     _PREFIX = "slp_cp_many"
+    _LIVE = "slp_many_cp"
 
     def __init__(self, lps, x0=None, alpha=1, theta=1):
         if len(lps) < 1:

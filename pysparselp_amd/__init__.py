@@ -21,7 +21,8 @@ LP on its own, by a test on the step of its multipliers inside the kernel; ``sol
 ``dual_gradient_ascent_many_cutoff`` also once its bound has reached a cut-off; ``solve_dga_many_compact`` /
 ``dual_gradient_ascent_many_compact`` are those with the LPs still moving handed consecutive workgroups in every launch), ``solve_admm_many`` / ``lp_admm_many`` for ADMM with the projected
 Gauss-Seidel x-step (``solve_admm_many_until`` / ``lp_admm_many_until`` stop every LP on its own, by a test on the residual and
-the step inside the kernel).  There is no CPU fallback: without the built
+the step inside the kernel).  ``CPManyState.set_compaction`` / ``ADMMManyState.set_compaction`` make every launch of an armed
+list state run over the LPs not yet stopped, with the same results bit for bit.  There is no CPU fallback: without the built
 library and a HIP device every solver call raises ``SlpError``.
 """
 from ._lib import ORDER_AUTO, ORDER_SEQUENTIAL, ORDER_TREE, SlpError  # noqa: F401

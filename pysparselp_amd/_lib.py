@@ -292,6 +292,16 @@ _EXT_DGA_MANY_LIVE_SIGNATURES = {
 
 EXT_DGA_MANY_LIVE_SYMBOLS = tuple(_EXT_DGA_MANY_LIVE_SIGNATURES)
 
+# name -> (restype, argtypes); mirrors include/slp_hip_ext_many_live.h (which slp_hip_ext.h includes) one to one
+_EXT_MANY_LIVE_SIGNATURES = {
+    "slp_many_cp_set_compaction": (c_int, [c_vp, c_int]),
+    "slp_many_admm_set_compaction": (c_int, [c_vp, c_int]),
+    "slp_many_cp_live_state": (c_int, [c_vp] * 5),
+    "slp_many_admm_live_state": (c_int, [c_vp] * 5),
+}
+
+EXT_MANY_LIVE_SYMBOLS = tuple(_EXT_MANY_LIVE_SIGNATURES)
+
 # name -> (restype, argtypes); mirrors include/slp_hip_ext_tall.h (which slp_hip_ext.h includes) one to one
 _EXT_TALL_SIGNATURES = {
     "slp_matrix_tall_records": (c_i64, [c_vp, c_int]),
@@ -323,7 +333,8 @@ def load():
         raise SlpError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_EXT_ADMM_BATCH_SIGNATURES.items())
                               + list(_EXT_DGA_BATCH_SIGNATURES.items()) + list(_EXT_DGA_MANY_SIGNATURES.items())
-                              + list(_EXT_DGA_MANY_LIVE_SIGNATURES.items()) + list(_EXT_TALL_SIGNATURES.items())):
+                              + list(_EXT_DGA_MANY_LIVE_SIGNATURES.items()) + list(_EXT_MANY_LIVE_SIGNATURES.items())
+                              + list(_EXT_TALL_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -137,10 +137,12 @@ def spread_stop_state(info, solved, state):
 
 class ManyState:
     """What the device states of a list share.  A subclass sets ``_PREFIX`` (its C entry points are ``<_PREFIX>_destroy``,
-    ``<_PREFIX>_form``, ``<_PREFIX>_get_*``), ``count``, the loaded library ``_l`` and its handle ``_h``."""
+    ``<_PREFIX>_form``, ``<_PREFIX>_get_*``), ``_LIVE`` (``<_LIVE>_set_compaction``, ``<_LIVE>_live_state``), ``count``, the loaded
+    library ``_l`` and its handle ``_h``."""
 
     FORMS = ("lds", "global")
     _PREFIX = None
+    _LIVE = None
 
     def close(self):
         if getattr(self, "_h", None):
@@ -157,6 +159,30 @@ class ManyState:
     def form(self, k):
         """``"lds"`` or ``"global"``: where LP ``k`` keeps its iterates during a launch."""
         return self.FORMS[int(getattr(self._l, self._PREFIX + "_form")(self._h, self._of_lp(k)))]
+
+    def set_compaction(self, on=True):
+        """Turns compaction on or off (``<_LIVE>_set_compaction``, include/slp_hip_ext_many_live.h; off after the constructor).
+        While it is on, a call on an armed state (``iterate`` and the two half steps) first reads the per-LP records back -- one
+        download, which synchronises -- and every launch of a form then runs over a list of that form's LPs not yet stopped, which
+        the device builds in front of it: the grid is the number of LPs of the form live when the call began, the iterations one
+        launch holds are those of that many workgroups, and a form without a live LP launches nothing.  An unarmed state has no
+        stopped LP and launches as without compaction.  Every LP's iterates, record and report are bit for bit those of the state
+        without it."""
+        if not isinstance(on, (bool, int, np.integer)) or int(on) not in (0, 1):
+            raise ValueError(f"on must be True or False, not {on!r}")
+        _lib.check(getattr(self._l, self._LIVE + "_set_compaction")(self._h, int(on)))
+
+    def live_state(self):
+        """``(live, order, launched, cap)`` (``<_LIVE>_live_state``): ``live`` the numbers of live LPs of the two forms (lds,
+        global; an int64 array of length 2), ``order`` the live LPs as the device lists them (int32: those of the lds form in
+        increasing order, then those of the global form in increasing order), ``launched`` the workgroups of each form's last
+        iteration launch and ``cap`` the iterations per launch each form was held to in the last call that launched it (int64
+        arrays of length 2, 0 before the first launch).  Works with compaction on or off; reading it synchronises."""
+        live, launched, cap = (np.zeros(2, dtype=np.int64) for _ in range(3))
+        order = np.zeros(self.count, dtype=np.int32)
+        _lib.check(getattr(self._l, self._LIVE + "_live_state")(self._h, _lib.ptr(live), _lib.ptr(order), _lib.ptr(launched), _lib.ptr(cap)))
+        assert np.all(order[int(live.sum()):] == -1)
+        return live, order[:int(live.sum())].copy(), launched, cap
 
     def _per_lp(self, what, sizes, *args):
         """The flat vector ``<_PREFIX>_get_<what>`` writes, cut into one array per LP."""

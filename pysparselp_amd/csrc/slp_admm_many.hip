@@ -60,6 +60,13 @@
 // written again; in the launch in which it stops it leaves the loop and, in the lds form, writes them back.  The count of an LP
 // is read from the record at the start of a launch, so the stopping iteration does not depend on how a run is split into calls
 // and launches.
+//
+// Compaction (slp_many_admm_set_compaction, include/slp_hip_ext_many_live.h; off after create): the template parameter LIVE of
+// k_admmm_iterate<., true, .>, by the text slp_cp_many.hip uses -- ManyFormLive, many_form_call (slp_many_plan.h), ManyFormLists,
+// many_form_list, many_form_state (slp_many.h).  With compaction on and the test armed, admmm_run reads the records back at the
+// start of a call (one download; it synchronises); per form every launch of the call is preceded by k_many_live for that form and
+// runs over as many workgroups as LPs of the form were live when the call began, held to the cap of that many workgroups; a.list
+// is the live list, and a workgroup at or past *live_n returns before anything else.  Every LP stays bit for bit.
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -70,6 +77,7 @@
 #include "slp_admm_iter.h"
 #include "slp_admm_shared.h"
 #include "slp_many.h"
+#include "../../include/slp_hip_ext_many_live.h"
 
 namespace slp {
 
@@ -192,12 +200,16 @@ static_assert(kAdmmmRed * sizeof(double) + kAdmmmLdsLimit * sizeof(double) <= 16
 
 // `iters` times the stages of one LP (bit 0 right-hand side + sweep, bit 1 multiplier); first: xp = xp0 in the first right-hand side.
 // STOP: the stopping test of the header comment, by the protocol of slp_many.h; `sp` is not looked at without it.
-template <bool LDS, bool STOP>
-__global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, int iters, int first, int stages, AdmmmStop sp) {
+// LIVE (with STOP only): a.list is the form's live list, which k_many_live wrote in front of this launch, and *live_n its length; a
+// workgroup at or past it returns before anything else (*live_n is the same for every lane).  `live_n` is not looked at without it.
+template <bool LDS, bool STOP, bool LIVE>
+__global__ __launch_bounds__(kAdmmmMaxBlock) void k_admmm_iterate(AdmmmArgs a, int iters, int first, int stages, AdmmmStop sp, const i32 *live_n) {
+    static_assert(STOP || !LIVE, "an unarmed state has no stopped LP: no live variant");
     extern __shared__ __attribute__((aligned(16))) double admmm_lds[];
     __shared__ double admmm_red[STOP ? kAdmmmRed : 1];  // unused without STOP: the compiler drops it
     using LD = typename std::conditional<LDS, AdmmLoadPlain, AdmmLoadWorkgroup>::type;
     const LD ld;
+    if (LIVE && blockIdx.x >= (unsigned)*live_n) return;
     const i32 id = a.list[blockIdx.x];
     const AdmmmLp lp = a.lps[id];
     const i32 N = lp.n + lp.m_in, m = lp.m_eq + lp.m_in, W = (i32)blockDim.x, tid = (i32)threadIdx.x;
@@ -363,6 +375,8 @@ struct slp_admm_many {
     double tol_residual = -1.0, tol_step = 0.0;
     i64 check_every = 1, uncounted = 0;
     bool mid_iteration = false;  // between sweep_step and multiplier_step
+    // compaction (slp_many_admm_set_compaction): the launches of an armed call run over the live list of each form
+    ManyFormLists live;
     ~slp_admm_many() { if (base) slp_admm_destroy(base); }
 };
 
@@ -382,30 +396,53 @@ static AdmmmArgs admmm_args(const slp_admm_many *s, int g) {
     return r;
 }
 
-template <bool LDS>
-static void admmm_launch(const slp_admm_many *s, const ManyGroup &gr, const AdmmmArgs &a, int it, int first, int stages, bool stop) {
+// one launch of form g over `wgs` workgroups.  LIVE (armed only): over the form's live list, built in front of it
+template <bool LDS, bool LIVE>
+static void admmm_launch(slp_admm_many *s, int g, AdmmmArgs a, i64 wgs, int it, int first, int stages, bool stop) {
+    const ManyGroup &gr = s->group[g];
     const AdmmmStop sp = {s->ctl.p, s->tol_residual, s->tol_step, s->check_every};
-    const dim3 grid((unsigned)gr.ids.size()), block(gr.block);
+    const dim3 grid((unsigned)wgs), block(gr.block);
     const size_t lds = LDS ? gr.lds_bytes : 0;
-    if (stop) hipLaunchKernelGGL((k_admmm_iterate<LDS, true>), grid, block, lds, ctx().stream, a, it, first, stages, sp);
-    else hipLaunchKernelGGL((k_admmm_iterate<LDS, false>), grid, block, lds, ctx().stream, a, it, first, stages, sp);
+    const i32 *live_n = nullptr;
+    if (LIVE) {
+        many_form_list(s->live, s->group, g, s->table.p, s->ctl.p, s->count);
+        a.list = s->live.ids[g].p;
+        live_n = s->live.n[g].p;
+    }
+    if (stop) hipLaunchKernelGGL((k_admmm_iterate<LDS, true, LIVE>), grid, block, lds, ctx().stream, a, it, first, stages, sp, live_n);
+    else hipLaunchKernelGGL((k_admmm_iterate<LDS, false, false>), grid, block, lds, ctx().stream, a, it, first, stages, sp, live_n);
 }
 
-// `k` times the stages, in launches of at most kmax iterations per form; with the stopping test when it is armed
+// `k` times the stages, in launches of at most kmax iterations per form; with the stopping test when it is armed.  With compaction
+// on an armed call reads the records back first (one download; it synchronises): per form its grid is the number of LPs live then,
+// its cap that of so many workgroups (many_form_call), and every launch runs over the live list k_many_live builds in front of it
+// -- an LP that stops in the call leaves the list at the next launch, the surplus workgroups return at its end.  A form without a
+// live LP launches nothing.
 static void admmm_run(slp_admm_many *s, i64 k, int stages) {
     if (k <= 0) return;
     const bool stop = s->tol_residual >= 0.0;
     if (!stop && (stages & 2)) s->uncounted += k;
     s->mid_iteration = !(stages & 2);
+    const bool live = stop && s->live.on;
+    ManyFormCall call = {};
+    if (live) call = many_form_call(s->lps, many_read_ctl(s->ctl, s->count, s->uncounted).data(), s->group, ctx().num_cu, s->cap);
     for (int g = 0; g < 2; ++g) {
         const ManyGroup &gr = s->group[g];
-        if (gr.ids.empty()) continue;
+        if (gr.ids.empty() || (live && call.live[g] == 0)) continue;
         const AdmmmArgs a = admmm_args(s, g);
+        const i64 wgs = live ? call.live[g] : (i64)gr.ids.size(), cap = live ? call.cap[g] : gr.kmax;
         bool xp_is_x = s->xp_is_x;
-        many_split(k, gr.kmax, [&](int it) {
+        many_split(k, cap, [&](int it) {
             const int first = ((stages & 1) && !xp_is_x) ? 1 : 0;
-            if (g == 0) admmm_launch<true>(s, gr, a, it, first, stages, stop);
-            else admmm_launch<false>(s, gr, a, it, first, stages, stop);
+            if (live) {
+                if (g == 0) admmm_launch<true, true>(s, g, a, wgs, it, first, stages, stop);
+                else admmm_launch<false, true>(s, g, a, wgs, it, first, stages, stop);
+            } else {
+                if (g == 0) admmm_launch<true, false>(s, g, a, wgs, it, first, stages, stop);
+                else admmm_launch<false, false>(s, g, a, wgs, it, first, stages, stop);
+            }
+            s->live.launched[g] = wgs;
+            s->live.cap[g] = cap;
             if (stages & 2) xp_is_x = true;  // :259
             return it;
         });
@@ -439,6 +476,7 @@ static void admmm_plan(slp_admm_many *s) {
         }
         gr.block = many_width(want, kAdmmmMaxBlock);
         gr.lds_bytes = g == 0 ? (size_t)doubles * sizeof(double) : 0;
+        gr.passes = passes;
         gr.kmax = many_launch_cap(kManyUnitsPerLaunch, passes, (i64)gr.ids.size(), ctx().num_cu, s->cap);
     }
 }
@@ -605,8 +643,10 @@ slp_admm_many *slp_admm_many_create(int64_t count, const int64_t *n, const int64
         hipLaunchKernelGGL(k_admmm_localise, per_lp, dim3(kBlock), 0, st, s->table.p, A.ptr.p, A.idx.p, At.ptr.p, At.idx.p, nn, Me);
         SLP_HIP(hipGetLastError());
         many_upload_lists(s->group, s->list);
-        many_lds_opt_in(reinterpret_cast<const void *>(k_admmm_iterate<true, false>), s->group[0].lds_bytes, kAdmmmLdsLimit * sizeof(double));
-        many_lds_opt_in(reinterpret_cast<const void *>(k_admmm_iterate<true, true>), s->group[0].lds_bytes, kAdmmmLdsLimit * sizeof(double));
+        for (const void *kernel : {reinterpret_cast<const void *>(k_admmm_iterate<true, false, false>),
+                                   reinterpret_cast<const void *>(k_admmm_iterate<true, true, false>),
+                                   reinterpret_cast<const void *>(k_admmm_iterate<true, true, true>)})
+            many_lds_opt_in(kernel, s->group[0].lds_bytes, kAdmmmLdsLimit * sizeof(double));
         s->b.alloc((size_t)M); s->lam.alloc((size_t)M); s->lam.zero();
         for (DevBuf<double> *v : {&s->q, &s->c, &s->lb, &s->ub, &s->xp0, &s->x, &s->y}) v->alloc((size_t)N);
         s->y.zero();
@@ -667,6 +707,22 @@ int slp_many_admm_stop_state(slp_admm_many *s, int64_t *iterations, int32_t *sto
             if (residual) residual[k] = h[k].residual;
             if (step) step[k] = h[k].step;
         }
+    })
+}
+
+int slp_many_admm_set_compaction(slp_admm_many *s, int on) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_admm_set_compaction: NULL handle");
+        SLP_REQUIRE(on == 0 || on == 1, "slp_many_admm_set_compaction: on must be 0 or 1");
+        if (on) many_form_alloc(s->live, s->group);
+        s->live.on = on != 0;
+    })
+}
+
+int slp_many_admm_live_state(slp_admm_many *s, int64_t live[2], int32_t *order, int64_t launched[2], int64_t cap[2]) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_admm_live_state: NULL handle");
+        many_form_state("slp_many_admm_live_state", s->live, s->group, s->table.p, s->ctl.p, s->count, live, order, launched, cap);
     })
 }
 

@@ -63,6 +63,15 @@
 // order (many_fold: one loop, four chains), writes the record CpmGap (primal, bound, violation: +inf, -inf, +inf before the first check) and ONE decision slot, and a
 // last barrier later every lane reads it.  The two sums are in that fixed order, a function of the shapes only.  The head of
 // CpmCtl is shared with the step test; nothing waits in a record between primal_step and dual_step.
+//
+// Compaction (slp_many_cp_set_compaction, include/slp_hip_ext_many_live.h; off after create): the template parameter LIVE of the
+// two armed kernels.  Without it a stopped LP keeps its workgroup index, the launch its full grid and its cap.  With compaction on
+// and a test armed, cpm_run reads the records back at the start of a call (one download; it synchronises), and per form every
+// launch of the call is preceded by k_many_live<ManyFormLive<CpmLp, CpmCtl>> (slp_many.h: the LPs of that form that are not
+// stopped, in increasing order, and their count) and is <., ., true> over as many workgroups as LPs of the form were live when
+// the call began, held to the cap of that many workgroups (many_form_call, slp_many_plan.h): a.list is the live list, a workgroup
+// at or past *live_n returns before anything else.  A form without a live LP launches nothing.  An LP's iterations read and write
+// its own data only, so which workgroup runs them changes no bit.  <., ., false> never looks at live_n: the kernels above.
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -71,6 +80,7 @@
 #include "slp_cp_shared.h"
 #include "slp_kernels.h"
 #include "slp_many.h"
+#include "../../include/slp_hip_ext_many_live.h"
 
 namespace slp {
 
@@ -212,12 +222,16 @@ __device__ __forceinline__ double cpm_dual_half(const CpmArgs &a, const CpmView 
 
 // `iters` times the stages of one LP (bit 0 primal half, bit 1 dual half); store: the primal half also writes x4.
 // STOP: the step test of the header comment, by the protocol of slp_many.h; `sp` is not looked at without it.
-template <bool LDS, bool STOP>
-__global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int iters, int stages, int store, CpmStop sp) {
+// LIVE (with STOP only): a.list is the form's live list, which k_many_live wrote in front of this launch, and *live_n its length; a
+// workgroup at or past it returns before anything else (*live_n is the same for every lane).  `live_n` is not looked at without it.
+template <bool LDS, bool STOP, bool LIVE>
+__global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate(CpmArgs a, int iters, int stages, int store, CpmStop sp, const i32 *live_n) {
+    static_assert(STOP || !LIVE, "an unarmed state has no stopped LP: no live variant");
     extern __shared__ __attribute__((aligned(16))) double cpm_lds[];
     __shared__ double cpm_red[STOP ? 2 * kCpmWaves + 1 : 1];  // per wave the maxima of the two halves, then the decision
     using LD = typename std::conditional<LDS, CpLoadPlain, CpLoadWorkgroup>::type;
     const LD ld;
+    if (LIVE && blockIdx.x >= (unsigned)*live_n) return;
     const i32 id = a.list[blockIdx.x];
     i64 done = 0, until = 0;
     if (STOP && !many_enter(sp.ctl + id, sp.check_every, &done, &until)) return;
@@ -283,12 +297,14 @@ struct CpmGapStop {
 // k_cpm_iterate with the duality-gap certificate (slp_cp_gap.h) as the per-LP stopping test (header comment).  An iteration that
 // is no check is the two halves above plus two scalar counters; a check iteration has its own dual loop and the certificate's
 // pass over the columns.  Every branch around a barrier is on `stages`, `until`, the record or the decision slot: uniform.
-template <bool LDS>
-__global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate_gap(CpmArgs a, int iters, int stages, int store, CpmGapStop sp) {
+// LIVE: as in k_cpm_iterate.
+template <bool LDS, bool LIVE>
+__global__ __launch_bounds__(kCpmMaxBlock) void k_cpm_iterate_gap(CpmArgs a, int iters, int stages, int store, CpmGapStop sp, const i32 *live_n) {
     extern __shared__ __attribute__((aligned(16))) double cpm_lds[];
     __shared__ double cpm_red[4 * kCpmWaves + 1];  // per wave: sum y b, violation, c x, the bound's column terms; then the decision
     using LD = typename std::conditional<LDS, CpLoadPlain, CpLoadWorkgroup>::type;
     const LD ld;
+    if (LIVE && blockIdx.x >= (unsigned)*live_n) return;
     const i32 id = a.list[blockIdx.x];
     i64 done, until;
     if (!many_enter(sp.ctl + id, sp.check_every, &done, &until)) return;
@@ -412,6 +428,9 @@ struct slp_cp_many {
     // the certificate (slp_many_cpgap_set_stop): off while tol_gap < 0; at most one of the two tests is armed
     DevBuf<CpmGap> gap;
     double tol_gap = -1.0, tol_feas = 0.0;
+    // compaction (slp_many_cp_set_compaction): the launches of an armed call run over the live list of each form
+    ManyFormLists live;
+    i64 cap = kManyMaxItersPerLaunch;  // SLP_CP_MANY_KMAX
     ~slp_cp_many() { delete k; }
 };
 
@@ -432,30 +451,53 @@ static CpmArgs cpm_args(const slp_cp_many *s, int g) {
     return r;
 }
 
-template <bool LDS>
-static void cpm_launch(const slp_cp_many *s, const ManyGroup &gr, const CpmArgs &a, int it, int stages, bool store, int stop) {
+// one launch of form g over `wgs` workgroups.  LIVE (armed only): over the form's live list, built in front of it
+template <bool LDS, bool LIVE>
+static void cpm_launch(slp_cp_many *s, int g, CpmArgs a, i64 wgs, int it, int stages, bool store, int stop) {
+    const ManyGroup &gr = s->group[g];
     const CpmStop sp = {s->ctl.p, s->tol, s->check_every};
-    const dim3 grid((unsigned)gr.ids.size()), block(gr.block);
+    const dim3 grid((unsigned)wgs), block(gr.block);
     const size_t lds = LDS ? gr.lds_bytes : 0;
+    const i32 *live_n = nullptr;
+    if (LIVE) {
+        many_form_list(s->live, s->group, g, s->table.p, s->ctl.p, s->count);
+        a.list = s->live.ids[g].p;
+        live_n = s->live.n[g].p;
+    }
     if (stop == 2) {
         const CpmGapStop gp = {s->ctl.p, s->gap.p, s->tol_gap, s->tol_feas, s->check_every};
-        hipLaunchKernelGGL((k_cpm_iterate_gap<LDS>), grid, block, lds, ctx().stream, a, it, stages, (int)store, gp);
-    } else if (stop) hipLaunchKernelGGL((k_cpm_iterate<LDS, true>), grid, block, lds, ctx().stream, a, it, stages, (int)store, sp);
-    else hipLaunchKernelGGL((k_cpm_iterate<LDS, false>), grid, block, lds, ctx().stream, a, it, stages, (int)store, sp);
+        hipLaunchKernelGGL((k_cpm_iterate_gap<LDS, LIVE>), grid, block, lds, ctx().stream, a, it, stages, (int)store, gp, live_n);
+    } else if (stop) hipLaunchKernelGGL((k_cpm_iterate<LDS, true, LIVE>), grid, block, lds, ctx().stream, a, it, stages, (int)store, sp, live_n);
+    else hipLaunchKernelGGL((k_cpm_iterate<LDS, false, false>), grid, block, lds, ctx().stream, a, it, stages, (int)store, sp, live_n);
 }
 
 // `k` times the stages, in launches of at most kmax iterations per form; with the stopping test that is armed (1 the step, 2 the
-// certificate), unless `plain` (the half-iteration timings of slp_cp_many_bench, which are no iterations)
+// certificate), unless `plain` (the half-iteration timings of slp_cp_many_bench, which are no iterations).  With compaction on an
+// armed call reads the records back first (one download; it synchronises): per form its grid is the number of LPs live then, its
+// cap that of so many workgroups (many_form_call), and every launch runs over the live list k_many_live builds in front of it -- an
+// LP that stops in the call leaves the list at the next launch, the surplus workgroups return at its end.  A form without a live
+// LP launches nothing.
 static void cpm_run(slp_cp_many *s, i64 k, int stages, bool store, bool plain = false) {
     const int stop = plain ? 0 : (s->tol_gap >= 0.0 ? 2 : (s->tol >= 0.0 ? 1 : 0));
     if (!stop && !plain && (stages & 2)) s->uncounted += k;
+    const bool live = stop && s->live.on;
+    ManyFormCall call = {};
+    if (live && k > 0) call = many_form_call(s->lps, many_read_ctl(s->ctl, s->count, s->uncounted).data(), s->group, ctx().num_cu, s->cap);
     for (int g = 0; g < 2; ++g) {
         const ManyGroup &gr = s->group[g];
-        if (gr.ids.empty()) continue;
+        if (gr.ids.empty() || (live && call.live[g] == 0)) continue;
         const CpmArgs a = cpm_args(s, g);
-        many_split(k, gr.kmax, [&](int it) {
-            if (g == 0) cpm_launch<true>(s, gr, a, it, stages, store, stop);
-            else cpm_launch<false>(s, gr, a, it, stages, store, stop);
+        const i64 wgs = live ? call.live[g] : (i64)gr.ids.size(), cap = live ? call.cap[g] : gr.kmax;
+        many_split(k, cap, [&](int it) {
+            if (live) {
+                if (g == 0) cpm_launch<true, true>(s, g, a, wgs, it, stages, store, stop);
+                else cpm_launch<false, true>(s, g, a, wgs, it, stages, store, stop);
+            } else {
+                if (g == 0) cpm_launch<true, false>(s, g, a, wgs, it, stages, store, stop);
+                else cpm_launch<false, false>(s, g, a, wgs, it, stages, store, stop);
+            }
+            s->live.launched[g] = wgs;
+            s->live.cap[g] = cap;
             return it;
         });
     }
@@ -488,7 +530,7 @@ static void cpm_state(slp_cp_many *s, int64_t *iterations, int32_t *stopped, dou
 // form per LP, workgroup, LDS and launch cap per form -- from the shapes (and the two environment switches) only
 static void cpm_plan(slp_cp_many *s) {
     const int force = many_form_switch("SLP_CP_MANY_FORM");
-    const i64 cap = many_kmax_switch("SLP_CP_MANY_KMAX", kManyMaxItersPerLaunch);
+    const i64 cap = s->cap = many_kmax_switch("SLP_CP_MANY_KMAX", kManyMaxItersPerLaunch);
     std::vector<i64> lds_doubles;
     for (const CpmLp &lp : s->lps) lds_doubles.push_back(2 * (i64)lp.n + lp.m_eq + lp.m_in);
     const std::vector<i32> form =
@@ -511,6 +553,7 @@ static void cpm_plan(slp_cp_many *s) {
             const CpmLp &lp = s->lps[(size_t)k];
             passes = std::max<i64>(passes, (lp.n + w - 1) / w + ((i64)lp.m_eq + lp.m_in + w - 1) / w);
         }
+        gr.passes = passes;
         gr.kmax = many_launch_cap(kManyUnitsPerLaunch, passes, (i64)gr.ids.size(), ctx().num_cu, cap);
     }
 }
@@ -572,9 +615,12 @@ slp_cp_many *slp_cp_many_create(int64_t count, const int64_t *n, const int64_t *
                            s->k->at.ptr.p, s->k->at.idx.p, Me);
         SLP_HIP(hipGetLastError());
         many_upload_lists(s->group, s->list);
-        many_lds_opt_in(reinterpret_cast<const void *>(k_cpm_iterate<true, false>), s->group[0].lds_bytes, kCpmLdsLimit * sizeof(double));
-        many_lds_opt_in(reinterpret_cast<const void *>(k_cpm_iterate<true, true>), s->group[0].lds_bytes, kCpmLdsLimit * sizeof(double));
-        many_lds_opt_in(reinterpret_cast<const void *>(k_cpm_iterate_gap<true>), s->group[0].lds_bytes, kCpmLdsLimit * sizeof(double));
+        for (const void *kernel : {reinterpret_cast<const void *>(k_cpm_iterate<true, false, false>),
+                                   reinterpret_cast<const void *>(k_cpm_iterate<true, true, false>),
+                                   reinterpret_cast<const void *>(k_cpm_iterate<true, true, true>),
+                                   reinterpret_cast<const void *>(k_cpm_iterate_gap<true, false>),
+                                   reinterpret_cast<const void *>(k_cpm_iterate_gap<true, true>)})
+            many_lds_opt_in(kernel, s->group[0].lds_bytes, kCpmLdsLimit * sizeof(double));
         s->c.upload(c, (size_t)N);
         s->lb.upload(lb, (size_t)N);
         s->ub.upload(ub, (size_t)N);
@@ -649,6 +695,22 @@ int slp_many_cp_stop_state(slp_cp_many *s, int64_t *iterations, int32_t *stopped
     SLP_API_INT({
         SLP_REQUIRE(s, "slp_many_cp_stop_state: NULL handle");
         cpm_state(s, iterations, stopped, step, nullptr, nullptr, nullptr);
+    })
+}
+
+int slp_many_cp_set_compaction(slp_cp_many *s, int on) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_cp_set_compaction: NULL handle");
+        SLP_REQUIRE(on == 0 || on == 1, "slp_many_cp_set_compaction: on must be 0 or 1");
+        if (on) many_form_alloc(s->live, s->group);
+        s->live.on = on != 0;
+    })
+}
+
+int slp_many_cp_live_state(slp_cp_many *s, int64_t live[2], int32_t *order, int64_t launched[2], int64_t cap[2]) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_many_cp_live_state: NULL handle");
+        many_form_state("slp_many_cp_live_state", s->live, s->group, s->table.p, s->ctl.p, s->count, live, order, launched, cap);
     })
 }
 

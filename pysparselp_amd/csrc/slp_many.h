@@ -123,6 +123,50 @@ __global__ __launch_bounds__(kManyLiveLanes) void k_many_live(Pred pred, i32 cou
     if (tid == 0) *live_n = all;
 }
 
+// the live list of each form of a solver with two forms (slp_cp_many.hip, slp_admm_many.hip), and what its last launches were
+struct ManyFormLists {
+    DevBuf<i32> ids[2], n[2];   // allocated at the first use: as many entries as the form has LPs, and one
+    bool on = false;            // compaction (slp_many_*_set_compaction; off after create)
+    i64 launched[2] = {0, 0};   // the workgroups of the form's last iteration launch
+    i64 cap[2] = {0, 0};        // the cap of the last call that launched the form
+};
+
+inline void many_form_alloc(ManyFormLists &l, const ManyGroup group[2]) {
+    for (int g = 0; g < 2; ++g) {
+        if (l.n[g].p) continue;
+        l.ids[g].alloc(std::max<size_t>(1, group[g].ids.size()));
+        l.n[g].alloc(1);
+    }
+}
+
+// the list of form g from the flags as they are on the device, behind everything enqueued so far: at most the form's LPs
+template <class Lp, class Ctl>
+void many_form_list(ManyFormLists &l, const ManyGroup group[2], int g, const Lp *lps, const Ctl *ctl, i64 count) {
+    many_form_alloc(l, group);
+    hipLaunchKernelGGL((k_many_live<ManyFormLive<Lp, Ctl>>), dim3(1), dim3(kManyLiveLanes), 0, ctx().stream, ManyFormLive<Lp, Ctl>{lps, ctl, g},
+                       (i32)count, l.ids[g].p, l.n[g].p);
+}
+
+// what both *_live_state calls do behind their handle check (include/slp_hip_ext_many_live.h); synchronises
+template <class Lp, class Ctl>
+void many_form_state(const char *who, ManyFormLists &l, const ManyGroup group[2], const Lp *lps, const Ctl *ctl, i64 count, int64_t *live,
+                     int32_t *order, int64_t *launched, int64_t *cap) {
+    i64 at = 0;
+    for (int g = 0; g < 2; ++g) {
+        many_form_list(l, group, g, lps, ctl, count);
+        SLP_HIP(hipGetLastError());
+        i32 n = 0;
+        l.n[g].download(&n, 1);   // synchronises
+        if (n < 0 || n > (i64)group[g].ids.size()) throw Error(std::string(who) + ": the device's count of live LPs is out of range");
+        if (live) live[g] = n;
+        if (order && n) l.ids[g].download(order + at, (size_t)n);
+        at += n;
+        if (launched) launched[g] = l.launched[g];
+        if (cap) cap[g] = l.cap[g];
+    }
+    if (order) std::fill(order + at, order + count, -1);
+}
+
 // host: the records with the iterations of the unarmed launches added (no LP is stopped while the test is off); synchronises
 template <class Ctl>
 std::vector<Ctl> many_read_ctl(const DevBuf<Ctl> &ctl, i64 count, i64 uncounted) {

@@ -39,6 +39,7 @@ struct ManyGroup {
     int block = 64;
     size_t lds_bytes = 0;
     int64_t kmax = 1;  // iterations one launch may hold
+    int64_t passes = 1;  // what kmax was made of: the passes of one iteration of the group's largest LP
 };
 
 // the switch `name`: -1 when unset or empty, 0 for lds, 1 for global
@@ -124,6 +125,36 @@ constexpr void many_live_write(ManyLiveRange r, int32_t at, int32_t *out, const 
 // iterations a launch of a call may hold when `live` LPs are live at its start: the cap of that many workgroups
 inline int64_t many_live_cap(int64_t passes, int64_t live, int64_t cus, int64_t cap) {
     return many_launch_cap(kManyUnitsPerLaunch, passes, std::max<int64_t>(1, live), cus, cap);
+}
+
+// ---- the live list per form (slp_cp_many.hip, slp_admm_many.hip: the LPs of each form are a launch of their own) ----
+// "LP k has form `form` and is not stopped", over ALL LPs of the list: the predicate k_many_live takes for the list of one form.
+// Lp: the solver's table entry (its `form`: 0 lds, 1 global); Ctl: its control record, whose head is ManyCtl (its `stopped`) -- a
+// template, because the records of the solvers differ in size.  constexpr: host and device alike under hipcc.
+template <class Lp, class Ctl>
+struct ManyFormLive {
+    const Lp *lps;
+    const Ctl *ctl;
+    int32_t form;
+    constexpr bool operator()(int32_t k) const { return lps[k].form == form && ctl[k].stopped == 0; }
+};
+
+// per form: the LPs live now and the iterations a launch over that many workgroups may hold
+struct ManyFormCall {
+    int64_t live[2], cap[2];
+};
+
+// What a compacted call is made of, from the records read back (`ctl`, one per LP of `lps`): per form the number of live LPs --
+// ManyFormLive counted by the chunk plan's own loop -- and many_live_cap of the group's passes for that many workgroups (a form
+// without a live LP launches nothing; its cap is that of one workgroup).  `cap`: many_kmax_switch.
+template <class Lp, class Ctl>
+inline ManyFormCall many_form_call(const std::vector<Lp> &lps, const Ctl *ctl, const ManyGroup group[2], int64_t cus, int64_t cap) {
+    ManyFormCall r;
+    for (int g = 0; g < 2; ++g) {
+        r.live[g] = many_live_count(ManyLiveRange{0, (int32_t)lps.size()}, ManyFormLive<Lp, Ctl>{lps.data(), ctl, g});
+        r.cap[g] = many_live_cap(group[g].passes, r.live[g], cus, cap);
+    }
+    return r;
 }
 
 // rows r0 <= r < r1 of a CSR block belong to LP `lp`, whose column indices there lie in lo <= j < hi
