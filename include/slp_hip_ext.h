@@ -20,6 +20,8 @@
 #include "slp_hip_ext_dga_many_live.h"
 /* the Chambolle-Pock and the ADMM list solver over the lists of their live LPs (compaction): likewise */
 #include "slp_hip_ext_many_live.h"
+/* per-instance right-hand sides of the batched dual ascent and the batched ADMM solver: likewise */
+#include "slp_hip_ext_batch_rhs.h"
 /* which packet form a tall-cell product copy has: likewise */
 #include "slp_hip_ext_tall.h"
 

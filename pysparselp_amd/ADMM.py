@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _lib
 from . import _many
-from ._batch import concat, first_offsets, shared_or_batched
+from ._batch import check_rhs, check_rhs_order, concat, first_offsets, shared_or_batched
 from ._lib import ORDER_AUTO
 from .tools import convert_to_standard_form_with_bounds, normal_matrix, precondition_constraints
 
@@ -258,9 +258,24 @@ def _validate_batch(cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0):
     return np.ascontiguousarray(cs), a_eq, beq, a_ineq, b_lower, b_upper, lb, lb_b, ub, ub_b, x0, x0_b
 
 
+def _check_batch_rhs(batch, m_eq, m_ineq, beq, b_lower, b_upper, kept_lower=None, kept_upper=None):
+    """The sides of ``ADMMBatchState.set_rhs`` checked without the library: each None or a contiguous float64 array of shape
+    ``(rows,)`` or ``(batch, rows)``; a side of a block without rows becomes None.  ``kept_lower`` / ``kept_upper``: what the other
+    side of the inequality block is compared against when only one is given."""
+    beq = None if beq is None or m_eq == 0 else check_rhs("beq", beq, batch, m_eq, finite=True)[0]
+    if beq is not None and beq.ndim == 1 and not np.all(np.isfinite(beq)):
+        raise ValueError("beq has an entry that is not finite")
+    b_lower = None if b_lower is None or m_ineq == 0 else check_rhs("b_lower", b_lower, batch, m_ineq)[0]
+    b_upper = None if b_upper is None or m_ineq == 0 else check_rhs("b_upper", b_upper, batch, m_ineq)[0]
+    if b_lower is not None or b_upper is not None:
+        check_rhs_order(kept_lower if b_lower is None else b_lower, kept_upper if b_upper is None else b_upper, batch)
+    return beq, b_lower, b_upper
+
+
 class ADMMBatchState:
     """Device-resident batched ADMM state (thin RAII wrapper of ``slp_admm_batch``): ``cs`` is ``(B, n)``; ``lb``, ``ub``, ``x0``
-    are shared vectors or carry a leading axis ``B``; the constraint blocks and their right-hand sides are shared."""
+    are shared vectors or carry a leading axis ``B``; the constraint blocks are shared, and so are their right-hand sides until
+    ``set_rhs`` gives every instance its own."""
 
     def __init__(self, cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0=None, gamma_eq=2, gamma_ineq=3, use_preconditioning=True):
         cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, lb_b, ub, ub_b, x0, x0_b = _validate_batch(cs, a_eq, beq, a_ineq, b_lower, b_upper,
@@ -269,6 +284,8 @@ class ADMMBatchState:
         m_eq = a_eq.shape[0] if a_eq is not None else 0
         m_ineq = a_ineq.shape[0]
         self.N, self.m = self.n + m_ineq, m_eq + m_ineq
+        self.m_eq, self.m_ineq = m_eq, m_ineq
+        self._b_lower, self._b_upper = b_lower, b_upper   # what set_rhs compares a new side against
         eq = (None, None, None) if a_eq is None else (_lib.ptr(a_eq.indptr), _lib.ptr(a_eq.indices), _lib.ptr(a_eq.data))
         # all of the above needs no GPU; the library is loaded (and bound to a device) only now
         self._l = _lib.lib()
@@ -298,6 +315,28 @@ class ADMMBatchState:
         out = np.zeros((self.batch, 3))
         _lib.check(self._l.slp_admm_batch_report(self._h, _lib.ptr(out)))
         return out
+
+    def set_rhs(self, beq=None, b_lower=None, b_upper=None):
+        """Replaces right-hand sides (``slp_admm_batch_set_rhs``): ``beq`` of shape ``(m_eq,)`` or ``(B, m_eq)``, ``b_lower`` and
+        ``b_upper`` of shape ``(m_ineq,)`` or ``(B, m_ineq)``, in the units of the constructor; None keeps what the state has.  The
+        library scales them with the row scalings of the shared set-up chain and rebuilds, per instance, ``b``, ``q`` and the slack
+        part of ``lb`` / ``ub``, so instance k is bit for bit ``lp_admm(..., order=ORDER_SEQUENTIAL)`` on row k.  Only before the
+        first iteration or half iteration (``SlpError`` afterwards, the state keeps what it had); may be called more than once.  A
+        wrong shape, a NaN, an infinite entry of a batched ``beq`` or ``b_lower[k] > b_upper[k]`` on a row (both name the instance)
+        is a ``ValueError`` before the library is touched."""
+        return self._set_rhs(*_check_batch_rhs(self.batch, self.m_eq, self.m_ineq, beq, b_lower, b_upper, self._b_lower, self._b_upper))
+
+    def _set_rhs(self, beq, b_lower, b_upper):
+        """``set_rhs`` with sides that ``_check_batch_rhs`` has checked."""
+        args = []
+        for v in (beq, b_lower, b_upper):
+            args += [_lib.ptr(v), 0 if v is None else int(v.ndim == 2)]
+        _lib.check(self._l.slp_admm_batch_set_rhs(self._h, *args))
+        # only now: after a refusal the state, and what a later call is compared against, keep the sides they had
+        if b_lower is not None:
+            self._b_lower = b_lower
+        if b_upper is not None:
+            self._b_upper = b_upper
 
     def set_stop(self, tol_residual, tol_step, check_every=1):
         """Arms the per-instance stopping test of the iteration kernels (``slp_admm_batch_set_stop``): at the end of every
@@ -371,8 +410,9 @@ def lp_admm_batch(
     ``a_eq x = beq``, ``b_lower <= a_ineq x <= b_upper``, ``lb[k] <= x <= ub[k]`` for every k.
 
     ``cs`` has shape ``(B, n)``; ``lb``, ``ub`` and ``x0`` each have shape ``(n,)`` (shared by all instances) or ``(B, n)``.
-    The right-hand sides are shared: a 2-D ``beq``, ``b_lower`` or ``b_upper`` raises ``ValueError`` (per-instance right-hand
-    sides are not built), like every shape, finiteness and column-index error, before anything is uploaded.  The instances
+    The right-hand sides are shared: a 2-D ``beq``, ``b_lower`` or ``b_upper`` raises ``ValueError`` (right-hand sides per
+    instance are what ``lp_admm_batch_rhs`` takes), like every shape, finiteness and column-index error, before anything is
+    uploaded.  The instances
     share the whole set-up chain (ADMM.py:73-101), ``M`` and its Gauss-Seidel plan; every instance is bit for bit what
     ``lp_admm(..., order=ORDER_SEQUENTIAL)`` computes for it.
 
@@ -388,10 +428,17 @@ def lp_admm_batch(
 
 
 def _admm_batch_run(cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
-                    use_preconditioning, nb_iter_plot, stop):
+                    use_preconditioning, nb_iter_plot, stop, rhs=None):
     """``lp_admm_batch`` (``stop`` None) and ``lp_admm_batch_until`` (``stop`` the checked ``(tol_residual, tol_step,
-    check_every)``): ``(X, info)``, ``info`` None without a stopping test."""
+    check_every)``): ``(X, info)``, ``info`` None without a stopping test.  ``rhs``: the checked ``(beq, b_lower, b_upper)`` of
+    ``lp_admm_batch_rhs``, handed to ``set_rhs`` before the first iteration."""
     state = ADMMBatchState(cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, use_preconditioning)
+    if rhs is not None:
+        try:
+            state._set_rhs(*rhs)
+        except BaseException:
+            state.close()
+            raise
     n = state.n
     solved = np.arange(state.batch)  # every instance takes part
     info = None if stop is None else _many.new_stop_info(state.batch, solved, residual=True)
@@ -483,6 +530,78 @@ def lp_admm_batch_until(
     tol_step, _ = _many.check_stop(tol_step, check_every, "tol_step")
     return _admm_batch_run(cs, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
                            use_preconditioning, nb_iter_plot, (tol_residual, tol_step, check_every))
+
+
+def lp_admm_batch_rhs(
+    cs,
+    a_eq,
+    beq,
+    a_ineq,
+    b_lower,
+    b_upper,
+    lb,
+    ub,
+    tol_residual=None,
+    tol_step=None,
+    check_every=10,
+    x0=None,
+    gamma_eq=2,
+    gamma_ineq=3,
+    nb_iter=100,
+    callback_func=None,
+    max_time=None,
+    use_preconditioning=True,
+    nb_iter_plot=10,
+):
+    """``lp_admm_batch`` / ``lp_admm_batch_until`` with right-hand sides per instance (extension): ``beq`` has shape ``(m_eq,)`` or
+    ``(B, m_eq)``, ``b_lower`` and ``b_upper`` ``(m_ineq,)`` or ``(B, m_ineq)`` (or None: no such bound) -- a sweep over
+    capacities, budgets or demands.  Returns ``(X, info)``; ``info`` is None without tolerances.
+
+    The row scalings of the set-up chain depend on the matrices only, so the instances still share the chain, ``M`` and its
+    Gauss-Seidel plan; ``ADMMBatchState.set_rhs`` builds every instance's ``b``, ``q`` and slack bounds on the device.  Instance k
+    is bit for bit ``lp_admm(cs[k], a_eq, beq[k], a_ineq, b_lower[k], b_upper[k], ..., order=ORDER_SEQUENTIAL)``.  The loop, the
+    reports and ``callback_func`` are those of ``lp_admm_batch``; the energies and violations handed to the callback are each
+    instance's own, against its own right-hand sides.  With ``tol_residual`` and ``tol_step`` (both or neither) the stopping
+    test, its arguments and ``info`` are those of ``lp_admm_batch_until``.
+
+    A wrong shape, a NaN, an infinite entry of a batched ``beq`` or ``b_lower[k] > b_upper[k]`` on a row (both name the instance)
+    raises ``ValueError`` before the library is loaded, like every error of ``lp_admm_batch`` and of the stopping arguments.
+    """
+    stop, rhs = _check_admm_batch_rhs_call(cs, a_eq, beq, a_ineq, b_lower, b_upper, tol_residual, tol_step, check_every)
+    return _admm_batch_rhs_run(cs, a_eq, beq, a_ineq, rhs, lb, ub, stop, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
+                               use_preconditioning, nb_iter_plot)
+
+
+def _check_admm_batch_rhs_call(cs, a_eq, beq, a_ineq, b_lower, b_upper, tol_residual, tol_step, check_every):
+    """What ``lp_admm_batch_rhs`` checks of its own, without the library: ``(stop, rhs)``, ``stop`` the checked ``(tol_residual,
+    tol_step, check_every)`` or None, ``rhs`` the three sides as ``_check_batch_rhs`` returns them."""
+    stop = None
+    if tol_residual is not None or tol_step is not None:
+        if tol_residual is None or tol_step is None:
+            raise ValueError("tol_residual and tol_step go together: give both, or neither for the fixed horizon")
+        tol_residual, check_every = _many.check_stop(tol_residual, check_every, "tol_residual")
+        tol_step, _ = _many.check_stop(tol_step, check_every, "tol_step")
+        stop = (tol_residual, tol_step, check_every)
+    from .tools import CsrArrays
+
+    if np.ndim(cs) != 2:
+        raise ValueError(f"cs has shape {np.shape(cs)}: expected (B, n), one row of costs per instance")
+    batch = np.shape(cs)[0]
+    shapes = [0 if a is None else CsrArrays.from_any(a).shape[0] for a in (a_eq, a_ineq)]
+    return stop, _check_batch_rhs(batch, shapes[0], shapes[1], beq, b_lower, b_upper)
+
+
+def _admm_batch_rhs_run(cs, a_eq, beq, a_ineq, rhs, lb, ub, stop, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
+                        use_preconditioning, nb_iter_plot):
+    """``lp_admm_batch_rhs`` behind its checks (``_check_admm_batch_rhs_call`` gives ``stop`` and ``rhs``)."""
+    first = [None if v is None else (v[0] if v.ndim == 2 else v) for v in rhs]   # the state is created with instance 0's sides
+    if a_eq is not None and beq is None:
+        raise ValueError("a_eq without beq")
+    if a_eq is not None and first[0] is None:
+        first[0] = beq
+    rhs = tuple(v if v is not None and v.ndim == 2 else None for v in rhs)   # a 1-D side is the one the state is created with
+    return _admm_batch_run(cs, a_eq, first[0], a_ineq, first[1], first[2], lb, ub, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
+                           use_preconditioning, nb_iter_plot, stop, rhs=rhs if any(v is not None for v in rhs) else None)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

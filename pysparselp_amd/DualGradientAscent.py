@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from . import _many
-from ._batch import check_costs, check_targets, concat, first_offsets, require_one_sided, shared_or_batched, split_by
+from ._batch import check_costs, check_rhs, check_targets, concat, first_offsets, require_one_sided, shared_or_batched, split_by
 
 PATHS = {"auto": 0, "fused": 1, "general": 2}
 FUSED_MAX = 8192    # most variables of the fused search (one workgroup, breakpoints in LDS)
@@ -276,7 +276,8 @@ def dual_gradient_ascent(x, lp, nb_max_iter=1000, callback_func=None, y_eq=None,
 
 class DeviceDGABatch(_DeviceDGA):
     """``DeviceDGA`` for B LPs over one ``DeviceMatrix`` ``a`` (with its CSR: not chunked) and one ``b`` (``slp_batch_dga_*``):
-    ``c`` of shape ``(B, n)``; ``lb``, ``ub`` of shape ``(n,)`` or ``(B, n)``; ``y0`` of shape ``(m,)`` or ``(B, m)``.  Results
+    ``c`` of shape ``(B, n)``; ``lb``, ``ub`` of shape ``(n,)`` or ``(B, n)``; ``y0`` of shape ``(m,)`` or ``(B, m)``; ``set_rhs``
+    gives every instance a ``b`` of its own before the first iteration.  Results
     carry a leading axis B.  All instances read one stream of tie draws (``draws(count)``, default a private ``RandomState(0)``),
     each at its own position.  An instance whose start has dual energy ``-inf`` is frozen (``frozen()``): its x and y stay the
     start's.  ``path``: ``"auto"`` (the fused search, one workgroup per instance, up to ``FUSED_AUTO`` variables and, from
@@ -345,6 +346,16 @@ class DeviceDGABatch(_DeviceDGA):
         _lib.check(self._l.slp_batch_dga_report(self._h, _lib.ptr(out)))
         return out
 
+    def set_rhs(self, b):
+        """Replaces the right-hand side (``slp_batch_dga_set_rhs``): ``b`` of shape ``(m,)`` -- one for all instances -- or ``(B, m)``
+        over the rows of ``[A_eq; A_ineq]``, one row per instance.  Instance k is then bit for bit ``DeviceDGA`` on ``b[k]``: the
+        gradient, ``g . b`` and the ``y . b`` of the energy read the instance's own vector, and which instances are frozen is
+        derived again.  Only before the first iteration (``SlpError`` afterwards, the state keeps running with the right-hand
+        sides it had); may be called more than once.  A wrong shape, a NaN, or an infinite entry of a batched ``b`` (the message
+        names the instance) is a ``ValueError`` before the library is touched."""
+        b, batched = check_rhs("b", b, self.batch, self.m, finite=True)
+        _lib.check(self._l.slp_batch_dga_set_rhs(self._h, _lib.ptr(b), int(batched)))
+
     def set_stop(self, tol, targets=None, check_every=1):
         """Arms the per-instance stopping test (``slp_batch_dga_set_stop``): at the end of every iteration ``t`` with
         ``t % check_every == 0`` -- counted from 1 over the life of the state, the same number for every instance that moves -- an
@@ -395,8 +406,9 @@ def dual_gradient_ascent_batch(lp, costs, nb_max_iter=1000, callback_func=None, 
     with ``costs[k]`` (and its bounds and start).  An instance whose start is dual infeasible (energy ``-inf``) stands still at
     its start, which is what its single solve returns; the others go on.  ``callback_func(niter, X, 0, 0, elapsed, 0, 0)`` is
     called for ``niter % 100 == 0``; ``max_time`` is tested there and stops the whole batch.  A finite ``b_lower``, a 2-D
-    right-hand side, a wrong shape, B < 1 or an LP without rows raises ``ValueError`` before the library is loaded; a status error
-    raises the single solver's exception, naming the instances."""
+    right-hand side (right-hand sides per instance are what ``dual_gradient_ascent_batch_rhs`` takes), a wrong shape, B < 1 or an
+    LP without rows raises ``ValueError`` before the library is loaded; a status error raises the single solver's exception,
+    naming the instances."""
     return _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path)[:3]
 
 
@@ -429,9 +441,69 @@ def dual_gradient_ascent_batch_until(lp, costs, tol=None, targets=None, check_ev
     return _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path, stop=stop)
 
 
-def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path, stop=None):
+def _check_batch_rhs(lp, batch, b_equalities, b_upper):
+    """The right-hand sides of ``dual_gradient_ascent_batch_rhs`` over the rows of ``[A_eq; A_ineq]``, checked without the library:
+    shape ``(m,)`` when both kinds are shared, else ``(batch, m)``.  Each kind defaults to the LP's own."""
+    parts, batched = [], False
+    for name, given, own, a in (("b_equalities", b_equalities, lp.b_equalities, lp.a_equalities), ("b_upper", b_upper, lp.b_upper, lp.a_inequalities)):
+        rows = 0 if a is None else a.shape[0]
+        if rows:
+            v, v_b = check_rhs(name, own if given is None else given, batch, rows, finite=True)
+            parts.append(v)
+            batched = batched or v_b
+    if not batched:
+        return np.concatenate(parts) if parts else np.zeros(0)
+    return np.ascontiguousarray(np.concatenate([np.broadcast_to(v, (batch, v.shape[-1])) for v in parts], axis=1))
+
+
+def dual_gradient_ascent_batch_rhs(lp, costs, b_equalities=None, b_upper=None, tol=None, targets=None, check_every=10, nb_max_iter=1000,
+                                   callback_func=None, y_eq=None, y_ineq=None, max_time=None, lower_bounds=None, upper_bounds=None, path=None):
+    """``dual_gradient_ascent_batch`` / ``dual_gradient_ascent_batch_until`` with right-hand sides per instance (extension): a sweep
+    over capacities, budgets or demands, or branch-and-bound nodes that tighten a row.  ``b_equalities`` has shape ``(m_eq,)`` or
+    ``(B, m_eq)``, ``b_upper`` ``(m_ineq,)`` or ``(B, m_ineq)``; each defaults to the LP's own 1-D one.  Returns
+    ``(X, Y_eq, Y_ineq, info)``.
+
+    Instance k is bit for bit ``dual_gradient_ascent`` on a copy of the LP with ``costs[k]`` and row k of the right-hand sides (and
+    its bounds and start): x, y and the tie draws taken.  With ``tol`` and ``targets`` both None the batch runs the fixed horizon
+    ``nb_max_iter``; ``info`` -- the dict of ``dual_gradient_ascent_batch_until`` -- then has ``lower_bound`` (the dual energy of the
+    returned multipliers against the instance's own right-hand sides, a certified lower bound on its LP value) and ``iterations``
+    filled, and nothing stopped.  Otherwise the stopping test, its arguments and ``info`` are those of
+    ``dual_gradient_ascent_batch_until``, the bound of instance k being evaluated with its own right-hand sides.
+
+    A finite ``b_lower`` on the LP, a wrong shape, a NaN, or an infinite entry of a batched right-hand side (the message names the
+    instance) raises ``ValueError`` before the library is loaded, as do the errors of ``tol``, ``targets`` and ``check_every``."""
+    stop, rhs = _check_dga_batch_rhs_call(lp, costs, b_equalities, b_upper, tol, targets, check_every)
+    return _dga_batch_rhs_run(lp, costs, rhs, stop, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path)
+
+
+def _check_dga_batch_rhs_call(lp, costs, b_equalities, b_upper, tol, targets, check_every):
+    """What ``dual_gradient_ascent_batch_rhs`` checks of its own, without the library: ``(stop, rhs)``, ``stop`` the checked
+    ``(tol, targets, check_every)`` or None for the fixed horizon, ``rhs`` as ``_check_batch_rhs`` returns it."""
+    batch = check_costs(costs, np.size(lp.costsvector))[1]
+    stop = None if tol is None and targets is None else _check_batch_stop(tol, targets, check_every, batch)
+    require_one_sided(getattr(lp, "b_lower", None))
+    return stop, _check_batch_rhs(lp, batch, b_equalities, b_upper)
+
+
+def _dga_batch_rhs_run(lp, costs, rhs, stop, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path):
+    """``dual_gradient_ascent_batch_rhs`` behind its checks (``_check_dga_batch_rhs_call`` gives ``stop`` and ``rhs``)."""
+    batch = np.shape(costs)[0]
+    out = _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path, stop=stop, rhs=rhs)
+    if stop is not None:
+        return out
+    x, ye, yi, report, iterations = out
+    info = _many.new_stop_info(batch, np.arange(batch))
+    info["reason"] = np.zeros(batch, dtype=np.int32)
+    info["iterations"][:] = iterations
+    info["lower_bound"] = report[:, 0].copy()
+    return x, ye, yi, info
+
+
+def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time, lower_bounds, upper_bounds, path, stop=None, rhs=None):
     """``dual_gradient_ascent_batch`` plus, as a fourth value, the final ``DeviceDGABatch.report()``; with ``stop`` (the checked
-    ``(tol, targets, check_every)`` of ``dual_gradient_ascent_batch_until``) what that function returns."""
+    ``(tol, targets, check_every)`` of ``dual_gradient_ascent_batch_until``) what that function returns.  ``rhs``: the checked
+    right-hand sides of ``dual_gradient_ascent_batch_rhs`` in place of the LP's, shape ``(m,)`` or ``(B, m)``; without a stopping
+    test the iterations completed per instance are then a fifth value."""
     require_one_sided(getattr(lp, "b_lower", None))
     from .device import DeviceMatrix
     from .tools import CsrArrays
@@ -444,9 +516,9 @@ def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time
     m_in = 0 if a_ineq is None else a_ineq.shape[0]
     if m_eq + m_in == 0:
         raise ValueError("dual_gradient_ascent_batch: the LP has no constraint rows")
-    for name, rhs, rows in (("b_equalities", lp.b_equalities, m_eq), ("b_upper", lp.b_upper, m_in)):
-        if rows and np.shape(rhs) != (rows,):
-            raise ValueError(f"{name} has shape {np.shape(rhs)}: expected ({rows},); per-instance right-hand sides are not built")
+    for name, own, rows in (("b_equalities", lp.b_equalities, m_eq), ("b_upper", lp.b_upper, m_in)):
+        if rhs is None and rows and np.shape(own) != (rows,):
+            raise ValueError(f"{name} has shape {np.shape(own)}: expected ({rows},); per-instance right-hand sides are not built")
     lb, _ = shared_or_batched("lower_bounds", lp.lower_bounds if lower_bounds is None else lower_bounds, batch, n)
     ub, _ = shared_or_batched("upper_bounds", lp.upper_bounds if upper_bounds is None else upper_bounds, batch, n)
     rs = np.random.RandomState(0)   # the reference draws the starts it is not given; the tie draws continue that stream
@@ -458,7 +530,10 @@ def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time
         y0 = np.concatenate((np.broadcast_to(ye, (batch, m_eq)), np.broadcast_to(yi, (batch, m_in))), axis=1)
     else:
         y0 = np.concatenate((ye, yi))
-    b = np.concatenate((_lib.f64(lp.b_equalities) if m_eq else np.zeros(0), _lib.f64(lp.b_upper) if m_in else np.zeros(0)))
+    if rhs is None:
+        b = np.concatenate((_lib.f64(lp.b_equalities) if m_eq else np.zeros(0), _lib.f64(lp.b_upper) if m_in else np.zeros(0)))
+    else:
+        b = _lib.f64(rhs[0] if rhs.ndim == 2 else rhs)   # the state is created with one vector; the rows follow through set_rhs
     mat = DeviceMatrix.from_blocks(a_eq if m_eq else None, a_ineq if m_in else None, n)
     state = None
 
@@ -468,10 +543,12 @@ def _dga_batch_run(lp, costs, nb_max_iter, callback_func, y_eq, y_ineq, max_time
 
     try:
         state = DeviceDGABatch(mat, b, costs, lb, ub, y0, m_eq=m_eq, draws=rs.random_sample, path=path)
+        if rhs is not None and rhs.ndim == 2:
+            state.set_rhs(rhs)
         frozen = state.frozen()
         if stop is None:
             _dga_drive(state, nb_max_iter, callback_func, max_time, start, all_frozen=frozen.all())
-            return result()
+            return result() if rhs is None else result() + (state.stop_state()[0],)
         info = _many.new_stop_info(batch, np.arange(batch))
         info["reason"] = np.zeros(batch, dtype=np.int32)
         info["lower_bound"] = np.full(batch, np.nan)

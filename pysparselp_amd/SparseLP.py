@@ -23,7 +23,7 @@ import numpy as np
 
 import scipy.sparse
 
-from .ADMM import lp_admm, lp_admm_batch, lp_admm_batch_until
+from .ADMM import _admm_batch_rhs_run, _check_admm_batch_rhs_call, lp_admm, lp_admm_batch, lp_admm_batch_until
 from .ChambollePockPPD import (chambolle_pock_ppd, chambolle_pock_ppd_batch, chambolle_pock_ppd_batch_certified, chambolle_pock_ppd_many,
                                chambolle_pock_ppd_many_certified, chambolle_pock_ppd_many_until)
 from ._many import check_stop
@@ -58,10 +58,11 @@ def _mean_each(distances):
     return np.array([np.mean(d) for d in distances])
 
 
-def _batch_recorder(lp, batch, ground_truth, ground_truth_indices, mean=_mean_together, expand=None):
+def _batch_recorder(lp, batch, ground_truth, ground_truth_indices, mean=_mean_together, expand=None, views=None):
     """The callback of the three ``(B, ...)`` forms: fills ``lp``'s curves as ``solve`` does, the per-instance ones with arrays of
     length ``batch`` (a number the solver reports once for all instances is repeated).  ``expand`` maps the solver's iterates to
-    the LP's variables."""
+    the LP's variables.  ``views``: per instance the LP against which its ``max_violated_constraint`` is taken (``_rhs_views``)
+    instead of ``lp`` itself."""
     def record(niter, solution, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
         if expand is not None:
             solution = expand(solution)
@@ -74,11 +75,26 @@ def _batch_recorder(lp, batch, ground_truth, ground_truth_indices, mean=_mean_to
         lp.dopttime_curve.append(duration)
         lp.dobj_curve.append(np.full(batch, energy2, dtype=np.float64))
         lp.pobj_curve.append(np.full(batch, energy1, dtype=np.float64))
-        lp.max_violated_constraint.append(np.array([lp.max_constraint_violation(solution[k]) for k in range(batch)]))
+        lp.max_violated_constraint.append(np.array([(lp if views is None else views[k]).max_constraint_violation(solution[k])
+                                                    for k in range(batch)]))
         lp.max_violated_equality.append(np.full(batch, max_violated_equality, dtype=np.float64))
         lp.max_violated_inequality.append(np.full(batch, max_violated_inequality, dtype=np.float64))
 
     return record
+
+
+def _rhs_views(lp, batch, **sides):
+    """Per instance a shallow copy of ``lp`` whose right-hand sides are row k of the given ones (``name=array`` of shape ``(rows,)``
+    or ``(batch, rows)``; None keeps the LP's): what instance k's constraint violations are measured against."""
+    views = []
+    for k in range(batch):
+        view = copy.copy(lp)
+        for name, v in sides.items():
+            if v is not None:
+                v = np.asarray(v, dtype=np.float64)
+                setattr(view, name, v[k] if v.ndim == 2 else v)
+        views.append(view)
+    return views
 
 
 def _list_recorder(lps, expand=None, skip=()):
@@ -738,6 +754,92 @@ class SparseLP:
         check_stop(tol_step, check_every, "tol_step")
         return self._solve_admm_batch(costs, (tol_residual, tol_step, check_every), get_timing, nb_iter, max_time, nb_iter_plot,
                                       ground_truth, ground_truth_indices)
+
+    def solve_admm_batch_rhs(
+        self,
+        costs,
+        b_equalities=None,
+        b_lower=None,
+        b_upper=None,
+        tol_residual=None,
+        tol_step=None,
+        check_every=10,
+        get_timing=True,
+        nb_iter=10000,
+        max_time=None,
+        nb_iter_plot=10,
+        ground_truth=None,
+        ground_truth_indices=None,
+    ):
+        """``solve_admm_batch`` / ``solve_admm_batch_until`` with right-hand sides per instance (``ADMM.lp_admm_batch_rhs``):
+        ``b_equalities`` of shape ``(m_eq,)`` or ``(B, m_eq)``, ``b_lower`` and ``b_upper`` ``(m_ineq,)`` or ``(B, m_ineq)``, each
+        defaulting to the LP's own.  Returns what ``solve_admm_batch_until`` returns, ``(X, elapsed, info)`` or ``(X, info)``;
+        ``info`` is None without ``tol_residual`` / ``tol_step`` (optional, both or neither).
+
+        ``X[k]`` and the k-th component of every curve are what ``solve(method="admm", order=ORDER_SEQUENTIAL, setup="host")``
+        gives on a copy of the LP whose ``costsvector`` is ``costs[k]`` and whose right-hand sides are row k; ``max_violated_*`` of
+        instance k is taken against instance k's right-hand sides.  The curves are filled as by ``solve_admm_batch``."""
+        costs, batch = check_costs(costs, self.nb_variables)
+        a_ineq = self.a_inequalities if (self.a_inequalities is not None and self.a_inequalities.shape[0] > 0) else None
+        a_eq = self.a_equalities if self.a_equalities.shape[0] > 0 else None
+        b_eq = None if a_eq is None else (self.b_equalities if b_equalities is None else b_equalities)
+        b_lower = self.b_lower if b_lower is None else b_lower
+        b_upper = self.b_upper if b_upper is None else b_upper
+        # the checks of lp_admm_batch_rhs, made once and before the curves are touched
+        stop, rhs = _check_admm_batch_rhs_call(costs, a_eq, b_eq, a_ineq, b_lower, b_upper, tol_residual, tol_step, check_every)
+        start = time.perf_counter()
+        _reset_curves(self)
+        views = _rhs_views(self, batch, b_equalities=rhs[0], b_lower=rhs[1], b_upper=rhs[2])
+        record = _batch_recorder(self, batch, ground_truth, ground_truth_indices, views=views)
+        x, info = _admm_batch_rhs_run(costs, a_eq, b_eq, a_ineq, rhs, self.lower_bounds, self.upper_bounds, stop, None, 2, 3, nb_iter, record,
+                                      max_time, True, nb_iter_plot)
+        elapsed = time.perf_counter() - start
+        return (x, elapsed, info) if get_timing else (x, info)
+
+    def solve_dga_batch_rhs(
+        self,
+        costs,
+        b_equalities=None,
+        b_upper=None,
+        tol=None,
+        targets=None,
+        check_every=10,
+        get_timing=True,
+        nb_iter=10000,
+        max_time=None,
+        nb_iter_plot=10,
+        ground_truth=None,
+        ground_truth_indices=None,
+        lower_bounds=None,
+        upper_bounds=None,
+    ):
+        """``solve_dga_batch`` / ``solve_dga_batch_until`` with right-hand sides per instance
+        (``DualGradientAscent.dual_gradient_ascent_batch_rhs``): ``b_equalities`` of shape ``(m_eq,)`` or ``(B, m_eq)``, ``b_upper``
+        ``(m_ineq,)`` or ``(B, m_ineq)``, each defaulting to the LP's own.  Returns ``(X, elapsed)`` or ``X`` as
+        ``solve_dga_batch_until``; ``tol``, ``targets`` and ``check_every`` are its stopping arguments, optional here: with ``tol``
+        and ``targets`` both None the batch runs ``nb_iter`` iterations.
+
+        ``X[k]`` and the k-th component of every curve are what ``solve(method="dual_gradient_ascent")`` gives on a copy of the LP
+        whose ``costsvector`` is ``costs[k]`` and whose right-hand sides are row k (bit for bit); ``max_violated_constraint`` of
+        instance k is taken against instance k's right-hand sides.  Sets ``self.dual_multipliers``, ``self.dual_lower_bounds``
+        (each a certified lower bound on its instance's LP value) and ``self.stop_info``, the ``info`` of
+        ``dual_gradient_ascent_batch_rhs``."""
+        from .DualGradientAscent import _check_dga_batch_rhs_call, _dga_batch_rhs_run
+
+        costs, batch = check_costs(costs, self.nb_variables)
+        # the checks of dual_gradient_ascent_batch_rhs, made once and before the curves are touched
+        stop, rhs = _check_dga_batch_rhs_call(self, costs, b_equalities, b_upper, tol, targets, check_every)
+        start = time.perf_counter()
+        _reset_curves(self)
+        views = _rhs_views(self, batch, b_equalities=b_equalities, b_upper=b_upper)
+        record = _batch_recorder(self, batch, ground_truth, ground_truth_indices, mean=_mean_each, views=views)
+        x, y_eq, y_ineq, info = _dga_batch_rhs_run(self, costs, rhs, stop, nb_iter, record, None, None, max_time, lower_bounds, upper_bounds,
+                                                   None)
+        self.dual_multipliers = (y_eq, y_ineq)
+        self.dual_lower_bounds = info["lower_bound"].copy()
+        self.stop_info = info
+        elapsed = time.perf_counter() - start
+        return (x, elapsed) if get_timing else x
 
     def solve_dga_batch(
         self,

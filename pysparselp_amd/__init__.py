@@ -12,7 +12,9 @@ do the same for ADMM with the projected Gauss-Seidel x-step (``SparseLP.solve_ad
 instance on its own, by a test on the residual and the step inside the kernels), ``SparseLP.solve_dga_batch`` / ``dual_gradient_ascent_batch`` for dual
 gradient ascent (certified lower bounds of B LPs over one matrix; ``SparseLP.solve_dga_batch_until`` /
 ``dual_gradient_ascent_batch_until`` stop every instance on its own, on the step of its multipliers or once its bound has reached a
-cut-off, tested on the device); ``solve_many`` / ``chambolle_pock_ppd_many`` solve a list of
+cut-off, tested on the device); ``SparseLP.solve_dga_batch_rhs`` / ``dual_gradient_ascent_batch_rhs`` and
+``SparseLP.solve_admm_batch_rhs`` / ``lp_admm_batch_rhs`` give every instance right-hand sides of its own as well
+(``DeviceDGABatch.set_rhs``, ``ADMMBatchState.set_rhs``), with or without those stopping tests; ``solve_many`` / ``chambolle_pock_ppd_many`` solve a list of
 LPs whose matrices differ, one workgroup per LP (Chambolle-Pock; ``solve_many_until`` / ``chambolle_pock_ppd_many_until`` stop every
 LP on its own, by a test on the step inside the kernel; ``solve_many_certified`` / ``chambolle_pock_ppd_many_certified`` by a
 certified duality gap and the primal violation, both handed back), ``solve_dga_many`` / ``dual_gradient_ascent_many`` do the same
@@ -27,11 +29,13 @@ library and a HIP device every solver call raises ``SlpError``.
 """
 from ._lib import ORDER_AUTO, ORDER_SEQUENTIAL, ORDER_TREE, SlpError  # noqa: F401
 from .ADMM import ADMMBatchState, ADMMManyState, lp_admm_batch, lp_admm_batch_until, lp_admm_many, lp_admm_many_until  # noqa: F401
+from .ADMM import lp_admm_batch_rhs  # noqa: F401
 from .ChambollePockPPD import (CPBatchState, CPManyState, chambolle_pock_ppd_batch, chambolle_pock_ppd_batch_certified,  # noqa: F401
                                chambolle_pock_ppd_many, chambolle_pock_ppd_many_certified, chambolle_pock_ppd_many_until)
 from .DualGradientAscent import (DeviceDGABatch, DeviceDGAMany, dual_gradient_ascent_batch, dual_gradient_ascent_batch_until,  # noqa: F401
                                  dual_gradient_ascent_many, dual_gradient_ascent_many_compact, dual_gradient_ascent_many_cutoff,
                                  dual_gradient_ascent_many_until)
+from .DualGradientAscent import dual_gradient_ascent_batch_rhs  # noqa: F401
 from .SparseLP import solve_admm_many, solve_admm_many_until, solve_dga_many, solve_dga_many_until, solve_many, solve_many_until  # noqa: F401
 from .SparseLP import solve_dga_many_compact, solve_dga_many_cutoff, solve_many_certified  # noqa: F401
 
@@ -41,4 +45,5 @@ __all__ = ["ORDER_AUTO", "ORDER_SEQUENTIAL", "ORDER_TREE", "SlpError", "CPBatchS
            "solve_admm_many", "chambolle_pock_ppd_many_until", "solve_many_until", "lp_admm_many_until", "solve_admm_many_until",
            "dual_gradient_ascent_many_until", "solve_dga_many_until", "chambolle_pock_ppd_many_certified", "solve_many_certified",
            "chambolle_pock_ppd_batch_certified", "lp_admm_batch_until", "dual_gradient_ascent_batch_until",
-           "dual_gradient_ascent_many_cutoff", "solve_dga_many_cutoff", "dual_gradient_ascent_many_compact", "solve_dga_many_compact"]
+           "dual_gradient_ascent_many_cutoff", "solve_dga_many_cutoff", "dual_gradient_ascent_many_compact", "solve_dga_many_compact",
+           "dual_gradient_ascent_batch_rhs", "lp_admm_batch_rhs"]

@@ -47,6 +47,30 @@ def check_targets(targets, batch):
     return _lib.f64(np.broadcast_to(t, (batch,)).copy())
 
 
+def check_rhs(name, v, batch, rows, finite=False):
+    """A right-hand side of ``set_rhs``: ``shared_or_batched(name, v, batch, rows)`` without a NaN and, with ``finite``, without an
+    infinite entry in a batched one (the ``ValueError`` names the first such instance)."""
+    v, batched = shared_or_batched(name, v, batch, rows)
+    if np.any(np.isnan(v)):
+        raise ValueError(f"{name} has a NaN")
+    if finite and batched and not np.all(np.isfinite(v)):
+        k = int(np.nonzero(~np.all(np.isfinite(v), axis=1))[0][0])
+        raise ValueError(f"instance {k} has an entry of {name} that is not finite")
+    return v, batched
+
+
+def check_rhs_order(b_lower, b_upper, batch):
+    """``b_lower <= b_upper`` row by row, each of shape ``(rows,)`` or ``(batch, rows)`` (either may be None): the ``ValueError``
+    names the first instance with a crossed row."""
+    if b_lower is None or b_upper is None:
+        return
+    rows = np.shape(b_lower)[-1]
+    crossed = np.broadcast_to(b_lower, (batch, rows)) > np.broadcast_to(b_upper, (batch, rows))
+    if np.any(crossed):
+        k = int(np.nonzero(np.any(crossed, axis=1))[0][0])
+        raise ValueError(f"instance {k} has b_lower > b_upper on row {int(np.nonzero(crossed[k])[0][0])}")
+
+
 def require_one_sided(b_lower, prefix=""):
     """Dual gradient ascent takes ``a x <= b_upper`` only (the reference's assert, DualGradientAscent.py:82)."""
     if b_lower is not None and np.size(b_lower) > 0 and np.max(b_lower) != -np.inf:

@@ -1,5 +1,5 @@
 """ctypes binding of libslp_hip.so (include/slp_hip.h, include/slp_hip_ext.h, include/slp_hip_ext_admm_batch.h,
-include/slp_hip_ext_dga_batch.h, include/slp_hip_ext_dga_many.h and include/slp_hip_ext_tall.h).
+include/slp_hip_ext_dga_batch.h, include/slp_hip_ext_dga_many.h, include/slp_hip_ext_batch_rhs.h and include/slp_hip_ext_tall.h).
 
 The library is the only execution path: if it is missing, cannot be loaded, or
 finds no HIP device, every solver entry point raises -- there is no CPU
@@ -302,6 +302,14 @@ _EXT_MANY_LIVE_SIGNATURES = {
 
 EXT_MANY_LIVE_SYMBOLS = tuple(_EXT_MANY_LIVE_SIGNATURES)
 
+# name -> (restype, argtypes); mirrors include/slp_hip_ext_batch_rhs.h (which slp_hip_ext.h includes) one to one
+_EXT_BATCH_RHS_SIGNATURES = {
+    "slp_batch_dga_set_rhs": (c_int, [c_vp, c_vp, c_int]),
+    "slp_admm_batch_set_rhs": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int]),
+}
+
+EXT_BATCH_RHS_SYMBOLS = tuple(_EXT_BATCH_RHS_SIGNATURES)
+
 # name -> (restype, argtypes); mirrors include/slp_hip_ext_tall.h (which slp_hip_ext.h includes) one to one
 _EXT_TALL_SIGNATURES = {
     "slp_matrix_tall_records": (c_i64, [c_vp, c_int]),
@@ -334,7 +342,7 @@ def load():
     for name, (res, args) in (list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_EXT_ADMM_BATCH_SIGNATURES.items())
                               + list(_EXT_DGA_BATCH_SIGNATURES.items()) + list(_EXT_DGA_MANY_SIGNATURES.items())
                               + list(_EXT_DGA_MANY_LIVE_SIGNATURES.items()) + list(_EXT_MANY_LIVE_SIGNATURES.items())
-                              + list(_EXT_TALL_SIGNATURES.items())):
+                              + list(_EXT_BATCH_RHS_SIGNATURES.items()) + list(_EXT_TALL_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

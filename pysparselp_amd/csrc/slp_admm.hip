@@ -1622,6 +1622,10 @@ struct slp_admm {
     DevBuf<double> lin;       // lambda_ineq (stays 0 for xstep 0)
     IterGraph graph;
     DevBuf<double> b, c, lb, ub, x, xp0, lam, q, y, rowparts, colparts, out;
+    // the row scalings of admm_create_lp's set-up chain, kept for a levels_only state (slp_admm_shared.h): the equality block's,
+    // the inequality block's, the stacked system's (empty without use_preconditioning)
+    i64 m_eq = 0;
+    DevBuf<double> scale_eq, scale_ineq, scale_rows;
 };
 
 namespace slp {
@@ -1832,14 +1836,15 @@ slp_admm *admm_create_lp(int64_t n, int64_t m_eq, const int64_t *eq_indptr, cons
             }
             SLP_HIP(hipStreamSynchronize(st));  // the host buffers may go away
             // ADMM.py:76-83: scale the rows of each block (the slack bounds are scaled with their rows; -inf / inf stay)
-            if (ae) ae2 = matrix_precondition_rows(ae, s->b.p, nullptr);
-            ai2 = matrix_precondition_rows(ai, s->lb.p + n, s->ub.p + n);
+            s->m_eq = m_eq;
+            if (ae) ae2 = matrix_precondition_rows(ae, s->b.p, nullptr, levels_only ? &s->scale_eq : nullptr);
+            ai2 = matrix_precondition_rows(ai, s->lb.p + n, s->ub.p + n, levels_only ? &s->scale_ineq : nullptr);
             // :84-86: [A_eq 0; A_ineq -I]; x0 = [x0; A_ineq x0] with the scaled block (csr_matvec over its stored order)
             a2 = matrix_standard_form(ae2, ai2);
             if (m_ineq) launch_spmv(ai2->a, s->x.p, s->x.p + n, SLP_ORDER_SEQUENTIAL);
             // :90-91: scale the rows of the stacked system
             if (use_preconditioning) {
-                s->a = matrix_precondition_rows(a2, s->b.p, nullptr);
+                s->a = matrix_precondition_rows(a2, s->b.p, nullptr, levels_only ? &s->scale_rows : nullptr);
             } else {
                 s->a = a2;
                 a2 = nullptr;
@@ -1866,6 +1871,8 @@ void admm_shared(slp_admm *s, AdmmShared *v) {
     v->b = s->b.p; v->lb = s->lb.p; v->ub = s->ub.p; v->x0 = s->x.p;
     v->atb = s->y.p;  // admm_finish_create leaves A^T b there; the first right-hand side overwrites it
     v->c = s->c.p; v->q = s->q.p; v->xp0 = s->xp0.p;
+    v->m_eq = s->m_eq;
+    v->scale_eq = s->scale_eq.p; v->scale_ineq = s->scale_ineq.p; v->scale_rows = s->scale_rows.p;
     v->nlevels = g.nlevels; v->max_width = g.max_width; v->nnz_m = g.nnz;
     v->lptr = g.lptr;
     v->gs_ptr = g.ptr.p; v->gs_idx = g.idx.p; v->gs_val = g.val.p; v->gs_invd = g.invd.p; v->gs_rows = g.rows.p;

@@ -51,6 +51,11 @@
 //           to one workgroup index, the launches of a stream follow each other, so no atomic is needed; the step slots are
 //           zeroed on the stream before the sweep.  k_admmb_decide, one workgroup per instance behind the multiplier kernel,
 //           folds the slots, writes the record and decides.
+// Right-hand sides per instance (slp_admm_batch_set_rhs, slp_hip_ext_batch_rhs.h; before the first iteration).  The row scalings
+// of the set-up chain depend on the matrices only, so the instances keep sharing the chain, M and its plan; the call scales the
+// caller's rows with the kept scalings (k_admmb_scale_rhs) and rebuilds per instance b (tiled like lambda: AdmmbArgs::b_b, the
+// template parameter BB of the kernels that read b in every iteration), A^T b_k with the set-up's product, q_k (k_admmb_q) and
+// the slack part of lb / ub (k_admmb_scatter_tail; the bound becomes tiled over N if it was shared).
 // `running` counts the real instances that go on (an integer atomic decrement where one stops): an armed state reads it once
 // at the start of iterate / multiplier_step and enqueues nothing when it is 0.  Nothing else is read back.
 #include <algorithm>
@@ -63,6 +68,7 @@
 #include "slp_admm_iter.h"
 #include "slp_admm_shared.h"
 #include "../../include/slp_hip_ext_admm_batch.h"
+#include "../../include/slp_hip_ext_batch_rhs.h"
 
 namespace slp {
 
@@ -75,10 +81,10 @@ struct AdmmbArgs {
     const i64 *tptr; const i32 *tidx; const double *tval;   // rows of A^T
     const i64 *aptr; const i32 *aidx; const double *aval;   // rows of A
     const i64 *gptr; const i32 *gidx; const double *gval; const double *ginvd; const i32 *grows; const i64 *lptr;  // M, level order
-    const double *b;                                        // [m]
+    const double *b;                                        // [m], or tiled like lambda (b_b)
     const double *q, *c, *lb, *ub, *xp0;
     double *x, *y, *lam;
-    int lb_b, ub_b, xp0_b;                                  // 1: tiled per instance, 0: one shared vector
+    int lb_b, ub_b, xp0_b, b_b;                             // 1: tiled per instance, 0: one shared vector
     double gamma_eq, gamma_ineq;
 };
 
@@ -119,19 +125,21 @@ __device__ __forceinline__ double admmb_sweep_one(const AdmmbArgs &a, i64 tile, 
     return fabs(v - xi);
 }
 
-template <int BT>
+// BB: b is tiled like lambda (after slp_admm_batch_set_rhs with a batched b_eq); a template parameter, so that a state with a
+// shared b launches the code it launched before the switch existed
+template <int BT, bool BB>
 __device__ __forceinline__ void admmb_mult_one(const AdmmbArgs &a, i64 tile, int k, i64 i) {
     const i64 o = (tile * a.m + i) * BT + k;
-    a.lam[o] = admm_mult_one<BT>(a.aptr[i], a.aptr[i + 1], a.aidx, a.aval, a.x + tile * a.N * BT + k, a.lam + o, a.b + i, a.gamma_eq,
+    a.lam[o] = admm_mult_one<BT>(a.aptr[i], a.aptr[i + 1], a.aidx, a.aval, a.x + tile * a.N * BT + k, a.lam + o, a.b + (BB ? o : i), a.gamma_eq,
                                  AdmmLoadWorkgroup());  // :261-263
 }
 
 // admmb_mult_one of a check iteration: the same lambda_i; returns |(A x)_i - b_i| as the update forms it
-template <int BT>
+template <int BT, bool BB>
 __device__ __forceinline__ double admmb_mult_res_one(const AdmmbArgs &a, i64 tile, int k, i64 i) {
     const i64 o = (tile * a.m + i) * BT + k;
     double res;
-    a.lam[o] = admm_mult_res_one<BT>(a.aptr[i], a.aptr[i + 1], a.aidx, a.aval, a.x + tile * a.N * BT + k, a.lam + o, a.b + i, a.gamma_eq,
+    a.lam[o] = admm_mult_res_one<BT>(a.aptr[i], a.aptr[i + 1], a.aidx, a.aval, a.x + tile * a.N * BT + k, a.lam + o, a.b + (BB ? o : i), a.gamma_eq,
                                      AdmmLoadWorkgroup(), &res);
     return fabs(res);
 }
@@ -185,8 +193,8 @@ __device__ __forceinline__ bool admmb_post_go(int *go, bool goes) {
 }
 
 // ---- tile form: `iters` iterations of one tile in one workgroup.  stages: bit 0 right-hand side + sweep, bit 1 multiplier.
-// STOP: the stopping test of the header comment; `sp` is not looked at without it.
-template <int BT, bool STOP>
+// STOP: the stopping test of the header comment; `sp` is not looked at without it.  BB: admmb_mult_one's.
+template <int BT, bool STOP, bool BB>
 __global__ __launch_bounds__(kAdmmbBlock) void k_admmb_tile(AdmmbArgs a, int iters, int first, int stages, AdmmbStop sp) {
     constexpr int kWaves = kAdmmbBlock / kWave;
     __shared__ double red[STOP ? 2 * kWaves * BT : 1];  // step, residual: a slot per (wave, instance).  Unused without STOP: dropped
@@ -228,11 +236,11 @@ __global__ __launch_bounds__(kAdmmbBlock) void k_admmb_tile(AdmmbArgs a, int ite
             if (check) {
                 double dr = 0.0;  // 0.0 without rows
                 if (active)
-                    for (i64 i = g; i < a.m; i += ng) dr = nan_max(dr, admmb_mult_res_one<BT>(a, tile, k, i));
+                    for (i64 i = g; i < a.m; i += ng) dr = nan_max(dr, admmb_mult_res_one<BT, BB>(a, tile, k, i));
                 admmb_post<BT>(red + kWaves * BT, dr);
             } else {
                 if (active)
-                    for (i64 i = g; i < a.m; i += ng) admmb_mult_one<BT>(a, tile, k, i);
+                    for (i64 i = g; i < a.m; i += ng) admmb_mult_one<BT, BB>(a, tile, k, i);
             }
             __syncthreads();
         }
@@ -296,21 +304,21 @@ __global__ __launch_bounds__(kBlock) void k_admmb_level(AdmmbArgs a, i64 beg, i6
     }
 }
 
-// part: NULL outside a check iteration; else the residual slots [gridDim.x x Bp]
-template <int BT, bool STOP>
+// part: NULL outside a check iteration; else the residual slots [gridDim.x x Bp].  BB: admmb_mult_one's
+template <int BT, bool STOP, bool BB>
 __global__ __launch_bounds__(kBlock) void k_admmb_mult(AdmmbArgs a, const AdmmbCtl *__restrict__ ctl, i64 Bp, double *__restrict__ part) {
     const int k = threadIdx.x & (BT - 1);
     const i64 tile = blockIdx.y;
     const i64 ng = (i64)gridDim.x * kBlock / BT;
     if (!STOP || !part) {
         if (STOP ? ctl[tile * BT + k].stopped != 0 : tile * BT + k >= a.B) return;
-        for (i64 i = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; i < a.m; i += ng) admmb_mult_one<BT>(a, tile, k, i);
+        for (i64 i = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; i < a.m; i += ng) admmb_mult_one<BT, BB>(a, tile, k, i);
         return;
     }
     const bool live = !ctl[tile * BT + k].stopped;
     double dr = 0.0;
     if (live)
-        for (i64 i = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; i < a.m; i += ng) dr = nan_max(dr, admmb_mult_res_one<BT>(a, tile, k, i));
+        for (i64 i = ((i64)blockIdx.x * kBlock + threadIdx.x) / BT; i < a.m; i += ng) dr = nan_max(dr, admmb_mult_res_one<BT, BB>(a, tile, k, i));
     double v;
     if (admmb_block_nanmax<BT>(dr, &v) && live) part[(i64)blockIdx.x * Bp + tile * BT + k] = v;
 }
@@ -354,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void k_admmb_report_rows(AdmmbArgs a, i64 B
     if (inst < a.B)
         for (i64 i = group; i < a.m; i += ng) {
             const double ax = admm_dot<BT>(a.aptr[i], a.aptr[i + 1], a.aidx, a.aval, a.x + tile * a.N * BT + k, AdmmLoadWorkgroup());
-            const double r = ax - a.b[i];
+            const double r = ax - a.b[a.b_b ? (tile * a.m + i) * BT + k : i];
             s0 += r * r;
             s1 += a.lam[(tile * a.m + i) * BT + k] * r;
             const double ar = fabs(r);
@@ -433,13 +441,39 @@ __global__ void k_admmb_gather(i64 len, i64 count, i64 B, int BT, const double *
 }
 
 // q = (-c) + gamma_eq A^T b (k_admm_q; c = +0 on the slack columns), tiled
+// (atb_batched: A^T b_k of instance k at atb + k * N, row-major, after slp_admm_batch_set_rhs)
 __global__ void k_admmb_q(i64 N, i64 n, i64 B, int BT, i64 Bp, const double *__restrict__ c, const double *__restrict__ atb,
-                          double gamma_eq, double *__restrict__ q) {
+                          int atb_batched, double gamma_eq, double *__restrict__ q) {
     const i64 total = N * Bp;
     for (i64 o = (i64)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (i64)gridDim.x * blockDim.x) {
         const i64 k = o % BT, rest = o / BT, j = rest % N, tile = rest / N;
         const double cj = j < n ? c[(tile * n + j) * BT + k] : 0.0;
-        q[o] = tile * BT + k < B ? (-cj) + gamma_eq * atb[j] : 0.0;
+        const i64 inst = tile * BT + k;
+        q[o] = inst < B ? (-cj) + gamma_eq * atb[atb_batched ? inst * N + j : j] : 0.0;
+    }
+}
+
+// slp_admm_batch_set_rhs: `count` = rows * (1 or B) right-hand sides of the caller, row-major, brought to the state's units by
+// the set-up chain's row scalings, one multiplication each in the chain's order (k_scale_vec: inf stays inf); row r of
+// instance k goes to dst[k * dst_stride + r]
+__global__ void k_admmb_scale_rhs(i64 rows, i64 count, const double *__restrict__ inv1, const double *__restrict__ inv2,
+                                  const double *__restrict__ src, i64 dst_stride, double *__restrict__ dst) {
+    for (i64 o = (i64)blockIdx.x * blockDim.x + threadIdx.x; o < count; o += (i64)gridDim.x * blockDim.x) {
+        const i64 inst = o / rows, r = o - inst * rows;
+        double v = inv1[r] * src[o];
+        if (inv2) v = inv2[r] * v;
+        dst[inst * dst_stride + r] = v;
+    }
+}
+
+// slp_admm_batch_set_rhs: the slack part (columns n .. n + rows) of a tiled bound over N from src [B x rows] row-major (or one
+// shared [rows] vector); the padding instances keep their zeros
+__global__ void k_admmb_scatter_tail(i64 N, i64 n, i64 rows, i64 B, int BT, const double *__restrict__ src, int batched,
+                                     double *__restrict__ dst) {
+    const i64 total = rows * B;
+    for (i64 o = (i64)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (i64)gridDim.x * blockDim.x) {
+        const i64 inst = o / rows, r = o - inst * rows;
+        dst[((inst / BT) * N + n + r) * BT + inst % BT] = src[batched ? o : r];
     }
 }
 
@@ -463,6 +497,10 @@ struct slp_admm_batch {
     DevBuf<i64> lptr;
     DevBuf<double> c, q, lb, ub, x, xp0, y, lam, rowparts, colparts, out;
     bool lb_b = false, ub_b = false, x0_b = false;
+    // slp_admm_batch_set_rhs: b tiled like lambda (b_b) or a shared vector of the state's own (b_own) in place of the set-up's;
+    // lb_own / ub_own: a shared [N] bound of the state's own whose slack part was replaced (only while !lb_b / !ub_b)
+    DevBuf<double> b;
+    bool b_b = false, b_own = false, lb_own = false, ub_own = false;
     i64 iters = 0;             // whole iterations over the state's life: bumped where a multiplier half is enqueued
     bool mid = false;          // between sweep_step and multiplier_step
     // the stopping test (slp_admm_batch_set_stop); its buffers exist from the first arming on, and from then on the state
@@ -521,13 +559,13 @@ static AdmmbArgs admmb_args(const slp_admm_batch *s) {
     a.aptr = A.ptr.p; a.aidx = A.idx.p; a.aval = A.val.p;
     a.gptr = s->sh.gs_ptr; a.gidx = s->sh.gs_idx; a.gval = s->sh.gs_val; a.ginvd = s->sh.gs_invd; a.grows = s->sh.gs_rows;
     a.lptr = s->lptr.p;
-    a.b = s->sh.b;
+    a.b = (s->b_b || s->b_own) ? s->b.p : s->sh.b;
     a.q = s->q.p; a.c = s->c.p;
-    a.lb = s->lb_b ? s->lb.p : s->sh.lb;
-    a.ub = s->ub_b ? s->ub.p : s->sh.ub;
+    a.lb = (s->lb_b || s->lb_own) ? s->lb.p : s->sh.lb;
+    a.ub = (s->ub_b || s->ub_own) ? s->ub.p : s->sh.ub;
     a.xp0 = s->xp0.p;
     a.x = s->x.p; a.y = s->y.p; a.lam = s->lam.p;
-    a.lb_b = s->lb_b; a.ub_b = s->ub_b; a.xp0_b = s->x0_b;
+    a.lb_b = s->lb_b; a.ub_b = s->ub_b; a.xp0_b = s->x0_b; a.b_b = s->b_b;
     a.gamma_eq = s->gamma_eq; a.gamma_ineq = s->gamma_ineq;
     return a;
 }
@@ -551,8 +589,13 @@ static void admmb_run_tile(slp_admm_batch *s, const AdmmbArgs &a, i64 iters, int
     while (iters > 0) {
         const i64 k = std::min(iters, s->kmax);
         const int first = ((stages & 1) && !s->xp_is_x) ? 1 : 0;
-        SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_tile<BT, STOP>), dim3((unsigned)s->ntiles), dim3(kAdmmbBlock), 0, ctx().stream, a,
-                                                 (int)k, first, stages, admmb_stop(s, test)));
+        if (s->b_b) {
+            SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_tile<BT, STOP, true>), dim3((unsigned)s->ntiles), dim3(kAdmmbBlock), 0, ctx().stream,
+                                                     a, (int)k, first, stages, admmb_stop(s, test)));
+        } else {
+            SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_tile<BT, STOP, false>), dim3((unsigned)s->ntiles), dim3(kAdmmbBlock), 0, ctx().stream,
+                                                     a, (int)k, first, stages, admmb_stop(s, test)));
+        }
         SLP_HIP(hipGetLastError());
         if (stages & 2) {
             s->xp_is_x = true;  // :259
@@ -591,8 +634,13 @@ static void admmb_run_levels(slp_admm_batch *s, const AdmmbArgs &a, i64 iters, i
             if (s->m > 0) {
                 const dim3 grid = admmb_grid(s, s->m);
                 nres = grid.x;
-                SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_mult<BT, STOP>), grid, dim3(kBlock), 0, st, a, ctl, s->Bp,
-                                                         check ? residuals : nullptr));
+                if (s->b_b) {
+                    SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_mult<BT, STOP, true>), grid, dim3(kBlock), 0, st, a, ctl, s->Bp,
+                                                             check ? residuals : nullptr));
+                } else {
+                    SLP_ADMMB_TILE(s->Bt, hipLaunchKernelGGL((k_admmb_mult<BT, STOP, false>), grid, dim3(kBlock), 0, st, a, ctl, s->Bp,
+                                                             check ? residuals : nullptr));
+                }
             }
         }
         if (check) {
@@ -736,7 +784,7 @@ slp_admm_batch *slp_admm_batch_create_lp(int64_t n, int64_t m_eq, const int64_t 
                 admmb_scatter(s, n, n, stage.p, c_batched, nullptr, s->c.p);
                 // A^T b of the set-up has not been overwritten: the base state never iterates
                 hipLaunchKernelGGL(k_admmb_q, dim3(grid_for(N * s->Bp, kBlock)), dim3(kBlock), 0, st, N, n, s->B, s->Bt, s->Bp, s->c.p, s->sh.atb,
-                                   gamma_eq, s->q.p);
+                                   0, gamma_eq, s->q.p);
                 SLP_HIP(hipGetLastError());
                 SLP_HIP(hipStreamSynchronize(st));  // the stage is reused
                 if (s->lb_b) {   // [lb_k; scaled b_lower]
@@ -836,6 +884,98 @@ int slp_admm_batch_bench(slp_admm_batch *s, int64_t k, double *ms) {
         float f = 0.f;
         SLP_HIP(hipEventElapsedTime(&f, c.ev0, c.ev1));
         *ms = (double)f / (double)k;
+    })
+}
+
+int slp_admm_batch_set_rhs(slp_admm_batch *s, const double *b_eq, int b_eq_batched, const double *b_lower, int b_lower_batched,
+                           const double *b_upper, int b_upper_batched) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_admm_batch_set_rhs: NULL handle");
+        SLP_REQUIRE(s->iters == 0 && !s->mid && !s->xp_is_x,
+                    "slp_admm_batch_set_rhs: the state has iterated; the right-hand sides are set before the first iteration or half iteration");
+        hipStream_t st = ctx().stream;
+        const i64 N = s->N, n = s->n, m = s->m, m_eq = s->sh.m_eq, m_ineq = N - n, B = s->B;
+        SLP_REQUIRE(m_eq + m_ineq == m, "slp_admm_batch_set_rhs: the state does not know its blocks");
+        if (m_eq == 0) b_eq = nullptr;       // no equality rows: nothing to replace
+        if (m_ineq == 0) b_lower = b_upper = nullptr;
+        SLP_REQUIRE(!b_eq || s->sh.scale_eq, "slp_admm_batch_set_rhs: the state did not keep the row scaling of the equality block");
+        SLP_REQUIRE(!(b_lower || b_upper) || s->sh.scale_ineq,
+                    "slp_admm_batch_set_rhs: the state did not keep the row scaling of the inequality block");
+        const bool eq_b = b_eq && b_eq_batched, lo_b = b_lower && b_lower_batched, hi_b = b_upper && b_upper_batched;
+        const size_t nb = (size_t)N * (size_t)s->Bp, mb = (size_t)m * (size_t)s->Bp;
+        const bool new_b = eq_b && !s->b_b, new_lb = lo_b && !s->lb_b, new_ub = hi_b && !s->ub_b;
+        SLP_HIP(hipStreamSynchronize(st));
+        {
+            // nothing is allocated before this check: what stays (the tiled b, the bounds that become batched, a shared vector of
+            // the state's own) and the staging of this call (the caller's rows, [b_k; 0] and A^T b_k per instance)
+            i64 free_b = 0, total_b = 0;
+            SLP_REQUIRE(slp_device_memory(&free_b, &total_b) == 0, slp_last_error());
+            double need = 8.0 * ((new_b ? (double)mb : 0.0) + ((new_lb ? 1.0 : 0.0) + (new_ub ? 1.0 : 0.0)) * (double)nb);
+            if (b_eq) need += 8.0 * (double)(eq_b ? B : 1) * (double)(m_eq + m + N) + 8.0 * (double)m;
+            if (b_lower || b_upper) need += 8.0 * 2.0 * (double)((lo_b || hi_b) ? B : 1) * (double)m_ineq + 8.0 * 2.0 * (double)N;
+            const double have = (double)free_b + (double)slp_cached_bytes();
+            if (need > have)
+                throw Error("slp_admm_batch_set_rhs: the right-hand sides of " + std::to_string(B) + " instances need " +
+                            std::to_string(need / 1e9) + " GB of device memory, " + std::to_string(have / 1e9) + " GB are free");
+        }
+        if (b_eq) {
+            const i64 reps = eq_b ? B : 1;
+            DevBuf<double> stage((size_t)(reps * m_eq)), bk((size_t)(reps * m)), atb((size_t)(reps * N));
+            stage.upload(b_eq, (size_t)(reps * m_eq));
+            bk.zero();   // the inequality rows of b are 0 (tools.py:88-127)
+            hipLaunchKernelGGL(k_admmb_scale_rhs, dim3(grid_for(reps * m_eq, kBlock)), dim3(kBlock), 0, st, m_eq, reps * m_eq, s->sh.scale_eq,
+                               s->sh.scale_rows, stage.p, m, bk.p);
+            SLP_HIP(hipGetLastError());
+            // A^T b_k with the set-up's product (ADMM.py:95), then q_k
+            for (i64 k = 0; k < reps; ++k) launch_spmv(s->sh.a->at, bk.p + k * m, atb.p + k * N, SLP_ORDER_SEQUENTIAL);
+            hipLaunchKernelGGL(k_admmb_q, dim3(grid_for(N * s->Bp, kBlock)), dim3(kBlock), 0, st, N, n, s->B, s->Bt, s->Bp, s->c.p, atb.p,
+                               eq_b ? 1 : 0, s->gamma_eq, s->q.p);
+            SLP_HIP(hipGetLastError());
+            if (eq_b || s->b_b) {
+                if (!s->b_b) s->b.alloc(mb);
+                admmb_scatter(s, m, m, bk.p, eq_b ? 1 : 0, nullptr, s->b.p);
+                s->b_b = true;
+                s->b_own = false;
+            } else {
+                if (!s->b_own) s->b.alloc((size_t)m);
+                SLP_HIP(hipMemcpyAsync(s->b.p, bk.p, (size_t)m * sizeof(double), hipMemcpyDeviceToDevice, st));
+                s->b_own = true;
+            }
+            SLP_HIP(hipStreamSynchronize(st));   // the staging goes away
+        }
+        // the slack part of a bound: the scaled b_lower / b_upper (:76-83; -inf / +inf stay)
+        auto slack = [&](const double *host, bool batched, DevBuf<double> &bound, bool &bound_b, bool &bound_own, const double *shared) {
+            const i64 reps = batched ? B : 1;
+            DevBuf<double> stage((size_t)(reps * m_ineq)), scaled((size_t)(reps * m_ineq));
+            stage.upload(host, (size_t)(reps * m_ineq));
+            hipLaunchKernelGGL(k_admmb_scale_rhs, dim3(grid_for(reps * m_ineq, kBlock)), dim3(kBlock), 0, st, m_ineq, reps * m_ineq,
+                               s->sh.scale_ineq, (const double *)nullptr, stage.p, m_ineq, scaled.p);
+            SLP_HIP(hipGetLastError());
+            if (batched && !bound_b) {   // the bound becomes batched over N because of its slack part
+                const double *cur = bound_own ? bound.p : shared;
+                DevBuf<double> tiled(nb);
+                admmb_scatter(s, N, n, cur, 0, cur + n, tiled.p);
+                SLP_HIP(hipStreamSynchronize(st));
+                bound = std::move(tiled);
+                bound_b = true;
+                bound_own = false;
+            }
+            if (bound_b) {
+                hipLaunchKernelGGL(k_admmb_scatter_tail, dim3(grid_for(m_ineq * B, kBlock)), dim3(kBlock), 0, st, N, n, m_ineq, B, s->Bt, scaled.p,
+                                   batched ? 1 : 0, bound.p);
+                SLP_HIP(hipGetLastError());
+            } else {
+                if (!bound_own) {
+                    bound.alloc((size_t)N);
+                    SLP_HIP(hipMemcpyAsync(bound.p, shared, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+                    bound_own = true;
+                }
+                SLP_HIP(hipMemcpyAsync(bound.p + n, scaled.p, (size_t)m_ineq * sizeof(double), hipMemcpyDeviceToDevice, st));
+            }
+            SLP_HIP(hipStreamSynchronize(st));
+        };
+        if (b_lower) slack(b_lower, lo_b, s->lb, s->lb_b, s->lb_own, s->sh.lb);
+        if (b_upper) slack(b_upper, hi_b, s->ub, s->ub_b, s->ub_own, s->sh.ub);
     })
 }
 

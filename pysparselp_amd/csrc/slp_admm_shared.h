@@ -20,6 +20,10 @@ struct AdmmShared {
     const double *x0 = nullptr;                                // [N] = [x0; A_ineq x0] (:84-86)
     const double *atb = nullptr;                               // [N] A^T b (:95)
     const double *c = nullptr, *q = nullptr, *xp0 = nullptr;   // [N] [c; 0], (-c) + gamma_eq A^T b (:97), max(x0, 0) (:98)
+    // the row scalings the chain applied (:76-83, :90-91): [m_eq] (NULL without an equality block), [m - m_eq], [m] (NULL without
+    // use_preconditioning); slp_admm_batch_set_rhs brings an instance's own right-hand sides to the state's units with them
+    i64 m_eq = 0;
+    const double *scale_eq = nullptr, *scale_ineq = nullptr, *scale_rows = nullptr;
     i64 nlevels = 0, max_width = 0, nnz_m = 0;
     std::vector<i64> lptr;
     const i64 *gs_ptr = nullptr;

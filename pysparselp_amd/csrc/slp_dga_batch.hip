@@ -3,6 +3,9 @@
 // The instances differ in c and, optionally, in lb, ub and the start multipliers.  Every chain of additions is the single
 // solver's (slp_dga_shared.h, included by slp_dga.hip too), so instance k is bit for bit what slp_dga computes on its data:
 // x, y, the tie draws taken and the status flags, on either search path, for any B and any split of the iterations over calls.
+// slp_batch_dga_set_rhs (include/slp_hip_ext_batch_rhs.h), before the first iteration, gives every instance a right-hand side of its
+// own: b then holds B segments of m and its readers -- the gradient pass, the y . b of the bound and of the report -- take
+// b + instance * b_stride (0 for the shared vector of the constructor).
 //
 // Layout: instance-major.  A batched vector over the n variables (c, x, c_bar, d; lb, ub when they are per instance) is B
 // segments of n, over the m rows (y, K x, g) B segments of m; the sort keys, sorted columns and both scan outputs are B segments
@@ -54,6 +57,7 @@
 #include "slp_many.h"
 #include "slp_dga_shared.h"
 #include "../../include/slp_hip_ext_dga_batch.h"
+#include "../../include/slp_hip_ext_batch_rhs.h"
 
 using namespace slp;
 
@@ -115,13 +119,16 @@ __global__ __launch_bounds__(kBlock) void k_dgab_product_all(i64 rows, i64 cols,
         out[inst * rows + i] = row_dot<1>(ptr, idx, val, vk, i, 0);
 }
 
-__global__ void k_dgab_grad(i64 m, i64 r0, i64 r1, int ineq, const double *__restrict__ ax, const double *__restrict__ b,
+// BB: b holds one vector per instance (slp_batch_dga_set_rhs), b_stride apart; a template parameter, so that a state with a
+// shared b launches the code it launched before the switch existed
+template <bool BB>
+__global__ void k_dgab_grad(i64 m, i64 r0, i64 r1, int ineq, const double *__restrict__ ax, const double *__restrict__ b, i64 b_stride,
                             const double *__restrict__ y, double *__restrict__ g, const DgaCtl *__restrict__ ctl,
                             double *__restrict__ part_gb, double *__restrict__ part_min, int *__restrict__ part_any) {
     __shared__ double red[kBlock / kWave];
     const i64 inst = blockIdx.y;
     if (ctl[inst].frozen) return;
-    dga_grad_body(m, r0, r1, ineq, ax + inst * m, b, y + inst * m, g + inst * m, part_gb + inst * kDgaParts, part_min + inst * kDgaParts,
+    dga_grad_body(m, r0, r1, ineq, ax + inst * m, BB ? b + inst * b_stride : b, y + inst * m, g + inst * m, part_gb + inst * kDgaParts, part_min + inst * kDgaParts,
                   part_any + inst * kDgaParts, (int)blockIdx.x, (int)gridDim.x, (int)threadIdx.x,
                   dga_part_tiles(m, (int)blockIdx.x, (int)gridDim.x), red);
 }
@@ -196,11 +203,11 @@ __global__ __launch_bounds__(kBlock) void k_dgab_bound_x(i64 n, const double *__
 }
 
 __global__ __launch_bounds__(kBlock) void k_dgab_bound_y(i64 m, i64 m_eq, const double *__restrict__ y, const double *__restrict__ b,
-                                                         const DgaCtl *__restrict__ ctl, double *__restrict__ part) {
+                                                         i64 b_stride, const DgaCtl *__restrict__ ctl, double *__restrict__ part) {
     __shared__ double red[kBlock / kWave];
     const i64 inst = blockIdx.y;
     if (ctl[inst].frozen) return;
-    dga_energy_y_body<false>(m, m_eq, y + inst * m, b, nullptr, part + inst * 4 * kDgaParts + kDgaParts, red);
+    dga_energy_y_body<false>(m, m_eq, y + inst * m, b + inst * b_stride, nullptr, part + inst * 4 * kDgaParts + kDgaParts, red);
 }
 
 // One workgroup per instance, at the end of check iteration `done`: the step from the instance's slots, the bound from the 4
@@ -325,11 +332,11 @@ __global__ void k_dgab_energy_x(i64 n, const double *__restrict__ cbar, const do
     dga_energy_x_body(n, cbar + inst * n, lb + inst * lb_stride, ub + inst * ub_stride, part + inst * 4 * kDgaParts, red);
 }
 
-__global__ void k_dgab_energy_y(i64 m, i64 m_eq, const double *__restrict__ y, const double *__restrict__ b, const double *__restrict__ ax,
+__global__ void k_dgab_energy_y(i64 m, i64 m_eq, const double *__restrict__ y, const double *__restrict__ b, i64 b_stride, const double *__restrict__ ax,
                                 double *__restrict__ part) {
     __shared__ double red[kBlock / kWave];
     const i64 inst = blockIdx.y;
-    dga_energy_y_body(m, m_eq, y + inst * m, b, ax + inst * m, part + inst * 4 * kDgaParts + kDgaParts, red);
+    dga_energy_y_body(m, m_eq, y + inst * m, b + inst * b_stride, ax + inst * m, part + inst * 4 * kDgaParts + kDgaParts, red);
 }
 
 }  // namespace
@@ -338,6 +345,7 @@ struct slp_batch_dga {
     slp_matrix *k = nullptr;   // borrowed
     i64 n = 0, m = 0, m_eq = 0, B = 0;
     i64 lb_stride = 0, ub_stride = 0;   // n when the bounds are per instance, 0 when all instances share them
+    i64 b_stride = 0;                   // m when the right-hand sides are per instance (slp_batch_dga_set_rhs), 0 when shared
     DevBuf<double> b, c, lb, ub, y, x, cbar, ax, g, d, rcbar, rx, rax, rpart;
     DevBuf<DgaCtl> ctl;
     DevBuf<double> part_gb, part_min;
@@ -449,8 +457,8 @@ void dgab_block(slp_batch_dga *s, i64 r0, i64 r1, int ineq, bool check) {
     const CsrDev &at = s->k->at;
     const i64 n = s->n, m = s->m, B = s->B;
     const unsigned int ub = (unsigned int)B;
-    hipLaunchKernelGGL(k_dgab_grad, dim3(kDgaParts, ub), dim3(kBlock), 0, st, m, r0, r1, ineq, s->ax.p, s->b.p, s->y.p, s->g.p, s->ctl.p,
-                       s->part_gb.p, s->part_min.p, s->part_any.p);
+    hipLaunchKernelGGL(s->b_stride ? k_dgab_grad<true> : k_dgab_grad<false>, dim3(kDgaParts, ub), dim3(kBlock), 0, st, m, r0, r1, ineq, s->ax.p,
+                       s->b.p, s->b_stride, s->y.p, s->g.p, s->ctl.p, s->part_gb.p, s->part_min.p, s->part_any.p);
     hipLaunchKernelGGL(k_dgab_begin, dim3(ub), dim3(kBlock), 0, st, s->part_gb.p, s->part_min.p, s->part_any.p, s->ctl.p);
     s->timer.mark(ST_REST);
     hipLaunchKernelGGL(k_dgab_product, grid2(n, B), dim3(kBlock), 0, st, n, m, at.ptr.p, at.idx.p, at.val.p, s->g.p, s->ctl.p, 1, s->d.p);
@@ -516,7 +524,7 @@ void dgab_check(slp_batch_dga *s, i64 done) {
         s->timer.mark(ST_PRODUCTS);
         hipLaunchKernelGGL(k_dgab_bound_x, dim3(kDgaParts, ub), dim3(kBlock), 0, st, s->n, s->rcbar.p, s->lb.p, s->lb_stride, s->ub.p, s->ub_stride,
                            s->ctl.p, s->rpart.p);
-        hipLaunchKernelGGL(k_dgab_bound_y, dim3(kDgaParts, ub), dim3(kBlock), 0, st, s->m, s->m_eq, s->y.p, s->b.p, s->ctl.p, s->rpart.p);
+        hipLaunchKernelGGL(k_dgab_bound_y, dim3(kDgaParts, ub), dim3(kBlock), 0, st, s->m, s->m_eq, s->y.p, s->b.p, s->b_stride, s->ctl.p, s->rpart.p);
     }
     hipLaunchKernelGGL(k_dgab_decide, dim3(ub), dim3(kBlock), 0, st, s->ctl.p, s->stop.p, done, s->tol, s->has_targets ? s->targets.p : nullptr,
                        s->step_part.p, s->step_parts_ineq + s->step_parts_eq, s->rpart.p);
@@ -555,7 +563,7 @@ void dgab_report(slp_batch_dga *s, double *out) {
     hipLaunchKernelGGL(k_dgab_product_all, grid2(s->m, s->B), dim3(kBlock), 0, st, s->m, s->n, a.ptr.p, a.idx.p, a.val.p, s->rx.p, s->rax.p);
     hipLaunchKernelGGL(k_dgab_energy_x, dim3(kDgaParts, ub), dim3(kBlock), 0, st, s->n, s->rcbar.p, s->lb.p, s->lb_stride, s->ub.p, s->ub_stride,
                        s->rpart.p);
-    hipLaunchKernelGGL(k_dgab_energy_y, dim3(kDgaParts, ub), dim3(kBlock), 0, st, s->m, s->m_eq, s->y.p, s->b.p, s->rax.p, s->rpart.p);
+    hipLaunchKernelGGL(k_dgab_energy_y, dim3(kDgaParts, ub), dim3(kBlock), 0, st, s->m, s->m_eq, s->y.p, s->b.p, s->b_stride, s->rax.p, s->rpart.p);
     SLP_HIP(hipGetLastError());
     std::vector<double> h((size_t)4 * kDgaParts * (size_t)s->B);
     s->rpart.download(h.data(), h.size());
@@ -716,6 +724,37 @@ int slp_batch_dga_report(slp_batch_dga *s, double *out) {
     SLP_API_INT({
         SLP_REQUIRE(s && out, "slp_batch_dga_report: NULL argument");
         dgab_report(s, out);
+    })
+}
+
+int slp_batch_dga_set_rhs(slp_batch_dga *s, const double *b, int b_batched) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && b, "slp_batch_dga_set_rhs: NULL argument");
+        SLP_REQUIRE(s->iters == 0, "slp_batch_dga_set_rhs: the state has iterated; the right-hand sides are set before the first iteration");
+        const size_t sm = (size_t)s->m, sb = (size_t)s->B, count = b_batched ? sm * sb : sm;
+        SLP_HIP(hipStreamSynchronize(ctx().stream));
+        DevBuf<double> nb;
+        if (count > s->b.n) {   // nothing is allocated before this check; a refusal leaves the old right-hand sides in place
+            i64 free_b = 0, total_b = 0;
+            SLP_REQUIRE(slp_device_memory(&free_b, &total_b) == 0, slp_last_error());
+            const double need = 8.0 * (double)count, have = (double)free_b + (double)slp_cached_bytes();
+            if (need > have)
+                throw Error("slp_batch_dga_set_rhs: per-instance right-hand sides need " + std::to_string(need / 1e9) +
+                            " GB of device memory, " + std::to_string(have / 1e9) + " GB are free");
+            nb.alloc(count);
+            nb.upload(b, count);
+            s->b = std::move(nb);
+        } else {
+            s->b.upload(b, count);
+        }
+        s->b_stride = b_batched ? s->m : 0;
+        // what the constructor derived from b: a start whose dual energy is -inf freezes its instance
+        std::vector<double> rep(3 * sb);
+        dgab_report(s, rep.data());
+        std::vector<DgaCtl> h(sb);
+        s->ctl.download(h.data(), sb);
+        for (size_t k = 0; k < sb; ++k) h[k].frozen = rep[3 * k] == -INFINITY;
+        s->ctl.upload(h.data(), sb);
     })
 }
 

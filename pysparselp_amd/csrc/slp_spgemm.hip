@@ -304,7 +304,7 @@ __global__ void k_scale_vec(i64 n, const double *__restrict__ inv, double *__res
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) b[i] = inv[i] * b[i];  // inf stays inf
 }
 
-slp_matrix *matrix_precondition_rows(slp_matrix *a, double *b, double *b2) {
+slp_matrix *matrix_precondition_rows(slp_matrix *a, double *b, double *b2, DevBuf<double> *keep_inv) {
     SLP_REQUIRE(a, "precondition_rows: NULL matrix");
     require_csr(a, "precondition_rows");
     hipStream_t st = ctx().stream;
@@ -337,6 +337,7 @@ slp_matrix *matrix_precondition_rows(slp_matrix *a, double *b, double *b2) {
         SLP_HIP(hipGetLastError());
         SLP_HIP(hipStreamSynchronize(st));
         finish_stats(m->a);
+        if (keep_inv) *keep_inv = std::move(inv);
     } catch (...) {
         delete m;
         throw;
