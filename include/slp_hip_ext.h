@@ -24,6 +24,8 @@
 #include "slp_hip_ext_batch_rhs.h"
 /* which packet form a tall-cell product copy has: likewise */
 #include "slp_hip_ext_tall.h"
+/* the single Chambolle-Pock solver stops on a certified duality gap: likewise */
+#include "slp_hip_ext_cp_gap.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _lib
 from . import _many
+from ._cp_gap import CPGapMethods, check_gap, vertex_certificate
 from ._batch import box_vertex, concat, first_offsets, shared_or_batched, split_by
 from ._lib import ORDER_AUTO
 from .parallel import collective_elapsed
@@ -61,8 +62,9 @@ def one_sided_system(a_ineq, b_lower, b_upper):
     return mat, b
 
 
-class CPState:
-    """Device-resident Chambolle-Pock state (thin RAII wrapper of ``slp_cp``)."""
+class CPState(CPGapMethods):
+    """Device-resident Chambolle-Pock state (thin RAII wrapper of ``slp_cp``); ``certificate``, ``set_stop_gap`` and ``gap_state``
+    are ``_cp_gap.CPGapMethods``'."""
 
     def __init__(self, c, a_eq, beq, ineq, b_ineq, lb, ub, x0, alpha, theta, order=ORDER_AUTO):
         self._l = _lib.lib()
@@ -202,14 +204,20 @@ def device_cp(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0=None, alpha=1, 
     return state, free, shift
 
 
-def _cp_loop(state, c, n, has_ineq, nb_max_iter, nb_iter_plot, callback_func, max_time, start, x_of):
+def _cp_loop(state, c, n, has_ineq, nb_max_iter, nb_iter_plot, callback_func, max_time, start, x_of, stopped_now=None):
     """The reporting loop of chambolle_pock_ppd (:195-343) over a solver state; ``x_of(state)`` is its iterate.
-    Returns ``(x, best_integer_solution)``."""
+    Returns ``(x, best_integer_solution)``.
+
+    ``stopped_now()`` (a state armed with ``set_stop_gap``; ``None``: no test) is asked before every report's primal half whether
+    the state is stopped: the loop ends there, without a report.  A stopped state ignores ``iterate``, so ``niter`` may run ahead
+    of the state's own count until then."""
     best_integer_solution_energy = np.inf
     best_integer_solution = None
     niter = 0
     while niter < nb_max_iter:
         if niter % nb_iter_plot == 0:
+            if stopped_now is not None and stopped_now():
+                break
             state.primal_step()
             elapsed = time.perf_counter() - start
             if (max_time is not None) and collective_elapsed(elapsed) > max_time:  # the same decision on every rank
@@ -279,6 +287,21 @@ def chambolle_pock_ppd(
     if save_problem or force_integer:
         # debugging pickle / rounding heuristic of the reference: outside the accelerated path
         raise NotImplementedError("save_problem / force_integer are not supported by pysparselp_amd")
+    x, best_integer_solution, _, has_rows = _cp_run(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, alpha, theta, nb_max_iter,
+                                                    callback_func, max_time, nb_iter_plot, order, setup)
+    return (x, best_integer_solution) if has_rows else x
+
+
+def _gap_info(state):
+    iterations, stopped, primal, bound, violation = state.gap_state()
+    return dict(iterations=iterations, stopped=stopped, primal=primal, lower_bound=bound, violation=violation)
+
+
+def _cp_run(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, alpha, theta, nb_max_iter, callback_func, max_time, nb_iter_plot, order,
+            setup, gap=None):
+    """``chambolle_pock_ppd`` (``gap`` None) and ``chambolle_pock_ppd_certified`` (``gap`` the checked ``(tol_gap, tol_feas,
+    check_every)``): ``(x, best_integer_solution, info, has_rows)``; ``info`` is None without a test; an LP without rows (``has_rows``
+    False) ran nothing: ``x`` is its box vertex (which ``chambolle_pock_ppd`` returns alone, as the reference does, :147-151)."""
     start = time.perf_counter()
     c = _lib.f64(c)
     lb, ub = _lib.f64(lb), _lib.f64(ub)
@@ -289,20 +312,26 @@ def chambolle_pock_ppd(
     if a_ineq is not None and a_ineq.shape[0] == 0:
         a_ineq = None
     if a_eq is None and a_ineq is None:  # reference :147-151: no constraints, a vertex of the box
-        return box_vertex(c, lb, ub)
+        x = box_vertex(c, lb, ub)
+        return x, None, None if gap is None else vertex_certificate(c, x), False
     for a in (a_eq, a_ineq):
         if a is not None:
             assert a.shape[1] == n
     from . import host_setup
 
+    info = None
     if host_setup.choose(setup, host_setup.nnz_of(a_eq, a_ineq)) == "device":
         state, _, _ = device_cp(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, alpha, theta, order)
         try:
+            if gap is not None:
+                state.set_stop_gap(*gap)
             x, best_integer_solution = _cp_loop(state, c, n, a_ineq is not None, nb_max_iter, nb_iter_plot, callback_func, max_time,
-                                                start, lambda st: st.x_reduced())
+                                                start, lambda st: st.x_reduced(), None if gap is None else lambda: state.gap_state()[1])
+            if gap is not None:
+                info = _gap_info(state)
         finally:
             close_device_cp(state)
-        return x, best_integer_solution
+        return x, best_integer_solution, info, True
     ineq, b_ineq = (None, None)
     if a_ineq is not None:
         ineq, b_ineq = one_sided_system(a_ineq, b_lower, b_upper)
@@ -310,13 +339,56 @@ def chambolle_pock_ppd(
 
     state = CPState(c, a_eq, beq, ineq, b_ineq, lb, ub, x0, alpha, theta, order)
     try:
+        if gap is not None:
+            state.set_stop_gap(*gap)
         x, best_integer_solution = _cp_loop(state, c, n, a_ineq is not None, nb_max_iter, nb_iter_plot, callback_func, max_time, start,
-                                            lambda st: st.x())
+                                            lambda st: st.x(), None if gap is None else lambda: state.gap_state()[1])
+        if gap is not None:
+            info = _gap_info(state)
     finally:
         state.close()
     if best_integer_solution is not None:
         best_integer_solution = best_integer_solution[:n]
-    return x[:n], best_integer_solution
+    return x[:n], best_integer_solution, info, True
+
+
+def chambolle_pock_ppd_certified(
+    c,
+    a_eq,
+    beq,
+    a_ineq,
+    b_lower,
+    b_upper,
+    lb,
+    ub,
+    tol_gap,
+    tol_feas,
+    check_every=10,
+    x0=None,
+    alpha=1,
+    theta=1,
+    nb_max_iter=10000,
+    callback_func=None,
+    max_time=None,
+    nb_iter_plot=10,
+    order=ORDER_AUTO,
+    setup="auto",
+):
+    """``chambolle_pock_ppd`` that stops on a certificate (extension; the reference stops on nothing): at the first iteration
+    ``t`` with ``t % check_every == 0`` at which the violation of ``x_t`` is at most ``tol_feas`` and the gap between ``c.x_t``
+    and a valid lower bound is at most ``tol_gap * (1 + |primal| + |bound|)`` (``CPState.set_stop_gap``), or after
+    ``nb_max_iter`` iterations.  Every format and set-up of ``chambolle_pock_ppd``, and its row partition under a communicator.
+
+    Returns ``(x, best_integer_solution, info)``; ``info`` is a dict of ``iterations`` (whole iterations completed), ``stopped``,
+    and the last evaluated certificate ``primal``, ``lower_bound``, ``violation`` of the LP the solver holds (``+inf``, ``-inf``,
+    ``+inf`` before the first check).  ``x`` is bit for bit ``chambolle_pock_ppd(..., nb_max_iter=info["iterations"])[0]``.  The
+    reporting loop is that of ``chambolle_pock_ppd``; it ends, without a report, at the first report that finds the state
+    stopped.  ``tol_gap`` and ``tol_feas`` finite floats ``>= 0`` and ``check_every`` an int ``>= 1``: a ``ValueError`` otherwise,
+    before anything is uploaded.  An LP without rows returns its box vertex, stopped after 0 iterations, with that vertex's
+    certificate."""
+    gap = check_gap(tol_gap, tol_feas, check_every)
+    return _cp_run(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, alpha, theta, nb_max_iter, callback_func, max_time, nb_iter_plot,
+                   order, setup, gap)[:3]
 
 
 # ---------------------------------------------------------------------------------------------------------------------

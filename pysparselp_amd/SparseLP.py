@@ -493,22 +493,7 @@ class SparseLP:
             assert a_ineq.indices.size == 0 or a_ineq.indices.max() < a_ineq.shape[1]
         start = time.perf_counter()
         _reset_curves(self)
-
-        def record(niter, solution, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
-            if ground_truth is not None:
-                picked = solution[ground_truth_indices]
-                self.distance_to_ground_truth.append(np.mean(np.abs(ground_truth - picked)))
-                self.distanceToGroundTruthAfterRounding.append(np.mean(np.abs(ground_truth - np.round(picked))))
-            self.itrn_curve.append(niter)
-            self.opttime_curve.append(duration)
-            self.dopttime_curve.append(duration)
-            self.dobj_curve.append(energy2)
-            self.pobj_curve.append(energy1)
-            self.max_violated_constraint.append(self.max_constraint_violation(solution))
-            self.max_violated_equality.append(max_violated_equality)
-            self.max_violated_inequality.append(max_violated_inequality)
-            if plot_solution is not None:
-                plot_solution(niter, solution, is_active_variable=None)
+        record = self._curve_recorder(ground_truth, ground_truth_indices, plot_solution)
 
         if method == "admm":
             if xstep == "auto":
@@ -539,41 +524,120 @@ class SparseLP:
             x, _, _ = dual_gradient_ascent(x=x0, lp=self, nb_max_iter=nb_iter, callback_func=record, y_eq=None, y_ineq=None,
                                            max_time=max_time, nb_iter_plot=nb_iter_plot)
         else:  # chambolle_pock_ppd: fixed variables are eliminated first (reference :1244-1248)
-            from . import host_setup
-            from .ChambollePockPPD import _cp_loop, close_device_cp, device_cp
+            x, _ = self._solve_cp(a_eq, b_eq, a_ineq, record, start, nb_iter, max_time, nb_iter_plot, order, setup)
+        elapsed = time.perf_counter() - start
+        return (x, elapsed) if get_timing else x
 
-            device = (a_eq is not None or a_ineq is not None) and host_setup.choose(setup, host_setup.nnz_of(a_eq, a_ineq)) == "device"
-            if device:  # no deep copy, no host remove_fixed_variables: the fixed variables are dropped on the device
-                state, free, shift = device_cp(self.costsvector, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds,
-                                               self.upper_bounds, x0=None, alpha=1, theta=1, order=order, remove_fixed=True)
-            else:
-                reduced = copy.deepcopy(self)
-                free, shift = reduced.remove_fixed_variables()
-            free_ids = np.nonzero(free)[0]
+    def _curve_recorder(self, ground_truth, ground_truth_indices, plot_solution=None):
+        """The callback that fills the curve attributes of ``solve`` at every report."""
+        def record(niter, solution, energy1, energy2, duration, max_violated_equality, max_violated_inequality):
+            if ground_truth is not None:
+                picked = solution[ground_truth_indices]
+                self.distance_to_ground_truth.append(np.mean(np.abs(ground_truth - picked)))
+                self.distanceToGroundTruthAfterRounding.append(np.mean(np.abs(ground_truth - np.round(picked))))
+            self.itrn_curve.append(niter)
+            self.opttime_curve.append(duration)
+            self.dopttime_curve.append(duration)
+            self.dobj_curve.append(energy2)
+            self.pobj_curve.append(energy1)
+            self.max_violated_constraint.append(self.max_constraint_violation(solution))
+            self.max_violated_equality.append(max_violated_equality)
+            self.max_violated_inequality.append(max_violated_inequality)
+            if plot_solution is not None:
+                plot_solution(niter, solution, is_active_variable=None)
 
-            def expand(sol):
-                # reference :1259,:1288: x = m_change * sol - shift (note the sign it applies to the fixed values)
-                full = np.zeros(free.size)
-                full[free_ids] = sol
-                return full - shift
+        return record
 
-            def record_reduced(niter, solution, *rest):
-                record(niter, expand(solution), *rest)
+    def _solve_cp(self, a_eq, b_eq, a_ineq, record, start, nb_iter, max_time, nb_iter_plot, order, setup, gap=None):
+        """The Chambolle-Pock branch of ``solve`` (``gap`` None) and of ``solve_certified`` (``gap`` the checked ``(tol_gap, tol_feas,
+        check_every)``): the reduction, the solver and ``expand``.  Returns ``(x, info)``, ``info`` None without a test."""
+        from . import host_setup
+        from .ChambollePockPPD import _cp_loop, _gap_info, chambolle_pock_ppd_certified, close_device_cp, device_cp
 
-            if device:
-                # (the iterate over the free variables goes through expand: DeviceCP.x() puts the fixed ones at +shift)
-                try:
-                    x, _ = _cp_loop(state, self.costsvector[free], state.n, a_ineq is not None, nb_iter, nb_iter_plot, record_reduced,
-                                    max_time, start, lambda st: st.x_reduced())
-                finally:
-                    close_device_cp(state)
-            else:
-                x, _ = chambolle_pock_ppd(reduced.costsvector, reduced.a_equalities, reduced.b_equalities,
-                                          reduced.a_inequalities, reduced.b_lower, reduced.b_upper, reduced.lower_bounds,
-                                          reduced.upper_bounds, x0=None, alpha=1, theta=1, nb_max_iter=nb_iter,
-                                          callback_func=record_reduced, max_time=max_time, nb_iter_plot=nb_iter_plot,
-                                          order=order, setup="host")
-            x = expand(x)
+        device = (a_eq is not None or a_ineq is not None) and host_setup.choose(setup, host_setup.nnz_of(a_eq, a_ineq)) == "device"
+        if device:  # no deep copy, no host remove_fixed_variables: the fixed variables are dropped on the device
+            state, free, shift = device_cp(self.costsvector, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds,
+                                           self.upper_bounds, x0=None, alpha=1, theta=1, order=order, remove_fixed=True)
+        else:
+            reduced = copy.deepcopy(self)
+            free, shift = reduced.remove_fixed_variables()
+        free_ids = np.nonzero(free)[0]
+
+        def expand(sol):
+            # reference :1259,:1288: x = m_change * sol - shift (note the sign it applies to the fixed values)
+            full = np.zeros(free.size)
+            full[free_ids] = sol
+            return full - shift
+
+        def record_reduced(niter, solution, *rest):
+            record(niter, expand(solution), *rest)
+
+        info = None
+        if device:
+            # (the iterate over the free variables goes through expand: DeviceCP.x() puts the fixed ones at +shift)
+            try:
+                if gap is not None:
+                    state.set_stop_gap(*gap)
+                x, _ = _cp_loop(state, self.costsvector[free], state.n, a_ineq is not None, nb_iter, nb_iter_plot, record_reduced,
+                                max_time, start, lambda st: st.x_reduced(), None if gap is None else lambda: state.gap_state()[1])
+                if gap is not None:
+                    info = _gap_info(state)
+            finally:
+                close_device_cp(state)
+        elif gap is not None:
+            x, _, info = chambolle_pock_ppd_certified(reduced.costsvector, reduced.a_equalities, reduced.b_equalities,
+                                                      reduced.a_inequalities, reduced.b_lower, reduced.b_upper, reduced.lower_bounds,
+                                                      reduced.upper_bounds, *gap, x0=None, alpha=1, theta=1, nb_max_iter=nb_iter,
+                                                      callback_func=record_reduced, max_time=max_time, nb_iter_plot=nb_iter_plot,
+                                                      order=order, setup="host")
+        else:
+            x, _ = chambolle_pock_ppd(reduced.costsvector, reduced.a_equalities, reduced.b_equalities,
+                                      reduced.a_inequalities, reduced.b_lower, reduced.b_upper, reduced.lower_bounds,
+                                      reduced.upper_bounds, x0=None, alpha=1, theta=1, nb_max_iter=nb_iter,
+                                      callback_func=record_reduced, max_time=max_time, nb_iter_plot=nb_iter_plot,
+                                      order=order, setup="host")
+        return expand(x), info
+
+    def solve_certified(
+        self,
+        tol_gap,
+        tol_feas,
+        check_every=10,
+        get_timing=True,
+        nb_iter=10000,
+        max_time=None,
+        nb_iter_plot=10,
+        ground_truth=None,
+        ground_truth_indices=None,
+        order=ORDER_AUTO,
+        setup="auto",
+    ):
+        """``solve(method="chambolle_pock_ppd")`` with a certificate as the stopping test
+        (``ChambollePockPPD.chambolle_pock_ppd_certified``): it stops at the first iteration ``t`` with ``t % check_every == 0`` at
+        which the violation of the iterate is at most ``tol_feas`` and the gap between its primal value and a valid lower bound is
+        at most ``tol_gap * (1 + |primal| + |bound|)``, or after ``nb_iter`` iterations.  Returns ``(x, elapsed)`` or ``x``;
+        ``tol_gap`` and ``tol_feas`` finite floats ``>= 0`` and ``check_every`` an int ``>= 1``, a ``ValueError`` otherwise.
+
+        The reduction (``remove_fixed_variables``, on the host or on the device by ``setup``), the curves and the row partition
+        under a communicator are those of ``solve``; the loop ends, without a report, at the first report that finds the solver
+        stopped.  ``x`` is bit for bit ``solve("chambolle_pock_ppd", nb_iter=stop_info["iterations"])``.
+
+        Sets ``self.stop_info``: ``iterations`` (whole iterations completed), ``stopped``, and the last evaluated certificate
+        ``primal``, ``lower_bound``, ``violation``.  These three are the numbers of the LP the solver holds, AFTER
+        ``remove_fixed_variables``: the cost of the removed variables at their fixed values is not in them.  It is given separately
+        as ``fixed_cost``; add it to ``primal`` and to ``lower_bound`` for the value and the bound of the LP as it was handed in.
+        """
+        from ._cp_gap import check_gap
+
+        gap = check_gap(tol_gap, tol_feas, check_every)
+        a_ineq = self.a_inequalities if (self.a_inequalities is not None and self.a_inequalities.shape[0] > 0) else None
+        a_eq, b_eq = (self.a_equalities, self.b_equalities) if self.a_equalities.shape[0] > 0 else (None, None)
+        start = time.perf_counter()
+        _reset_curves(self)
+        record = self._curve_recorder(ground_truth, ground_truth_indices)
+        x, info = self._solve_cp(a_eq, b_eq, a_ineq, record, start, nb_iter, max_time, nb_iter_plot, order, setup, gap)
+        fixed = ~(self.upper_bounds > self.lower_bounds)
+        self.stop_info = dict(info, fixed_cost=float(np.dot(self.costsvector[fixed], self.lower_bounds[fixed])))
         elapsed = time.perf_counter() - start
         return (x, elapsed) if get_timing else x
 

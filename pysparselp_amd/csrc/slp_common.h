@@ -163,13 +163,12 @@ struct IterGraph {
         graph = nullptr;
         unroll = 0;
     }
-    // Runs `k` iterations of `body` (which only enqueues kernels on ctx().stream).
+    // Captures the graph of `want_unroll` iterations of `body` unless one exists (or SLP_NO_GRAPH=1); launches nothing.
     template <class F>
-    void run(i64 k, int want_unroll, F body) {
+    void capture(int want_unroll, F body) {
         hipStream_t st = ctx().stream;
-        if (want_unroll > k) want_unroll = (int)k;
         const char *off = getenv("SLP_NO_GRAPH");  // eager launches, e.g. under a profiler
-        if (!exec && k >= 2 && want_unroll >= 1 && !(off && off[0] == '1')) {
+        if (!exec && want_unroll >= 1 && !(off && off[0] == '1')) {
             std::lock_guard<std::mutex> no_helper_calls(capture_mutex());
             SLP_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
             try {
@@ -184,6 +183,13 @@ struct IterGraph {
             SLP_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
             unroll = want_unroll;
         }
+    }
+    // Runs `k` iterations of `body` (which only enqueues kernels on ctx().stream).
+    template <class F>
+    void run(i64 k, int want_unroll, F body) {
+        hipStream_t st = ctx().stream;
+        if (want_unroll > k) want_unroll = (int)k;
+        if (k >= 2) capture(want_unroll, body);
         if (exec) {
             for (; k >= unroll; k -= unroll) SLP_HIP(hipGraphLaunch(exec, st));
         }

@@ -5,7 +5,20 @@
 //                 x+ = clip(x - T d), z = (1+theta) x+ - theta x   [:198-228]
 //   k_cp_dual   : r = K z - b (walks the rows of K), y += Sigma r,
 //                 inequality rows clamped at 0                     [:231-240,:333-342]
+//
+// Stopping on a certified duality gap (slp_cp_set_stop_gap, include/slp_hip_ext_cp_gap.h; the certificate of slp_cp_many.hip and
+// slp_cp_batch.hip, its scalar arithmetic shared through slp_cp_gap.h).  The state counts its whole iterations t on the host.  An
+// unarmed state launches what it always did.  An armed one cuts slp_cp_iterate at the iterations t with t % check_every == 0 and
+// evaluates the certificate behind each of them, never inside a captured graph: K^T y_t by the products of the next primal half
+// (into its scratch pre / pre2, or inside the column pass where the primal half walks the CSR or ELL copy), K x_t by the product of
+// the dual half (into its scratch kz, or inside the row pass), k_cp_gap_cols / k_cp_gap_rows(_from) with one slice sum per lane
+// group (term r in slice r mod S, S a function of the count alone), k_cp_gap_fold and k_cp_gap_final folding the slices in two stages, and one
+// read of four doubles; the decision is cp_gap_decide on the host, under a communicator from the reduced numbers.
+#include <cmath>
+
+#include "../../include/slp_hip_ext.h"
 #include "slp_common.h"
+#include "slp_cp_gap.h"
 #include "slp_kernels.h"
 
 namespace slp {
@@ -413,6 +426,148 @@ __global__ __launch_bounds__(kBlock) void k_cp_report_final(int nrowparts, const
     }
 }
 
+// ---------------------------------------------------------------------------
+// certificate (header comment).  A pass over `count` terms has S = cp_gap_slices(count) slices, one per lane group of its launch:
+// term r belongs to slice r mod S, a slice adds its terms from 0.0 in increasing r -- whatever the format and the lanes per row.
+constexpr int kGapBlocks = 512;
+inline i64 cp_gap_slices(i64 count) {
+    i64 blocks = (count + kBlock - 1) / kBlock;
+    blocks = blocks < 1 ? 1 : (blocks > kGapBlocks ? kGapBlocks : blocks);
+    return blocks * kBlock;
+}
+
+// column pass, S = gridDim.x * kBlock / L slices: part[slice] = sum c_j x_j, part[S + slice] = sum of the bound's column terms;
+// d as k_cp_primal forms it (FROM_PRE: from the products taken beforehand; else the CSR walk of K^T, L lanes per column)
+template <int L, bool FROM_PRE>
+__global__ __launch_bounds__(kBlock) void k_cp_gap_cols(i64 n, const i64 *__restrict__ tptr, const i32 *__restrict__ tidx,
+                                                        const double *__restrict__ tval, const double *__restrict__ y,
+                                                        const double *__restrict__ pre, const double *__restrict__ pre2,
+                                                        const double *__restrict__ c, const double *__restrict__ x,
+                                                        const double *__restrict__ lb, const double *__restrict__ ub, i32 m_eq,
+                                                        i64 m_ineq, double *__restrict__ part) {
+    const int sub = threadIdx.x & (L - 1);
+    const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / L;
+    const i64 ngroups = (i64)gridDim.x * kBlock / L;
+    double cx = 0.0, terms = 0.0;
+    for (i64 j = group; j < n; j += ngroups) {
+        double d;
+        if (FROM_PRE) {
+            d = pre2 ? (c[j] + pre[j]) + pre2[j] : c[j] + pre[j];
+        } else {
+            double se, si;
+            row_dot_split<L>(tptr, tidx, tval, y, j, sub, m_eq, &se, &si);
+            if (m_eq > 0 && m_ineq > 0) d = (c[j] + se) + si;  // :206,216
+            else if (m_eq > 0) d = c[j] + se;
+            else d = c[j] + si;
+        }
+        if (sub == 0) {
+            cx += c[j] * x[j];
+            terms += cp_gap_col_term(d, lb[j], ub[j]);
+        }
+    }
+    if (sub == 0) {
+        part[group] = cx;
+        part[ngroups + group] = terms;
+    }
+}
+
+// row pass from K x as a vector (strip, tall-cell and chunked copies, with or without the CSR arrays), S = gridDim.x * kBlock
+// slices: part[slice] = sum [y_r != 0 ? y_r b_r : 0], part[S + slice] = the violation folded from 0
+__global__ __launch_bounds__(kBlock) void k_cp_gap_rows_from(i64 m, const double *__restrict__ kx, const double *__restrict__ b,
+                                                             const double *__restrict__ y, i64 m_eq, double *__restrict__ part) {
+    const i64 slice = (i64)blockIdx.x * kBlock + threadIdx.x, nslices = (i64)gridDim.x * kBlock;
+    double yb = 0.0, viol = 0.0;
+    for (i64 i = slice; i < m; i += nslices) {
+        const double bi = b[i];
+        yb += cp_gap_row_term(y[i], bi);
+        viol = cp_gap_violation(viol, kx[i] - bi, i < m_eq);
+    }
+    part[slice] = yb;
+    part[nslices + slice] = viol;
+}
+
+// row pass over the CSR of K (the walk of k_cp_dual, L lanes per row; the ELL copies hold the same chains), S = gridDim.x * kBlock / L
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_cp_gap_rows(i64 m, const i64 *__restrict__ ptr, const i32 *__restrict__ idx,
+                                                        const double *__restrict__ val, const double *__restrict__ x,
+                                                        const double *__restrict__ b, const double *__restrict__ y, i64 m_eq,
+                                                        double *__restrict__ part) {
+    const int sub = threadIdx.x & (L - 1);
+    const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / L;
+    const i64 ngroups = (i64)gridDim.x * kBlock / L;
+    double yb = 0.0, viol = 0.0;
+    for (i64 i = group; i < m; i += ngroups) {
+        const double kx = row_dot<L>(ptr, idx, val, x, i, sub);
+        if (sub == 0) {
+            const double bi = b[i];
+            yb += cp_gap_row_term(y[i], bi);
+            viol = cp_gap_violation(viol, kx - bi, i < m_eq);
+        }
+    }
+    if (sub == 0) {
+        part[group] = yb;
+        part[ngroups + group] = viol;
+    }
+}
+
+// NaN-propagating maximum of one double per thread, valid in thread 0 (block_reduce<true> drops a NaN)
+__device__ __forceinline__ double block_nan_max(double v, double *lds /* >= blockDim.x / kWave */) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = nan_max(v, __shfl_down(v, off, kWave));
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    if (lane == 0) lds[w] = v;
+    __syncthreads();
+    double r = v;
+    if (threadIdx.x == 0) {
+        r = lds[0];
+        for (int i = 1; i < (int)(blockDim.x / kWave); ++i) r = nan_max(r, lds[i]);
+    }
+    __syncthreads();
+    return r;
+}
+
+// The fold of the slice sums, two stages in a fixed order.  k_cp_gap_fold: workgroup q of a pass holds its slices 256 q .. 256 q + 255,
+// one per lane, and adds them in the workgroup's fixed tree (a wavefront by halving, the four wavefronts in increasing order); the
+// column pass's workgroups come first, the row pass's behind them.  bp[2 q], bp[2 q + 1]: the two quantities of workgroup q.
+__global__ __launch_bounds__(kBlock) void k_cp_gap_fold(i64 scols, const double *__restrict__ cp, i64 srows,
+                                                        const double *__restrict__ rp, double *__restrict__ bp) {
+    __shared__ double lds[kBlock / kWave];
+    const i64 colblocks = scols / kBlock;
+    const bool rows = (i64)blockIdx.x >= colblocks;   // uniform over the workgroup
+    const i64 slice = (rows ? (i64)blockIdx.x - colblocks : (i64)blockIdx.x) * kBlock + threadIdx.x;
+    const double q0 = rows ? rp[slice] : cp[slice], q1 = rows ? rp[srows + slice] : cp[scols + slice];
+    const double r0 = block_reduce<false>(q0, lds);
+    const double r1 = rows ? block_nan_max(q1, lds) : block_reduce<false>(q1, lds);
+    if (threadIdx.x == 0) {
+        bp[2 * (i64)blockIdx.x] = r0;
+        bp[2 * (i64)blockIdx.x + 1] = r1;
+    }
+}
+
+// k_cp_gap_final, one workgroup: lane l adds the sums of the workgroups l and l + 256 of a pass (at most 512) from 0.0, then the same tree.
+// out[0] = c.x, out[1] = the bound's column terms, out[2] = y.b over this rank's rows, out[3] = their violation
+__global__ __launch_bounds__(kBlock) void k_cp_gap_final(i64 colblocks, i64 rowblocks, const double *__restrict__ bp,
+                                                         double *__restrict__ out) {
+    __shared__ double lds[kBlock / kWave];
+    double cx = 0.0, terms = 0.0, yb = 0.0, viol = 0.0;
+    for (i64 i = threadIdx.x; i < colblocks; i += kBlock) {
+        cx += bp[2 * i];
+        terms += bp[2 * i + 1];
+    }
+    for (i64 i = threadIdx.x; i < rowblocks; i += kBlock) {
+        yb += bp[2 * (colblocks + i)];
+        viol = nan_max(viol, bp[2 * (colblocks + i) + 1]);
+    }
+    const double r0 = block_reduce<false>(cx, lds), r1 = block_reduce<false>(terms, lds), r2 = block_reduce<false>(yb, lds);
+    const double r3 = block_nan_max(viol, lds);
+    if (threadIdx.x == 0) {
+        out[0] = r0;
+        out[1] = r1;
+        out[2] = r2;
+        out[3] = r3;
+    }
+}
+
 }  // namespace slp
 
 using namespace slp;
@@ -450,6 +605,13 @@ struct slp_cp {
     bool distributed = false;
     bool csr_bound = false;  // an iteration half walks the CSR arrays of `k` (counted in k->csr_bound for borrowed matrices)
     IterGraph graph;
+    // whole iterations over the state's life, and the certificate test (slp_cp_set_stop_gap): off while tol_gap < 0
+    i64 iters = 0;
+    double tol_gap = -1.0, tol_feas = 0.0;
+    i64 check_every = 1;
+    bool stopped = false;
+    double rec[3] = {__builtin_inf(), -__builtin_inf(), __builtin_inf()};  // primal, bound, violation of the last check
+    DevBuf<double> gapparts;  // the slice sums of the two passes, allocated at the first evaluation
     ~slp_cp() {
         delete own[0];
         delete own[1];
@@ -769,6 +931,88 @@ static void cp_dual(slp_cp *s) {
     SLP_HIP(hipGetLastError());
 }
 
+// The certificate of the current (x, y): h[0] = c.x, h[1] = the bound's column terms, h[2] = y.b, h[3] = the violation -- under a
+// communicator the last two reduced over the ranks.  Writes scratch of the two halves only (pre, pre2, ymask, kz) and the
+// report's `out`; x, z, y, d stay.  Every buffer a captured iteration names keeps its address: pre, pre2, ymask and kz are used
+// here exactly where the state's own halves use them, hence allocated by then.  One synchronising read.
+static void cp_gap_evaluate(slp_cp *s, double h[4]) {
+    hipStream_t st = ctx().stream;
+    const CsrDev &a = s->k->a, &at = s->k->at;
+    const i64 sc = s->n ? cp_gap_slices(s->n) : 0, sr = s->m ? cp_gap_slices(s->m) : 0;
+    const i64 blocks = (sc + sr) / kBlock;   // the workgroups of the two passes: their sums behind the slice sums
+    if (s->gapparts.n < (size_t)(2 * (sc + sr + blocks))) s->gapparts.alloc((size_t)(2 * (sc + sr + blocks)));
+    double *colparts = s->gapparts.p, *rowparts = s->gapparts.p + 2 * sc, *blockparts = s->gapparts.p + 2 * (sc + sr);
+    if (s->n) {
+        // K^T y in the form and the order of cp_primal
+        const double *pre = s->pre.p, *pre2 = nullptr;
+        bool walk = false;
+        if (s->distributed) {
+            if (const StripJds *f = fast_format(s->k, true)) {
+                strip_spmv(*f, s->y.p, s->pre.p);
+            } else {
+                require_csr(s->k, "Chambolle-Pock certificate (CSR walk)");
+                const int lanes = s->lanes_cols;
+                const int grid = grid_for(s->n * lanes, kBlock);
+                SLP_DISPATCH_LANES(lanes, hipLaunchKernelGGL((k_cp_colsum_y<L>), dim3(grid), dim3(kBlock), 0, st, s->n, at.ptr.p,
+                                                             at.idx.p, at.val.p, s->y.p, s->pre.p));
+            }
+            SLP_HIP(hipGetLastError());
+            comm_allreduce_dev(s->pre.p, s->n, 0);
+        } else if (s->split) {
+            cp_kt_product(s, 0, s->y.p, s->pre.p);
+            cp_kt_product(s, 1, s->y.p, s->pre2.p);
+            pre2 = s->pre2.p;
+        } else if (const StripJds *f = cp_primal_strips(s)) {
+            strip_spmv(*f, s->y.p, s->pre.p);
+        } else {
+            walk = true;  // the CSR of K^T: the chains of k_cp_primal and, one lane per column, of k_cp_primal_ell
+        }
+        if (walk) {
+            require_csr(s->k, "Chambolle-Pock certificate (CSR walk)");
+            const int lanes = s->lanes_cols;
+            SLP_DISPATCH_LANES(lanes, hipLaunchKernelGGL((k_cp_gap_cols<L, false>), dim3((unsigned)(sc * L / kBlock)), dim3(kBlock), 0, st,
+                                                         s->n, at.ptr.p, at.idx.p, at.val.p, s->y.p, nullptr, nullptr, s->c.p, s->x.p,
+                                                         s->lb.p, s->ub.p, (i32)s->m_eq, s->m_ineq, colparts));
+        } else {
+            hipLaunchKernelGGL((k_cp_gap_cols<1, true>), dim3((unsigned)(sc / kBlock)), dim3(kBlock), 0, st, s->n, at.ptr.p, at.idx.p,
+                               at.val.p, s->y.p, pre, pre2, s->c.p, s->x.p, s->lb.p, s->ub.p, (i32)s->m_eq, s->m_ineq, colparts);
+        }
+        SLP_HIP(hipGetLastError());
+    }
+    if (s->m) {
+        if (const StripJds *f = fast_format(s->k, false)) {
+            if (s->kz.n < (size_t)s->m) s->kz.alloc((size_t)s->m);  // (as cp_dual: set up by cp_setup)
+            strip_spmv(*f, s->x.p, s->kz.p);  // the dual half's scratch, free between whole iterations
+            hipLaunchKernelGGL(k_cp_gap_rows_from, dim3((unsigned)(sr / kBlock)), dim3(kBlock), 0, st, s->m, s->kz.p, s->b.p, s->y.p,
+                               s->m_eq, rowparts);
+        } else {
+            require_csr(s->k, "Chambolle-Pock certificate (CSR walk)");
+            const int lanes = s->lanes_rows;
+            SLP_DISPATCH_LANES(lanes, hipLaunchKernelGGL((k_cp_gap_rows<L>), dim3((unsigned)(sr * L / kBlock)), dim3(kBlock), 0, st, s->m,
+                                                         a.ptr.p, a.idx.p, a.val.p, s->x.p, s->b.p, s->y.p, s->m_eq, rowparts));
+        }
+        SLP_HIP(hipGetLastError());
+    }
+    if (blocks) hipLaunchKernelGGL(k_cp_gap_fold, dim3((unsigned)blocks), dim3(kBlock), 0, st, sc, colparts, sr, rowparts, blockparts);
+    hipLaunchKernelGGL(k_cp_gap_final, dim3(1), dim3(kBlock), 0, st, sc / kBlock, sr / kBlock, blockparts, s->out.p);
+    SLP_HIP(hipGetLastError());
+    s->out.download(h, 4);
+    if (s->distributed) {
+        // c.x and the column terms are replicated; y.b is summed and the violation maxed over the ranks
+        SLP_REQUIRE(slp_comm_allreduce_host(&h[2], 1, 0) == 0, slp_last_error());
+        SLP_REQUIRE(slp_comm_allreduce_host(&h[3], 1, 1) == 0, slp_last_error());
+    }
+}
+
+// after a check iteration of an armed state: the certificate, its record, the decision
+static void cp_gap_check(slp_cp *s) {
+    double h[4];
+    cp_gap_evaluate(s, h);
+    s->stopped = cp_gap_decide(h[0], h[1], h[2], h[3], s->tol_gap, s->tol_feas, &s->rec[1]);
+    s->rec[0] = h[0];
+    s->rec[2] = h[3];
+}
+
 static slp_cp *cp_make(slp_matrix *k, bool owns, i64 m_eq, const double *b, const double *c, const double *lb,
                        const double *ub, const double *x0, double alpha, double theta, int order) {
     auto *s = new slp_cp();
@@ -849,17 +1093,84 @@ int slp_cp_iterate(slp_cp *s, int64_t k) {
     SLP_API_INT({
         SLP_REQUIRE(s && k >= 0, "slp_cp_iterate: bad arguments");
         auto one = [&]() { cp_primal(s, false); cp_dual(s); };
-        // cache-resident problems are launch-latency bound: replay a captured graph of 16 iterations
-        if (!s->distributed && s->k->a.nnz <= 20000000) s->graph.run(k, 16, one);
-        else for (i64 it = 0; it < k; ++it) one();
+        auto run = [&](i64 count) {
+            // cache-resident problems are launch-latency bound: replay a captured graph of 16 iterations
+            if (!s->distributed && s->k->a.nnz <= 20000000) s->graph.run(count, 16, one);
+            else for (i64 it = 0; it < count; ++it) one();
+            s->iters += count;
+        };
+        if (s->tol_gap < 0.0) {
+            run(k);
+        } else {
+            // armed: pieces that end at the check iterations, each run as above; the certificate behind a check iteration.  The graph
+            // is captured at its full 16 iterations first: a short first piece would otherwise fix a shorter one for the state's life.
+            if (!s->distributed && s->k->a.nnz <= 20000000 && k > 0 && !s->stopped) s->graph.capture(16, one);
+            while (k > 0 && !s->stopped) {
+                const i64 piece = std::min<i64>(k, s->check_every - s->iters % s->check_every);
+                run(piece);
+                k -= piece;
+                if (s->iters % s->check_every == 0) cp_gap_check(s);
+            }
+        }
     })
 }
 
 int slp_cp_split_form(const slp_cp *s) { return s ? s->split : -1; }
 
-int slp_cp_primal_step(slp_cp *s) { SLP_API_INT({ SLP_REQUIRE(s, "NULL handle"); cp_primal(s, true); }) }
+int slp_cp_primal_step(slp_cp *s) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "NULL handle");
+        if (!s->stopped) cp_primal(s, true);
+    })
+}
 
-int slp_cp_dual_step(slp_cp *s) { SLP_API_INT({ SLP_REQUIRE(s, "NULL handle"); cp_dual(s); }) }
+int slp_cp_dual_step(slp_cp *s) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "NULL handle");
+        if (!s->stopped) {
+            cp_dual(s);
+            ++s->iters;  // the dual half ends an iteration
+            if (s->tol_gap >= 0.0 && s->iters % s->check_every == 0) cp_gap_check(s);
+        }
+    })
+}
+
+int slp_cp_certificate(slp_cp *s, double out[3]) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && out, "slp_cp_certificate: NULL argument");
+        double h[4];
+        cp_gap_evaluate(s, h);
+        out[0] = h[0];
+        (void)cp_gap_decide(h[0], h[1], h[2], h[3], 0.0, 0.0, &out[1]);
+        out[2] = h[3];
+    })
+}
+
+int slp_cp_set_stop_gap(slp_cp *s, double tol_gap, double tol_feas, int64_t check_every) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_cp_set_stop_gap: NULL handle");
+        SLP_REQUIRE(tol_gap < 0.0 || (std::isfinite(tol_gap) && std::isfinite(tol_feas) && tol_feas >= 0.0 && check_every >= 1),
+                    "slp_cp_set_stop_gap: tol_gap and tol_feas must be finite and >= 0 with check_every >= 1 (tol_gap < 0 turns the "
+                    "test off)");
+        s->tol_gap = tol_gap < 0.0 ? -1.0 : tol_gap;
+        if (tol_gap >= 0.0) {
+            s->tol_feas = tol_feas;
+            s->check_every = check_every;
+        }
+        s->stopped = false;
+    })
+}
+
+int slp_cp_gap_state(slp_cp *s, int64_t *iterations, int32_t *stopped, double *primal, double *bound, double *violation) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_cp_gap_state: NULL handle");
+        if (iterations) *iterations = s->iters;
+        if (stopped) *stopped = s->stopped ? 1 : 0;
+        if (primal) *primal = s->rec[0];
+        if (bound) *bound = s->rec[1];
+        if (violation) *violation = s->rec[2];
+    })
+}
 
 int slp_cp_report(slp_cp *s, double out[5]) {
     SLP_API_INT({

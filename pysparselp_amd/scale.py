@@ -7,6 +7,7 @@ and solved in place.  All rows are inequalities ``A x <= b_upper``.
 import numpy as np
 
 from . import _lib
+from ._cp_gap import CPGapMethods
 from ._lib import ORDER_AUTO
 
 
@@ -35,8 +36,9 @@ def one_sided_rows(m, m_eq, b_lower, b_upper):
     return rows.astype(np.int64), scale, np.ascontiguousarray(b)
 
 
-class DeviceCP:
-    """Chambolle-Pock (reference ChambollePockPPD.py:195-343) on a DeviceMatrix."""
+class DeviceCP(CPGapMethods):
+    """Chambolle-Pock (reference ChambollePockPPD.py:195-343) on a DeviceMatrix; ``certificate``, ``set_stop_gap`` and
+    ``gap_state`` are ``_cp_gap.CPGapMethods``'."""
 
     def __init__(self, a, b_upper, c, lb, ub, alpha=1.0, theta=1.0, order=ORDER_AUTO, m_eq=0, b_lower=None, remove_fixed=False,
                  x0=None):
@@ -125,6 +127,12 @@ class DeviceCP:
             return self.x_reduced()
         out = self.shift.copy()
         out[self.free] = self.x_reduced()
+        return out
+
+    def y(self):
+        """The multipliers of the rows the solver holds (this rank's, after the one-sided stacking): ``[y_eq; y_ineq]``."""
+        out = np.empty(self.a.shape[0])
+        _lib.check(self._l.slp_cp_get_y(self._h, _lib.ptr(out)))
         return out
 
     def objective(self):
