@@ -26,6 +26,8 @@
 #include "slp_hip_ext_tall.h"
 /* the single Chambolle-Pock solver stops on a certified duality gap: likewise */
 #include "slp_hip_ext_cp_gap.h"
+/* the two single ADMM solvers (Gauss-Seidel and matrix-free CG) stop on a certified duality gap: likewise */
+#include "slp_hip_ext_admm_gap.h"
 
 #ifdef __cplusplus
 extern "C" {

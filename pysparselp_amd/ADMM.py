@@ -25,13 +25,15 @@ import numpy as np
 
 from . import _lib
 from . import _many
+from ._admm_gap import ADMMGapMethods, gap_info
 from ._batch import check_rhs, check_rhs_order, concat, first_offsets, shared_or_batched
 from ._lib import ORDER_AUTO
 from .tools import convert_to_standard_form_with_bounds, normal_matrix, precondition_constraints
 
 
-class ADMMState:
-    """Device-resident ADMM state (thin RAII wrapper of ``slp_admm``)."""
+class ADMMState(ADMMGapMethods):
+    """Device-resident ADMM state (thin RAII wrapper of ``slp_admm``).  ``certificate``, ``set_stop_gap`` and ``gap_state`` are
+    ``_admm_gap.ADMMGapMethods``'."""
 
     def __init__(self, a, b, c, lb, ub, x0, m, gamma_eq, gamma_ineq, order=ORDER_AUTO):
         """``m``: the explicit ``M`` (CSR arrays) or ``None`` to have it formed on the device from ``a``."""
@@ -149,12 +151,19 @@ def lp_admm(
     ``setup`` (extension, ``xstep="cg"`` only): where its set-up chain runs,
     ``"auto"`` / ``"host"`` / ``"device"`` -- see ``admm_cg.lp_admm_cg``.
     """
-    if xstep == "cg":
-        from .admm_cg import lp_admm_cg
+    return _admm_run(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
+                     use_preconditioning, nb_iter_plot, order, xstep, setup)[0]
 
-        return lp_admm_cg(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0=x0, gamma_eq=gamma_eq, gamma_ineq=gamma_ineq,
-                          nb_iter=nb_iter, callback_func=callback_func, max_time=max_time,
-                          use_preconditioning=use_preconditioning, nb_iter_plot=nb_iter_plot, order=order, setup=setup)
+
+def _admm_run(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
+              use_preconditioning, nb_iter_plot, order, xstep, setup, gap=None):
+    """``lp_admm`` (``gap`` None) and ``lp_admm_certified`` (``gap`` the checked ``(tol_gap, tol_feas, check_every)``): ``(x, info)``,
+    ``info`` None without a test."""
+    if xstep == "cg":
+        from .admm_cg import _admm_cg_run
+
+        return _admm_cg_run(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
+                            use_preconditioning, nb_iter_plot, order, False, setup, gap)
     if xstep not in ("gauss_seidel", "gauss_seidel_unbounded"):
         raise ValueError(f"unknown xstep {xstep!r}")
     c = _lib.f64(c)
@@ -178,10 +187,15 @@ def lp_admm(
     if xstep == "gauss_seidel_unbounded":  # the reference's use_unbounded_gauss_siedel flags (ADMM.py:164-181)
         state.set_xstep(1)
     try:
+        if gap is not None:
+            state.set_stop_gap(*gap)
         start = time.perf_counter()
         i = 0
         while i <= nb_iter:  # ADMM.py:143: nb_iter + 1 sweeps
             if i % nb_iter_plot == 0:
+                # a stopped state ignores iterate, so i may run ahead of the state's own count until this report finds it stopped
+                if gap is not None and state.gap_state()[1]:
+                    break
                 state.sweep_step()
                 elapsed = time.perf_counter() - start
                 if max_time is not None and elapsed > max_time:
@@ -195,9 +209,32 @@ def lp_admm(
                 k = min(nb_iter_plot - i % nb_iter_plot, nb_iter + 1 - i)
                 state.iterate(k)
                 i += k
-        return state.x(n)
+        return state.x(n), None if gap is None else gap_info(state)
     finally:
         state.close()
+
+
+def lp_admm_certified(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, tol_gap, tol_feas, check_every=10, x0=None, gamma_eq=2,
+                      gamma_ineq=3, nb_iter=100, callback_func=None, max_time=None, use_preconditioning=True, nb_iter_plot=10,
+                      order=ORDER_AUTO, xstep="gauss_seidel", setup="auto"):
+    """``lp_admm`` that stops on a certificate (extension; the reference stops on nothing): at the first iteration ``t`` with
+    ``t % check_every == 0`` at which the violation of ``x_t`` is at most ``tol_feas`` and the gap between ``c.x_t`` and a valid
+    lower bound is at most ``tol_gap * (1 + |primal| + |bound|)`` (``ADMMState.set_stop_gap``), or after the ``nb_iter + 1``
+    iterations of ``lp_admm``.  Every ``xstep`` and ``setup`` of ``lp_admm``, and the row partition of ``xstep="cg"`` under a
+    communicator.
+
+    Returns ``(x, info)``; ``info`` is a dict of ``iterations`` (whole iterations completed), ``stopped``, and the last evaluated
+    certificate ``primal``, ``lower_bound``, ``violation`` (``+inf``, ``-inf``, ``+inf`` before the first check).  The three numbers
+    belong to the standard form the solver holds: ``violation`` is in its row-normalised units, those of the callback's
+    ``max_violated_equality``, not in the caller's.  ``x`` is bit for bit ``lp_admm(..., nb_iter=info["iterations"] - 1)``.  The
+    callback cadence is that of ``lp_admm``; the loop ends, without a report, at the first report that finds the state stopped.
+    ``tol_gap`` and ``tol_feas`` finite floats ``>= 0`` and ``check_every`` an int ``>= 1``: a ``ValueError`` otherwise, before
+    anything is uploaded."""
+    from ._cp_gap import check_gap
+
+    gap = check_gap(tol_gap, tol_feas, check_every)
+    return _admm_run(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
+                     use_preconditioning, nb_iter_plot, order, xstep, setup, gap)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -48,6 +48,18 @@ def _reset_curves(lp):
         setattr(lp, name, [])
 
 
+def _admm_auto_xstep(a_eq, a_ineq):
+    """``xstep="auto"`` of ``solve(method="admm")`` and ``solve_admm_certified``: ``"cg"`` when the standard-form rows promise more
+    than ``ADMM_AUTO_M_ENTRIES`` entries in ``M`` (sum of squared row lengths) or a communicator is active, else ``"gauss_seidel"``."""
+    from .parallel import comm_world
+
+    rows_sq = 0.0
+    for blk, slack in ((a_eq, 0), (a_ineq, 1)):
+        if blk is not None:
+            rows_sq += float(np.sum((np.diff(blk.indptr).astype(np.float64) + slack) ** 2))
+    return "cg" if (rows_sq > ADMM_AUTO_M_ENTRIES or comm_world()[0] > 1) else "gauss_seidel"
+
+
 def _mean_together(distances):
     """Per instance the mean of its distances to the ground truth, one reduction over the whole batch."""
     return np.mean(distances, axis=tuple(range(1, distances.ndim)))
@@ -497,13 +509,7 @@ class SparseLP:
 
         if method == "admm":
             if xstep == "auto":
-                from .parallel import comm_world
-
-                rows_sq = 0.0
-                for blk, slack in ((a_eq, 0), (a_ineq, 1)):
-                    if blk is not None:
-                        rows_sq += float(np.sum((np.diff(blk.indptr).astype(np.float64) + slack) ** 2))
-                xstep = "cg" if (rows_sq > ADMM_AUTO_M_ENTRIES or comm_world()[0] > 1) else "gauss_seidel"
+                xstep = _admm_auto_xstep(a_eq, a_ineq)
             x = lp_admm(self.costsvector, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds,
                         self.upper_bounds, nb_iter=nb_iter, x0=x0, callback_func=record, max_time=max_time,
                         nb_iter_plot=nb_iter_plot, order=order, xstep=xstep, setup=setup)
@@ -638,6 +644,57 @@ class SparseLP:
         x, info = self._solve_cp(a_eq, b_eq, a_ineq, record, start, nb_iter, max_time, nb_iter_plot, order, setup, gap)
         fixed = ~(self.upper_bounds > self.lower_bounds)
         self.stop_info = dict(info, fixed_cost=float(np.dot(self.costsvector[fixed], self.lower_bounds[fixed])))
+        elapsed = time.perf_counter() - start
+        return (x, elapsed) if get_timing else x
+
+    def solve_admm_certified(
+        self,
+        tol_gap,
+        tol_feas,
+        check_every=10,
+        xstep="gauss_seidel",
+        get_timing=True,
+        x0=None,
+        nb_iter=10000,
+        max_time=None,
+        nb_iter_plot=10,
+        ground_truth=None,
+        ground_truth_indices=None,
+        order=ORDER_AUTO,
+        setup="auto",
+    ):
+        """``solve(method="admm")`` with a certificate as the stopping test (``ADMM.lp_admm_certified``): it stops at the first
+        iteration ``t`` with ``t % check_every == 0`` at which the violation of the iterate is at most ``tol_feas`` and the gap
+        between its primal value and a valid lower bound is at most ``tol_gap * (1 + |primal| + |bound|)``, or after the
+        ``nb_iter + 1`` iterations of ``solve``.  Returns ``(x, elapsed)`` or ``x``; ``tol_gap`` and ``tol_feas`` finite floats
+        ``>= 0`` and ``check_every`` an int ``>= 1``, a ``ValueError`` otherwise, before any library is touched.
+
+        ``xstep`` is ``"gauss_seidel"``, ``"cg"`` or ``"auto"`` as in ``solve``, and so are ``setup``, the curves and the row
+        partition of ``"cg"`` under a communicator; the loop ends, without a report, at the first report that finds the solver
+        stopped.  ``x`` is bit for bit ``solve("admm", nb_iter=stop_info["iterations"] - 1, xstep=...)``.
+
+        Sets ``self.stop_info``, with the keys of ``solve_certified``: ``iterations`` (whole iterations completed), ``stopped``,
+        and the last evaluated certificate ``primal``, ``lower_bound``, ``violation``.  These three are the numbers of the
+        standard form the solver holds; its value is the LP's, but ``violation`` is in the solver's row-normalised units, not
+        in those of ``max_constraint_violation``.  ADMM runs no ``remove_fixed_variables``, so ``fixed_cost`` is 0.0: nothing is
+        to be added to ``primal`` or ``lower_bound``."""
+        from ._cp_gap import check_gap
+        from .ADMM import lp_admm_certified
+
+        gap = check_gap(tol_gap, tol_feas, check_every)
+        if xstep not in ("gauss_seidel", "cg", "auto"):
+            raise ValueError(f"unknown xstep {xstep!r}: 'gauss_seidel', 'cg' or 'auto'")
+        a_ineq = self.a_inequalities if (self.a_inequalities is not None and self.a_inequalities.shape[0] > 0) else None
+        a_eq, b_eq = (self.a_equalities, self.b_equalities) if self.a_equalities.shape[0] > 0 else (None, None)
+        start = time.perf_counter()
+        _reset_curves(self)
+        record = self._curve_recorder(ground_truth, ground_truth_indices)
+        if xstep == "auto":
+            xstep = _admm_auto_xstep(a_eq, a_ineq)
+        x, info = lp_admm_certified(self.costsvector, a_eq, b_eq, a_ineq, self.b_lower, self.b_upper, self.lower_bounds,
+                                    self.upper_bounds, *gap, x0=x0, nb_iter=nb_iter, callback_func=record, max_time=max_time,
+                                    nb_iter_plot=nb_iter_plot, order=order, xstep=xstep, setup=setup)
+        self.stop_info = dict(info, fixed_cost=0.0)
         elapsed = time.perf_counter() - start
         return (x, elapsed) if get_timing else x
 

@@ -26,7 +26,10 @@ Gauss-Seidel x-step (``solve_admm_many_until`` / ``lp_admm_many_until`` stop eve
 the step inside the kernel).  ``CPManyState.set_compaction`` / ``ADMMManyState.set_compaction`` make every launch of an armed
 list state run over the LPs not yet stopped, with the same results bit for bit.  ``SparseLP.solve_certified`` /
 ``chambolle_pock_ppd_certified`` stop the single Chambolle-Pock solver, on every format and row-partitioned over ranks, on that
-certified duality gap (``CPState.set_stop_gap`` / ``DeviceCP.set_stop_gap``, ``certificate``, ``gap_state``).  There is no CPU fallback: without the built
+certified duality gap (``CPState.set_stop_gap`` / ``DeviceCP.set_stop_gap``, ``certificate``, ``gap_state``).
+``SparseLP.solve_admm_certified`` / ``lp_admm_certified`` do the same for the two single ADMM solvers, with a multiplier repaired
+into a dual feasible vector (``ADMMState`` / ``ADMMCGState`` / ``ADMMCGLPState`` / ``DeviceADMM`` ``.set_stop_gap``,
+``.certificate``, ``.gap_state``).  There is no CPU fallback: without the built
 library and a HIP device every solver call raises ``SlpError``.
 """
 from ._lib import ORDER_AUTO, ORDER_SEQUENTIAL, ORDER_TREE, SlpError  # noqa: F401
@@ -41,6 +44,7 @@ from .DualGradientAscent import dual_gradient_ascent_batch_rhs  # noqa: F401
 from .SparseLP import solve_admm_many, solve_admm_many_until, solve_dga_many, solve_dga_many_until, solve_many, solve_many_until  # noqa: F401
 from .SparseLP import solve_dga_many_compact, solve_dga_many_cutoff, solve_many_certified  # noqa: F401
 from .ChambollePockPPD import chambolle_pock_ppd_certified  # noqa: F401
+from .ADMM import lp_admm_certified  # noqa: F401
 
 __all__ = ["ORDER_AUTO", "ORDER_SEQUENTIAL", "ORDER_TREE", "SlpError", "CPBatchState", "chambolle_pock_ppd_batch",
            "ADMMBatchState", "lp_admm_batch", "DeviceDGABatch", "dual_gradient_ascent_batch", "CPManyState", "chambolle_pock_ppd_many",
@@ -49,4 +53,4 @@ __all__ = ["ORDER_AUTO", "ORDER_SEQUENTIAL", "ORDER_TREE", "SlpError", "CPBatchS
            "dual_gradient_ascent_many_until", "solve_dga_many_until", "chambolle_pock_ppd_many_certified", "solve_many_certified",
            "chambolle_pock_ppd_batch_certified", "lp_admm_batch_until", "dual_gradient_ascent_batch_until",
            "dual_gradient_ascent_many_cutoff", "solve_dga_many_cutoff", "dual_gradient_ascent_many_compact", "solve_dga_many_compact",
-           "dual_gradient_ascent_batch_rhs", "lp_admm_batch_rhs", "chambolle_pock_ppd_certified"]
+           "dual_gradient_ascent_batch_rhs", "lp_admm_batch_rhs", "chambolle_pock_ppd_certified", "lp_admm_certified"]

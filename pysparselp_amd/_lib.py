@@ -1,6 +1,6 @@
 """ctypes binding of libslp_hip.so (include/slp_hip.h, include/slp_hip_ext.h, include/slp_hip_ext_admm_batch.h,
-include/slp_hip_ext_dga_batch.h, include/slp_hip_ext_dga_many.h, include/slp_hip_ext_batch_rhs.h, include/slp_hip_ext_tall.h and
-include/slp_hip_ext_cp_gap.h).
+include/slp_hip_ext_dga_batch.h, include/slp_hip_ext_dga_many.h, include/slp_hip_ext_batch_rhs.h, include/slp_hip_ext_tall.h,
+include/slp_hip_ext_cp_gap.h and include/slp_hip_ext_admm_gap.h).
 
 The library is the only execution path: if it is missing, cannot be loaded, or
 finds no HIP device, every solver entry point raises -- there is no CPU
@@ -327,6 +327,20 @@ _EXT_CP_GAP_SIGNATURES = {
 
 EXT_CP_GAP_SYMBOLS = tuple(_EXT_CP_GAP_SIGNATURES)
 
+# name -> (restype, argtypes); mirrors include/slp_hip_ext_admm_gap.h (which slp_hip_ext.h includes) one to one
+_EXT_ADMM_GAP_SIGNATURES = {
+    "slp_admm_certificate": (c_int, [c_vp, c_vp]),
+    "slp_admm_cg_certificate": (c_int, [c_vp, c_vp]),
+    "slp_admm_set_stop_gap": (c_int, [c_vp, c_dbl, c_dbl, c_i64]),
+    "slp_admm_cg_set_stop_gap": (c_int, [c_vp, c_dbl, c_dbl, c_i64]),
+    "slp_admm_gap_state": (c_int, [c_vp] * 6),
+    "slp_admm_cg_gap_state": (c_int, [c_vp] * 6),
+    "slp_admm_cg_get_xp": (c_int, [c_vp, c_vp, c_i64]),
+    "slp_admm_cg_get_lambda": (c_int, [c_vp, c_vp]),
+}
+
+EXT_ADMM_GAP_SYMBOLS = tuple(_EXT_ADMM_GAP_SIGNATURES)
+
 # int fn(double *buf, int64_t count, int op, void *user): the host all-reduce of slp_comm_init_host
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, ctypes.POINTER(c_dbl), c_i64, c_int, c_vp)
 
@@ -353,7 +367,7 @@ def load():
                               + list(_EXT_DGA_BATCH_SIGNATURES.items()) + list(_EXT_DGA_MANY_SIGNATURES.items())
                               + list(_EXT_DGA_MANY_LIVE_SIGNATURES.items()) + list(_EXT_MANY_LIVE_SIGNATURES.items())
                               + list(_EXT_BATCH_RHS_SIGNATURES.items()) + list(_EXT_TALL_SIGNATURES.items())
-                              + list(_EXT_CP_GAP_SIGNATURES.items())):
+                              + list(_EXT_CP_GAP_SIGNATURES.items()) + list(_EXT_ADMM_GAP_SIGNATURES.items())):
         fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -13,11 +13,16 @@ import time
 import numpy as np
 
 from . import _lib
+from ._admm_gap import ADMMGapMethods, gap_info
 from ._lib import ORDER_AUTO
 from .tools import convert_to_standard_form_with_bounds, precondition_constraints
 
 
-class _CGBase:
+class _CGBase(ADMMGapMethods):
+    """What the wrappers of ``slp_admm_cg`` share; ``certificate``, ``set_stop_gap`` and ``gap_state`` are
+    ``_admm_gap.ADMMGapMethods``'."""
+    _gap_prefix = "slp_admm_cg"
+
     def close(self):
         if getattr(self, "_h", None):
             self._l.slp_admm_cg_destroy(self._h)
@@ -56,6 +61,19 @@ class _CGBase:
         count = self.N if count is None else int(count)
         out = np.empty(count)
         _lib.check(self._l.slp_admm_cg_get_x(self._h, _lib.ptr(out), count))
+        return out
+
+    def xp(self, count=None):
+        """The first ``count`` entries (all ``N``) of the projected iterate ``xp``."""
+        count = self.N if count is None else int(count)
+        out = np.empty(count)
+        _lib.check(self._l.slp_admm_cg_get_xp(self._h, _lib.ptr(out), count))
+        return out
+
+    def lam(self):
+        """The multipliers of this rank's rows."""
+        out = np.empty(int(self.m))
+        _lib.check(self._l.slp_admm_cg_get_lambda(self._h, _lib.ptr(out)))
         return out
 
 
@@ -140,6 +158,7 @@ class DeviceADMM(_CGBase):
         self.a = a
         self.n = a.shape[1]
         self.N = a.shape[1] + a.shape[0]
+        self.m = a.shape[0]
         self.c = _lib.f64(c)
         b_upper, lb, ub = _lib.f64(b_upper), _lib.f64(lb), _lib.f64(ub)
         b_lower = None if b_lower is None else _lib.f64(b_lower)  # two-sided rows b_lower <= a_i x <= b_upper
@@ -180,6 +199,14 @@ def lp_admm_cg(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0=None, gamma_eq
     ``setup`` (extension): ``"host"`` runs the reference's set-up chain (ADMM.py:73-101) in numpy and uploads the explicit
     standard form; ``"device"`` uploads the two blocks and runs it on the device (``ADMMCGLPState``); ``"auto"`` takes the
     device at ``SparseLP.DEVICE_SETUP_ENTRIES`` stored entries or more.  Both give the same iterates up to fp64 rounding."""
+    return _admm_cg_run(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
+                        use_preconditioning, nb_iter_plot, order, reuse, setup)[0]
+
+
+def _admm_cg_run(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0, gamma_eq, gamma_ineq, nb_iter, callback_func, max_time,
+                 use_preconditioning, nb_iter_plot, order, reuse, setup, gap=None):
+    """``lp_admm_cg`` (``gap`` None) and the ``xstep="cg"`` branch of ``ADMM.lp_admm_certified`` (``gap`` the checked ``(tol_gap,
+    tol_feas, check_every)``): ``(x, info)``, ``info`` None without a test."""
     from . import host_setup
     from .parallel import collective_elapsed, local_rows
 
@@ -209,10 +236,16 @@ def lp_admm_cg(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0=None, gamma_eq
         state = ADMMCGState(a, b, c2, lb2, ub2, x_init, gamma_eq, gamma_ineq, order)
     state.set_reuse(reuse)
     try:
+        if gap is not None:
+            state.set_stop_gap(*gap)
         start = time.perf_counter()
         i = 0
         while i <= nb_iter:
             if i % nb_iter_plot == 0:
+                # a stopped state ignores iterate, so i may run ahead of the state's own count until this report finds it stopped
+                # (under a communicator every rank is stopped by the same reduced numbers)
+                if gap is not None and state.gap_state()[1]:
+                    break
                 state.xstep()
                 elapsed = time.perf_counter() - start
                 # (under a communicator the decision is the same on every rank: the max over the ranks' clocks)
@@ -227,6 +260,6 @@ def lp_admm_cg(c, a_eq, beq, a_ineq, b_lower, b_upper, lb, ub, x0=None, gamma_eq
                 k = min(nb_iter_plot - i % nb_iter_plot, nb_iter + 1 - i)
                 state.iterate(k)
                 i += k
-        return state.x(n)
+        return state.x(n), None if gap is None else gap_info(state)
     finally:
         state.close()

@@ -17,9 +17,12 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "../../include/slp_hip_ext.h"
 #include "slp_common.h"
 #include "slp_kernels.h"
 #include "slp_admm_shared.h"
+#include "slp_admm_gap.h"
+#include "slp_gap_fold.h"
 
 namespace slp {
 
@@ -1601,6 +1604,90 @@ __global__ void k_max0(i64 n, const double *__restrict__ x, double *__restrict__
         xp[j] = (x[j] < 0.0) ? 0.0 : x[j];  // np.maximum(x, 0)  (ADMM.py:98)
 }
 
+// ---------------------------------------------------------------------------
+// Duality-gap certificate (include/slp_hip_ext_admm_gap.h).  The scalar arithmetic is slp_cp_gap.h's and slp_admm_gap.h's, the slice
+// order and the fold slp_gap_fold.h's; the three passes below write slice sums only, into buffers the certificate owns.
+
+// flag[j] = 1 where column j is a slack column: cost 0 and exactly one stored entry (the transposed copy's row length)
+__global__ __launch_bounds__(kBlock) void k_admm_gap_slack_flags(i64 N, const i64 *__restrict__ tptr, const double *__restrict__ c,
+                                                                 unsigned char *__restrict__ flag) {
+    for (i64 j = (i64)blockIdx.x * kBlock + threadIdx.x; j < N; j += (i64)gridDim.x * kBlock)
+        flag[j] = (c[j] == 0.0 && tptr[j + 1] - tptr[j] == 1) ? 1 : 0;
+}
+
+// yhat_i = 0 where a slack column among row i's entries would put -inf into the bound under lam_i, else lam_i; one lane per row
+// (the rows of a matrix whose M is explicit are short), no atomics
+__global__ __launch_bounds__(kBlock) void k_admm_gap_dual(i64 m, const i64 *__restrict__ ptr, const i32 *__restrict__ idx,
+                                                          const double *__restrict__ val, const double *__restrict__ lam,
+                                                          const double *__restrict__ lb, const double *__restrict__ ub,
+                                                          const unsigned char *__restrict__ flag, double *__restrict__ yhat) {
+    for (i64 i = (i64)blockIdx.x * kBlock + threadIdx.x; i < m; i += (i64)gridDim.x * kBlock) {
+        const double l = lam[i];
+        bool repaired = false;
+        for (i64 k = ptr[i]; k < ptr[i + 1]; ++k) {
+            const i32 j = idx[k];
+            if (flag[j]) repaired = repaired || admm_gap_slack_unbounded(val[k], l, lb[j], ub[j]);
+        }
+        yhat[i] = admm_gap_dual(l, repaired);
+    }
+}
+
+// column pass, S = gridDim.x * kBlock / L slices: cx[slice] = sum c_j x_j, terms[slice] = sum of the bound's column terms with
+// d_j = c_j + (A^T yhat)_j (the CSR walk of A^T, L lanes per column), viol[slice] = the bound violations of x folded from 0;
+// zero[slice] = 0.0: the fold takes the violations as a row-kind quantity, whose sum slot must hold nothing
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_admm_gap_cols(i64 N, const i64 *__restrict__ tptr, const i32 *__restrict__ tidx,
+                                                          const double *__restrict__ tval, const double *__restrict__ yhat,
+                                                          const double *__restrict__ c, const double *__restrict__ x,
+                                                          const double *__restrict__ lb, const double *__restrict__ ub,
+                                                          double *__restrict__ cxp, double *__restrict__ termp,
+                                                          double *__restrict__ zerop, double *__restrict__ violp) {
+    const int sub = threadIdx.x & (L - 1);
+    const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / L;
+    const i64 ngroups = (i64)gridDim.x * kBlock / L;
+    double cx = 0.0, terms = 0.0, viol = 0.0;
+    for (i64 j = group; j < N; j += ngroups) {
+        const double d = c[j] + row_dot<L>(tptr, tidx, tval, yhat, j, sub);
+        if (sub == 0) {
+            const double xj = x[j], l = lb[j], u = ub[j];
+            cx += c[j] * xj;
+            terms += cp_gap_col_term(d, l, u);
+            viol = nan_max(nan_max(viol, l - xj), xj - u);
+        }
+    }
+    if (sub == 0) {
+        cxp[group] = cx;
+        termp[group] = terms;
+        zerop[group] = 0.0;
+        violp[group] = viol;
+    }
+}
+
+// row pass, S = gridDim.x * kBlock / L slices: ybp[slice] = sum [yhat_i != 0 ? yhat_i b_i : 0], violp[slice] = |(A x)_i - b_i|
+// folded from 0 (the CSR walk of the multiplier update, L lanes per row)
+template <int L>
+__global__ __launch_bounds__(kBlock) void k_admm_gap_rows(i64 m, const i64 *__restrict__ ptr, const i32 *__restrict__ idx,
+                                                          const double *__restrict__ val, const double *__restrict__ x,
+                                                          const double *__restrict__ b, const double *__restrict__ yhat,
+                                                          double *__restrict__ ybp, double *__restrict__ violp) {
+    const int sub = threadIdx.x & (L - 1);
+    const i64 group = ((i64)blockIdx.x * kBlock + threadIdx.x) / L;
+    const i64 ngroups = (i64)gridDim.x * kBlock / L;
+    double yb = 0.0, viol = 0.0;
+    for (i64 i = group; i < m; i += ngroups) {
+        const double ax = row_dot<L>(ptr, idx, val, x, i, sub);
+        if (sub == 0) {
+            const double bi = b[i];
+            yb += cp_gap_row_term(yhat[i], bi);
+            viol = cp_gap_violation(viol, ax - bi, true);
+        }
+    }
+    if (sub == 0) {
+        ybp[group] = yb;
+        violp[group] = viol;
+    }
+}
+
 }  // namespace slp
 
 using namespace slp;
@@ -1626,6 +1713,17 @@ struct slp_admm {
     // the inequality block's, the stacked system's (empty without use_preconditioning)
     i64 m_eq = 0;
     DevBuf<double> scale_eq, scale_ineq, scale_rows;
+    // whole iterations over the state's life (a sweep half then a multiplier half is one; `mid`: between the two), and the
+    // certificate test (slp_admm_set_stop_gap): off while tol_gap < 0
+    i64 iters = 0;
+    bool mid = false;
+    double tol_gap = -1.0, tol_feas = 0.0;
+    i64 check_every = 1;
+    bool stopped = false;
+    double rec[3] = {__builtin_inf(), -__builtin_inf(), __builtin_inf()};  // primal, bound, violation of the last check
+    // the certificate's own buffers, allocated at its first evaluation: the slack-column flags, yhat, the slice sums, four results
+    DevBuf<unsigned char> gapflag;
+    DevBuf<double> gapdual, gapparts, gapout;
 };
 
 namespace slp {
@@ -1664,6 +1762,59 @@ static void admm_multiplier(slp_admm *s) {
                                                  ctx().stream, s->m, a.ptr.p, a.idx.p, a.val.p, s->x.p, s->b.p, s->gamma_eq,
                                                  s->lam.p));
     SLP_HIP(hipGetLastError());
+}
+
+// The certificate of the current (x, lam), between whole iterations: h[0] = c.x, h[1] = the bound's column terms, h[2] = yhat.b,
+// h[3] = the violation.  Reads the state, writes the four gap* buffers only: nothing an iteration or a captured graph names.
+// One synchronising read.
+static void admm_gap_evaluate(slp_admm *s, double h[4]) {
+    hipStream_t st = ctx().stream;
+    const CsrDev &a = s->a->a, &at = s->a->at;
+    const i64 N = s->N, m = s->m;
+    const i64 sc = N ? cp_gap_slices(N) : 0, sr = m ? cp_gap_slices(m) : 0;
+    // the fold sees two passes: the columns' two sums (sc slices), and a row-kind pass of sr + sc slices -- yhat.b over the rows,
+    // then a run of zeros; behind them the rows' violations, then the columns'
+    const i64 srv = sr + sc, blocks = (sc + srv) / kBlock;
+    if (s->gapflag.n < (size_t)N || !s->gapflag.p) {
+        s->gapflag.alloc((size_t)N);
+        s->gapdual.alloc((size_t)m);
+        s->gapparts.alloc((size_t)(2 * (sc + srv + blocks)));
+        s->gapout.alloc(4);
+        if (N) hipLaunchKernelGGL(k_admm_gap_slack_flags, dim3(grid_for(N, kBlock)), dim3(kBlock), 0, st, N, at.ptr.p, s->c.p, s->gapflag.p);
+        SLP_HIP(hipGetLastError());
+    }
+    double *colparts = s->gapparts.p, *rowparts = s->gapparts.p + 2 * sc, *blockparts = s->gapparts.p + 2 * (sc + srv);
+    if (m) {
+        hipLaunchKernelGGL(k_admm_gap_dual, dim3(grid_for(m, kBlock)), dim3(kBlock), 0, st, m, a.ptr.p, a.idx.p, a.val.p, s->lam.p,
+                           s->lb.p, s->ub.p, s->gapflag.p, s->gapdual.p);
+        SLP_HIP(hipGetLastError());
+    }
+    if (N) {
+        const int lanes = s->lanes_cols;
+        SLP_DISPATCH_LANES(lanes, hipLaunchKernelGGL((k_admm_gap_cols<L>), dim3((unsigned)(sc * L / kBlock)), dim3(kBlock), 0, st, N,
+                                                     at.ptr.p, at.idx.p, at.val.p, s->gapdual.p, s->c.p, s->x.p, s->lb.p, s->ub.p,
+                                                     colparts, colparts + sc, rowparts + sr, rowparts + srv + sr));
+        SLP_HIP(hipGetLastError());
+    }
+    if (m) {
+        const int lanes = s->lanes_rows;
+        SLP_DISPATCH_LANES(lanes, hipLaunchKernelGGL((k_admm_gap_rows<L>), dim3((unsigned)(sr * L / kBlock)), dim3(kBlock), 0, st, m,
+                                                     a.ptr.p, a.idx.p, a.val.p, s->x.p, s->b.p, s->gapdual.p, rowparts, rowparts + srv));
+        SLP_HIP(hipGetLastError());
+    }
+    if (blocks) hipLaunchKernelGGL(k_cp_gap_fold, dim3((unsigned)blocks), dim3(kBlock), 0, st, sc, colparts, srv, rowparts, blockparts);
+    hipLaunchKernelGGL(k_cp_gap_final, dim3(1), dim3(kBlock), 0, st, sc / kBlock, srv / kBlock, blockparts, s->gapout.p);
+    SLP_HIP(hipGetLastError());
+    s->gapout.download(h, 4);
+}
+
+// after a check iteration of an armed state: the certificate, its record, the decision
+static void admm_gap_check(slp_admm *s) {
+    double h[4];
+    admm_gap_evaluate(s, h);
+    s->stopped = cp_gap_decide(h[0], h[1], h[2], h[3], s->tol_gap, s->tol_feas, &s->rec[1]);
+    s->rec[0] = h[0];
+    s->rec[2] = h[3];
 }
 }  // namespace slp
 
@@ -1902,13 +2053,36 @@ int slp_admm_iterate(slp_admm *s, int64_t k) {
     SLP_API_INT({
         SLP_REQUIRE(s && k >= 0, "slp_admm_iterate: bad arguments");
         auto one = [&]() { admm_sweep(s); admm_multiplier(s); };
-        if (k > 0 && !s->xp_is_x && s->xstep == 0) {  // the first iteration reads xp0 instead of x: not part of the replayed graph
-            one();
-            --k;
-        }
         // one launch per dependency level is launch-latency bound: replay the iteration as a captured graph
-        if (s->a->a.nnz <= 20000000) s->graph.run(k, (s->plan.pipelined ? (i64)s->plan.segments.size() : s->plan.nlevels) > 64 || s->plan.one_block ? 1 : 8, one);
-        else for (i64 it = 0; it < k; ++it) one();
+        const bool graphed = s->a->a.nnz <= 20000000, armed = s->tol_gap >= 0.0;
+        const int unroll = (s->plan.pipelined ? (i64)s->plan.segments.size() : s->plan.nlevels) > 64 || s->plan.one_block ? 1 : 8;
+        auto run = [&](i64 count) {
+            s->iters += count;
+            if (count > 0) s->mid = false;  // (a lone sweep half before it is swept again: whole iterations from here)
+            if (count > 0 && !s->xp_is_x && s->xstep == 0) {  // the first iteration reads xp0 instead of x: not part of the replayed graph
+                one();
+                --count;
+            }
+            if (graphed) {
+                // armed: the graph at its full length before a piece runs, or a short first piece would fix a shorter one for the
+                // state's life
+                if (armed && (s->xp_is_x || s->xstep != 0)) s->graph.capture(unroll, one);
+                s->graph.run(count, unroll, one);
+            } else {
+                for (i64 it = 0; it < count; ++it) one();
+            }
+        };
+        if (!armed) {
+            run(k);
+        } else {
+            // pieces that end at the check iterations, each run as an unarmed state runs it; the certificate behind a check iteration
+            while (k > 0 && !s->stopped) {
+                const i64 piece = std::min<i64>(k, s->check_every - s->iters % s->check_every);
+                run(piece);
+                k -= piece;
+                if (s->iters % s->check_every == 0) admm_gap_check(s);
+            }
+        }
     })
 }
 
@@ -1921,9 +2095,66 @@ int slp_admm_set_xstep(slp_admm *s, int mode) {
     })
 }
 
-int slp_admm_sweep_step(slp_admm *s) { SLP_API_INT({ SLP_REQUIRE(s, "NULL handle"); admm_sweep(s); }) }
+int slp_admm_sweep_step(slp_admm *s) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "NULL handle");
+        if (!s->stopped) {
+            admm_sweep(s);
+            s->mid = true;
+        }
+    })
+}
 
-int slp_admm_multiplier_step(slp_admm *s) { SLP_API_INT({ SLP_REQUIRE(s, "NULL handle"); admm_multiplier(s); }) }
+int slp_admm_multiplier_step(slp_admm *s) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "NULL handle");
+        if (!s->stopped) {
+            admm_multiplier(s);
+            s->mid = false;
+            ++s->iters;  // the multiplier half ends an iteration
+            if (s->tol_gap >= 0.0 && s->iters % s->check_every == 0) admm_gap_check(s);
+        }
+    })
+}
+
+int slp_admm_certificate(slp_admm *s, double out[3]) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && out, "slp_admm_certificate: NULL argument");
+        SLP_REQUIRE(!s->mid, "slp_admm_certificate: between the two halves of an iteration");
+        double h[4];
+        admm_gap_evaluate(s, h);
+        out[0] = h[0];
+        (void)cp_gap_decide(h[0], h[1], h[2], h[3], 0.0, 0.0, &out[1]);
+        out[2] = h[3];
+    })
+}
+
+int slp_admm_set_stop_gap(slp_admm *s, double tol_gap, double tol_feas, int64_t check_every) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_admm_set_stop_gap: NULL handle");
+        SLP_REQUIRE(tol_gap < 0.0 || (std::isfinite(tol_gap) && std::isfinite(tol_feas) && tol_feas >= 0.0 && check_every >= 1),
+                    "slp_admm_set_stop_gap: tol_gap and tol_feas must be finite and >= 0 with check_every >= 1 (tol_gap < 0 turns the "
+                    "test off)");
+        SLP_REQUIRE(!s->mid, "slp_admm_set_stop_gap: between the two halves of an iteration");
+        s->tol_gap = tol_gap < 0.0 ? -1.0 : tol_gap;
+        if (tol_gap >= 0.0) {
+            s->tol_feas = tol_feas;
+            s->check_every = check_every;
+        }
+        s->stopped = false;
+    })
+}
+
+int slp_admm_gap_state(slp_admm *s, int64_t *iterations, int32_t *stopped, double *primal, double *bound, double *violation) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_admm_gap_state: NULL handle");
+        if (iterations) *iterations = s->iters;
+        if (stopped) *stopped = s->stopped ? 1 : 0;
+        if (primal) *primal = s->rec[0];
+        if (bound) *bound = s->rec[1];
+        if (violation) *violation = s->rec[2];
+    })
+}
 
 int slp_admm_report(slp_admm *s, double out[3]) {
     SLP_API_INT({

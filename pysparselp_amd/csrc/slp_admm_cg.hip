@@ -18,8 +18,11 @@
 // sums; each dot product one scalar all-reduce of its slack part.
 #include <cmath>
 
+#include "../../include/slp_hip_ext.h"
 #include "slp_common.h"
 #include "slp_kernels.h"
+#include "slp_admm_gap.h"
+#include "slp_gap_fold.h"
 
 namespace slp {
 bool comm_active();
@@ -536,6 +539,93 @@ __global__ void k_fill(i64 n, double *__restrict__ p, double v) {
     for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (i64)gridDim.x * blockDim.x) p[j] = v;
 }
 
+// ---------------------------------------------------------------------------
+// Duality-gap certificate (include/slp_hip_ext_admm_gap.h).  Scalar arithmetic: slp_cp_gap.h and slp_admm_gap.h; slice order and
+// fold: slp_gap_fold.h.  A^T yhat and A x come from cg_cols / cg_rows, on whatever copy of the matrix the solver runs on; the
+// passes below are elementwise over vectors and write slice sums only, into buffers the certificate owns.
+
+// explicit form: flag[j] = 1 where column j is a slack column (cost 0, one stored entry).  The entry counts are the transposed
+// copy's row lengths, as doubles: where the rows are partitioned over ranks they are summed once before the flags are taken.
+__global__ __launch_bounds__(kBlock) void k_cg_gap_col_counts(i64 N, const i64 *__restrict__ tptr, double *__restrict__ cnt) {
+    for (i64 j = (i64)blockIdx.x * kBlock + threadIdx.x; j < N; j += (i64)gridDim.x * kBlock) cnt[j] = (double)(tptr[j + 1] - tptr[j]);
+}
+
+__global__ __launch_bounds__(kBlock) void k_cg_gap_slack_flags(i64 N, const double *__restrict__ cnt, const double *__restrict__ c,
+                                                               unsigned char *__restrict__ flag) {
+    for (i64 j = (i64)blockIdx.x * kBlock + threadIdx.x; j < N; j += (i64)gridDim.x * kBlock)
+        flag[j] = (c[j] == 0.0 && cnt[j] == 1.0) ? 1 : 0;
+}
+
+// yhat_i = 0 where a slack column of row i would put -inf into the bound under lam_i, else lam_i.  Implicit slack (sc != NULL):
+// row i's slack is column n_o + i with the entry sc_i.  Explicit form: the slack columns among row i's stored entries, by flag.
+__global__ __launch_bounds__(kBlock) void k_cg_gap_dual(i64 m, i64 n_o, const double *__restrict__ sc, const i64 *__restrict__ ptr,
+                                                        const i32 *__restrict__ idx, const double *__restrict__ val,
+                                                        const unsigned char *__restrict__ flag, const double *__restrict__ lam,
+                                                        const double *__restrict__ lb, const double *__restrict__ ub,
+                                                        double *__restrict__ yhat) {
+    for (i64 i = (i64)blockIdx.x * kBlock + threadIdx.x; i < m; i += (i64)gridDim.x * kBlock) {
+        const double l = lam[i];
+        bool repaired = false;
+        if (sc) {
+            repaired = admm_gap_slack_unbounded(sc[i], l, lb[n_o + i], ub[n_o + i]);
+        } else {
+            for (i64 k = ptr[i]; k < ptr[i + 1]; ++k) {
+                const i32 j = idx[k];
+                if (flag[j]) repaired = repaired || admm_gap_slack_unbounded(val[k], l, lb[j], ub[j]);
+            }
+        }
+        yhat[i] = admm_gap_dual(l, repaired);
+    }
+}
+
+// column pass over the n_o original columns (explicit form: all N), S = gridDim.x * kBlock slices, S a function of n_o alone --
+// under a communicator these columns are replicated and every rank adds them in the same order: d_j = c_j + u_j, u = A^T yhat.
+// cx[slice] = sum c_j x_j, terms[slice] = sum of the column terms, viol[slice] = the bound violations of x folded from 0;
+// zero[slice] = 0.0: the fold takes the violations as a row-kind quantity, whose sum slot must hold nothing.
+__global__ __launch_bounds__(kBlock) void k_cg_gap_cols(i64 n_o, const double *__restrict__ u, const double *__restrict__ c,
+                                                        const double *__restrict__ x, const double *__restrict__ lb,
+                                                        const double *__restrict__ ub, double *__restrict__ cxp,
+                                                        double *__restrict__ termp, double *__restrict__ zerop,
+                                                        double *__restrict__ violp) {
+    const i64 slice = (i64)blockIdx.x * kBlock + threadIdx.x, nslices = (i64)gridDim.x * kBlock;
+    double cx = 0.0, terms = 0.0, viol = 0.0;
+    for (i64 j = slice; j < n_o; j += nslices) {
+        const double xj = x[j], l = lb[j], h = ub[j];
+        cx += c[j] * xj;
+        terms += cp_gap_col_term(c[j] + u[j], l, h);
+        viol = nan_max(nan_max(viol, l - xj), xj - h);
+    }
+    cxp[slice] = cx;
+    termp[slice] = terms;
+    zerop[slice] = 0.0;
+    violp[slice] = viol;
+}
+
+// row pass from w = A x, S = gridDim.x * kBlock slices, with the implicit slack column of every row (sc != NULL), which is
+// rank-local like the row: side[slice] = sum of [yhat_i != 0 ? yhat_i b_i : 0] minus the slack column's term, d = sc_i yhat_i (one
+// product; bound = columns - side, and the slack's cost is 0 by construction, so it has no part in c.x); viol[slice] = |w_i - b_i|
+// and the slack's two bound violations folded from 0
+__global__ __launch_bounds__(kBlock) void k_cg_gap_rows(i64 m, i64 n_o, const double *__restrict__ w, const double *__restrict__ b,
+                                                        const double *__restrict__ yhat, const double *__restrict__ sc,
+                                                        const double *__restrict__ x, const double *__restrict__ lb,
+                                                        const double *__restrict__ ub, double *__restrict__ sidep,
+                                                        double *__restrict__ violp) {
+    const i64 slice = (i64)blockIdx.x * kBlock + threadIdx.x, nslices = (i64)gridDim.x * kBlock;
+    double side = 0.0, viol = 0.0;
+    for (i64 i = slice; i < m; i += nslices) {
+        const double bi = b[i], y = yhat[i];
+        side += cp_gap_row_term(y, bi);
+        viol = cp_gap_violation(viol, w[i] - bi, true);
+        if (sc) {
+            const double xs = x[n_o + i], l = lb[n_o + i], h = ub[n_o + i];
+            side -= cp_gap_col_term(sc[i] * y, l, h);
+            viol = nan_max(nan_max(viol, l - xs), xs - h);
+        }
+    }
+    sidep[slice] = side;
+    violp[slice] = viol;
+}
+
 }  // namespace slp
 
 using namespace slp;
@@ -567,6 +657,19 @@ struct slp_admm_cg {
     DevBuf<double> ex;
     bool started = false;   // at least one full iteration done: the steady-state kernel sequence can be replayed
     IterGraph graph;        // launch-bound problems: iterations replayed as a captured graph
+    // whole iterations over the state's life (an x-step half then a multiplier half is one; `mid`: between the two), and the
+    // certificate test (slp_admm_cg_set_stop_gap): off while tol_gap < 0
+    i64 iters = 0;
+    bool mid = false;
+    double tol_gap = -1.0, tol_feas = 0.0;
+    i64 check_every = 1;
+    bool stopped = false;
+    double rec[3] = {__builtin_inf(), -__builtin_inf(), __builtin_inf()};  // primal, bound, violation of the last check
+    // the certificate's own buffers, allocated at its first evaluation: slack-column flags (explicit form), yhat, A x, A^T yhat,
+    // the row-scaled yhat of a deferred row scaling, the slice sums, four results
+    bool gap_ready = false;
+    DevBuf<unsigned char> gapflag;
+    DevBuf<double> gapdual, gapw, gapu, gaptmp, gapparts, gapout;
 };
 
 namespace slp {
@@ -649,12 +752,15 @@ static void cg_rows2(slp_admm_cg *s, const double *v0, const double *v1, double 
 
 // u_out = (A^T w) restricted to the original variables, summed over the ranks; `tail` more doubles stored right behind the
 // n_o sums (packed exchange: rank-local slack parts of dot products) are summed in the same all-reduce
-static void cg_cols(slp_admm_cg *s, const double *w, double *u_out = nullptr, bool reduce = true, i64 tail = 0) {
+// (scratch: where rs o w goes under a deferred row scaling when w is not one of the solver's own row vectors -- the certificate
+// passes a buffer of its own)
+static void cg_cols(slp_admm_cg *s, const double *w, double *u_out = nullptr, bool reduce = true, i64 tail = 0,
+                    DevBuf<double> *scratch = nullptr) {
     if (s->n_o == 0) return;
     double *u = u_out ? u_out : s->u.p;
     const CsrDev &at = s->a->at;
     if (const StripJds *f = fast_format(s->a, true)) {
-        strip_spmv(*f, cg_scaled_rows(s, w, s->ws0), u);
+        strip_spmv(*f, cg_scaled_rows(s, w, scratch ? *scratch : s->ws0), u);
     } else {
         SLP_REQUIRE(!s->rs.p, "deferred row scaling needs the strip format in both orientations");
         require_csr(s->a, "matrix-free ADMM column product (CSR walk)");
@@ -928,6 +1034,80 @@ static void cg_multipliers(slp_admm_cg *s) {
     }
 }
 
+// The certificate of the current (x, lam), between whole iterations: h[0] = c.x, h[1] = the bound's column terms, h[2] = yhat.b minus
+// the implicit slack columns' terms (rows partitioned: summed over the ranks), h[3] = the violation (maxed over the ranks).
+// Reads the state and writes the gap* buffers only -- none of w, u, wx, wd, v1, the scratch of the deferred row scaling, the
+// reuse bookkeeping or anything a captured graph names; slices that are stale under sharded updates are gathered first, which
+// leaves every owner's values as they are.  Under a communicator every rank calls it: one all-reduce of n_o doubles on the
+// compute stream, two scalar reductions on the host.  One synchronising read.
+static void cg_gap_evaluate(slp_admm_cg *s, double h[4]) {
+    hipStream_t st = ctx().stream;
+    cg_gather_state(s);
+    const i64 N = s->N, m = s->m, n_o = s->n_o;
+    // the slices of the column pass are a function of n_o alone: the same on every rank, whatever its row block
+    const i64 sc = n_o ? cp_gap_slices(n_o) : 0, sr = m ? cp_gap_slices(m) : 0;
+    // the fold sees two passes: the original columns' two sums (sc slices), and a row-kind pass of sr + sc slices -- the rows' side
+    // sums (yhat.b minus the implicit slack columns' terms), then a run of zeros; behind them the rows' violations, then the columns'
+    const i64 srv = sr + sc, blocks = (sc + srv) / kBlock;
+    if (!s->gap_ready) {
+        s->gapdual.alloc((size_t)m);
+        s->gapw.alloc((size_t)m);
+        s->gapu.alloc((size_t)n_o);
+        s->gapparts.alloc((size_t)(2 * (sc + srv + blocks)));
+        s->gapout.alloc(4);
+        if (!s->ns && N) {
+            // explicit slack columns: their flags from the transposed copy's row lengths (a matrix that runs on tall cells has
+            // formed no transposed CSR so far: it is built here, once), summed over the ranks where the rows are partitioned
+            SLP_REQUIRE(!s->rs.p, "ADMM certificate: explicit slack columns under a deferred row scaling");
+            require_csr(s->a, "ADMM certificate (slack columns of the explicit form)");
+            if (!s->a->have_at) build_transpose(s->a);
+            s->gapflag.alloc((size_t)N);
+            hipLaunchKernelGGL(k_cg_gap_col_counts, dim3(grid_for(N, kBlock)), dim3(kBlock), 0, st, N, s->a->at.ptr.p, s->gapu.p);
+            SLP_HIP(hipGetLastError());
+            if (s->distributed) comm_allreduce_dev(s->gapu.p, N, 0);
+            hipLaunchKernelGGL(k_cg_gap_slack_flags, dim3(grid_for(N, kBlock)), dim3(kBlock), 0, st, N, s->gapu.p, s->c.p, s->gapflag.p);
+            SLP_HIP(hipGetLastError());
+        }
+        s->gap_ready = true;
+    }
+    double *colparts = s->gapparts.p, *rowparts = s->gapparts.p + 2 * sc, *blockparts = s->gapparts.p + 2 * (sc + srv);
+    if (m) {
+        const CsrDev &a = s->a->a;
+        hipLaunchKernelGGL(k_cg_gap_dual, dim3(grid_for(m, kBlock)), dim3(kBlock), 0, st, m, n_o, s->ns ? s->sc.p : (const double *)nullptr,
+                           a.ptr.p, a.idx.p, a.val.p, s->gapflag.p, s->lam.p, s->lb.p, s->ub.p, s->gapdual.p);
+        SLP_HIP(hipGetLastError());
+    }
+    cg_cols(s, s->gapdual.p, s->gapu.p, true, 0, &s->gaptmp);   // A^T yhat over the original variables, summed over the ranks
+    if (n_o) {
+        hipLaunchKernelGGL(k_cg_gap_cols, dim3((unsigned)(sc / kBlock)), dim3(kBlock), 0, st, n_o, s->gapu.p, s->c.p, s->x.p, s->lb.p,
+                           s->ub.p, colparts, colparts + sc, rowparts + sr, rowparts + srv + sr);
+        SLP_HIP(hipGetLastError());
+    }
+    if (m) {
+        cg_rows(s, s->x.p, s->gapw.p);
+        hipLaunchKernelGGL(k_cg_gap_rows, dim3((unsigned)(sr / kBlock)), dim3(kBlock), 0, st, m, n_o, s->gapw.p, s->b.p, s->gapdual.p,
+                           s->ns ? s->sc.p : (const double *)nullptr, s->x.p, s->lb.p, s->ub.p, rowparts, rowparts + srv);
+        SLP_HIP(hipGetLastError());
+    }
+    if (blocks) hipLaunchKernelGGL(k_cp_gap_fold, dim3((unsigned)blocks), dim3(kBlock), 0, st, sc, colparts, srv, rowparts, blockparts);
+    hipLaunchKernelGGL(k_cp_gap_final, dim3(1), dim3(kBlock), 0, st, sc / kBlock, srv / kBlock, blockparts, s->gapout.p);
+    SLP_HIP(hipGetLastError());
+    s->gapout.download(h, 4);
+    if (s->distributed) {
+        SLP_REQUIRE(slp_comm_allreduce_host(&h[2], 1, 0) == 0, slp_last_error());
+        SLP_REQUIRE(slp_comm_allreduce_host(&h[3], 1, 1) == 0, slp_last_error());
+    }
+}
+
+// after a check iteration of an armed state: the certificate, its record, the decision
+static void cg_gap_check(slp_admm_cg *s) {
+    double h[4];
+    cg_gap_evaluate(s, h);
+    s->stopped = cp_gap_decide(h[0], h[1], h[2], h[3], s->tol_gap, s->tol_feas, &s->rec[1]);
+    s->rec[0] = h[0];
+    s->rec[2] = h[3];
+}
+
 static void cg_alloc_state(slp_admm_cg *s) {
     const size_t N = (size_t)s->N, m = (size_t)s->m;
     s->lam.alloc(m); s->lam.zero();
@@ -1197,13 +1377,36 @@ int slp_admm_cg_iterate(slp_admm_cg *s, int64_t k) {
     SLP_API_INT({
         SLP_REQUIRE(s && k >= 0, "slp_admm_cg_iterate: bad arguments");
         auto one = [&]() { cg_xstep(s); cg_multipliers(s); s->started = true; };
-        if (k > 0 && !s->started) {  // the first iteration builds the derived formats and the shared products
-            one();
-            --k;
-        }
+        const bool armed = s->tol_gap >= 0.0;
         // ~30 small kernels per iteration: replay them as a graph when the matrix is cache-sized (no collectives inside)
-        if (!s->distributed && s->a->a.nnz <= 20000000 && s->reuse < 3) s->graph.run(k, 4, one);  // (level 3 alternates two sequences)
-        else for (i64 it = 0; it < k; ++it) one();
+        const bool graphed = !s->distributed && s->a->a.nnz <= 20000000 && s->reuse < 3;  // (level 3 alternates two sequences)
+        auto run = [&](i64 count) {
+            s->iters += count;
+            if (count > 0) s->mid = false;  // (a lone x-step half before it: whole iterations from here)
+            if (count > 0 && !s->started) {  // the first iteration builds the derived formats and the shared products
+                one();
+                --count;
+            }
+            if (graphed) {
+                // armed: the graph at its full length before a piece runs, or a short first piece would fix a shorter one for the
+                // state's life
+                if (armed && s->started) s->graph.capture(4, one);
+                s->graph.run(count, 4, one);
+            } else {
+                for (i64 it = 0; it < count; ++it) one();
+            }
+        };
+        if (!armed) {
+            run(k);
+        } else {
+            // pieces that end at the check iterations, each run as an unarmed state runs it; the certificate behind a check iteration
+            while (k > 0 && !s->stopped) {
+                const i64 piece = std::min<i64>(k, s->check_every - s->iters % s->check_every);
+                run(piece);
+                k -= piece;
+                if (s->iters % s->check_every == 0) cg_gap_check(s);
+            }
+        }
     })
 }
 
@@ -1224,13 +1427,76 @@ int slp_admm_cg_set_reuse(slp_admm_cg *s, int reuse) {
 int slp_admm_cg_xstep(slp_admm_cg *s) {
     SLP_API_INT({
         SLP_REQUIRE(s, "NULL handle");
-        cg_xstep(s);
-        if (s->sharded && s->shard_dirty) comm_all_gather_dev(s->x.p, s->scnt);  // the caller may read x between the halves (report, callback)
+        if (!s->stopped) {
+            cg_xstep(s);
+            if (s->sharded && s->shard_dirty) comm_all_gather_dev(s->x.p, s->scnt);  // the caller may read x between the halves (report, callback)
+            s->mid = true;
+        }
     })
 }
 
 int slp_admm_cg_multiplier_step(slp_admm_cg *s) {
-    SLP_API_INT({ SLP_REQUIRE(s, "NULL handle"); cg_multipliers(s); s->started = true; })
+    SLP_API_INT({
+        SLP_REQUIRE(s, "NULL handle");
+        if (!s->stopped) {
+            cg_multipliers(s);
+            s->started = true;
+            s->mid = false;
+            ++s->iters;  // the multiplier half ends an iteration
+            if (s->tol_gap >= 0.0 && s->iters % s->check_every == 0) cg_gap_check(s);
+        }
+    })
+}
+
+int slp_admm_cg_certificate(slp_admm_cg *s, double out[3]) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && out, "slp_admm_cg_certificate: NULL argument");
+        SLP_REQUIRE(!s->mid, "slp_admm_cg_certificate: between the two halves of an iteration");
+        double h[4];
+        cg_gap_evaluate(s, h);
+        out[0] = h[0];
+        (void)cp_gap_decide(h[0], h[1], h[2], h[3], 0.0, 0.0, &out[1]);
+        out[2] = h[3];
+    })
+}
+
+int slp_admm_cg_set_stop_gap(slp_admm_cg *s, double tol_gap, double tol_feas, int64_t check_every) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_admm_cg_set_stop_gap: NULL handle");
+        SLP_REQUIRE(tol_gap < 0.0 || (std::isfinite(tol_gap) && std::isfinite(tol_feas) && tol_feas >= 0.0 && check_every >= 1),
+                    "slp_admm_cg_set_stop_gap: tol_gap and tol_feas must be finite and >= 0 with check_every >= 1 (tol_gap < 0 turns "
+                    "the test off)");
+        SLP_REQUIRE(!s->mid, "slp_admm_cg_set_stop_gap: between the two halves of an iteration");
+        s->tol_gap = tol_gap < 0.0 ? -1.0 : tol_gap;
+        if (tol_gap >= 0.0) {
+            s->tol_feas = tol_feas;
+            s->check_every = check_every;
+        }
+        s->stopped = false;
+    })
+}
+
+int slp_admm_cg_gap_state(slp_admm_cg *s, int64_t *iterations, int32_t *stopped, double *primal, double *bound, double *violation) {
+    SLP_API_INT({
+        SLP_REQUIRE(s, "slp_admm_cg_gap_state: NULL handle");
+        if (iterations) *iterations = s->iters;
+        if (stopped) *stopped = s->stopped ? 1 : 0;
+        if (primal) *primal = s->rec[0];
+        if (bound) *bound = s->rec[1];
+        if (violation) *violation = s->rec[2];
+    })
+}
+
+int slp_admm_cg_get_xp(slp_admm_cg *s, double *xp, int64_t count) {
+    SLP_API_INT({
+        SLP_REQUIRE(s && xp && count >= 0 && count <= s->N, "slp_admm_cg_get_xp: bad arguments");
+        cg_gather_state(s);
+        s->xp.download(xp, (size_t)count);
+    })
+}
+
+int slp_admm_cg_get_lambda(slp_admm_cg *s, double *lam) {
+    SLP_API_INT({ SLP_REQUIRE(s && lam, "slp_admm_cg_get_lambda: NULL argument"); s->lam.download(lam, (size_t)s->m); })
 }
 
 int slp_admm_cg_report(slp_admm_cg *s, double out[3]) {
